@@ -9,7 +9,14 @@ including the per-target setup (packing, cell-list build).  Inputs are resident 
 region.  N > 1: one process per GPU, independent pairs (weak scaling), the 96-byte (R,t) records
 all-gathered over RCCL inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value` in iterations/s, `ms_per_step`).
+`--dump-outputs DIR` writes what the last timed step returned (the registration record: T, fitness, last_mse, iterations,
+converged, state, pair_id) as DIR/<name>.npy (float32 / float64; rank r > 0 of an N-rank run adds `_rank<r>`); the inputs
+are seeded, so two builds compare output for output.  `--full` adds everything else below: HIP-event sampling of the
+kernels in the timed region with the `roofline` / `setup` figures, the brute-force measurement, the `secondary` legs and
+the CPU baseline.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself: N child processes (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* set), spawned BEFORE this process imports torch or touches a GPU; rank 0's JSON
@@ -19,8 +26,8 @@ already and each process is one of them; a --gpus that disagrees with WORLD_SIZE
 Two NN engines produce bit-identical correspondences (tests/test_gpu_grid.py):
   * default (--mode auto/grid): exact uniform cell list + brute-force fallback  -> `value`, `roofline`
   * --mode brute: the north star's LDS-tiled source x target sweep              -> `brute_force` object
-    (always measured too, on a few steps, because it is the kernel graded against the FP32 VALU roofline)
-`secondary` (N = 1): GPU-only legs of the other BASELINE configs -- C3 (1024 x 10k x 10k batch), C4 (1M x 1M: pre-shape,
+    (with --full measured too, on a few steps, because it is the kernel graded against the FP32 VALU roofline)
+`secondary` (--full, N = 1): GPU-only legs of the other BASELINE configs -- C3 (1024 x 10k x 10k batch), C4 (1M x 1M: pre-shape,
 one NN pass, 10 iterations), the pre-shape kernels streaming 64M points -- each with its kernel's launch time -- and
 `register`: the reference's one live entry point (KSSICP_Registration on <= 2000-point samples) with the oracle's one-core
 time beside it.  N > 1: `secondary.c5` -- every rank registers its 1024-pair shard in one batch call, ONE all-gather of the
@@ -54,6 +61,11 @@ def parse_args(argv=None):
     ap.add_argument("--spt", type=int, default=0, help="brute force: sources per thread (0 = auto)")
     ap.add_argument("--splits", type=int, default=0, help="brute force: target splits (0 = auto)")
     ap.add_argument("--mode", default="auto", choices=["auto", "brute", "grid"], help="NN engine of the timed path")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel sampling + roofline, brute force, secondary legs, "
+                         "CPU baseline (the options below that name them apply to --full runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's registration record as DIR/<name>.npy")
     ap.add_argument("--brute-steps", type=int, default=3, help="steps of the secondary brute-force measurement (0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the C3 / C4 / streaming / register / C5 legs")
@@ -71,7 +83,22 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run-dist", action="store_true",
                     help="CPU rehearsal of the N-rank protocol (launcher, gloo process group, barriers, max-over-ranks timing, "
                          "record gather, one JSON line): the step is a stand-in, nothing is measured")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+def dump_outputs(out_dir, res, rank):
+    """The registration record a caller of kss_icp_dev receives, one .npy per field (T float32, the rest float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    import numpy as np
+    sfx = "_rank%d" % rank if rank > 0 else ""
+    arrays = {"T": np.array(res.T, dtype=np.float32).reshape(4, 4)}
+    for k in ("fitness", "last_mse", "iterations", "converged", "state", "pair_id"):
+        arrays[k] = np.array(getattr(res, k), dtype=np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + sfx + ".npy"), v)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -203,9 +230,11 @@ def dry_run(a, world, rank):
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last, rank)
     # the C5 leg's protocol with stand-in records: every rank's shard of a.c5_pairs records, ONE gather, ids in global order
     c5 = None
-    if world > 1 and "c5" in a.legs.split(","):
+    if a.full and world > 1 and "c5" in a.legs.split(","):
         shard = (pkg.IcpResult * a.c5_pairs)()
         for i in range(a.c5_pairs):
             shard[i].fitness = float(rank * a.c5_pairs + i)
@@ -560,20 +589,25 @@ def main():
     for _ in range(a.warmup):
         step()
     finish()
-    ctx.profile_enable(a.prof_stride)   # HIP events around every n-th launch of the timed region
-    ctx.profile_reset()
+    if a.full:
+        ctx.profile_enable(a.prof_stride)   # HIP events around every n-th launch of the timed region
+        ctx.profile_reset()
     dt, last = run_steps(step, a.steps, dist, world, torch.cuda.synchronize, finish)
-    prof = {k: ctx.profile_get(getattr(pkg, k)) for k in ("K_NN_SWEEP", "K_CORR_REDUCE", "K_GRID_NN", "K_GRID_BUILD", "K_GRID_CHAIN", "K_GRID_CHAIN_PASS")}
     gstats = ctx.grid_stats()
-    ctx.profile_enable(False)
+    if a.full:
+        prof = {k: ctx.profile_get(getattr(pkg, k)) for k in ("K_NN_SWEEP", "K_CORR_REDUCE", "K_GRID_NN", "K_GRID_BUILD", "K_GRID_CHAIN", "K_GRID_CHAIN_PASS")}
+        ctx.profile_enable(False)
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    used_grid = prof["K_GRID_NN"][1] > 0
-    ev_over_s = ctx.profile_event_overhead() * 1e-3 if rank == 0 else 0.0   # event pair around an empty launch
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last, rank)
+    # (a plain run reads the engine from the cell-list setup the steps recorded; --full from the sampled launches)
+    used_grid = prof["K_GRID_NN"][1] > 0 if a.full else gstats["n_src"] > 0
+    ev_over_s = ctx.profile_event_overhead() * 1e-3 if a.full and rank == 0 else 0.0   # event pair around an empty launch
     evals_per_launch = None
-    if used_grid and rank == 0 and not split:   # (split: a step is collective, every rank would have to join)
+    if a.full and used_grid and rank == 0 and not split:   # (split: a step is collective, every rank would have to join)
         # untimed diagnostic step: the kernel counts its distance evaluations (mean over the step's launches)
         import ctypes as C
         lib = pkg.load_library()
@@ -592,7 +626,7 @@ def main():
 
     # ---- secondary: the brute-force sweep (north-star kernel), single-GPU runs only ------------------------
     brute = None
-    if world == 1 and a.brute_steps > 0 and used_grid:
+    if a.full and world == 1 and a.brute_steps > 0 and used_grid:
         bstep, bfinish = make_step("brute")
         bstep()
         bfinish()
@@ -605,7 +639,7 @@ def main():
 
     # ---- C5 (world > 1, or KSS_BENCH_FORCE_DIST=1 with one rank): every rank's 1024-pair shard + ONE gather -- all ranks take part
     c5 = None
-    if (world > 1 or force_dist) and not split and not a.no_secondary and "c5" in a.legs.split(","):
+    if a.full and (world > 1 or force_dist) and not split and not a.no_secondary and "c5" in a.legs.split(","):
         c5 = c5_leg(pkg, ctx, torch, np, dist, world, rank, dev, pairs_per_rank=a.c5_pairs)
 
     if rank == 0:
@@ -639,7 +673,7 @@ def main():
             "correspondences_per_sec": float(a.n) * passes * a.steps * (1 if split else world) / dt,
             "result": {"iterations": int(last.iterations), "fitness": float(last.fitness)},
         }
-        if used_grid:
+        if a.full and used_grid:
             gms, gn = prof["K_GRID_NN"]
             raw_s = gms / max(1, gn) * 1e-3
             # chained launches (one kernel runs the remaining iterations of a registration, waiting at an in-kernel gate for
@@ -692,7 +726,7 @@ def main():
                 "grid": {k: gstats[k] for k in ("h", "gx", "gy", "gz", "occupied_cells")}}
             out["setup"] = {"cell_list_build_avg_ms": prof["K_GRID_BUILD"][0] / max(1, prof["K_GRID_BUILD"][1]),
                             "builds": prof["K_GRID_BUILD"][1], "fallback_sweep_launches": prof["K_NN_SWEEP"][1]}
-        else:
+        elif a.full:
             nms, nn_ = prof["K_NN_SWEEP"]
             out["roofline"] = valu_roofline(nms / max(1, nn_) * 1e-3, nn_)
         if brute is not None:
@@ -702,7 +736,7 @@ def main():
                                   "point_pairs_evaluated_per_sec": float(a.n) * a.n * passes * a.brute_steps / bdt,
                                   "roofline": valu_roofline(bms / max(1, bn) * 1e-3, bn),
                                   "max_abs_T_diff_vs_default": float(np.abs(np.array(blast.T) - np.array(last.T)).max())}
-        if world == 1 and not a.no_secondary:
+        if a.full and world == 1 and not a.no_secondary:
             del d_src, d_tgt
             legs = set(a.legs.split(","))
             out["secondary"] = secondary_legs(pkg, ctx, torch, np, legs)
@@ -710,7 +744,7 @@ def main():
                 out["secondary"]["register"] = register_leg(pkg, ctx, np, cpu=not a.no_cpu_baseline)
         if c5 is not None:
             out.setdefault("secondary", {})["c5"] = c5
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cb = cpu_baseline(a.n, a.iters, src, tgt)
             Tg = np.array(last.T, dtype=np.float64)
             out["parity_vs_cpu_baseline_max_abs_T"] = float(np.abs(Tg - np.array(cb.pop("T"))).max())

@@ -7,6 +7,10 @@ data/registration_scale/*.{gird,wlop} (13 pairs, source also scaled and translat
 not recorded by the reference).  Format of the inputs: first line N, then N lines "x y z" (Main_KSS_List.cpp:65-94).
 <name>.gird = source (rotated grid resampling), <name>.wlop = target (WLOP resampling), transferPC.hpp:140-160.
 Run in the build container (the reference tree does not travel):  python tests/golden/make_ref_fixtures.py
+
+Each fixture is written as parts, <sub>_all.part<k>.npz, so that no file exceeds 1 MiB: an array of more than
+CHUNK_ROWS rows is stored as row blocks "<key>.0", "<key>.1", ..., and the blocks are packed into parts of at most
+PART_BYTES uncompressed bytes.  tests/test_oracle.py:_ref_npz reassembles them.
 """
 import os
 
@@ -14,6 +18,29 @@ import numpy as np
 
 REF = "/root/reference/PS_AIS_Simplification/data"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_data")
+CHUNK_ROWS = 24000
+PART_BYTES = 960000
+
+
+def write_parts(out_dir, sub, names, arrays):
+    """Writes `names` and the dict `arrays` (key -> array, in order) as <sub>_all.part<k>.npz files under 1 MiB each."""
+    blocks = []
+    for key, a in arrays.items():
+        if len(a) <= CHUNK_ROWS:
+            blocks.append((key, a))
+        else:
+            blocks += [("%s.%d" % (key, i), a[lo:lo + CHUNK_ROWS]) for i, lo in enumerate(range(0, len(a), CHUNK_ROWS))]
+    parts, cur, size = [], {"names": np.array(names)}, 0
+    for key, a in blocks:
+        if cur and size + a.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[key] = a
+        size += a.nbytes
+    parts.append(cur)
+    for k, part in enumerate(parts):
+        np.savez_compressed(os.path.join(out_dir, "%s_all.part%d.npz" % (sub, k)), **part)
+    return len(parts)
 
 
 def pack(sub):
@@ -26,7 +53,7 @@ def pack(sub):
             cnt = int(open(os.path.join(d, n + "." + ext)).readline().split()[0])
             assert a.shape == (cnt, 3), (n, ext, a.shape, cnt)
             arrays["%s_%s" % (n, ext)] = a
-    np.savez_compressed(os.path.join(OUT, sub + "_all.npz"), names=np.array(names), **arrays)
+    write_parts(OUT, sub, names, arrays)
     return names
 
 

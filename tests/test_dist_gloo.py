@@ -145,7 +145,7 @@ def test_bench_gpus_n_starts_n_ranks():
     touches torch / HIP) and print ONE JSON line with n_gpus = 2.  --dry-run-dist swaps the registration for a stand-in
     so that the protocol (gloo group, barriers, MAX over ranks, padded record gather) runs on CPU."""
     import json
-    r = _run_bench(["--gpus", "2", "--dry-run-dist", "--steps", "3", "--warmup", "1", "--c5-pairs", "96"])
+    r = _run_bench(["--gpus", "2", "--dry-run-dist", "--full", "--steps", "3", "--warmup", "1", "--c5-pairs", "96"])
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -158,6 +158,27 @@ def test_bench_gpus_n_starts_n_ranks():
     # the time is the slowest rank's: rank 1 sleeps 4 ms per step
     assert d["ms_per_step"] >= 4.0
     assert abs(d["value"] - 3 * 50 * 2 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+
+
+def test_plain_dry_run_dumps_every_ranks_last_record(tmp_path):
+    """Without --full the run stops at the headline (no C5 leg); --dump-outputs writes the last timed step's record of
+    every rank (rank r > 0 with a `_rank<r>` suffix) as float32 / float64 .npy files, the same on every run."""
+    import json
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = _run_bench(["--gpus", "2", "--dry-run-dist", "--steps", "2", "--warmup", "0", "--dump-outputs", str(out)])
+        assert r.returncode == 0, r.stdout + r.stderr
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["secondary"] == {} and d["steps"] == 2 and d["ms_per_step"] > 0
+        dumps.append({f: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[f], b[f]) for f in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    for rank, sfx in ((0, ""), (1, "_rank1")):
+        assert a["T" + sfx + ".npy"].dtype == np.float32
+        assert np.array_equal(a["T" + sfx + ".npy"], np.arange(16 * rank, 16 * rank + 16, dtype=np.float32).reshape(4, 4))
+        assert a["fitness" + sfx + ".npy"] == float(rank) and a["iterations" + sfx + ".npy"] == 50.0
 
 
 def test_bench_rejects_a_rank_count_that_disagrees_with_the_environment():

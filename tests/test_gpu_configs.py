@@ -231,7 +231,7 @@ def test_c5_leg_of_the_bench_on_one_rank_over_rccl():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update({"KSS_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29533"})
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--brute-steps", "0", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--brute-steps", "0", "--no-cpu-baseline",
                         "--legs", "c5", "--c5-pairs", "96"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -239,3 +239,33 @@ def test_c5_leg_of_the_bench_on_one_rank_over_rccl():
     assert c5["n_gpus"] == 1 and c5["pairs_total"] == 96 and c5["result_iterations"] == 20
     assert c5["gathered_records_equal_local"] is True and c5["gathered_pair_ids_in_order"] is True
     assert c5["registrations_per_sec"] > 0 and c5["gather_us_max_over_ranks"] > 0
+
+
+def test_plain_bench_run_dumps_the_record_of_its_last_step(ctx, pkg, tmp_path):
+    """A plain `bench.py` run measures the headline only (no sampling, diagnostics or secondary legs: those are --full) and
+    --dump-outputs writes what its last timed step returned: the same record as one registration of the same seeded C2
+    pair through kss_icp_dev here, bit for bit."""
+    import json, subprocess, sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "KSS_BENCH_FORCE_DIST")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["metric"] == "icp_iterations_per_sec" and d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 3 * 50 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "setup", "brute_force", "secondary", "cpu_baseline"} & set(d)
+    got = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("T", "fitness", "last_mse", "iterations", "converged", "state", "pair_id")}
+    assert got["T"].dtype == np.float32 and got["T"].shape == (4, 4)
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    S = pkg.synth
+    src, tgt = S.make_pair(0, 100000, R=S.rot_axis_angle([0, 0, 1], np.deg2rad(10.0)))
+    d_src, d_tgt = _dev(torch, src), _dev(torch, tgt)
+    p = ctx.icp_params(max_iterations=50, fixed_iterations=1, compute_fitness=1, nn_fma=0, nn_sources_per_thread=0,
+                       nn_target_splits=0, nn_mode=pkg.NN_AUTO)
+    one = ctx.icp_dev(d_src.data_ptr(), len(src), d_tgt.data_ptr(), len(tgt), p)
+    assert np.array_equal(got["T"], one.matrix())
+    assert got["fitness"] == one.fitness and got["last_mse"] == one.last_mse
+    assert (got["iterations"], got["converged"], got["state"]) == (one.iterations, one.converged, one.state) and one.iterations == 50
+    assert d["result"] == {"iterations": 50, "fitness": one.fitness}

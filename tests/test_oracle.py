@@ -4,6 +4,7 @@ copied data files of PS_AIS_Simplification/data/registration*/) and against comm
 Pin status: first-party arithmetic is pinned by the fixtures' known rotations (transfer.txt); the ICP
 restatement of PCL 1.8.1 is "parity unpinned" numerically (PCL is absent from the reference tree and
 this image; the reference holds no numeric golden output for it)."""
+import glob
 import os
 
 import numpy as np
@@ -45,7 +46,23 @@ ICP_TXT = {"Armadillo": True, "Bunny": True, "Cat": True, "Girl": True, "hand": 
 
 
 def _ref_npz(sub):
-    return np.load(os.path.join(GOLDEN, "ref_data", sub + "_all.npz"))
+    """The fixture <sub>_all as one dict: its parts (tests/golden/make_ref_fixtures.py keeps every file under 1 MiB)
+    merged, row blocks "<key>.<i>" joined back into <key>."""
+    parts = glob.glob(os.path.join(GOLDEN, "ref_data", sub + "_all.part*.npz"))
+    assert parts, "missing fixture parts of " + sub
+    out, blocks = {}, {}
+    for p in parts:
+        with np.load(p) as z:
+            for key in z.files:
+                if "." in key:
+                    base, i = key.rsplit(".", 1)
+                    blocks.setdefault(base, {})[int(i)] = z[key]
+                else:
+                    out[key] = z[key]
+    for base, bl in blocks.items():
+        assert sorted(bl) == list(range(len(bl))), (sub, base, sorted(bl))
+        out[base] = np.concatenate([bl[i] for i in range(len(bl))])
+    return out
 
 
 def _down(O, P, m):

@@ -42,7 +42,7 @@ def read_counters(d):
 
 def main():
     src, dst, tag = sys.argv[1], sys.argv[2], sys.argv[3]
-    cmd = sys.argv[4] if len(sys.argv) > 4 else "python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline"
+    cmd = sys.argv[4] if len(sys.argv) > 4 else "python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
     os.makedirs(dst, exist_ok=True)
     lines = ["# rocprofv3 summary %s" % tag, "",
              "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- %s`" % cmd, "",

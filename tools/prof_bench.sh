@@ -9,7 +9,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 P=gpurun_out/prof
 rm -rf $P && mkdir -p $P
-ARGS="bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+ARGS="bench.py --full --steps 10 --warmup 2 --no-cpu-baseline"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $P/stats -- python3 $ARGS > $P/stats_run.txt 2>&1 &&
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $P/pmc_fetch -- python3 $ARGS > $P/fetch_run.txt 2>&1 &&
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $P/pmc_write -- python3 $ARGS > $P/write_run.txt 2>&1 &&
