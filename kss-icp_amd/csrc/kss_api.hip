@@ -621,7 +621,7 @@ int kss_downsample_octree(kss_ctx* c, const double* xyz, int64_t n, int32_t* out
     HIPCHK(c, hipMemcpyAsync(kd.data(), c->stage_d2.p, kd.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double radiusSum = 0;
-    for (int i = 0; i < 1000; ++i) radiusSum = radiusSum + std::sqrt((double)kd[(size_t)i * kn + kn - 1]);
+    for (int i = 0; i < 1000; ++i) radiusSum = radiusSum + (double)sqrtf(kd[(size_t)i * kn + kn - 1]);   // :141 float sqrt, widened
     radiusSum = radiusSum / 1000;
     const float resolution = (float)radiusSum;
     if (resolution_out) *resolution_out = (double)resolution;

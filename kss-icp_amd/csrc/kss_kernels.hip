@@ -1314,7 +1314,7 @@ void launch_fps(hipStream_t st, const double* d_xyz, int n, int m, double* d_min
 // ---------------------------------------------------------------------------------------------
 // rotation search: grid = (source blocks, g^3 candidates).  Each lane rotates its pre-shaped
 // source point in f64 by the candidate's Euler angles, narrows to f32 (:440-442), sweeps the
-// whole target through LDS keeping only the minimum d2, and contributes sqrt((double)d2) (:444).
+// whole target through LDS keeping only the minimum d2, and contributes (double)sqrtf(d2) (:444: float sqrt, widened).
 // ---------------------------------------------------------------------------------------------
 template <int S, int NTH>
 __global__ __launch_bounds__(NTH) void rot_search_kernel(const double* __restrict__ src, int ns,
@@ -1362,7 +1362,7 @@ __global__ __launch_bounds__(NTH) void rot_search_kernel(const double* __restric
     }
     double acc[S];
 #pragma unroll
-    for (int j = 0; j < S; ++j) acc[j] = valid ? sqrt((double)best[j]) : 0.0;   // mean of sqrt(float d2) in double (:444-448)
+    for (int j = 0; j < S; ++j) acc[j] = valid ? (double)sqrtf(best[j]) : 0.0;   // mean of widened sqrtf(float d2) in double (:444-448)
     const double r = block_sum<S>(acc, sh);
     if (tid < S) {
         const int cand = (int)blockIdx.y * S + tid;

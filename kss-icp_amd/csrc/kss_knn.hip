@@ -224,7 +224,8 @@ __global__ __launch_bounds__(256) void normals_kernel(const float4* __restrict__
     const float vx = 0.f - p.x, vy = 0.f - p.y, vz = 0.f - p.z;   // flipNormalTowardsViewpoint, view point (0, 0, 0)
     const float cos_theta = vx * nx + vy * ny + vz * nz;
     if (cos_theta < 0) { nx *= -1; ny *= -1; nz *= -1; }
-    const double dis = sqrt((double)nx * (double)nx + (double)ny * (double)ny + (double)nz * (double)nz);   // normalCompute.hpp:342-348
+    // normalCompute.hpp:342-348: float fields, so f32 products, sums and sqrt; then normal_x / dis_i in double
+    const double dis = (double)sqrtf((nx * nx + ny * ny) + nz * nz);
     normals[3 * (int64_t)i] = (double)nx / dis;
     normals[3 * (int64_t)i + 1] = (double)ny / dis;
     normals[3 * (int64_t)i + 2] = (double)nz / dis;

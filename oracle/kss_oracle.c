@@ -266,14 +266,15 @@ int ko_grid_angles(double step, double *angles, int cap) {
 }
 
 double ko_error_ave(const double *cloud, int64_t n, const float *tf, int64_t nt, const ko_kdtree *tree) {
-    /* :430-450: searchPoint.x = (float)pointS[i][0]; K=2 asked, [0] used; sqrt in double */
+    /* :430-450: searchPoint.x = (float)pointS[i][0]; K=2 asked, [0] used; sqrt of the float d2 is float sqrt
+       (<math.h> + `using namespace std`), widened, summed in double */
     double sum = 0;
     for (int64_t i = 0; i < n; i++) {
         float q[3] = {(float)cloud[3 * i], (float)cloud[3 * i + 1], (float)cloud[3 * i + 2]};
         int32_t id; float d;
         if (tree) kd_nn_one(tree, q, 0, &id, &d);
         else ko_nn_brute(q, 1, tf, nt, 0, &id, &d);
-        double di = sqrt((double)d);
+        double di = (double)sqrtf(d);
         sum = sum + di;
     }
     return sum / (double)n;
@@ -1142,9 +1143,11 @@ void ko_normals_pcl(const double *P, int64_t n, int k, double *normals) {
         float vx = 0.f - p[0], vy = 0.f - p[1], vz = 0.f - p[2];
         float cos_theta = vx * nx + vy * ny + vz * nz;
         if (cos_theta < 0) { nx *= -1; ny *= -1; nz *= -1; }
-        /* normalCompute.hpp:342-348: renormalise in double */
-        double dis = sqrt((double)nx * (double)nx + (double)ny * (double)ny + (double)nz * (double)nz);
-        normals[3 * i] = nx / dis; normals[3 * i + 1] = ny / dis; normals[3 * i + 2] = nz / dis;
+        /* normalCompute.hpp:342-348: the float fields give a float length (f32 products, sums and sqrt); then
+           normal_x / dis_i divides in double */
+        float dis = sqrtf((nx * nx + ny * ny) + nz * nz);
+        normals[3 * i] = (double)nx / (double)dis; normals[3 * i + 1] = (double)ny / (double)dis;
+        normals[3 * i + 2] = (double)nz / (double)dis;
     }
     free(pf); free(idx); free(d2);
 }
@@ -1258,7 +1261,8 @@ int64_t ko_octree_downsample(const double *pts, int64_t n, int32_t *out_idx, int
     float *kd = (float *)malloc((size_t)1000 * kn * sizeof(float));
     ko_knn_brute(pf, 1000, pf, n, kn, ki, kd);
     double radiusSum = 0;
-    for (int i = 0; i < 1000; i++) radiusSum = radiusSum + sqrt((double)kd[(size_t)i * kn + kn - 1]);
+    /* Method_Octree.hpp:141: float sqrt of the float d2, widened */
+    for (int i = 0; i < 1000; i++) radiusSum = radiusSum + (double)sqrtf(kd[(size_t)i * kn + kn - 1]);
     radiusSum = radiusSum / 1000;
     const float resolution = (float)radiusSum;
     free(ki); free(kd);

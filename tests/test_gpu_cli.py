@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import refmath
 from conftest import GOLDEN, ROOT
 
 pytestmark = pytest.mark.gpu
@@ -274,9 +275,10 @@ def test_normal_orientation_matches_oracle(ctx, O, pkg, ref_pairs):
             assert np.mean((flipped[:, None, :] * flipped[idx[:, 1:]]).sum(-1) > 0) < 0.6
 
 
-def test_knn_and_normals_match_oracle(ctx, O, pkg, ref_pairs):
+def test_knn_and_float_renormalised_normals_match_oracle(ctx, O, pkg, ref_pairs):
     """Exact k-NN (ascending (d2, index)) bit for bit; PCL-style normals within float round-off of the oracle's
-    restatement (device atan2f/cosf/sinf differ from glibc's in the last ulps)."""
+    restatement (device atan2f/cosf/sinf differ from glibc's in the last ulps).  Each normal is exactly a float
+    triple divided in double by its float length (normalCompute.hpp:345-347), so |n| - 1 is float round-off."""
     rng = np.random.default_rng(2)
     t = rng.normal(size=(3000, 3)).astype(np.float32)
     t[100] = t[7]; t[2000] = t[7]                      # duplicates: ties keep the lower index first
@@ -297,7 +299,8 @@ def test_knn_and_normals_match_oracle(ctx, O, pkg, ref_pairs):
     for P in (pkg.synth.bumpy(4, 6000), ref_pairs[("registration", "Horse")][0]):
         n = ctx.normals(P, 20)
         r = O.normals_pcl(P, 20)
-        assert np.abs(np.linalg.norm(n, axis=1) - 1).max() < 1e-12
+        assert len(refmath.check_renormalised(n)) == 0
+        assert np.abs(np.linalg.norm(n, axis=1) - 1).max() < 2.0 ** -20
         dev = np.abs(n - r).max(axis=1)
         assert np.mean(dev < 1e-4) > 0.995               # ill-conditioned (near-isotropic) neighbourhoods may differ more
         assert np.median(dev) < 1e-6

@@ -148,7 +148,9 @@ def test_transform_apply_matches_reference_expression(ctx):
 
 # ---- (a4) rotation search ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("step", [6, 8])
-def test_rotation_search_matches_oracle(ctx, pkg, step):
+def test_rotation_search_matches_float_sqrt_golden(ctx, pkg, step):
+    """The G2 volume, angle and angleList (tests/golden/make_golden.py), computed with the reference's f32 sqrt of the
+    NN d2 (initRegistrationKSS.hpp:444; the volume itself is pinned to tests/refmath.py by test_refmath.py)."""
     g = np.load(os.path.join(GOLDEN, "oracle_vectors.npz"))
     err = ctx.rotation_search(g["g1_preshaped"], g["g1_tgt"].astype(np.float64), step)
     ref = g["g2_value_%d" % step]
