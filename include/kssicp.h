@@ -37,7 +37,8 @@ enum {
     KSS_ERR_NOMEM = -3,
     KSS_ERR_NODEVICE = -4, /* no usable GPU */
     KSS_ERR_CAPACITY = -5, /* caller-provided output buffer too small */
-    KSS_ERR_RCCL = -6
+    KSS_ERR_RCCL = -6,
+    KSS_ERR_DEGENERATE = -7 /* kss_rigid_from_p2l_sums: the 6x6 normal equations are singular (planar target ...) */
 };
 
 enum { KSS_F32 = 0, KSS_F64 = 1 };
@@ -206,7 +207,8 @@ typedef struct {
 enum { KSS_NN_AUTO = 0, KSS_NN_BRUTE = 1, KSS_NN_GRID = 2 };
 
 enum { KSS_STATE_NOT_CONVERGED = 0, KSS_STATE_ITERATIONS = 1, KSS_STATE_TRANSFORM = 2,
-       KSS_STATE_ABS_MSE = 3, KSS_STATE_REL_MSE = 4, KSS_STATE_NO_CORRESPONDENCES = 5 };
+       KSS_STATE_ABS_MSE = 3, KSS_STATE_REL_MSE = 4, KSS_STATE_NO_CORRESPONDENCES = 5,
+       KSS_STATE_DEGENERATE = 6 /* point-to-plane only: the pass's normal equations were singular */ };
 
 typedef struct {
     float   T[16];       /* getFinalTransformation(), row-major Matrix4f  (:222) */
@@ -231,6 +233,35 @@ int kss_icp_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off,
 int kss_icp_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off,
                       const float *d_tgt_all, const int64_t *tgt_off, int npairs,
                       const kss_icp_params *p, kss_icp_result *results);
+
+/* ---- point-to-plane ICP for one pair with target normals: pcl::IterativeClosestPointWithNormals /
+ *      TransformationEstimationPointToPlaneLLS (PCL 1.8.1, restated in DESIGN.md 2.9) ----
+ * Per kept correspondence (d2 <= max_d2 and a finite normal n of target q), in float without fma:
+ *   a = nz*sy - ny*sz, b = nx*sz - nz*sx, c = ny*sx - nx*sy, r = ((nx*qx + ny*qy) + nz*qz) - nx*sx - ny*sy - nz*sz,
+ * widened to f64, v = (a, b, c, nx, ny, nz): ATA += v v^T, ATb += v r.  Sums record (f64, fixed summation order that depends
+ * on the source count only):
+ *   [0] kept count, [1..21] upper triangle of ATA row-major, [22..27] ATb, [28] sum d2 kept, [29] sum d2 all,
+ *   [30] sum r^2 kept, [31] 0.
+ * kss_p2l_sums[_dev]: the record for given correspondences (d2 recomputed as in kss_cov); idx entries outside [0, nt)
+ * contribute nothing. */
+#define KSS_P2L_NSUMS 32
+int kss_p2l_sums(kss_ctx *ctx, const float *src, const float *tgt, const float *tgt_normals, const int32_t *idx,
+                 int64_t n, int64_t nt, double max_d2, double sums[KSS_P2L_NSUMS]);
+int kss_p2l_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_tgt, const float *d_tgt_normals, const int32_t *d_idx,
+                     int64_t n, int64_t nt, double max_d2, double sums[KSS_P2L_NSUMS]);
+/* host-side: Cholesky solve of ATA x = ATb, x = (alpha, beta, gamma, tx, ty, tz), and PCL's constructTransformationMatrix
+ * (R = Rz(gamma) Ry(beta) Rx(alpha)) rounded to float; row-major 4x4.  KSS_ERR_DEGENERATE (T = identity) when a pivot is
+ * not finite or <= 1e-12 * max(diag ATA). */
+int kss_rigid_from_p2l_sums(const double sums[KSS_P2L_NSUMS], float T[16]);
+/* The ICP loop of kss_icp with the point-to-plane step: same NN, max_corr_dist, convergence criteria (MSE = point-to-point
+ * d2 over kept correspondences), fitness and source update.  tgt_normals: nt*3 floats, or NULL to compute them with
+ * kss_normals' definition (k = 20, flipped towards the origin) from the target.  A singular system ends the loop with
+ * KSS_STATE_DEGENERATE (not converged, T as accumulated so far).  trace_sums receives trace_cap * KSS_P2L_NSUMS doubles.
+ * p->allreduce must be NULL. */
+int kss_icp_p2l(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt, int64_t nt, const float *tgt_normals,
+                const kss_icp_params *p, kss_icp_result *res);
+int kss_icp_p2l_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
+                    const kss_icp_params *p, kss_icp_result *res);
 
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);

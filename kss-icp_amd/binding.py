@@ -15,6 +15,9 @@ _ROOT = os.path.dirname(_HERE)
 NSUMS = 20
 K_NN_SWEEP, K_CORR_REDUCE, K_PRESHAPE, K_ROT_SEARCH, K_POSE_APPLY, K_GRID_NN, K_GRID_BUILD, K_GRID_CHAIN, K_GRID_CHAIN_PASS, K_RESIDENT, K_RESIDENT_PASS = range(11)
 NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2
+P2L_NSUMS = 32           # KSS_P2L_NSUMS: the point-to-plane sums record
+STATE_DEGENERATE = 6     # KSS_STATE_DEGENERATE: a point-to-plane pass met a singular system
+ERR_DEGENERATE = -7      # KSS_ERR_DEGENERATE
 F32, F64 = 0, 1
 
 # every symbol include/kssicp.h declares (checked by tests/test_abi.py against the header text)
@@ -26,6 +29,7 @@ SYMBOLS = [
     "kss_rotation_search_dev", "kss_grid_angles", "kss_rotation_candidates", "kss_icp_default_params", "kss_icp",
     "kss_icp_dev", "kss_icp_batch", "kss_icp_batch_dev", "kss_transform_apply", "kss_transform_apply_dev",
     "kss_pcr_qm", "kss_register", "kss_register_batch", "kss_gather_results", "kss_rccl_allreduce_sum", "kss_transform_apply_f32", "kss_downsample_fps", "kss_downsample_aivs", "kss_downsample_aivs_pair", "kss_downsample_octree", "kss_knn", "kss_knn_dev", "kss_normals", "kss_normals_orient",
+    "kss_p2l_sums", "kss_p2l_sums_dev", "kss_rigid_from_p2l_sums", "kss_icp_p2l", "kss_icp_p2l_dev",
 ]
 
 
@@ -139,6 +143,11 @@ def load_library():
     for n in ("kss_cov", "kss_cov_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, i64, i64, dbl, vp]
     L.kss_rigid_from_sums.argtypes = [vp, vp]
+    for n in ("kss_p2l_sums", "kss_p2l_sums_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, i64, i64, dbl, vp]
+    L.kss_rigid_from_p2l_sums.argtypes = [vp, vp]
+    for n in ("kss_icp_p2l", "kss_icp_p2l_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     for n in ("kss_rotation_search", "kss_rotation_search_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, dbl, vp, i64, C.POINTER(C.c_int)]
     L.kss_grid_angles.argtypes = [dbl, vp, C.c_int]
@@ -212,6 +221,19 @@ def rigid_from_sums(sums):
     if rc != 0:
         raise KssError(rc, "kss_rigid_from_sums")
     return T.reshape(4, 4)
+
+
+def rigid_from_p2l_sums(sums):
+    """kss_rigid_from_p2l_sums: (T, status) -- status 0, or ERR_DEGENERATE with T the identity."""
+    L = load_library()
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.size != P2L_NSUMS:
+        raise ValueError("need %d sums" % P2L_NSUMS)
+    T = np.empty(16, np.float32)
+    rc = L.kss_rigid_from_p2l_sums(_p(s), _p(T))
+    if rc not in (0, ERR_DEGENERATE):
+        raise KssError(rc, "kss_rigid_from_p2l_sums")
+    return T.reshape(4, 4), rc
 
 
 # ---- context --------------------------------------------------------------------------------------------
@@ -392,6 +414,68 @@ class Context:
             out["fitness_idx"], out["fitness_d2"] = fc
             p.fitness_idx = None; p.fitness_d2 = None
         return out
+
+    # ---- point-to-plane
+    def p2l_sums(self, src, tgt, normals, idx, max_d2=1.0):
+        s, t, nr = _f32(src), _f32(tgt), _f32(normals)
+        i = np.ascontiguousarray(idx, dtype=np.int32)
+        sums = np.empty(P2L_NSUMS, np.float64)
+        self._chk(self.L.kss_p2l_sums(self.h, _p(s), _p(t), _p(nr), _p(i), len(s), len(t), float(max_d2), _p(sums)), "kss_p2l_sums")
+        return sums
+
+    def p2l_sums_dev(self, d_src, d_tgt, d_normals, d_idx, n, nt, max_d2=1.0):
+        sums = np.empty(P2L_NSUMS, np.float64)
+        self._chk(self.L.kss_p2l_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_tgt)), C.c_void_p(int(d_normals)),
+                                          C.c_void_p(int(d_idx)), int(n), int(nt), float(max_d2), _p(sums)), "kss_p2l_sums_dev")
+        return sums
+
+    def icp_p2l(self, src, tgt, normals=None, params=None, trace_cap=0, fitness_corr=False):
+        """Point-to-plane ICP (kss_icp_p2l).  normals: nt x 3 target normals, or None to have the library compute them
+        (kss_normals' definition, k = 20, rounded to float).  Same result dictionary as icp(); trace_sums rows hold P2L_NSUMS."""
+        s, t = _f32(src), _f32(tgt)
+        nr = _f32(normals) if normals is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        p = params if params is not None else self.icp_params()
+        res = IcpResult()
+        tr = None
+        fc = None
+        if fitness_corr:
+            fc = (np.full(len(s), -1, np.int32), np.full(len(s), np.nan, np.float32))
+            p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
+            p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
+        if trace_cap > 0:
+            sums = np.zeros((trace_cap, P2L_NSUMS), np.float64)
+            tk = np.zeros((trace_cap, 16), np.float32)
+            n = C.c_int(0)
+            p.trace_sums = sums.ctypes.data_as(C.POINTER(C.c_double))
+            p.trace_Tk = tk.ctypes.data_as(C.POINTER(C.c_float))
+            p.trace_cap = trace_cap
+            p.trace_n = C.pointer(n)
+            tr = (sums, tk, n)
+        try:
+            self._chk(self.L.kss_icp_p2l(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(res)), "kss_icp_p2l")
+        finally:
+            if tr:
+                p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
+            if fc:
+                p.fitness_idx = None; p.fitness_d2 = None
+        out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
+               "state": res.state, "fitness": res.fitness, "last_mse": res.last_mse}
+        if tr:
+            out["trace_sums"] = tr[0][:tr[2].value].copy()
+            out["trace_Tk"] = tr[1][:tr[2].value].reshape(-1, 4, 4).copy()
+        if fc:
+            out["fitness_idx"], out["fitness_d2"] = fc
+        return out
+
+    def icp_p2l_dev(self, d_src, ns, d_tgt, nt, d_normals, params):
+        """kss_icp_p2l_dev on device pointers (d_normals may be 0 / None); returns the IcpResult."""
+        res = IcpResult()
+        self._chk(self.L.kss_icp_p2l_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
+                                         C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(res)),
+                  "kss_icp_p2l_dev")
+        return res
 
     def icp_dev(self, d_src, ns, d_tgt, nt, params):
         res = IcpResult()

@@ -18,6 +18,7 @@ const char* kss_status_string(int s) {
         case KSS_ERR_NODEVICE: return "no usable GPU device";
         case KSS_ERR_CAPACITY: return "output buffer too small";
         case KSS_ERR_RCCL: return "RCCL error";
+        case KSS_ERR_DEGENERATE: return "degenerate point-to-plane system";
         default: return "unknown status";
     }
 }
@@ -65,11 +66,12 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->cand_tags, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pair_ticket, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->cand_tags, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pair_ticket, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
     if (c->h_seq) hipHostFree(c->h_seq);
+    if (c->h_p2l) hipHostFree(c->h_p2l);
     if (c->h_box) hipHostFree(c->h_box);
     if (c->h_xf) hipHostFree(c->h_xf);
     if (c->gate_bar) hipFree(c->gate_bar);
@@ -414,6 +416,88 @@ int kss_rigid_from_sums(const double sums[KSS_NSUMS], float T[16]) {
     if (!(sums[0] >= 1.0)) return KSS_ERR_ARG;
     rigid_from_sums(sums, T);
     return KSS_OK;
+}
+
+// ---- point-to-plane ---------------------------------------------------------------------------------
+int kss_p2l_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n,
+                     int64_t nt, double max_d2, double sums[KSS_P2L_NSUMS]) {
+    if (!c || !d_src || !d_tgt || !d_nrm || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "p2l_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "p2l_sums: empty input");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
+    {
+        ProfScope ps(c, KSS_K_CORR_REDUCE);
+        launch_p2l_sums(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_tgt, d_nrm, n, nt, max_d2, (double*)c->p2l_rows.p,
+                        (double*)c->h_p2l_dev);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(sums, c->h_p2l, KSS_P2L_NSUMS * sizeof(double));
+    return KSS_OK;
+}
+
+int kss_p2l_sums(kss_ctx* c, const float* src, const float* tgt, const float* nrm, const int32_t* idx, int64_t n, int64_t nt,
+                 double max_d2, double sums[KSS_P2L_NSUMS]) {
+    if (!c || !src || !tgt || !nrm || !idx || !sums) return set_err(c, KSS_ERR_ARG, "p2l_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "p2l_sums: empty input");
+    for (int64_t i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= nt) return set_err(c, KSS_ERR_ARG, "p2l_sums: index out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
+    return kss_p2l_sums_dev(c, (const float*)c->stage_src.p, (const float*)c->stage_tgt.p, (const float*)c->p2l_nrm.p,
+                            (const int32_t*)c->stage_idx.p, n, nt, max_d2, sums);
+}
+
+int kss_rigid_from_p2l_sums(const double sums[KSS_P2L_NSUMS], float T[16]) {
+    if (!sums || !T) return KSS_ERR_ARG;
+    if (!rigid_from_p2l_sums(sums, T)) {
+        mat4_identity(T);
+        return KSS_ERR_DEGENERATE;
+    }
+    return KSS_OK;
+}
+
+int kss_icp_p2l_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                    const kss_icp_params* p, kss_icp_result* res) {
+    if (!c) return KSS_ERR_ARG;
+    if (!d_src || !d_tgt || !p || !res) return set_err(c, KSS_ERR_ARG, "icp_p2l: null argument");
+    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_p2l: empty cloud");
+    if (ns > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "icp_p2l: cloud too large");
+    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_p2l: the source-row split (allreduce) is not available for point-to-plane");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!d_nrm) {
+        // kss_normals' definition (k = 20 incl. the point itself, view-point flip, renormalised in double) on the target widened
+        // to f64 -- whose float narrowing is the target itself -- then rounded to float
+        const int k = nt < 20 ? (int)nt : 20;
+        KCHK(ensure(c, c->p2l_idx, (size_t)nt * k * sizeof(int32_t)));
+        KCHK(ensure(c, c->p2l_d2, (size_t)nt * k * sizeof(float)));
+        KCHK(ensure(c, c->p2l_n64, (size_t)nt * 3 * sizeof(double)));
+        KCHK(ensure(c, c->p2l_nrm, (size_t)nt * 3 * sizeof(float)));
+        KCHK(knn_generic_dev(c, d_tgt, nt, d_tgt, nt, KSS_F32, k, (int32_t*)c->p2l_idx.p, (float*)c->p2l_d2.p));
+        launch_normals(c->stream, (const float4*)c->src0.p, (int)nt, (const int32_t*)c->p2l_idx.p, k, (double*)c->p2l_n64.p);
+        launch_f64_to_f32(c->stream, (const double*)c->p2l_n64.p, nt * 3, (float*)c->p2l_nrm.p);
+        HIPCHK(c, hipGetLastError());
+        d_nrm = (const float*)c->p2l_nrm.p;
+    }
+    return p2l_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, res);
+}
+
+int kss_icp_p2l(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
+                const kss_icp_params* p, kss_icp_result* res) {
+    if (!c || !src || !tgt) return set_err(c, KSS_ERR_ARG, "icp_p2l: null cloud");
+    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_p2l: empty cloud");
+    if (!p || !res) return set_err(c, KSS_ERR_ARG, "icp_p2l: null argument");
+    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_p2l: the source-row split (allreduce) is not available for point-to-plane");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_p2l_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
+                           p, res);
 }
 
 // ---- pre-shape ------------------------------------------------------------------------------------

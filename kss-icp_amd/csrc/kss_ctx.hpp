@@ -48,6 +48,9 @@ struct kss_ctx {
     DevBuf tgt4, src0, cur[2], keys, partials, sums, nn_work, red_work, pair_red, state, cs, scratch_a,
         scratch_b, scratch_c, stage_src, stage_tgt, stage_idx, stage_d2, stage_out, g_counts, g_start, g_cursor,
         g_bsums, g_sorted, g_list, g_count, g_bbox, g_partials, g_start2, g_pairs, g_stamps, g_pos, g_nnst, res_pos, res_wc, res_perm, cand_tags, pack_seg, reg_s, reg_t, reg_p, reg_all, reg_f, reg_g, oct_pts, oct_cen, oct_a, oct_b, oct_tmp, pair_ticket, pre_partials, pre_state, g_rowpair, g_gate;
+    // point-to-plane ICP (kss_p2l.hip): per-pass idx / d2, source slot of each original index, partial rows, float normals
+    // (staged or computed) and their f64 form from the normals kernel
+    DevBuf p2l_idx, p2l_d2, p2l_perm, p2l_rows, p2l_nrm, p2l_n64;
     HostPool pool;   // per-pair host work of batched iterations
     std::vector<kss_ctx*> workers;   // contexts of kss_register_batch's worker threads (same device, own streams)
     std::vector<unsigned long long> last_stamps;
@@ -59,6 +62,8 @@ struct kss_ctx {
     // pinned host staging
     void* h_sums = nullptr;  size_t h_sums_cap = 0;   // host-mapped: kernels write it through h_sums_dev
     void* h_sums_dev = nullptr;
+    void* h_p2l = nullptr; size_t h_p2l_cap = 0;     // host-mapped: the KSS_P2L_NSUMS record, written through h_p2l_dev
+    void* h_p2l_dev = nullptr;
     unsigned long long* h_seq = nullptr;       // host-mapped result of the fused grid kernel: NSUMS x {bits(sum), sequence number}
     unsigned long long* h_seq_dev = nullptr;
     size_t h_seq_bytes = 0;
@@ -160,6 +165,11 @@ static inline int ensure_pinned(kss_ctx* c, void*& p, size_t& cap, size_t bytes)
         HIPCHK(c, hipHostGetDevicePointer(&d, p, 0));
         c->h_sums_dev = d;
     }
+    if (&p == &c->h_p2l) {
+        void* d = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer(&d, p, 0));
+        c->h_p2l_dev = d;
+    }
     return KSS_OK;
 }
 
@@ -225,6 +235,9 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // one exact NN pass of a single pair (+ the correspondence sums when sums_out is given)
 int nn_generic_dev(kss_ctx* c, const void* d_src, int64_t ns, const void* d_tgt, int64_t nt, int dtype,
                    int32_t* d_idx, float* d_d2, double sums_out[NSUMS]);
+// point-to-plane ICP of one pair (float clouds and target normals on the device)
+int p2l_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                const kss_icp_params* p, kss_icp_result* res);
 // host-mapped {value, sequence number} result slots: allocate them; wait for the first nslots of launch c->seq
 int ensure_pub_slots(kss_ctx* c);
 int wait_slots(kss_ctx* c, int nslots, double* out);

@@ -118,6 +118,77 @@ inline void rigid_from_sums(const double sums[NSUMS], float T[16]) {
     T[15] = 1.f;
 }
 
+// ---- TransformationEstimationPointToPlaneLLS from the point-to-plane sums (KSS_P2L_NSUMS in include/kssicp.h) --------
+// ATA x = ATb by Cholesky L L^T in the textbook column order, forward then back substitution, every sum added left to right
+// (PCL takes ATA.inverse () * ATb).  x = (alpha, beta, gamma, tx, ty, tz).  Degenerate -- false, T untouched --
+// when a pivot is not finite or <= 1e-12 * max(diag ATA).
+constexpr int P2L_NSUMS = 32;
+
+inline bool p2l_solve(const double sums[P2L_NSUMS], double x[6]) {
+    double A[6][6], L[6][6] = {}, b[6], y[6];
+    for (int i = 0, k = 1; i < 6; ++i)
+        for (int j = i; j < 6; ++j, ++k) A[i][j] = A[j][i] = sums[k];
+    for (int i = 0; i < 6; ++i) b[i] = sums[22 + i];
+    double dmax = 0.0;
+    for (int i = 0; i < 6; ++i)
+        if (A[i][i] > dmax) dmax = A[i][i];
+    const double tol = 1e-12 * dmax;
+    for (int j = 0; j < 6; ++j) {
+        double s = A[j][j];
+        for (int k = 0; k < j; ++k) s = s - L[j][k] * L[j][k];
+        if (!std::isfinite(s) || s <= tol) return false;
+        L[j][j] = std::sqrt(s);
+        for (int i = j + 1; i < 6; ++i) {
+            double t = A[i][j];
+            for (int k = 0; k < j; ++k) t = t - L[i][k] * L[j][k];
+            L[i][j] = t / L[j][j];
+        }
+    }
+    for (int i = 0; i < 6; ++i) {
+        double t = b[i];
+        for (int k = 0; k < i; ++k) t = t - L[i][k] * y[k];
+        y[i] = t / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double t = y[i];
+        for (int k = i + 1; k < 6; ++k) t = t - L[k][i] * x[k];
+        x[i] = t / L[i][i];
+    }
+    return true;
+}
+
+// pcl::registration::TransformationEstimationPointToPlaneLLS::constructTransformationMatrix: R = Rz(gamma) Ry(beta) Rx(alpha),
+// every entry written as PCL writes it, evaluated in double with libm sin / cos, then rounded to float.
+inline void p2l_transform(const double x[6], float T[16]) {
+    // (the angles go through a volatile for the cos calls: a compiler that merges sin(a) and cos(a) into sincos() must not
+    // get the chance -- the tests compare against separate sin and cos bit for bit)
+    volatile double va = x[0], vb = x[1], vg = x[2];
+    const double sa = std::sin(x[0]), sb = std::sin(x[1]), sg = std::sin(x[2]);
+    const double ca = std::cos(va), cb = std::cos(vb), cg = std::cos(vg);
+    T[0] = (float)(cg * cb);
+    T[1] = (float)(-sg * ca + cg * sb * sa);
+    T[2] = (float)(sg * sa + cg * sb * ca);
+    T[3] = (float)x[3];
+    T[4] = (float)(sg * cb);
+    T[5] = (float)(cg * ca + sg * sb * sa);
+    T[6] = (float)(-cg * sa + sg * sb * ca);
+    T[7] = (float)x[4];
+    T[8] = (float)(-sb);
+    T[9] = (float)(cb * sa);
+    T[10] = (float)(cb * ca);
+    T[11] = (float)x[5];
+    T[12] = T[13] = T[14] = 0.f;
+    T[15] = 1.f;
+}
+
+// T from the sums; false (T untouched) when the system is degenerate
+inline bool rigid_from_p2l_sums(const double sums[P2L_NSUMS], float T[16]) {
+    double x[6];
+    if (!p2l_solve(sums, x)) return false;
+    p2l_transform(x, T);
+    return true;
+}
+
 // ---- Matrix4f product, Eigen order: ((a0*b0 + a1*b1) + a2*b2) + a3*b3, no fma -------------
 inline void mat4_mul(const float A[16], const float B[16], float C[16]) {
     float R[16];

@@ -326,6 +326,17 @@ void launch_normals(hipStream_t st, const float4* d_pts, int n, const int32_t* d
 int preshape_blocks(int64_t n);
 int stream_blocks(int64_t n);
 
+// point-to-plane sums (kss_p2l.hip): partial rows over p2l_rows_blocks(n) workgroups, then one workgroup writes the
+// KSS_P2L_NSUMS record to d_out (device or host-mapped).  Sources: d_src3 (packed float triples, original order) or d_src4
+// (float4; with d_perm: cell order, d_perm[i] = slot of original source i).  d_d2: NN distances (null: recomputed).
+static_assert(P2L_NSUMS == KSS_P2L_NSUMS, "kss_host_math.hpp and include/kssicp.h disagree");
+int p2l_rows_blocks(int64_t n);
+void launch_p2l_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
+                     const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
+                     double* d_rows, double* d_out);
+void launch_p2l_perm(hipStream_t st, const float4* d_src, int64_t n, int32_t* d_perm);
+void launch_f64_to_f32(hipStream_t st, const double* d_in, int64_t n, float* d_out);
+
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,
                 const std::function<void*(size_t)>& scratch);
