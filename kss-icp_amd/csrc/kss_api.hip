@@ -66,7 +66,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->cand_tags, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pair_ticket, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -514,16 +514,14 @@ int kss_preshape_stats_pair_dev(kss_ctx* c, const void* d_src, int64_t ns, const
     const void* xyz[2] = {d_src, d_tgt};
     const int64_t n[2] = {ns, d_tgt ? nt : 0};
     const int nb = preshape_blocks(ns) + (d_tgt ? preshape_blocks(nt) : 0);
-    KCHK(ensure(c, c->pre_partials, (size_t)nb * 4 * sizeof(double)));
-    if (!c->pre_state.p) {
-        KCHK(ensure(c, c->pre_state, 128));   // [0, 16): four tickets, [64, 128): two centroids
-        HIPCHK(c, hipMemsetAsync(c->pre_state.p, 0, 128, c->stream));
-    }
+    KCHK(ensure_zeroed(c, c->pre_partials, (size_t)nb * 4 * sizeof(Granule)));   // (zeroed when (re)allocated: no granule of an earlier owner)
+    KCHK(ensure_zeroed(c, c->pre_state, 8 * sizeof(double)));   // the two centroids, each with the number of the launch that stored it
     KCHK(ensure_pub_slots(c));
     {
         ProfScope ps(c, KSS_K_PRESHAPE);
-        launch_preshape_pair(c->stream, xyz, n, dtype, (double*)c->pre_partials.p, (int32_t*)c->pre_state.p,
-                             (double*)((char*)c->pre_state.p + 64), c->h_seq_dev, ++c->seq);
+        const unsigned long long seq_sum = ++c->seq;   // (each launch hands its rows over under a number of its own)
+        const unsigned long long seq = ++c->seq;
+        launch_preshape_pair(c->stream, xyz, n, dtype, (Granule*)c->pre_partials.p, (double*)c->pre_state.p, c->h_seq_dev, seq_sum, seq);
     }
     HIPCHK(c, hipGetLastError());
     double h[8];

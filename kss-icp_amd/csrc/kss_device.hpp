@@ -83,6 +83,100 @@ __device__ __forceinline__ double rows_column_sum(const double* __restrict__ row
     return v;
 }
 
+// ---- row hand-over: the one way a reduction's rows reach the workgroup that adds them up --------------------------------
+// Every workgroup of a reduction that spans several leaves one row of sums.  Each value travels as a GRANULE {bits(value),
+// sequence number of its launch or pass}, written by ONE 16-byte write-through (sc1) store: no drain, no flag, no counter.
+// The reducer accepts a granule when it carries the number it expects, so nothing has to be reset between launches (a
+// granule of another launch carries another number; a granule buffer is zeroed when it is (re)allocated, and numbers
+// start at 1).  A reducer that waits inside its launch holds a workgroup slot while it polls: it may wait there only where
+// the launch has at most one waiter per compute unit -- the other workgroups never wait, so they all get to run (HIP
+// promises no dispatch order).  Otherwise the rows are added up by the next launch.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// granule `col` of a row: `row` is the same in every lane (a scalar base; the lane's offset is formed inside the asm, where
+// the compiler cannot hoist it and keep it live across the kernel: two registers and one wave per SIMD in cand_pass_kernel)
+__device__ __forceinline__ void row_put(Granule* row, int col, double v, unsigned long long seq) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    u32x4 o;
+    o.x = (unsigned)b; o.y = (unsigned)(b >> 32); o.z = (unsigned)seq; o.w = (unsigned)(seq >> 32);
+    unsigned off;
+    asm volatile("v_lshlrev_b32 %0, 4, %2\n\tglobal_store_dwordx4 %0, %1, %3 sc1" : "=&v"(off) : "v"(o), "v"(col), "s"(row) : "memory");
+}
+
+// Sum of column `col` over the rows first, first + stride, ... < n (ncols granules per row), added in increasing row
+// order, eight sc1 loads in flight per poll.  A batch of eight is accepted when every granule carries `seq`; the wave sleeps
+// between polls (the ballot keeps the loads convergent).  More than `polls` polls, or stop() (asked every 32 polls),
+// ends the wait: returns false.  `rows` is the same in every lane (scalar base + 32-bit lane offsets: half the address
+// registers) and spans less than 4 GB.
+struct NoStop { __device__ bool operator()() const { return false; } };
+template <typename Stop = NoStop>
+__device__ __forceinline__ bool rows_take(const Granule* __restrict__ rows, int ncols, int col, int first, int stride, int n,
+                                          unsigned long long seq, int polls, double& sum, Stop stop = Stop()) {
+    const unsigned lo = (unsigned)seq, hi = (unsigned)(seq >> 32);
+    double acc = 0.0;
+    for (int k = first; k < n; k += 8 * stride) {
+        unsigned o[8];   // byte offsets
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (unsigned)((k + j * stride < n ? k + j * stride : k) * ncols + col) * (unsigned)sizeof(Granule);
+        u32x4 t0, t1, t2, t3, t4, t5, t6, t7;
+        int spins = 0;
+        for (;;) {
+            asm volatile(
+                "global_load_dwordx4 %0, %8, %16 sc1\n\tglobal_load_dwordx4 %1, %9, %16 sc1\n\t"
+                "global_load_dwordx4 %2, %10, %16 sc1\n\tglobal_load_dwordx4 %3, %11, %16 sc1\n\t"
+                "global_load_dwordx4 %4, %12, %16 sc1\n\tglobal_load_dwordx4 %5, %13, %16 sc1\n\t"
+                "global_load_dwordx4 %6, %14, %16 sc1\n\tglobal_load_dwordx4 %7, %15, %16 sc1\n\t"
+                "s_waitcnt vmcnt(0)"
+                : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(t4), "=&v"(t5), "=&v"(t6), "=&v"(t7)
+                : "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(o[4]), "v"(o[5]), "v"(o[6]), "v"(o[7]), "s"(rows)
+                : "memory");
+            const bool ok = t0.z == lo && t0.w == hi && t1.z == lo && t1.w == hi && t2.z == lo && t2.w == hi && t3.z == lo && t3.w == hi &&
+                            t4.z == lo && t4.w == hi && t5.z == lo && t5.w == hi && t6.z == lo && t6.w == hi && t7.z == lo && t7.w == hi;
+            if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;
+            if (++spins > polls || ((spins & 31) == 0 && stop())) return false;
+            __builtin_amdgcn_s_sleep(1);
+        }
+        const u32x4 tt[8] = {t0, t1, t2, t3, t4, t5, t6, t7};
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (k + j * stride < n) acc += __longlong_as_double((long long)(((unsigned long long)tt[j].y << 32) | tt[j].x));
+    }
+    sum = acc;
+    return true;
+}
+
+// The reducer's column totals of n rows of NSUMS granules: lane slot (g, c) adds rows g, g + G, g + 2G, ... of column c
+// (rows_take), then the G group totals are added in group order -- a function of the rows only.  The result is valid in
+// lanes tid < NSUMS; false (in every lane) when a row never came.  shg: G x NSUMS doubles of LDS.
+template <int G, typename Stop = NoStop>
+__device__ __forceinline__ bool rows_total(const Granule* __restrict__ rows, int n, unsigned long long seq, int polls,
+                                           double (*shg)[NSUMS], int* s_ok, double& v, Stop stop = Stop()) {
+    if (threadIdx.x == 0) *s_ok = 1;
+    __syncthreads();
+    for (int t = (int)threadIdx.x; t < G * NSUMS; t += (int)blockDim.x) {
+        const int g = t / NSUMS, c = t % NSUMS;
+        if (!rows_take(rows, NSUMS, c, g, G, n, seq, polls, shg[g][c], stop)) *s_ok = 0;
+    }
+    __syncthreads();
+    v = 0.0;
+    if (threadIdx.x < NSUMS)
+        for (int gg = 0; gg < G; ++gg) v += shg[gg][threadIdx.x];
+    return *s_ok != 0;
+}
+
+// One published value: {bits(v), low word of seq, check word of those three} as ONE aligned 16-byte system-scope store into
+// host-mapped memory (slot `slot` of pub).  The host takes a slot when the number matches and the check word fits, so no
+// flag has to be ordered after the data and no L2 write-back is needed.  torn_xor != 0 (test hook only): the bits are
+// stored altered, the check word of the true ones -- a slot as a torn read would see it.
+__device__ __forceinline__ void pub_put(unsigned long long* pub, int64_t slot, double v, unsigned long long seq, unsigned torn_xor = 0u) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    u32x4 o;
+    o.x = (unsigned)b; o.y = (unsigned)(b >> 32); o.z = (unsigned)seq; o.w = kss_mix3(o.x, o.y, o.z);
+    o.x ^= torn_xor;
+    unsigned long long* dst = pub + 2 * slot;
+    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(o) : "memory");
+}
+
 // ---- the canonical summation order of the fused cell-list pass (grid_pass_kernel) ------------------------------
 // One ROW = the sums over one CHUNK of 512 consecutive (cell-sorted) sources of a pair: lane t holds source
 // 512 * chunk + t.  Per f64 column the row value is a fixed binary tree over the 64 lanes of each wave -- partners at lane

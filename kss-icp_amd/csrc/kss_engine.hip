@@ -15,8 +15,9 @@ static int restore_zero_at_rest(kss_ctx* c);
 static bool resident_gate_available(kss_ctx* c, int npairs);
 
 // Workgroups of ONE launch that are certainly on the chip at the same time: one per compute unit of THIS device (the fused
-// single-pair kernels need at most one CU's registers and LDS each).  Tagged rows and chained launches rely on it; on a
-// partitioned or smaller part the limit shrinks with the CU count instead of stalling every chain until its polls run out.
+// single-pair kernels need at most one CU's registers and LDS each).  Chained launches and the batches whose reducers wait
+// in-launch rely on it; on a partitioned or smaller part the limit shrinks with the CU count instead of stalling every
+// chain until its polls run out.
 static int resident_rows_limit(kss_ctx* c) {
     if (c->cu_count <= 0) {
         hipDeviceProp_t prop;
@@ -244,13 +245,12 @@ static int stage_plan(kss_ctx* c, const IcpPlan& pl) {
     KCHK(ensure(c, c->cur[0], (size_t)pl.total_src * sizeof(float4)));
     KCHK(ensure(c, c->cur[1], (size_t)pl.total_src * sizeof(float4)));
     KCHK(ensure(c, c->keys, (size_t)pl.total_keys * sizeof(unsigned long long)));
-    KCHK(ensure_zeroed(c, c->partials, std::max<size_t>(pl.red.size(), 2 * (size_t)pl.total_rows) * NSUMS * sizeof(double)));   // (x2: rows as 16-byte granules; zeroed when (re)allocated: no stale {bits, number} granule of an earlier owner of the block)
+    KCHK(ensure_zeroed(c, c->partials, std::max<size_t>(pl.red.size(), (size_t)pl.total_rows) * NSUMS * sizeof(Granule)));   // (rows as 16-byte granules; zeroed when (re)allocated: no stale {bits, number} granule of an earlier owner of the block)
     KCHK(ensure(c, c->sums, (size_t)pl.npairs * NSUMS * sizeof(double)));
     KCHK(ensure(c, c->nn_work, pl.nn_count * sizeof(NNWork)));
     KCHK(ensure(c, c->red_work, pl.red.size() * sizeof(RedWork)));
     KCHK(ensure(c, c->pair_red, pl.pred.size() * sizeof(PairRed)));
     KCHK(ensure(c, c->state, (size_t)pl.npairs * sizeof(PairState)));
-    KCHK(ensure_zeroed(c, c->pair_ticket, (size_t)std::max(pl.npairs, PUB_PAIRS) * sizeof(int32_t)));   // zero at rest (kss_ctx.hpp)
     KCHK(ensure_pinned(c, c->h_sums, c->h_sums_cap, (size_t)pl.npairs * NSUMS * sizeof(double)));
     KCHK(ensure_pinned(c, c->h_state, c->h_state_cap, (size_t)pl.npairs * sizeof(PairState)));
     KCHK(ensure_pub(c, pl.npairs));
@@ -744,7 +744,7 @@ static PassArgs pass_args(kss_ctx* c, const IcpPlan& pl, const float4* d_in, flo
     static const bool noprev = getenv("KSS_GRID_NOPREV") != nullptr;   // A/B switch: the previous winner is stored but not used as a bound
     a.use_prev = !noprev && c->nn_have ? 1 : 0;   // (nn_have: a search pass of this registration has written the per-source state)
     a.max_d2 = max_d2;
-    a.rows = (double*)c->partials.p; a.tickets = (int32_t*)c->pair_ticket.p;
+    a.rows = (Granule*)c->partials.p;
     a.pub = c->h_seq_dev;
     a.idx_out = d_idx_out; a.d2_out = d_d2_out;
     {   // test hook: the n-th fused launch stores one of its result slots torn first (kss_grid.hip)
@@ -755,16 +755,11 @@ static PassArgs pass_args(kss_ctx* c, const IcpPlan& pl, const float4* d_in, flo
     if (pl.gridb) {
         a.pairs = (const GridPairDev*)c->g_pairs.p;
         a.row_pair = (const int32_t*)c->g_rowpair.p;
+        // each pair's first workgroup adds the pair's rows up in the pass -- one waiter per pair, so at most one per compute
+        // unit -- or, with more pairs than that, a finalize launch right after it does
+        a.defer_pairs = pl.npairs > resident_rows_limit(c) ? pl.npairs : 0;
     } else {
-        a.pair0 = pl.gpairs[0];
-        // rows as tagged granules + a designated reducer instead of drain + ticket.  Only the reducer waits -- for rows of
-        // workgroups that nothing keeps from starting (it holds one slot of the chip) -- so the form does not need the launch
-        // to be resident at once; the CHAIN built on it does (below).  At 1954 rows it takes the store-acknowledge wait and the
-        // ticket round trip (2 of 9 us) off every workgroup's life and most of the last workgroup's 1954-row total off the
-        // tail.  KSS_TAGGED_ROWS=0: A/B switch; KSS_TAGGED_ROWS_MAX: rows up to which the form is used (default: any).
-        static const bool tagged = getenv("KSS_TAGGED_ROWS") == nullptr || atoi(getenv("KSS_TAGGED_ROWS")) != 0;
-        static const int tagged_max = getenv("KSS_TAGGED_ROWS_MAX") ? atoi(getenv("KSS_TAGGED_ROWS_MAX")) : (1 << 30);
-        a.tagged_rows = tagged && pl.total_rows <= std::max(tagged_max, resident_rows_limit(c)) ? 1 : 0;
+        a.pair0 = pl.gpairs[0];   // (a single pair: its first workgroup is the one waiter, at any row count)
     }
     return a;
 }
@@ -827,13 +822,12 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
         // the profiler samples (every n-th) are plain launches; the others advance its tick here
         const bool next_sampled = c->prof == 1 || (c->prof > 1 && c->prof_tick[KSS_K_GRID_NN] % (unsigned)c->prof == 0);
         // how many iterations a pre-enqueued launch may run: all that can still follow (KSS_CHAIN=0: one, the form of every
-        // system without a large BAR).  Chains need rows handed over as tagged granules (no ticket to re-arm between
-        // passes) or a single row.  A single gated launch stays out of the way of the launches the profiler samples; a
+        // system without a large BAR).  A single gated launch stays out of the way of the launches the profiler samples; a
         // chain is bracketed as a whole instead.
         static const bool want_chain = getenv("KSS_CHAIN") == nullptr || atoi(getenv("KSS_CHAIN")) != 0;
         int len = 1;
         if (G.want_next && !G.pending && plain_args && gated_available(c) && want_chain && c->gate_bar &&
-            ((a.tagged_rows && pl.total_rows <= resident_rows_limit(c)) || pl.total_rows == 1))   // (every workgroup of a chain waits at its gates: resident at once)
+            (pl.total_rows <= resident_rows_limit(c) || pl.total_rows == 1))   // (every workgroup of a chain waits at its gates: resident at once)
             len = std::max(1, std::min(G.max_steps, 1 << 16));
         if (G.want_next && !G.pending && plain_args && gated_available(c) && (len > 1 || !next_sampled)) {
             if (c->prof > 1 && len == 1) ++c->prof_tick[KSS_K_GRID_NN];
@@ -879,8 +873,8 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
                 c->err.clear();
                 std::fprintf(stderr, "[kss] a waiting kernel was not answered in time and left; the pass is launched again\n");
                 // With more rows than resident workgroups the launch may have left in part only: workgroups that started after
-                // the answer finally arrived have run, written their sources and drawn tickets that nobody completed.  The
-                // stream has drained (wait_seq synchronised): re-arm everything that is zero at rest before the plain launch.
+                // the answer finally arrived have run, written their sources and may have put sources on the fallback list.
+                // The stream has drained (wait_seq synchronised): re-arm everything that is zero at rest before the plain launch.
                 c->ws_dirty = true;
                 KCHK(restore_zero_at_rest(c));
                 ProfScope ps(c, KSS_K_GRID_NN);
@@ -952,7 +946,9 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
         return KSS_OK;
     }
     if (pl.gridb) {
-        // batch: one launch searches every active pair and publishes each pair's sums as its last workgroup finishes.
+        // batch: one launch searches every active pair; each pair's sums are published as soon as its rows are added up --
+        // inside the launch by the pair's first workgroup, or, with more pairs than compute units, by the finalize launch
+        // right after it (then every pair lands only once the whole pass is done).
         // The per-pair states (transform to apply, active flag) are read by every workgroup: a small batch reads them
         // straight from the pinned host-mapped table (no copy operation on the stream), a large one (thousands of
         // workgroups) gets the table copied to device memory once per pass.
@@ -1006,13 +1002,12 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
         bool same = true;
         for (int p = 1; p < pl.npairs; ++p) same = same && pl.g[p].ns == pl.g[0].ns && pl.g[p].src_base == (int64_t)p * pl.g[0].ns;
         const int bpp = cand_pass_blocks_per_pair(pl.g[0].ns);
-        if (same && ensure_zeroed(c, c->partials, (size_t)pl.npairs * bpp * NSUMS * sizeof(double)) == KSS_OK &&
-            ensure_zeroed(c, c->cand_tags, (size_t)pl.npairs * bpp * sizeof(unsigned)) == KSS_OK) {
+        if (same && ensure_zeroed(c, c->partials, (size_t)pl.npairs * bpp * NSUMS * sizeof(Granule)) == KSS_OK) {
             bool launched;
             {
                 ProfScope ps(c, KSS_K_NN_SWEEP);
                 launched = launch_cand_pass(c->stream, fma, pl.npairs, d_state, d_in, d_out, (const float4*)c->tgt4.p + pl.g[0].tgt_base, pl.g[0].tgt_pad,
-                                            (int)pl.g[0].ns, max_d2, (double*)c->partials.p, (unsigned*)c->cand_tags.p, c->h_seq_dev, c->seq + 1, d_idx_out, d_d2_out);
+                                            (int)pl.g[0].ns, max_d2, (Granule*)c->partials.p, c->h_seq_dev, c->seq + 1, d_idx_out, d_d2_out);
             }
             if (launched) {
                 ++c->seq;
@@ -1031,11 +1026,11 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
     const bool spin = pl.npairs <= PUB_PAIRS;
     {
         ProfScope ps(c, KSS_K_CORR_REDUCE);
-        if (spin) {   // small batch: the reduce also adds each pair's rows up and publishes (pair tickets zeroed by stage_plan)
+        if (spin) {   // small batch: the reduce also adds each pair's rows up and publishes
             launch_corr_reduce_publish(c->stream, (const RedWork*)c->red_work.p, (int)pl.red.size(), d_state,
                                        d_out, (const float4*)c->tgt4.p, (const unsigned long long*)c->keys.p, max_d2,
-                                       (double*)c->partials.p, d_idx_out, d_d2_out, pl.src_in_cell_order ? 1 : 0,
-                                       (const PairRed*)c->pair_red.p, (int32_t*)c->pair_ticket.p, c->h_seq_dev, ++c->seq);
+                                       (Granule*)c->partials.p, d_idx_out, d_d2_out, pl.src_in_cell_order ? 1 : 0,
+                                       (const PairRed*)c->pair_red.p, c->h_seq_dev, ++c->seq);
         } else {
             launch_corr_reduce(c->stream, (const RedWork*)c->red_work.p, (int)pl.red.size(), d_state,
                                d_out, (const float4*)c->tgt4.p, (const unsigned long long*)c->keys.p, max_d2,
@@ -1274,7 +1269,7 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
         if (!tpw) return KSS_OK;
         gate = resident_gate(c, np);
         if (!gate) return KSS_OK;
-        if (ensure_zeroed(c, c->partials, (size_t)np * bpp * NSUMS * sizeof(double)) != KSS_OK) return KSS_OK;
+        if (ensure_zeroed(c, c->partials, (size_t)np * bpp * NSUMS * sizeof(Granule)) != KSS_OK) return KSS_OK;
         CandArgs ca;
         std::memset(&ca, 0, sizeof ca);
         ca.src0 = (const float4*)c->src0.p;
@@ -1282,9 +1277,7 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
         ca.nt_pad = nt_pad; ca.ns = (int)pl.g[0].ns;
         ca.bpp = bpp; ca.tpw = tpw; ca.wpp = (bpp + tpw - 1) / tpw;
         ca.max_d2 = P.max_corr_dist * P.max_corr_dist;
-        ca.partials = (double*)c->partials.p;
-        KCHK(ensure_zeroed(c, c->cand_tags, (size_t)np * bpp * sizeof(unsigned)));   // (zeroed when (re)allocated: no tag of the block's earlier owner; pass numbers start at 1)
-        ca.row_tag = (unsigned*)c->cand_tags.p;
+        ca.rows = (Granule*)c->partials.p;   // (zeroed when (re)allocated: no granule of the block's earlier owner; pass numbers start at 1)
         ca.gate = gate;
         ca.pub = c->h_seq_dev;
         ca.exit_flags = c->h_seq_dev + (size_t)2 * NSUMS * np;
@@ -1503,11 +1496,10 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
     if (failed.load()) {
         // let every workgroup that still waits (or has not started yet) leave, then report: the caller starts over on the
         // launch-per-pass engine (the resident kernel has written nothing but its result slots -- and, for candidates, rows
-        // and row tags that carry this launch's numbers)
+        // that carry this launch's numbers)
         for (int p = 0; p < np; ++p)
             if (H[p].phase != PH_DONE) send(p, nullptr, 0, 2, true);
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (cand) { c->ws_dirty = true; KCHK(restore_zero_at_rest(c)); }
         static const int backoff_s = getenv("KSS_RES_BACKOFF_S") ? atoi(getenv("KSS_RES_BACKOFF_S")) : 30;
         c->res_backoff[cand ? 1 : 0] = std::chrono::steady_clock::now() + std::chrono::seconds(backoff_s);   // not again for a while: each failure costs the polls' bound (~1 s)
         {
@@ -1692,8 +1684,8 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
         c->gated.want_next = plan->grid && !P.allreduce && it + 1 < P.max_iterations;
         c->gated.want_full = full;
         c->gated.max_steps = P.max_iterations - (it + 1);
-        // batched cell lists: every pair's sums are published as its last workgroup finishes, and the solve loop
-        // picks the pairs up in that order while the rest of the launch is still running
+        // batched cell lists: the solve loop picks each pair up as its sums land -- while the rest of the launch is still
+        // running where the pairs' first workgroups add their rows up in the pass (at most one pair per compute unit)
         c->defer_wait = plan->gridb;
         const auto tb0 = c->timing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
         const int rc_pass = nn_pass(c, *plan, P.nn_fma != 0, d_in, d_out, max_d2, nullptr, nullptr, full, active.data());
@@ -1783,7 +1775,7 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
 static int restore_zero_at_rest(kss_ctx* c) {
     if (!c->ws_dirty) return KSS_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (DevBuf* b : {&c->pair_ticket, &c->g_count, &c->g_counts})
+    for (DevBuf* b : {&c->g_count, &c->g_counts})
         if (b->p) HIPCHK(c, hipMemsetAsync(b->p, 0, b->cap, c->stream));
     c->ws_dirty = false;
     return KSS_OK;

@@ -688,10 +688,10 @@ do {                                                                            
 //   - sums: every lane contributes its correspondence to 16 f64 columns (+ 2 in FULL mode: sum of all d2 and of
 //     sqrt(d2) for getFitnessScore / PCR_QM; counts are ballots), reduced in the canonical order of kss_device.hpp:
 //     in-wave tree by permlane swaps + DPP (no LDS, no barrier), 8 wave totals through LDS, one row per workgroup;
-//   - rows are handed over with write-through sc1 stores + vmcnt(0) + workgroup barrier + ONE agent-scope ticket on the
-//     pair's counter (MI355X_MICROARCH.md, "Valid forms", table row 1); the workgroup drawing the pair's last ticket
-//     adds the rows in the canonical order and publishes the 20 sums of the pair as {bits(sum), seq} 16-byte stores into
-//     host-mapped memory, where the host spins on the sequence numbers (no completion flag, no stream sync);
+//   - rows are handed over as granules tagged with the launch's sequence number (kss_device.hpp, rows_take); the pair's
+//     first workgroup adds them up in the canonical order -- in this launch, or in gridb_finalize_kernel right after it
+//     when a batch has more pairs than compute units -- and publishes the 20 sums of the pair as {bits(sum), seq} 16-byte
+//     stores into host-mapped memory, where the host spins on the sequence numbers (no completion flag, no stream sync);
 //   - a pair of a single chunk skips the hand-over (0.0 + row: the same bits as the general path).
 // The result of a pair is a function of its own clouds only: alone or in a batch of any size, bit for bit.
 // =============================================================================================
@@ -705,8 +705,8 @@ template <bool FMA, bool FULL, bool BATCH, bool SEARCH, bool CHAIN>
 __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES) void grid_pass_kernel(const PassArgs a) {
     static_assert(!CHAIN || (!BATCH && SEARCH), "chained launches: single pair, search passes");
     // diagnostic stamps (100 MHz s_memrealtime): [block*16 + {0 start, 13 first loads in, 9 gate open, 14 phase A done,
-    // 5 phase B entered, 8 answered, 15 phase B done, 1 searched, 2 row ready, 3 ticketed, 4 result stored (last
-    // workgroup)}]; counts: 10 = distance evaluations of the r = 1 block, 11 = evaluation slots, 12 = walkers
+    // 5 phase B entered, 8 answered, 15 phase B done, 1 searched, 2 row ready, 3 row handed over, 4 result stored
+    // (reducer)}]; counts: 10 = distance evaluations of the r = 1 block, 11 = evaluation slots, 12 = walkers
 #define KSS_STAMP(k) do { if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
     KSS_STAMP(0);
     constexpr int BS = PASS_BS;
@@ -738,7 +738,7 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
     __shared__ unsigned short s_wl[BS];
     enum { WK_X, WK_Y, WK_Z, WK_IDX, WK_D2, WK_R, WK_POS, WK_FL = WK_POS, WK_COLS };   // (position code in the request, flags in the answer: one column)
     static_assert(sizeof(PairState) == 64, "the gated launch reads the transform record as 16 dwords");
-    double (*shf)[NSUMS] = reinterpret_cast<double (*)[NSUMS]>(&rowq[0][0]);   // the last workgroup's group totals: rowq is dead by then (two barriers later)
+    double (*shf)[NSUMS] = reinterpret_cast<double (*)[NSUMS]>(&rowq[0][0]);   // the reducer's group totals: rowq is dead by then (two barriers later)
     static_assert(sizeof(double) * PASS_FG * NSUMS <= sizeof(int2) * 9 * WQ, "shf must fit inside rowq");
 
     const int local = (w - pr.row_base) * BS + (int)threadIdx.x;
@@ -841,7 +841,7 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
 #pragma unroll
             for (int k = 0; k < 16; ++k) d32[k] = sh_ps[k];
             if (ps.pad[0] != 0) return;
-            __syncthreads();               // s_last is reused by the ticket below
+            __syncthreads();               // s_last is reused by the reducer below
             KSS_STAMP(9);
         }
     }
@@ -962,123 +962,29 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
         for (int ww = 0; ww < BS / 64; ++ww) r += shw[ww][threadIdx.x];
     KSS_STAMP(2);
 
-    double v = 0.0 + r;                    // a single-chunk pair: exactly what the general path below computes
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    if (pr.n_rows > 1 && a.tagged_rows) {
-        // Single pair whose workgroups are all resident at once (<= 256 of them): rows travel as self-validating 16-byte
-        // granules {bits(sum), launch sequence number} -- one sc1 store per sum, no drain, no ticket -- and the pair's FIRST
-        // workgroup, once its own row is out, polls every row until all carry this launch's number, then adds them in the
-        // canonical order.  Saves the store-acknowledge wait and the ticket round trip of the general protocol below
-        // (~2 us of a 11 us launch); every other workgroup is done the moment its row is stored.  The poll is bounded.
-        if (threadIdx.x < NSUMS) {
-            const unsigned long long rb = (unsigned long long)__double_as_longlong(r);
-            u32x4 o;
-            o.x = (unsigned)rb; o.y = (unsigned)(rb >> 32); o.z = (unsigned)seq_k; o.w = (unsigned)(seq_k >> 32);
-            unsigned long long* dst = reinterpret_cast<unsigned long long*>(a.rows) + 2 * ((int64_t)w * NSUMS + threadIdx.x);
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(o) : "memory");
-        }
-        if (w != pr.row_base) {            // uniform
+    double v = 0.0 + r;                    // a single-chunk pair: exactly what the reducer computes from one row
+    if (pr.n_rows > 1) {
+        // the row goes out as granules (kss_device.hpp); the pair's FIRST workgroup, once its own row is out, adds the rows up
+        // -- in this launch, or in gridb_finalize_kernel after it (a.defer_pairs: more pairs than compute units).  Every
+        // other workgroup is done the moment its row is stored.  The reducer's poll is bounded.
+        Granule* const rows = a.rows + (int64_t)pr.row_base * NSUMS;
+        if (threadIdx.x < NSUMS) row_put(rows + (int64_t)(w - pr.row_base) * NSUMS, threadIdx.x, r, seq_k);
+        KSS_STAMP(3);
+        if (w != pr.row_base || a.defer_pairs) {   // uniform
             if (last_step) return;
             continue;
         }
-        KSS_STAMP(3);
-        if (threadIdx.x == 0) s_last = 1;
-        __syncthreads();
-        {
-            const int g = threadIdx.x / NSUMS, c = threadIdx.x % NSUMS;
-            const unsigned long long* __restrict__ rows2 = reinterpret_cast<const unsigned long long*>(a.rows) + 2 * (int64_t)pr.row_base * NSUMS;
-            if (g < PASS_FG) {
-                double acc = 0.0;
-                for (int k = g; k < pr.n_rows; k += 8 * PASS_FG) {
-                    const unsigned long long* p[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) p[j] = rows2 + 2 * ((int64_t)(k + j * PASS_FG < pr.n_rows ? k + j * PASS_FG : k) * NSUMS + c);
-                    u32x4 t0, t1, t2, t3, t4, t5, t6, t7;
-                    int spins = 0;
-                    for (;;) {
-                        asm volatile(
-                            "global_load_dwordx4 %0, %8, off sc1\n\tglobal_load_dwordx4 %1, %9, off sc1\n\t"
-                            "global_load_dwordx4 %2, %10, off sc1\n\tglobal_load_dwordx4 %3, %11, off sc1\n\t"
-                            "global_load_dwordx4 %4, %12, off sc1\n\tglobal_load_dwordx4 %5, %13, off sc1\n\t"
-                            "global_load_dwordx4 %6, %14, off sc1\n\tglobal_load_dwordx4 %7, %15, off sc1\n\t"
-                            "s_waitcnt vmcnt(0)"
-                            : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(t4), "=&v"(t5), "=&v"(t6), "=&v"(t7)
-                            : "v"(p[0]), "v"(p[1]), "v"(p[2]), "v"(p[3]), "v"(p[4]), "v"(p[5]), "v"(p[6]), "v"(p[7])
-                            : "memory");
-                        const unsigned lo = (unsigned)seq_k, hi = (unsigned)(seq_k >> 32);
-                        const bool ok = t0.z == lo && t0.w == hi && t1.z == lo && t1.w == hi && t2.z == lo && t2.w == hi && t3.z == lo && t3.w == hi &&
-                                        t4.z == lo && t4.w == hi && t5.z == lo && t5.w == hi && t6.z == lo && t6.w == hi && t7.z == lo && t7.w == hi;
-                        if (__builtin_amdgcn_ballot_w64(!ok) == 0ull) break;      // wave-uniform: the loads stay convergent
-                        if (++spins > (1 << 20)) { s_last = 0; break; }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                    const u32x4 tt[8] = {t0, t1, t2, t3, t4, t5, t6, t7};
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        if (k + j * PASS_FG < pr.n_rows) acc += __longlong_as_double((long long)(((unsigned long long)tt[j].y << 32) | tt[j].x));
-                }
-                shf[g][c] = acc;
-            }
-        }
-        __syncthreads();
-        if (!s_last) return;               // a row never arrived: leave without publishing, the host's wait reports it
-        v = 0.0;
-        if (threadIdx.x < NSUMS)
-            for (int gg = 0; gg < PASS_FG; ++gg) v += shf[gg][threadIdx.x];
-    } else if (pr.n_rows > 1) {
-        if (threadIdx.x < NSUMS) {
-            __hip_atomic_store(&a.rows[(int64_t)w * NSUMS + threadIdx.x], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_last = atomicAdd(&a.tickets[pi], 1) == pr.n_rows - 1;
-        __syncthreads();
-        KSS_STAMP(3);
-        if (!s_last) return;
-        // pair total: lane (g, c) adds rows g, g + 25, ... of column c -- eight sc1 loads in flight per batch -- and the 25
-        // group totals are then added in group order
-        {
-            const int g = threadIdx.x / NSUMS, c = threadIdx.x % NSUMS;
-            const double* __restrict__ rows = a.rows + (int64_t)pr.row_base * NSUMS;
-            if (g < PASS_FG) {
-                double acc = 0.0;
-                // (rows in flight per batch: a 1M-point pair has 1954 rows, 78 per lane -- at eight per batch the pair's last
-                // workgroup spent ten dependent round trips here, a fifth of the iteration; the order of the additions is the same)
-                constexpr int RB = BATCH ? 8 : 32;
-                for (int k = g; k < pr.n_rows; k += RB * PASS_FG) {
-                    double t[RB];
-#pragma unroll
-                    for (int j = 0; j < RB; ++j)
-                        t[j] = k + j * PASS_FG < pr.n_rows ? __hip_atomic_load(&rows[(int64_t)(k + j * PASS_FG) * NSUMS + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-#pragma unroll
-                    for (int j = 0; j < RB; ++j) acc += t[j];
-                }
-                shf[g][c] = acc;
-            }
-        }
-        __syncthreads();
-        v = 0.0;
-        if (threadIdx.x < NSUMS)
-            for (int gg = 0; gg < PASS_FG; ++gg) v += shf[gg][threadIdx.x];
-        if (threadIdx.x == 0) a.tickets[pi] = 0;   // re-armed for the next launch (stream order makes it visible)
+        if (!rows_total<PASS_FG>(rows, pr.n_rows, seq_k, 1 << 20, shf, &s_last, v)) return;   // a row never arrived: leave without publishing, the host's wait reports it
     }
     if (threadIdx.x < NSUMS) {
         if (!FULL && (threadIdx.x == 17 || threadIdx.x == 18)) v = 0.0;
-        // {bits(sum), seq} as ONE aligned 16-byte system-scope store per sum into host-mapped memory: the host accepts a
-        // slot when its sequence number matches, so no flag has to be ordered after the data (that ordering would cost a
-        // write-acknowledge round trip over PCIe) and no L2 write-back fence is needed
-        const unsigned long long vb = (unsigned long long)__double_as_longlong(v);
-        u32x4 o;
-        o.x = (unsigned)vb; o.y = (unsigned)(vb >> 32); o.z = (unsigned)seq_k; o.w = kss_mix3(o.x, o.y, o.z);   // (check word: a slot seen torn is read again)
+        const int64_t slot = (int64_t)pi * NSUMS + threadIdx.x;
         if (a.test_torn && threadIdx.x == 5) {   // test hook: first a slot whose data does not fit its check word, the real one a while later
-            u32x4 bad = o;
-            bad.x ^= 0x00100000u;
-            unsigned long long* dst0 = a.pub + 2 * ((int64_t)pi * NSUMS + threadIdx.x);
-            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" ::"v"(dst0), "v"(bad) : "memory");
+            pub_put(a.pub, slot, v, seq_k, 0x00100000u);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             for (int k = 0; k < 400; ++k) __builtin_amdgcn_s_sleep(64);
         }
-        unsigned long long* dst = a.pub + 2 * ((int64_t)pi * NSUMS + threadIdx.x);
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(o) : "memory");
+        pub_put(a.pub, slot, v, seq_k);
         KSS_STAMP(4);
     }
     if (last_step) break;
@@ -1231,50 +1137,38 @@ __global__ __launch_bounds__(256, KSS_BATCH2_WAVES) void gridb_pass_kernel(const
         for (int ww = 0; ww < BS / 64; ++ww) r += shw[ww][threadIdx.x];
     KSS_STAMP(2);
     double v = 0.0 + r;
-    if (pr.n_rows > 1) {
-        if (threadIdx.x < NSUMS) {
-            __hip_atomic_store(&a.rows[(int64_t)w * NSUMS + threadIdx.x], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_last = atomicAdd(&a.tickets[pi], 1) == pr.n_rows - 1;
-        __syncthreads();
+    if (pr.n_rows > 1) {   // hand-over as in grid_pass_kernel
+        Granule* const rows = a.rows + (int64_t)pr.row_base * NSUMS;
+        if (threadIdx.x < NSUMS) row_put(rows + (int64_t)(w - pr.row_base) * NSUMS, threadIdx.x, r, a.seq);
         KSS_STAMP(3);
-        if (!s_last) return;
-        // pair total as in grid_pass_kernel: (group g, column c) adds rows g, g + 25, ...; the 25 group totals in order
-        {
-            const double* __restrict__ rows = a.rows + (int64_t)pr.row_base * NSUMS;
-            for (int t = (int)threadIdx.x; t < PASS_FG * NSUMS; t += NT) {
-                const int g = t / NSUMS, c = t % NSUMS;
-                double acc = 0.0;
-                for (int k = g; k < pr.n_rows; k += 8 * PASS_FG) {
-                    double tt[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        tt[j] = k + j * PASS_FG < pr.n_rows ? __hip_atomic_load(&rows[(int64_t)(k + j * PASS_FG) * NSUMS + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc += tt[j];
-                }
-                shf[g][c] = acc;
-            }
-        }
-        __syncthreads();
-        v = 0.0;
-        if (threadIdx.x < NSUMS)
-            for (int gg = 0; gg < PASS_FG; ++gg) v += shf[gg][threadIdx.x];
-        if (threadIdx.x == 0) a.tickets[pi] = 0;
+        if (w != pr.row_base || a.defer_pairs) return;
+        if (!rows_total<PASS_FG>(rows, pr.n_rows, a.seq, 1 << 20, shf, &s_last, v)) return;
     }
     if (threadIdx.x < NSUMS) {
         if (!FULL && (threadIdx.x == 17 || threadIdx.x == 18)) v = 0.0;
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        const unsigned long long vb = (unsigned long long)__double_as_longlong(v);
-        u32x4 o;
-        o.x = (unsigned)vb; o.y = (unsigned)(vb >> 32); o.z = (unsigned)a.seq; o.w = kss_mix3(o.x, o.y, o.z);
-        unsigned long long* dst = a.pub + 2 * ((int64_t)pi * NSUMS + threadIdx.x);
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(o) : "memory");
+        pub_put(a.pub, (int64_t)pi * NSUMS + threadIdx.x, v, a.seq);
         KSS_STAMP(4);
     }
 #undef KSS_STAMP
+}
+
+// The reducer of grid_pass_kernel / gridb_pass_kernel one launch later, for batches with more pairs than compute units
+// (PassArgs::defer_pairs): one workgroup per pair adds up the rows the pass left and publishes the pair's sums.  The pass
+// has ended, so a pair took part in it exactly when its rows carry the launch's number.
+__global__ __launch_bounds__(256) void gridb_finalize_kernel(const PassArgs a, int full) {
+    __shared__ double shf[PASS_FG][NSUMS];
+    __shared__ int s_ok;
+    const int pi = (int)blockIdx.x;
+    const GridPairDev pr = a.pairs[pi];
+    const Granule* rows = a.rows + (int64_t)pr.row_base * NSUMS;
+    if (pr.n_rows <= 1 || rows[0].seq != a.seq) return;   // (a single-row pair publishes from the pass itself)
+    double v;
+    if (!rows_total<PASS_FG>(rows, pr.n_rows, a.seq, 1 << 20, shf, &s_ok, v)) return;
+    if (threadIdx.x < NSUMS) pub_put(a.pub, (int64_t)pi * NSUMS + threadIdx.x, !full && (threadIdx.x == 17 || threadIdx.x == 18) ? 0.0 : v, a.seq);
+    if (a.stamps && threadIdx.x == 0) {   // stamp 4 ("result stored") in the pass's slot of the pair's first workgroup
+        const int per_xcd = (a.total_rows + 7) / 8, b = (pr.row_base % per_xcd) * 8 + pr.row_base / per_xcd;   // (the pass's XCD remap, inverted)
+        a.stamps[(size_t)b * 16 + 4] = __builtin_amdgcn_s_memrealtime();
+    }
 }
 
 // =============================================================================================
@@ -1645,6 +1539,7 @@ void launch_grid_pass(hipStream_t st, bool fma, bool full, bool batch, bool sear
             }
 #undef KSS_PASSB
         }
+        if (a.defer_pairs) hipLaunchKernelGGL(gridb_finalize_kernel, dim3(a.defer_pairs), dim3(256), 0, st, a, full ? 1 : 0);
     } else if (a.chain_len > 1) {
         if (fma) { if (full) KSS_CHAIN(true, true); else KSS_CHAIN(true, false); }
         else     { if (full) KSS_CHAIN(false, true); else KSS_CHAIN(false, false); }

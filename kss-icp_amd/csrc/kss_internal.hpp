@@ -95,6 +95,9 @@ struct PackSeg {
     int64_t n;          // real points; slots [n, next segment) are sentinel padding
 };
 
+// one value of a row handed over between the workgroups of a reduction: {bits(value), sequence number} (kss_device.hpp)
+struct alignas(16) Granule { unsigned long long bits, seq; };
+
 // arguments of the fused cell-list pass (kss_grid.hip: grid_pass_kernel), by value
 struct PassArgs {
     const float4* src_in; float4* src_out;      // cell-sorted sources (.w = original index): read, transformed copy written
@@ -117,10 +120,12 @@ struct PassArgs {
     int32_t gate_polls;                         // bound of the gate's poll loop (a kernel nobody answers leaves without touching anything)
     int32_t chain_len, gate_slot;               // chained launch: passes run by this one launch (1: a plain launch); first of the two gate records
     float4* src_alt;                            // chained launch: the other work buffer (== src_in), written by every second pass
-    int32_t gate_seq, tagged_rows;              // gated single-pair launch: the stamp `state->pad[1]` must carry; rows as tagged granules
+    int32_t gate_seq;                           // gated single-pair launch: the stamp `state->pad[1]` must carry
+    int32_t defer_pairs;                        // BATCH with more pairs than compute units: its pair count -- gridb_finalize_kernel adds
+                                                // the rows up in the next launch (0: the pair's first workgroup, in this one)
     unsigned int* gate_dev;                     // ... and the device-side copy of the record (five 16-byte granules)
     double max_d2;
-    double* rows; int32_t* tickets;
+    Granule* rows;                              // NSUMS granules per row (kss_device.hpp: the row hand-over)
     unsigned long long* pub; unsigned long long seq;
     int32_t* idx_out; float* d2_out;
     unsigned long long* stamps;                 // diagnostics (null in production): see KSS_STAMP below
@@ -256,16 +261,16 @@ void launch_grid_stats(hipStream_t st, const float4* d_src, int ns, const GridPa
 void launch_corr_reduce(hipStream_t st, const RedWork* d_work, int n_work, const PairState* d_state,
                         const float4* d_src, const float4* d_tgt4, const unsigned long long* d_keys,
                         double max_d2, double* d_partials, int32_t* d_idx_out, float* d_d2_out, int index_in_w);
-// small batches: reduce + per-pair final sum + publication in one launch (d_pair_ticket: one zeroed int per pair)
+// small batches: reduce + per-pair final sum + publication in one launch (rows as granules, d_rows: NSUMS per work item)
 void launch_corr_reduce_publish(hipStream_t st, const RedWork* d_work, int n_work, const PairState* d_state,
                                 const float4* d_src, const float4* d_tgt4, const unsigned long long* d_keys,
-                                double max_d2, double* d_partials, int32_t* d_idx_out, float* d_d2_out, int index_in_w,
-                                const PairRed* d_pair_red, int32_t* d_pair_ticket, unsigned long long* d_pub, unsigned long long seq);
+                                double max_d2, Granule* d_rows, int32_t* d_idx_out, float* d_d2_out, int index_in_w,
+                                const PairRed* d_pair_red, unsigned long long* d_pub, unsigned long long seq);
 // the candidate batch of a registration (pairs sharing one small target): sweep + sums + publication in ONE launch per pass
 size_t cand_pass_lds_bytes(int nt_pad);
 int cand_pass_blocks_per_pair(int64_t ns);
 bool launch_cand_pass(hipStream_t st, bool fma, int npairs, const PairState* d_state, const float4* d_src_in, float4* d_src_out, const float4* d_tgt,
-                      int nt_pad, int ns, double max_d2, double* d_partials, unsigned int* d_row_tag, unsigned long long* d_pub, unsigned long long seq,
+                      int nt_pad, int ns, double max_d2, Granule* d_rows, unsigned long long* d_pub, unsigned long long seq,
                       int32_t* d_idx_out, float* d_d2_out);
 // ... and the same batch with every workgroup RESIDENT for the whole registration (cand_resident_kernel): the target is staged
 // once, the sources stay in registers, and between passes a candidate's workgroups wait at its gate record for the transform
@@ -278,8 +283,7 @@ struct CandArgs {
     int32_t nt_pad, ns;
     int32_t bpp, wpp, tpw;                      // tiles per candidate, workgroups per candidate, tiles per workgroup (<= CAND_TPW)
     double max_d2;
-    double* partials;                           // one row of NSUMS per tile
-    unsigned int* row_tag;                      // one word per tile: the launch-and-pass number its row belongs to (no counter to keep zero at rest)
+    Granule* rows;                              // one row of NSUMS granules per tile, tagged with the launch-and-pass number
     const unsigned int* gate;                   // per candidate 32 words the host stores into through the BAR
     unsigned long long* pub;                    // host-mapped result slots
     unsigned long long seq0;
@@ -297,9 +301,10 @@ void launch_corr_reduce_idx(hipStream_t st, const float* d_src3, const float* d_
 void launch_finalize_sums(hipStream_t st, const PairRed* d_pairs, int n_pairs, const double* d_partials,
                           double* d_out /* n_pairs * NSUMS, device or host-mapped */);
 
-// pre-shape statistics of one or two clouds: two launches, result published to host-mapped {bits, seq} slots
-void launch_preshape_pair(hipStream_t st, const void* const d_xyz[2], const int64_t n[2], int dtype, double* d_partials,
-                          int32_t* d_tickets, double* d_cent, unsigned long long* d_pub, unsigned long long seq);
+// pre-shape statistics of one or two clouds: two launches (sequence numbers seq_sum, seq), result published to host-mapped
+// {bits, seq} slots
+void launch_preshape_pair(hipStream_t st, const void* const d_xyz[2], const int64_t n[2], int dtype, Granule* d_rows,
+                          double* d_cent, unsigned long long* d_pub, unsigned long long seq_sum, unsigned long long seq);
 void launch_sum_columns(hipStream_t st, const double* d_partials, int n_rows, int n_cols, double* d_out);
 void launch_row_sums(hipStream_t st, const double* d_partials, int n_rows, int n_cols, double scale, double* d_out);
 

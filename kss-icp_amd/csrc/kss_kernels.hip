@@ -320,10 +320,9 @@ void launch_nn_sweep_list(hipStream_t st, int S, bool fma, const NNWork* d_work,
 // (c) correspondence reduce: merge the per-split keys, gather the matched target, accumulate the
 // 20 sums in f64 (wave shuffle reduce -> LDS -> one partial row per workgroup).
 // ---------------------------------------------------------------------------------------------
-// FUSE = true (small batches): the pair's last workgroup to finish also adds the pair's rows up and publishes the 20 sums
-// as {bits, seq} pairs into host-mapped memory -- one launch less per ICP pass than corr_reduce + finalize_sums.  The rows
-// are handed over as in grid_nn_kernel: write-through (sc1) stores, vmcnt(0), workgroup barrier, ONE agent-scope ticket;
-// the workgroup drawing the pair's last ticket reads every row with sc1 loads, in row order (bitwise reproducible).
+// FUSE = true (small batches): the pair's rows are handed over as granules (kss_device.hpp) and the workgroup of the pair's
+// first row adds them up and publishes the 20 sums as {bits, seq} pairs into host-mapped memory -- one launch less per ICP
+// pass than corr_reduce + finalize_sums.  (At most PUB_PAIRS pairs: one waiting workgroup per pair.)
 template <bool FUSE>
 __global__ __launch_bounds__(256) void corr_reduce_kernel(const RedWork* __restrict__ work,
                                                           const PairState* __restrict__ state,
@@ -333,10 +332,9 @@ __global__ __launch_bounds__(256) void corr_reduce_kernel(const RedWork* __restr
                                                           double max_d2, double* __restrict__ partials,
                                                           int32_t* __restrict__ idx_out,
                                                           float* __restrict__ d2_out, int index_in_w,
-                                                          const PairRed* __restrict__ pair_red, int32_t* __restrict__ pair_ticket,
+                                                          const PairRed* __restrict__ pair_red, Granule* __restrict__ rows,
                                                           unsigned long long* __restrict__ pub, unsigned long long seq) {
     __shared__ double sh[4][NSUMS];
-    __shared__ int s_last;
     const RedWork w = work[blockIdx.x];
     double acc[NSUMS];
 #pragma unroll
@@ -365,46 +363,15 @@ __global__ __launch_bounds__(256) void corr_reduce_kernel(const RedWork* __restr
         if (t0 < NSUMS) partials[(int64_t)w.partial_index * NSUMS + t0] = r;
     } else {
         const PairRed pr = pair_red[w.pair];
-        if (t0 < NSUMS) {
-            __hip_atomic_store(&partials[(int64_t)w.partial_index * NSUMS + t0], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-        if (t0 == 0) s_last = atomicAdd(&pair_ticket[w.pair], 1) == pr.count - 1;
-        __syncthreads();
-        if (!s_last) return;
-        // column sums of the pair's rows, fixed order: lane (g, c) adds rows g, g + 12, ... (sc1 loads, eight in flight),
-        // then the 12 group totals are added in group order -- a 100k-source pair has ~400 rows
+        if (t0 < NSUMS) row_put(rows + (int64_t)w.partial_index * NSUMS, t0, r, seq);
+        if (w.partial_index != pr.first) return;
+        // the pair's rows in a fixed order: lane (g, c) adds rows g, g + 12, ..., then the 12 group totals in group order --
+        // a 100k-source pair has ~400 rows
         __shared__ double shg[ROWSUM_GROUPS][NSUMS];
-        {
-            const int g = t0 / NSUMS, c = t0 % NSUMS;
-            if (g < ROWSUM_GROUPS) {
-                double a = 0.0;
-                for (int k = g; k < pr.count; k += 8 * ROWSUM_GROUPS) {
-                    double tt[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        tt[j] = k + j * ROWSUM_GROUPS < pr.count
-                                    ? __hip_atomic_load(&partials[(int64_t)(pr.first + k + j * ROWSUM_GROUPS) * NSUMS + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                    : 0.0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) a += tt[j];
-                }
-                shg[g][c] = a;
-            }
-        }
-        __syncthreads();
-        if (t0 < NSUMS) {
-            double v = 0.0;
-            for (int gg = 0; gg < ROWSUM_GROUPS; ++gg) v += shg[gg][t0];
-            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-            const unsigned long long vb = (unsigned long long)__double_as_longlong(v);
-            u32x4 o;
-            o.x = (unsigned)vb; o.y = (unsigned)(vb >> 32); o.z = (unsigned)seq; o.w = kss_mix3(o.x, o.y, o.z);
-            unsigned long long* dst = pub + 2 * ((int64_t)w.pair * NSUMS + t0);
-            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(o) : "memory");
-        }
-        if (t0 == 0) pair_ticket[w.pair] = 0;   // re-arm for the next pass (stream order makes it visible)
+        __shared__ int s_ok;
+        double v;
+        if (!rows_total<ROWSUM_GROUPS>(rows + (int64_t)pr.first * NSUMS, pr.count, seq, 1 << 20, shg, &s_ok, v)) return;
+        if (t0 < NSUMS) pub_put(pub, (int64_t)w.pair * NSUMS + t0, v, seq);
     }
 }
 
@@ -414,7 +381,7 @@ __global__ __launch_bounds__(256) void corr_reduce_kernel(const RedWork* __restr
 // 32 sources of one candidate x ALL targets, the (padded) target staged in LDS once, EIGHT lanes per source each sweeping an
 // eighth of it (sub-tile minima, then the exact arg-min inside the winning sub-tile: the scheme of nn_sweep_kernel, same
 // arithmetic, ties to the lowest index), merged by DPP; the correspondence sums of the 32 sources -> one row per workgroup;
-// the candidate's last workgroup (ticket) adds its rows in a fixed order and publishes the 20 sums.  Exact brute force:
+// the candidate's last workgroup adds its rows (granules) in a fixed order and publishes the 20 sums.  Exact brute force:
 // these candidates start from local minima of the rotation search, far from convergence -- no cell list pays here.
 // Eighth e of the target sits in LDS shifted by e float4 (the eighths are a multiple of 128 dwords apart: unshifted, the
 // eight addresses of a wave's read would hit the same banks).
@@ -533,79 +500,10 @@ __device__ __forceinline__ double cand_block_sum(double (&v)[NSUMS], double (*sh
     return out;
 }
 
-// Row hand-over of the candidate kernels WITHOUT a counter.  Every tile's row carries a tag -- the launch-and-pass number, stored
-// after the row's twenty values have been acknowledged -- and the candidate's workgroup 0 waits until every tile of the
-// candidate shows the tag of THIS pass before it adds the rows up.  (Round 3 handed rows over with one ticket per workgroup on
-// a per-candidate counter that had to be zero at rest.  With eight registrations in flight on contexts of their own, a debug
-// build counted tickets beyond the candidate's workgroups and rows of another pass in launches that ended normally: one
-// registration in ten then differed from its solitary run, some grossly.  Where the extra tickets came from was not found in
-// the time left; a tag cannot be left over, and a row of another pass cannot be added.)  Returns whether this workgroup adds
-// the candidate's rows up (false also when a row never came: bounded; the host's wait reports it).
-// stop_rec / stop_tag (resident kernel): the candidate's gate record; a stop order "at whatever pass" may have taken some of the
-// candidate's workgroups away before this pass, so a waiting lane looks at the record every 32 polls and gives up when it reads one.
-__device__ __forceinline__ bool cand_rows_ready(unsigned int* __restrict__ row_tag, int row0, int nrows, unsigned tag, bool reducer, int polls, int* s_flag,
-                                                const unsigned int* stop_rec = nullptr, unsigned stop_tag = 0) {
-    if (!reducer) return false;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    const int tid = threadIdx.x;
-    if (tid == 0) *s_flag = 1;
-    __syncthreads();
-    for (int r = tid; r < nrows; r += 256) {
-        int n = 0;
-        while (__hip_atomic_load(&row_tag[row0 + r], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != tag) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++n > polls) { *s_flag = 0; break; }
-            if (stop_rec && (n & 31) == 0) {
-                u32x4 v;
-                asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(stop_rec) : "memory");
-                if (v.w - kss_mix3(v.x, v.y, v.z) == stop_tag) { *s_flag = 0; break; }
-            }
-        }
-    }
-    __syncthreads();
-    return *s_flag != 0;
-}
-
-// A candidate's last workgroup: the column sums of its rows in a fixed order (lane (g, c) adds rows g, g + 12, ..., then the
-// 12 group totals in group order) and the publication of the 20 sums as checked {bits, launch number} granules.
-__device__ __forceinline__ void cand_rows_publish(const double* __restrict__ partials, int row0, int nrows, double (*shg)[NSUMS],
-                                                  unsigned long long* __restrict__ pub, int pair, unsigned long long seq) {
-    const int tid = threadIdx.x;
-    {
-        const int g = tid / NSUMS, c = tid % NSUMS;
-        if (g < ROWSUM_GROUPS) {
-            double a = 0.0;
-            for (int k = g; k < nrows; k += 8 * ROWSUM_GROUPS) {
-                double tt[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    tt[j] = k + j * ROWSUM_GROUPS < nrows
-                                ? __hip_atomic_load(&partials[(int64_t)(row0 + k + j * ROWSUM_GROUPS) * NSUMS + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                : 0.0;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) a += tt[j];
-            }
-            shg[g][c] = a;
-        }
-    }
-    __syncthreads();
-    if (tid < NSUMS) {
-        double v = 0.0;
-        for (int gg = 0; gg < ROWSUM_GROUPS; ++gg) v += shg[gg][tid];
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        const unsigned long long vb = (unsigned long long)__double_as_longlong(v);
-        u32x4 o;
-        o.x = (unsigned)vb; o.y = (unsigned)(vb >> 32); o.z = (unsigned)seq; o.w = kss_mix3(o.x, o.y, o.z);
-        unsigned long long* dst = pub + 2 * ((int64_t)pair * NSUMS + tid);
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(o) : "memory");
-    }
-}
-
 template <bool FMA>
 __global__ __launch_bounds__(256) void cand_pass_kernel(const PairState* __restrict__ state, const float4* __restrict__ src_in, float4* __restrict__ src_out,
                                                         const float4* __restrict__ tgt, int nt_pad, int ns, int blocks_per_pair, double max_d2,
-                                                        double* __restrict__ partials, unsigned int* __restrict__ row_tag,
-                                                        unsigned long long* __restrict__ pub, unsigned long long seq,
+                                                        Granule* __restrict__ rows, unsigned long long* __restrict__ pub, unsigned long long seq,
                                                         int32_t* __restrict__ idx_out, float* __restrict__ d2_out) {
     extern __shared__ float4 cand_tile[];
     __shared__ double sh[4][NSUMS];
@@ -643,31 +541,29 @@ __global__ __launch_bounds__(256) void cand_pass_kernel(const PairState* __restr
         if (d2_out) d2_out[gi] = d2;
     }
     const double r = cand_block_sum(acc, sh);
-    const int row0 = pair * blocks_per_pair;
-    if (tid < NSUMS) {
-        __hip_atomic_store(&partials[(int64_t)(row0 + blk) * NSUMS + tid], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(&row_tag[row0 + blk], (unsigned)seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    if (!cand_rows_ready(row_tag, row0, blocks_per_pair, (unsigned)seq, blk == blocks_per_pair - 1, 1 << 22, &s_last)) return;   // (the candidate's LAST workgroup waits: every other one was dispatched before it)
+    Granule* const crows = rows + (int64_t)pair * blocks_per_pair * NSUMS;
+    if (tid < NSUMS) row_put(crows + (int64_t)blk * NSUMS, tid, r, seq);
+    if (blk != blocks_per_pair - 1) return;   // (the candidate's LAST workgroup adds the rows up: every other one was dispatched before it)
+    // the candidate's rows in a fixed order (lane (g, c) adds rows g, g + 12, ..., then the 12 group totals in group order)
     __shared__ double shg[ROWSUM_GROUPS][NSUMS];
-    cand_rows_publish(partials, row0, blocks_per_pair, shg, pub, pair, seq);
+    double v;
+    if (!rows_total<ROWSUM_GROUPS>(crows, blocks_per_pair, seq, 1 << 22, shg, &s_last, v)) return;   // (bounded; the host's wait reports it)
+    if (tid < NSUMS) pub_put(pub, (int64_t)pair * NSUMS + tid, v, seq);
 }
 
 size_t cand_pass_lds_bytes(int nt_pad) { return (size_t)(16 * (((nt_pad + 15) / 16 + 7) / 8 * 8) + 24) * sizeof(float4); }   // 16 padded slices at stride chunk + 1, eight points of look-ahead
 int cand_pass_blocks_per_pair(int64_t ns) { return (int)((ns + CAND_SRC - 1) / CAND_SRC); }
 // false: the device refused the LDS size (the caller runs sweep + reduce)
 bool launch_cand_pass(hipStream_t st, bool fma, int npairs, const PairState* d_state, const float4* d_src_in, float4* d_src_out, const float4* d_tgt,
-                      int nt_pad, int ns, double max_d2, double* d_partials, unsigned int* d_row_tag, unsigned long long* d_pub, unsigned long long seq,
+                      int nt_pad, int ns, double max_d2, Granule* d_rows, unsigned long long* d_pub, unsigned long long seq,
                       int32_t* d_idx_out, float* d_d2_out) {
     const size_t bytes = cand_pass_lds_bytes(nt_pad);
     const void* fn = fma ? reinterpret_cast<const void*>(&cand_pass_kernel<true>) : reinterpret_cast<const void*>(&cand_pass_kernel<false>);
     if (bytes > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
     const int bpp = cand_pass_blocks_per_pair(ns);
     const dim3 grid((unsigned)(npairs * bpp)), block(256);
-    if (fma) hipLaunchKernelGGL(cand_pass_kernel<true>, grid, block, bytes, st, d_state, d_src_in, d_src_out, d_tgt, nt_pad, ns, bpp, max_d2, d_partials, d_row_tag, d_pub, seq, d_idx_out, d_d2_out);
-    else hipLaunchKernelGGL(cand_pass_kernel<false>, grid, block, bytes, st, d_state, d_src_in, d_src_out, d_tgt, nt_pad, ns, bpp, max_d2, d_partials, d_row_tag, d_pub, seq, d_idx_out, d_d2_out);
+    if (fma) hipLaunchKernelGGL(cand_pass_kernel<true>, grid, block, bytes, st, d_state, d_src_in, d_src_out, d_tgt, nt_pad, ns, bpp, max_d2, d_rows, d_pub, seq, d_idx_out, d_d2_out);
+    else hipLaunchKernelGGL(cand_pass_kernel<false>, grid, block, bytes, st, d_state, d_src_in, d_src_out, d_tgt, nt_pad, ns, bpp, max_d2, d_rows, d_pub, seq, d_idx_out, d_d2_out);
     return true;
 }
 
@@ -688,7 +584,6 @@ __global__ __launch_bounds__(256) void cand_resident_kernel(const CandArgs a) {
     __shared__ double shg[ROWSUM_GROUPS][NSUMS];
     __shared__ int s_ps[16];
     __shared__ int s_ctl[2];      // [0] the gate was answered, [1] every row of the candidate has come (workgroup 0)
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     const int pair = (int)blockIdx.x / a.wpp, wg = (int)blockIdx.x % a.wpp;
     const int tid = threadIdx.x, sub = tid & 7;
     const int nt_pad = a.nt_pad, ns = a.ns;
@@ -701,8 +596,8 @@ __global__ __launch_bounds__(256) void cand_resident_kernel(const CandArgs a) {
 #define KSS_CLAP(k) do { if (stamping) { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); if (pass > 0) a.stamps[(size_t)pair * 16 + (k)] += now_ - t_last; t_last = now_; } } while (0)
     KSS_CSTAMP(0);
     // leaving (every exit is uniform over the workgroup): the candidate's workgroup 0 -- the one that publishes its sums -- tells
-    // the host that nothing more will come for this candidate.  (No count of the workgroups that have left: like the row
-    // tickets it would have to be zero at rest, see cand_rows_ready.)
+    // the host that nothing more will come for this candidate.  (No count of the workgroups that have left: it would have to
+    // be zero at rest.)
     auto leave = [&]() {
         if (wg == 0 && tid == 0) res_store_exit_flag(a.exit_flags, pair, a.stamp0);
     };
@@ -791,7 +686,7 @@ __global__ __launch_bounds__(256) void cand_resident_kernel(const CandArgs a) {
                 if (fit && a.d2_out) a.d2_out[gi] = d2;
             }
             const double r = cand_block_sum(acc, sh);
-            if (tid < NSUMS) __hip_atomic_store(&a.partials[(int64_t)(row0 + blk) * NSUMS + tid], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid < NSUMS) row_put(a.rows + (int64_t)(row0 + blk) * NSUMS, tid, r, a.seq0 + (unsigned long long)pass);
             __syncthreads();               // (sh is written again by the next tile)
             }
             {
@@ -801,19 +696,22 @@ __global__ __launch_bounds__(256) void cand_resident_kernel(const CandArgs a) {
                 px[CAND_TPW - 1] = x0; py[CAND_TPW - 1] = y0; pz[CAND_TPW - 1] = z0;
             }
         }
-        if (tid < NSUMS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
         KSS_CLAP(10);
-        {
-            const unsigned tag = (unsigned)(a.seq0 + (unsigned long long)pass);
-            if (tid < CAND_TPW) {          // this workgroup's tiles: their rows are out
-                const int blk = wg + tid * a.wpp;
-                if (tid < a.tpw && blk < a.bpp) __hip_atomic_store(&a.row_tag[row0 + blk], tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            const bool sum_it = cand_rows_ready(a.row_tag, row0, a.bpp, tag, wg == 0, a.gate_polls, &s_ctl[1], a.gate + (size_t)pair * 32, a.stamp0 + RES_STAMP_ANY);
+        if (wg == 0) {   // uniform: the candidate's workgroup 0 adds its rows up (in a fixed order, as cand_pass_kernel does)
+            const unsigned long long seq = a.seq0 + (unsigned long long)pass;
+            // a stop order "at whatever pass" may have taken some of the candidate's workgroups away before this pass: every 32
+            // polls a waiting lane looks at the candidate's gate record and gives up when it reads one
+            const unsigned int* stop_rec = a.gate + (size_t)pair * 32;
+            auto stop = [&]() {
+                u32x4 g;
+                asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(g) : "v"(stop_rec) : "memory");
+                return g.w - kss_mix3(g.x, g.y, g.z) == a.stamp0 + RES_STAMP_ANY;
+            };
+            double v;
+            const bool sum_it = rows_total<ROWSUM_GROUPS>(a.rows + (int64_t)row0 * NSUMS, a.bpp, seq, a.gate_polls, shg, &s_ctl[1], v, stop);
             KSS_CLAP(11);
-            if (sum_it) cand_rows_publish(a.partials, row0, a.bpp, shg, a.pub, pair, a.seq0 + (unsigned long long)pass);
-            else if (wg == 0) { KSS_CSTAMP(15); leave(); return; }   // stopped, or a row never came (bounded wait; the host's wait reports it)
+            if (!sum_it) { KSS_CSTAMP(15); leave(); return; }   // stopped, or a row never came (bounded wait; the host's wait reports it)
+            if (tid < NSUMS) pub_put(a.pub, (int64_t)pair * NSUMS + tid, v, seq);
         }
         KSS_CLAP(12);
         if (stamping) a.stamps[(size_t)pair * 16 + 7] = (unsigned long long)(pass + 1);
@@ -856,17 +754,17 @@ void launch_corr_reduce(hipStream_t st, const RedWork* d_work, int n_work, const
                         double max_d2, double* d_partials, int32_t* d_idx_out, float* d_d2_out, int index_in_w) {
     if (n_work <= 0) return;
     hipLaunchKernelGGL(corr_reduce_kernel<false>, dim3(n_work), dim3(256), 0, st, d_work, d_state, d_src, d_tgt4,
-                       d_keys, max_d2, d_partials, d_idx_out, d_d2_out, index_in_w, (const PairRed*)nullptr, (int32_t*)nullptr,
+                       d_keys, max_d2, d_partials, d_idx_out, d_d2_out, index_in_w, (const PairRed*)nullptr, (Granule*)nullptr,
                        (unsigned long long*)nullptr, 0ull);
 }
 
 void launch_corr_reduce_publish(hipStream_t st, const RedWork* d_work, int n_work, const PairState* d_state,
                                 const float4* d_src, const float4* d_tgt4, const unsigned long long* d_keys,
-                                double max_d2, double* d_partials, int32_t* d_idx_out, float* d_d2_out, int index_in_w,
-                                const PairRed* d_pair_red, int32_t* d_pair_ticket, unsigned long long* d_pub, unsigned long long seq) {
+                                double max_d2, Granule* d_rows, int32_t* d_idx_out, float* d_d2_out, int index_in_w,
+                                const PairRed* d_pair_red, unsigned long long* d_pub, unsigned long long seq) {
     if (n_work <= 0) return;
     hipLaunchKernelGGL(corr_reduce_kernel<true>, dim3(n_work), dim3(256), 0, st, d_work, d_state, d_src, d_tgt4,
-                       d_keys, max_d2, d_partials, d_idx_out, d_d2_out, index_in_w, d_pair_red, d_pair_ticket, d_pub, seq);
+                       d_keys, max_d2, (double*)nullptr, d_idx_out, d_d2_out, index_in_w, d_pair_red, d_rows, d_pub, seq);
 }
 
 // idx-driven variant behind kss_cov(): packed float3 clouds + an index array
@@ -915,14 +813,15 @@ void launch_finalize_sums(hipStream_t st, const PairRed* d_pairs, int n_pairs, c
 // (a) KSS pre-shape statistics (initRegistration_MiddleAlign, initRegistrationKSS.hpp:144-207): centroid and mean
 // distance to the centroid of ONE OR TWO clouds (source and target of a registration) in TWO launches and no stream
 // synchronisation:
-//   launch A  every workgroup sums its slice (f64) -> one partial row; the workgroup that draws the cloud's last
-//             ticket adds the rows in row order and stores centroid = sum / n;
+//   launch A  every workgroup sums its slice (f64) -> one partial row; the cloud's first workgroup adds the rows in row
+//             order and stores centroid = sum / n;
 //   launch B  every workgroup sums sqrt(|p - centroid|^2) over the SAME slice (one IEEE f64 sqrt per point; the slice is
-//             still in that XCD's L2 at <= a few million points) -> partial row; the last workgroup of the cloud adds
-//             the rows and publishes {centroid, radius sum} as {bits, sequence number} 16-byte pairs into host-mapped
+//             still in that XCD's L2 at <= a few million points) -> partial row; the cloud's first workgroup adds the
+//             rows and publishes {centroid, radius sum} as {bits, sequence number} 16-byte pairs into host-mapped
 //             memory, where the host spins on the sequence numbers (as the ICP loop does).
 // A kernel boundary (~2 us) is cheaper than a grid-wide barrier (4-7 us, MI355X_MICROARCH.md price list) and has no
-// co-residency requirement.  Row hand-off as in grid_nn_kernel: sc1 stores, vmcnt(0), workgroup barrier, one ticket.
+// co-residency requirement.  Rows are handed over as granules (kss_device.hpp), each launch under its own sequence number;
+// one waiting workgroup per cloud, two at most.
 // The block decomposition of a cloud depends on its size only, so "both clouds in one call" and "one call per cloud"
 // give the same bits.
 // ---------------------------------------------------------------------------------------------
@@ -934,11 +833,11 @@ int stream_blocks(int64_t n) {   // streaming kernels without a hand-over: 256 C
 }
 
 int preshape_blocks(int64_t n) {
-    // >= 8 points per lane before another workgroup is added: every workgroup costs a row hand-over and a ticket on the
-    // cloud's counter (one counter takes ~12 ns per ticket: 2048 workgroups on a 1M-point cloud spent 25 us per launch
-    // queueing there).  Capped at 256 CUs x 8 workgroups, grid-stride beyond (64M points: 2048 workgroups, as before).
-    // (round 3: 16 points per lane -- 245 workgroups and tickets per 1M-point cloud instead of 489: both launches of C4's two
-    // clouds are held by their tails -- the serial tickets, then the last workgroup's row sum -- not by the 24 MB they stream)
+    // >= 16 points per lane before another workgroup is added: every workgroup costs a row hand-over (round 3, when each
+    // also drew a ticket on one counter per cloud at ~12 ns each: 2048 workgroups on a 1M-point cloud spent 25 us per launch
+    // queueing there; 245 workgroups per 1M-point cloud instead of 489 shortened both launches of C4's two clouds, which
+    // were held by their tails rather than by the 24 MB they stream).  Capped at 256 CUs x 8 workgroups, grid-stride beyond
+    // (64M points: 2048 workgroups).
     int64_t b = (n + 4095) / 4096;
     if (b > 2048) b = 2048;
     if (b < 1) b = 1;
@@ -1019,25 +918,24 @@ __device__ __forceinline__ double pre_radius_f32v(const float* __restrict__ xyz,
     return acc;
 }
 
-// hand the workgroup's row over and tell whether this workgroup drew the cloud's last ticket (then every row is visible
-// to its sc1 loads)
+// the cloud's first workgroup: lane t adds rows t, t + 256, ... of each of the NV columns (granules, in row order); false
+// when a row never came
 template <int NV>
-__device__ __forceinline__ bool pre_row_handoff(double r, double* __restrict__ row, int32_t* __restrict__ ticket, int nb, int* s_last) {
-    if (threadIdx.x < NV) {
-        __hip_atomic_store(&row[threadIdx.x], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+__device__ __forceinline__ bool pre_rows_take(const Granule* __restrict__ rows, int nb, unsigned long long seq, double (&t)[NV], int* s_ok) {
+    if (threadIdx.x == 0) *s_ok = 1;
     __syncthreads();
-    if (threadIdx.x == 0) *s_last = atomicAdd(ticket, 1) == nb - 1;
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+        if (!rows_take(rows, 4, k, (int)threadIdx.x, 256, nb, seq, 1 << 20, t[k])) *s_ok = 0;
     __syncthreads();
-    return *s_last != 0;
+    return *s_ok != 0;
 }
 
-// launch A.  partials: 4 doubles per workgroup of the launch; tickets[0..1]; cent: 4 doubles per cloud.
-__global__ __launch_bounds__(256) void preshape_sum_kernel(PreArgs a, double* __restrict__ partials, int32_t* __restrict__ tickets,
-                                                           double* __restrict__ cent) {
+// launch A.  rows: 4 granules per workgroup of the launch; cent: per cloud the centroid and, in the fourth word, the number of
+// the launch that stored it (a reducer that gave up stores nothing, and launch B then publishes nothing).
+__global__ __launch_bounds__(256) void preshape_sum_kernel(PreArgs a, Granule* __restrict__ rows, double* __restrict__ cent, unsigned long long seq) {
     __shared__ double sh[4][3];
-    __shared__ int s_last;
+    __shared__ int s_ok;
     const int ci = (a.nclouds > 1 && (int)blockIdx.x >= a.c[1].first_block) ? 1 : 0;
     const PreCloud cl = a.c[ci];
     const int lb = (int)blockIdx.x - cl.first_block, nb = cl.n_blocks;
@@ -1046,24 +944,21 @@ __global__ __launch_bounds__(256) void preshape_sum_kernel(PreArgs a, double* __
     else if (cl.kind == 2) pre_sum_f32v((const float*)cl.xyz, cl.n, lb, nb, acc);
     else pre_sum_scalar((const float*)cl.xyz, cl.n, lb, nb, acc);
     const double r = block_sum<3>(acc, sh);
-    if (!pre_row_handoff<3>(r, partials + (int64_t)blockIdx.x * 4, tickets + ci, nb, &s_last)) return;
+    if (threadIdx.x < 3) row_put(rows + (int64_t)blockIdx.x * 4, threadIdx.x, r, seq);
+    if (lb != 0) return;
     // centroid = (sum over the cloud's rows, lanes striding the rows, then a fixed-order block sum) / n
-    double t[3] = {0.0, 0.0, 0.0};
-    for (int rr = threadIdx.x; rr < nb; rr += 256)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            t[k] += __hip_atomic_load(&partials[(int64_t)(cl.first_block + rr) * 4 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    double t[3];
+    if (!pre_rows_take<3>(rows + (int64_t)cl.first_block * 4, nb, seq, t, &s_ok)) return;
     const double v = block_sum<3>(t, sh);
     if (threadIdx.x < 3) cent[ci * 4 + threadIdx.x] = v / (double)cl.n;
-    if (threadIdx.x == 0) tickets[ci] = 0;   // re-armed for the next call (stream order)
+    if (threadIdx.x == 3) reinterpret_cast<unsigned long long*>(cent)[ci * 4 + 3] = seq;
 }
 
-// launch B.  tickets[2..3]; pub: host-mapped {bits, seq} pairs, slots ci * 4 + {0,1,2: centroid, 3: sum of radii}.
-__global__ __launch_bounds__(256) void preshape_radius_kernel(PreArgs a, double* __restrict__ partials, int32_t* __restrict__ tickets,
-                                                              const double* __restrict__ cent, unsigned long long* __restrict__ pub,
-                                                              unsigned long long seq) {
+// launch B.  pub: host-mapped {bits, seq} pairs, slots ci * 4 + {0,1,2: centroid, 3: sum of radii}.
+__global__ __launch_bounds__(256) void preshape_radius_kernel(PreArgs a, Granule* __restrict__ rows, const double* __restrict__ cent,
+                                                              unsigned long long seq_sum, unsigned long long* __restrict__ pub, unsigned long long seq) {
     __shared__ double sh[4][1];
-    __shared__ int s_last;
+    __shared__ int s_ok;
     const int ci = (a.nclouds > 1 && (int)blockIdx.x >= a.c[1].first_block) ? 1 : 0;
     const PreCloud cl = a.c[ci];
     const int lb = (int)blockIdx.x - cl.first_block, nb = cl.n_blocks;
@@ -1073,30 +968,23 @@ __global__ __launch_bounds__(256) void preshape_radius_kernel(PreArgs a, double*
     else if (cl.kind == 2) acc[0] = pre_radius_f32v((const float*)cl.xyz, cl.n, lb, nb, cx, cy, cz);
     else acc[0] = pre_radius_scalar((const float*)cl.xyz, cl.n, lb, nb, cx, cy, cz);
     const double r = block_sum<1>(acc, sh);
-    if (!pre_row_handoff<1>(r, partials + (int64_t)blockIdx.x * 4, tickets + 2 + ci, nb, &s_last)) return;
-    double t[1] = {0.0};
-    for (int rr = threadIdx.x; rr < nb; rr += 256)
-        t[0] += __hip_atomic_load(&partials[(int64_t)(cl.first_block + rr) * 4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) row_put(rows + (int64_t)blockIdx.x * 4, 0, r, seq);
+    if (lb != 0 || reinterpret_cast<const unsigned long long*>(cent)[ci * 4 + 3] != seq_sum) return;   // (no centroid of launch A: publish nothing)
+    double t[1];
+    if (!pre_rows_take<1>(rows + (int64_t)cl.first_block * 4, nb, seq, t, &s_ok)) return;
     const double v = block_sum<1>(t, sh);
     if (threadIdx.x < 4) {
         const double o = threadIdx.x == 0 ? v : (threadIdx.x == 1 ? cx : (threadIdx.x == 2 ? cy : cz));
-        const int slot = ci * 4 + (threadIdx.x == 0 ? 3 : (int)threadIdx.x - 1);
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        const unsigned long long vb = (unsigned long long)__double_as_longlong(o);
-        u32x4 w;
-        w.x = (unsigned)vb; w.y = (unsigned)(vb >> 32); w.z = (unsigned)seq; w.w = kss_mix3(w.x, w.y, w.z);
-        unsigned long long* dst = pub + 2 * slot;
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(w) : "memory");
+        pub_put(pub, ci * 4 + (threadIdx.x == 0 ? 3 : (int)threadIdx.x - 1), o, seq);
     }
-    if (threadIdx.x == 0) tickets[2 + ci] = 0;
 }
 
 static bool f32_vector_ok(const void* p, int64_t n) { return ((uintptr_t)p & 15u) == 0 && n >= 1024; }
 
-// d_partials: 4 doubles per workgroup (preshape_blocks(n0) + preshape_blocks(n1)); d_tickets: 4 zeroed ints;
-// d_cent: 8 doubles; d_pub: 8 host-mapped {bits, seq} slots.  d_xyz[1] == nullptr: one cloud.
-void launch_preshape_pair(hipStream_t st, const void* const d_xyz[2], const int64_t n[2], int dtype, double* d_partials,
-                          int32_t* d_tickets, double* d_cent, unsigned long long* d_pub, unsigned long long seq) {
+// d_rows: 4 granules per workgroup (preshape_blocks(n0) + preshape_blocks(n1)); d_cent: 8 doubles; d_pub: 8 host-mapped
+// {bits, seq} slots.  d_xyz[1] == nullptr: one cloud.
+void launch_preshape_pair(hipStream_t st, const void* const d_xyz[2], const int64_t n[2], int dtype, Granule* d_rows,
+                          double* d_cent, unsigned long long* d_pub, unsigned long long seq_sum, unsigned long long seq) {
     PreArgs a;
     a.nclouds = d_xyz[1] ? 2 : 1;
     int first = 0;
@@ -1110,8 +998,8 @@ void launch_preshape_pair(hipStream_t st, const void* const d_xyz[2], const int6
         c.pad = 0;
         first += c.n_blocks;
     }
-    hipLaunchKernelGGL(preshape_sum_kernel, dim3(first), dim3(256), 0, st, a, d_partials, d_tickets, d_cent);
-    hipLaunchKernelGGL(preshape_radius_kernel, dim3(first), dim3(256), 0, st, a, d_partials, d_tickets, (const double*)d_cent, d_pub, seq);
+    hipLaunchKernelGGL(preshape_sum_kernel, dim3(first), dim3(256), 0, st, a, d_rows, d_cent, seq_sum);
+    hipLaunchKernelGGL(preshape_radius_kernel, dim3(first), dim3(256), 0, st, a, d_rows, (const double*)d_cent, seq_sum, d_pub, seq);
 }
 
 // out[c] = sum over rows of partials[r][c], n_cols <= NSUMS: lanes stride over the rows (many loads in flight)

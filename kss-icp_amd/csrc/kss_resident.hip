@@ -36,9 +36,6 @@
 
 namespace kss {
 
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct ResLds {
     const float* t3;                                     // targets of the pair in cell order: x, y, z of point k at [3k .. 3k + 2]
     const unsigned short* tab;                           // [rows][tw]: start of x-cell (j << xs) of the row, [tw - 1] = end of the row
@@ -653,13 +650,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_icp_kernel(const ResA
                 v += acc;
             }
             if (!full && (tid == 17 || tid == 18)) v = 0.0;
-            // {bits(sum), sequence number, check}: ONE aligned 16-byte system-scope store per sum into host-mapped memory;
-            // the host takes a slot when the number matches and the check word fits the other three
-            const unsigned long long vb = (unsigned long long)__double_as_longlong(v);
-            u32x4 o;
-            o.x = (unsigned)vb; o.y = (unsigned)(vb >> 32); o.z = (unsigned)seq_k; o.w = kss_mix3(o.x, o.y, o.z);
-            unsigned long long* dst = a.pub + 2 * ((int64_t)pi * NSUMS + tid);
-            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(o) : "memory");
+            pub_put(a.pub, (int64_t)pi * NSUMS + tid, v, seq_k);
         }
         KSS_RLAP(pass > 0 ? 12 : 6);
         if (fit || (a.split_at > 0 && pass + 1 == a.split_at)) {   // the fitness pass is the last one; so is pass split_at - 1 of a split batch's first launch

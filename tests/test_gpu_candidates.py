@@ -133,7 +133,8 @@ print("RESULT" + json.dumps(out))
 def test_registrations_under_load_equal_the_solitary_one():
     """One context registers the same pair 300 times while five threads register other pairs on contexts of their own
     (tools/load_repro.py).  Round 3: with rows handed over by per-candidate ticket counters, one registration in ten differed
-    from the solitary result under exactly this load; rows are now handed over by launch-and-pass tags.
+    from the solitary result under exactly this load; rows are now granules tagged with the launch
+    and pass, and no ticket counter is left anywhere.
     Every registration must give the solitary run's bits."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "load_repro.py"), "300", "register", "5"], capture_output=True, text=True,
                        timeout=600, env=dict(os.environ))

@@ -167,6 +167,38 @@ def test_grid_batch_matches_brute_batch_and_oracle(ctx, O, pkg):
         assert np.abs(g2[i].matrix() - b2[i].matrix()).max() < 1e-6 and abs(g2[i].last_mse - b2[i].last_mse) < 1e-12
 
 
+def test_batch_rows_added_in_the_pass_or_after_it_same_bits():
+    """A batched cell-list pass hands each pair's rows to the pair's first workgroup inside the launch while the batch has at
+    most one pair per compute unit, and to a finalize launch right after it otherwise (kss_grid.hip, gridb_finalize_kernel).
+    Four pairs registered as a batch of their own and again inside a batch of 320 (more pairs than the MI355X's 256 compute
+    units, padded with small pairs) give the same records bit for bit.  KSS_RESIDENT=0: the launch-per-pass engine."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = r"""
+import sys, json, numpy as np
+sys.path.insert(0, %r)
+import __graft_entry__ as g
+pkg = g.load_package(); S = pkg.synth; ctx = pkg.Context(0)
+rng = np.random.default_rng(11)
+few = [S.make_pair(700 + i, 6000 + 3000 * i, R=S.rot_axis_angle(rng.normal(size=3), np.deg2rad(4.0 + 2 * i)),
+                   t=tuple(rng.normal(scale=0.01, size=3)), shape="bumpy") for i in range(4)]
+pad = [S.make_pair(800 + i, 700, R=S.rot_axis_angle(rng.normal(size=3), np.deg2rad(3.0)), shape="sphere") for i in range(316)]
+def run(pairs, **kw):
+    src = np.concatenate([p[0] for p in pairs]); tgt = np.concatenate([p[1] for p in pairs])
+    so = np.concatenate([[0], np.cumsum([len(p[0]) for p in pairs])]).astype(np.int64)
+    to = np.concatenate([[0], np.cumsum([len(p[1]) for p in pairs])]).astype(np.int64)
+    res = ctx.icp_batch(src, so, tgt, to, ctx.icp_params(nn_mode=pkg.NN_GRID, **kw))
+    return [[list(r.T), r.iterations, r.state, r.converged, r.fitness, r.last_mse] for r in res[:len(few)]]
+out = [[run(few, **kw), run(few + pad, **kw)] for kw in (dict(), dict(max_iterations=6, fixed_iterations=1))]
+print("RESULT" + json.dumps(out))
+""" % root
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, KSS_RESIDENT="0"))
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT")][0][6:])
+    for alone, padded in out:
+        assert padded == alone
+
+
 def test_non_finite_coordinates_are_contained(ctx, pkg):
     """Non-finite input must not hang or fault the search: a target with an infinite coordinate is rejected by the
     cell-list build, a NaN source point matches nothing (it is dropped from the sums) and the rest registers normally."""

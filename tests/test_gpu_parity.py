@@ -549,10 +549,10 @@ print("RESULT" + json.dumps(out))
     assert res["lost"] == res["default"] and res["lost_late"] == res["default"]
 
 
-def test_large_pair_rows_tagged_or_ticketed_same_bits(pkg):
+def test_large_pair_rows_same_bits_under_every_switch(pkg):
     """Pairs with more rows than compute units (300k points: 586 rows) hand their rows over as tagged granules to a polling
-    reducer since round 3 (before: store + ticket, the last workgroup adds 586 rows); the two forms, gated or not, must give
-    the same registration bit for bit -- the additions are the same in the same order."""
+    reducer; gated or not, with either scan of the cell table and either way of taking the target's box, the registration
+    is the same bit for bit -- the additions are the same in the same order."""
     import subprocess, sys, json
     code = r"""
 import sys, json, numpy as np
@@ -567,8 +567,7 @@ for kw in (dict(max_iterations=7, fixed_iterations=1), dict()):
 print("RESULT" + json.dumps(out))
 """ % ROOT
     res = {}
-    for name, extra in {"default": {}, "ticket": {"KSS_TAGGED_ROWS_MAX": "256"}, "ticket_all": {"KSS_TAGGED_ROWS": "0"},
-                        "ungated": {"KSS_GATED": "0"}, "ungated_ticket": {"KSS_GATED": "0", "KSS_TAGGED_ROWS_MAX": "256"},
+    for name, extra in {"default": {}, "ungated": {"KSS_GATED": "0"},
                         "library_scan": {"KSS_SCAN_LIB": "1"},   # (the cell table's scan by rocPRIM instead of kss_grid.hip's own: same starts)
                         "box_by_copy": {"KSS_BBOX_HOST": "0"}}.items():
         r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=dict(os.environ, **extra))
@@ -601,7 +600,7 @@ def test_a_new_context_never_takes_an_old_contexts_rows(pkg):
 
 
 def test_growing_registrations_on_one_context(pkg):
-    """Work buffers that are zero at rest (cell counters, tickets, the fallback list's length) across registrations of
+    """Work buffers that are zero at rest (cell counters, the fallback list's length) across registrations of
     growing and shrinking size on ONE context -- the sequence that once left the tail of a re-allocated counter buffer
     uninitialised (DESIGN.md, incidents).  KSS_COUNTS_CHECK makes the library verify the counters before every build;
     every result must equal the same registration on a fresh context."""

@@ -28,7 +28,7 @@ print('entries', k, 'nonzero', int((buf[:max(k,0)] != 0).sum()))
 st = buf[:k].reshape(-1, 16).astype(np.int64)
 st = st[st[:, 0] > 0]
 print("workgroups:", len(st), " kernel span %.1f us" % ((st[:, [0, 1, 2]].max() - st[:, 0].min()) / 100.0))
-seq = [(0, "start"), (13, "loads in"), (14, "phase A"), (15, "phase B"), (1, "searched"), (2, "row ready"), (3, "ticketed")]
+seq = [(0, "start"), (13, "loads in"), (14, "phase A"), (15, "phase B"), (1, "searched"), (2, "row ready"), (3, "row handed over")]
 prev = None
 for i, nm in seq:
     ok = st[:, i] > 0

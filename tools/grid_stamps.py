@@ -25,7 +25,7 @@ st = buf[:k].reshape(-1, 16).astype(np.int64)
 st = st[st[:, 0] > 0]
 t0 = st[:, 0].min()
 us = lambda a: (a - t0) / 100.0
-names = [(0, "start"), (13, "loads issued"), (9, "gate open"), (14, "phase A"), (5, "B enter"), (8, "B answered"), (15, "phase B"), (1, "searched"), (2, "row ready"), (3, "ticketed")]
+names = [(0, "start"), (13, "loads issued"), (9, "gate open"), (14, "phase A"), (5, "B enter"), (8, "B answered"), (15, "phase B"), (1, "searched"), (2, "row ready"), (3, "row handed over")]
 print("workgroups:", len(st))
 for i, nm in names:
     v = us(st[:, i])
