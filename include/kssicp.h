@@ -263,6 +263,38 @@ int kss_icp_p2l(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt, in
 int kss_icp_p2l_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
                     const kss_icp_params *p, kss_icp_result *res);
 
+/* ---- trimmed ICP for one partly overlapping pair (Chetverikov et al., TrICP), both metrics ----
+ * One pass, with the exact NN target idx[i] and float d2[i] of every source as the NN pass writes them:
+ *   candidates  0 <= d2[i] <= max_d2 (ordered compares in double: a NaN is none; -0.0f counts as +0.0f), m of them;
+ *   rank        k = kss_trim_rank(m, overlap) = m == 0 ? 0 : max(1, (int64)ceil(overlap * (double)m)), one f64 multiplication;
+ *   cut         tau = the k-th smallest candidate d2 (exact; m == 0: tau = 0 and nothing is kept);
+ *   kept        the candidates with d2 <= tau -- ties at tau are all kept, so kept >= k; the plane metric also asks for a
+ *               finite normal, as kss_icp_p2l does (the rank is taken on d2 alone);
+ *   sums        over the kept set, f64, fixed order that depends on ns only: the KSS_NSUMS record ([17], [18], [19] = 0) solved
+ *               by kss_rigid_from_sums (point metric), or the KSS_P2L_NSUMS record solved by kss_rigid_from_p2l_sums (plane).
+ * The loop around it is kss_icp_p2l's: PCL's criteria on MSE = sum d2 kept / kept, fewer than min_correspondences kept ->
+ * KSS_STATE_NO_CORRESPONDENCES, a singular plane system -> KSS_STATE_DEGENERATE, fitness over ALL sources.  overlap = 1 keeps
+ * every candidate: with the plane metric that is kss_icp_p2l bit for bit.  overlap outside (0, 1] is KSS_ERR_ARG. */
+enum { KSS_METRIC_POINT = 0, KSS_METRIC_PLANE = 1 };
+#define KSS_TRIM_NINFO 4   /* {m candidates, k rank, tau widened to double, kept} */
+/* host only, no context */
+int kss_trim_rank(int64_t m, double overlap, int64_t *k);
+/* the selection alone, for n squared distances: info[3] = the number of candidates <= tau */
+int kss_trim_threshold(kss_ctx *ctx, const float *d2, int64_t n, double max_d2, double overlap, double info[KSS_TRIM_NINFO]);
+int kss_trim_threshold_dev(kss_ctx *ctx, const float *d_d2, int64_t n, double max_d2, double overlap, double info[KSS_TRIM_NINFO]);
+typedef struct {
+    double  overlap;      /* share of the candidates kept per pass, 0 < overlap <= 1 */
+    int     metric;       /* KSS_METRIC_POINT or KSS_METRIC_PLANE */
+    double *trace_trim;   /* p->trace_cap * KSS_TRIM_NINFO doubles, row i beside trace_sums row i; may be NULL */
+} kss_trim_params;
+/* tgt_normals: plane metric: nt*3 floats or NULL (computed as in kss_icp_p2l); point metric: must be NULL.
+ * p->trace_sums rows hold KSS_NSUMS (point) or KSS_P2L_NSUMS (plane) doubles.  In trace_trim and last_info (may be NULL: the
+ * last pass's record) [3] is the number of correspondences the step was computed from.  p->allreduce must be NULL. */
+int kss_icp_trimmed(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt, int64_t nt, const float *tgt_normals,
+                    const kss_icp_params *p, const kss_trim_params *tp, kss_icp_result *res, double last_info[KSS_TRIM_NINFO]);
+int kss_icp_trimmed_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
+                        const kss_icp_params *p, const kss_trim_params *tp, kss_icp_result *res, double last_info[KSS_TRIM_NINFO]);
+
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);
 int kss_transform_apply_dev(kss_ctx *ctx, const float T[16], const double *d_in, int64_t n, double *d_out);

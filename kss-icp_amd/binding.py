@@ -18,6 +18,8 @@ NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2
 P2L_NSUMS = 32           # KSS_P2L_NSUMS: the point-to-plane sums record
 STATE_DEGENERATE = 6     # KSS_STATE_DEGENERATE: a point-to-plane pass met a singular system
 ERR_DEGENERATE = -7      # KSS_ERR_DEGENERATE
+METRIC_POINT, METRIC_PLANE = 0, 1   # KSS_METRIC_*: the step of kss_icp_trimmed
+TRIM_NINFO = 4           # KSS_TRIM_NINFO: {m candidates, k rank, tau, kept} of a trimmed pass
 F32, F64 = 0, 1
 
 # every symbol include/kssicp.h declares (checked by tests/test_abi.py against the header text)
@@ -30,6 +32,7 @@ SYMBOLS = [
     "kss_icp_dev", "kss_icp_batch", "kss_icp_batch_dev", "kss_transform_apply", "kss_transform_apply_dev",
     "kss_pcr_qm", "kss_register", "kss_register_batch", "kss_gather_results", "kss_rccl_allreduce_sum", "kss_transform_apply_f32", "kss_downsample_fps", "kss_downsample_aivs", "kss_downsample_aivs_pair", "kss_downsample_octree", "kss_knn", "kss_knn_dev", "kss_normals", "kss_normals_orient",
     "kss_p2l_sums", "kss_p2l_sums_dev", "kss_rigid_from_p2l_sums", "kss_icp_p2l", "kss_icp_p2l_dev",
+    "kss_trim_rank", "kss_trim_threshold", "kss_trim_threshold_dev", "kss_icp_trimmed", "kss_icp_trimmed_dev",
 ]
 
 
@@ -60,6 +63,10 @@ class IcpParams(C.Structure):
                 ("trace_cap", C.c_int), ("trace_n", C.POINTER(C.c_int)),
                 ("fitness_idx", C.POINTER(C.c_int32)), ("fitness_d2", C.POINTER(C.c_float)),
                 ("allreduce", ALLREDUCE_FN), ("allreduce_user", C.c_void_p)]
+
+
+class TrimParams(C.Structure):
+    _fields_ = [("overlap", C.c_double), ("metric", C.c_int), ("trace_trim", C.POINTER(C.c_double))]
 
 
 class IcpResult(C.Structure):
@@ -148,6 +155,11 @@ def load_library():
     L.kss_rigid_from_p2l_sums.argtypes = [vp, vp]
     for n in ("kss_icp_p2l", "kss_icp_p2l_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    L.kss_trim_rank.argtypes = [i64, dbl, C.POINTER(i64)]
+    for n in ("kss_trim_threshold", "kss_trim_threshold_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, dbl, dbl, vp]
+    for n in ("kss_icp_trimmed", "kss_icp_trimmed_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(TrimParams), C.POINTER(IcpResult), vp]
     for n in ("kss_rotation_search", "kss_rotation_search_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, dbl, vp, i64, C.POINTER(C.c_int)]
     L.kss_grid_angles.argtypes = [dbl, vp, C.c_int]
@@ -221,6 +233,16 @@ def rigid_from_sums(sums):
     if rc != 0:
         raise KssError(rc, "kss_rigid_from_sums")
     return T.reshape(4, 4)
+
+
+def trim_rank(m, overlap):
+    """kss_trim_rank: the rank k of trimmed ICP for m candidates (host only)."""
+    L = load_library()
+    k = C.c_int64(0)
+    rc = L.kss_trim_rank(int(m), float(overlap), C.byref(k))
+    if rc != 0:
+        raise KssError(rc, "kss_trim_rank")
+    return k.value
 
 
 def rigid_from_p2l_sums(sums):
@@ -476,6 +498,78 @@ class Context:
                                          C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(res)),
                   "kss_icp_p2l_dev")
         return res
+
+    # ---- trimmed ICP
+    def trim_threshold(self, d2, max_d2=1.0, overlap=0.5):
+        """kss_trim_threshold: {m, k, tau, kept} of the squared distances d2 (float32) as a float64 array of TRIM_NINFO."""
+        d = np.ascontiguousarray(d2, dtype=np.float32).reshape(-1)
+        info = np.zeros(TRIM_NINFO, np.float64)
+        self._chk(self.L.kss_trim_threshold(self.h, _p(d), len(d), float(max_d2), float(overlap), _p(info)), "kss_trim_threshold")
+        return info
+
+    def trim_threshold_dev(self, d_d2, n, max_d2=1.0, overlap=0.5):
+        info = np.zeros(TRIM_NINFO, np.float64)
+        self._chk(self.L.kss_trim_threshold_dev(self.h, C.c_void_p(int(d_d2)), int(n), float(max_d2), float(overlap), _p(info)),
+                  "kss_trim_threshold_dev")
+        return info
+
+    def icp_trimmed(self, src, tgt, normals=None, overlap=0.5, metric=METRIC_POINT, params=None, trace_cap=0, fitness_corr=False):
+        """Trimmed ICP (kss_icp_trimmed): per pass the closest `overlap` share of the correspondences within max_corr_dist is
+        kept.  metric METRIC_POINT (normals must be None) or METRIC_PLANE (normals nt x 3, or None to have them computed).
+        The result dictionary of icp_p2l() plus trace_trim (one {m, k, tau, kept} row per traced pass) and trim_info (the last
+        pass's); trace_sums rows hold NSUMS or P2L_NSUMS doubles by metric."""
+        s, t = _f32(src), _f32(tgt)
+        nr = _f32(normals) if normals is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        p = params if params is not None else self.icp_params()
+        tp = TrimParams(float(overlap), int(metric), None)
+        res = IcpResult()
+        info = np.zeros(TRIM_NINFO, np.float64)
+        tr = None
+        fc = None
+        if fitness_corr:
+            fc = (np.full(len(s), -1, np.int32), np.full(len(s), np.nan, np.float32))
+            p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
+            p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
+        if trace_cap > 0:
+            sums = np.zeros((trace_cap, P2L_NSUMS if metric == METRIC_PLANE else NSUMS), np.float64)
+            tk = np.zeros((trace_cap, 16), np.float32)
+            tt = np.zeros((trace_cap, TRIM_NINFO), np.float64)
+            n = C.c_int(0)
+            p.trace_sums = sums.ctypes.data_as(C.POINTER(C.c_double))
+            p.trace_Tk = tk.ctypes.data_as(C.POINTER(C.c_float))
+            p.trace_cap = trace_cap
+            p.trace_n = C.pointer(n)
+            tp.trace_trim = tt.ctypes.data_as(C.POINTER(C.c_double))
+            tr = (sums, tk, n, tt)
+        try:
+            self._chk(self.L.kss_icp_trimmed(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(tp), C.byref(res),
+                                             _p(info)), "kss_icp_trimmed")
+        finally:
+            if tr:
+                p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
+            if fc:
+                p.fitness_idx = None; p.fitness_d2 = None
+        out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
+               "state": res.state, "fitness": res.fitness, "last_mse": res.last_mse, "trim_info": info}
+        if tr:
+            out["trace_sums"] = tr[0][:tr[2].value].copy()
+            out["trace_Tk"] = tr[1][:tr[2].value].reshape(-1, 4, 4).copy()
+            out["trace_trim"] = tr[3][:tr[2].value].copy()
+        if fc:
+            out["fitness_idx"], out["fitness_d2"] = fc
+        return out
+
+    def icp_trimmed_dev(self, d_src, ns, d_tgt, nt, d_normals, params, overlap=0.5, metric=METRIC_POINT):
+        """kss_icp_trimmed_dev on device pointers (d_normals may be 0 / None); returns (IcpResult, trim_info)."""
+        res = IcpResult()
+        tp = TrimParams(float(overlap), int(metric), None)
+        info = np.zeros(TRIM_NINFO, np.float64)
+        self._chk(self.L.kss_icp_trimmed_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
+                                             C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(tp),
+                                             C.byref(res), _p(info)), "kss_icp_trimmed_dev")
+        return res, info
 
     def icp_dev(self, d_src, ns, d_tgt, nt, params):
         res = IcpResult()

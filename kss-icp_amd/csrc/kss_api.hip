@@ -66,7 +66,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -498,6 +498,78 @@ int kss_icp_p2l(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int6
     if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
     return kss_icp_p2l_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
                            p, res);
+}
+
+// ---- trimmed ICP -------------------------------------------------------------------
+static inline bool trim_overlap_ok(double overlap) { return overlap > 0.0 && overlap <= 1.0; }   // (a NaN fails both)
+
+int kss_trim_rank(int64_t m, double overlap, int64_t* k) {
+    if (!k || m < 0 || !trim_overlap_ok(overlap)) return KSS_ERR_ARG;
+    *k = (int64_t)trim_rank_of((long long)m, overlap);
+    return KSS_OK;
+}
+
+int kss_trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double info[KSS_TRIM_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!d_d2 || !info) return set_err(c, KSS_ERR_ARG, "trim_threshold: null argument");
+    if (n <= 0 || n > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "trim_threshold: n out of range");
+    if (!trim_overlap_ok(overlap)) return set_err(c, KSS_ERR_ARG, "trim_threshold: overlap must be in (0, 1]");
+    return trim_threshold_dev(c, d_d2, n, max_d2, overlap, info);
+}
+
+int kss_trim_threshold(kss_ctx* c, const float* d2, int64_t n, double max_d2, double overlap, double info[KSS_TRIM_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!d2 || !info) return set_err(c, KSS_ERR_ARG, "trim_threshold: null argument");
+    if (n <= 0 || n > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "trim_threshold: n out of range");
+    if (!trim_overlap_ok(overlap)) return set_err(c, KSS_ERR_ARG, "trim_threshold: overlap must be in (0, 1]");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_d2, d2, (size_t)n * sizeof(float)));
+    return trim_threshold_dev(c, (const float*)c->stage_d2.p, n, max_d2, overlap, info);
+}
+
+static int trim_check(kss_ctx* c, const void* src, const void* tgt, int64_t ns, int64_t nt, const float* nrm, const kss_icp_params* p,
+                      const kss_trim_params* tp, const kss_icp_result* res) {
+    if (!src || !tgt || !p || !tp || !res) return set_err(c, KSS_ERR_ARG, "icp_trimmed: null argument");
+    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_trimmed: empty cloud");
+    if (ns > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "icp_trimmed: cloud too large");
+    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_trimmed: the source-row split (allreduce) is not available for trimmed ICP");
+    if (!trim_overlap_ok(tp->overlap)) return set_err(c, KSS_ERR_ARG, "icp_trimmed: overlap must be in (0, 1]");
+    if (tp->metric != KSS_METRIC_POINT && tp->metric != KSS_METRIC_PLANE) return set_err(c, KSS_ERR_ARG, "icp_trimmed: unknown metric");
+    if (tp->metric == KSS_METRIC_POINT && nrm) return set_err(c, KSS_ERR_ARG, "icp_trimmed: the point metric takes no normals");
+    return KSS_OK;
+}
+
+int kss_icp_trimmed_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                        const kss_icp_params* p, const kss_trim_params* tp, kss_icp_result* res, double last_info[KSS_TRIM_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(trim_check(c, d_src, d_tgt, ns, nt, d_nrm, p, tp, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    if (tp->metric == KSS_METRIC_PLANE && !d_nrm) {
+        // the target's normals, exactly as kss_icp_p2l_dev computes them
+        const int k = nt < 20 ? (int)nt : 20;
+        KCHK(ensure(c, c->p2l_idx, (size_t)nt * k * sizeof(int32_t)));
+        KCHK(ensure(c, c->p2l_d2, (size_t)nt * k * sizeof(float)));
+        KCHK(ensure(c, c->p2l_n64, (size_t)nt * 3 * sizeof(double)));
+        KCHK(ensure(c, c->p2l_nrm, (size_t)nt * 3 * sizeof(float)));
+        KCHK(knn_generic_dev(c, d_tgt, nt, d_tgt, nt, KSS_F32, k, (int32_t*)c->p2l_idx.p, (float*)c->p2l_d2.p));
+        launch_normals(c->stream, (const float4*)c->src0.p, (int)nt, (const int32_t*)c->p2l_idx.p, k, (double*)c->p2l_n64.p);
+        launch_f64_to_f32(c->stream, (const double*)c->p2l_n64.p, nt * 3, (float*)c->p2l_nrm.p);
+        HIPCHK(c, hipGetLastError());
+        d_nrm = (const float*)c->p2l_nrm.p;
+    }
+    return trim_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, tp->overlap, tp->trace_trim, res, last_info);
+}
+
+int kss_icp_trimmed(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
+                    const kss_icp_params* p, const kss_trim_params* tp, kss_icp_result* res, double last_info[KSS_TRIM_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(trim_check(c, src, tgt, ns, nt, nrm, p, tp, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_trimmed_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
+                               p, tp, res, last_info);
 }
 
 // ---- pre-shape ------------------------------------------------------------------------------------

@@ -51,6 +51,9 @@ struct kss_ctx {
     // point-to-plane ICP (kss_p2l.hip): per-pass idx / d2, source slot of each original index, partial rows, float normals
     // (staged or computed) and their f64 form from the normals kernel
     DevBuf p2l_idx, p2l_d2, p2l_perm, p2l_rows, p2l_nrm, p2l_n64;
+    // trimmed ICP (kss_trim.hip): the selection's histogram rows (one per workgroup, rewritten by every digit) and its
+    // TRIM_NSTATE TrimState records; neither has to hold anything between passes
+    DevBuf trim_rows, trim_state;
     HostPool pool;   // per-pair host work of batched iterations
     std::vector<kss_ctx*> workers;   // contexts of kss_register_batch's worker threads (same device, own streams)
     std::vector<unsigned long long> last_stamps;
@@ -236,6 +239,10 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 int nn_generic_dev(kss_ctx* c, const void* d_src, int64_t ns, const void* d_tgt, int64_t nt, int dtype,
                    int32_t* d_idx, float* d_d2, double sums_out[NSUMS]);
 // point-to-plane ICP of one pair (float clouds and target normals on the device)
+// trimmed ICP of one pair (kss_icp_trimmed): d_nrm null = point metric.  trace_trim / last_info: KSS_TRIM_NINFO doubles per pass
+int trim_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                 const kss_icp_params* p, double overlap, double* trace_trim, kss_icp_result* res, double* last_info);
+int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info);
 int p2l_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                 const kss_icp_params* p, kss_icp_result* res);
 // host-mapped {value, sequence number} result slots: allocate them; wait for the first nslots of launch c->seq

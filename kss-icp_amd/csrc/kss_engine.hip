@@ -1947,6 +1947,156 @@ int p2l_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, 
     return rc;
 }
 
+// ---- trimmed ICP of one pair (kss_icp_trimmed): p2l_loop with the closest `overlap` share of the pass's
+// candidates kept.  Per pass: the NN pass as in p2l_loop, the radix select over its d2 output (four plain launches, tau / m / k
+// stay on the device), the rows + final launches of the metric reading the cut from there, ONE stream synchronisation, then
+// the solve and the PCL criteria on the host.  The record and {m, k, tau, kept} arrive in host-mapped memory (h_p2l: the sums
+// in front, the info behind KSS_P2L_NSUMS doubles).  plane: d_nrm given; point: d_nrm null.
+static int trim_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, double overlap, const float* d_tgt, const float* d_nrm,
+                     const int32_t* d_perm, double* trace_trim, kss_icp_result* res, double* last_info) {
+    const int64_t ns = pl.g[0].ns, nt = pl.g[0].nt;
+    const bool plane = d_nrm != nullptr;
+    const int ncol = plane ? P2L_NSUMS : NSUMS;
+    Convergence cv;
+    cv.max_iterations = P.max_iterations;
+    cv.rotation_threshold = 1.0 - P.transformation_epsilon;
+    cv.translation_threshold = P.transformation_epsilon;
+    cv.mse_rel = P.euclidean_fitness_epsilon;
+    cv.mse_abs = P.abs_mse_epsilon;
+    cv.fixed_iterations = P.fixed_iterations != 0;
+    float fin[16], tk[16], I[16];
+    mat4_identity(fin);
+    mat4_identity(I);
+    PairState* hs = (PairState*)c->h_state;
+    set_state(hs[0], I, 1, 0);
+    const double max_d2 = P.max_corr_dist * P.max_corr_dist;
+    int32_t* d_idx = (int32_t*)c->p2l_idx.p;
+    float* d_d2 = (float*)c->p2l_d2.p;
+    const double* hp = (const double*)c->h_p2l;
+    double* d_rec = (double*)c->h_p2l_dev;
+    TrimState* d_state = (TrimState*)c->trim_state.p;
+    const double* d_cut = &d_state[TRIM_NSTATE - 1].cut;
+    if (P.trace_n) *P.trace_n = 0;
+    if (last_info) for (int q = 0; q < KSS_TRIM_NINFO; ++q) last_info[q] = 0.0;
+    int it = 0, iters = 0, state = KSS_STATE_NOT_CONVERGED, converged = 0;
+    double last_mse = 0.0;
+    GatedGuard gated_guard(c);
+    c->gated.want_next = false;
+    while (P.max_iterations > 0) {
+        const float4* d_in = it == 0 ? (const float4*)c->src0.p : (const float4*)c->cur[(it - 1) & 1].p;
+        float4* d_out = (float4*)c->cur[it & 1].p;
+        KCHK(nn_pass(c, pl, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false));
+        {
+            ProfScope ps(c, KSS_K_CORR_REDUCE);
+            launch_trim_select(c->stream, d_d2, ns, max_d2, overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
+            if (plane)
+                launch_p2l_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, (double*)c->p2l_rows.p, d_rec, d_cut);
+            else
+                launch_trim_point_sums(c->stream, d_out, d_perm, d_idx, d_d2, d_tgt, ns, nt, d_cut, (double*)c->p2l_rows.p, d_rec);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        ++it;
+        double s[P2L_NSUMS], info[KSS_TRIM_NINFO];
+        std::memcpy(s, hp, (size_t)ncol * sizeof(double));
+        std::memcpy(info, hp + P2L_NSUMS, sizeof info);
+        info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
+        if (last_info) std::memcpy(last_info, info, sizeof info);
+        if ((int)s[0] < P.min_correspondences) { state = KSS_STATE_NO_CORRESPONDENCES; break; }
+        if (plane) {
+            if (!rigid_from_p2l_sums(s, tk)) { state = KSS_STATE_DEGENERATE; break; }
+        } else {
+            rigid_from_sums(s, tk);
+        }
+        mat4_mul(tk, fin, fin);   // final = transformation_ * final
+        ++iters;
+        const double mse = (plane ? s[28] : s[16]) / s[0];
+        last_mse = mse;
+        if (P.trace_n && *P.trace_n < P.trace_cap) {
+            if (P.trace_sums) std::memcpy(P.trace_sums + (size_t)(*P.trace_n) * ncol, s, (size_t)ncol * sizeof(double));
+            if (P.trace_Tk) std::memcpy(P.trace_Tk + (size_t)(*P.trace_n) * 16, tk, 16 * sizeof(float));
+            if (trace_trim) std::memcpy(trace_trim + (size_t)(*P.trace_n) * KSS_TRIM_NINFO, info, sizeof info);
+            ++*P.trace_n;
+        }
+        const bool done = cv.has_converged(iters, tk, mse);
+        state = cv.state;
+        if (done) { converged = 1; break; }
+        set_state(hs[0], tk, 1, 1);   // next NN pass applies T_k on load (transformCloud)
+    }
+    std::memcpy(res->T, fin, sizeof fin);
+    res->iterations = iters; res->converged = converged; res->state = state;
+    res->last_mse = last_mse; res->fitness = 0.0; res->pair_id = 0;
+    if (P.compute_fitness) {
+        // getFitnessScore() over ALL sources, as in p2l_loop
+        set_state(hs[0], fin, 1, 1);
+        if (pl.grid && iters >= 1 && state != KSS_STATE_NO_CORRESPONDENCES && state != KSS_STATE_DEGENERATE) hs[0].pad[0] = 1 + ((iters - 1) & 1);
+        c->fit_last = pl.grid;
+        struct FitGuard { kss_ctx* c; ~FitGuard() { c->fit_last = false; } } fit_guard{c};
+        const bool corr = P.fitness_idx || P.fitness_d2;
+        KCHK(nn_pass(c, pl, P.nn_fma != 0, (const float4*)c->src0.p, (float4*)c->cur[0].p, max_d2, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, true));
+        res->fitness = ((const double*)c->h_sums)[17] / (double)ns;
+        if (corr) {
+            if (P.fitness_idx) HIPCHK(c, hipMemcpyAsync(P.fitness_idx, d_idx, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            if (P.fitness_d2) HIPCHK(c, hipMemcpyAsync(P.fitness_d2, d_d2, (size_t)ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    return KSS_OK;
+}
+
+int trim_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                 const kss_icp_params* p, double overlap, double* trace_trim, kss_icp_result* res, double* last_info) {
+    if (!c || !d_src || !d_tgt || !p || !res) return set_err(c, KSS_ERR_ARG, "icp_trimmed: bad argument");
+    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_trimmed: empty cloud");
+    if (!(overlap > 0.0 && overlap <= 1.0)) return set_err(c, KSS_ERR_ARG, "icp_trimmed: overlap must be in (0, 1]");
+    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_trimmed: the source-row split (allreduce) is not available for trimmed ICP");
+    HIPCHK(c, hipSetDevice(c->device));
+    IcpPlan pl;
+    const auto t0 = std::chrono::steady_clock::now();
+    KCHK(restore_zero_at_rest(c));
+    DirtyGuard guard(c);
+    c->timing = false;
+    KCHK(build_plan(c, &ns, &nt, 1, false, p->nn_sources_per_thread, p->nn_target_splits, p->nn_mode, pl));
+    KCHK(stage_plan(c, pl));
+    KCHK(ensure(c, c->p2l_idx, (size_t)ns * sizeof(int32_t)));
+    KCHK(ensure(c, c->p2l_d2, (size_t)ns * sizeof(float)));
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(ns) * P2L_NSUMS * sizeof(double)));
+    KCHK(ensure(c, c->trim_rows, trim_rows_bytes(ns)));
+    KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
+    const int64_t so[2] = {0, ns}, to[2] = {0, nt};
+    KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));
+    KCHK(grid_setup(c, pl));
+    const int32_t* d_perm = nullptr;
+    if (pl.src_in_cell_order) {
+        KCHK(ensure(c, c->p2l_perm, (size_t)ns * sizeof(int32_t)));
+        launch_p2l_perm(c->stream, (const float4*)c->src0.p + pl.g[0].src_base, ns, (int32_t*)c->p2l_perm.p);
+        HIPCHK(c, hipGetLastError());
+        d_perm = (const int32_t*)c->p2l_perm.p;
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    const int rc = trim_loop(c, pl, *p, overlap, d_tgt, d_nrm, d_perm, trace_trim, res, last_info);
+    guard.ok = rc == KSS_OK;
+    const auto t2 = std::chrono::steady_clock::now();
+    c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return rc;
+}
+
+// tau / m / k / kept of n squared distances on the device (kss_trim_threshold_dev)
+int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info) {
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(ensure(c, c->trim_rows, trim_rows_bytes(n)));
+    KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
+    launch_trim_select(c->stream, d_d2, n, max_d2, overlap, (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p,
+                       (double*)c->h_p2l_dev + P2L_NSUMS);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_TRIM_NINFO * sizeof(double));
+    return KSS_OK;
+}
+
 int nn_generic_dev(kss_ctx* c, const void* d_src, int64_t ns, const void* d_tgt, int64_t nt, int dtype,
                           int32_t* d_idx, float* d_d2, double sums_out[NSUMS]) {
     if (!c || !d_src || !d_tgt) return set_err(c, KSS_ERR_ARG, "nn: null cloud");

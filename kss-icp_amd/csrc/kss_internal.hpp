@@ -334,12 +334,42 @@ int stream_blocks(int64_t n);
 // point-to-plane sums (kss_p2l.hip): partial rows over p2l_rows_blocks(n) workgroups, then one workgroup writes the
 // KSS_P2L_NSUMS record to d_out (device or host-mapped).  Sources: d_src3 (packed float triples, original order) or d_src4
 // (float4; with d_perm: cell order, d_perm[i] = slot of original source i).  d_d2: NN distances (null: recomputed).
+// d_cut (trimmed ICP): the threshold is read from *d_cut on the device and kept means 0 <= d2 <= *d_cut; max_d2 is unused.
 static_assert(P2L_NSUMS == KSS_P2L_NSUMS, "kss_host_math.hpp and include/kssicp.h disagree");
 int p2l_rows_blocks(int64_t n);
 void launch_p2l_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
                      const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
-                     double* d_rows, double* d_out);
+                     double* d_rows, double* d_out, const double* d_cut = nullptr);
 void launch_p2l_perm(hipStream_t st, const float4* d_src, int64_t n, int32_t* d_perm);
+
+// ---- trimmed ICP (kss_trim.hip) ----
+// What one digit of the radix select hands to the next, and the last one to the sums kernels of the same pass: the key
+// prefix found so far, the rank inside the keys that carry it, m candidates, k = trim_rank_of(m, overlap); after the last digit
+// cut = tau widened (-1: no candidate, nothing is kept) and kept = the candidates <= tau.  Four of them per context: step d
+// reads [d] and writes [d + 1], so nothing is updated in place and nothing has to be reset between passes.
+struct alignas(16) TrimState {
+    unsigned prefix, pad;
+    long long rank, m, k;
+    double cut;
+    long long kept;
+};
+constexpr int TRIM_NSTATE = 4;
+// k of the definition: one IEEE f64 multiplication, then ceil; the device code and kss_trim_rank share this function
+__host__ __device__ inline long long trim_rank_of(long long m, double overlap) {
+    if (m == 0) return 0;
+    const double x = overlap * (double)m;
+    const long long k = (long long)ceil(x);
+    return k < 1 ? 1 : k;
+}
+int trim_hist_blocks(int64_t n);
+size_t trim_rows_bytes(int64_t n);
+// four plain launches: tau / m / k of d_d2[0..n) into d_state[TRIM_NSTATE - 1] and {m, k, tau, kept} into d_info (may be
+// null); d_rows holds trim_rows_bytes(n)
+void launch_trim_select(hipStream_t st, const float* d_d2, int64_t n, double max_d2, double overlap, unsigned* d_rows,
+                        TrimState* d_state, double* d_info);
+// the KSS_NSUMS record over the correspondences with 0 <= d2 <= *d_cut (slots 17..19 are 0)
+void launch_trim_point_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                            const float* d_tgt3, int64_t n, int64_t nt, const double* d_cut, double* d_rows, double* d_out);
 void launch_f64_to_f32(hipStream_t st, const double* d_in, int64_t n, float* d_out);
 
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order

@@ -19,16 +19,20 @@ constexpr int P2L_THREADS = 256;
 // original source i.
 enum { SRC_F3 = 0, SRC_F4 = 1, SRC_F4_PERM = 2 };
 
-template <int SRC>
+// TRIM (trimmed ICP, kss_trim.hip): the threshold is the pass's cut tau, read from device memory where the selection left it
+// (-1: no candidate), and a correspondence is kept when 0 <= d2 <= tau; the body and the summation order are the same, so an
+// overlap of 1 -- tau = the largest d2 within max_d2 -- gives the untrimmed record bit for bit.
+template <int SRC, bool TRIM>
 __global__ __launch_bounds__(P2L_THREADS) void p2l_rows_kernel(const float* __restrict__ src3, const float4* __restrict__ src4,
                                                                const int32_t* __restrict__ perm, const int32_t* __restrict__ idx,
                                                                const float* __restrict__ d2_in, const float* __restrict__ tgt,
                                                                const float* __restrict__ nrm, int64_t n, int64_t nt, double max_d2,
-                                                               double* __restrict__ rows) {
+                                                               const double* __restrict__ cut_ptr, double* __restrict__ rows) {
     __shared__ double sh[P2L_THREADS / 64][P2L_NSUMS];
     double acc[P2L_NSUMS];
 #pragma unroll
     for (int c = 0; c < P2L_NSUMS; ++c) acc[c] = 0.0;
+    if constexpr (TRIM) max_d2 = *cut_ptr;
     for (int64_t i = (int64_t)blockIdx.x * P2L_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * P2L_THREADS) {
         const int64_t j = idx[i];
         if (j < 0 || j >= nt) continue;   // (kss_p2l_sums_dev: an index outside the target contributes nothing)
@@ -44,7 +48,7 @@ __global__ __launch_bounds__(P2L_THREADS) void p2l_rows_kernel(const float* __re
         const double d2 = (double)(d2_in ? d2_in[i] : dist2<false>(sx, sy, sz, qx, qy, qz));
         acc[29] += d2;
         // PCL: `if (distance > max_dist_sqr) continue;`, and a correspondence whose normal is not finite is dropped
-        if (!(d2 > max_d2) && isfinite(nx) && isfinite(ny) && isfinite(nz)) {
+        if ((TRIM ? d2 >= 0.0 && d2 <= max_d2 : !(d2 > max_d2)) && isfinite(nx) && isfinite(ny) && isfinite(nz)) {
             // float, left to right, no fma (PCL computes these in float and widens)
             const float a = nz * sy - ny * sz;
             const float b = nx * sz - nz * sx;
@@ -110,17 +114,21 @@ int p2l_rows_blocks(int64_t n) { return stream_blocks(n); }
 
 void launch_p2l_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
                      const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
-                     double* d_rows, double* d_out) {
+                     double* d_rows, double* d_out, const double* d_cut) {
     const int nb = p2l_rows_blocks(n);
-    if (d_src3)
-        hipLaunchKernelGGL(p2l_rows_kernel<SRC_F3>, dim3(nb), dim3(P2L_THREADS), 0, st, d_src3, d_src4, d_perm, d_idx, d_d2, d_tgt3,
-                           d_nrm3, n, nt, max_d2, d_rows);
-    else if (d_perm)
-        hipLaunchKernelGGL(p2l_rows_kernel<SRC_F4_PERM>, dim3(nb), dim3(P2L_THREADS), 0, st, d_src3, d_src4, d_perm, d_idx, d_d2, d_tgt3,
-                           d_nrm3, n, nt, max_d2, d_rows);
-    else
-        hipLaunchKernelGGL(p2l_rows_kernel<SRC_F4>, dim3(nb), dim3(P2L_THREADS), 0, st, d_src3, d_src4, d_perm, d_idx, d_d2, d_tgt3,
-                           d_nrm3, n, nt, max_d2, d_rows);
+    const dim3 g(nb), b(P2L_THREADS);
+#define KSS_P2L_ROWS(SRC, TRIM) \
+    hipLaunchKernelGGL((p2l_rows_kernel<SRC, TRIM>), g, b, 0, st, d_src3, d_src4, d_perm, d_idx, d_d2, d_tgt3, d_nrm3, n, nt, max_d2, d_cut, d_rows)
+    if (d_cut) {   // trimmed: d_d2 is the NN pass's output
+        if (d_src3) KSS_P2L_ROWS(SRC_F3, true);
+        else if (d_perm) KSS_P2L_ROWS(SRC_F4_PERM, true);
+        else KSS_P2L_ROWS(SRC_F4, true);
+    } else {
+        if (d_src3) KSS_P2L_ROWS(SRC_F3, false);
+        else if (d_perm) KSS_P2L_ROWS(SRC_F4_PERM, false);
+        else KSS_P2L_ROWS(SRC_F4, false);
+    }
+#undef KSS_P2L_ROWS
     hipLaunchKernelGGL(p2l_final_kernel, dim3(1), dim3(P2L_THREADS), 0, st, (const double*)d_rows, nb, d_out);
 }
 

@@ -80,6 +80,22 @@ def make_pair(pair_id, n, R=None, scale=1.0, t=(0, 0, 0), jitter=1e-3, shape="sp
     return src.astype(np.float32), tgt.astype(np.float32)
 
 
+def make_partial_pair(pair_id, n, deg, lo, hi, t=(0.02, -0.01, 0.03), jitter=1e-3):
+    """A partly overlapping pair of the bumpy surface M = bumpy(1000 + pair_id, n): the target is the part of M with x > lo,
+    the source the part with x < hi (in the seed-shuffled order), moved by R (deg degrees about sphere(7000 + pair_id, 1)[0])
+    and t, plus jitter.  Returns (source, target) float32, the true (R, t) of source = R model + t, and the true overlap: the
+    share of source rows whose model point lies in the target."""
+    M = bumpy(1000 + pair_id, n)
+    tgt = M[M[:, 0] > lo]
+    Ms = M[permutation(3000 + pair_id, n)]
+    Ms = Ms[Ms[:, 0] < hi]
+    R = rot_axis_angle(sphere(7000 + pair_id, 1)[0], np.deg2rad(deg))
+    t = np.asarray(t, dtype=np.float64)
+    src = Ms @ R.T + t + jitter * normal(2000 + pair_id, 3 * len(Ms)).reshape(-1, 3)
+    overlap = float(np.mean(Ms[:, 0] > lo))
+    return src.astype(np.float32), tgt.astype(np.float32), R, t, overlap
+
+
 def config_c2(n=100000):
     """C2: single 100k x 100k pair, R_z(10 deg) (inside ICP's basin)."""
     return make_pair(0, n, R=rot_axis_angle([0, 0, 1], np.deg2rad(10.0)))
