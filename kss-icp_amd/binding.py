@@ -100,25 +100,8 @@ def build_library(force=False):
     return lib_path()
 
 
-_LIB = None
-
-
-def load_library():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    p = lib_path()
-    if not os.path.exists(p):
-        raise KssError(-4, "load_library", "libkssicp.so not built: run __graft_entry__.build() (no CPU fallback exists)")
-    # One HIP runtime per process: PyTorch ships its own libamdhip64.so; if libkssicp.so pulled in /opt/rocm's copy
-    # first, torch would later load a second runtime and see no devices.  Importing torch first (when it is installed)
-    # makes both resolve to the same library.  KSS_NO_TORCH=1 skips this for hosts that never use torch.
-    if "torch" not in sys.modules and not os.environ.get("KSS_NO_TORCH"):
-        try:
-            import torch  # noqa: F401
-        except Exception:
-            pass
-    L = C.CDLL(p)
+def _declare(L):
+    """restype / argtypes of every entry point of a loaded libkssicp.so."""
     vp, i64, dbl = C.c_void_p, C.c_int64, C.c_double
     L.kss_version.restype = C.c_int
     L.kss_status_string.restype = C.c_char_p
@@ -181,7 +164,33 @@ def load_library():
     L.kss_normals.argtypes = [vp, vp, i64, C.c_int, vp]
     L.kss_register.argtypes = [vp, vp, i64, vp, i64, vp, i64, dbl, C.c_int, vp, C.POINTER(RegisterResult)]
     L.kss_gather_results.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp]
-    _LIB = L
+    return L
+
+
+_LIB = None
+
+
+def load_library(path=None):
+    """The product library, loaded and declared once.  With a path: a second, uncached handle on that build of libkssicp.so
+    (Context(lib=...) runs on it; tools that compare two builds in one process)."""
+    global _LIB
+    if path is None and _LIB is not None:
+        return _LIB
+    p = lib_path() if path is None else os.path.abspath(path)
+    if not os.path.exists(p):
+        raise KssError(-4, "load_library", "libkssicp.so not built: run __graft_entry__.build() (no CPU fallback exists)"
+                       if path is None else "%s does not exist" % p)
+    # One HIP runtime per process: PyTorch ships its own libamdhip64.so; if libkssicp.so pulled in /opt/rocm's copy
+    # first, torch would later load a second runtime and see no devices.  Importing torch first (when it is installed)
+    # makes both resolve to the same library.  KSS_NO_TORCH=1 skips this for hosts that never use torch.
+    if "torch" not in sys.modules and not os.environ.get("KSS_NO_TORCH"):
+        try:
+            import torch  # noqa: F401
+        except Exception:
+            pass
+    L = _declare(C.CDLL(p))
+    if path is None:
+        _LIB = L
     return L
 
 
@@ -262,8 +271,8 @@ def rigid_from_p2l_sums(sums):
 class Context:
     """One kss_ctx (one GPU, one stream)."""
 
-    def __init__(self, device=0, stream=None):
-        self.L = load_library()
+    def __init__(self, device=0, stream=None, lib=None):
+        self.L = lib if lib is not None else load_library()
         self.h = C.c_void_p()
         if stream is None:
             rc = self.L.kss_ctx_create(int(device), C.byref(self.h))
@@ -406,36 +415,49 @@ class Context:
             setattr(p, k, v)
         return p
 
-    def icp(self, src, tgt, params=None, trace_cap=0, fitness_corr=False):
-        s, t = _f32(src), _f32(tgt)
-        p = params if params is not None else self.icp_params()
+    def _icp_call(self, call, where, p, ns, ncol, trace_cap, fitness_corr, tp=None):
+        """call(res) with the trace and fitness_corr arrays attached to the params p (and to the TrimParams tp), detached again
+        whether it returns or raises; the result dictionary of icp()."""
         res = IcpResult()
         tr = None
         fc = None
-        if fitness_corr:
-            fc = (np.full(len(s), -1, np.int32), np.full(len(s), np.nan, np.float32))
-            p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
-            p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
-        if trace_cap > 0:
-            sums = np.zeros((trace_cap, NSUMS), np.float64)
-            tk = np.zeros((trace_cap, 16), np.float32)
-            n = C.c_int(0)
-            p.trace_sums = sums.ctypes.data_as(C.POINTER(C.c_double))
-            p.trace_Tk = tk.ctypes.data_as(C.POINTER(C.c_float))
-            p.trace_cap = trace_cap
-            p.trace_n = C.pointer(n)
-            tr = (sums, tk, n)
-        self._chk(self.L.kss_icp(self.h, _p(s), len(s), _p(t), len(t), C.byref(p), C.byref(res)), "kss_icp")
+        try:
+            if fitness_corr:
+                fc = (np.full(ns, -1, np.int32), np.full(ns, np.nan, np.float32))
+                p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
+                p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
+            if trace_cap > 0:
+                tr = (np.zeros((trace_cap, ncol), np.float64), np.zeros((trace_cap, 16), np.float32), C.c_int(0),
+                      np.zeros((trace_cap, TRIM_NINFO), np.float64) if tp is not None else None)
+                p.trace_sums = tr[0].ctypes.data_as(C.POINTER(C.c_double))
+                p.trace_Tk = tr[1].ctypes.data_as(C.POINTER(C.c_float))
+                p.trace_cap = trace_cap
+                p.trace_n = C.pointer(tr[2])
+                if tp is not None:
+                    tp.trace_trim = tr[3].ctypes.data_as(C.POINTER(C.c_double))
+            self._chk(call(res), where)
+        finally:
+            if tr:
+                p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
+            if fc:
+                p.fitness_idx = None; p.fitness_d2 = None
         out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
                "state": res.state, "fitness": res.fitness, "last_mse": res.last_mse}
         if tr:
-            out["trace_sums"] = tr[0][:tr[2].value].copy()
-            out["trace_Tk"] = tr[1][:tr[2].value].reshape(-1, 4, 4).copy()
-            p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
+            n = tr[2].value
+            out["trace_sums"] = tr[0][:n].copy()
+            out["trace_Tk"] = tr[1][:n].reshape(-1, 4, 4).copy()
+            if tp is not None:
+                out["trace_trim"] = tr[3][:n].copy()
         if fc:
             out["fitness_idx"], out["fitness_d2"] = fc
-            p.fitness_idx = None; p.fitness_d2 = None
         return out
+
+    def icp(self, src, tgt, params=None, trace_cap=0, fitness_corr=False):
+        s, t = _f32(src), _f32(tgt)
+        p = params if params is not None else self.icp_params()
+        return self._icp_call(lambda res: self.L.kss_icp(self.h, _p(s), len(s), _p(t), len(t), C.byref(p), C.byref(res)),
+                              "kss_icp", p, len(s), NSUMS, trace_cap, fitness_corr)
 
     # ---- point-to-plane
     def p2l_sums(self, src, tgt, normals, idx, max_d2=1.0):
@@ -459,37 +481,8 @@ class Context:
         if nr is not None and len(nr) != len(t):
             raise ValueError("normals must have one row per target point")
         p = params if params is not None else self.icp_params()
-        res = IcpResult()
-        tr = None
-        fc = None
-        if fitness_corr:
-            fc = (np.full(len(s), -1, np.int32), np.full(len(s), np.nan, np.float32))
-            p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
-            p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
-        if trace_cap > 0:
-            sums = np.zeros((trace_cap, P2L_NSUMS), np.float64)
-            tk = np.zeros((trace_cap, 16), np.float32)
-            n = C.c_int(0)
-            p.trace_sums = sums.ctypes.data_as(C.POINTER(C.c_double))
-            p.trace_Tk = tk.ctypes.data_as(C.POINTER(C.c_float))
-            p.trace_cap = trace_cap
-            p.trace_n = C.pointer(n)
-            tr = (sums, tk, n)
-        try:
-            self._chk(self.L.kss_icp_p2l(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(res)), "kss_icp_p2l")
-        finally:
-            if tr:
-                p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-            if fc:
-                p.fitness_idx = None; p.fitness_d2 = None
-        out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
-               "state": res.state, "fitness": res.fitness, "last_mse": res.last_mse}
-        if tr:
-            out["trace_sums"] = tr[0][:tr[2].value].copy()
-            out["trace_Tk"] = tr[1][:tr[2].value].reshape(-1, 4, 4).copy()
-        if fc:
-            out["fitness_idx"], out["fitness_d2"] = fc
-        return out
+        return self._icp_call(lambda res: self.L.kss_icp_p2l(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(res)),
+                              "kss_icp_p2l", p, len(s), P2L_NSUMS, trace_cap, fitness_corr)
 
     def icp_p2l_dev(self, d_src, ns, d_tgt, nt, d_normals, params):
         """kss_icp_p2l_dev on device pointers (d_normals may be 0 / None); returns the IcpResult."""
@@ -524,41 +517,11 @@ class Context:
             raise ValueError("normals must have one row per target point")
         p = params if params is not None else self.icp_params()
         tp = TrimParams(float(overlap), int(metric), None)
-        res = IcpResult()
         info = np.zeros(TRIM_NINFO, np.float64)
-        tr = None
-        fc = None
-        if fitness_corr:
-            fc = (np.full(len(s), -1, np.int32), np.full(len(s), np.nan, np.float32))
-            p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
-            p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
-        if trace_cap > 0:
-            sums = np.zeros((trace_cap, P2L_NSUMS if metric == METRIC_PLANE else NSUMS), np.float64)
-            tk = np.zeros((trace_cap, 16), np.float32)
-            tt = np.zeros((trace_cap, TRIM_NINFO), np.float64)
-            n = C.c_int(0)
-            p.trace_sums = sums.ctypes.data_as(C.POINTER(C.c_double))
-            p.trace_Tk = tk.ctypes.data_as(C.POINTER(C.c_float))
-            p.trace_cap = trace_cap
-            p.trace_n = C.pointer(n)
-            tp.trace_trim = tt.ctypes.data_as(C.POINTER(C.c_double))
-            tr = (sums, tk, n, tt)
-        try:
-            self._chk(self.L.kss_icp_trimmed(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(tp), C.byref(res),
-                                             _p(info)), "kss_icp_trimmed")
-        finally:
-            if tr:
-                p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-            if fc:
-                p.fitness_idx = None; p.fitness_d2 = None
-        out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
-               "state": res.state, "fitness": res.fitness, "last_mse": res.last_mse, "trim_info": info}
-        if tr:
-            out["trace_sums"] = tr[0][:tr[2].value].copy()
-            out["trace_Tk"] = tr[1][:tr[2].value].reshape(-1, 4, 4).copy()
-            out["trace_trim"] = tr[3][:tr[2].value].copy()
-        if fc:
-            out["fitness_idx"], out["fitness_d2"] = fc
+        out = self._icp_call(lambda res: self.L.kss_icp_trimmed(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(tp),
+                                                                C.byref(res), _p(info)),
+                             "kss_icp_trimmed", p, len(s), P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, tp)
+        out["trim_info"] = info
         return out
 
     def icp_trimmed_dev(self, d_src, ns, d_tgt, nt, d_normals, params, overlap=0.5, metric=METRIC_POINT):

@@ -461,37 +461,56 @@ int kss_rigid_from_p2l_sums(const double sums[KSS_P2L_NSUMS], float T[16]) {
     return KSS_OK;
 }
 
+// ---- what kss_icp_p2l[_dev] and kss_icp_trimmed[_dev] share ----
+static inline bool trim_overlap_ok(double overlap) { return overlap > 0.0 && overlap <= 1.0; }   // (a NaN fails both)
+
+// the argument check of both families.  who: the name the messages carry; tp: null for kss_icp_p2l
+static int pair_check(kss_ctx* c, const char* who, bool trimmed, const void* src, const void* tgt, int64_t ns, int64_t nt, const float* nrm,
+                      const kss_icp_params* p, const kss_trim_params* tp, const kss_icp_result* res) {
+    const std::string w = std::string(who) + ": ";
+    auto bad = [&](const std::string& what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
+    if (!src || !tgt || !p || !res || (trimmed && !tp)) return bad("null argument");
+    if (ns <= 0 || nt <= 0) return bad("empty cloud");
+    if (ns > 0x7fff0000ll || nt > 0x7fff0000ll) return bad("cloud too large");
+    if (p->allreduce) return bad(std::string("the source-row split (allreduce) is not available for ") + (trimmed ? "trimmed ICP" : "point-to-plane"));
+    if (!trimmed) return KSS_OK;
+    if (!trim_overlap_ok(tp->overlap)) return bad("overlap must be in (0, 1]");
+    if (tp->metric != KSS_METRIC_POINT && tp->metric != KSS_METRIC_PLANE) return bad("unknown metric");
+    if (tp->metric == KSS_METRIC_POINT && nrm) return bad("the point metric takes no normals");
+    return KSS_OK;
+}
+
+// the target's normals where the caller gave none: kss_normals' definition (k = 20 incl. the point itself, view-point flip,
+// renormalised in double) on the target widened to f64 -- whose float narrowing is the target itself -- then rounded to float
+static int target_normals_dev(kss_ctx* c, const float* d_tgt, int64_t nt, const float** d_nrm) {
+    const int k = nt < 20 ? (int)nt : 20;
+    KCHK(ensure(c, c->p2l_idx, (size_t)nt * k * sizeof(int32_t)));
+    KCHK(ensure(c, c->p2l_d2, (size_t)nt * k * sizeof(float)));
+    KCHK(ensure(c, c->p2l_n64, (size_t)nt * 3 * sizeof(double)));
+    KCHK(ensure(c, c->p2l_nrm, (size_t)nt * 3 * sizeof(float)));
+    KCHK(knn_generic_dev(c, d_tgt, nt, d_tgt, nt, KSS_F32, k, (int32_t*)c->p2l_idx.p, (float*)c->p2l_d2.p));
+    launch_normals(c->stream, (const float4*)c->src0.p, (int)nt, (const int32_t*)c->p2l_idx.p, k, (double*)c->p2l_n64.p);
+    launch_f64_to_f32(c->stream, (const double*)c->p2l_n64.p, nt * 3, (float*)c->p2l_nrm.p);
+    HIPCHK(c, hipGetLastError());
+    *d_nrm = (const float*)c->p2l_nrm.p;
+    return KSS_OK;
+}
+
 int kss_icp_p2l_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                     const kss_icp_params* p, kss_icp_result* res) {
     if (!c) return KSS_ERR_ARG;
-    if (!d_src || !d_tgt || !p || !res) return set_err(c, KSS_ERR_ARG, "icp_p2l: null argument");
-    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_p2l: empty cloud");
-    if (ns > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "icp_p2l: cloud too large");
-    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_p2l: the source-row split (allreduce) is not available for point-to-plane");
+    KCHK(pair_check(c, "icp_p2l", false, d_src, d_tgt, ns, nt, d_nrm, p, nullptr, res));
     HIPCHK(c, hipSetDevice(c->device));
-    if (!d_nrm) {
-        // kss_normals' definition (k = 20 incl. the point itself, view-point flip, renormalised in double) on the target widened
-        // to f64 -- whose float narrowing is the target itself -- then rounded to float
-        const int k = nt < 20 ? (int)nt : 20;
-        KCHK(ensure(c, c->p2l_idx, (size_t)nt * k * sizeof(int32_t)));
-        KCHK(ensure(c, c->p2l_d2, (size_t)nt * k * sizeof(float)));
-        KCHK(ensure(c, c->p2l_n64, (size_t)nt * 3 * sizeof(double)));
-        KCHK(ensure(c, c->p2l_nrm, (size_t)nt * 3 * sizeof(float)));
-        KCHK(knn_generic_dev(c, d_tgt, nt, d_tgt, nt, KSS_F32, k, (int32_t*)c->p2l_idx.p, (float*)c->p2l_d2.p));
-        launch_normals(c->stream, (const float4*)c->src0.p, (int)nt, (const int32_t*)c->p2l_idx.p, k, (double*)c->p2l_n64.p);
-        launch_f64_to_f32(c->stream, (const double*)c->p2l_n64.p, nt * 3, (float*)c->p2l_nrm.p);
-        HIPCHK(c, hipGetLastError());
-        d_nrm = (const float*)c->p2l_nrm.p;
-    }
-    return p2l_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, res);
+    if (!d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
+    PairMode mode;
+    mode.plane = true;
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
 }
 
 int kss_icp_p2l(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
                 const kss_icp_params* p, kss_icp_result* res) {
     if (!c || !src || !tgt) return set_err(c, KSS_ERR_ARG, "icp_p2l: null cloud");
-    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_p2l: empty cloud");
-    if (!p || !res) return set_err(c, KSS_ERR_ARG, "icp_p2l: null argument");
-    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_p2l: the source-row split (allreduce) is not available for point-to-plane");
+    KCHK(pair_check(c, "icp_p2l", false, src, tgt, ns, nt, nrm, p, nullptr, res));
     HIPCHK(c, hipSetDevice(c->device));
     KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
     KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
@@ -501,8 +520,6 @@ int kss_icp_p2l(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int6
 }
 
 // ---- trimmed ICP -------------------------------------------------------------------
-static inline bool trim_overlap_ok(double overlap) { return overlap > 0.0 && overlap <= 1.0; }   // (a NaN fails both)
-
 int kss_trim_rank(int64_t m, double overlap, int64_t* k) {
     if (!k || m < 0 || !trim_overlap_ok(overlap)) return KSS_ERR_ARG;
     *k = (int64_t)trim_rank_of((long long)m, overlap);
@@ -527,43 +544,25 @@ int kss_trim_threshold(kss_ctx* c, const float* d2, int64_t n, double max_d2, do
     return trim_threshold_dev(c, (const float*)c->stage_d2.p, n, max_d2, overlap, info);
 }
 
-static int trim_check(kss_ctx* c, const void* src, const void* tgt, int64_t ns, int64_t nt, const float* nrm, const kss_icp_params* p,
-                      const kss_trim_params* tp, const kss_icp_result* res) {
-    if (!src || !tgt || !p || !tp || !res) return set_err(c, KSS_ERR_ARG, "icp_trimmed: null argument");
-    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_trimmed: empty cloud");
-    if (ns > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "icp_trimmed: cloud too large");
-    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_trimmed: the source-row split (allreduce) is not available for trimmed ICP");
-    if (!trim_overlap_ok(tp->overlap)) return set_err(c, KSS_ERR_ARG, "icp_trimmed: overlap must be in (0, 1]");
-    if (tp->metric != KSS_METRIC_POINT && tp->metric != KSS_METRIC_PLANE) return set_err(c, KSS_ERR_ARG, "icp_trimmed: unknown metric");
-    if (tp->metric == KSS_METRIC_POINT && nrm) return set_err(c, KSS_ERR_ARG, "icp_trimmed: the point metric takes no normals");
-    return KSS_OK;
-}
-
 int kss_icp_trimmed_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                         const kss_icp_params* p, const kss_trim_params* tp, kss_icp_result* res, double last_info[KSS_TRIM_NINFO]) {
     if (!c) return KSS_ERR_ARG;
-    KCHK(trim_check(c, d_src, d_tgt, ns, nt, d_nrm, p, tp, res));
+    KCHK(pair_check(c, "icp_trimmed", true, d_src, d_tgt, ns, nt, d_nrm, p, tp, res));
     HIPCHK(c, hipSetDevice(c->device));
-    if (tp->metric == KSS_METRIC_PLANE && !d_nrm) {
-        // the target's normals, exactly as kss_icp_p2l_dev computes them
-        const int k = nt < 20 ? (int)nt : 20;
-        KCHK(ensure(c, c->p2l_idx, (size_t)nt * k * sizeof(int32_t)));
-        KCHK(ensure(c, c->p2l_d2, (size_t)nt * k * sizeof(float)));
-        KCHK(ensure(c, c->p2l_n64, (size_t)nt * 3 * sizeof(double)));
-        KCHK(ensure(c, c->p2l_nrm, (size_t)nt * 3 * sizeof(float)));
-        KCHK(knn_generic_dev(c, d_tgt, nt, d_tgt, nt, KSS_F32, k, (int32_t*)c->p2l_idx.p, (float*)c->p2l_d2.p));
-        launch_normals(c->stream, (const float4*)c->src0.p, (int)nt, (const int32_t*)c->p2l_idx.p, k, (double*)c->p2l_n64.p);
-        launch_f64_to_f32(c->stream, (const double*)c->p2l_n64.p, nt * 3, (float*)c->p2l_nrm.p);
-        HIPCHK(c, hipGetLastError());
-        d_nrm = (const float*)c->p2l_nrm.p;
-    }
-    return trim_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, tp->overlap, tp->trace_trim, res, last_info);
+    PairMode mode;
+    mode.plane = tp->metric == KSS_METRIC_PLANE;
+    mode.trimmed = true;
+    mode.overlap = tp->overlap;
+    mode.trace_trim = tp->trace_trim;
+    mode.last_info = last_info;
+    if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
 }
 
 int kss_icp_trimmed(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
                     const kss_icp_params* p, const kss_trim_params* tp, kss_icp_result* res, double last_info[KSS_TRIM_NINFO]) {
     if (!c) return KSS_ERR_ARG;
-    KCHK(trim_check(c, src, tgt, ns, nt, nrm, p, tp, res));
+    KCHK(pair_check(c, "icp_trimmed", true, src, tgt, ns, nt, nrm, p, tp, res));
     HIPCHK(c, hipSetDevice(c->device));
     KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
     KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));

@@ -238,13 +238,18 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // one exact NN pass of a single pair (+ the correspondence sums when sums_out is given)
 int nn_generic_dev(kss_ctx* c, const void* d_src, int64_t ns, const void* d_tgt, int64_t nt, int dtype,
                    int32_t* d_idx, float* d_d2, double sums_out[NSUMS]);
-// point-to-plane ICP of one pair (float clouds and target normals on the device)
-// trimmed ICP of one pair (kss_icp_trimmed): d_nrm null = point metric.  trace_trim / last_info: KSS_TRIM_NINFO doubles per pass
-int trim_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
-                 const kss_icp_params* p, double overlap, double* trace_trim, kss_icp_result* res, double* last_info);
+// ICP of one pair by kss_icp_p2l (plane, untrimmed) or kss_icp_trimmed (either metric): float clouds on the device, d_nrm
+// the target's normals for the plane metric.  The untrimmed point metric is icp_run_dev's.
+struct PairMode {
+    bool plane = false;             // point-to-plane step (d_nrm given); otherwise point-to-point
+    bool trimmed = false;           // keep the closest `overlap` share of each pass's candidates
+    double overlap = 1.0;
+    double* trace_trim = nullptr;   // trimmed: KSS_TRIM_NINFO doubles per traced pass
+    double* last_info = nullptr;    // trimmed: KSS_TRIM_NINFO doubles of the last pass
+};
+int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                 const kss_icp_params* p, const PairMode& mode, kss_icp_result* res);
 int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info);
-int p2l_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
-                const kss_icp_params* p, kss_icp_result* res);
 // host-mapped {value, sequence number} result slots: allocate them; wait for the first nslots of launch c->seq
 int ensure_pub_slots(kss_ctx* c);
 int wait_slots(kss_ctx* c, int nslots, double* out);

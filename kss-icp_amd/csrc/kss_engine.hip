@@ -1077,6 +1077,72 @@ static inline void mirror_state(PairState* bar, int p, const PairState& s) {
     for (int k = 0; k < 4; ++k) _mm_store_si128(d + k, _mm_loadu_si128(v + k));
 }
 
+// ---- what every ICP loop below shares ----
+static inline Convergence convergence_of(const kss_icp_params& P) {   // PCL's criteria as kss_icp_params states them
+    Convergence cv;
+    cv.max_iterations = P.max_iterations;
+    cv.rotation_threshold = 1.0 - P.transformation_epsilon;
+    cv.translation_threshold = P.transformation_epsilon;
+    cv.mse_rel = P.euclidean_fitness_epsilon;
+    cv.mse_abs = P.abs_mse_epsilon;
+    cv.fixed_iterations = P.fixed_iterations != 0;
+    return cv;
+}
+// one row of the caller's trace: the pass's sums (ncol of them), its T_k and, for a trimmed pass, its {m, k, tau, kept}
+static inline void trace_row(const kss_icp_params& P, const double* s, int ncol, const float* tk, double* trace_trim = nullptr,
+                             const double* info = nullptr) {
+    if (!P.trace_n || *P.trace_n >= P.trace_cap) return;
+    if (P.trace_sums) std::memcpy(P.trace_sums + (size_t)(*P.trace_n) * ncol, s, (size_t)ncol * sizeof(double));
+    if (P.trace_Tk) std::memcpy(P.trace_Tk + (size_t)(*P.trace_n) * 16, tk, 16 * sizeof(float));
+    if (trace_trim) std::memcpy(trace_trim + (size_t)(*P.trace_n) * KSS_TRIM_NINFO, info, KSS_TRIM_NINFO * sizeof(double));
+    ++*P.trace_n;
+}
+static inline void fill_result(kss_icp_result& r, const float fin[16], int iterations, int converged, int state, double last_mse,
+                               double fitness, int pair) {
+    std::memcpy(r.T, fin, 16 * sizeof(float));
+    r.iterations = iterations; r.converged = converged; r.state = state;
+    r.last_mse = last_mse; r.fitness = fitness; r.pair_id = pair;
+}
+// getFitnessScore(): NN of final * ORIGINAL input, mean d2 over ALL source points of each pair, into results[p].fitness.
+// fin / iters / state: per pair, as the loop left them.  claim_last: the plan is the one every pass of the loop ran on.
+// d_idx / d_d2 (pl.total_src each; null: not wanted): the pass's correspondences by original source index, pair 0's copied to
+// P.fitness_idx / P.fitness_d2.
+static int fitness_pass(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, const float* fin, const int* iters, const int* state,
+                        bool claim_last, PairState* bar, int32_t* d_idx, float* d_d2, kss_icp_result* results) {
+    const int np = pl.npairs;
+    PairState* hs = (PairState*)c->h_state;
+    // (pad[0]: which work buffer holds the positions of the pair's last pass -- pass k writes cur[k & 1] -- so that the
+    // cell-list pass can measure how far each source is from where its skip state was last brought up to date)
+    const bool claim = claim_last && (pl.grid || pl.gridb);
+    for (int p = 0; p < np; ++p) {
+        set_state(hs[p], fin + (size_t)p * 16, 1, 1);
+        // (a pair that ended without correspondences, or on a singular system, took part in one more pass than it counted: its
+        // last position is in the other buffer -- no claim is made for it, its sources simply search)
+        if (claim && iters[p] >= 1 && state[p] != KSS_STATE_NO_CORRESPONDENCES && state[p] != KSS_STATE_DEGENERATE)
+            hs[p].pad[0] = 1 + ((iters[p] - 1) & 1);
+        mirror_state(bar, p, hs[p]);
+    }
+    c->fit_last = claim;
+    struct FitGuard { kss_ctx* c; ~FitGuard() { c->fit_last = false; } } fit_guard{c};
+    c->gated.want_next = false;
+    KCHK(nn_pass(c, pl, P.nn_fma != 0, (const float4*)c->src0.p, (float4*)c->cur[0].p, P.max_corr_dist * P.max_corr_dist, d_idx, d_d2, true));
+    const double* hsum = (const double*)c->h_sums;
+    if (P.allreduce) {   // mean over ALL source rows of the job
+        double v[2] = {hsum[17], (double)pl.g[0].ns};
+        if (P.allreduce(P.allreduce_user, v, 2) != 0) return set_err(c, KSS_ERR_RCCL, "icp: the allreduce callback failed");
+        results[0].fitness = v[0] / v[1];
+    } else {
+        for (int p = 0; p < np; ++p) results[p].fitness = hsum[(size_t)p * NSUMS + 17] / (double)pl.g[p].ns;
+    }
+    if (d_idx) {
+        const size_t n0 = (size_t)pl.g[0].ns;
+        if (P.fitness_idx) HIPCHK(c, hipMemcpyAsync(P.fitness_idx, d_idx, n0 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (P.fitness_d2) HIPCHK(c, hipMemcpyAsync(P.fitness_d2, d_d2, n0 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return KSS_OK;
+}
+
 // ---- the pair-resident engine (kss_resident.hip), host side ------------------------------------------------------------
 // One launch runs every registration of the batch, one workgroup per pair; the host's part of an ICP iteration -- 20 sums in,
 // 3x3 SVD, convergence tests, transform out -- is served per PAIR as its sums land, by a few threads that each own an
@@ -1302,13 +1368,7 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
     struct PairHost { Convergence cv; float fin[16]; int iters = 0, converged = 0, state = 0, k = 0, phase = PH_ITER, cancelled = 0, parked = 0; double last_mse = 0.0, fitness = 0.0, step0 = 0.0; };
     std::vector<PairHost> H((size_t)np);
     for (int p = 0; p < np; ++p) {
-        Convergence& cv = H[p].cv;
-        cv.max_iterations = P.max_iterations;
-        cv.rotation_threshold = 1.0 - P.transformation_epsilon;
-        cv.translation_threshold = P.transformation_epsilon;
-        cv.mse_rel = P.euclidean_fitness_epsilon;
-        cv.mse_abs = P.abs_mse_epsilon;
-        cv.fixed_iterations = P.fixed_iterations != 0;
+        H[p].cv = convergence_of(P);
         mat4_identity(H[p].fin);
     }
     if (P.trace_n) *P.trace_n = 0;
@@ -1390,11 +1450,7 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
                     const double mse = s[16] / s[0];
                     h.last_mse = mse;
                     if (h.iters == 1) h.step0 = (3.0 - ((double)tk[0] + (double)tk[5] + (double)tk[10])) + std::sqrt((double)tk[3] * tk[3] + (double)tk[7] * tk[7] + (double)tk[11] * tk[11]);   // how far the first step went: 2 (1 - cos angle) + |t|
-                    if (p == 0 && P.trace_n && *P.trace_n < P.trace_cap) {
-                        if (P.trace_sums) std::memcpy(P.trace_sums + (size_t)(*P.trace_n) * NSUMS, s, NSUMS * sizeof(double));
-                        if (P.trace_Tk) std::memcpy(P.trace_Tk + (size_t)(*P.trace_n) * 16, tk, 16 * sizeof(float));
-                        ++*P.trace_n;
-                    }
+                    if (p == 0) trace_row(P, s, NSUMS, tk);
                     const bool done = h.cv.has_converged(h.iters, tk, mse);
                     h.state = h.cv.state;
                     if (done) { h.converged = 1; finished = true; }
@@ -1526,10 +1582,9 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
     HIPCHK(c, hipStreamSynchronize(c->stream));   // every workgroup has left (its last act was the publication just consumed)
     if (c->prof > 0) { c->prof_n[KSS_K_RESIDENT_PASS] += units.load(); }
     for (int p = 0; p < np; ++p) {
-        kss_icp_result& r = results[p];
-        std::memcpy(r.T, H[p].fin, 16 * sizeof(float));
-        r.iterations = H[p].iters; r.converged = H[p].cancelled ? 0 : H[p].converged; r.state = H[p].cancelled ? KSS_STATE_NOT_CONVERGED : H[p].state;
-        r.last_mse = H[p].last_mse; r.fitness = P.compute_fitness && !H[p].cancelled ? H[p].fitness : 0.0; r.pair_id = p;
+        const PairHost& h = H[p];   // (a cancelled candidate: its result will not be looked at)
+        fill_result(results[p], h.fin, h.iters, h.cancelled ? 0 : h.converged, h.cancelled ? KSS_STATE_NOT_CONVERGED : h.state, h.last_mse,
+                    P.compute_fitness && !h.cancelled ? h.fitness : 0.0, p);
     }
     if (judge >= 0) { c->spec_ran = true; c->spec_cancelled = cancel_all.load() != 0; }
     if (a.idx_out) {
@@ -1575,7 +1630,7 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
     const IcpPlan* plan = &pl_in;   // may change to the brute-force plan below
     IcpPlan brute_plan;
     const int np = pl_in.npairs;
-    std::vector<Convergence> conv(np);
+    std::vector<Convergence> conv(np, convergence_of(P));
     std::vector<float> fin((size_t)np * 16), Tk((size_t)np * 16);
     std::vector<int> iters(np, 0), active(np, 1), converged(np, 0), state(np, 0), solved(np, 0), was_active;
     std::vector<double> last_mse(np, 0.0);
@@ -1585,13 +1640,6 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
     float I[16];
     mat4_identity(I);
     for (int p = 0; p < np; ++p) {
-        Convergence& cv = conv[p];
-        cv.max_iterations = P.max_iterations;
-        cv.rotation_threshold = 1.0 - P.transformation_epsilon;
-        cv.translation_threshold = P.transformation_epsilon;
-        cv.mse_rel = P.euclidean_fitness_epsilon;
-        cv.mse_abs = P.abs_mse_epsilon;
-        cv.fixed_iterations = P.fixed_iterations != 0;
         mat4_identity(&fin[(size_t)p * 16]);
         set_state(hs[p], I, 1, 0);
         mirror_state(bar, p, hs[p]);
@@ -1631,11 +1679,7 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
                 ++iters[p];
                 const double mse = s[16] / s[0];
                 last_mse[p] = mse;
-                if (p == 0 && P.trace_n && *P.trace_n < P.trace_cap) {
-                    if (P.trace_sums) std::memcpy(P.trace_sums + (size_t)(*P.trace_n) * NSUMS, s, NSUMS * sizeof(double));
-                    if (P.trace_Tk) std::memcpy(P.trace_Tk + (size_t)(*P.trace_n) * 16, tk, 16 * sizeof(float));
-                    ++*P.trace_n;
-                }
+                if (p == 0) trace_row(P, s, NSUMS, tk);
                 const bool done = conv[p].has_converged(iters[p], tk, mse);
                 state[p] = conv[p].state;
                 solved[p] = 1;
@@ -1725,50 +1769,16 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
         n_active -= fin_now;
         ++it;
     }
-    for (int p = 0; p < np; ++p) {
-        kss_icp_result& r = results[p];
-        std::memcpy(r.T, &fin[(size_t)p * 16], 16 * sizeof(float));
-        r.iterations = iters[p]; r.converged = converged[p]; r.state = state[p];
-        r.last_mse = last_mse[p]; r.fitness = 0.0; r.pair_id = p;
+    for (int p = 0; p < np; ++p) fill_result(results[p], &fin[(size_t)p * 16], iters[p], converged[p], state[p], last_mse[p], 0.0, p);
+    if (!P.compute_fitness) return KSS_OK;
+    int32_t* d_idx = nullptr;
+    float* d_d2 = nullptr;
+    if (P.fitness_idx || P.fitness_d2) {   // per-source correspondences of the fitness pass
+        KCHK(ensure(c, c->stage_idx, (size_t)plan->total_src * sizeof(int32_t)));
+        KCHK(ensure(c, c->stage_d2, (size_t)plan->total_src * sizeof(float)));
+        d_idx = (int32_t*)c->stage_idx.p; d_d2 = (float*)c->stage_d2.p;
     }
-    if (P.compute_fitness) {
-        // getFitnessScore(): NN of final * ORIGINAL input, mean d2 over all source points
-        // (pad[0]: which work buffer holds the positions of the pair's last pass -- pass k writes cur[k & 1] -- so that the
-        // cell-list pass can measure how far each source is from where its skip state was last brought up to date)
-        const bool cell_lists = plan->grid || plan->gridb;
-        for (int p = 0; p < np; ++p) {
-            set_state(hs[p], &fin[(size_t)p * 16], 1, 1);
-            // (a pair that ended without correspondences took part in one more pass than it counted: its last position is in
-            // the other buffer -- no claim is made for it, its sources simply search)
-            if (cell_lists && plan == &pl_in && iters[p] >= 1 && state[p] != KSS_STATE_NO_CORRESPONDENCES) hs[p].pad[0] = 1 + ((iters[p] - 1) & 1);
-            mirror_state(bar, p, hs[p]);
-        }
-        c->fit_last = cell_lists && plan == &pl_in;
-        struct FitGuard { kss_ctx* c; ~FitGuard() { c->fit_last = false; } } fit_guard{c};
-        c->gated.want_next = false;
-        int32_t* d_idx = nullptr;
-        float* d_d2 = nullptr;
-        if (P.fitness_idx || P.fitness_d2) {   // per-source correspondences of this pass (indexed by original source index)
-            KCHK(ensure(c, c->stage_idx, (size_t)plan->total_src * sizeof(int32_t)));
-            KCHK(ensure(c, c->stage_d2, (size_t)plan->total_src * sizeof(float)));
-            d_idx = (int32_t*)c->stage_idx.p; d_d2 = (float*)c->stage_d2.p;
-        }
-        KCHK(nn_pass(c, *plan, P.nn_fma != 0, (const float4*)c->src0.p, (float4*)c->cur[0].p, max_d2, d_idx, d_d2, true));
-        if (P.allreduce) {   // mean over ALL source rows of the job
-            double v[2] = {hsum[17], (double)plan->g[0].ns};
-            if (P.allreduce(P.allreduce_user, v, 2) != 0) return set_err(c, KSS_ERR_RCCL, "icp: the allreduce callback failed");
-            results[0].fitness = v[0] / v[1];
-        } else {
-            for (int p = 0; p < np; ++p) results[p].fitness = hsum[(size_t)p * NSUMS + 17] / (double)plan->g[p].ns;
-        }
-        if (d_idx) {
-            const size_t n0 = (size_t)plan->g[0].ns;
-            if (P.fitness_idx) HIPCHK(c, hipMemcpyAsync(P.fitness_idx, d_idx, n0 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            if (P.fitness_d2) HIPCHK(c, hipMemcpyAsync(P.fitness_d2, d_d2, n0 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-    }
-    return KSS_OK;
+    return fitness_pass(c, *plan, P, fin.data(), iters.data(), state.data(), plan == &pl_in, bar, d_idx, d_d2, results);
 }
 
 // zero-at-rest buffers (kss_ctx.hpp): cleared here when the previous call on this context did not finish
@@ -1832,20 +1842,19 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
     return rc;
 }
 
-// ---- point-to-plane ICP of one pair (kss_icp_p2l): icp_loop's PCL align() with TransformationEstimationPointToPlaneLLS ----
-// Per pass: the NN pass (plain launches; the pending T_k rides in as on the plain point-to-point path) writes idx / d2 by
-// original source index, the two p2l launches reduce the 32 sums into host-mapped memory, one stream synchronisation, then
-// the 6x6 solve and the PCL criteria on the host.  The plan, the packed clouds and the cell list are built once per call.
-static int p2l_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, const float* d_tgt, const float* d_nrm,
-                    const int32_t* d_perm, kss_icp_result* res) {
+// ---- one pair with a metric or a selection the chained point-to-point path does not have: kss_icp_p2l (plane, untrimmed),
+// kss_icp_trimmed (point or plane, the closest `overlap` share of each pass's candidates kept) ----
+// icp_loop's PCL align() for a single pair.  Per pass: the NN pass (plain launches; the pending T_k rides in as on the plain
+// point-to-point path) writes idx / d2 by original source index; trimmed: the radix select over that d2 (four plain launches,
+// tau / m / k stay on the device); the metric's rows + final launches reduce the sums into host-mapped memory (h_p2l: the sums
+// in front, the selection's {m, k, tau, kept} behind KSS_P2L_NSUMS doubles); ONE stream synchronisation; then the solve and
+// the PCL criteria on the host.  Untrimmed plane passes make no selection launches and keep a correspondence by
+// !(d2 > max_d2).  The plan, the packed clouds and the cell list are built once per call.
+static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
+                     const int32_t* d_perm, kss_icp_result* res) {
     const int64_t ns = pl.g[0].ns, nt = pl.g[0].nt;
-    Convergence cv;
-    cv.max_iterations = P.max_iterations;
-    cv.rotation_threshold = 1.0 - P.transformation_epsilon;
-    cv.translation_threshold = P.transformation_epsilon;
-    cv.mse_rel = P.euclidean_fitness_epsilon;
-    cv.mse_abs = P.abs_mse_epsilon;
-    cv.fixed_iterations = P.fixed_iterations != 0;
+    const int ncol = M.plane ? P2L_NSUMS : NSUMS;
+    Convergence cv = convergence_of(P);
     float fin[16], tk[16], I[16];
     mat4_identity(fin);
     mat4_identity(I);
@@ -1854,8 +1863,13 @@ static int p2l_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, cons
     const double max_d2 = P.max_corr_dist * P.max_corr_dist;
     int32_t* d_idx = (int32_t*)c->p2l_idx.p;
     float* d_d2 = (float*)c->p2l_d2.p;
+    double* d_rows = (double*)c->p2l_rows.p;
     const double* hp = (const double*)c->h_p2l;
+    double* d_rec = (double*)c->h_p2l_dev;
+    TrimState* d_state = (TrimState*)c->trim_state.p;
+    const double* d_cut = M.trimmed ? &d_state[TRIM_NSTATE - 1].cut : nullptr;
     if (P.trace_n) *P.trace_n = 0;
+    if (M.last_info) for (int q = 0; q < KSS_TRIM_NINFO; ++q) M.last_info[q] = 0.0;
     int it = 0, iters = 0, state = KSS_STATE_NOT_CONVERGED, converged = 0;
     double last_mse = 0.0;
     GatedGuard gated_guard(c);
@@ -1866,56 +1880,48 @@ static int p2l_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, cons
         KCHK(nn_pass(c, pl, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false));
         {
             ProfScope ps(c, KSS_K_CORR_REDUCE);
-            launch_p2l_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, (double*)c->p2l_rows.p,
-                            (double*)c->h_p2l_dev);
+            if (M.trimmed) launch_trim_select(c->stream, d_d2, ns, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
+            if (M.plane)
+                launch_p2l_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, d_rows, d_rec, d_cut);
+            else
+                launch_trim_point_sums(c->stream, d_out, d_perm, d_idx, d_d2, d_tgt, ns, nt, d_cut, d_rows, d_rec);
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
         ++it;
-        double s[P2L_NSUMS];
-        std::memcpy(s, hp, sizeof s);
+        double s[P2L_NSUMS], info[KSS_TRIM_NINFO] = {};
+        std::memcpy(s, hp, (size_t)ncol * sizeof(double));
+        if (M.trimmed) {
+            std::memcpy(info, hp + P2L_NSUMS, sizeof info);
+            info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
+            if (M.last_info) std::memcpy(M.last_info, info, sizeof info);
+        }
         if ((int)s[0] < P.min_correspondences) { state = KSS_STATE_NO_CORRESPONDENCES; break; }   // PCL: "Not enough correspondences found"
-        if (!rigid_from_p2l_sums(s, tk)) { state = KSS_STATE_DEGENERATE; break; }
+        if (M.plane) {
+            if (!rigid_from_p2l_sums(s, tk)) { state = KSS_STATE_DEGENERATE; break; }
+        } else {
+            rigid_from_sums(s, tk);
+        }
         mat4_mul(tk, fin, fin);   // final = transformation_ * final
         ++iters;
-        const double mse = s[28] / s[0];   // point-to-point d2 of the kept correspondences, as PCL's criteria read it
+        const double mse = (M.plane ? s[28] : s[16]) / s[0];   // point-to-point d2 of the kept correspondences, as PCL's criteria read it
         last_mse = mse;
-        if (P.trace_n && *P.trace_n < P.trace_cap) {
-            if (P.trace_sums) std::memcpy(P.trace_sums + (size_t)(*P.trace_n) * P2L_NSUMS, s, sizeof s);
-            if (P.trace_Tk) std::memcpy(P.trace_Tk + (size_t)(*P.trace_n) * 16, tk, 16 * sizeof(float));
-            ++*P.trace_n;
-        }
+        trace_row(P, s, ncol, tk, M.trimmed ? M.trace_trim : nullptr, info);
         const bool done = cv.has_converged(iters, tk, mse);
         state = cv.state;
         if (done) { converged = 1; break; }
         set_state(hs[0], tk, 1, 1);   // next NN pass applies T_k on load (transformCloud)
     }
-    std::memcpy(res->T, fin, sizeof fin);
-    res->iterations = iters; res->converged = converged; res->state = state;
-    res->last_mse = last_mse; res->fitness = 0.0; res->pair_id = 0;
-    if (P.compute_fitness) {
-        // getFitnessScore(): NN of final * ORIGINAL input, mean d2 over all sources (icp_loop's fitness pass)
-        set_state(hs[0], fin, 1, 1);
-        if (pl.grid && iters >= 1 && state != KSS_STATE_NO_CORRESPONDENCES && state != KSS_STATE_DEGENERATE) hs[0].pad[0] = 1 + ((iters - 1) & 1);
-        c->fit_last = pl.grid;
-        struct FitGuard { kss_ctx* c; ~FitGuard() { c->fit_last = false; } } fit_guard{c};
-        const bool corr = P.fitness_idx || P.fitness_d2;
-        KCHK(nn_pass(c, pl, P.nn_fma != 0, (const float4*)c->src0.p, (float4*)c->cur[0].p, max_d2, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, true));
-        res->fitness = ((const double*)c->h_sums)[17] / (double)ns;
-        if (corr) {
-            if (P.fitness_idx) HIPCHK(c, hipMemcpyAsync(P.fitness_idx, d_idx, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            if (P.fitness_d2) HIPCHK(c, hipMemcpyAsync(P.fitness_d2, d_d2, (size_t)ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-    }
-    return KSS_OK;
+    fill_result(*res, fin, iters, converged, state, last_mse, 0.0, 0);
+    if (!P.compute_fitness) return KSS_OK;
+    const bool corr = P.fitness_idx || P.fitness_d2;
+    return fitness_pass(c, pl, P, fin, &iters, &state, true, nullptr, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, res);
 }
 
-int p2l_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
-                const kss_icp_params* p, kss_icp_result* res) {
-    if (!c || !d_src || !d_tgt || !d_nrm || !p || !res) return set_err(c, KSS_ERR_ARG, "icp_p2l: bad argument");
-    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_p2l: empty cloud");
-    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_p2l: the source-row split (allreduce) is not available for point-to-plane");
+// (the arguments are the entry points' to check: kss_api.hip)
+int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                 const kss_icp_params* p, const PairMode& M, kss_icp_result* res) {
+    if (!M.plane && !M.trimmed) return set_err(c, KSS_ERR_ARG, "pair_run: the untrimmed point metric is kss_icp's");
     HIPCHK(c, hipSetDevice(c->device));
     IcpPlan pl;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1927,7 +1933,11 @@ int p2l_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, 
     KCHK(ensure(c, c->p2l_idx, (size_t)ns * sizeof(int32_t)));
     KCHK(ensure(c, c->p2l_d2, (size_t)ns * sizeof(float)));
     KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(ns) * P2L_NSUMS * sizeof(double)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
+    if (M.trimmed) {
+        KCHK(ensure(c, c->trim_rows, trim_rows_bytes(ns)));
+        KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
+    }
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
     const int64_t so[2] = {0, ns}, to[2] = {0, nt};
     KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));
     KCHK(grid_setup(c, pl));
@@ -1939,143 +1949,7 @@ int p2l_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, 
         d_perm = (const int32_t*)c->p2l_perm.p;
     }
     const auto t1 = std::chrono::steady_clock::now();
-    const int rc = p2l_loop(c, pl, *p, d_tgt, d_nrm, d_perm, res);
-    guard.ok = rc == KSS_OK;
-    const auto t2 = std::chrono::steady_clock::now();
-    c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    return rc;
-}
-
-// ---- trimmed ICP of one pair (kss_icp_trimmed): p2l_loop with the closest `overlap` share of the pass's
-// candidates kept.  Per pass: the NN pass as in p2l_loop, the radix select over its d2 output (four plain launches, tau / m / k
-// stay on the device), the rows + final launches of the metric reading the cut from there, ONE stream synchronisation, then
-// the solve and the PCL criteria on the host.  The record and {m, k, tau, kept} arrive in host-mapped memory (h_p2l: the sums
-// in front, the info behind KSS_P2L_NSUMS doubles).  plane: d_nrm given; point: d_nrm null.
-static int trim_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, double overlap, const float* d_tgt, const float* d_nrm,
-                     const int32_t* d_perm, double* trace_trim, kss_icp_result* res, double* last_info) {
-    const int64_t ns = pl.g[0].ns, nt = pl.g[0].nt;
-    const bool plane = d_nrm != nullptr;
-    const int ncol = plane ? P2L_NSUMS : NSUMS;
-    Convergence cv;
-    cv.max_iterations = P.max_iterations;
-    cv.rotation_threshold = 1.0 - P.transformation_epsilon;
-    cv.translation_threshold = P.transformation_epsilon;
-    cv.mse_rel = P.euclidean_fitness_epsilon;
-    cv.mse_abs = P.abs_mse_epsilon;
-    cv.fixed_iterations = P.fixed_iterations != 0;
-    float fin[16], tk[16], I[16];
-    mat4_identity(fin);
-    mat4_identity(I);
-    PairState* hs = (PairState*)c->h_state;
-    set_state(hs[0], I, 1, 0);
-    const double max_d2 = P.max_corr_dist * P.max_corr_dist;
-    int32_t* d_idx = (int32_t*)c->p2l_idx.p;
-    float* d_d2 = (float*)c->p2l_d2.p;
-    const double* hp = (const double*)c->h_p2l;
-    double* d_rec = (double*)c->h_p2l_dev;
-    TrimState* d_state = (TrimState*)c->trim_state.p;
-    const double* d_cut = &d_state[TRIM_NSTATE - 1].cut;
-    if (P.trace_n) *P.trace_n = 0;
-    if (last_info) for (int q = 0; q < KSS_TRIM_NINFO; ++q) last_info[q] = 0.0;
-    int it = 0, iters = 0, state = KSS_STATE_NOT_CONVERGED, converged = 0;
-    double last_mse = 0.0;
-    GatedGuard gated_guard(c);
-    c->gated.want_next = false;
-    while (P.max_iterations > 0) {
-        const float4* d_in = it == 0 ? (const float4*)c->src0.p : (const float4*)c->cur[(it - 1) & 1].p;
-        float4* d_out = (float4*)c->cur[it & 1].p;
-        KCHK(nn_pass(c, pl, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false));
-        {
-            ProfScope ps(c, KSS_K_CORR_REDUCE);
-            launch_trim_select(c->stream, d_d2, ns, max_d2, overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
-            if (plane)
-                launch_p2l_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, (double*)c->p2l_rows.p, d_rec, d_cut);
-            else
-                launch_trim_point_sums(c->stream, d_out, d_perm, d_idx, d_d2, d_tgt, ns, nt, d_cut, (double*)c->p2l_rows.p, d_rec);
-        }
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        ++it;
-        double s[P2L_NSUMS], info[KSS_TRIM_NINFO];
-        std::memcpy(s, hp, (size_t)ncol * sizeof(double));
-        std::memcpy(info, hp + P2L_NSUMS, sizeof info);
-        info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
-        if (last_info) std::memcpy(last_info, info, sizeof info);
-        if ((int)s[0] < P.min_correspondences) { state = KSS_STATE_NO_CORRESPONDENCES; break; }
-        if (plane) {
-            if (!rigid_from_p2l_sums(s, tk)) { state = KSS_STATE_DEGENERATE; break; }
-        } else {
-            rigid_from_sums(s, tk);
-        }
-        mat4_mul(tk, fin, fin);   // final = transformation_ * final
-        ++iters;
-        const double mse = (plane ? s[28] : s[16]) / s[0];
-        last_mse = mse;
-        if (P.trace_n && *P.trace_n < P.trace_cap) {
-            if (P.trace_sums) std::memcpy(P.trace_sums + (size_t)(*P.trace_n) * ncol, s, (size_t)ncol * sizeof(double));
-            if (P.trace_Tk) std::memcpy(P.trace_Tk + (size_t)(*P.trace_n) * 16, tk, 16 * sizeof(float));
-            if (trace_trim) std::memcpy(trace_trim + (size_t)(*P.trace_n) * KSS_TRIM_NINFO, info, sizeof info);
-            ++*P.trace_n;
-        }
-        const bool done = cv.has_converged(iters, tk, mse);
-        state = cv.state;
-        if (done) { converged = 1; break; }
-        set_state(hs[0], tk, 1, 1);   // next NN pass applies T_k on load (transformCloud)
-    }
-    std::memcpy(res->T, fin, sizeof fin);
-    res->iterations = iters; res->converged = converged; res->state = state;
-    res->last_mse = last_mse; res->fitness = 0.0; res->pair_id = 0;
-    if (P.compute_fitness) {
-        // getFitnessScore() over ALL sources, as in p2l_loop
-        set_state(hs[0], fin, 1, 1);
-        if (pl.grid && iters >= 1 && state != KSS_STATE_NO_CORRESPONDENCES && state != KSS_STATE_DEGENERATE) hs[0].pad[0] = 1 + ((iters - 1) & 1);
-        c->fit_last = pl.grid;
-        struct FitGuard { kss_ctx* c; ~FitGuard() { c->fit_last = false; } } fit_guard{c};
-        const bool corr = P.fitness_idx || P.fitness_d2;
-        KCHK(nn_pass(c, pl, P.nn_fma != 0, (const float4*)c->src0.p, (float4*)c->cur[0].p, max_d2, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, true));
-        res->fitness = ((const double*)c->h_sums)[17] / (double)ns;
-        if (corr) {
-            if (P.fitness_idx) HIPCHK(c, hipMemcpyAsync(P.fitness_idx, d_idx, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            if (P.fitness_d2) HIPCHK(c, hipMemcpyAsync(P.fitness_d2, d_d2, (size_t)ns * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-        }
-    }
-    return KSS_OK;
-}
-
-int trim_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
-                 const kss_icp_params* p, double overlap, double* trace_trim, kss_icp_result* res, double* last_info) {
-    if (!c || !d_src || !d_tgt || !p || !res) return set_err(c, KSS_ERR_ARG, "icp_trimmed: bad argument");
-    if (ns <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "icp_trimmed: empty cloud");
-    if (!(overlap > 0.0 && overlap <= 1.0)) return set_err(c, KSS_ERR_ARG, "icp_trimmed: overlap must be in (0, 1]");
-    if (p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_trimmed: the source-row split (allreduce) is not available for trimmed ICP");
-    HIPCHK(c, hipSetDevice(c->device));
-    IcpPlan pl;
-    const auto t0 = std::chrono::steady_clock::now();
-    KCHK(restore_zero_at_rest(c));
-    DirtyGuard guard(c);
-    c->timing = false;
-    KCHK(build_plan(c, &ns, &nt, 1, false, p->nn_sources_per_thread, p->nn_target_splits, p->nn_mode, pl));
-    KCHK(stage_plan(c, pl));
-    KCHK(ensure(c, c->p2l_idx, (size_t)ns * sizeof(int32_t)));
-    KCHK(ensure(c, c->p2l_d2, (size_t)ns * sizeof(float)));
-    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(ns) * P2L_NSUMS * sizeof(double)));
-    KCHK(ensure(c, c->trim_rows, trim_rows_bytes(ns)));
-    KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
-    const int64_t so[2] = {0, ns}, to[2] = {0, nt};
-    KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));
-    KCHK(grid_setup(c, pl));
-    const int32_t* d_perm = nullptr;
-    if (pl.src_in_cell_order) {
-        KCHK(ensure(c, c->p2l_perm, (size_t)ns * sizeof(int32_t)));
-        launch_p2l_perm(c->stream, (const float4*)c->src0.p + pl.g[0].src_base, ns, (int32_t*)c->p2l_perm.p);
-        HIPCHK(c, hipGetLastError());
-        d_perm = (const int32_t*)c->p2l_perm.p;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    const int rc = trim_loop(c, pl, *p, overlap, d_tgt, d_nrm, d_perm, trace_trim, res, last_info);
+    const int rc = pair_loop(c, pl, *p, M, d_tgt, d_nrm, d_perm, res);
     guard.ok = rc == KSS_OK;
     const auto t2 = std::chrono::steady_clock::now();
     c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();

@@ -2,12 +2,12 @@
 """Trimmed ICP (kss_icp_trimmed_dev) per pass, both metrics at overlap 1.0 and 0.5, next to kss_icp_p2l_dev / kss_icp_dev:
 us per pass in fixed-iteration mode (difference of a 50- and a 100-pass run, so setup and the first pass drop out), on the
 bumpy 100k x 100k pair of tools/p2l_time.py and on partial pair 1 of the tests scaled to n = 200000.  With --baseline LIB
-the two untrimmed entry points are also timed from that build of libkssicp.so (the parent commit's), loaded beside the
-current one; all variants run alternately, --rounds times, and the median is reported with the spread.  The comparison
+every variant is also timed from that build of libkssicp.so (the parent commit's), loaded beside the current one
+(binding.load_library(path)); all variants run alternately, --rounds times, and the median is reported with the spread.  The comparison
 that matters: trimmed plane pass minus kss_icp_p2l pass = the cost of the selection.  Then PCL mode (iterations, error
 against the true motion).  Under rocprofv3 --kernel-trace --stats the per-kernel times come from the trace.
 usage: python tools/trim_time.py [--baseline path/to/parent/libkssicp.so] [--rounds 5] [--passes 50] [--quick]"""
-import argparse, ctypes as C, os, sys, time
+import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as g
@@ -23,26 +23,8 @@ ctx = pkg.Context(0)
 if args.quick:
     args.rounds = 1
 
-base = None
-if args.baseline:
-    # the parent build exports the untrimmed entry points only: bind just those
-    BL = C.CDLL(os.path.abspath(args.baseline))
-    vp, i64 = C.c_void_p, C.c_int64
-    BL.kss_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
-    BL.kss_ctx_destroy.argtypes = [vp]
-    BL.kss_icp_dev.argtypes = [vp, vp, i64, vp, i64, C.POINTER(B.IcpParams), C.POINTER(B.IcpResult)]
-    BL.kss_icp_p2l_dev.argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(B.IcpParams), C.POINTER(B.IcpResult)]
-    base = vp()
-    if BL.kss_ctx_create(0, C.byref(base)) != 0:
-        raise SystemExit("baseline library: kss_ctx_create failed")
-
-
-def base_run(name, *a):
-    res = B.IcpResult()
-    rc = getattr(BL, name)(base, *a, C.byref(res))
-    if rc != 0:
-        raise SystemExit("baseline %s failed: %d" % (name, rc))
-    return res
+# the parent commit's build, loaded beside the current one: every variant is timed from both
+base = pkg.Context(0, lib=B.load_library(args.baseline)) if args.baseline else None
 
 
 def timed(fn):
@@ -62,26 +44,31 @@ for name, src, tgt, R, t in (("bumpy", *S.make_pair(0, 100000, R=Rb, t=tb, shape
     ds, dt, dn = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (src, tgt, nrm))
     print("== %s, %d x %d" % (name, ns, nt), flush=True)
     a = (ds.data_ptr(), ns, dt.data_ptr(), nt)
-    runs = {"p2p": lambda p: ctx.icp_dev(*a, p),
-            "p2l": lambda p: ctx.icp_p2l_dev(*a, dn.data_ptr(), p)}
-    if base:
-        runs["p2p parent"] = lambda p: base_run("kss_icp_dev", *a, C.byref(p))
-        runs["p2l parent"] = lambda p: base_run("kss_icp_p2l_dev", *a, dn.data_ptr(), C.byref(p))
+    variants = {"p2p": lambda cx, p: cx.icp_dev(*a, p),
+                "p2l": lambda cx, p: cx.icp_p2l_dev(*a, dn.data_ptr(), p)}
     for ov in (1.0, 0.5):
-        runs["trim point %.1f" % ov] = lambda p, ov=ov: ctx.icp_trimmed_dev(*a, None, p, overlap=ov, metric=pkg.METRIC_POINT)[0]
-        runs["trim plane %.1f" % ov] = lambda p, ov=ov: ctx.icp_trimmed_dev(*a, dn.data_ptr(), p, overlap=ov, metric=pkg.METRIC_PLANE)[0]
+        variants["trim point %.1f" % ov] = lambda cx, p, ov=ov: cx.icp_trimmed_dev(*a, None, p, overlap=ov, metric=pkg.METRIC_POINT)[0]
+        variants["trim plane %.1f" % ov] = lambda cx, p, ov=ov: cx.icp_trimmed_dev(*a, dn.data_ptr(), p, overlap=ov, metric=pkg.METRIC_PLANE)[0]
+    runs = {}      # each variant from this build, then from the parent's
+    for k, v in variants.items():
+        runs[k] = lambda p, v=v: v(ctx, p)
+        if base:
+            runs[k + " parent"] = lambda p, v=v: v(base, p)
     P = [ctx.icp_params(max_iterations=it, fixed_iterations=1, compute_fitness=0) for it in (args.passes, 2 * args.passes)]
     for run in runs.values():      # warm-up of every variant and shape (allocations, cell list sizes)
         for p in P:
             run(p)
     per = {k: [] for k in runs}
-    for _ in range(args.rounds):
-        for k, run in runs.items():
-            ts = [timed(lambda: run(p))[1] for p in P]
+    for r in range(args.rounds):
+        order = list(runs)
+        if base and r % 2:      # the parent's first in every other round: whichever build runs second finds the caches warm
+            order = [k for i in range(0, len(order), 2) for k in (order[i + 1], order[i])]
+        for k in order:
+            ts = [timed(lambda: runs[k](p))[1] for p in P]
             per[k].append((ts[1] - ts[0]) / args.passes * 1e6)
     med = {k: float(np.median(v)) for k, v in per.items()}
     for k, v in per.items():
-        print("%-16s %7.1f us per pass  (min %.1f, max %.1f over %d rounds)" % (k, med[k], min(v), max(v), len(v)), flush=True)
+        print("%-22s %7.1f us per pass  (min %.1f, max %.1f over %d rounds)" % (k, med[k], min(v), max(v), len(v)), flush=True)
     print("selection = trim plane 1.0 - p2l: %.1f us;  trim plane 0.5 - p2l: %.1f us;  trim point 1.0 - p2p: %.1f us" % (
         med["trim plane 1.0"] - med["p2l"], med["trim plane 0.5"] - med["p2l"], med["trim point 1.0"] - med["p2p"]), flush=True)
     if args.quick:
@@ -90,8 +77,8 @@ for name, src, tgt, R, t in (("bumpy", *S.make_pair(0, 100000, R=Rb, t=tb, shape
     for k, run in runs.items():
         r, dt_s = timed(lambda: run(ctx.icp_params(max_iterations=200)))
         T = r.matrix()
-        print("%-16s PCL mode: %3d iterations, state %d, fitness %.3e, |R - R_true| %.2e, |t - t_true| %.2e, %.2f ms"
+        print("%-22s PCL mode: %3d iterations, state %d, fitness %.3e, |R - R_true| %.2e, |t - t_true| %.2e, %.2f ms"
               % (k, r.iterations, r.state, r.fitness, np.abs(T[:3, :3] - R_true).max(), np.abs(T[:3, 3] - t_true).max(), dt_s * 1e3), flush=True)
 if base:
-    BL.kss_ctx_destroy(base)
+    base.close()
 ctx.close()
