@@ -295,6 +295,33 @@ int kss_icp_trimmed(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt
 int kss_icp_trimmed_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
                         const kss_icp_params *p, const kss_trim_params *tp, kss_icp_result *res, double last_info[KSS_TRIM_NINFO]);
 
+/* ---- the two ICP steps above for MANY pairs per call ----
+ * Arguments as kss_icp_batch: packed float[n][3] clouds and npairs + 1 HOST offsets in points; tgt_normals_all is laid out like
+ * tgt_all (NULL: computed per target as kss_icp_p2l does; the point metric takes none).  Nothing is redefined: the definitions at
+ * kss_icp_p2l and kss_icp_trimmed hold for every pair, and every pair's record is the single-pair call's BIT FOR BIT (fitness:
+ * to the rounding of the NN engine's own summation order), in any batch order and any split over calls; results[i].pair_id = i.
+ * The pairs run in lockstep, three launches per pass behind the NN pass whatever the pair count; a pair that ends -- converged,
+ * KSS_STATE_NO_CORRESPONDENCES, KSS_STATE_DEGENERATE -- leaves the others untouched.  overlaps: one per pair, or NULL for
+ * tp->overlap everywhere.  info_all: npairs * KSS_TRIM_NINFO doubles, every pair's last selection record (may be NULL).  trace_*,
+ * tp->trace_trim and fitness_idx / fitness_d2 describe pair 0.  KSS_ERR_ARG: a set allreduce, an overlap outside (0, 1], normals
+ * with the point metric, an empty pair. */
+int kss_icp_p2l_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *tgt_all, const int64_t *tgt_off,
+                      const float *tgt_normals_all, int npairs, const kss_icp_params *p, kss_icp_result *results);
+int kss_icp_p2l_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_tgt_all, const int64_t *tgt_off,
+                          const float *d_tgt_normals_all, int npairs, const kss_icp_params *p, kss_icp_result *results);
+int kss_icp_trimmed_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *tgt_all, const int64_t *tgt_off,
+                          const float *tgt_normals_all, int npairs, const kss_icp_params *p, const kss_trim_params *tp,
+                          const double *overlaps, kss_icp_result *results, double *info_all);
+int kss_icp_trimmed_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_tgt_all, const int64_t *tgt_off,
+                              const float *d_tgt_normals_all, int npairs, const kss_icp_params *p, const kss_trim_params *tp,
+                              const double *overlaps, kss_icp_result *results, double *info_all);
+/* the selection alone for nseg segments [off[i], off[i + 1]) of d2_all in ONE launch: overlaps and info_all (nseg * KSS_TRIM_NINFO)
+ * hold one entry per segment; every record equals kss_trim_threshold on that segment.  An empty segment is KSS_ERR_ARG. */
+int kss_trim_threshold_batch(kss_ctx *ctx, const float *d2_all, const int64_t *off, int nseg, double max_d2,
+                             const double *overlaps, double *info_all);
+int kss_trim_threshold_batch_dev(kss_ctx *ctx, const float *d_d2_all, const int64_t *off, int nseg, double max_d2,
+                                 const double *overlaps, double *info_all);
+
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);
 int kss_transform_apply_dev(kss_ctx *ctx, const float T[16], const double *d_in, int64_t n, double *d_out);

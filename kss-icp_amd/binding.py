@@ -33,6 +33,8 @@ SYMBOLS = [
     "kss_pcr_qm", "kss_register", "kss_register_batch", "kss_gather_results", "kss_rccl_allreduce_sum", "kss_transform_apply_f32", "kss_downsample_fps", "kss_downsample_aivs", "kss_downsample_aivs_pair", "kss_downsample_octree", "kss_knn", "kss_knn_dev", "kss_normals", "kss_normals_orient",
     "kss_p2l_sums", "kss_p2l_sums_dev", "kss_rigid_from_p2l_sums", "kss_icp_p2l", "kss_icp_p2l_dev",
     "kss_trim_rank", "kss_trim_threshold", "kss_trim_threshold_dev", "kss_icp_trimmed", "kss_icp_trimmed_dev",
+    "kss_icp_p2l_batch", "kss_icp_p2l_batch_dev", "kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev",
+    "kss_trim_threshold_batch", "kss_trim_threshold_batch_dev",
 ]
 
 
@@ -143,6 +145,12 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, i64, dbl, dbl, vp]
     for n in ("kss_icp_trimmed", "kss_icp_trimmed_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(TrimParams), C.POINTER(IcpResult), vp]
+    for n in ("kss_icp_p2l_batch", "kss_icp_p2l_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), vp]
+    for n in ("kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(TrimParams), vp, vp, vp]
+    for n in ("kss_trim_threshold_batch", "kss_trim_threshold_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, C.c_int, dbl, vp, vp]
     for n in ("kss_rotation_search", "kss_rotation_search_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, dbl, vp, i64, C.POINTER(C.c_int)]
     L.kss_grid_angles.argtypes = [dbl, vp, C.c_int]
@@ -533,6 +541,134 @@ class Context:
                                              C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(tp),
                                              C.byref(res), _p(info)), "kss_icp_trimmed_dev")
         return res, info
+
+    # ---- point-to-plane and trimmed ICP, many pairs per call
+    def _batch_call(self, call, where, p, so, ncol, trace_cap, fitness_corr, tp=None):
+        """call(res) for a batch: the trace and fitness_corr arrays (pair 0's) attached to p / tp as in _icp_call, detached again
+        whether it returns or raises.  Returns (list of IcpResult, extras of pair 0)."""
+        npairs = len(so) - 1
+        res = (IcpResult * npairs)()
+        ns0 = int(so[1] - so[0]) if npairs > 0 else 0
+        tr = fc = None
+        try:
+            if fitness_corr:
+                fc = (np.full(ns0, -1, np.int32), np.full(ns0, np.nan, np.float32))
+                p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
+                p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
+            if trace_cap > 0:
+                tr = (np.zeros((trace_cap, ncol), np.float64), np.zeros((trace_cap, 16), np.float32), C.c_int(0),
+                      np.zeros((trace_cap, TRIM_NINFO), np.float64) if tp is not None else None)
+                p.trace_sums = tr[0].ctypes.data_as(C.POINTER(C.c_double))
+                p.trace_Tk = tr[1].ctypes.data_as(C.POINTER(C.c_float))
+                p.trace_cap = trace_cap
+                p.trace_n = C.pointer(tr[2])
+                if tp is not None:
+                    tp.trace_trim = tr[3].ctypes.data_as(C.POINTER(C.c_double))
+            self._chk(call(C.cast(res, C.c_void_p)), where)
+        finally:
+            if tr:
+                p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
+            if fc:
+                p.fitness_idx = None; p.fitness_d2 = None
+        extra = {}
+        if tr:
+            n = tr[2].value
+            extra["trace_sums"] = tr[0][:n].copy()
+            extra["trace_Tk"] = tr[1][:n].reshape(-1, 4, 4).copy()
+            if tp is not None:
+                extra["trace_trim"] = tr[3][:n].copy()
+        if fc:
+            extra["fitness_idx"], extra["fitness_d2"] = fc
+        return list(res), extra
+
+    @staticmethod
+    def _offsets(src_off, tgt_off):
+        so = np.ascontiguousarray(src_off, dtype=np.int64)
+        to = np.ascontiguousarray(tgt_off, dtype=np.int64)
+        if len(so) != len(to) or len(so) < 1:
+            raise ValueError("src_off and tgt_off must hold npairs + 1 entries each")
+        return so, to
+
+    @staticmethod
+    def _overlaps(overlaps, npairs):
+        if overlaps is None:
+            return None
+        ov = np.ascontiguousarray(overlaps, dtype=np.float64).reshape(-1)
+        if len(ov) != npairs:
+            raise ValueError("overlaps must hold one entry per pair")
+        return ov
+
+    def icp_p2l_batch(self, src_all, src_off, tgt_all, tgt_off, normals_all=None, params=None, trace_cap=0, fitness_corr=False):
+        """kss_icp_p2l_batch: point-to-plane ICP of npairs pairs in one call (packed clouds, npairs + 1 offsets in points; normals_all
+        laid out like tgt_all, or None to have them computed).  Returns (list of IcpResult, dictionary with pair 0's trace_sums /
+        trace_Tk / fitness_idx / fitness_d2 where asked for)."""
+        s, t = _f32(src_all), _f32(tgt_all)
+        nr = _f32(normals_all) if normals_all is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        so, to = self._offsets(src_off, tgt_off)
+        p = params if params is not None else self.icp_params()
+        return self._batch_call(lambda res: self.L.kss_icp_p2l_batch(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), len(so) - 1, C.byref(p), res),
+                                "kss_icp_p2l_batch", p, so, P2L_NSUMS, trace_cap, fitness_corr)
+
+    def icp_p2l_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params):
+        """kss_icp_p2l_batch_dev on device pointers (d_normals_all may be 0 / None); returns the list of IcpResult."""
+        so, to = self._offsets(src_off, tgt_off)
+        res = (IcpResult * (len(so) - 1))()
+        self._chk(self.L.kss_icp_p2l_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
+                                               C.c_void_p(int(d_normals_all)) if d_normals_all else None, len(so) - 1, C.byref(params),
+                                               C.cast(res, C.c_void_p)), "kss_icp_p2l_batch_dev")
+        return list(res)
+
+    def icp_trimmed_batch(self, src_all, src_off, tgt_all, tgt_off, normals_all=None, overlaps=None, overlap=0.5, metric=METRIC_POINT,
+                          params=None, trace_cap=0, fitness_corr=False):
+        """kss_icp_trimmed_batch: trimmed ICP of npairs pairs in one call.  overlaps: one per pair, or None for `overlap` everywhere.
+        Returns (list of IcpResult, trim_info of every pair as npairs x TRIM_NINFO, dictionary with pair 0's traces)."""
+        s, t = _f32(src_all), _f32(tgt_all)
+        nr = _f32(normals_all) if normals_all is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        ov = self._overlaps(overlaps, npairs)
+        p = params if params is not None else self.icp_params()
+        tp = TrimParams(float(overlap), int(metric), None)
+        info = np.zeros((max(npairs, 0), TRIM_NINFO), np.float64)
+        res, extra = self._batch_call(
+            lambda res: self.L.kss_icp_trimmed_batch(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), npairs, C.byref(p), C.byref(tp), _p(ov), res, _p(info)),
+            "kss_icp_trimmed_batch", p, so, P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, tp)
+        return res, info, extra
+
+    def icp_trimmed_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params, overlaps=None, overlap=0.5,
+                              metric=METRIC_POINT):
+        """kss_icp_trimmed_batch_dev on device pointers; returns (list of IcpResult, trim_info npairs x TRIM_NINFO)."""
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        ov = self._overlaps(overlaps, npairs)
+        res = (IcpResult * npairs)()
+        tp = TrimParams(float(overlap), int(metric), None)
+        info = np.zeros((npairs, TRIM_NINFO), np.float64)
+        self._chk(self.L.kss_icp_trimmed_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
+                                                   C.c_void_p(int(d_normals_all)) if d_normals_all else None, npairs, C.byref(params),
+                                                   C.byref(tp), _p(ov), C.cast(res, C.c_void_p), _p(info)), "kss_icp_trimmed_batch_dev")
+        return list(res), info
+
+    def trim_threshold_batch(self, d2_all, off, overlaps, max_d2=1.0):
+        """kss_trim_threshold_batch: {m, k, tau, kept} of every segment [off[i], off[i + 1]) of d2_all, nseg x TRIM_NINFO."""
+        d = np.ascontiguousarray(d2_all, dtype=np.float32).reshape(-1)
+        o = np.ascontiguousarray(off, dtype=np.int64)
+        ov = self._overlaps(overlaps, len(o) - 1)
+        info = np.zeros((max(len(o) - 1, 0), TRIM_NINFO), np.float64)
+        self._chk(self.L.kss_trim_threshold_batch(self.h, _p(d), _p(o), len(o) - 1, float(max_d2), _p(ov), _p(info)), "kss_trim_threshold_batch")
+        return info
+
+    def trim_threshold_batch_dev(self, d_d2_all, off, overlaps, max_d2=1.0):
+        o = np.ascontiguousarray(off, dtype=np.int64)
+        ov = self._overlaps(overlaps, len(o) - 1)
+        info = np.zeros((max(len(o) - 1, 0), TRIM_NINFO), np.float64)
+        self._chk(self.L.kss_trim_threshold_batch_dev(self.h, C.c_void_p(int(d_d2_all)), _p(o), len(o) - 1, float(max_d2), _p(ov), _p(info)),
+                  "kss_trim_threshold_batch_dev")
+        return info
 
     def icp_dev(self, d_src, ns, d_tgt, nt, params):
         res = IcpResult()

@@ -1,5 +1,5 @@
 // kss_api.hip -- the C-ABI of include/kssicp.h: context and profiling entry points, and the compute entry points over
-// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree .hip).
+// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_pairb .hip).
 // There is no CPU compute fallback anywhere in this file.
 #pragma clang fp contract(off)
 
@@ -66,7 +66,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -464,17 +464,33 @@ int kss_rigid_from_p2l_sums(const double sums[KSS_P2L_NSUMS], float T[16]) {
 // ---- what kss_icp_p2l[_dev] and kss_icp_trimmed[_dev] share ----
 static inline bool trim_overlap_ok(double overlap) { return overlap > 0.0 && overlap <= 1.0; }   // (a NaN fails both)
 
-// the argument check of both families.  who: the name the messages carry; tp: null for kss_icp_p2l
+// the argument check of both families, single pair and batch.  who: the name the messages carry; tp: null for kss_icp_p2l.
+// Batch (src_off given): ns / nt are not read, every pair's counts come from the npairs + 1 offsets, and overlaps (may be null:
+// tp->overlap for every pair) holds one overlap per pair.
 static int pair_check(kss_ctx* c, const char* who, bool trimmed, const void* src, const void* tgt, int64_t ns, int64_t nt, const float* nrm,
-                      const kss_icp_params* p, const kss_trim_params* tp, const kss_icp_result* res) {
+                      const kss_icp_params* p, const kss_trim_params* tp, const kss_icp_result* res,
+                      const int64_t* src_off = nullptr, const int64_t* tgt_off = nullptr, int npairs = 1, const double* overlaps = nullptr) {
     const std::string w = std::string(who) + ": ";
     auto bad = [&](const std::string& what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
     if (!src || !tgt || !p || !res || (trimmed && !tp)) return bad("null argument");
-    if (ns <= 0 || nt <= 0) return bad("empty cloud");
-    if (ns > 0x7fff0000ll || nt > 0x7fff0000ll) return bad("cloud too large");
+    if (src_off) {
+        if (!tgt_off || npairs <= 0) return bad("bad batch");
+        for (int i = 0; i < npairs; ++i) {
+            const int64_t n = src_off[i + 1] - src_off[i], m = tgt_off[i + 1] - tgt_off[i];
+            if (n <= 0 || m <= 0) return bad("empty pair");
+            if (n > 0x7fff0000ll || m > 0x7fff0000ll) return bad("cloud too large");
+        }
+        if (src_off[npairs] - src_off[0] > 0x7fff0000ll || tgt_off[npairs] - tgt_off[0] > 0x7fff0000ll) return bad("batch too large");
+    } else {
+        if (ns <= 0 || nt <= 0) return bad("empty cloud");
+        if (ns > 0x7fff0000ll || nt > 0x7fff0000ll) return bad("cloud too large");
+    }
     if (p->allreduce) return bad(std::string("the source-row split (allreduce) is not available for ") + (trimmed ? "trimmed ICP" : "point-to-plane"));
     if (!trimmed) return KSS_OK;
-    if (!trim_overlap_ok(tp->overlap)) return bad("overlap must be in (0, 1]");
+    if (overlaps) {
+        for (int i = 0; i < npairs; ++i)
+            if (!trim_overlap_ok(overlaps[i])) return bad("overlap must be in (0, 1]");
+    } else if (!trim_overlap_ok(tp->overlap)) return bad("overlap must be in (0, 1]");
     if (tp->metric != KSS_METRIC_POINT && tp->metric != KSS_METRIC_PLANE) return bad("unknown metric");
     if (tp->metric == KSS_METRIC_POINT && nrm) return bad("the point metric takes no normals");
     return KSS_OK;
@@ -569,6 +585,116 @@ int kss_icp_trimmed(kss_ctx* c, const float* src, int64_t ns, const float* tgt, 
     if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
     return kss_icp_trimmed_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
                                p, tp, res, last_info);
+}
+
+// ---- the same for many pairs per call ------------------------------------------------
+// Every pair's normals where the caller gave none: target_normals_dev pair after pair into one packed buffer laid out like
+// the targets (setup cost of the call, not optimised: a k-NN and a normals launch per pair).
+static int batch_normals_dev(kss_ctx* c, const float* d_tgt, const int64_t* tgt_off, int npairs, const float** d_nrm) {
+    KCHK(ensure(c, c->pb_nrm, (size_t)tgt_off[npairs] * 3 * sizeof(float)));
+    for (int i = 0; i < npairs; ++i) {
+        const int64_t nt = tgt_off[i + 1] - tgt_off[i];
+        const float* one = nullptr;
+        KCHK(target_normals_dev(c, d_tgt + 3 * tgt_off[i], nt, &one));
+        HIPCHK(c, hipMemcpyAsync((float*)c->pb_nrm.p + 3 * tgt_off[i], one, (size_t)nt * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    }
+    *d_nrm = (const float*)c->pb_nrm.p;
+    return KSS_OK;
+}
+
+// what the four ICP entry points below share.  The offsets are rebased to the first pair, so that every buffer of the call is
+// indexed from 0.  tp: null for kss_icp_p2l_batch.
+static int pairs_batch_dev(kss_ctx* c, const char* who, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off,
+                           const float* d_nrm, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
+                           kss_icp_result* results, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": bad batch").c_str());
+    KCHK(pair_check(c, who, tp != nullptr, d_src, d_tgt, 0, 0, d_nrm, p, tp, results, src_off, tgt_off, npairs, overlaps));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
+    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
+    if (d_nrm) d_nrm += 3 * tgt_off[0];
+    PairMode mode;
+    mode.plane = !tp || tp->metric == KSS_METRIC_PLANE;
+    mode.trimmed = tp != nullptr;
+    mode.trace_trim = tp ? tp->trace_trim : nullptr;
+    std::vector<double> ov;
+    if (tp) ov.assign((size_t)npairs, tp->overlap);
+    if (tp && overlaps) ov.assign(overlaps, overlaps + npairs);
+    if (mode.plane && !d_nrm) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, &d_nrm));
+    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_nrm, npairs, p, mode, tp ? ov.data() : nullptr, results, info_all);
+}
+
+// host clouds: the batch's slices of the packed arrays are staged, then the device form runs
+static int pairs_batch_host(kss_ctx* c, const char* who, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off,
+                            const float* nrm, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
+                            kss_icp_result* results, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": bad batch").c_str());
+    KCHK(pair_check(c, who, tp != nullptr, src, tgt, 0, 0, nrm, p, tp, results, src_off, tgt_off, npairs, overlaps));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
+    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    if (nrm) KCHK(upload(c, c->pb_nrm, nrm + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
+    return pairs_batch_dev(c, who, (const float*)c->stage_src.p, so.data(), (const float*)c->stage_tgt.p, to.data(),
+                           nrm ? (const float*)c->pb_nrm.p : nullptr, npairs, p, tp, overlaps, results, info_all);
+}
+
+int kss_icp_p2l_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
+                          const float* d_nrm_all, int npairs, const kss_icp_params* p, kss_icp_result* results) {
+    return pairs_batch_dev(c, "icp_p2l_batch", d_src_all, src_off, d_tgt_all, tgt_off, d_nrm_all, npairs, p, nullptr, nullptr, results, nullptr);
+}
+
+int kss_icp_p2l_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
+                      const float* nrm_all, int npairs, const kss_icp_params* p, kss_icp_result* results) {
+    return pairs_batch_host(c, "icp_p2l_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, nullptr, nullptr, results, nullptr);
+}
+
+int kss_icp_trimmed_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
+                              const float* d_nrm_all, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
+                              kss_icp_result* results, double* info_all) {
+    if (c && !tp) return set_err(c, KSS_ERR_ARG, "icp_trimmed_batch: null argument");
+    return pairs_batch_dev(c, "icp_trimmed_batch", d_src_all, src_off, d_tgt_all, tgt_off, d_nrm_all, npairs, p, tp, overlaps, results, info_all);
+}
+
+int kss_icp_trimmed_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
+                          const float* nrm_all, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
+                          kss_icp_result* results, double* info_all) {
+    if (c && !tp) return set_err(c, KSS_ERR_ARG, "icp_trimmed_batch: null argument");
+    return pairs_batch_host(c, "icp_trimmed_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, tp, overlaps, results, info_all);
+}
+
+static int trim_batch_check(kss_ctx* c, const float* d2, const int64_t* off, int nseg, const double* overlaps, const double* info_all) {
+    if (!d2 || !off || !overlaps || !info_all) return set_err(c, KSS_ERR_ARG, "trim_threshold_batch: null argument");
+    if (nseg <= 0) return set_err(c, KSS_ERR_ARG, "trim_threshold_batch: no segment");
+    for (int i = 0; i < nseg; ++i) {
+        const int64_t n = off[i + 1] - off[i];
+        if (n <= 0 || n > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "trim_threshold_batch: segment empty or out of range");
+        if (!trim_overlap_ok(overlaps[i])) return set_err(c, KSS_ERR_ARG, "trim_threshold_batch: overlap must be in (0, 1]");
+    }
+    return KSS_OK;
+}
+
+int kss_trim_threshold_batch_dev(kss_ctx* c, const float* d_d2_all, const int64_t* off, int nseg, double max_d2, const double* overlaps,
+                                 double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(trim_batch_check(c, d_d2_all, off, nseg, overlaps, info_all));
+    return trim_threshold_batch_dev(c, d_d2_all, off, nseg, max_d2, overlaps, info_all);
+}
+
+int kss_trim_threshold_batch(kss_ctx* c, const float* d2_all, const int64_t* off, int nseg, double max_d2, const double* overlaps,
+                             double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(trim_batch_check(c, d2_all, off, nseg, overlaps, info_all));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_d2, d2_all + off[0], (size_t)(off[nseg] - off[0]) * sizeof(float)));
+    std::vector<int64_t> o(nseg + 1);
+    for (int i = 0; i <= nseg; ++i) o[i] = off[i] - off[0];
+    return trim_threshold_batch_dev(c, (const float*)c->stage_d2.p, o.data(), nseg, max_d2, overlaps, info_all);
 }
 
 // ---- pre-shape ------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // pass (fused cell-list launch, batched cell lists, or sweep + reduce + finalize) and the ICP loop around it.
 // Host code only orchestrates: per iteration it launches the pass, takes 20 doubles per pair back, solves the 3x3 SVD
 // (kss_host_math.hpp) and evaluates the PCL convergence criteria.  There is no CPU compute fallback in this file.
+// Point-to-plane and trimmed ICP run pair_loop (one pair) or pairs_loop (many pairs in lockstep, kss_pairb.hip) on the same host step.
 #pragma clang fp contract(off)
 
 #include <emmintrin.h>
@@ -965,6 +966,7 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
         }
         if (a.state == (const PairState*)c->state.p)
             HIPCHK(c, hipMemcpyAsync(c->state.p, hs, (size_t)pl.npairs * sizeof(PairState), hipMemcpyHostToDevice, c->stream));
+        c->last_state_dev = a.state;
         const int nblk = grid_pass_blocks(pl.total_rows);
         if (getenv("KSS_GRID_STAMPS")) {   // diagnostic build of the timeline (tools/batch_stamps.py)
             KCHK(ensure(c, c->g_stamps, (size_t)nblk * 16 * sizeof(unsigned long long)));
@@ -994,6 +996,7 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
     }
     if (d_state == (const PairState*)c->state.p)
         HIPCHK(c, hipMemcpyAsync(c->state.p, hs, (size_t)pl.npairs * sizeof(PairState), hipMemcpyHostToDevice, c->stream));
+    c->last_state_dev = d_state;
     // The candidate batch of a registration (pairs sharing ONE small target, all of one size): sweep + sums + publication in a
     // single launch per pass (kss_kernels.hip: cand_pass_kernel).  KSS_CAND_FUSED=0: sweep + reduce as before (A/B; the two
     // forms agree on every correspondence, their sums differ in the order of additions).
@@ -1039,6 +1042,7 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
         }
     }
     HIPCHK(c, hipGetLastError());
+    if (c->defer_wait) return KSS_OK;   // (pairs_loop: its own launches follow on the stream, it synchronises once behind them)
     if (spin) KCHK(wait_seq(c, pl.npairs));
     else HIPCHK(c, hipStreamSynchronize(c->stream));
     return KSS_OK;
@@ -1601,6 +1605,28 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
     return KSS_OK;
 }
 
+// Batched cell lists: slot 19 of a pair's sums counts the lanes that ended in the in-wave brute-force fallback.  When more
+// than 10 % of the sources of the pairs that were active in the pass did (badly posed or partly overlapping pairs), the rest of
+// the call runs on the brute-force engine, whose tiled sweep is several times faster at that job; the engines agree bit for
+// bit on every correspondence, so the switch only changes speed.  The packed clouds stay where they are.  plan: the batched
+// cell-list plan the pass ran on, replaced by brute_plan (built and staged here) when the rule fires.
+static int switch_engine_on_fallback(kss_ctx* c, const IcpPlan*& plan, IcpPlan& brute_plan, bool shared_target, const kss_icp_params& P,
+                                     const std::vector<int>& was_active) {
+    const int np = plan->npairs;
+    const double* hsum = (const double*)c->h_sums;
+    double fallback = 0.0, act = 0.0;
+    for (int p = 0; p < np; ++p)
+        if (was_active[p]) { fallback += hsum[(size_t)p * NSUMS + NSUMS - 1]; act += (double)plan->g[p].ns; }
+    if (!(fallback > 0.10 * act) || getenv("KSS_GRID_NOSWITCH")) return KSS_OK;
+    std::vector<int64_t> ns(np), nt(np);
+    for (int p = 0; p < np; ++p) { ns[p] = plan->g[p].ns; nt[p] = plan->g[p].nt; }
+    KCHK(build_plan(c, ns.data(), nt.data(), np, shared_target, P.nn_sources_per_thread, P.nn_target_splits, KSS_NN_BRUTE, brute_plan));
+    brute_plan.src_in_cell_order = true;
+    KCHK(stage_plan(c, brute_plan));
+    plan = &brute_plan;
+    return KSS_OK;
+}
+
 // The ICP loop over a packed workspace (src0/tgt4 already filled).
 static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, kss_icp_result* results) {
     if (pl_in.gridb) {   // batches whose pairs fit a CU each: one launch, every pair resident for its whole registration
@@ -1749,23 +1775,7 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
             c->t_launch_us += std::chrono::duration<double, std::micro>(tb1 - tb0).count();
             c->t_wait_us += std::chrono::duration<double, std::micro>(tb2 - tb1).count();
         }
-        if (plan->gridb) {
-            // Batched cell lists: slot 19 counts the lanes that ended in the in-wave brute-force fallback.  When more
-            // than 10 % of the active sources did (badly posed pairs), the rest of this call runs on the brute-force
-            // engine, whose tiled sweep is several times faster at that job; the engines agree bit for bit on every
-            // correspondence, so the switch only changes speed.  The packed clouds stay where they are.
-            double fallback = 0.0, act = 0.0;
-            for (int p = 0; p < np; ++p)
-                if (was_active[p]) { fallback += hsum[(size_t)p * NSUMS + NSUMS - 1]; act += (double)plan->g[p].ns; }
-            if (fallback > 0.10 * act && !getenv("KSS_GRID_NOSWITCH")) {
-                std::vector<int64_t> ns(np), nt(np);
-                for (int p = 0; p < np; ++p) { ns[p] = plan->g[p].ns; nt[p] = plan->g[p].nt; }
-                KCHK(build_plan(c, ns.data(), nt.data(), np, pl_in.shared_target, P.nn_sources_per_thread, P.nn_target_splits, KSS_NN_BRUTE, brute_plan));
-                brute_plan.src_in_cell_order = true;
-                KCHK(stage_plan(c, brute_plan));
-                plan = &brute_plan;
-            }
-        }
+        if (plan->gridb) KCHK(switch_engine_on_fallback(c, plan, brute_plan, pl_in.shared_target, P, was_active));
         n_active -= fin_now;
         ++it;
     }
@@ -1850,13 +1860,43 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // in front, the selection's {m, k, tau, kept} behind KSS_P2L_NSUMS doubles); ONE stream synchronisation; then the solve and
 // the PCL criteria on the host.  Untrimmed plane passes make no selection launches and keep a correspondence by
 // !(d2 > max_d2).  The plan, the packed clouds and the cell list are built once per call.
+// What the host does for ONE pair after a pass, the same code for a single pair (pair_loop) and inside a batch (pairs_loop): the
+// min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
+// its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
+// ended (state / converged say how) and hs is left as it was.  trace: the pair whose passes the caller's trace receives.
+struct PairTrack {
+    Convergence cv;
+    float fin[16], tk[16];
+    int iters = 0, state = KSS_STATE_NOT_CONVERGED, converged = 0;
+    double last_mse = 0.0;
+    explicit PairTrack(const kss_icp_params& P) : cv(convergence_of(P)) { mat4_identity(fin); mat4_identity(tk); }
+};
+static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const double* s, const double* info, PairTrack& t, PairState& hs,
+                           bool trace) {
+    if ((int)s[0] < P.min_correspondences) { t.state = KSS_STATE_NO_CORRESPONDENCES; return false; }   // PCL: "Not enough correspondences found"
+    if (M.plane) {
+        if (!rigid_from_p2l_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
+    } else {
+        rigid_from_sums(s, t.tk);
+    }
+    mat4_mul(t.tk, t.fin, t.fin);   // final = transformation_ * final
+    ++t.iters;
+    const double mse = (M.plane ? s[28] : s[16]) / s[0];   // point-to-point d2 of the kept correspondences, as PCL's criteria read it
+    t.last_mse = mse;
+    if (trace) trace_row(P, s, M.plane ? P2L_NSUMS : NSUMS, t.tk, M.trimmed ? M.trace_trim : nullptr, info);
+    const bool done = t.cv.has_converged(t.iters, t.tk, mse);
+    t.state = t.cv.state;
+    if (done) { t.converged = 1; return false; }
+    set_state(hs, t.tk, 1, 1);   // next NN pass applies T_k on load (transformCloud)
+    return true;
+}
+
 static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
                      const int32_t* d_perm, kss_icp_result* res) {
     const int64_t ns = pl.g[0].ns, nt = pl.g[0].nt;
     const int ncol = M.plane ? P2L_NSUMS : NSUMS;
-    Convergence cv = convergence_of(P);
-    float fin[16], tk[16], I[16];
-    mat4_identity(fin);
+    PairTrack tr(P);
+    float I[16];
     mat4_identity(I);
     PairState* hs = (PairState*)c->h_state;
     set_state(hs[0], I, 1, 0);
@@ -1870,8 +1910,7 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
     const double* d_cut = M.trimmed ? &d_state[TRIM_NSTATE - 1].cut : nullptr;
     if (P.trace_n) *P.trace_n = 0;
     if (M.last_info) for (int q = 0; q < KSS_TRIM_NINFO; ++q) M.last_info[q] = 0.0;
-    int it = 0, iters = 0, state = KSS_STATE_NOT_CONVERGED, converged = 0;
-    double last_mse = 0.0;
+    int it = 0;
     GatedGuard gated_guard(c);
     c->gated.want_next = false;
     while (P.max_iterations > 0) {
@@ -1896,26 +1935,12 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
             info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
             if (M.last_info) std::memcpy(M.last_info, info, sizeof info);
         }
-        if ((int)s[0] < P.min_correspondences) { state = KSS_STATE_NO_CORRESPONDENCES; break; }   // PCL: "Not enough correspondences found"
-        if (M.plane) {
-            if (!rigid_from_p2l_sums(s, tk)) { state = KSS_STATE_DEGENERATE; break; }
-        } else {
-            rigid_from_sums(s, tk);
-        }
-        mat4_mul(tk, fin, fin);   // final = transformation_ * final
-        ++iters;
-        const double mse = (M.plane ? s[28] : s[16]) / s[0];   // point-to-point d2 of the kept correspondences, as PCL's criteria read it
-        last_mse = mse;
-        trace_row(P, s, ncol, tk, M.trimmed ? M.trace_trim : nullptr, info);
-        const bool done = cv.has_converged(iters, tk, mse);
-        state = cv.state;
-        if (done) { converged = 1; break; }
-        set_state(hs[0], tk, 1, 1);   // next NN pass applies T_k on load (transformCloud)
+        if (!pair_host_step(P, M, s, info, tr, hs[0], true)) break;
     }
-    fill_result(*res, fin, iters, converged, state, last_mse, 0.0, 0);
+    fill_result(*res, tr.fin, tr.iters, tr.converged, tr.state, tr.last_mse, 0.0, 0);
     if (!P.compute_fitness) return KSS_OK;
     const bool corr = P.fitness_idx || P.fitness_d2;
-    return fitness_pass(c, pl, P, fin, &iters, &state, true, nullptr, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, res);
+    return fitness_pass(c, pl, P, tr.fin, &tr.iters, &tr.state, true, nullptr, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, res);
 }
 
 // (the arguments are the entry points' to check: kss_api.hip)
@@ -1968,6 +1993,206 @@ int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, 
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_TRIM_NINFO * sizeof(double));
+    return KSS_OK;
+}
+
+// ---- the same metrics for MANY pairs per call: kss_icp_p2l_batch, kss_icp_trimmed_batch ----
+// pair_loop in lockstep over npairs >= 1 pairs.  Per pass: ONE NN pass over the pairs still active (idx / d2 by global source
+// index), ONE selection launch when trimmed, TWO sums launches (kss_pairb.hip), ONE stream synchronisation, then
+// pair_host_step for every active pair (the host pool from 64 pairs up, each pair on exactly one thread).  A pair that ends
+// goes inactive in the per-pair state table; the workgroups of the later passes' launches leave at once for it and its rows
+// of the host-mapped tables are not written again: no ending touches another pair's record.  icp_loop's engine switch applies.
+struct DeferWait {   // the NN pass does not wait for its sums: the launches behind it are waited for instead
+    kss_ctx* c;
+    explicit DeferWait(kss_ctx* c_) : c(c_) { c->defer_wait = true; }
+    ~DeferWait() { c->defer_wait = false; }
+};
+static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
+                      const int32_t* d_perm, kss_icp_result* results, double* info_all) {
+    const int np = pl_in.npairs;
+    const IcpPlan* plan = &pl_in;   // may change to the brute-force plan below
+    IcpPlan brute_plan;
+    std::vector<PairTrack> tr((size_t)np, PairTrack(P));
+    std::vector<int> active(np, 1), was_active;
+    PairState* hs = (PairState*)c->h_state;
+    PairState* bar = pl_in.gridb ? bar_state_table(c, np) : nullptr;   // (null without a large BAR)
+    float I[16];
+    mat4_identity(I);
+    for (int p = 0; p < np; ++p) {
+        set_state(hs[p], I, 1, 0);
+        mirror_state(bar, p, hs[p]);
+    }
+    const double max_d2 = P.max_corr_dist * P.max_corr_dist;
+    int32_t* d_idx = (int32_t*)c->p2l_idx.p;
+    float* d_d2 = (float*)c->p2l_d2.p;
+    const double* hrec = (const double*)c->h_p2l;                          // np records of P2L_NSUMS doubles ...
+    const double* hinfo = hrec + (size_t)np * P2L_NSUMS;                   // ... and np selection records behind them
+    double* d_rec = (double*)c->h_p2l_dev;
+    double* d_info = d_rec + (size_t)np * P2L_NSUMS;
+    TrimState* d_ts = (TrimState*)c->trim_state.p;
+    const PairbDesc* d_desc = (const PairbDesc*)c->pb_desc.p;
+    int total_rows = 0;
+    for (int p = 0; p < np; ++p) total_rows += stream_blocks(pl_in.g[p].ns);
+    if (P.trace_n) *P.trace_n = 0;
+    if (info_all) std::fill(info_all, info_all + (size_t)np * KSS_TRIM_NINFO, 0.0);
+    int n_active = P.max_iterations > 0 ? np : 0;
+    if (n_active == 0) std::fill(active.begin(), active.end(), 0);
+    int it = 0;
+    GatedGuard gated_guard(c);
+    c->gated.want_next = false;
+    while (n_active > 0) {
+        const float4* d_in = it == 0 ? (const float4*)c->src0.p : (const float4*)c->cur[(it - 1) & 1].p;
+        float4* d_out = (float4*)c->cur[it & 1].p;
+        c->last_state_dev = nullptr;
+        {
+            DeferWait defer(c);
+            KCHK(nn_pass(c, *plan, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false, active.data()));
+        }
+        const unsigned long long pass_seq = c->seq;
+        const PairState* d_state = c->last_state_dev;   // (a single pair on its own cell list has none: it is active)
+        {
+            ProfScope ps(c, KSS_K_CORR_REDUCE);
+            if (M.trimmed) launch_pairb_select(c->stream, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
+            launch_pairb_sums(c->stream, M.plane, M.trimmed, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, (const int32_t*)c->pb_rowpair.p,
+                              total_rows, np, d_state, d_ts, max_d2, (double*)c->p2l_rows.p, d_rec);
+        }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        ++it;
+        if (plan->gridb) {   // the NN pass's own sums (slot 19: the fallback count) have landed with everything else
+            for (int p = 0; p < np; ++p)
+                if (active[p] && !collect_pair(c, p, pass_seq)) return set_err(c, KSS_ERR_HIP, "kernel finished without publishing its result");
+            was_active = active;
+        }
+        std::atomic<int> finished{0};
+        auto solve = [&](int pb, int pe) {
+            int fin_here = 0;
+            for (int p = pb; p < pe; ++p) {
+                if (!active[p]) continue;
+                const double* s = hrec + (size_t)p * P2L_NSUMS;
+                double info[KSS_TRIM_NINFO] = {};
+                if (M.trimmed) {
+                    std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, sizeof info);
+                    info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
+                    if (info_all) std::memcpy(info_all + (size_t)p * KSS_TRIM_NINFO, info, sizeof info);
+                }
+                if (!pair_host_step(P, M, s, info, tr[p], hs[p], p == 0)) {
+                    active[p] = 0; ++fin_here;
+                    set_state(hs[p], I, 0, 0);
+                }
+                mirror_state(bar, p, hs[p]);
+            }
+            finished.fetch_add(fin_here, std::memory_order_relaxed);
+        };
+        if (np >= 64) {
+            std::atomic<int> next{0};
+            constexpr int kBlock = 64;   // pairs claimed at a time (solve_pairs' grain)
+            c->pool.parallel_for(np, [&](int, int) {
+                for (;;) {
+                    const int pb = next.fetch_add(1) * kBlock;
+                    if (pb >= np) break;
+                    solve(pb, std::min(np, pb + kBlock));
+                }
+            });
+        } else {
+            solve(0, np);
+        }
+        n_active -= finished.load(std::memory_order_relaxed);
+        if (plan->gridb && n_active > 0) KCHK(switch_engine_on_fallback(c, plan, brute_plan, false, P, was_active));
+    }
+    std::vector<float> fin((size_t)np * 16);
+    std::vector<int> iters(np), state(np);
+    for (int p = 0; p < np; ++p) {
+        std::memcpy(&fin[(size_t)p * 16], tr[p].fin, sizeof tr[p].fin);
+        iters[p] = tr[p].iters; state[p] = tr[p].state;
+        fill_result(results[p], tr[p].fin, tr[p].iters, tr[p].converged, tr[p].state, tr[p].last_mse, 0.0, p);
+    }
+    if (!P.compute_fitness) return KSS_OK;
+    const bool corr = P.fitness_idx || P.fitness_d2;
+    return fitness_pass(c, *plan, P, fin.data(), iters.data(), state.data(), plan == &pl_in, bar, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, results);
+}
+
+// per-pair descriptors (and the row -> pair table) of the batched kernels, uploaded once per call
+static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows) {
+    std::vector<int32_t> row_pair;
+    if (rows)
+        for (size_t p = 0; p < desc.size(); ++p) row_pair.insert(row_pair.end(), (size_t)desc[p].nrows, (int32_t)p);
+    KCHK(ensure(c, c->pb_desc, desc.size() * sizeof(PairbDesc)));
+    HIPCHK(c, hipMemcpyAsync(c->pb_desc.p, desc.data(), desc.size() * sizeof(PairbDesc), hipMemcpyHostToDevice, c->stream));
+    if (rows) {
+        KCHK(ensure(c, c->pb_rowpair, row_pair.size() * sizeof(int32_t)));
+        HIPCHK(c, hipMemcpyAsync(c->pb_rowpair.p, row_pair.data(), row_pair.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // pageable sources about to go out of scope
+    return KSS_OK;
+}
+
+// (the arguments are the entry points' to check: kss_api.hip)
+int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, const float* d_nrm,
+                  int npairs, const kss_icp_params* p, const PairMode& M, const double* overlaps, kss_icp_result* results, double* info_all) {
+    if (!M.plane && !M.trimmed) return set_err(c, KSS_ERR_ARG, "pairs_run: the untrimmed point metric is kss_icp_batch's");
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> ns(npairs), nt(npairs);
+    for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }
+    IcpPlan pl;
+    const auto t0 = std::chrono::steady_clock::now();
+    KCHK(restore_zero_at_rest(c));
+    DirtyGuard guard(c);
+    c->timing = false;
+    KCHK(build_plan(c, ns.data(), nt.data(), npairs, false, p->nn_sources_per_thread, p->nn_target_splits, p->nn_mode, pl));
+    KCHK(stage_plan(c, pl));
+    std::vector<PairbDesc> desc((size_t)npairs);
+    int64_t total_rows = 0;
+    for (int i = 0; i < npairs; ++i) {
+        PairbDesc& d = desc[i];
+        d.src_base = pl.g[i].src_base; d.ns = ns[i];
+        d.tgt_off = tgt_off[i]; d.nt = nt[i];
+        d.overlap = M.trimmed ? overlaps[i] : 1.0;
+        d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(ns[i]);
+        total_rows += d.nrows;
+        if (total_rows > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "batch too large for 32-bit indexing");
+    }
+    KCHK(stage_pairb(c, desc, true));
+    KCHK(ensure(c, c->p2l_idx, (size_t)pl.total_src * sizeof(int32_t)));
+    KCHK(ensure(c, c->p2l_d2, (size_t)pl.total_src * sizeof(float)));
+    KCHK(ensure(c, c->p2l_rows, (size_t)total_rows * P2L_NSUMS * sizeof(double)));
+    KCHK(ensure(c, c->trim_state, (size_t)std::max(npairs, TRIM_NSTATE) * sizeof(TrimState)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
+    KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));
+    KCHK(grid_setup(c, pl));
+    KCHK(grid_setup_batch(c, pl));
+    const int32_t* d_perm = nullptr;
+    if (pl.src_in_cell_order) {   // the cell-list setup re-ordered the sources (.w: the global original index): where each one went
+        KCHK(ensure(c, c->p2l_perm, (size_t)pl.total_src * sizeof(int32_t)));
+        launch_p2l_perm(c->stream, (const float4*)c->src0.p, pl.total_src, (int32_t*)c->p2l_perm.p);
+        HIPCHK(c, hipGetLastError());
+        d_perm = (const int32_t*)c->p2l_perm.p;
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    const int rc = pairs_loop(c, pl, *p, M, d_tgt, d_nrm, d_perm, results, info_all);
+    guard.ok = rc == KSS_OK;
+    const auto t2 = std::chrono::steady_clock::now();
+    c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return rc;
+}
+
+// tau / m / k / kept of nseg segments of squared distances in one launch (kss_trim_threshold_batch_dev)
+int trim_threshold_batch_dev(kss_ctx* c, const float* d_d2, const int64_t* off, int nseg, double max_d2, const double* overlaps, double* info_all) {
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<PairbDesc> desc((size_t)nseg);
+    for (int i = 0; i < nseg; ++i) {
+        PairbDesc& d = desc[i];
+        d.src_base = off[i]; d.ns = off[i + 1] - off[i];
+        d.tgt_off = 0; d.nt = 0; d.overlap = overlaps[i]; d.row_base = 0; d.nrows = 0;
+    }
+    KCHK(stage_pairb(c, desc, false));
+    KCHK(ensure(c, c->trim_state, (size_t)std::max(nseg, TRIM_NSTATE) * sizeof(TrimState)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)nseg * (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
+    launch_pairb_select(c->stream, d_d2, (const PairbDesc*)c->pb_desc.p, nseg, nullptr, max_d2, (TrimState*)c->trim_state.p, (double*)c->h_p2l_dev);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(info_all, c->h_p2l, (size_t)nseg * KSS_TRIM_NINFO * sizeof(double));
     return KSS_OK;
 }
 

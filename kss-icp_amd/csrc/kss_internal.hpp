@@ -372,6 +372,24 @@ void launch_trim_point_sums(hipStream_t st, const float4* d_src4, const int32_t*
                             const float* d_tgt3, int64_t n, int64_t nt, const double* d_cut, double* d_rows, double* d_out);
 void launch_f64_to_f32(hipStream_t st, const double* d_in, int64_t n, float* d_out);
 
+// ---- point-to-plane and trimmed ICP for many pairs per call (kss_pairb.hip) ----
+// one pair (or one segment of kss_trim_threshold_batch) as the batched kernels see it
+struct alignas(16) PairbDesc {
+    int64_t src_base, ns;      // the pair's sources in the batch-wide per-source arrays (idx, d2, perm)
+    int64_t tgt_off, nt;       // its target in the caller's packed float triples (points), normals alike
+    double overlap;
+    int32_t row_base, nrows;   // its partial rows: stream_blocks(ns) of them, the single-pair kernels' count
+};
+// one launch: every active pair's TrimState into d_ts[pair] and {m, k, tau, kept} into d_info[pair * KSS_TRIM_NINFO]
+// (d_state: the NN pass's per-pair states, null: every pair is active)
+void launch_pairb_select(hipStream_t st, const float* d_d2, const PairbDesc* d_desc, int npairs, const PairState* d_state, double max_d2,
+                         TrimState* d_ts, double* d_info);
+// two launches: every active pair's record into d_out[pair * KSS_P2L_NSUMS] (the point metric fills KSS_NSUMS of them)
+void launch_pairb_sums(hipStream_t st, bool plane, bool trimmed, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
+                       const float* d_d2, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
+                       int total_rows, int npairs, const PairState* d_state, const TrimState* d_ts, double max_d2, double* d_rows,
+                       double* d_out);
+
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,
                 const std::function<void*(size_t)>& scratch);

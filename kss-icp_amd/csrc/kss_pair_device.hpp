@@ -1,0 +1,187 @@
+// kss_pair_device.hpp -- the device code that the single-pair kernels (kss_p2l.hip, kss_trim.hip) and the batched ones
+// (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
+//   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
+//   p2l_rows_column_sum              the fixed-order column sums of the plane metric's rows,
+//   trim_key / trim_resolve_counts   the candidate test and the resolution of one radix digit from a lane's eight bin counts.
+// A pair's bits are the same alone and inside a batch because both forms run these bodies in the same order.
+#pragma once
+#include "kss_device.hpp"
+
+namespace kss {
+
+// ---- point-to-plane --------------------------------------------------------------------------------------
+constexpr int P2L_THREADS = 256;
+
+// Where the current source positions come from: SRC_F3 packed float triples in original order (kss_p2l_sums); SRC_F4 the
+// NN pass's float4 output in original order (brute-force engine); SRC_F4_PERM the same in cell order, perm[i] = the slot of
+// original source i.
+enum { SRC_F3 = 0, SRC_F4 = 1, SRC_F4_PERM = 2 };
+
+// Source i (an index into idx / d2_in / perm / src3; in a batch the global one) against the target tgt / nrm of nt points.
+// TRIM (trimmed ICP): max_d2 is the pass's cut tau (-1: no candidate) and a correspondence is kept when 0 <= d2 <= tau; the
+// body and the summation order are the same, so an overlap of 1 -- tau = the largest d2 within max_d2 -- gives the untrimmed
+// record bit for bit.
+template <int SRC, bool TRIM>
+__device__ __forceinline__ void p2l_source(double (&acc)[P2L_NSUMS], const float* __restrict__ src3, const float4* __restrict__ src4,
+                                           const int32_t* __restrict__ perm, const int32_t* __restrict__ idx,
+                                           const float* __restrict__ d2_in, const float* __restrict__ tgt,
+                                           const float* __restrict__ nrm, int64_t i, int64_t nt, double max_d2) {
+    const int64_t j = idx[i];
+    if (j < 0 || j >= nt) return;   // (kss_p2l_sums_dev: an index outside the target contributes nothing)
+    float sx, sy, sz;
+    if constexpr (SRC == SRC_F3) {
+        sx = src3[3 * i]; sy = src3[3 * i + 1]; sz = src3[3 * i + 2];
+    } else {
+        const float4 p = src4[SRC == SRC_F4_PERM ? (int64_t)perm[i] : i];
+        sx = p.x; sy = p.y; sz = p.z;
+    }
+    const float qx = tgt[3 * j], qy = tgt[3 * j + 1], qz = tgt[3 * j + 2];
+    const float nx = nrm[3 * j], ny = nrm[3 * j + 1], nz = nrm[3 * j + 2];
+    const double d2 = (double)(d2_in ? d2_in[i] : dist2<false>(sx, sy, sz, qx, qy, qz));
+    acc[29] += d2;
+    // PCL: `if (distance > max_dist_sqr) continue;`, and a correspondence whose normal is not finite is dropped
+    if ((TRIM ? d2 >= 0.0 && d2 <= max_d2 : !(d2 > max_d2)) && isfinite(nx) && isfinite(ny) && isfinite(nz)) {
+        // float, left to right, no fma (PCL computes these in float and widens)
+        const float a = nz * sy - ny * sz;
+        const float b = nx * sz - nz * sx;
+        const float c = ny * sx - nx * sy;
+        const float r = ((nx * qx + ny * qy) + nz * qz) - nx * sx - ny * sy - nz * sz;
+        const double v[6] = {(double)a, (double)b, (double)c, (double)nx, (double)ny, (double)nz};
+        const double rd = (double)r;
+        acc[0] += 1.0;
+        int k = 1;
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+#pragma unroll
+            for (int q = p; q < 6; ++q) acc[k++] += v[p] * v[q];
+#pragma unroll
+        for (int p = 0; p < 6; ++p) acc[22 + p] += v[p] * rd;
+        acc[28] += d2;
+        acc[30] += rd * rd;
+    }
+}
+
+// Column c of the rows: lane (g, c) = (tid / 32, tid % 32) takes rows g, g + 8, g + 16, ... (32 lanes read one 256-byte
+// row) into eight accumulators -- row g + 8 (8 m + u) goes to accumulator u while a whole round of eight fits, the tail to
+// accumulator 0 -- added as ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)); then the 8 group totals in group order.
+// (Eight loads in flight per lane: with one accumulator the lane waits out one memory latency per row, 12 us at 391 rows.)
+// The column total in lanes tid < P2L_NSUMS.  Needs blockDim.x == P2L_THREADS.
+constexpr int P2L_GROUPS = P2L_THREADS / P2L_NSUMS;
+__device__ __forceinline__ double p2l_rows_column_sum(const double* __restrict__ rows, int nrows, double (*shg)[P2L_NSUMS]) {
+    const int g = threadIdx.x / P2L_NSUMS, c = threadIdx.x % P2L_NSUMS;
+    constexpr int G = P2L_GROUPS;
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int k = g;
+    for (; k + 7 * G < nrows; k += 8 * G) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) a[u] += rows[(int64_t)(k + u * G) * P2L_NSUMS + c];
+    }
+    for (; k < nrows; k += G) a[0] += rows[(int64_t)k * P2L_NSUMS + c];
+    shg[g][c] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    __syncthreads();
+    double v = 0.0;
+    if (threadIdx.x < P2L_NSUMS)
+        for (int gg = 0; gg < P2L_GROUPS; ++gg) v += shg[gg][threadIdx.x];
+    return v;
+}
+
+// ---- trimmed ICP ----------------------------------------------------------------------------------------
+constexpr int TRIM_BINS = 2048;                 // row width: the widest digit
+constexpr int TRIM_HIST_THREADS = 256;
+constexpr int TRIM_LANE_BINS = TRIM_BINS / TRIM_HIST_THREADS;   // bins per lane when a digit is resolved
+constexpr int TRIM_THREADS = 256;
+// digit d covers key bits [trim_shift(d), trim_shift(d) + trim_bits(d))
+// (a key has its sign bit clear: 31 bits; the first digit is the exponent and three mantissa bits)
+__device__ __host__ constexpr int trim_shift(int d) { return d == 0 ? 20 : d == 1 ? 10 : 0; }
+__device__ __host__ constexpr int trim_bits(int d) { return d == 0 ? 11 : 10; }
+
+// candidate test and key of one squared distance
+__device__ __forceinline__ bool trim_key(float d2f, double max_d2, unsigned& key) {
+    const double d = (double)d2f;
+    key = d2f == 0.0f ? 0u : __float_as_uint(d2f);
+    return d >= 0.0 && d <= max_d2;
+}
+
+// Resolves digit DIGIT from its bin counts, lane t holding the counts c[0..7] of the bins 8t .. 8t + 7: the state after it
+// (prefix, rank inside the keys that carry it, m, k; after the last digit cut and kept) in *out (LDS), valid for every lane
+// after the call.  *prev is the state before it (digit 0 has none: m is the total of the counts); prev and out must not
+// alias.  Needs blockDim.x == TRIM_HIST_THREADS.
+template <int DIGIT>
+__device__ __forceinline__ void trim_resolve_counts(const unsigned (&c)[TRIM_LANE_BINS], double overlap,
+                                                    const TrimState* __restrict__ prev, TrimState* out, unsigned* wave_tot) {
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    // inclusive scan of the lane totals over the workgroup (counts stay below 2^31: n is capped by the C-ABI)
+    unsigned mine = 0u;
+#pragma unroll
+    for (int q = 0; q < TRIM_LANE_BINS; ++q) mine += c[q];
+    unsigned inc = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned o = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += o;
+    }
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    unsigned base = 0u, total = 0u;
+    for (int w = 0; w < TRIM_HIST_THREADS / 64; ++w) {
+        if (w < wave) base += wave_tot[w];
+        total += wave_tot[w];
+    }
+    const unsigned excl = base + inc - mine;   // keys of this digit below bin 8t
+    long long m, k, rank;
+    unsigned prefix;
+    if constexpr (DIGIT == 0) {
+        m = (long long)total;
+        k = trim_rank_of(m, overlap);
+        rank = k;
+        prefix = 0u;
+    } else {
+        m = prev->m; k = prev->k; rank = prev->rank; prefix = prev->prefix;
+    }
+    if (t == 0) {   // no candidate (rank 0); otherwise overwritten below by the lane that holds the rank
+        TrimState o;
+        o.prefix = 0u; o.pad = 0u; o.rank = 0; o.m = m; o.k = k; o.cut = -1.0; o.kept = 0;
+        *out = o;
+    }
+    __syncthreads();
+    const unsigned rk = (unsigned)rank;
+    if (rank > 0 && excl < rk && rk <= excl + mine) {   // exactly one lane: the counts of a digit add up to at least the rank
+        unsigned below = excl, bin = 0u, cnt = 0u;
+        bool found = false;
+#pragma unroll
+        for (int q = 0; q < TRIM_LANE_BINS; ++q) {
+            if (!found) {
+                if (rk <= below + c[q]) { found = true; bin = (unsigned)(TRIM_LANE_BINS * t + q); cnt = c[q]; }
+                else below += c[q];
+            }
+        }
+        TrimState o;
+        o.prefix = (prefix << trim_bits(DIGIT)) | bin;
+        o.pad = 0u;
+        o.rank = (long long)(rk - below);
+        o.m = m; o.k = k;
+        o.cut = -1.0; o.kept = 0;
+        if constexpr (DIGIT == 2) {
+            o.cut = (double)__uint_as_float(o.prefix);   // tau
+            o.kept = (k - o.rank) + (long long)cnt;      // the keys below tau + the whole tie at tau
+        }
+        *out = o;
+    }
+    __syncthreads();
+}
+
+// point metric: source i (as in p2l_source) on accumulate_corr's arithmetic, kept when 0 <= d2 <= cut
+template <bool PERM>
+__device__ __forceinline__ void trim_point_source(double (&acc)[NSUMS], const float4* __restrict__ src4, const int32_t* __restrict__ perm,
+                                                  const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
+                                                  const float* __restrict__ tgt, int64_t i, int64_t nt, double cut) {
+    const int64_t j = idx[i];
+    if (j < 0 || j >= nt) return;
+    const float d2f = d2_in[i];
+    const double d2 = (double)d2f;
+    if (!(d2 >= 0.0 && d2 <= cut)) return;
+    const float4 p = src4[PERM ? (int64_t)perm[i] : i];
+    accumulate_corr(acc, p.x, p.y, p.z, tgt[3 * j], tgt[3 * j + 1], tgt[3 * j + 2], d2f, cut);
+}
+
+}  // namespace kss

@@ -23,19 +23,13 @@
 // rows_column_sum's fixed order.  The plane metric uses p2l_rows_kernel<SRC, true> (kss_p2l.hip), which reads the same cut.
 #pragma clang fp contract(off)
 
-#include "kss_device.hpp"
+#include "kss_pair_device.hpp"
 
 namespace kss {
 
-constexpr int TRIM_BINS = 2048;                 // row width: the widest digit
-constexpr int TRIM_HIST_THREADS = 256;
-constexpr int TRIM_LANE_BINS = TRIM_BINS / TRIM_HIST_THREADS;   // bins per lane when a digit is resolved
+// (TRIM_BINS, the digits, trim_key and the resolution of a digit from bin counts: kss_pair_device.hpp, shared with the batch)
 constexpr int TRIM_KEYS_PER_BLOCK = 4096;       // >= 16 keys per lane before another histogram row (8 KB) is added
 constexpr int TRIM_MAX_BLOCKS = 128;            // every workgroup of the next step reads all rows (L2): 1 MB each at most
-// digit d covers key bits [trim_shift(d), trim_shift(d) + trim_bits(d))
-// (a key has its sign bit clear: 31 bits; the first digit is the exponent and three mantissa bits)
-__device__ __host__ constexpr int trim_shift(int d) { return d == 0 ? 20 : d == 1 ? 10 : 0; }
-__device__ __host__ constexpr int trim_bits(int d) { return d == 0 ? 11 : 10; }
 
 int trim_hist_blocks(int64_t n) {
     int64_t b = (n + TRIM_KEYS_PER_BLOCK - 1) / TRIM_KEYS_PER_BLOCK;
@@ -44,20 +38,13 @@ int trim_hist_blocks(int64_t n) {
     return (int)b;
 }
 
-// candidate test and key of one squared distance
-__device__ __forceinline__ bool trim_key(float d2f, double max_d2, unsigned& key) {
-    const double d = (double)d2f;
-    key = d2f == 0.0f ? 0u : __float_as_uint(d2f);
-    return d >= 0.0 && d <= max_d2;
-}
-
 // Resolves digit DIGIT from its histogram rows: the state after it (prefix, rank inside the keys that carry it, m, k; after the
 // last digit cut and kept) in *out (LDS), valid for every lane after the call.  st[DIGIT] is the state before it (digit 0 has
 // none: m is the total of the rows).  Needs blockDim.x == TRIM_HIST_THREADS; lane t owns the bins 8t .. 8t + 7.
 template <int DIGIT>
 __device__ __forceinline__ void trim_resolve(const unsigned* __restrict__ rows, int nrows, double overlap,
                                              const TrimState* __restrict__ st, TrimState* out, unsigned* wave_tot) {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     unsigned c[TRIM_LANE_BINS];
 #pragma unroll
     for (int q = 0; q < TRIM_LANE_BINS; ++q) c[q] = 0u;
@@ -81,64 +68,7 @@ __device__ __forceinline__ void trim_resolve(const unsigned* __restrict__ rows, 
             }
         }
     }
-    // inclusive scan of the lane totals over the workgroup (counts stay below 2^31: n is capped by the C-ABI)
-    unsigned mine = 0u;
-#pragma unroll
-    for (int q = 0; q < TRIM_LANE_BINS; ++q) mine += c[q];
-    unsigned inc = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) wave_tot[wave] = inc;
-    __syncthreads();
-    unsigned base = 0u, total = 0u;
-    for (int w = 0; w < TRIM_HIST_THREADS / 64; ++w) {
-        if (w < wave) base += wave_tot[w];
-        total += wave_tot[w];
-    }
-    const unsigned excl = base + inc - mine;   // keys of this digit below bin 8t
-    long long m, k, rank;
-    unsigned prefix;
-    if constexpr (DIGIT == 0) {
-        m = (long long)total;
-        k = trim_rank_of(m, overlap);
-        rank = k;
-        prefix = 0u;
-    } else {
-        m = st[DIGIT].m; k = st[DIGIT].k; rank = st[DIGIT].rank; prefix = st[DIGIT].prefix;
-    }
-    if (t == 0) {   // no candidate (rank 0); otherwise overwritten below by the lane that holds the rank
-        TrimState o;
-        o.prefix = 0u; o.pad = 0u; o.rank = 0; o.m = m; o.k = k; o.cut = -1.0; o.kept = 0;
-        *out = o;
-    }
-    __syncthreads();
-    const unsigned rk = (unsigned)rank;
-    if (rank > 0 && excl < rk && rk <= excl + mine) {   // exactly one lane: the counts of a digit add up to at least the rank
-        unsigned below = excl, bin = 0u, cnt = 0u;
-        bool found = false;
-#pragma unroll
-        for (int q = 0; q < TRIM_LANE_BINS; ++q) {
-            if (!found) {
-                if (rk <= below + c[q]) { found = true; bin = (unsigned)(TRIM_LANE_BINS * t + q); cnt = c[q]; }
-                else below += c[q];
-            }
-        }
-        TrimState o;
-        o.prefix = (prefix << trim_bits(DIGIT)) | bin;
-        o.pad = 0u;
-        o.rank = (long long)(rk - below);
-        o.m = m; o.k = k;
-        o.cut = -1.0; o.kept = 0;
-        if constexpr (DIGIT == 2) {
-            o.cut = (double)__uint_as_float(o.prefix);   // tau
-            o.kept = (k - o.rank) + (long long)cnt;      // the keys below tau + the whole tie at tau
-        }
-        *out = o;
-    }
-    __syncthreads();
+    trim_resolve_counts<DIGIT>(c, overlap, st + DIGIT, out, wave_tot);
 }
 
 template <int DIGIT>
@@ -215,8 +145,6 @@ void launch_trim_select(hipStream_t st, const float* d_d2, int64_t n, double max
 size_t trim_rows_bytes(int64_t n) { return 2 * (size_t)trim_hist_blocks(n) * TRIM_BINS * sizeof(unsigned); }
 
 // ---- point-metric sums over the kept correspondences ---------------------------------------------------------------------
-constexpr int TRIM_THREADS = 256;
-
 template <bool PERM>
 __global__ __launch_bounds__(TRIM_THREADS) void trim_point_rows_kernel(const float4* __restrict__ src4, const int32_t* __restrict__ perm,
                                                                        const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
@@ -227,15 +155,8 @@ __global__ __launch_bounds__(TRIM_THREADS) void trim_point_rows_kernel(const flo
 #pragma unroll
     for (int c = 0; c < NSUMS; ++c) acc[c] = 0.0;
     const double cut = *cut_ptr;   // tau of this pass (-1: no candidate), written by the last selection step
-    for (int64_t i = (int64_t)blockIdx.x * TRIM_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TRIM_THREADS) {
-        const int64_t j = idx[i];
-        if (j < 0 || j >= nt) continue;
-        const float d2f = d2_in[i];
-        const double d2 = (double)d2f;
-        if (!(d2 >= 0.0 && d2 <= cut)) continue;
-        const float4 p = src4[PERM ? (int64_t)perm[i] : i];
-        accumulate_corr(acc, p.x, p.y, p.z, tgt[3 * j], tgt[3 * j + 1], tgt[3 * j + 2], d2f, cut);
-    }
+    for (int64_t i = (int64_t)blockIdx.x * TRIM_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TRIM_THREADS)
+        trim_point_source<PERM>(acc, src4, perm, idx, d2_in, tgt, i, nt, cut);   // (kss_pair_device.hpp)
     const double r = block_sum<NSUMS>(acc, sh);
     if (threadIdx.x < NSUMS) rows[(int64_t)blockIdx.x * NSUMS + threadIdx.x] = r;
 }
