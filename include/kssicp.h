@@ -295,7 +295,70 @@ int kss_icp_trimmed(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt
 int kss_icp_trimmed_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
                         const kss_icp_params *p, const kss_trim_params *tp, kss_icp_result *res, double last_info[KSS_TRIM_NINFO]);
 
+/* ---- robust ICP for one pair with gross outliers of unknown share (M-estimator weights, one iteratively re-weighted
+ *      least-squares step per pass), both metrics ----
+ * One pass, with the NN pass's idx[i] and float d2[i], the source's current float position p, its target point q and normal n.
+ * Every operation is f64 +, -, *, / (and one sqrt in Huber), none fused:
+ *   candidate   idx[i] in [0, nt) and 0 <= d2[i] <= max_d2 (ordered compares in double, as in trimmed ICP); the plane metric also
+ *               asks for a finite nx, ny, nz.  m of them.
+ *   residual    x (f64, squared): point metric x = (double)d2; plane metric x = rd*rd, rd = (double)r with the float r of
+ *               kss_icp_p2l (the product of two widened floats is exact).
+ *   key         (float) point metric d2, plane metric fabsf(r); a source that is no candidate has a NaN key.
+ *   scale       fixed form (rp->scale > 0): c2 = scale*scale.  Automatic form (rp->scale == 0): k = kss_trim_rank(m, 0.5), med =
+ *               the exact k-th smallest key, medx = (double)med (point) or (double)med*(double)med (plane),
+ *               K = (tune*1.4826)*(tune*1.4826), c2 = K*medx, raised to min_scale*min_scale where it is below that; m == 0: c2 = 0.
+ *               kss_robust_scale2 is this expression.
+ *   weight      kss_robust_weight: L2: w = 1.  Otherwise, c2 == 0: w = (x == 0) ? 1 : 0.  Otherwise u2 = x / c2 and
+ *               Huber x <= c2 ? 1 : sqrt(c2 / x);  Tukey x < c2 ? (1 - u2)*(1 - u2) : 0;  Cauchy 1 / (1 + u2).
+ *   kept        a candidate whose w is finite and > 0, decided by compares that involve no division (L2: every candidate;
+ *               c2 == 0: x == 0; Huber and Cauchy: x < inf, or x <= c2 for Huber; Tukey: x < c2; a NaN c2 keeps nothing): cnt of
+ *               them.  The two readings differ only where c2 / x underflows to 0 or x / c2 overflows, which no float residual
+ *               reaches once c2 >= 2^-768.
+ *   sums        over the kept set, f64, in kss_icp_trimmed's fixed order (a function of ns alone).  Point metric, the KSS_NSUMS
+ *               record with ws[k] = w*p[k]: [0] += w, [1+k] += ws[k], [4+k] += w*q[k], [7+3k+l] += ws[k]*q[l], [16] += w*d2,
+ *               [17] = m, [18] = 0, [19] = cnt.  Plane metric, the KSS_P2L_NSUMS record with v of kss_icp_p2l and wv[p] = w*v[p]:
+ *               [0] += w, upper triangle += wv[p]*v[q], [22+p] += wv[p]*rd, [28] += w*d2, [29] = m, [30] += (w*rd)*rd, [31] = cnt.
+ *               [0] being the weight total, kss_rigid_from_sums / kss_rigid_from_p2l_sums solve these records as they are.
+ *   info        {m, c2, [0], cnt}.
+ * The loop around it is kss_icp_trimmed's: PCL's criteria on MSE = [16 or 28] / [0], cnt < min_correspondences ->
+ * KSS_STATE_NO_CORRESPONDENCES, a singular plane system -> KSS_STATE_DEGENERATE, fitness over ALL sources.  KSS_LOSS_L2 is the
+ * unweighted step: with the plane metric kss_icp_p2l's, with the point metric kss_icp_trimmed's at overlap 1, bit for bit in the
+ * slots they share.  A residual that is NaN (a source that is not finite) is outside this definition. */
+enum { KSS_LOSS_L2 = 0, KSS_LOSS_HUBER = 1, KSS_LOSS_TUKEY = 2, KSS_LOSS_CAUCHY = 3 };
+#define KSS_ROBUST_NINFO 4            /* {m candidates, c2, sum of weights, cnt kept} */
+typedef struct {
+    int     loss, metric;             /* KSS_LOSS_*, KSS_METRIC_POINT / _PLANE */
+    double  scale;                    /* > 0: fixed c;  0: per pass from the median (above) */
+    double  tune;                     /* scale == 0: c = tune * 1.4826 * median residual; > 0 and finite */
+    double  min_scale;                /* >= 0: floor of c in the automatic form */
+    double *trace_robust;             /* p->trace_cap * KSS_ROBUST_NINFO, row i beside trace_sums row i; may be NULL */
+} kss_robust_params;
+/* scale 0, min_scale 0, trace_robust NULL, tune 1.345 (Huber) / 4.685 (Tukey) / 2.385 (Cauchy) / 1 (L2, unused) */
+int kss_robust_default_params(int loss, int metric, kss_robust_params *rp);
+/* host only, no context.  kss_robust_weight: x >= 0 or NaN, c2 >= 0 or NaN.  kss_robust_scale2: med_key >= 0 (-0.0f counts as
+ * +0.0f; negative or NaN: KSS_ERR_ARG), the floor applied. */
+int kss_robust_weight(int loss, double x, double c2, double *w);
+int kss_robust_scale2(int metric, double tune, float med_key, double min_scale, double *c2);
+/* The pass's record for given correspondences (d2 recomputed as in kss_cov), conventions of kss_p2l_sums: tgt_normals are nt*3
+ * floats for the plane metric and NULL for the point metric; sums holds KSS_NSUMS or KSS_P2L_NSUMS doubles by metric.  An idx
+ * entry outside [0, nt) is no candidate (both forms take it). */
+int kss_robust_sums(kss_ctx *ctx, const float *src, const float *tgt, const float *tgt_normals, const int32_t *idx, int64_t n,
+                    int64_t nt, double max_d2, const kss_robust_params *rp, double *sums, double info[KSS_ROBUST_NINFO]);
+int kss_robust_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_tgt, const float *d_tgt_normals, const int32_t *d_idx,
+                        int64_t n, int64_t nt, double max_d2, const kss_robust_params *rp, double *sums,
+                        double info[KSS_ROBUST_NINFO]);
+/* tgt_normals: plane metric: nt*3 floats or NULL (computed as in kss_icp_p2l); point metric: must be NULL.  last_info (may be
+ * NULL): the last pass's info record, all zero when no pass ran.  p->allreduce must be NULL.  KSS_ERR_ARG: a loss or metric
+ * out of range, scale negative or not finite, scale == 0 with tune not positive or not finite, min_scale negative or NaN,
+ * normals with the point metric. */
+int kss_icp_robust(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt, int64_t nt, const float *tgt_normals,
+                   const kss_icp_params *p, const kss_robust_params *rp, kss_icp_result *res, double last_info[KSS_ROBUST_NINFO]);
+int kss_icp_robust_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
+                       const kss_icp_params *p, const kss_robust_params *rp, kss_icp_result *res,
+                       double last_info[KSS_ROBUST_NINFO]);
+
 /* ---- the two ICP steps above for MANY pairs per call ----
+ * (kss_icp_p2l and kss_icp_trimmed; robust ICP has no batched form yet.)
  * Arguments as kss_icp_batch: packed float[n][3] clouds and npairs + 1 HOST offsets in points; tgt_normals_all is laid out like
  * tgt_all (NULL: computed per target as kss_icp_p2l does; the point metric takes none).  Nothing is redefined: the definitions at
  * kss_icp_p2l and kss_icp_trimmed hold for every pair, and every pair's record is the single-pair call's BIT FOR BIT (fitness:

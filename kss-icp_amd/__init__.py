@@ -12,11 +12,15 @@ from .binding import (KssError, Context, IcpParams, IcpResult, RegisterResult, P
                       exported_symbols, NSUMS, K_NN_SWEEP, K_CORR_REDUCE, K_PRESHAPE, K_ROT_SEARCH, K_POSE_APPLY, K_GRID_NN, K_GRID_BUILD, K_GRID_CHAIN, K_GRID_CHAIN_PASS, K_RESIDENT, K_RESIDENT_PASS, NN_AUTO, NN_BRUTE, NN_GRID,
                       grid_angles, rotation_candidates, rigid_from_sums, build_library,
                       P2L_NSUMS, STATE_DEGENERATE, ERR_DEGENERATE, rigid_from_p2l_sums,
-                      METRIC_POINT, METRIC_PLANE, TRIM_NINFO, TrimParams, trim_rank)
+                      METRIC_POINT, METRIC_PLANE, TRIM_NINFO, TrimParams, trim_rank,
+                      LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, ROBUST_NINFO, RobustParams, robust_params, robust_weight,
+                      robust_scale2)
 from . import synth
 from . import shard
 
 __all__ = ["KssError", "Context", "IcpParams", "IcpResult", "RegisterResult", "Pose", "lib_path", "load_library",
            "exported_symbols", "NSUMS", "grid_angles", "rotation_candidates", "rigid_from_sums", "build_library", "synth",
            "P2L_NSUMS", "STATE_DEGENERATE", "ERR_DEGENERATE", "rigid_from_p2l_sums",
-           "METRIC_POINT", "METRIC_PLANE", "TRIM_NINFO", "TrimParams", "trim_rank"]
+           "METRIC_POINT", "METRIC_PLANE", "TRIM_NINFO", "TrimParams", "trim_rank",
+           "LOSS_L2", "LOSS_HUBER", "LOSS_TUKEY", "LOSS_CAUCHY", "ROBUST_NINFO", "RobustParams", "robust_params", "robust_weight",
+           "robust_scale2"]

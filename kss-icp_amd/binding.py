@@ -20,6 +20,8 @@ STATE_DEGENERATE = 6     # KSS_STATE_DEGENERATE: a point-to-plane pass met a sin
 ERR_DEGENERATE = -7      # KSS_ERR_DEGENERATE
 METRIC_POINT, METRIC_PLANE = 0, 1   # KSS_METRIC_*: the step of kss_icp_trimmed
 TRIM_NINFO = 4           # KSS_TRIM_NINFO: {m candidates, k rank, tau, kept} of a trimmed pass
+LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY = 0, 1, 2, 3   # KSS_LOSS_*: the weight of kss_icp_robust
+ROBUST_NINFO = 4         # KSS_ROBUST_NINFO: {m candidates, c2, sum of weights, cnt kept} of a robust pass
 F32, F64 = 0, 1
 
 # every symbol include/kssicp.h declares (checked by tests/test_abi.py against the header text)
@@ -35,6 +37,8 @@ SYMBOLS = [
     "kss_trim_rank", "kss_trim_threshold", "kss_trim_threshold_dev", "kss_icp_trimmed", "kss_icp_trimmed_dev",
     "kss_icp_p2l_batch", "kss_icp_p2l_batch_dev", "kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev",
     "kss_trim_threshold_batch", "kss_trim_threshold_batch_dev",
+    "kss_robust_default_params", "kss_robust_weight", "kss_robust_scale2", "kss_robust_sums", "kss_robust_sums_dev",
+    "kss_icp_robust", "kss_icp_robust_dev",
 ]
 
 
@@ -69,6 +73,11 @@ class IcpParams(C.Structure):
 
 class TrimParams(C.Structure):
     _fields_ = [("overlap", C.c_double), ("metric", C.c_int), ("trace_trim", C.POINTER(C.c_double))]
+
+
+class RobustParams(C.Structure):
+    _fields_ = [("loss", C.c_int), ("metric", C.c_int), ("scale", C.c_double), ("tune", C.c_double), ("min_scale", C.c_double),
+                ("trace_robust", C.POINTER(C.c_double))]
 
 
 class IcpResult(C.Structure):
@@ -145,6 +154,13 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, i64, dbl, dbl, vp]
     for n in ("kss_icp_trimmed", "kss_icp_trimmed_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(TrimParams), C.POINTER(IcpResult), vp]
+    L.kss_robust_default_params.argtypes = [C.c_int, C.c_int, C.POINTER(RobustParams)]
+    L.kss_robust_weight.argtypes = [C.c_int, dbl, dbl, C.POINTER(dbl)]
+    L.kss_robust_scale2.argtypes = [C.c_int, dbl, C.c_float, dbl, C.POINTER(dbl)]
+    for n in ("kss_robust_sums", "kss_robust_sums_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, i64, i64, dbl, C.POINTER(RobustParams), vp, vp]
+    for n in ("kss_icp_robust", "kss_icp_robust_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(RobustParams), C.POINTER(IcpResult), vp]
     for n in ("kss_icp_p2l_batch", "kss_icp_p2l_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), vp]
     for n in ("kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev"):
@@ -260,6 +276,40 @@ def trim_rank(m, overlap):
     if rc != 0:
         raise KssError(rc, "kss_trim_rank")
     return k.value
+
+
+def robust_params(loss=LOSS_HUBER, metric=METRIC_POINT, **kw):
+    """kss_robust_default_params for the loss and metric, then the fields given by keyword (scale, tune, min_scale)."""
+    L = load_library()
+    rp = RobustParams()
+    rc = L.kss_robust_default_params(int(loss), int(metric), C.byref(rp))
+    if rc != 0:
+        raise KssError(rc, "kss_robust_default_params")
+    for k, v in kw.items():
+        if k not in ("scale", "tune", "min_scale"):
+            raise AttributeError(k)
+        setattr(rp, k, float(v))
+    return rp
+
+
+def robust_weight(loss, x, c2):
+    """kss_robust_weight: the weight of the squared residual x under the loss with squared scale c2 (host only)."""
+    L = load_library()
+    w = C.c_double(0.0)
+    rc = L.kss_robust_weight(int(loss), float(x), float(c2), C.byref(w))
+    if rc != 0:
+        raise KssError(rc, "kss_robust_weight")
+    return w.value
+
+
+def robust_scale2(metric, tune, med_key, min_scale=0.0):
+    """kss_robust_scale2: c2 of the automatic scale from the median key (a float32; host only)."""
+    L = load_library()
+    c2 = C.c_double(0.0)
+    rc = L.kss_robust_scale2(int(metric), float(tune), C.c_float(float(np.float32(med_key))), float(min_scale), C.byref(c2))
+    if rc != 0:
+        raise KssError(rc, "kss_robust_scale2")
+    return c2.value
 
 
 def rigid_from_p2l_sums(sums):
@@ -424,8 +474,9 @@ class Context:
         return p
 
     def _icp_call(self, call, where, p, ns, ncol, trace_cap, fitness_corr, tp=None):
-        """call(res) with the trace and fitness_corr arrays attached to the params p (and to the TrimParams tp), detached again
-        whether it returns or raises; the result dictionary of icp()."""
+        """call(res) with the trace and fitness_corr arrays attached to the params p (and to the TrimParams or RobustParams tp),
+        detached again whether it returns or raises; the result dictionary of icp()."""
+        tname = "trace_robust" if isinstance(tp, RobustParams) else "trace_trim"
         res = IcpResult()
         tr = None
         fc = None
@@ -442,11 +493,13 @@ class Context:
                 p.trace_cap = trace_cap
                 p.trace_n = C.pointer(tr[2])
                 if tp is not None:
-                    tp.trace_trim = tr[3].ctypes.data_as(C.POINTER(C.c_double))
+                    setattr(tp, tname, tr[3].ctypes.data_as(C.POINTER(C.c_double)))
             self._chk(call(res), where)
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
+                if isinstance(tp, RobustParams):
+                    tp.trace_robust = None
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
         out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
@@ -456,7 +509,7 @@ class Context:
             out["trace_sums"] = tr[0][:n].copy()
             out["trace_Tk"] = tr[1][:n].reshape(-1, 4, 4).copy()
             if tp is not None:
-                out["trace_trim"] = tr[3][:n].copy()
+                out[tname] = tr[3][:n].copy()
         if fc:
             out["fitness_idx"], out["fitness_d2"] = fc
         return out
@@ -540,6 +593,64 @@ class Context:
         self._chk(self.L.kss_icp_trimmed_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
                                              C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(tp),
                                              C.byref(res), _p(info)), "kss_icp_trimmed_dev")
+        return res, info
+
+    # ---- robust ICP
+    @staticmethod
+    def _robust_params(rp, loss, metric):
+        return rp if rp is not None else robust_params(loss, metric)
+
+    def robust_sums(self, src, tgt, normals, idx, max_d2=1.0, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT):
+        """kss_robust_sums: (sums, info) of one robust pass over given correspondences.  rp: a RobustParams (robust_params()), or
+        None for the defaults of loss / metric.  normals: nt x 3 for the plane metric, None for the point metric; sums holds
+        NSUMS or P2L_NSUMS doubles by metric, info {m, c2, sum of weights, cnt}."""
+        rp = self._robust_params(rp, loss, metric)
+        s, t = _f32(src), _f32(tgt)
+        nr = _f32(normals) if normals is not None else None
+        i = np.ascontiguousarray(idx, dtype=np.int32)
+        sums = np.zeros(P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, np.float64)
+        info = np.zeros(ROBUST_NINFO, np.float64)
+        self._chk(self.L.kss_robust_sums(self.h, _p(s), _p(t), _p(nr), _p(i), len(s), len(t), float(max_d2), C.byref(rp), _p(sums),
+                                         _p(info)), "kss_robust_sums")
+        return sums, info
+
+    def robust_sums_dev(self, d_src, d_tgt, d_normals, d_idx, n, nt, max_d2=1.0, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT):
+        """kss_robust_sums_dev on device pointers (d_normals 0 / None for the point metric); returns (sums, info)."""
+        rp = self._robust_params(rp, loss, metric)
+        sums = np.zeros(P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, np.float64)
+        info = np.zeros(ROBUST_NINFO, np.float64)
+        self._chk(self.L.kss_robust_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_tgt)),
+                                             C.c_void_p(int(d_normals)) if d_normals else None, C.c_void_p(int(d_idx)), int(n), int(nt),
+                                             float(max_d2), C.byref(rp), _p(sums), _p(info)), "kss_robust_sums_dev")
+        return sums, info
+
+    def icp_robust(self, src, tgt, normals=None, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT, params=None, trace_cap=0,
+                   fitness_corr=False):
+        """Robust ICP (kss_icp_robust): every pass weighs its correspondences with the loss's M-estimator weight, the scale
+        fixed or taken per pass from the median residual.  rp: a RobustParams (robust_params()), or None for the defaults of
+        loss / metric; normals as in icp_trimmed().  The result dictionary of icp_trimmed() with trace_robust (one {m, c2, sum
+        of weights, cnt} row per traced pass) and robust_info (the last pass's) in place of the trimmed records."""
+        rp = self._robust_params(rp, loss, metric)
+        s, t = _f32(src), _f32(tgt)
+        nr = _f32(normals) if normals is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        p = params if params is not None else self.icp_params()
+        info = np.zeros(ROBUST_NINFO, np.float64)
+        out = self._icp_call(lambda res: self.L.kss_icp_robust(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(rp),
+                                                               C.byref(res), _p(info)),
+                             "kss_icp_robust", p, len(s), P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, rp)
+        out["robust_info"] = info
+        return out
+
+    def icp_robust_dev(self, d_src, ns, d_tgt, nt, d_normals, params, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT):
+        """kss_icp_robust_dev on device pointers (d_normals may be 0 / None); returns (IcpResult, robust_info)."""
+        rp = self._robust_params(rp, loss, metric)
+        res = IcpResult()
+        info = np.zeros(ROBUST_NINFO, np.float64)
+        self._chk(self.L.kss_icp_robust_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
+                                            C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(rp),
+                                            C.byref(res), _p(info)), "kss_icp_robust_dev")
         return res, info
 
     # ---- point-to-plane and trimmed ICP, many pairs per call

@@ -1,9 +1,13 @@
 // kss_api.hip -- the C-ABI of include/kssicp.h: context and profiling entry points, and the compute entry points over
-// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_pairb .hip).
+// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_robust / kss_pairb .hip).
 // There is no CPU compute fallback anywhere in this file.
 #pragma clang fp contract(off)
 
+#include <cmath>
+#include <limits>
+
 #include "kss_ctx.hpp"
+#include "kss_robust.hpp"
 
 extern "C" {
 
@@ -66,7 +70,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -569,7 +573,7 @@ int kss_icp_trimmed_dev(kss_ctx* c, const float* d_src, int64_t ns, const float*
     mode.plane = tp->metric == KSS_METRIC_PLANE;
     mode.trimmed = true;
     mode.overlap = tp->overlap;
-    mode.trace_trim = tp->trace_trim;
+    mode.trace_info = tp->trace_trim;
     mode.last_info = last_info;
     if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
     return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
@@ -585,6 +589,147 @@ int kss_icp_trimmed(kss_ctx* c, const float* src, int64_t ns, const float* tgt, 
     if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
     return kss_icp_trimmed_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
                                p, tp, res, last_info);
+}
+
+// ---- robust ICP --------------------------------------------------------------------
+static inline bool robust_loss_ok(int loss) { return loss >= KSS_LOSS_L2 && loss <= KSS_LOSS_CAUCHY; }
+static inline bool robust_metric_ok(int metric) { return metric == KSS_METRIC_POINT || metric == KSS_METRIC_PLANE; }
+
+int kss_robust_default_params(int loss, int metric, kss_robust_params* rp) {
+    if (!rp || !robust_loss_ok(loss) || !robust_metric_ok(metric)) return KSS_ERR_ARG;
+    rp->loss = loss; rp->metric = metric;
+    rp->scale = 0.0;
+    rp->tune = loss == KSS_LOSS_HUBER ? 1.345 : loss == KSS_LOSS_TUKEY ? 4.685 : loss == KSS_LOSS_CAUCHY ? 2.385 : 1.0;
+    rp->min_scale = 0.0;
+    rp->trace_robust = nullptr;
+    return KSS_OK;
+}
+
+int kss_robust_weight(int loss, double x, double c2, double* w) {
+    if (!w || !robust_loss_ok(loss)) return KSS_ERR_ARG;
+    bool kept;
+    *w = robust_weight_of(loss, x, c2, kept);
+    return KSS_OK;
+}
+
+// K of the automatic form: the one place it is formed
+static inline double robust_K(double tune) { return (tune * 1.4826) * (tune * 1.4826); }
+
+int kss_robust_scale2(int metric, double tune, float med_key, double min_scale, double* c2) {
+    if (!c2 || !robust_metric_ok(metric)) return KSS_ERR_ARG;
+    if (!(tune > 0.0) || !std::isfinite(tune) || !(min_scale >= 0.0) || !(med_key >= 0.0f)) return KSS_ERR_ARG;
+    const float med = med_key == 0.0f ? 0.0f : med_key;
+    *c2 = robust_scale2_of(metric == KSS_METRIC_PLANE, robust_K(tune), (double)med, min_scale * min_scale);
+    return KSS_OK;
+}
+
+// the checks of rp that kss_robust_sums and kss_icp_robust share
+static int robust_check(kss_ctx* c, const char* who, const kss_robust_params* rp, const float* nrm) {
+    const std::string w = std::string(who) + ": ";
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
+    if (!rp) return bad("null argument");
+    if (!robust_loss_ok(rp->loss)) return bad("unknown loss");
+    if (!robust_metric_ok(rp->metric)) return bad("unknown metric");
+    if (!(rp->scale >= 0.0) || !std::isfinite(rp->scale)) return bad("scale must be finite and >= 0");
+    if (rp->scale == 0.0 && (!(rp->tune > 0.0) || !std::isfinite(rp->tune))) return bad("tune must be finite and > 0");
+    if (!(rp->min_scale >= 0.0)) return bad("min_scale must be >= 0");
+    if (rp->metric == KSS_METRIC_POINT && nrm) return bad("the point metric takes no normals");
+    return KSS_OK;
+}
+
+// the scale of a checked rp as the kernels take it
+static RobustScale robust_scale_of(const kss_robust_params* rp) {
+    RobustScale rs;
+    rs.loss = rp->loss;
+    rs.autoscale = rp->scale == 0.0;
+    rs.c2 = rp->scale * rp->scale;
+    rs.K = rs.autoscale ? robust_K(rp->tune) : 0.0;
+    rs.min2 = rp->min_scale * rp->min_scale;
+    return rs;
+}
+
+int kss_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n, int64_t nt,
+                        double max_d2, const kss_robust_params* rp, double* sums, double info[KSS_ROBUST_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(robust_check(c, "robust_sums", rp, d_nrm));
+    const RobustScale rs = robust_scale_of(rp);
+    const bool plane = rp->metric == KSS_METRIC_PLANE;
+    if (!d_src || !d_tgt || !d_idx || !sums || !info || (plane && !d_nrm)) return set_err(c, KSS_ERR_ARG, "robust_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "robust_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "robust_sums: cloud too large");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_ROBUST_NINFO) * sizeof(double)));
+    const TrimState* d_sel = nullptr;
+    if (rs.autoscale) {
+        KCHK(ensure(c, c->rob_keys, (size_t)n * sizeof(float)));
+        KCHK(ensure(c, c->trim_rows, trim_rows_bytes(n)));
+        KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
+        d_sel = (const TrimState*)c->trim_state.p + (TRIM_NSTATE - 1);
+    }
+    {
+        ProfScope ps(c, KSS_K_CORR_REDUCE);
+        if (rs.autoscale) {
+            // the keys carry the whole candidate test (a NaN is none); the point metric's bound is applied again, to the same effect
+            launch_robust_keys(c->stream, plane, d_src, nullptr, nullptr, d_idx, nullptr, d_tgt, d_nrm, n, nt, max_d2, (float*)c->rob_keys.p);
+            launch_trim_select(c->stream, (const float*)c->rob_keys.p, n, plane ? std::numeric_limits<double>::infinity() : max_d2, 0.5,
+                               (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p, nullptr);
+        }
+        launch_robust_sums(c->stream, plane, d_src, nullptr, nullptr, d_idx, nullptr, d_tgt, d_nrm, n, nt, max_d2, rs, d_sel,
+                           (double*)c->p2l_rows.p, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(sums, c->h_p2l, (size_t)(plane ? KSS_P2L_NSUMS : KSS_NSUMS) * sizeof(double));
+    std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_ROBUST_NINFO * sizeof(double));
+    return KSS_OK;
+}
+
+int kss_robust_sums(kss_ctx* c, const float* src, const float* tgt, const float* nrm, const int32_t* idx, int64_t n, int64_t nt,
+                    double max_d2, const kss_robust_params* rp, double* sums, double info[KSS_ROBUST_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(robust_check(c, "robust_sums", rp, nrm));
+    if (!src || !tgt || !idx || !sums || !info || (rp->metric == KSS_METRIC_PLANE && !nrm)) return set_err(c, KSS_ERR_ARG, "robust_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "robust_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "robust_sums: cloud too large");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
+    return kss_robust_sums_dev(c, (const float*)c->stage_src.p, (const float*)c->stage_tgt.p, nrm ? (const float*)c->p2l_nrm.p : nullptr,
+                               (const int32_t*)c->stage_idx.p, n, nt, max_d2, rp, sums, info);
+}
+
+int kss_icp_robust_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                       const kss_icp_params* p, const kss_robust_params* rp, kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(robust_check(c, "icp_robust", rp, d_nrm));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_robust: the source-row split (allreduce) is not available for robust ICP");
+    KCHK(pair_check(c, "icp_robust", false, d_src, d_tgt, ns, nt, d_nrm, p, nullptr, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    PairMode mode;
+    mode.plane = rp->metric == KSS_METRIC_PLANE;
+    mode.robust = true;
+    mode.rs = robust_scale_of(rp);
+    mode.trace_info = rp->trace_robust;
+    mode.last_info = last_info;
+    if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
+}
+
+int kss_icp_robust(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm, const kss_icp_params* p,
+                   const kss_robust_params* rp, kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(robust_check(c, "icp_robust", rp, nrm));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_robust: the source-row split (allreduce) is not available for robust ICP");
+    KCHK(pair_check(c, "icp_robust", false, src, tgt, ns, nt, nrm, p, nullptr, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_robust_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
+                              p, rp, res, last_info);
 }
 
 // ---- the same for many pairs per call ------------------------------------------------
@@ -618,7 +763,7 @@ static int pairs_batch_dev(kss_ctx* c, const char* who, const float* d_src, cons
     PairMode mode;
     mode.plane = !tp || tp->metric == KSS_METRIC_PLANE;
     mode.trimmed = tp != nullptr;
-    mode.trace_trim = tp ? tp->trace_trim : nullptr;
+    mode.trace_info = tp ? tp->trace_trim : nullptr;
     std::vector<double> ov;
     if (tp) ov.assign((size_t)npairs, tp->overlap);
     if (tp && overlaps) ov.assign(overlaps, overlaps + npairs);

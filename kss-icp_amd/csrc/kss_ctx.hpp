@@ -54,6 +54,8 @@ struct kss_ctx {
     // trimmed ICP (kss_trim.hip): the selection's histogram rows (one per workgroup, rewritten by every digit) and its
     // TRIM_NSTATE TrimState records; neither has to hold anything between passes
     DevBuf trim_rows, trim_state;
+    // robust ICP (kss_robust.hip): the keys its median is selected over where they are not the NN pass's d2
+    DevBuf rob_keys;
     // the same for many pairs per call (kss_pairb.hip): per-pair descriptors, row -> pair table, packed normals computed at setup
     DevBuf pb_desc, pb_rowpair, pb_nrm;
     const PairState* last_state_dev = nullptr;   // the per-pair state table the last batched NN pass read (null: none, a single pair)
@@ -241,20 +243,23 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // one exact NN pass of a single pair (+ the correspondence sums when sums_out is given)
 int nn_generic_dev(kss_ctx* c, const void* d_src, int64_t ns, const void* d_tgt, int64_t nt, int dtype,
                    int32_t* d_idx, float* d_d2, double sums_out[NSUMS]);
-// ICP of one pair by kss_icp_p2l (plane, untrimmed) or kss_icp_trimmed (either metric): float clouds on the device, d_nrm
-// the target's normals for the plane metric.  The untrimmed point metric is icp_run_dev's.
+// ICP of one pair by kss_icp_p2l (plane, untrimmed), kss_icp_trimmed or kss_icp_robust (either metric): float clouds on the
+// device, d_nrm the target's normals for the plane metric.  The untrimmed, unweighted point metric is icp_run_dev's.
 struct PairMode {
     bool plane = false;             // point-to-plane step (d_nrm given); otherwise point-to-point
     bool trimmed = false;           // keep the closest `overlap` share of each pass's candidates
     double overlap = 1.0;
-    double* trace_trim = nullptr;   // trimmed: KSS_TRIM_NINFO doubles per traced pass
-    double* last_info = nullptr;    // trimmed: KSS_TRIM_NINFO doubles of the last pass
+    double* trace_info = nullptr;   // trimmed / robust: KSS_TRIM_NINFO = KSS_ROBUST_NINFO doubles per traced pass
+    double* last_info = nullptr;    // trimmed / robust: the same of the last pass
+    bool robust = false;            // M-estimator weights (kss_icp_robust; not together with trimmed), scale and loss in rs
+    RobustScale rs;
 };
+static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                  const kss_icp_params* p, const PairMode& mode, kss_icp_result* res);
 int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info);
 // npairs >= 1 pairs in lockstep (kss_icp_p2l_batch, kss_icp_trimmed_batch): d_nrm laid out like d_tgt; overlaps: one per pair
-// (trimmed; M.overlap is not read); info_all: npairs * KSS_TRIM_NINFO or null; M.trace_trim / M.last_info: pair 0's / unused
+// (trimmed; M.overlap is not read); info_all: npairs * KSS_TRIM_NINFO or null; M.trace_info / M.last_info: pair 0's / unused
 int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, const float* d_nrm,
                   int npairs, const kss_icp_params* p, const PairMode& mode, const double* overlaps, kss_icp_result* results, double* info_all);
 // the selection alone for nseg segments of d_d2 in one launch

@@ -7,6 +7,7 @@
 #pragma clang fp contract(off)
 
 #include <emmintrin.h>
+#include <limits>
 
 #include "kss_ctx.hpp"
 
@@ -1093,12 +1094,12 @@ static inline Convergence convergence_of(const kss_icp_params& P) {   // PCL's c
     return cv;
 }
 // one row of the caller's trace: the pass's sums (ncol of them), its T_k and, for a trimmed pass, its {m, k, tau, kept}
-static inline void trace_row(const kss_icp_params& P, const double* s, int ncol, const float* tk, double* trace_trim = nullptr,
+static inline void trace_row(const kss_icp_params& P, const double* s, int ncol, const float* tk, double* trace_info = nullptr,
                              const double* info = nullptr) {
     if (!P.trace_n || *P.trace_n >= P.trace_cap) return;
     if (P.trace_sums) std::memcpy(P.trace_sums + (size_t)(*P.trace_n) * ncol, s, (size_t)ncol * sizeof(double));
     if (P.trace_Tk) std::memcpy(P.trace_Tk + (size_t)(*P.trace_n) * 16, tk, 16 * sizeof(float));
-    if (trace_trim) std::memcpy(trace_trim + (size_t)(*P.trace_n) * KSS_TRIM_NINFO, info, KSS_TRIM_NINFO * sizeof(double));
+    if (trace_info) std::memcpy(trace_info + (size_t)(*P.trace_n) * KSS_TRIM_NINFO, info, KSS_TRIM_NINFO * sizeof(double));
     ++*P.trace_n;
 }
 static inline void fill_result(kss_icp_result& r, const float fin[16], int iterations, int converged, int state, double last_mse,
@@ -1860,6 +1861,10 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // in front, the selection's {m, k, tau, kept} behind KSS_P2L_NSUMS doubles); ONE stream synchronisation; then the solve and
 // the PCL criteria on the host.  Untrimmed plane passes make no selection launches and keep a correspondence by
 // !(d2 > max_d2).  The plan, the packed clouds and the cell list are built once per call.
+// Robust (kss_icp_robust; stated in PairMode, never inferred): behind the NN pass, with the automatic scale, the
+// plane metric's key launch and the same radix select at overlap 0.5 for the median key, then the weighted rows + final
+// launches (the info slots hold {m, c2, sum of weights, cnt}); with a fixed scale only the latter two.  The host step reads cnt
+// for the min_correspondences test and solves the weighted record as it is: [0] is the weight total.
 // What the host does for ONE pair after a pass, the same code for a single pair (pair_loop) and inside a batch (pairs_loop): the
 // min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
 // its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
@@ -1873,7 +1878,9 @@ struct PairTrack {
 };
 static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const double* s, const double* info, PairTrack& t, PairState& hs,
                            bool trace) {
-    if ((int)s[0] < P.min_correspondences) { t.state = KSS_STATE_NO_CORRESPONDENCES; return false; }   // PCL: "Not enough correspondences found"
+    // PCL: "Not enough correspondences found" (robust: the count kept, [0] being the weight total)
+    const double cnt = M.robust ? s[(M.plane ? P2L_NSUMS : NSUMS) - 1] : s[0];
+    if ((int)cnt < P.min_correspondences) { t.state = KSS_STATE_NO_CORRESPONDENCES; return false; }
     if (M.plane) {
         if (!rigid_from_p2l_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
     } else {
@@ -1883,7 +1890,7 @@ static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const dou
     ++t.iters;
     const double mse = (M.plane ? s[28] : s[16]) / s[0];   // point-to-point d2 of the kept correspondences, as PCL's criteria read it
     t.last_mse = mse;
-    if (trace) trace_row(P, s, M.plane ? P2L_NSUMS : NSUMS, t.tk, M.trimmed ? M.trace_trim : nullptr, info);
+    if (trace) trace_row(P, s, M.plane ? P2L_NSUMS : NSUMS, t.tk, M.trimmed || M.robust ? M.trace_info : nullptr, info);
     const bool done = t.cv.has_converged(t.iters, t.tk, mse);
     t.state = t.cv.state;
     if (done) { t.converged = 1; return false; }
@@ -1920,7 +1927,22 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
         {
             ProfScope ps(c, KSS_K_CORR_REDUCE);
             if (M.trimmed) launch_trim_select(c->stream, d_d2, ns, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
-            if (M.plane)
+            if (M.robust) {
+                const TrimState* d_sel = nullptr;
+                if (M.rs.autoscale) {   // the median key: the point metric's keys are the NN pass's d2, the plane metric's are written here
+                    const float* d_keys = d_d2;
+                    double bound = max_d2;
+                    if (M.plane) {
+                        launch_robust_keys(c->stream, true, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, (float*)c->rob_keys.p);
+                        d_keys = (const float*)c->rob_keys.p;
+                        bound = std::numeric_limits<double>::infinity();
+                    }
+                    launch_trim_select(c->stream, d_keys, ns, bound, 0.5, (unsigned*)c->trim_rows.p, d_state, nullptr);
+                    d_sel = d_state + (TRIM_NSTATE - 1);
+                }
+                launch_robust_sums(c->stream, M.plane, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, M.rs, d_sel, d_rows,
+                                   d_rec, d_rec + P2L_NSUMS);
+            } else if (M.plane)
                 launch_p2l_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, d_rows, d_rec, d_cut);
             else
                 launch_trim_point_sums(c->stream, d_out, d_perm, d_idx, d_d2, d_tgt, ns, nt, d_cut, d_rows, d_rec);
@@ -1930,9 +1952,9 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
         ++it;
         double s[P2L_NSUMS], info[KSS_TRIM_NINFO] = {};
         std::memcpy(s, hp, (size_t)ncol * sizeof(double));
-        if (M.trimmed) {
+        if (M.trimmed || M.robust) {
             std::memcpy(info, hp + P2L_NSUMS, sizeof info);
-            info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
+            if (M.trimmed) info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
             if (M.last_info) std::memcpy(M.last_info, info, sizeof info);
         }
         if (!pair_host_step(P, M, s, info, tr, hs[0], true)) break;
@@ -1946,7 +1968,8 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
 // (the arguments are the entry points' to check: kss_api.hip)
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                  const kss_icp_params* p, const PairMode& M, kss_icp_result* res) {
-    if (!M.plane && !M.trimmed) return set_err(c, KSS_ERR_ARG, "pair_run: the untrimmed point metric is kss_icp's");
+    if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: the untrimmed point metric is kss_icp's");
+    if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: trimmed and robust exclude each other");
     HIPCHK(c, hipSetDevice(c->device));
     IcpPlan pl;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1958,10 +1981,11 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
     KCHK(ensure(c, c->p2l_idx, (size_t)ns * sizeof(int32_t)));
     KCHK(ensure(c, c->p2l_d2, (size_t)ns * sizeof(float)));
     KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(ns) * P2L_NSUMS * sizeof(double)));
-    if (M.trimmed) {
+    if (M.trimmed || (M.robust && M.rs.autoscale)) {
         KCHK(ensure(c, c->trim_rows, trim_rows_bytes(ns)));
         KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
     }
+    if (M.robust && M.rs.autoscale && M.plane) KCHK(ensure(c, c->rob_keys, (size_t)ns * sizeof(float)));
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
     const int64_t so[2] = {0, ns}, to[2] = {0, nt};
     KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));

@@ -372,6 +372,25 @@ void launch_trim_point_sums(hipStream_t st, const float4* d_src4, const int32_t*
                             const float* d_tgt3, int64_t n, int64_t nt, const double* d_cut, double* d_rows, double* d_out);
 void launch_f64_to_f32(hipStream_t st, const double* d_in, int64_t n, float* d_out);
 
+// ---- robust ICP (kss_robust.hip) ----
+// The scale of a call: fixed (c2 = scale^2) or automatic (K = (tune * 1.4826)^2 and min2 = min_scale^2, all formed on the
+// host; the pass's c2 = robust_scale2_of(median key) is derived by the sums kernels from the selection's TrimState).
+struct RobustScale {
+    int loss = 0, autoscale = 0;
+    double c2 = 0.0, K = 0.0, min2 = 0.0;
+};
+// Sources as in launch_p2l_sums (d_src3, or d_src4 with an optional d_perm); d_d2: the NN pass's distances, or null with
+// d_src3 (recomputed).  plane: d_nrm3 given.
+// One launch: d_keys[i] = the selection key of source i (point: d2, plane: |r|), NaN where it is no candidate.
+void launch_robust_keys(hipStream_t st, bool plane, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
+                        const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2, float* d_keys);
+// Two launches: the weighted record (KSS_NSUMS or KSS_P2L_NSUMS doubles) into d_out and {m, c2, sum of weights, cnt} into
+// d_info.  d_sel: the TrimState the selection's last step left (automatic scale), null for the fixed one.  d_rows holds
+// p2l_rows_blocks(n) rows of KSS_P2L_NSUMS.
+void launch_robust_sums(hipStream_t st, bool plane, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
+                        const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
+                        const RobustScale& rs, const TrimState* d_sel, double* d_rows, double* d_out, double* d_info);
+
 // ---- point-to-plane and trimmed ICP for many pairs per call (kss_pairb.hip) ----
 // one pair (or one segment of kss_trim_threshold_batch) as the batched kernels see it
 struct alignas(16) PairbDesc {

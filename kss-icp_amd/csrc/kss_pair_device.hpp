@@ -1,13 +1,26 @@
-// kss_pair_device.hpp -- the device code that the single-pair kernels (kss_p2l.hip, kss_trim.hip) and the batched ones
-// (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
+// kss_pair_device.hpp -- the device code that the single-pair kernels (kss_p2l.hip, kss_trim.hip, kss_robust.hip) and the batched
+// ones (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
 //   p2l_rows_column_sum              the fixed-order column sums of the plane metric's rows,
 //   trim_key / trim_resolve_counts   the candidate test and the resolution of one radix digit from a lane's eight bin counts.
 // A pair's bits are the same alone and inside a batch because both forms run these bodies in the same order.
 #pragma once
 #include "kss_device.hpp"
+#include "kss_robust.hpp"
 
 namespace kss {
+
+// ---- robust ICP: what the per-source bodies below do for a candidate ---------------------------------------
+// PAIR_PLAIN   add it to the record unweighted (kss_icp_p2l, kss_icp_trimmed and their batches: the code they always ran);
+// PAIR_ROBUST  count it ([29] / [17] += 1), weigh it with robust_weight_of and, when kept, add the weighted terms and count it
+//              again ([31] / [19] += 1): counts are sums of ones in f64, exact in any order;
+// PAIR_KEY     write its selection key to *ra.key (the caller's, preset to NaN: no candidate) and add nothing.
+enum { PAIR_PLAIN = 0, PAIR_ROBUST = 1, PAIR_KEY = 2 };
+struct RobustArg {
+    int loss = 0;
+    double c2 = 0.0;
+    float* key = nullptr;
+};
 
 // ---- point-to-plane --------------------------------------------------------------------------------------
 constexpr int P2L_THREADS = 256;
@@ -20,12 +33,14 @@ enum { SRC_F3 = 0, SRC_F4 = 1, SRC_F4_PERM = 2 };
 // Source i (an index into idx / d2_in / perm / src3; in a batch the global one) against the target tgt / nrm of nt points.
 // TRIM (trimmed ICP): max_d2 is the pass's cut tau (-1: no candidate) and a correspondence is kept when 0 <= d2 <= tau; the
 // body and the summation order are the same, so an overlap of 1 -- tau = the largest d2 within max_d2 -- gives the untrimmed
-// record bit for bit.
-template <int SRC, bool TRIM>
+// record bit for bit.  MODE != PAIR_PLAIN (robust ICP, with TRIM: the candidates are 0 <= d2 <= max_d2): see above.
+template <int SRC, bool TRIM, int MODE = PAIR_PLAIN>
 __device__ __forceinline__ void p2l_source(double (&acc)[P2L_NSUMS], const float* __restrict__ src3, const float4* __restrict__ src4,
                                            const int32_t* __restrict__ perm, const int32_t* __restrict__ idx,
                                            const float* __restrict__ d2_in, const float* __restrict__ tgt,
-                                           const float* __restrict__ nrm, int64_t i, int64_t nt, double max_d2) {
+                                           const float* __restrict__ nrm, int64_t i, int64_t nt, double max_d2,
+                                           const RobustArg ra = RobustArg()) {
+    static_assert(MODE == PAIR_PLAIN || TRIM, "the robust candidates are those of the trimmed test");
     const int64_t j = idx[i];
     if (j < 0 || j >= nt) return;   // (kss_p2l_sums_dev: an index outside the target contributes nothing)
     float sx, sy, sz;
@@ -38,7 +53,7 @@ __device__ __forceinline__ void p2l_source(double (&acc)[P2L_NSUMS], const float
     const float qx = tgt[3 * j], qy = tgt[3 * j + 1], qz = tgt[3 * j + 2];
     const float nx = nrm[3 * j], ny = nrm[3 * j + 1], nz = nrm[3 * j + 2];
     const double d2 = (double)(d2_in ? d2_in[i] : dist2<false>(sx, sy, sz, qx, qy, qz));
-    acc[29] += d2;
+    if constexpr (MODE == PAIR_PLAIN) acc[29] += d2;
     // PCL: `if (distance > max_dist_sqr) continue;`, and a correspondence whose normal is not finite is dropped
     if ((TRIM ? d2 >= 0.0 && d2 <= max_d2 : !(d2 > max_d2)) && isfinite(nx) && isfinite(ny) && isfinite(nz)) {
         // float, left to right, no fma (PCL computes these in float and widens)
@@ -46,18 +61,43 @@ __device__ __forceinline__ void p2l_source(double (&acc)[P2L_NSUMS], const float
         const float b = nx * sz - nz * sx;
         const float c = ny * sx - nx * sy;
         const float r = ((nx * qx + ny * qy) + nz * qz) - nx * sx - ny * sy - nz * sz;
+        if constexpr (MODE == PAIR_KEY) {
+            *ra.key = fabsf(r);
+            return;
+        }
         const double v[6] = {(double)a, (double)b, (double)c, (double)nx, (double)ny, (double)nz};
         const double rd = (double)r;
-        acc[0] += 1.0;
-        int k = 1;
+        if constexpr (MODE == PAIR_ROBUST) {
+            acc[29] += 1.0;
+            bool kept;
+            const double w = robust_weight_of(ra.loss, rd * rd, ra.c2, kept);   // (the product of two widened floats is exact)
+            if (!kept) return;
+            double wv[6];
 #pragma unroll
-        for (int p = 0; p < 6; ++p)
+            for (int p = 0; p < 6; ++p) wv[p] = w * v[p];
+            acc[0] += w;
+            int k = 1;
 #pragma unroll
-            for (int q = p; q < 6; ++q) acc[k++] += v[p] * v[q];
+            for (int p = 0; p < 6; ++p)
 #pragma unroll
-        for (int p = 0; p < 6; ++p) acc[22 + p] += v[p] * rd;
-        acc[28] += d2;
-        acc[30] += rd * rd;
+                for (int q = p; q < 6; ++q) acc[k++] += wv[p] * v[q];
+#pragma unroll
+            for (int p = 0; p < 6; ++p) acc[22 + p] += wv[p] * rd;
+            acc[28] += w * d2;
+            acc[30] += (w * rd) * rd;
+            acc[31] += 1.0;
+        } else {
+            acc[0] += 1.0;
+            int k = 1;
+#pragma unroll
+            for (int p = 0; p < 6; ++p)
+#pragma unroll
+                for (int q = p; q < 6; ++q) acc[k++] += v[p] * v[q];
+#pragma unroll
+            for (int p = 0; p < 6; ++p) acc[22 + p] += v[p] * rd;
+            acc[28] += d2;
+            acc[30] += rd * rd;
+        }
     }
 }
 
@@ -170,18 +210,58 @@ __device__ __forceinline__ void trim_resolve_counts(const unsigned (&c)[TRIM_LAN
     __syncthreads();
 }
 
-// point metric: source i (as in p2l_source) on accumulate_corr's arithmetic, kept when 0 <= d2 <= cut
-template <bool PERM>
+// point metric: source i (as in p2l_source) on accumulate_corr's arithmetic, kept when 0 <= d2 <= cut.  MODE != PAIR_PLAIN
+// (robust ICP): as above, cut = max_d2; F3 (kss_robust_sums): the sources are the packed float triples src3 and d2 is
+// recomputed as kss_cov does.
+template <bool PERM, int MODE = PAIR_PLAIN, bool F3 = false>
 __device__ __forceinline__ void trim_point_source(double (&acc)[NSUMS], const float4* __restrict__ src4, const int32_t* __restrict__ perm,
                                                   const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
-                                                  const float* __restrict__ tgt, int64_t i, int64_t nt, double cut) {
+                                                  const float* __restrict__ tgt, int64_t i, int64_t nt, double cut,
+                                                  const float* __restrict__ src3 = nullptr, const RobustArg ra = RobustArg()) {
+    static_assert(MODE != PAIR_PLAIN || !F3, "the unweighted form reads the NN pass's float4 output");
     const int64_t j = idx[i];
     if (j < 0 || j >= nt) return;
-    const float d2f = d2_in[i];
-    const double d2 = (double)d2f;
-    if (!(d2 >= 0.0 && d2 <= cut)) return;
-    const float4 p = src4[PERM ? (int64_t)perm[i] : i];
-    accumulate_corr(acc, p.x, p.y, p.z, tgt[3 * j], tgt[3 * j + 1], tgt[3 * j + 2], d2f, cut);
+    if constexpr (MODE == PAIR_PLAIN) {
+        const float d2f = d2_in[i];
+        const double d2 = (double)d2f;
+        if (!(d2 >= 0.0 && d2 <= cut)) return;
+        const float4 p = src4[PERM ? (int64_t)perm[i] : i];
+        accumulate_corr(acc, p.x, p.y, p.z, tgt[3 * j], tgt[3 * j + 1], tgt[3 * j + 2], d2f, cut);
+    } else {
+        float sx, sy, sz;
+        if constexpr (F3) {
+            sx = src3[3 * i]; sy = src3[3 * i + 1]; sz = src3[3 * i + 2];
+        } else {
+            const float4 p = src4[PERM ? (int64_t)perm[i] : i];
+            sx = p.x; sy = p.y; sz = p.z;
+        }
+        const float qx = tgt[3 * j], qy = tgt[3 * j + 1], qz = tgt[3 * j + 2];
+        const float d2f = F3 ? dist2<false>(sx, sy, sz, qx, qy, qz) : d2_in[i];
+        const double d2 = (double)d2f;
+        if (!(d2 >= 0.0 && d2 <= cut)) return;
+        if constexpr (MODE == PAIR_KEY) {
+            *ra.key = d2f;
+            return;
+        }
+        acc[17] += 1.0;
+        bool kept;
+        const double w = robust_weight_of(ra.loss, d2, ra.c2, kept);
+        if (!kept) return;
+        const double p[3] = {(double)sx, (double)sy, (double)sz};
+        const double q[3] = {(double)qx, (double)qy, (double)qz};
+        double ws[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ws[k] = w * p[k];
+        acc[0] += w;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { acc[1 + k] += ws[k]; acc[4 + k] += w * q[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int l = 0; l < 3; ++l) acc[7 + 3 * k + l] += ws[k] * q[l];
+        acc[16] += w * d2;
+        acc[19] += 1.0;
+    }
 }
 
 }  // namespace kss

@@ -96,6 +96,21 @@ def make_partial_pair(pair_id, n, deg, lo, hi, t=(0.02, -0.01, 0.03), jitter=1e-
     return src.astype(np.float32), tgt.astype(np.float32), R, t, overlap
 
 
+def make_outlier_pair(pair_id, n, deg, frac, t=(0.02, -0.01, 0.03), box=0.6):
+    """A fully overlapping bumpy pair -- make_pair(pair_id, n, R, t, shape="bumpy") with R = deg degrees about
+    sphere(7000 + pair_id, 1)[0] -- whose first k = int(frac * n) source points are pushed off the surface: (u - 0.5) * 2 * box is
+    added to them in f64, u[:, j] = u01(9000 + pair_id, k, j * k), then rounded to float.  Returns (source, target) float32 and
+    the true (R, t) of source = R model + t."""
+    R = rot_axis_angle(sphere(7000 + pair_id, 1)[0], np.deg2rad(deg))
+    t = np.asarray(t, dtype=np.float64)
+    src, tgt = make_pair(pair_id, n, R=R, t=t, shape="bumpy")
+    k = int(frac * n)
+    u = np.stack([u01(9000 + pair_id, k, j * k) for j in range(3)], axis=1)
+    out = src.astype(np.float64)
+    out[:k] += (u - 0.5) * 2.0 * box
+    return out.astype(np.float32), tgt, R, t
+
+
 def config_c2(n=100000):
     """C2: single 100k x 100k pair, R_z(10 deg) (inside ICP's basin)."""
     return make_pair(0, n, R=rot_axis_angle([0, 0, 1], np.deg2rad(10.0)))
