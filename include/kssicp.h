@@ -357,8 +357,8 @@ int kss_icp_robust_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float
                        const kss_icp_params *p, const kss_robust_params *rp, kss_icp_result *res,
                        double last_info[KSS_ROBUST_NINFO]);
 
-/* ---- the two ICP steps above for MANY pairs per call ----
- * (kss_icp_p2l and kss_icp_trimmed; robust ICP has no batched form yet.)
+/* ---- the ICP steps above for MANY pairs per call ----
+ * (kss_icp_p2l and kss_icp_trimmed here; robust ICP: kss_icp_robust_batch below.)
  * Arguments as kss_icp_batch: packed float[n][3] clouds and npairs + 1 HOST offsets in points; tgt_normals_all is laid out like
  * tgt_all (NULL: computed per target as kss_icp_p2l does; the point metric takes none).  Nothing is redefined: the definitions at
  * kss_icp_p2l and kss_icp_trimmed hold for every pair, and every pair's record is the single-pair call's BIT FOR BIT (fitness:
@@ -378,6 +378,25 @@ int kss_icp_trimmed_batch(kss_ctx *ctx, const float *src_all, const int64_t *src
 int kss_icp_trimmed_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_tgt_all, const int64_t *tgt_off,
                               const float *d_tgt_normals_all, int npairs, const kss_icp_params *p, const kss_trim_params *tp,
                               const double *overlaps, kss_icp_result *results, double *info_all);
+/* ---- robust ICP for MANY pairs per call ----
+ * Arguments as kss_icp_trimmed_batch.  Nothing is redefined: the definition at kss_icp_robust holds for every pair, and every
+ * pair's record -- T, iterations, state, converged, last_mse, the info record, pair 0's traces -- is the single-pair call's BIT FOR
+ * BIT (fitness: to the rounding of the NN engine's own summation order), in any batch order and any split over calls, under every NN
+ * engine and tuning knob.  rp gives the loss, the metric, tune and min_scale of the whole batch.  scales: one double per pair, or
+ * NULL for rp->scale everywhere; per pair > 0 is a fixed scale and 0 the automatic one from the pair's own per-pass median, so a
+ * batch may mix both.  info_all: npairs * KSS_ROBUST_NINFO doubles, every pair's last {m, c2, sum of weights, cnt}, all zero for a
+ * pair that ran no pass (may be NULL).  The pairs run in lockstep; behind the NN pass a pass makes two launches when every pair has
+ * a fixed scale, otherwise three (point metric) or four (plane metric), whatever the pair count.  A pair that ends -- converged,
+ * KSS_STATE_NO_CORRESPONDENCES, KSS_STATE_DEGENERATE -- leaves the others untouched.  trace_*, rp->trace_robust and fitness_idx /
+ * fitness_d2 describe pair 0.  KSS_ERR_ARG: a set allreduce, everything kss_icp_robust refuses in rp, a scales entry that is
+ * negative or not finite, an automatic pair with a tune that is not positive and finite, normals with the point metric, an empty
+ * pair, NULL results. */
+int kss_icp_robust_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *tgt_all, const int64_t *tgt_off,
+                         const float *tgt_normals_all, int npairs, const kss_icp_params *p, const kss_robust_params *rp,
+                         const double *scales, kss_icp_result *results, double *info_all);
+int kss_icp_robust_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_tgt_all, const int64_t *tgt_off,
+                             const float *d_tgt_normals_all, int npairs, const kss_icp_params *p, const kss_robust_params *rp,
+                             const double *scales, kss_icp_result *results, double *info_all);
 /* the selection alone for nseg segments [off[i], off[i + 1]) of d2_all in ONE launch: overlaps and info_all (nseg * KSS_TRIM_NINFO)
  * hold one entry per segment; every record equals kss_trim_threshold on that segment.  An empty segment is KSS_ERR_ARG. */
 int kss_trim_threshold_batch(kss_ctx *ctx, const float *d2_all, const int64_t *off, int nseg, double max_d2,

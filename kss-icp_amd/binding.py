@@ -38,7 +38,7 @@ SYMBOLS = [
     "kss_icp_p2l_batch", "kss_icp_p2l_batch_dev", "kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev",
     "kss_trim_threshold_batch", "kss_trim_threshold_batch_dev",
     "kss_robust_default_params", "kss_robust_weight", "kss_robust_scale2", "kss_robust_sums", "kss_robust_sums_dev",
-    "kss_icp_robust", "kss_icp_robust_dev",
+    "kss_icp_robust", "kss_icp_robust_dev", "kss_icp_robust_batch", "kss_icp_robust_batch_dev",
 ]
 
 
@@ -165,6 +165,8 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), vp]
     for n in ("kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(TrimParams), vp, vp, vp]
+    for n in ("kss_icp_robust_batch", "kss_icp_robust_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(RobustParams), vp, vp, vp]
     for n in ("kss_trim_threshold_batch", "kss_trim_threshold_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, C.c_int, dbl, vp, vp]
     for n in ("kss_rotation_search", "kss_rotation_search_dev"):
@@ -657,6 +659,7 @@ class Context:
     def _batch_call(self, call, where, p, so, ncol, trace_cap, fitness_corr, tp=None):
         """call(res) for a batch: the trace and fitness_corr arrays (pair 0's) attached to p / tp as in _icp_call, detached again
         whether it returns or raises.  Returns (list of IcpResult, extras of pair 0)."""
+        tname = "trace_robust" if isinstance(tp, RobustParams) else "trace_trim"
         npairs = len(so) - 1
         res = (IcpResult * npairs)()
         ns0 = int(so[1] - so[0]) if npairs > 0 else 0
@@ -674,11 +677,13 @@ class Context:
                 p.trace_cap = trace_cap
                 p.trace_n = C.pointer(tr[2])
                 if tp is not None:
-                    tp.trace_trim = tr[3].ctypes.data_as(C.POINTER(C.c_double))
+                    setattr(tp, tname, tr[3].ctypes.data_as(C.POINTER(C.c_double)))
             self._chk(call(C.cast(res, C.c_void_p)), where)
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
+                if isinstance(tp, RobustParams):
+                    tp.trace_robust = None
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
         extra = {}
@@ -687,7 +692,7 @@ class Context:
             extra["trace_sums"] = tr[0][:n].copy()
             extra["trace_Tk"] = tr[1][:n].reshape(-1, 4, 4).copy()
             if tp is not None:
-                extra["trace_trim"] = tr[3][:n].copy()
+                extra[tname] = tr[3][:n].copy()
         if fc:
             extra["fitness_idx"], extra["fitness_d2"] = fc
         return list(res), extra
@@ -762,6 +767,50 @@ class Context:
         self._chk(self.L.kss_icp_trimmed_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
                                                    C.c_void_p(int(d_normals_all)) if d_normals_all else None, npairs, C.byref(params),
                                                    C.byref(tp), _p(ov), C.cast(res, C.c_void_p), _p(info)), "kss_icp_trimmed_batch_dev")
+        return list(res), info
+
+    # ---- robust ICP, many pairs per call
+    @staticmethod
+    def _scales(scales, npairs):
+        if scales is None:
+            return None
+        sc = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
+        if len(sc) != npairs:
+            raise ValueError("scales must hold one entry per pair")
+        return sc
+
+    def icp_robust_batch(self, src_all, src_off, tgt_all, tgt_off, normals_all=None, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT,
+                         scales=None, params=None, trace_cap=0, fitness_corr=False):
+        """kss_icp_robust_batch: robust ICP of npairs pairs in one call.  rp as in icp_robust() (loss, metric, tune and min_scale of
+        the whole batch); scales: one per pair (> 0 fixed, 0 automatic), or None for rp.scale everywhere.  Returns (list of
+        IcpResult, robust_info of every pair as npairs x ROBUST_NINFO, dictionary with pair 0's traces, trace_robust among them)."""
+        rp = self._robust_params(rp, loss, metric)
+        s, t = _f32(src_all), _f32(tgt_all)
+        nr = _f32(normals_all) if normals_all is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        sc = self._scales(scales, npairs)
+        p = params if params is not None else self.icp_params()
+        info = np.zeros((max(npairs, 0), ROBUST_NINFO), np.float64)
+        res, extra = self._batch_call(
+            lambda res: self.L.kss_icp_robust_batch(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), npairs, C.byref(p), C.byref(rp), _p(sc), res, _p(info)),
+            "kss_icp_robust_batch", p, so, P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, rp)
+        return res, info, extra
+
+    def icp_robust_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params, rp=None, loss=LOSS_HUBER,
+                             metric=METRIC_POINT, scales=None):
+        """kss_icp_robust_batch_dev on device pointers; returns (list of IcpResult, robust_info npairs x ROBUST_NINFO)."""
+        rp = self._robust_params(rp, loss, metric)
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        sc = self._scales(scales, npairs)
+        res = (IcpResult * npairs)()
+        info = np.zeros((npairs, ROBUST_NINFO), np.float64)
+        self._chk(self.L.kss_icp_robust_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
+                                                  C.c_void_p(int(d_normals_all)) if d_normals_all else None, npairs, C.byref(params),
+                                                  C.byref(rp), _p(sc), C.cast(res, C.c_void_p), _p(info)), "kss_icp_robust_batch_dev")
         return list(res), info
 
     def trim_threshold_batch(self, d2_all, off, overlaps, max_d2=1.0):

@@ -637,16 +637,17 @@ static int robust_check(kss_ctx* c, const char* who, const kss_robust_params* rp
     return KSS_OK;
 }
 
-// the scale of a checked rp as the kernels take it
-static RobustScale robust_scale_of(const kss_robust_params* rp) {
+// the scale of a checked rp as the kernels take it (scale: rp->scale, or the pair's own in a batch)
+static RobustScale robust_scale_of(const kss_robust_params* rp, double scale) {
     RobustScale rs;
     rs.loss = rp->loss;
-    rs.autoscale = rp->scale == 0.0;
-    rs.c2 = rp->scale * rp->scale;
+    rs.autoscale = scale == 0.0;
+    rs.c2 = scale * scale;
     rs.K = rs.autoscale ? robust_K(rp->tune) : 0.0;
     rs.min2 = rp->min_scale * rp->min_scale;
     return rs;
 }
+static RobustScale robust_scale_of(const kss_robust_params* rp) { return robust_scale_of(rp, rp->scale); }
 
 int kss_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n, int64_t nt,
                         double max_d2, const kss_robust_params* rp, double* sums, double info[KSS_ROBUST_NINFO]) {
@@ -811,6 +812,62 @@ int kss_icp_trimmed_batch(kss_ctx* c, const float* src_all, const int64_t* src_o
                           kss_icp_result* results, double* info_all) {
     if (c && !tp) return set_err(c, KSS_ERR_ARG, "icp_trimmed_batch: null argument");
     return pairs_batch_host(c, "icp_trimmed_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, tp, overlaps, results, info_all);
+}
+
+// ---- robust ICP for many pairs per call ----------------------------------------------
+// what the two entry points share beyond pair_check: rp, allreduce and the per-pair scales (null: rp->scale everywhere)
+static int robust_batch_check(kss_ctx* c, const kss_robust_params* rp, const float* nrm, const kss_icp_params* p, const int64_t* src_off,
+                              const int64_t* tgt_off, int npairs, const double* scales) {
+    KCHK(robust_check(c, "icp_robust_batch", rp, nrm));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: the source-row split (allreduce) is not available for robust ICP");
+    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: bad batch");
+    if (scales) {
+        const bool tune_ok = rp->tune > 0.0 && std::isfinite(rp->tune);
+        for (int i = 0; i < npairs; ++i) {
+            if (!(scales[i] >= 0.0) || !std::isfinite(scales[i])) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: a scale must be finite and >= 0");
+            if (scales[i] == 0.0 && !tune_ok) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: tune must be finite and > 0");
+        }
+    }
+    return KSS_OK;
+}
+
+int kss_icp_robust_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off,
+                             const float* d_nrm, int npairs, const kss_icp_params* p, const kss_robust_params* rp, const double* scales,
+                             kss_icp_result* results, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(robust_batch_check(c, rp, d_nrm, p, src_off, tgt_off, npairs, scales));
+    KCHK(pair_check(c, "icp_robust_batch", false, d_src, d_tgt, 0, 0, d_nrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);   // rebased to the first pair, as in pairs_batch_dev
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
+    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
+    if (d_nrm) d_nrm += 3 * tgt_off[0];
+    PairMode mode;
+    mode.plane = rp->metric == KSS_METRIC_PLANE;
+    mode.robust = true;
+    mode.rs = robust_scale_of(rp);
+    mode.trace_info = rp->trace_robust;
+    std::vector<RobustScale> rs((size_t)npairs);
+    for (int i = 0; i < npairs; ++i) rs[i] = robust_scale_of(rp, scales ? scales[i] : rp->scale);
+    if (mode.plane && !d_nrm) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, &d_nrm));
+    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_nrm, npairs, p, mode, nullptr, results, info_all, rs.data());
+}
+
+int kss_icp_robust_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off, const float* nrm,
+                         int npairs, const kss_icp_params* p, const kss_robust_params* rp, const double* scales, kss_icp_result* results,
+                         double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(robust_batch_check(c, rp, nrm, p, src_off, tgt_off, npairs, scales));
+    KCHK(pair_check(c, "icp_robust_batch", false, src, tgt, 0, 0, nrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
+    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    if (nrm) KCHK(upload(c, c->pb_nrm, nrm + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
+    return kss_icp_robust_batch_dev(c, (const float*)c->stage_src.p, so.data(), (const float*)c->stage_tgt.p, to.data(),
+                                    nrm ? (const float*)c->pb_nrm.p : nullptr, npairs, p, rp, scales, results, info_all);
 }
 
 static int trim_batch_check(kss_ctx* c, const float* d2, const int64_t* off, int nseg, const double* overlaps, const double* info_all) {

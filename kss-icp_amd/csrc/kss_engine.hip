@@ -2020,7 +2020,8 @@ int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, 
     return KSS_OK;
 }
 
-// ---- the same metrics for MANY pairs per call: kss_icp_p2l_batch, kss_icp_trimmed_batch ----
+// ---- the same metrics for MANY pairs per call: kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch
+// (2.13: behind the NN pass the key launch (plane) and the selection when any pair has the automatic scale, then two sums launches) ----
 // pair_loop in lockstep over npairs >= 1 pairs.  Per pass: ONE NN pass over the pairs still active (idx / d2 by global source
 // index), ONE selection launch when trimmed, TWO sums launches (kss_pairb.hip), ONE stream synchronisation, then
 // pair_host_step for every active pair (the host pool from 64 pairs up, each pair on exactly one thread).  A pair that ends
@@ -2032,7 +2033,7 @@ struct DeferWait {   // the NN pass does not wait for its sums: the launches beh
     ~DeferWait() { c->defer_wait = false; }
 };
 static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
-                      const int32_t* d_perm, kss_icp_result* results, double* info_all) {
+                      const int32_t* d_perm, bool rob_select, kss_icp_result* results, double* info_all) {
     const int np = pl_in.npairs;
     const IcpPlan* plan = &pl_in;   // may change to the brute-force plan below
     IcpPlan brute_plan;
@@ -2055,6 +2056,8 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     double* d_info = d_rec + (size_t)np * P2L_NSUMS;
     TrimState* d_ts = (TrimState*)c->trim_state.p;
     const PairbDesc* d_desc = (const PairbDesc*)c->pb_desc.p;
+    const RobustScale* d_rs = (const RobustScale*)c->pb_rscale.p;   // (robust)
+    const int32_t* d_row_pair = (const int32_t*)c->pb_rowpair.p;
     int total_rows = 0;
     for (int p = 0; p < np; ++p) total_rows += stream_blocks(pl_in.g[p].ns);
     if (P.trace_n) *P.trace_n = 0;
@@ -2076,9 +2079,17 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
         const PairState* d_state = c->last_state_dev;   // (a single pair on its own cell list has none: it is active)
         {
             ProfScope ps(c, KSS_K_CORR_REDUCE);
-            if (M.trimmed) launch_pairb_select(c->stream, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
-            launch_pairb_sums(c->stream, M.plane, M.trimmed, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, (const int32_t*)c->pb_rowpair.p,
-                              total_rows, np, d_state, d_ts, max_d2, (double*)c->p2l_rows.p, d_rec);
+            if (M.robust) {
+                if (rob_select)   // some pair takes its scale from the pass's median key
+                    launch_pairb_robust_select(c->stream, M.plane, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
+                                               d_state, d_rs, max_d2, (float*)c->rob_keys.p, d_ts);
+                launch_pairb_robust_sums(c->stream, M.plane, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np, d_state,
+                                         d_rs, d_ts, max_d2, (double*)c->p2l_rows.p, d_rec, d_info);
+            } else {
+                if (M.trimmed) launch_pairb_select(c->stream, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
+                launch_pairb_sums(c->stream, M.plane, M.trimmed, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
+                                  d_state, d_ts, max_d2, (double*)c->p2l_rows.p, d_rec);
+            }
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2095,9 +2106,9 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                 if (!active[p]) continue;
                 const double* s = hrec + (size_t)p * P2L_NSUMS;
                 double info[KSS_TRIM_NINFO] = {};
-                if (M.trimmed) {
+                if (M.trimmed || M.robust) {
                     std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, sizeof info);
-                    info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
+                    if (M.trimmed) info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
                     if (info_all) std::memcpy(info_all + (size_t)p * KSS_TRIM_NINFO, info, sizeof info);
                 }
                 if (!pair_host_step(P, M, s, info, tr[p], hs[p], p == 0)) {
@@ -2153,8 +2164,11 @@ static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows
 
 // (the arguments are the entry points' to check: kss_api.hip)
 int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, const float* d_nrm,
-                  int npairs, const kss_icp_params* p, const PairMode& M, const double* overlaps, kss_icp_result* results, double* info_all) {
-    if (!M.plane && !M.trimmed) return set_err(c, KSS_ERR_ARG, "pairs_run: the untrimmed point metric is kss_icp_batch's");
+                  int npairs, const kss_icp_params* p, const PairMode& M, const double* overlaps, kss_icp_result* results, double* info_all,
+                  const RobustScale* rscales) {
+    if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: the untrimmed point metric is kss_icp_batch's");
+    if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: trimmed and robust exclude each other");
+    if (M.robust && !rscales) return set_err(c, KSS_ERR_ARG, "pairs_run: robust needs the per-pair scales");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> ns(npairs), nt(npairs);
     for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }
@@ -2181,6 +2195,13 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
     KCHK(ensure(c, c->p2l_d2, (size_t)pl.total_src * sizeof(float)));
     KCHK(ensure(c, c->p2l_rows, (size_t)total_rows * P2L_NSUMS * sizeof(double)));
     KCHK(ensure(c, c->trim_state, (size_t)std::max(npairs, TRIM_NSTATE) * sizeof(TrimState)));
+    bool rob_select = false;
+    if (M.robust) {   // the per-pair scale table; the keys of the plane metric's median where a pair asks for one
+        for (int i = 0; i < npairs; ++i) rob_select = rob_select || rscales[i].autoscale != 0;
+        KCHK(upload(c, c->pb_rscale, rscales, (size_t)npairs * sizeof(RobustScale)));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's table may be pageable and short-lived)
+        if (rob_select && M.plane) KCHK(ensure(c, c->rob_keys, (size_t)pl.total_src * sizeof(float)));
+    }
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
     KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));
     KCHK(grid_setup(c, pl));
@@ -2193,7 +2214,7 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         d_perm = (const int32_t*)c->p2l_perm.p;
     }
     const auto t1 = std::chrono::steady_clock::now();
-    const int rc = pairs_loop(c, pl, *p, M, d_tgt, d_nrm, d_perm, results, info_all);
+    const int rc = pairs_loop(c, pl, *p, M, d_tgt, d_nrm, d_perm, rob_select, results, info_all);
     guard.ok = rc == KSS_OK;
     const auto t2 = std::chrono::steady_clock::now();
     c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();

@@ -408,6 +408,18 @@ void launch_pairb_sums(hipStream_t st, bool plane, bool trimmed, const float4* d
                        const float* d_d2, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
                        int total_rows, int npairs, const PairState* d_state, const TrimState* d_ts, double max_d2, double* d_rows,
                        double* d_out);
+// ---- robust ICP for many pairs per call (kss_pairb.hip): d_rs holds one RobustScale per pair ----
+// the median key of every active AUTOMATIC pair into d_ts[pair] (the others' entries are not written): the plane metric's key
+// launch (|r| into d_keys by global source index) and the selection over them; the point metric selects over d_d2 (one launch)
+void launch_pairb_robust_select(hipStream_t st, bool plane, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                                const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair, int total_rows,
+                                int npairs, const PairState* d_state, const RobustScale* d_rs, double max_d2, float* d_keys, TrimState* d_ts);
+// two launches: every active pair's weighted record into d_out[pair * KSS_P2L_NSUMS] and {m, c2, sum of weights, cnt} into
+// d_info[pair * KSS_ROBUST_NINFO]
+void launch_pairb_robust_sums(hipStream_t st, bool plane, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                              const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair, int total_rows,
+                              int npairs, const PairState* d_state, const RobustScale* d_rs, const TrimState* d_ts, double max_d2,
+                              double* d_rows, double* d_out, double* d_info);
 
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,

@@ -15,9 +15,18 @@
 //   pairb_final_kernel    one workgroup per pair: the fixed-order column sums of the pair's rows, written to host-mapped memory.
 // So a pair's record is added in the order its source count alone decides: the single-pair call's bits.
 // Workgroups of pairs that are no longer active leave at once: they read the per-pair state table of the NN pass.
+//
+// Robust ICP for many pairs has the same shape, with the pair's RobustScale from a per-pair table:
+//   pairb_robust_keys_kernel     plane metric, automatic pairs: pairb_rows_kernel's grid writes |r| per source (NaN: no candidate)
+//                                into a batch-wide key array by global original source index.
+//   pairb_robust_select_kernel   automatic pairs: the select above at overlap 0.5 over the pair's keys (point: the NN pass's d2),
+//                                the pair's TrimState alone -- its {m, k, tau, kept} is no part of the robust info record.
+//   pairb_robust_rows_kernel     pairb_rows_kernel with the PAIR_ROBUST bodies; every workgroup derives the pass's c2 itself.
+//   pairb_robust_final_kernel    the column sums, the record and {m, c2, sum of weights, cnt} to host-mapped memory.
+// Fixed-scale pairs skip the first two; a batch without an automatic pair does not launch them.
 #pragma clang fp contract(off)
 
-#include "kss_pair_device.hpp"
+#include "kss_robust_device.hpp"
 
 namespace kss {
 
@@ -133,6 +142,117 @@ __global__ __launch_bounds__(P2L_THREADS) void pairb_final_kernel(const double* 
     }
 }
 
+// ---- robust ICP (kss_robust.hip's kernels, per pair) ------------------------------------------------------------------------
+__device__ __forceinline__ bool pairb_robust_selects(const PairState* __restrict__ state, const RobustScale* __restrict__ rs, int p) {
+    return pairb_active(state, p) && rs[p].autoscale != 0;
+}
+
+template <bool PERM>
+__global__ __launch_bounds__(P2L_THREADS) void pairb_robust_keys_kernel(const float4* __restrict__ src4, const int32_t* __restrict__ perm,
+                                                                        const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
+                                                                        const float* __restrict__ tgt_all, const float* __restrict__ nrm_all,
+                                                                        const PairbDesc* __restrict__ desc, const int32_t* __restrict__ row_pair,
+                                                                        const PairState* __restrict__ state, const RobustScale* __restrict__ rs,
+                                                                        double max_d2, float* __restrict__ keys) {
+    const int p = row_pair[blockIdx.x];
+    if (!pairb_robust_selects(state, rs, p)) return;
+    const PairbDesc d = desc[p];
+    const float* tgt = tgt_all + 3 * d.tgt_off;
+    const float* nrm = nrm_all + 3 * d.tgt_off;
+    const int64_t step = (int64_t)d.nrows * P2L_THREADS;
+    for (int64_t i = (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x; i < d.ns; i += step) {
+        float key = __uint_as_float(0x7fc00000u);
+        RobustArg ra;
+        ra.key = &key;
+        double acc[P2L_NSUMS];   // (never read in this mode)
+        p2l_source<PERM ? SRC_F4_PERM : SRC_F4, true, PAIR_KEY>(acc, nullptr, src4, perm, idx, d2_in, tgt, nrm, d.src_base + i, d.nt, max_d2, ra);
+        keys[d.src_base + i] = key;
+    }
+}
+
+// the median key of every automatic pair: pairb_select_kernel at overlap 0.5, the TrimState alone
+__global__ __launch_bounds__(TRIM_HIST_THREADS) void pairb_robust_select_kernel(const float* __restrict__ keys_all, const PairbDesc* __restrict__ desc,
+                                                                                const PairState* __restrict__ state,
+                                                                                const RobustScale* __restrict__ rs, double bound,
+                                                                                TrimState* __restrict__ st_out) {
+    __shared__ unsigned hist[TRIM_BINS];
+    __shared__ TrimState cur[2];
+    __shared__ unsigned wave_tot[TRIM_HIST_THREADS / 64];
+    const int p = blockIdx.x;
+    if (!pairb_robust_selects(state, rs, p)) return;
+    const PairbDesc d = desc[p];
+    const float* keys = keys_all + d.src_base;
+    pairb_digit<0>(keys, d.ns, bound, 0.5, hist, &cur[1], &cur[0], wave_tot);
+    pairb_digit<1>(keys, d.ns, bound, 0.5, hist, &cur[0], &cur[1], wave_tot);
+    pairb_digit<2>(keys, d.ns, bound, 0.5, hist, &cur[1], &cur[0], wave_tot);
+    if (threadIdx.x == 0) st_out[p] = cur[0];
+}
+
+template <bool PLANE, bool PERM>
+__global__ __launch_bounds__(P2L_THREADS) void pairb_robust_rows_kernel(const float4* __restrict__ src4, const int32_t* __restrict__ perm,
+                                                                        const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
+                                                                        const float* __restrict__ tgt_all, const float* __restrict__ nrm_all,
+                                                                        const PairbDesc* __restrict__ desc, const int32_t* __restrict__ row_pair,
+                                                                        const PairState* __restrict__ state, const RobustScale* __restrict__ rs,
+                                                                        const TrimState* __restrict__ ts, double max_d2, double* __restrict__ rows) {
+    constexpr int NC = PLANE ? P2L_NSUMS : NSUMS;
+    __shared__ double sh[P2L_THREADS / 64][NC];
+    const int p = row_pair[blockIdx.x];
+    if (!pairb_active(state, p)) return;
+    const PairbDesc d = desc[p];
+    double acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+    const RobustScale s = rs[p];
+    RobustArg ra;
+    ra.loss = s.loss;
+    ra.c2 = robust_pass_c2(s, PLANE, ts + p);
+    const float* tgt = tgt_all + 3 * d.tgt_off;
+    const int64_t step = (int64_t)d.nrows * P2L_THREADS;
+    for (int64_t i = (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x; i < d.ns; i += step) {
+        if constexpr (PLANE)
+            p2l_source<PERM ? SRC_F4_PERM : SRC_F4, true, PAIR_ROBUST>(acc, nullptr, src4, perm, idx, d2_in, tgt, nrm_all + 3 * d.tgt_off,
+                                                                       d.src_base + i, d.nt, max_d2, ra);
+        else
+            trim_point_source<PERM, PAIR_ROBUST, false>(acc, src4, perm, idx, d2_in, tgt, d.src_base + i, d.nt, max_d2, nullptr, ra);
+    }
+    const double r = block_sum<NC>(acc, sh);
+    if (threadIdx.x < NC) rows[(int64_t)blockIdx.x * NC + threadIdx.x] = r;
+}
+
+// out: KSS_P2L_NSUMS doubles per pair for either metric, the record as the columns are (plane [29] = m, [31] = cnt; point [17] = m,
+// [18] = 0, [19] = cnt); info: {m, c2, [0], cnt} per pair
+template <bool PLANE>
+__global__ __launch_bounds__(P2L_THREADS) void pairb_robust_final_kernel(const double* __restrict__ rows, const PairbDesc* __restrict__ desc,
+                                                                         const PairState* __restrict__ state, const RobustScale* __restrict__ rs,
+                                                                         const TrimState* __restrict__ ts, double* __restrict__ out,
+                                                                         double* __restrict__ info_out) {
+    constexpr int NC = PLANE ? P2L_NSUMS : NSUMS;
+    constexpr int NG = PLANE ? P2L_GROUPS : ROWSUM_GROUPS;
+    __shared__ double shg[NG][NC];
+    const int p = blockIdx.x;
+    if (!pairb_active(state, p)) return;
+    const PairbDesc d = desc[p];
+    const double* r = rows + (int64_t)d.row_base * NC;
+    double* o = out + (int64_t)p * P2L_NSUMS;
+    double* info = info_out + (int64_t)p * KSS_ROBUST_NINFO;
+    const int t = threadIdx.x;
+    if constexpr (PLANE) {
+        const double v = p2l_rows_column_sum(r, d.nrows, shg);
+        if (t < P2L_NSUMS) o[t] = v;
+        if (t == 29) info[0] = v;
+        if (t == 0) info[2] = v;
+        if (t == 31) info[3] = v;
+    } else {
+        const double v = rows_column_sum(r, d.nrows, shg);
+        if (t < NSUMS) o[t] = t == 18 ? 0.0 : v;
+        if (t == 17) info[0] = v;
+        if (t == 0) info[2] = v;
+        if (t == 19) info[3] = v;
+    }
+    if (t == 1) info[1] = robust_pass_c2(rs[p], PLANE, ts + p);
+}
+
 void launch_pairb_select(hipStream_t st, const float* d_d2, const PairbDesc* d_desc, int npairs, const PairState* d_state, double max_d2,
                          TrimState* d_ts, double* d_info) {
     hipLaunchKernelGGL(pairb_select_kernel, dim3(npairs), dim3(TRIM_HIST_THREADS), 0, st, d_d2, d_desc, d_state, max_d2, d_ts, d_info);
@@ -154,6 +274,40 @@ void launch_pairb_sums(hipStream_t st, bool plane, bool trimmed, const float4* d
         hipLaunchKernelGGL(pairb_final_kernel<false>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_out);
     }
 #undef KSS_PAIRB_ROWS
+}
+
+void launch_pairb_robust_select(hipStream_t st, bool plane, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                                const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair, int total_rows,
+                                int npairs, const PairState* d_state, const RobustScale* d_rs, double max_d2, float* d_keys, TrimState* d_ts) {
+    const float* keys = d_d2;   // the point metric's keys are the NN pass's d2, the plane metric's are written here
+    double bound = max_d2;
+    if (plane) {
+        const dim3 g(total_rows), b(P2L_THREADS);
+        if (d_perm)
+            hipLaunchKernelGGL(pairb_robust_keys_kernel<true>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_rs, max_d2, d_keys);
+        else
+            hipLaunchKernelGGL(pairb_robust_keys_kernel<false>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_rs, max_d2, d_keys);
+        keys = d_keys;
+        bound = __builtin_huge_val();
+    }
+    hipLaunchKernelGGL(pairb_robust_select_kernel, dim3(npairs), dim3(TRIM_HIST_THREADS), 0, st, keys, d_desc, d_state, d_rs, bound, d_ts);
+}
+
+void launch_pairb_robust_sums(hipStream_t st, bool plane, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                              const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair, int total_rows,
+                              int npairs, const PairState* d_state, const RobustScale* d_rs, const TrimState* d_ts, double max_d2,
+                              double* d_rows, double* d_out, double* d_info) {
+    const dim3 g(total_rows), b(P2L_THREADS);
+#define KSS_PAIRB_ROBUST_ROWS(PLANE, PERM) \
+    hipLaunchKernelGGL((pairb_robust_rows_kernel<PLANE, PERM>), g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_rs, d_ts, max_d2, d_rows)
+    if (plane) {
+        if (d_perm) KSS_PAIRB_ROBUST_ROWS(true, true); else KSS_PAIRB_ROBUST_ROWS(true, false);
+        hipLaunchKernelGGL(pairb_robust_final_kernel<true>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_rs, d_ts, d_out, d_info);
+    } else {
+        if (d_perm) KSS_PAIRB_ROBUST_ROWS(false, true); else KSS_PAIRB_ROBUST_ROWS(false, false);
+        hipLaunchKernelGGL(pairb_robust_final_kernel<false>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_rs, d_ts, d_out, d_info);
+    }
+#undef KSS_PAIRB_ROBUST_ROWS
 }
 
 }  // namespace kss

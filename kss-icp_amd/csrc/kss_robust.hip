@@ -13,15 +13,9 @@
 // PAIR_KEY modes (kss_pair_device.hpp).  m and cnt travel as columns of the rows: sums of ones, exact in f64.
 #pragma clang fp contract(off)
 
-#include "kss_pair_device.hpp"
+#include "kss_robust_device.hpp"
 
 namespace kss {
-
-__device__ __forceinline__ double robust_pass_c2(const RobustScale& rs, bool plane, const TrimState* __restrict__ sel) {
-    if (!rs.autoscale) return rs.c2;
-    const double med = sel->cut;   // the median key widened (-1: no candidate)
-    return med >= 0.0 ? robust_scale2_of(plane, rs.K, med, rs.min2) : 0.0;
-}
 
 // ---- keys ---------------------------------------------------------------------------------------------------------------
 template <bool PLANE, int SRC>
