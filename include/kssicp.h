@@ -404,6 +404,67 @@ int kss_trim_threshold_batch(kss_ctx *ctx, const float *d2_all, const int64_t *o
 int kss_trim_threshold_batch_dev(kss_ctx *ctx, const float *d_d2_all, const int64_t *off, int nseg, double max_d2,
                                  const double *overlaps, double *info_all);
 
+/* ---- generalized ICP (plane-to-plane; Segal, Haehnel, Thrun: Generalized-ICP, RSS 2009) for one pair ----
+ * Both clouds carry a local surface model: PCL-style GICP replaces the eigenvalues of each point's k-NN covariance by
+ * (epsilon, 1, 1), which is I - (1 - epsilon) n n^T with n the smallest eigenvector -- the normal kss_normals computes.  So the
+ * inputs are the NORMALS of both clouds (nt*3 and ns*3 floats); their signs do not matter, only n n^T enters.
+ * One pass.  F is the float 4x4 accumulated so far (identity in pass 0; it maps the original source onto its current positions),
+ * R_F its upper left 3x3.  For source i: its current float position p, the exact NN target j = idx[i] with float d2[i], the
+ * float target point q, the float target normal nq = tgt_normals[j] and the float source normal ns = src_normals[i] (by ORIGINAL
+ * index).  Everything below is f64 on the widened floats with +, -, *, / only, nothing fused, in exactly this order:
+ *   candidate   j in [0, nt), !(d2 > max_d2) as in kss_icp_p2l, and all six normal components finite;
+ *   m           m[k] = (R_F[k][0]*ns[0] + R_F[k][1]*ns[1]) + R_F[k][2]*ns[2], k = 0, 1, 2;
+ *   C           e = 1 - epsilon;  g(a,b) = nq[a]*nq[b] + m[a]*m[b];  c_aa = 2 - e*g(a,a);  c_ab = -(e*g(a,b)) for a < b
+ *               (C = 2I - (1 - epsilon)(nq nq^T + m m^T), six entries c00 c01 c02 c11 c12 c22);
+ *   M           M = adj(C) / det(C) by cofactors:
+ *               a00 = c11*c22 - c12*c12,  a01 = c02*c12 - c01*c22,  a02 = c01*c12 - c02*c11,
+ *               a11 = c00*c22 - c02*c02,  a12 = c01*c02 - c00*c12,  a22 = c00*c11 - c01*c01,
+ *               det = (c00*a00 + c01*a01) + c02*a02,  M_ab = a_ab / det (six divisions);
+ *   dropped     a candidate whose det is not finite or not > 0.  Unit normals always give det >= 8*epsilon*(...) > 0; normals
+ *               that are not of unit length are the caller's responsibility;
+ *   d, u        d = q - p;  u = M d, u[a] = (M_a0*d[0] + M_a1*d[1]) + M_a2*d[2];
+ *   A           A = [ -[p]x | I3 ], 3 x 6, x = (alpha, beta, gamma, tx, ty, tz) (with M = nq nq^T this is kss_icp_p2l's v and r).
+ *               A^T M A by blocks, [p]x = (0 -pz py; pz 0 -px; -py px 0):
+ *               B = [p]x M (upper right):   B_0b = py*M_2b - pz*M_1b,  B_1b = pz*M_0b - px*M_2b,  B_2b = px*M_1b - py*M_0b;
+ *               B [p]x^T (upper left):      UL_a0 = B_a2*py - B_a1*pz,  UL_a1 = B_a0*pz - B_a2*px,  UL_a2 = B_a1*px - B_a0*py;
+ *               lower right: M.   A^T M d = ( py*u[2] - pz*u[1],  pz*u[0] - px*u[2],  px*u[1] - py*u[0],  u[0], u[1], u[2] );
+ *   record      KSS_P2L_NSUMS doubles: [0] kept count, [1..21] upper triangle of sum A^T M A row-major (UL00 UL01 UL02 B00 B01
+ *               B02 | UL11 UL12 B10 B11 B12 | UL22 B20 B21 B22 | M00 M01 M02 | M11 M12 | M22), [22..27] sum A^T M d, [28] sum d2
+ *               kept, [29] sum d2 over all sources with a valid j, [30] sum d^T M d = (d[0]*u[0] + d[1]*u[1]) + d[2]*u[2], [31] 0;
+ *   order       the fixed summation order of kss_icp_p2l, a function of the source count alone;
+ *   step        kss_rigid_from_p2l_sums on the record as it is: ONE Gauss-Newton step per pass (Cholesky, R = Rz Ry Rx).
+ * The loop around it is kss_icp_p2l's: fewer than min_correspondences kept -> KSS_STATE_NO_CORRESPONDENCES, a failed Cholesky ->
+ * KSS_STATE_DEGENERATE, PCL's criteria on MSE = [28] / [0], fitness over ALL sources, p->allreduce must be NULL.
+ * 0 < epsilon <= 1, anything else is KSS_ERR_ARG; epsilon = 1 gives M = I/2, the point-to-point metric.  Accuracy: det(C) falls
+ * with epsilon and the f64 cofactor inverse loses what C's condition (about 2 / epsilon) costs -- its error against an exact
+ * inverse is about 1e-14 relative at epsilon = 1e-3 and reaches 5e-11 at epsilon = 1e-6; the result stays deterministic, but
+ * epsilon well below 1e-3 buys nothing.  The batched form, robust or trimmed weights on top, the C++ mirror classes and the CLI
+ * do not have this metric. */
+typedef struct {
+    double epsilon;     /* 1e-3 */
+    int    normals_k;   /* 20: read only when a set of normals is NULL; 3..64 */
+} kss_gicp_params;
+int kss_gicp_default_params(kss_gicp_params *gp);
+/* host only, no context: M[6] = upper triangle (M00 M01 M02 M11 M12 M22) of (2I - (1-eps)(nq nq^T + m m^T))^-1 by the definition
+ * above, nq widened to f64; *ok = 0 (M all zero) when dropped or a component is not finite, else 1. */
+int kss_gicp_metric(const float nq[3], const double m[3], double epsilon, double M[6], int *ok);
+/* The record for given correspondences (d2 recomputed as in kss_cov; the _dev form takes idx entries outside [0, nt) as no
+ * correspondence, the host form refuses them).  Rn: HOST pointer to the row-major 3x3 float applied to the source normals in
+ * place of R_F, NULL = identity.  src_normals / tgt_normals: n*3 / nt*3 floats, each may be NULL: then computed with kss_normals'
+ * definition at k = min(normals_k, points) from the cloud as it is passed in, and rounded to float. */
+int kss_gicp_sums(kss_ctx *ctx, const float *src, const float *src_normals, const float *tgt, const float *tgt_normals,
+                  const int32_t *idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_gicp_params *gp,
+                  double sums[KSS_P2L_NSUMS]);
+int kss_gicp_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_src_normals, const float *d_tgt, const float *d_tgt_normals,
+                      const int32_t *d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_gicp_params *gp,
+                      double sums[KSS_P2L_NSUMS]);
+/* normals as in kss_gicp_sums (NULL: computed from the cloud as passed in, the source before any motion).  trace_sums receives
+ * trace_cap * KSS_P2L_NSUMS doubles.  The result is that of kss_icp_p2l. */
+int kss_icp_gicp(kss_ctx *ctx, const float *src, int64_t ns, const float *src_normals, const float *tgt, int64_t nt,
+                 const float *tgt_normals, const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res);
+int kss_icp_gicp_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const float *d_tgt, int64_t nt,
+                     const float *d_tgt_normals, const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res);
+
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);
 int kss_transform_apply_dev(kss_ctx *ctx, const float T[16], const double *d_in, int64_t n, double *d_out);

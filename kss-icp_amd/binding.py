@@ -39,6 +39,7 @@ SYMBOLS = [
     "kss_trim_threshold_batch", "kss_trim_threshold_batch_dev",
     "kss_robust_default_params", "kss_robust_weight", "kss_robust_scale2", "kss_robust_sums", "kss_robust_sums_dev",
     "kss_icp_robust", "kss_icp_robust_dev", "kss_icp_robust_batch", "kss_icp_robust_batch_dev",
+    "kss_gicp_default_params", "kss_gicp_metric", "kss_gicp_sums", "kss_gicp_sums_dev", "kss_icp_gicp", "kss_icp_gicp_dev",
 ]
 
 
@@ -78,6 +79,10 @@ class TrimParams(C.Structure):
 class RobustParams(C.Structure):
     _fields_ = [("loss", C.c_int), ("metric", C.c_int), ("scale", C.c_double), ("tune", C.c_double), ("min_scale", C.c_double),
                 ("trace_robust", C.POINTER(C.c_double))]
+
+
+class GicpParams(C.Structure):
+    _fields_ = [("epsilon", C.c_double), ("normals_k", C.c_int)]
 
 
 class IcpResult(C.Structure):
@@ -161,6 +166,12 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, i64, i64, dbl, C.POINTER(RobustParams), vp, vp]
     for n in ("kss_icp_robust", "kss_icp_robust_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(RobustParams), C.POINTER(IcpResult), vp]
+    L.kss_gicp_default_params.argtypes = [C.POINTER(GicpParams)]
+    L.kss_gicp_metric.argtypes = [vp, vp, dbl, vp, C.POINTER(C.c_int)]
+    for n in ("kss_gicp_sums", "kss_gicp_sums_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, dbl, vp, C.POINTER(GicpParams), vp]
+    for n in ("kss_icp_gicp", "kss_icp_gicp_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(GicpParams), C.POINTER(IcpResult)]
     for n in ("kss_icp_p2l_batch", "kss_icp_p2l_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), vp]
     for n in ("kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev"):
@@ -312,6 +323,37 @@ def robust_scale2(metric, tune, med_key, min_scale=0.0):
     if rc != 0:
         raise KssError(rc, "kss_robust_scale2")
     return c2.value
+
+
+def gicp_params(**kw):
+    """kss_gicp_default_params (epsilon 1e-3, normals_k 20), then the fields given by keyword."""
+    L = load_library()
+    gp = GicpParams()
+    rc = L.kss_gicp_default_params(C.byref(gp))
+    if rc != 0:
+        raise KssError(rc, "kss_gicp_default_params")
+    for k, v in kw.items():
+        if k == "epsilon":
+            gp.epsilon = float(v)
+        elif k == "normals_k":
+            gp.normals_k = int(v)
+        else:
+            raise AttributeError(k)
+    return gp
+
+
+def gicp_metric(nq, m, epsilon=1e-3):
+    """kss_gicp_metric: (M, ok) -- the six upper-triangle entries of the metric of one correspondence from the float32 target
+    normal nq and the turned source normal m (float64), ok False when the correspondence is dropped (host only)."""
+    L = load_library()
+    a = np.ascontiguousarray(nq, dtype=np.float32).reshape(3)
+    b = np.ascontiguousarray(m, dtype=np.float64).reshape(3)
+    M = np.zeros(6, np.float64)
+    ok = C.c_int(0)
+    rc = L.kss_gicp_metric(_p(a), _p(b), float(epsilon), _p(M), C.byref(ok))
+    if rc != 0:
+        raise KssError(rc, "kss_gicp_metric")
+    return M, bool(ok.value)
 
 
 def rigid_from_p2l_sums(sums):
@@ -654,6 +696,63 @@ class Context:
                                             C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(rp),
                                             C.byref(res), _p(info)), "kss_icp_robust_dev")
         return res, info
+
+    # ---- generalized ICP
+    @staticmethod
+    def _gicp_normals(normals, n, what):
+        nr = _f32(normals) if normals is not None else None
+        if nr is not None and len(nr) != n:
+            raise ValueError("%s normals must have one row per point" % what)
+        return nr
+
+    @staticmethod
+    def _gicp_rot(Rn):
+        return np.ascontiguousarray(Rn, dtype=np.float32).reshape(9) if Rn is not None else None
+
+    def gicp_sums(self, src, src_normals, tgt, tgt_normals, idx, max_d2=1.0, Rn=None, gp=None):
+        """kss_gicp_sums: the P2L_NSUMS record of one generalized-ICP pass over given correspondences.  Rn: the 3 x 3 applied to the
+        source normals (None: identity); either set of normals may be None (computed); gp: a GicpParams (gicp_params())."""
+        gp = gp if gp is not None else gicp_params()
+        s, t = _f32(src), _f32(tgt)
+        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
+        i = np.ascontiguousarray(idx, dtype=np.int32)
+        r = self._gicp_rot(Rn)
+        sums = np.zeros(P2L_NSUMS, np.float64)
+        self._chk(self.L.kss_gicp_sums(self.h, _p(s), _p(sn), _p(t), _p(tn), _p(i), len(s), len(t), float(max_d2), _p(r), C.byref(gp),
+                                       _p(sums)), "kss_gicp_sums")
+        return sums
+
+    def gicp_sums_dev(self, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2=1.0, Rn=None, gp=None):
+        """kss_gicp_sums_dev on device pointers (either normals pointer may be 0 / None; Rn stays a host array)."""
+        gp = gp if gp is not None else gicp_params()
+        r = self._gicp_rot(Rn)
+        sums = np.zeros(P2L_NSUMS, np.float64)
+        self._chk(self.L.kss_gicp_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
+                                           C.c_void_p(int(d_tgt)), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
+                                           C.c_void_p(int(d_idx)), int(n), int(nt), float(max_d2), _p(r), C.byref(gp), _p(sums)),
+                  "kss_gicp_sums_dev")
+        return sums
+
+    def icp_gicp(self, src, tgt, src_normals=None, tgt_normals=None, gp=None, params=None, trace_cap=0, fitness_corr=False):
+        """Generalized ICP (kss_icp_gicp): every correspondence is weighed by the inverse of the sum of both points' surface
+        covariances, given as the normals of both clouds (ns x 3 and nt x 3; None: computed with kss_normals' definition at
+        gp.normals_k and rounded to float).  gp: a GicpParams (gicp_params()).  The result dictionary of icp_p2l()."""
+        gp = gp if gp is not None else gicp_params()
+        s, t = _f32(src), _f32(tgt)
+        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
+        p = params if params is not None else self.icp_params()
+        return self._icp_call(lambda res: self.L.kss_icp_gicp(self.h, _p(s), len(s), _p(sn), _p(t), len(t), _p(tn), C.byref(p), C.byref(gp),
+                                                              C.byref(res)),
+                              "kss_icp_gicp", p, len(s), P2L_NSUMS, trace_cap, fitness_corr)
+
+    def icp_gicp_dev(self, d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals, params, gp=None):
+        """kss_icp_gicp_dev on device pointers (either normals pointer may be 0 / None); returns the IcpResult."""
+        gp = gp if gp is not None else gicp_params()
+        res = IcpResult()
+        self._chk(self.L.kss_icp_gicp_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
+                                          C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
+                                          C.byref(params), C.byref(gp), C.byref(res)), "kss_icp_gicp_dev")
+        return res
 
     # ---- point-to-plane and trimmed ICP, many pairs per call
     def _batch_call(self, call, where, p, so, ncol, trace_cap, fitness_corr, tp=None):

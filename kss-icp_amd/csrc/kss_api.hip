@@ -7,6 +7,7 @@
 #include <limits>
 
 #include "kss_ctx.hpp"
+#include "kss_gicp.hpp"
 #include "kss_robust.hpp"
 
 extern "C" {
@@ -70,7 +71,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -500,20 +501,24 @@ static int pair_check(kss_ctx* c, const char* who, bool trimmed, const void* src
     return KSS_OK;
 }
 
-// the target's normals where the caller gave none: kss_normals' definition (k = 20 incl. the point itself, view-point flip,
-// renormalised in double) on the target widened to f64 -- whose float narrowing is the target itself -- then rounded to float
-static int target_normals_dev(kss_ctx* c, const float* d_tgt, int64_t nt, const float** d_nrm) {
-    const int k = nt < 20 ? (int)nt : 20;
-    KCHK(ensure(c, c->p2l_idx, (size_t)nt * k * sizeof(int32_t)));
-    KCHK(ensure(c, c->p2l_d2, (size_t)nt * k * sizeof(float)));
-    KCHK(ensure(c, c->p2l_n64, (size_t)nt * 3 * sizeof(double)));
-    KCHK(ensure(c, c->p2l_nrm, (size_t)nt * 3 * sizeof(float)));
-    KCHK(knn_generic_dev(c, d_tgt, nt, d_tgt, nt, KSS_F32, k, (int32_t*)c->p2l_idx.p, (float*)c->p2l_d2.p));
-    launch_normals(c->stream, (const float4*)c->src0.p, (int)nt, (const int32_t*)c->p2l_idx.p, k, (double*)c->p2l_n64.p);
-    launch_f64_to_f32(c->stream, (const double*)c->p2l_n64.p, nt * 3, (float*)c->p2l_nrm.p);
+// A cloud's normals where the caller gave none: kss_normals' definition (k incl. the point itself, view-point flip, renormalised
+// in double) on the cloud widened to f64 -- whose float narrowing is the cloud itself -- then rounded to float, into `out`
+static int cloud_normals_dev(kss_ctx* c, const float* d_pts, int64_t n, int kk, DevBuf& out, const float** d_nrm) {
+    const int k = n < kk ? (int)n : kk;
+    KCHK(ensure(c, c->p2l_idx, (size_t)n * k * sizeof(int32_t)));
+    KCHK(ensure(c, c->p2l_d2, (size_t)n * k * sizeof(float)));
+    KCHK(ensure(c, c->p2l_n64, (size_t)n * 3 * sizeof(double)));
+    KCHK(ensure(c, out, (size_t)n * 3 * sizeof(float)));
+    KCHK(knn_generic_dev(c, d_pts, n, d_pts, n, KSS_F32, k, (int32_t*)c->p2l_idx.p, (float*)c->p2l_d2.p));
+    launch_normals(c->stream, (const float4*)c->src0.p, (int)n, (const int32_t*)c->p2l_idx.p, k, (double*)c->p2l_n64.p);
+    launch_f64_to_f32(c->stream, (const double*)c->p2l_n64.p, n * 3, (float*)out.p);
     HIPCHK(c, hipGetLastError());
-    *d_nrm = (const float*)c->p2l_nrm.p;
+    *d_nrm = (const float*)out.p;
     return KSS_OK;
+}
+// the target's, k = 20 (kss_icp_p2l, kss_icp_trimmed, kss_icp_robust)
+static int target_normals_dev(kss_ctx* c, const float* d_tgt, int64_t nt, const float** d_nrm) {
+    return cloud_normals_dev(c, d_tgt, nt, 20, c->p2l_nrm, d_nrm);
 }
 
 int kss_icp_p2l_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
@@ -731,6 +736,117 @@ int kss_icp_robust(kss_ctx* c, const float* src, int64_t ns, const float* tgt, i
     if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
     return kss_icp_robust_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
                               p, rp, res, last_info);
+}
+
+// ---- generalized ICP ---------------------------------------------------------------
+static inline bool gicp_epsilon_ok(double e) { return e > 0.0 && e <= 1.0; }   // (a NaN fails both)
+
+int kss_gicp_default_params(kss_gicp_params* gp) {
+    if (!gp) return KSS_ERR_ARG;
+    gp->epsilon = 1e-3;
+    gp->normals_k = 20;
+    return KSS_OK;
+}
+
+int kss_gicp_metric(const float nq[3], const double m[3], double epsilon, double M[6], int* ok) {
+    if (!nq || !m || !M || !ok || !gicp_epsilon_ok(epsilon)) return KSS_ERR_ARG;
+    const double n64[3] = {(double)nq[0], (double)nq[1], (double)nq[2]};
+    for (int k = 0; k < 6; ++k) M[k] = 0.0;
+    bool fin = true;
+    for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(n64[k]) && std::isfinite(m[k]);
+    *ok = fin && gicp_metric_of(n64, m, 1.0 - epsilon, M) ? 1 : 0;
+    return KSS_OK;
+}
+
+// the checks of gp that kss_gicp_sums and kss_icp_gicp share; need_k: a set of normals is to be computed
+static int gicp_check(kss_ctx* c, const char* who, const kss_gicp_params* gp, bool need_k) {
+    const std::string w = std::string(who) + ": ";
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
+    if (!gp) return bad("null argument");
+    if (!gicp_epsilon_ok(gp->epsilon)) return bad("epsilon must be in (0, 1]");
+    if (need_k && (gp->normals_k < 3 || gp->normals_k > 64)) return bad("normals_k must be in 3..64");
+    return KSS_OK;
+}
+
+// both clouds' normals where the caller gave none (the target's into p2l_nrm, the source's into gicp_snrm)
+static int gicp_normals_dev(kss_ctx* c, const float* d_src, int64_t ns, const float** d_snrm, const float* d_tgt, int64_t nt,
+                            const float** d_tnrm, int k) {
+    if (!*d_tnrm) KCHK(cloud_normals_dev(c, d_tgt, nt, k, c->p2l_nrm, d_tnrm));
+    if (!*d_snrm) KCHK(cloud_normals_dev(c, d_src, ns, k, c->gicp_snrm, d_snrm));
+    return KSS_OK;
+}
+
+int kss_gicp_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals, const float* d_tgt, const float* d_tgt_normals,
+                      const int32_t* d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_gicp_params* gp,
+                      double sums[KSS_P2L_NSUMS]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(gicp_check(c, "gicp_sums", gp, !d_src_normals || !d_tgt_normals));
+    if (!d_src || !d_tgt || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "gicp_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "gicp_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "gicp_sums: cloud too large");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, gp->normals_k));
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
+    {
+        ProfScope ps(c, KSS_K_CORR_REDUCE);
+        launch_gicp_sums(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, d_tgt, d_tgt_normals, n, nt, max_d2, Rn,
+                         gp->epsilon, (double*)c->p2l_rows.p, (double*)c->h_p2l_dev);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(sums, c->h_p2l, KSS_P2L_NSUMS * sizeof(double));
+    return KSS_OK;
+}
+
+int kss_gicp_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals, const int32_t* idx,
+                  int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_gicp_params* gp, double sums[KSS_P2L_NSUMS]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(gicp_check(c, "gicp_sums", gp, !src_normals || !tgt_normals));
+    if (!src || !tgt || !idx || !sums) return set_err(c, KSS_ERR_ARG, "gicp_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "gicp_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "gicp_sums: cloud too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= nt) return set_err(c, KSS_ERR_ARG, "gicp_sums: index out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)n * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
+    return kss_gicp_sums_dev(c, (const float*)c->stage_src.p, src_normals ? (const float*)c->gicp_snrm.p : nullptr, (const float*)c->stage_tgt.p,
+                             tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, (const int32_t*)c->stage_idx.p, n, nt, max_d2, Rn, gp, sums);
+}
+
+int kss_icp_gicp_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const float* d_tgt, int64_t nt,
+                     const float* d_tgt_normals, const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* res) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(gicp_check(c, "icp_gicp", gp, !d_src_normals || !d_tgt_normals));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_gicp: the source-row split (allreduce) is not available for generalized ICP");
+    KCHK(pair_check(c, "icp_gicp", false, d_src, d_tgt, ns, nt, d_tgt_normals, p, nullptr, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(gicp_normals_dev(c, d_src, ns, &d_src_normals, d_tgt, nt, &d_tgt_normals, gp->normals_k));
+    PairMode mode;
+    mode.plane = true;
+    mode.gicp = true;
+    mode.gicp_epsilon = gp->epsilon;
+    mode.d_src_nrm = d_src_normals;
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_tgt_normals, p, mode, res);
+}
+
+int kss_icp_gicp(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const float* tgt, int64_t nt, const float* tgt_normals,
+                 const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* res) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(gicp_check(c, "icp_gicp", gp, !src_normals || !tgt_normals));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_gicp: the source-row split (allreduce) is not available for generalized ICP");
+    KCHK(pair_check(c, "icp_gicp", false, src, tgt, ns, nt, tgt_normals, p, nullptr, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)ns * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_gicp_dev(c, (const float*)c->stage_src.p, ns, src_normals ? (const float*)c->gicp_snrm.p : nullptr,
+                            (const float*)c->stage_tgt.p, nt, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, p, gp, res);
 }
 
 // ---- the same for many pairs per call ------------------------------------------------

@@ -56,6 +56,8 @@ struct kss_ctx {
     DevBuf trim_rows, trim_state;
     // robust ICP (kss_robust.hip): the keys its median is selected over where they are not the NN pass's d2
     DevBuf rob_keys;
+    // generalized ICP (kss_gicp.hip): the source's float normals (staged or computed)
+    DevBuf gicp_snrm;
     // the same for many pairs per call (kss_pairb.hip): per-pair descriptors, row -> pair table, packed normals computed at setup
     DevBuf pb_desc, pb_rowpair, pb_nrm;
     // robust ICP for many pairs: one RobustScale per pair, uploaded once per call
@@ -245,8 +247,8 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // one exact NN pass of a single pair (+ the correspondence sums when sums_out is given)
 int nn_generic_dev(kss_ctx* c, const void* d_src, int64_t ns, const void* d_tgt, int64_t nt, int dtype,
                    int32_t* d_idx, float* d_d2, double sums_out[NSUMS]);
-// ICP of one pair by kss_icp_p2l (plane, untrimmed), kss_icp_trimmed or kss_icp_robust (either metric): float clouds on the
-// device, d_nrm the target's normals for the plane metric.  The untrimmed, unweighted point metric is icp_run_dev's.
+// ICP of one pair by kss_icp_p2l (plane, untrimmed), kss_icp_trimmed, kss_icp_robust (either metric) or kss_icp_gicp: float clouds
+// on the device, d_nrm the target's normals for the plane metric.  The untrimmed, unweighted point metric is icp_run_dev's.
 struct PairMode {
     bool plane = false;             // point-to-plane step (d_nrm given); otherwise point-to-point
     bool trimmed = false;           // keep the closest `overlap` share of each pass's candidates
@@ -255,6 +257,9 @@ struct PairMode {
     double* last_info = nullptr;    // trimmed / robust: the same of the last pass
     bool robust = false;            // M-estimator weights (kss_icp_robust; not together with trimmed), scale and loss in rs
     RobustScale rs;
+    bool gicp = false;              // generalized ICP (kss_icp_gicp; with plane, not with trimmed or robust): d_nrm and the SOURCE's
+    double gicp_epsilon = 0.0;      // normals d_src_nrm (device, float triples by original source index) weigh every correspondence
+    const float* d_src_nrm = nullptr;
 };
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,

@@ -1865,6 +1865,9 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // plane metric's key launch and the same radix select at overlap 0.5 for the median key, then the weighted rows + final
 // launches (the info slots hold {m, c2, sum of weights, cnt}); with a fixed scale only the latter two.  The host step reads cnt
 // for the min_correspondences test and solves the weighted record as it is: [0] is the weight total.
+// Generalized (kss_icp_gicp; M.gicp with M.plane): the gicp rows launch in place of the plane metric's, given the
+// rotation of the transform accumulated so far for the source normals; the final launch, the record's layout, the host step and
+// the criteria are the plane metric's.
 // What the host does for ONE pair after a pass, the same code for a single pair (pair_loop) and inside a batch (pairs_loop): the
 // min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
 // its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
@@ -1942,6 +1945,11 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
                 }
                 launch_robust_sums(c->stream, M.plane, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, M.rs, d_sel, d_rows,
                                    d_rec, d_rec + P2L_NSUMS);
+            } else if (M.gicp) {   // the source normals turn with the transform accumulated so far
+                const float* F = tr.fin;
+                const float Rn[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
+                launch_gicp_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn, M.gicp_epsilon,
+                                 d_rows, d_rec);
             } else if (M.plane)
                 launch_p2l_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, d_rows, d_rec, d_cut);
             else
@@ -1970,6 +1978,8 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
                  const kss_icp_params* p, const PairMode& M, kss_icp_result* res) {
     if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: the untrimmed point metric is kss_icp's");
     if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: trimmed and robust exclude each other");
+    if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm))
+        return set_err(c, KSS_ERR_ARG, "pair_run: generalized ICP is the plane record with both clouds' normals, neither trimmed nor robust");
     HIPCHK(c, hipSetDevice(c->device));
     IcpPlan pl;
     const auto t0 = std::chrono::steady_clock::now();

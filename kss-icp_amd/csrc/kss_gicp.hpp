@@ -1,0 +1,38 @@
+// kss_gicp.hpp -- generalized ICP (plane-to-plane): the metric of one correspondence, ONE body for the device
+// kernel (kss_gicp.hip through kss_pair_device.hpp) and the C-ABI's host helper (kss_gicp_metric).
+// f64 +, -, *, / in the order written down at kss_icp_gicp in include/kssicp.h; the including translation unit is compiled with
+// fp contraction off, so nothing here becomes an fma.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace kss {
+
+// M[6] = {M00, M01, M02, M11, M12, M22}, the upper triangle of (2I - e (nq nq^T + m m^T))^-1 with e = 1 - epsilon formed by the
+// caller.  False (M untouched): dropped, det is not finite or not > 0.
+__host__ __device__ inline bool gicp_metric_of(const double nq[3], const double m[3], double e, double M[6]) {
+#pragma clang fp contract(off)
+    const double c00 = 2.0 - e * (nq[0] * nq[0] + m[0] * m[0]);
+    const double c01 = -(e * (nq[0] * nq[1] + m[0] * m[1]));
+    const double c02 = -(e * (nq[0] * nq[2] + m[0] * m[2]));
+    const double c11 = 2.0 - e * (nq[1] * nq[1] + m[1] * m[1]);
+    const double c12 = -(e * (nq[1] * nq[2] + m[1] * m[2]));
+    const double c22 = 2.0 - e * (nq[2] * nq[2] + m[2] * m[2]);
+    const double a00 = c11 * c22 - c12 * c12;
+    const double a01 = c02 * c12 - c01 * c22;
+    const double a02 = c01 * c12 - c02 * c11;
+    const double a11 = c00 * c22 - c02 * c02;
+    const double a12 = c01 * c02 - c00 * c12;
+    const double a22 = c00 * c11 - c01 * c01;
+    const double det = (c00 * a00 + c01 * a01) + c02 * a02;
+    if (!(det > 0.0) || !(det < __builtin_huge_val())) return false;
+    M[0] = a00 / det; M[1] = a01 / det; M[2] = a02 / det;
+    M[3] = a11 / det; M[4] = a12 / det; M[5] = a22 / det;
+    return true;
+}
+
+// the rotation applied to the source normals, by value into the kernel (row-major, float as in the accumulated Matrix4f)
+struct GicpRot {
+    float r[9];
+};
+
+}  // namespace kss

@@ -341,6 +341,13 @@ void launch_p2l_sums(hipStream_t st, const float* d_src3, const float4* d_src4, 
                      const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
                      double* d_rows, double* d_out, const double* d_cut = nullptr);
 void launch_p2l_perm(hipStream_t st, const float4* d_src, int64_t n, int32_t* d_perm);
+void launch_p2l_final(hipStream_t st, const double* d_rows, int nrows, double* d_out);   // p2l_final_kernel over given rows
+
+// generalized ICP sums (kss_gicp.hip): launch_p2l_sums' sources, rows and record; d_sn3: the source normals as
+// packed float triples by ORIGINAL source index; Rn: the row-major 3x3 applied to them (null: identity); 0 < epsilon <= 1.
+void launch_gicp_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
+                      const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
+                      double max_d2, const float Rn[9], double epsilon, double* d_rows, double* d_out);
 
 // ---- trimmed ICP (kss_trim.hip) ----
 // What one digit of the radix select hands to the next, and the last one to the sums kernels of the same pass: the key

@@ -72,6 +72,11 @@ void launch_p2l_sums(hipStream_t st, const float* d_src3, const float4* d_src4, 
     hipLaunchKernelGGL(p2l_final_kernel, dim3(1), dim3(P2L_THREADS), 0, st, (const double*)d_rows, nb, d_out);
 }
 
+// the final launch alone, for a rows kernel of another translation unit (kss_gicp.hip)
+void launch_p2l_final(hipStream_t st, const double* d_rows, int nrows, double* d_out) {
+    hipLaunchKernelGGL(p2l_final_kernel, dim3(1), dim3(P2L_THREADS), 0, st, d_rows, nrows, d_out);
+}
+
 void launch_p2l_perm(hipStream_t st, const float4* d_src, int64_t n, int32_t* d_perm) {
     hipLaunchKernelGGL(p2l_perm_kernel, dim3(stream_blocks(n)), dim3(256), 0, st, d_src, n, d_perm);
 }

@@ -1,11 +1,13 @@
 // kss_pair_device.hpp -- the device code that the single-pair kernels (kss_p2l.hip, kss_trim.hip, kss_robust.hip) and the batched
 // ones (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
+//   gicp_source                      the same for generalized ICP (single pair only: kss_gicp.hip),
 //   p2l_rows_column_sum              the fixed-order column sums of the plane metric's rows,
 //   trim_key / trim_resolve_counts   the candidate test and the resolution of one radix digit from a lane's eight bin counts.
 // A pair's bits are the same alone and inside a batch because both forms run these bodies in the same order.
 #pragma once
 #include "kss_device.hpp"
+#include "kss_gicp.hpp"
 #include "kss_robust.hpp"
 
 namespace kss {
@@ -98,6 +100,72 @@ __device__ __forceinline__ void p2l_source(double (&acc)[P2L_NSUMS], const float
             acc[28] += d2;
             acc[30] += rd * rd;
         }
+    }
+}
+
+// ---- generalized ICP ------------------------------------------------------------------------------------
+// Source i as in p2l_source, with the source's own normal sn[3 * i ..] (by ORIGINAL index) turned by Rn: the definition at
+// kss_icp_gicp in include/kssicp.h.  The 6 x 6 block A^T M A of A = [ -[p]x | I ] is formed by blocks -- lower right M, upper
+// right B = [p]x M, upper left B [p]x^T -- and not by a generic triple product: 54 f64 multiplications instead of 162.
+template <int SRC>
+__device__ __forceinline__ void gicp_source(double (&acc)[P2L_NSUMS], const float* __restrict__ src3, const float4* __restrict__ src4,
+                                            const int32_t* __restrict__ perm, const int32_t* __restrict__ idx,
+                                            const float* __restrict__ d2_in, const float* __restrict__ sn, const float* __restrict__ tgt,
+                                            const float* __restrict__ nrm, int64_t i, int64_t nt, double max_d2, const GicpRot& Rn, double e) {
+    const int64_t j = idx[i];
+    if (j < 0 || j >= nt) return;
+    float sx, sy, sz;
+    if constexpr (SRC == SRC_F3) {
+        sx = src3[3 * i]; sy = src3[3 * i + 1]; sz = src3[3 * i + 2];
+    } else {
+        const float4 p = src4[SRC == SRC_F4_PERM ? (int64_t)perm[i] : i];
+        sx = p.x; sy = p.y; sz = p.z;
+    }
+    const float qx = tgt[3 * j], qy = tgt[3 * j + 1], qz = tgt[3 * j + 2];
+    const float nx = nrm[3 * j], ny = nrm[3 * j + 1], nz = nrm[3 * j + 2];
+    const float ux = sn[3 * i], uy = sn[3 * i + 1], uz = sn[3 * i + 2];
+    const double d2 = (double)(d2_in ? d2_in[i] : dist2<false>(sx, sy, sz, qx, qy, qz));
+    acc[29] += d2;
+    if (!(d2 > max_d2) && isfinite(nx) && isfinite(ny) && isfinite(nz) && isfinite(ux) && isfinite(uy) && isfinite(uz)) {
+        const double nq[3] = {(double)nx, (double)ny, (double)nz};
+        const double us[3] = {(double)ux, (double)uy, (double)uz};
+        double m[3], M[6];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] = ((double)Rn.r[3 * k] * us[0] + (double)Rn.r[3 * k + 1] * us[1]) + (double)Rn.r[3 * k + 2] * us[2];
+        if (!gicp_metric_of(nq, m, e, M)) return;
+        const double px = (double)sx, py = (double)sy, pz = (double)sz;
+        const double d0 = (double)qx - px, d1 = (double)qy - py, dz = (double)qz - pz;
+        // M as rows (symmetric)
+        const double Mr[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
+        double u[3], B[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) u[a] = (Mr[a][0] * d0 + Mr[a][1] * d1) + Mr[a][2] * dz;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            B[0][b] = py * Mr[2][b] - pz * Mr[1][b];
+            B[1][b] = pz * Mr[0][b] - px * Mr[2][b];
+            B[2][b] = px * Mr[1][b] - py * Mr[0][b];
+        }
+        acc[0] += 1.0;
+        // row 0: UL00 UL01 UL02 B00 B01 B02; row 1: UL11 UL12 B10 B11 B12; row 2: UL22 B20 B21 B22; then M
+        acc[1] += B[0][2] * py - B[0][1] * pz;
+        acc[2] += B[0][0] * pz - B[0][2] * px;
+        acc[3] += B[0][1] * px - B[0][0] * py;
+        acc[4] += B[0][0]; acc[5] += B[0][1]; acc[6] += B[0][2];
+        acc[7] += B[1][0] * pz - B[1][2] * px;
+        acc[8] += B[1][1] * px - B[1][0] * py;
+        acc[9] += B[1][0]; acc[10] += B[1][1]; acc[11] += B[1][2];
+        acc[12] += B[2][1] * px - B[2][0] * py;
+        acc[13] += B[2][0]; acc[14] += B[2][1]; acc[15] += B[2][2];
+        acc[16] += M[0]; acc[17] += M[1]; acc[18] += M[2];
+        acc[19] += M[3]; acc[20] += M[4];
+        acc[21] += M[5];
+        acc[22] += py * u[2] - pz * u[1];
+        acc[23] += pz * u[0] - px * u[2];
+        acc[24] += px * u[1] - py * u[0];
+        acc[25] += u[0]; acc[26] += u[1]; acc[27] += u[2];
+        acc[28] += d2;
+        acc[30] += (d0 * u[0] + d1 * u[1]) + dz * u[2];
     }
 }
 
