@@ -438,8 +438,8 @@ int kss_trim_threshold_batch_dev(kss_ctx *ctx, const float *d_d2_all, const int6
  * 0 < epsilon <= 1, anything else is KSS_ERR_ARG; epsilon = 1 gives M = I/2, the point-to-point metric.  Accuracy: det(C) falls
  * with epsilon and the f64 cofactor inverse loses what C's condition (about 2 / epsilon) costs -- its error against an exact
  * inverse is about 1e-14 relative at epsilon = 1e-3 and reaches 5e-11 at epsilon = 1e-6; the result stays deterministic, but
- * epsilon well below 1e-3 buys nothing.  The batched form, robust or trimmed weights on top, the C++ mirror classes and the CLI
- * do not have this metric. */
+ * epsilon well below 1e-3 buys nothing.  Many pairs per call: kss_icp_gicp_batch below.  Robust or trimmed weights on top, the
+ * C++ mirror classes and the CLI do not have this metric. */
 typedef struct {
     double epsilon;     /* 1e-3 */
     int    normals_k;   /* 20: read only when a set of normals is NULL; 3..64 */
@@ -464,6 +464,27 @@ int kss_icp_gicp(kss_ctx *ctx, const float *src, int64_t ns, const float *src_no
                  const float *tgt_normals, const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res);
 int kss_icp_gicp_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const float *d_tgt, int64_t nt,
                      const float *d_tgt_normals, const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res);
+
+/* ---- generalized ICP for MANY pairs per call ----
+ * Arguments as kss_icp_p2l_batch: packed float[n][3] clouds and npairs + 1 HOST offsets in points (the _dev form takes device clouds
+ * and normals; the offsets stay host arrays).  src_normals_all is laid out like src_all, tgt_normals_all like tgt_all; either may
+ * be NULL: then each cloud's normals are computed as kss_icp_gicp computes them, per pair, at gp->normals_k from the cloud as
+ * passed in.  epsilons: one double per pair, or NULL for gp->epsilon everywhere.  Nothing is redefined: the definition at
+ * kss_icp_gicp holds for every pair -- the rotation R_F applied to the source normals is the PAIR's own, pass by pass -- and every
+ * pair's record -- T, iterations, state, converged, last_mse, pair 0's trace_* -- is the single-pair call's BIT FOR BIT (fitness: to
+ * the rounding of the NN engine's own summation order), in any batch order and any split over calls, under every NN engine and
+ * tuning knob; results[i].pair_id = i.  Offsets whose first entry is not 0 address a sub-range of the packed arrays.  The pairs
+ * run in lockstep, one small table copy and two launches per pass behind the NN pass whatever the pair count; a pair that ends --
+ * converged, KSS_STATE_NO_CORRESPONDENCES, KSS_STATE_DEGENERATE -- leaves the others untouched.  trace_* and fitness_idx /
+ * fitness_d2 describe pair 0.  KSS_ERR_ARG: NULL ctx (refused before anything touches the device), offsets, gp or results;
+ * npairs <= 0; an empty pair; a set allreduce; gp->epsilon or an epsilons entry outside (0, 1] or NaN; normals_k outside 3..64
+ * where a set of normals has to be computed; everything kss_icp_p2l_batch refuses. */
+int kss_icp_gicp_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *src_normals_all,
+                       const float *tgt_all, const int64_t *tgt_off, const float *tgt_normals_all, int npairs,
+                       const kss_icp_params *p, const kss_gicp_params *gp, const double *epsilons, kss_icp_result *results);
+int kss_icp_gicp_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_src_normals_all,
+                           const float *d_tgt_all, const int64_t *tgt_off, const float *d_tgt_normals_all, int npairs,
+                           const kss_icp_params *p, const kss_gicp_params *gp, const double *epsilons, kss_icp_result *results);
 
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);

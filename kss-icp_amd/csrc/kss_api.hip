@@ -71,12 +71,13 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
     if (c->h_seq) hipHostFree(c->h_seq);
     if (c->h_p2l) hipHostFree(c->h_p2l);
+    if (c->h_gicp) hipHostFree(c->h_gicp);
     if (c->h_box) hipHostFree(c->h_box);
     if (c->h_xf) hipHostFree(c->h_xf);
     if (c->gate_bar) hipFree(c->gate_bar);
@@ -850,17 +851,18 @@ int kss_icp_gicp(kss_ctx* c, const float* src, int64_t ns, const float* src_norm
 }
 
 // ---- the same for many pairs per call ------------------------------------------------
-// Every pair's normals where the caller gave none: target_normals_dev pair after pair into one packed buffer laid out like
-// the targets (setup cost of the call, not optimised: a k-NN and a normals launch per pair).
-static int batch_normals_dev(kss_ctx* c, const float* d_tgt, const int64_t* tgt_off, int npairs, const float** d_nrm) {
-    KCHK(ensure(c, c->pb_nrm, (size_t)tgt_off[npairs] * 3 * sizeof(float)));
+// Every cloud's normals where the caller gave none: cloud_normals_dev at k, cloud after cloud (off: npairs + 1 offsets in points
+// from 0), into the packed buffer `out` laid out like the clouds (setup cost of the call, not optimised: a k-NN and a normals
+// launch per cloud).  The targets' go to pb_nrm at k = 20 (the plane metric) or normals_k (generalized), the sources' to pb_snrm.
+static int batch_normals_dev(kss_ctx* c, const float* d_pts, const int64_t* off, int npairs, int k, DevBuf& out, const float** d_nrm) {
+    KCHK(ensure(c, out, (size_t)off[npairs] * 3 * sizeof(float)));
     for (int i = 0; i < npairs; ++i) {
-        const int64_t nt = tgt_off[i + 1] - tgt_off[i];
+        const int64_t n = off[i + 1] - off[i];
         const float* one = nullptr;
-        KCHK(target_normals_dev(c, d_tgt + 3 * tgt_off[i], nt, &one));
-        HIPCHK(c, hipMemcpyAsync((float*)c->pb_nrm.p + 3 * tgt_off[i], one, (size_t)nt * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        KCHK(cloud_normals_dev(c, d_pts + 3 * off[i], n, k, c->p2l_nrm, &one));
+        HIPCHK(c, hipMemcpyAsync((float*)out.p + 3 * off[i], one, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     }
-    *d_nrm = (const float*)c->pb_nrm.p;
+    *d_nrm = (const float*)out.p;
     return KSS_OK;
 }
 
@@ -884,7 +886,7 @@ static int pairs_batch_dev(kss_ctx* c, const char* who, const float* d_src, cons
     std::vector<double> ov;
     if (tp) ov.assign((size_t)npairs, tp->overlap);
     if (tp && overlaps) ov.assign(overlaps, overlaps + npairs);
-    if (mode.plane && !d_nrm) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, &d_nrm));
+    if (mode.plane && !d_nrm) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, 20, c->pb_nrm, &d_nrm));
     return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_nrm, npairs, p, mode, tp ? ov.data() : nullptr, results, info_all);
 }
 
@@ -965,7 +967,7 @@ int kss_icp_robust_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_
     mode.trace_info = rp->trace_robust;
     std::vector<RobustScale> rs((size_t)npairs);
     for (int i = 0; i < npairs; ++i) rs[i] = robust_scale_of(rp, scales ? scales[i] : rp->scale);
-    if (mode.plane && !d_nrm) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, &d_nrm));
+    if (mode.plane && !d_nrm) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, 20, c->pb_nrm, &d_nrm));
     return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_nrm, npairs, p, mode, nullptr, results, info_all, rs.data());
 }
 
@@ -984,6 +986,61 @@ int kss_icp_robust_batch(kss_ctx* c, const float* src, const int64_t* src_off, c
     for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
     return kss_icp_robust_batch_dev(c, (const float*)c->stage_src.p, so.data(), (const float*)c->stage_tgt.p, to.data(),
                                     nrm ? (const float*)c->pb_nrm.p : nullptr, npairs, p, rp, scales, results, info_all);
+}
+
+// ---- generalized ICP for many pairs per call -----------------------------------------
+// what the two entry points share: gp, allreduce, the per-pair epsilons (null: gp->epsilon everywhere) and pair_check
+static int gicp_batch_check(kss_ctx* c, const void* src, const float* snrm, const void* tgt, const float* tnrm, const int64_t* src_off,
+                            const int64_t* tgt_off, int npairs, const kss_icp_params* p, const kss_gicp_params* gp, const double* epsilons,
+                            const kss_icp_result* results) {
+    KCHK(gicp_check(c, "icp_gicp_batch", gp, !snrm || !tnrm));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_gicp_batch: the source-row split (allreduce) is not available for generalized ICP");
+    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_gicp_batch: bad batch");
+    if (epsilons)
+        for (int i = 0; i < npairs; ++i)
+            if (!gicp_epsilon_ok(epsilons[i])) return set_err(c, KSS_ERR_ARG, "icp_gicp_batch: every epsilon must be in (0, 1]");
+    return pair_check(c, "icp_gicp_batch", false, src, tgt, 0, 0, tnrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr);
+}
+
+int kss_icp_gicp_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
+                           const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
+                           const kss_gicp_params* gp, const double* epsilons, kss_icp_result* results) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(gicp_batch_check(c, d_src, d_src_normals, d_tgt, d_tgt_normals, src_off, tgt_off, npairs, p, gp, epsilons, results));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);   // rebased to the first pair, as in pairs_batch_dev
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
+    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
+    if (d_src_normals) d_src_normals += 3 * src_off[0];
+    if (d_tgt_normals) d_tgt_normals += 3 * tgt_off[0];
+    // each cloud's normals where the caller gave none, as kss_icp_gicp computes them: from the cloud as passed in, at normals_k
+    if (!d_tgt_normals) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, gp->normals_k, c->pb_nrm, &d_tgt_normals));
+    if (!d_src_normals) KCHK(batch_normals_dev(c, d_src, so.data(), npairs, gp->normals_k, c->pb_snrm, &d_src_normals));
+    PairMode mode;
+    mode.plane = true;
+    mode.gicp = true;
+    mode.d_src_nrm = d_src_normals;
+    std::vector<double> eps((size_t)npairs, gp->epsilon);
+    if (epsilons) eps.assign(epsilons, epsilons + npairs);
+    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_tgt_normals, npairs, p, mode, nullptr, results, nullptr, nullptr, eps.data());
+}
+
+int kss_icp_gicp_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
+                       const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_gicp_params* gp,
+                       const double* epsilons, kss_icp_result* results) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(gicp_batch_check(c, src, src_normals, tgt, tgt_normals, src_off, tgt_off, npairs, p, gp, epsilons, results));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
+    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->pb_snrm, src_normals + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->pb_nrm, tgt_normals + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
+    return kss_icp_gicp_batch_dev(c, (const float*)c->stage_src.p, so.data(), src_normals ? (const float*)c->pb_snrm.p : nullptr,
+                                  (const float*)c->stage_tgt.p, to.data(), tgt_normals ? (const float*)c->pb_nrm.p : nullptr, npairs, p, gp,
+                                  epsilons, results);
 }
 
 static int trim_batch_check(kss_ctx* c, const float* d2, const int64_t* off, int nseg, const double* overlaps, const double* info_all) {

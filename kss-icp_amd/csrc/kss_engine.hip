@@ -2031,7 +2031,8 @@ int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, 
 }
 
 // ---- the same metrics for MANY pairs per call: kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch
-// (2.13: behind the NN pass the key launch (plane) and the selection when any pair has the automatic scale, then two sums launches) ----
+// (2.13: behind the NN pass the key launch (plane) and the selection when any pair has the automatic scale, then two sums launches),
+// kss_icp_gicp_batch (2.15: one copy of the per-pair pass table -- the rotation of every pair's fin and its e -- then two sums launches) ----
 // pair_loop in lockstep over npairs >= 1 pairs.  Per pass: ONE NN pass over the pairs still active (idx / d2 by global source
 // index), ONE selection launch when trimmed, TWO sums launches (kss_pairb.hip), ONE stream synchronisation, then
 // pair_host_step for every active pair (the host pool from 64 pairs up, each pair on exactly one thread).  A pair that ends
@@ -2045,6 +2046,16 @@ struct DeferWait {   // the NN pass does not wait for its sums: the launches beh
 static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
                       const int32_t* d_perm, bool rob_select, kss_icp_result* results, double* info_all) {
     const int np = pl_in.npairs;
+    // generalized: every pair's GicpPass (pinned; e staged by pairs_run_dev) starts from the identity and follows the pair's fin
+    GicpPass* hgp = M.gicp ? (GicpPass*)c->h_gicp : nullptr;
+    auto gicp_rot_of = [](GicpPass& g, const float* F) {
+        const float R[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
+        std::memcpy(g.r, R, sizeof R);
+    };
+    // A/B switch: the kernel reads the pinned table across the bus instead of a device copy made per pass
+    const char* env_mapped = hgp ? getenv("KSS_GICP_TABLE_MAPPED") : nullptr;
+    const bool gicp_mapped = env_mapped && atoi(env_mapped) != 0 && c->h_gicp_dev;
+    const GicpPass* d_gpass = hgp ? (gicp_mapped ? (const GicpPass*)c->h_gicp_dev : (const GicpPass*)c->pb_gicp.p) : nullptr;
     const IcpPlan* plan = &pl_in;   // may change to the brute-force plan below
     IcpPlan brute_plan;
     std::vector<PairTrack> tr((size_t)np, PairTrack(P));
@@ -2056,6 +2067,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     for (int p = 0; p < np; ++p) {
         set_state(hs[p], I, 1, 0);
         mirror_state(bar, p, hs[p]);
+        if (hgp) gicp_rot_of(hgp[p], tr[p].fin);
     }
     const double max_d2 = P.max_corr_dist * P.max_corr_dist;
     int32_t* d_idx = (int32_t*)c->p2l_idx.p;
@@ -2095,6 +2107,12 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                                                d_state, d_rs, max_d2, (float*)c->rob_keys.p, d_ts);
                 launch_pairb_robust_sums(c->stream, M.plane, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np, d_state,
                                          d_rs, d_ts, max_d2, (double*)c->p2l_rows.p, d_rec, d_info);
+            } else if (M.gicp) {
+                // the table as the host steps left it: the last pass's synchronisation has ordered those writes behind its copy
+                if (!gicp_mapped)
+                    HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hgp, (size_t)np * sizeof(GicpPass), hipMemcpyHostToDevice, c->stream));
+                launch_pairb_gicp_sums(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
+                                       d_state, d_gpass, max_d2, (double*)c->p2l_rows.p, d_rec);
             } else {
                 if (M.trimmed) launch_pairb_select(c->stream, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
                 launch_pairb_sums(c->stream, M.plane, M.trimmed, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
@@ -2125,6 +2143,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                     active[p] = 0; ++fin_here;
                     set_state(hs[p], I, 0, 0);
                 }
+                if (hgp) gicp_rot_of(hgp[p], tr[p].fin);   // the source normals turn with the transform accumulated so far
                 mirror_state(bar, p, hs[p]);
             }
             finished.fetch_add(fin_here, std::memory_order_relaxed);
@@ -2175,10 +2194,12 @@ static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows
 // (the arguments are the entry points' to check: kss_api.hip)
 int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, const float* d_nrm,
                   int npairs, const kss_icp_params* p, const PairMode& M, const double* overlaps, kss_icp_result* results, double* info_all,
-                  const RobustScale* rscales) {
+                  const RobustScale* rscales, const double* gicp_eps) {
     if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: the untrimmed point metric is kss_icp_batch's");
     if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: trimmed and robust exclude each other");
     if (M.robust && !rscales) return set_err(c, KSS_ERR_ARG, "pairs_run: robust needs the per-pair scales");
+    if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm || !gicp_eps))
+        return set_err(c, KSS_ERR_ARG, "pairs_run: generalized ICP is the plane record with both clouds' normals and the per-pair epsilons, neither trimmed nor robust");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> ns(npairs), nt(npairs);
     for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }
@@ -2194,6 +2215,8 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
     for (int i = 0; i < npairs; ++i) {
         PairbDesc& d = desc[i];
         d.src_base = pl.g[i].src_base; d.ns = ns[i];
+        // (the source normals are packed like the caller's sources and read by src_base + i)
+        if (M.gicp && d.src_base != src_off[i]) return set_err(c, KSS_ERR_ARG, "pairs_run: the plan's source segments are not the caller's offsets");
         d.tgt_off = tgt_off[i]; d.nt = nt[i];
         d.overlap = M.trimmed ? overlaps[i] : 1.0;
         d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(ns[i]);
@@ -2211,6 +2234,14 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         KCHK(upload(c, c->pb_rscale, rscales, (size_t)npairs * sizeof(RobustScale)));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's table may be pageable and short-lived)
         if (rob_select && M.plane) KCHK(ensure(c, c->rob_keys, (size_t)pl.total_src * sizeof(float)));
+    }
+    if (M.gicp) {   // the per-pair pass table: e = 1 - epsilon as launch_gicp_sums forms it; pairs_loop fills the rotations
+        KCHK(ensure(c, c->pb_gicp, (size_t)npairs * sizeof(GicpPass)));
+        KCHK(ensure_pinned(c, c->h_gicp, c->h_gicp_cap, (size_t)npairs * sizeof(GicpPass)));
+        HIPCHK(c, hipHostGetDevicePointer(&c->h_gicp_dev, c->h_gicp, 0));
+        GicpPass* hgp = (GicpPass*)c->h_gicp;
+        std::memset(hgp, 0, (size_t)npairs * sizeof(GicpPass));
+        for (int i = 0; i < npairs; ++i) hgp[i].e = 1.0 - gicp_eps[i];
     }
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
     KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));

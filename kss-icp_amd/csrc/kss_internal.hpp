@@ -428,6 +428,21 @@ void launch_pairb_robust_sums(hipStream_t st, bool plane, const float4* d_src4, 
                               int npairs, const PairState* d_state, const RobustScale* d_rs, const TrimState* d_ts, double max_d2,
                               double* d_rows, double* d_out, double* d_info);
 
+// ---- generalized ICP for many pairs per call (kss_pairb.hip) ----
+// what one pass of one pair needs beyond its descriptor: the rotation block of the transform accumulated so far (row-major, the
+// float bits launch_gicp_sums takes as Rn) and e = 1 - epsilon.  One entry per pair, rewritten by the host before every pass.
+struct GicpPass {
+    float r[9];
+    double e;
+};
+static_assert(sizeof(GicpPass) == 48, "the host and the device table share this layout");
+// two launches: every active pair's record into d_out[pair * KSS_P2L_NSUMS].  d_sn3: the source normals packed like the
+// sources (by global original index); d_pass: one GicpPass per pair (device memory, as of this pass)
+void launch_pairb_gicp_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                            const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
+                            int total_rows, int npairs, const PairState* d_state, const GicpPass* d_pass, double max_d2, double* d_rows,
+                            double* d_out);
+
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,
                 const std::function<void*(size_t)>& scratch);

@@ -1,7 +1,7 @@
 // kss_pair_device.hpp -- the device code that the single-pair kernels (kss_p2l.hip, kss_trim.hip, kss_robust.hip) and the batched
 // ones (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
-//   gicp_source                      the same for generalized ICP (single pair only: kss_gicp.hip),
+//   gicp_source                      the same for generalized ICP (kss_gicp.hip; in a batch: pairb_gicp_rows_kernel),
 //   p2l_rows_column_sum              the fixed-order column sums of the plane metric's rows,
 //   trim_key / trim_resolve_counts   the candidate test and the resolution of one radix digit from a lane's eight bin counts.
 // A pair's bits are the same alone and inside a batch because both forms run these bodies in the same order.
@@ -104,7 +104,7 @@ __device__ __forceinline__ void p2l_source(double (&acc)[P2L_NSUMS], const float
 }
 
 // ---- generalized ICP ------------------------------------------------------------------------------------
-// Source i as in p2l_source, with the source's own normal sn[3 * i ..] (by ORIGINAL index) turned by Rn: the definition at
+// Source i as in p2l_source, with the source's own normal sn[3 * i ..] (by ORIGINAL index; in a batch the global one) turned by Rn: the definition at
 // kss_icp_gicp in include/kssicp.h.  The 6 x 6 block A^T M A of A = [ -[p]x | I ] is formed by blocks -- lower right M, upper
 // right B = [p]x M, upper left B [p]x^T -- and not by a generic triple product: 54 f64 multiplications instead of 162.
 template <int SRC>

@@ -24,6 +24,13 @@
 //   pairb_robust_rows_kernel     pairb_rows_kernel with the PAIR_ROBUST bodies; every workgroup derives the pass's c2 itself.
 //   pairb_robust_final_kernel    the column sums, the record and {m, c2, sum of weights, cnt} to host-mapped memory.
 // Fixed-scale pairs skip the first two; a batch without an automatic pair does not launch them.
+//
+// Generalized ICP for many pairs: two launches per pass behind the NN pass.
+//   pairb_gicp_rows_kernel       pairb_rows_kernel's grid on gicp_source (kss_pair_device.hpp); the rotation applied to the source
+//                                normals and e = 1 - epsilon are the PAIR's, read once per workgroup from a per-pair table of
+//                                GicpPass that the host rewrites before every pass.  The source normals are packed like the
+//                                sources and read by global original index.
+//   pairb_final_kernel<true>     unchanged.
 #pragma clang fp contract(off)
 
 #include "kss_robust_device.hpp"
@@ -140,6 +147,36 @@ __global__ __launch_bounds__(P2L_THREADS) void pairb_final_kernel(const double* 
         const double v = rows_column_sum(r, d.nrows, shg);
         if (threadIdx.x < NSUMS) o[threadIdx.x] = threadIdx.x >= 17 ? 0.0 : v;
     }
+}
+
+// ---- generalized ICP (kss_gicp.hip's kernel, per pair) ----------------------------------------------------------------------
+// pass[p] is the same for every lane of the workgroup (p comes from blockIdx.x alone): one uniform load, nothing per source
+template <bool PERM>
+__global__ __launch_bounds__(P2L_THREADS) void pairb_gicp_rows_kernel(const float4* __restrict__ src4, const int32_t* __restrict__ perm,
+                                                                      const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
+                                                                      const float* __restrict__ sn_all, const float* __restrict__ tgt_all,
+                                                                      const float* __restrict__ nrm_all, const PairbDesc* __restrict__ desc,
+                                                                      const int32_t* __restrict__ row_pair, const PairState* __restrict__ state,
+                                                                      const GicpPass* __restrict__ pass, double max_d2,
+                                                                      double* __restrict__ rows) {
+    __shared__ double sh[P2L_THREADS / 64][P2L_NSUMS];
+    const int p = row_pair[blockIdx.x];
+    if (!pairb_active(state, p)) return;
+    const PairbDesc d = desc[p];
+    const GicpPass gp = pass[p];
+    GicpRot Rn;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rn.r[k] = gp.r[k];
+    double acc[P2L_NSUMS];
+#pragma unroll
+    for (int c = 0; c < P2L_NSUMS; ++c) acc[c] = 0.0;
+    const float* tgt = tgt_all + 3 * d.tgt_off;
+    const float* nrm = nrm_all + 3 * d.tgt_off;
+    const int64_t step = (int64_t)d.nrows * P2L_THREADS;
+    for (int64_t i = (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x; i < d.ns; i += step)
+        gicp_source<PERM ? SRC_F4_PERM : SRC_F4>(acc, nullptr, src4, perm, idx, d2_in, sn_all, tgt, nrm, d.src_base + i, d.nt, max_d2, Rn, gp.e);
+    const double r = block_sum<P2L_NSUMS>(acc, sh);
+    if (threadIdx.x < P2L_NSUMS) rows[(int64_t)blockIdx.x * P2L_NSUMS + threadIdx.x] = r;
 }
 
 // ---- robust ICP (kss_robust.hip's kernels, per pair) ------------------------------------------------------------------------
@@ -274,6 +311,18 @@ void launch_pairb_sums(hipStream_t st, bool plane, bool trimmed, const float4* d
         hipLaunchKernelGGL(pairb_final_kernel<false>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_out);
     }
 #undef KSS_PAIRB_ROWS
+}
+
+void launch_pairb_gicp_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                            const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
+                            int total_rows, int npairs, const PairState* d_state, const GicpPass* d_pass, double max_d2, double* d_rows,
+                            double* d_out) {
+    const dim3 g(total_rows), b(P2L_THREADS);
+    if (d_perm)
+        hipLaunchKernelGGL(pairb_gicp_rows_kernel<true>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_pass, max_d2, d_rows);
+    else
+        hipLaunchKernelGGL(pairb_gicp_rows_kernel<false>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_pass, max_d2, d_rows);
+    hipLaunchKernelGGL(pairb_final_kernel<true>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_out);
 }
 
 void launch_pairb_robust_select(hipStream_t st, bool plane, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
