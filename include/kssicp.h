@@ -486,6 +486,63 @@ int kss_icp_gicp_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *
                            const float *d_tgt_all, const int64_t *tgt_off, const float *d_tgt_normals_all, int npairs,
                            const kss_icp_params *p, const kss_gicp_params *gp, const double *epsilons, kss_icp_result *results);
 
+/* ---- symmetric ICP (point-to-plane on the sum of both normals; Rusinkiewicz: A Symmetric Objective Function for ICP, SIGGRAPH
+ * 2019; PCL's TransformationEstimationSymmetricPointToPlaneLLS) for one pair ----
+ * The point-to-plane residual is taken against nq + ns and each cloud is turned by half the step towards the other: the residual
+ * is zero for any pair on a common second-order patch, not only a common plane, so the basin of convergence is wider than
+ * kss_icp_p2l's or kss_icp_gicp's at point-to-plane's cost per pass.  Both clouds carry normals (nt*3 and ns*3 floats).
+ * One pass.  F is the float 4x4 accumulated so far (identity in pass 0), R_F its upper left 3x3.  For source i: its current float
+ * position p, the exact NN target j = idx[i] with float d2[i], the float target point q, the float target normal
+ * nq = tgt_normals[j] and the float source normal ns = src_normals[i] (by ORIGINAL index).  Everything below is f64 on the
+ * widened floats with +, -, * only, nothing fused, in exactly this order:
+ *   candidate   j in [0, nt), !(d2 > max_d2), and all six normal components finite (kss_icp_gicp's tests); slot [29] receives d2
+ *               for every source with a valid j;
+ *   m           m[k] = (R_F[k][0]*ns[0] + R_F[k][1]*ns[1]) + R_F[k][2]*ns[2], k = 0, 1, 2;
+ *   n           dot = (m[0]*nq[0] + m[1]*nq[1]) + m[2]*nq[2];  align_normals = 1: n = nq - m if dot < 0, else n = nq + m;
+ *               align_normals = 0: always n = nq + m (consistently oriented normals, e.g. from kss_normals_orient).  The residual
+ *               is squared, so with align_normals = 1 the record does not depend on the sign of any input normal, bit for bit;
+ *   w, d        w = p + q,  d = q - p, component by component;
+ *   c           c = w x n:  c0 = w[1]*n[2] - w[2]*n[1],  c1 = w[2]*n[0] - w[0]*n[2],  c2 = w[0]*n[1] - w[1]*n[0];
+ *   v, r        v = (c0, c1, c2, n[0], n[1], n[2]);  r = (d[0]*n[0] + d[1]*n[1]) + d[2]*n[2];
+ *   record      KSS_P2L_NSUMS doubles: [0] kept count, [1..21] upper triangle of sum v v^T row-major, [22..27] sum v*r, [28] sum d2
+ *               kept, [29] sum d2 over all sources with a valid j, [30] sum r*r, [31] 0;
+ *   order       the fixed summation order of kss_icp_p2l, a function of the source count alone.
+ * The system is uncentred, as kss_icp_p2l's is (a stated choice: the record, the solve and the final launch are reused as they
+ * are; the clouds this library sees are pre-shaped to unit scale).
+ * Step (kss_rigid_from_symm_sums, host): x = (a, t) = (a0, a1, a2, t0, t1, t2) by kss_rigid_from_p2l_sums' Cholesky solve of the
+ * record; a failed Cholesky gives KSS_ERR_DEGENERATE / KSS_STATE_DEGENERATE and T the identity.  Then, in f64:
+ *   s2 = (a0*a0 + a1*a1) + a2*a2;   c = 1 / sqrt(1 + s2);   k = (c*c) / (1 + c);
+ *   H_ab = c*(delta_ab + K_ab) + k*(a_a*a_b),  K = (0 -a2 a1; a2 0 -a0; -a1 a0 0)   (the half rotation: Rodrigues with
+ *          tan(theta) = |a|, exactly orthogonal in real arithmetic, no division by |a|, no libm call);
+ *   R_ab = (H_a0*H_0b + H_a1*H_1b) + H_a2*H_2b;    t_a = (H_a0*(c*t0) + H_a1*(c*t1)) + H_a2*(c*t2);
+ * the twelve entries rounded to float, last row 0 0 0 1: p -> H (H p + c t), the paper's R p + t ~ R^-1 q.
+ * The loop around it is kss_icp_p2l's: fewer than min_correspondences kept -> KSS_STATE_NO_CORRESPONDENCES, PCL's criteria on
+ * MSE = [28] / [0], fitness over ALL sources, p->allreduce must be NULL.  KSS_ERR_ARG: everything kss_icp_gicp refuses, and
+ * align_normals outside {0, 1}.  The batched form, robust or trimmed weights on top, the C++ mirror classes and the CLI do not
+ * have this metric. */
+typedef struct {
+    int normals_k;      /* 20: read only when a set of normals is NULL; 3..64 */
+    int align_normals;  /* 1: n = nq - m where m . nq < 0;  0: always n = nq + m */
+} kss_symm_params;
+int kss_symm_default_params(kss_symm_params *sp);
+/* host only, no context: the step above from a record; KSS_ERR_DEGENERATE with T the identity when the Cholesky fails */
+int kss_rigid_from_symm_sums(const double sums[KSS_P2L_NSUMS], float T[16]);
+/* The record for given correspondences: the arguments of kss_gicp_sums (d2 recomputed as in kss_cov; the _dev form takes idx
+ * entries outside [0, nt) as no correspondence, the host form refuses them; Rn: HOST pointer to the row-major 3x3 float applied
+ * to the source normals in place of R_F, NULL = identity; either set of normals may be NULL: computed as for kss_gicp_sums). */
+int kss_symm_sums(kss_ctx *ctx, const float *src, const float *src_normals, const float *tgt, const float *tgt_normals,
+                  const int32_t *idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params *sp,
+                  double sums[KSS_P2L_NSUMS]);
+int kss_symm_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_src_normals, const float *d_tgt, const float *d_tgt_normals,
+                      const int32_t *d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params *sp,
+                      double sums[KSS_P2L_NSUMS]);
+/* normals as in kss_icp_gicp (NULL: computed from the cloud as passed in, the source before any motion).  trace_sums receives
+ * trace_cap * KSS_P2L_NSUMS doubles.  The result is that of kss_icp_p2l. */
+int kss_icp_symm(kss_ctx *ctx, const float *src, int64_t ns, const float *src_normals, const float *tgt, int64_t nt,
+                 const float *tgt_normals, const kss_icp_params *p, const kss_symm_params *sp, kss_icp_result *res);
+int kss_icp_symm_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const float *d_tgt, int64_t nt,
+                     const float *d_tgt_normals, const kss_icp_params *p, const kss_symm_params *sp, kss_icp_result *res);
+
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);
 int kss_transform_apply_dev(kss_ctx *ctx, const float T[16], const double *d_in, int64_t n, double *d_out);

@@ -41,6 +41,7 @@ SYMBOLS = [
     "kss_icp_robust", "kss_icp_robust_dev", "kss_icp_robust_batch", "kss_icp_robust_batch_dev",
     "kss_gicp_default_params", "kss_gicp_metric", "kss_gicp_sums", "kss_gicp_sums_dev", "kss_icp_gicp", "kss_icp_gicp_dev",
     "kss_icp_gicp_batch", "kss_icp_gicp_batch_dev",
+    "kss_symm_default_params", "kss_rigid_from_symm_sums", "kss_symm_sums", "kss_symm_sums_dev", "kss_icp_symm", "kss_icp_symm_dev",
 ]
 
 
@@ -84,6 +85,10 @@ class RobustParams(C.Structure):
 
 class GicpParams(C.Structure):
     _fields_ = [("epsilon", C.c_double), ("normals_k", C.c_int)]
+
+
+class SymmParams(C.Structure):
+    _fields_ = [("normals_k", C.c_int), ("align_normals", C.c_int)]
 
 
 class IcpResult(C.Structure):
@@ -179,6 +184,12 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(TrimParams), vp, vp, vp]
     for n in ("kss_icp_robust_batch", "kss_icp_robust_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(RobustParams), vp, vp, vp]
+    L.kss_symm_default_params.argtypes = [C.POINTER(SymmParams)]
+    L.kss_rigid_from_symm_sums.argtypes = [vp, vp]
+    for n in ("kss_symm_sums", "kss_symm_sums_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, dbl, vp, C.POINTER(SymmParams), vp]
+    for n in ("kss_icp_symm", "kss_icp_symm_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(SymmParams), C.POINTER(IcpResult)]
     for n in ("kss_icp_gicp_batch", "kss_icp_gicp_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(GicpParams), vp, vp]
     for n in ("kss_trim_threshold_batch", "kss_trim_threshold_batch_dev"):
@@ -369,6 +380,35 @@ def rigid_from_p2l_sums(sums):
     rc = L.kss_rigid_from_p2l_sums(_p(s), _p(T))
     if rc not in (0, ERR_DEGENERATE):
         raise KssError(rc, "kss_rigid_from_p2l_sums")
+    return T.reshape(4, 4), rc
+
+
+def symm_params(**kw):
+    """kss_symm_default_params (normals_k 20, align_normals 1), then the fields given by keyword."""
+    L = load_library()
+    sp = SymmParams()
+    rc = L.kss_symm_default_params(C.byref(sp))
+    if rc != 0:
+        raise KssError(rc, "kss_symm_default_params")
+    for k, v in kw.items():
+        if k in ("normals_k", "align_normals"):
+            setattr(sp, k, int(v))
+        else:
+            raise AttributeError(k)
+    return sp
+
+
+def rigid_from_symm_sums(sums):
+    """kss_rigid_from_symm_sums: (T, status) -- the symmetric step (two half rotations) from a P2L_NSUMS record; status 0, or
+    ERR_DEGENERATE with T the identity."""
+    L = load_library()
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.size != P2L_NSUMS:
+        raise ValueError("need %d sums" % P2L_NSUMS)
+    T = np.empty(16, np.float32)
+    rc = L.kss_rigid_from_symm_sums(_p(s), _p(T))
+    if rc not in (0, ERR_DEGENERATE):
+        raise KssError(rc, "kss_rigid_from_symm_sums")
     return T.reshape(4, 4), rc
 
 
@@ -755,6 +795,52 @@ class Context:
         self._chk(self.L.kss_icp_gicp_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
                                           C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
                                           C.byref(params), C.byref(gp), C.byref(res)), "kss_icp_gicp_dev")
+        return res
+
+    # ---- symmetric ICP
+    def symm_sums(self, src, src_normals, tgt, tgt_normals, idx, max_d2=1.0, Rn=None, sp=None):
+        """kss_symm_sums: the P2L_NSUMS record of one symmetric-ICP pass over given correspondences.  Rn: the 3 x 3 applied to the
+        source normals (None: identity); either set of normals may be None (computed); sp: a SymmParams (symm_params())."""
+        sp = sp if sp is not None else symm_params()
+        s, t = _f32(src), _f32(tgt)
+        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
+        i = np.ascontiguousarray(idx, dtype=np.int32)
+        r = self._gicp_rot(Rn)
+        sums = np.zeros(P2L_NSUMS, np.float64)
+        self._chk(self.L.kss_symm_sums(self.h, _p(s), _p(sn), _p(t), _p(tn), _p(i), len(s), len(t), float(max_d2), _p(r), C.byref(sp),
+                                       _p(sums)), "kss_symm_sums")
+        return sums
+
+    def symm_sums_dev(self, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2=1.0, Rn=None, sp=None):
+        """kss_symm_sums_dev on device pointers (either normals pointer may be 0 / None; Rn stays a host array)."""
+        sp = sp if sp is not None else symm_params()
+        r = self._gicp_rot(Rn)
+        sums = np.zeros(P2L_NSUMS, np.float64)
+        self._chk(self.L.kss_symm_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
+                                           C.c_void_p(int(d_tgt)), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
+                                           C.c_void_p(int(d_idx)), int(n), int(nt), float(max_d2), _p(r), C.byref(sp), _p(sums)),
+                  "kss_symm_sums_dev")
+        return sums
+
+    def icp_symm(self, src, tgt, src_normals=None, tgt_normals=None, sp=None, params=None, trace_cap=0, fitness_corr=False):
+        """Symmetric ICP (kss_icp_symm): the point-to-plane residual against the sum of both clouds' normals, each cloud turned by
+        half the step (ns x 3 and nt x 3 normals; None: computed with kss_normals' definition at sp.normals_k and rounded to
+        float).  sp: a SymmParams (symm_params()).  The result dictionary of icp_p2l()."""
+        sp = sp if sp is not None else symm_params()
+        s, t = _f32(src), _f32(tgt)
+        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
+        p = params if params is not None else self.icp_params()
+        return self._icp_call(lambda res: self.L.kss_icp_symm(self.h, _p(s), len(s), _p(sn), _p(t), len(t), _p(tn), C.byref(p), C.byref(sp),
+                                                              C.byref(res)),
+                              "kss_icp_symm", p, len(s), P2L_NSUMS, trace_cap, fitness_corr)
+
+    def icp_symm_dev(self, d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals, params, sp=None):
+        """kss_icp_symm_dev on device pointers (either normals pointer may be 0 / None); returns the IcpResult."""
+        sp = sp if sp is not None else symm_params()
+        res = IcpResult()
+        self._chk(self.L.kss_icp_symm_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
+                                          C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
+                                          C.byref(params), C.byref(sp), C.byref(res)), "kss_icp_symm_dev")
         return res
 
     # ---- point-to-plane and trimmed ICP, many pairs per call

@@ -850,6 +850,106 @@ int kss_icp_gicp(kss_ctx* c, const float* src, int64_t ns, const float* src_norm
                             (const float*)c->stage_tgt.p, nt, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, p, gp, res);
 }
 
+// ---- symmetric ICP -----------------------------------------------------------------
+int kss_symm_default_params(kss_symm_params* sp) {
+    if (!sp) return KSS_ERR_ARG;
+    sp->normals_k = 20;
+    sp->align_normals = 1;
+    return KSS_OK;
+}
+
+int kss_rigid_from_symm_sums(const double sums[KSS_P2L_NSUMS], float T[16]) {
+    if (!sums || !T) return KSS_ERR_ARG;
+    if (!rigid_from_symm_sums(sums, T)) {
+        mat4_identity(T);
+        return KSS_ERR_DEGENERATE;
+    }
+    return KSS_OK;
+}
+
+// the checks of sp that kss_symm_sums and kss_icp_symm share; need_k: a set of normals is to be computed
+static int symm_check(kss_ctx* c, const char* who, const kss_symm_params* sp, bool need_k) {
+    const std::string w = std::string(who) + ": ";
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
+    if (!sp) return bad("null argument");
+    if (sp->align_normals != 0 && sp->align_normals != 1) return bad("align_normals must be 0 or 1");
+    if (need_k && (sp->normals_k < 3 || sp->normals_k > 64)) return bad("normals_k must be in 3..64");
+    return KSS_OK;
+}
+
+int kss_symm_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals, const float* d_tgt, const float* d_tgt_normals,
+                      const int32_t* d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp,
+                      double sums[KSS_P2L_NSUMS]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_check(c, "symm_sums", sp, !d_src_normals || !d_tgt_normals));
+    if (!d_src || !d_tgt || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "symm_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "symm_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_sums: cloud too large");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
+    {
+        ProfScope ps(c, KSS_K_CORR_REDUCE);
+        launch_symm_sums(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, d_tgt, d_tgt_normals, n, nt, max_d2, Rn,
+                         sp->align_normals, (double*)c->p2l_rows.p, (double*)c->h_p2l_dev);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(sums, c->h_p2l, KSS_P2L_NSUMS * sizeof(double));
+    return KSS_OK;
+}
+
+int kss_symm_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals, const int32_t* idx,
+                  int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp, double sums[KSS_P2L_NSUMS]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_check(c, "symm_sums", sp, !src_normals || !tgt_normals));
+    if (!src || !tgt || !idx || !sums) return set_err(c, KSS_ERR_ARG, "symm_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "symm_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_sums: cloud too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= nt) return set_err(c, KSS_ERR_ARG, "symm_sums: index out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)n * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
+    return kss_symm_sums_dev(c, (const float*)c->stage_src.p, src_normals ? (const float*)c->gicp_snrm.p : nullptr, (const float*)c->stage_tgt.p,
+                             tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, (const int32_t*)c->stage_idx.p, n, nt, max_d2, Rn, sp, sums);
+}
+
+int kss_icp_symm_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const float* d_tgt, int64_t nt,
+                     const float* d_tgt_normals, const kss_icp_params* p, const kss_symm_params* sp, kss_icp_result* res) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_check(c, "icp_symm", sp, !d_src_normals || !d_tgt_normals));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm: the source-row split (allreduce) is not available for symmetric ICP");
+    KCHK(pair_check(c, "icp_symm", false, d_src, d_tgt, ns, nt, d_tgt_normals, p, nullptr, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(gicp_normals_dev(c, d_src, ns, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
+    PairMode mode;
+    mode.plane = true;
+    mode.symm = true;
+    mode.symm_align = sp->align_normals;
+    mode.d_src_nrm = d_src_normals;
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_tgt_normals, p, mode, res);
+}
+
+int kss_icp_symm(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const float* tgt, int64_t nt, const float* tgt_normals,
+                 const kss_icp_params* p, const kss_symm_params* sp, kss_icp_result* res) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_check(c, "icp_symm", sp, !src_normals || !tgt_normals));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm: the source-row split (allreduce) is not available for symmetric ICP");
+    KCHK(pair_check(c, "icp_symm", false, src, tgt, ns, nt, tgt_normals, p, nullptr, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)ns * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_symm_dev(c, (const float*)c->stage_src.p, ns, src_normals ? (const float*)c->gicp_snrm.p : nullptr,
+                            (const float*)c->stage_tgt.p, nt, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, p, sp, res);
+}
+
 // ---- the same for many pairs per call ------------------------------------------------
 // Every cloud's normals where the caller gave none: cloud_normals_dev at k, cloud after cloud (off: npairs + 1 offsets in points
 // from 0), into the packed buffer `out` laid out like the clouds (setup cost of the call, not optimised: a k-NN and a normals

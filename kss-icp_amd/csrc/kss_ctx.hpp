@@ -252,8 +252,8 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // one exact NN pass of a single pair (+ the correspondence sums when sums_out is given)
 int nn_generic_dev(kss_ctx* c, const void* d_src, int64_t ns, const void* d_tgt, int64_t nt, int dtype,
                    int32_t* d_idx, float* d_d2, double sums_out[NSUMS]);
-// ICP of one pair by kss_icp_p2l (plane, untrimmed), kss_icp_trimmed, kss_icp_robust (either metric) or kss_icp_gicp: float clouds
-// on the device, d_nrm the target's normals for the plane metric.  The untrimmed, unweighted point metric is icp_run_dev's.
+// ICP of one pair by kss_icp_p2l (plane, untrimmed), kss_icp_trimmed, kss_icp_robust (either metric), kss_icp_gicp or kss_icp_symm:
+// float clouds on the device, d_nrm the target's normals for the plane metric.  The untrimmed, unweighted point metric is icp_run_dev's.
 struct PairMode {
     bool plane = false;             // point-to-plane step (d_nrm given); otherwise point-to-point
     bool trimmed = false;           // keep the closest `overlap` share of each pass's candidates
@@ -265,6 +265,8 @@ struct PairMode {
     bool gicp = false;              // generalized ICP (kss_icp_gicp; with plane, not with trimmed or robust): d_nrm and the SOURCE's
     double gicp_epsilon = 0.0;      // normals d_src_nrm (device, float triples by original source index) weigh every correspondence
     const float* d_src_nrm = nullptr;
+    bool symm = false;              // symmetric ICP (kss_icp_symm; with plane, not with trimmed, robust or gicp): the plane record on
+    int symm_align = 1;             // nq +- R_F ns, ns from d_src_nrm as for gicp; the step is rigid_from_symm_sums
 };
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,

@@ -1868,6 +1868,8 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // Generalized (kss_icp_gicp; M.gicp with M.plane): the gicp rows launch in place of the plane metric's, given the
 // rotation of the transform accumulated so far for the source normals; the final launch, the record's layout, the host step and
 // the criteria are the plane metric's.
+// Symmetric (kss_icp_symm; M.symm with M.plane): the symmetric rows launch with the same rotation; the record's
+// layout and the solve are the plane metric's, the step built from the solution is rigid_from_symm_sums' (two half rotations).
 // What the host does for ONE pair after a pass, the same code for a single pair (pair_loop) and inside a batch (pairs_loop): the
 // min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
 // its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
@@ -1884,7 +1886,9 @@ static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const dou
     // PCL: "Not enough correspondences found" (robust: the count kept, [0] being the weight total)
     const double cnt = M.robust ? s[(M.plane ? P2L_NSUMS : NSUMS) - 1] : s[0];
     if ((int)cnt < P.min_correspondences) { t.state = KSS_STATE_NO_CORRESPONDENCES; return false; }
-    if (M.plane) {
+    if (M.symm) {
+        if (!rigid_from_symm_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
+    } else if (M.plane) {
         if (!rigid_from_p2l_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
     } else {
         rigid_from_sums(s, t.tk);
@@ -1950,6 +1954,11 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
                 const float Rn[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
                 launch_gicp_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn, M.gicp_epsilon,
                                  d_rows, d_rec);
+            } else if (M.symm) {   // the same rotation for the symmetric sums
+                const float* F = tr.fin;
+                const float Rn[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
+                launch_symm_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn, M.symm_align,
+                                 d_rows, d_rec);
             } else if (M.plane)
                 launch_p2l_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, d_rows, d_rec, d_cut);
             else
@@ -1980,6 +1989,8 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
     if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: trimmed and robust exclude each other");
     if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm))
         return set_err(c, KSS_ERR_ARG, "pair_run: generalized ICP is the plane record with both clouds' normals, neither trimmed nor robust");
+    if (M.symm && (!M.plane || M.trimmed || M.robust || M.gicp || !M.d_src_nrm || !d_nrm))
+        return set_err(c, KSS_ERR_ARG, "pair_run: symmetric ICP is the plane record with both clouds' normals, neither trimmed, robust nor generalized");
     HIPCHK(c, hipSetDevice(c->device));
     IcpPlan pl;
     const auto t0 = std::chrono::steady_clock::now();
@@ -2200,6 +2211,7 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
     if (M.robust && !rscales) return set_err(c, KSS_ERR_ARG, "pairs_run: robust needs the per-pair scales");
     if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm || !gicp_eps))
         return set_err(c, KSS_ERR_ARG, "pairs_run: generalized ICP is the plane record with both clouds' normals and the per-pair epsilons, neither trimmed nor robust");
+    if (M.symm) return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP has no batched form");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> ns(npairs), nt(npairs);
     for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }

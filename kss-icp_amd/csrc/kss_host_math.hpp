@@ -189,6 +189,34 @@ inline bool rigid_from_p2l_sums(const double sums[P2L_NSUMS], float T[16]) {
     return true;
 }
 
+// ---- the symmetric step (kss_icp_symm in include/kssicp.h) --------------------------------------------------
+// x = (a~, t~) from p2l_solve; the half rotation H = c (I + [a~]x) + k a~ a~^T with c = 1 / sqrt(1 + |a~|^2), k = c^2 / (1 + c)
+// (Rodrigues at tan(theta) = |a~|: no division by |a~|, no libm call beyond sqrt); R = H H, t = H (c t~); rounded to float.
+inline void symm_transform(const double x[6], float T[16]) {
+    const double s2 = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2];
+    const double c = 1.0 / std::sqrt(1.0 + s2);
+    const double k = (c * c) / (1.0 + c);
+    const double K[3][3] = {{0.0, -x[2], x[1]}, {x[2], 0.0, -x[0]}, {-x[1], x[0], 0.0}};
+    double H[3][3];
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) H[a][b] = c * ((a == b ? 1.0 : 0.0) + K[a][b]) + k * (x[a] * x[b]);
+    const double ct[3] = {c * x[3], c * x[4], c * x[5]};
+    for (int a = 0; a < 3; ++a) {
+        for (int b = 0; b < 3; ++b) T[4 * a + b] = (float)((H[a][0] * H[0][b] + H[a][1] * H[1][b]) + H[a][2] * H[2][b]);
+        T[4 * a + 3] = (float)((H[a][0] * ct[0] + H[a][1] * ct[1]) + H[a][2] * ct[2]);
+    }
+    T[12] = T[13] = T[14] = 0.f;
+    T[15] = 1.f;
+}
+
+// T from the sums; false (T untouched) when the system is degenerate
+inline bool rigid_from_symm_sums(const double sums[P2L_NSUMS], float T[16]) {
+    double x[6];
+    if (!p2l_solve(sums, x)) return false;
+    symm_transform(x, T);
+    return true;
+}
+
 // ---- Matrix4f product, Eigen order: ((a0*b0 + a1*b1) + a2*b2) + a3*b3, no fma -------------
 inline void mat4_mul(const float A[16], const float B[16], float C[16]) {
     float R[16];

@@ -349,6 +349,12 @@ void launch_gicp_sums(hipStream_t st, const float* d_src3, const float4* d_src4,
                       const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
                       double max_d2, const float Rn[9], double epsilon, double* d_rows, double* d_out);
 
+// symmetric ICP sums (kss_symm.hip): launch_gicp_sums' arguments; align: 1 = n = nq - m where m . nq < 0, 0 = always
+// n = nq + m.
+void launch_symm_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
+                      const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
+                      double max_d2, const float Rn[9], int align, double* d_rows, double* d_out);
+
 // ---- trimmed ICP (kss_trim.hip) ----
 // What one digit of the radix select hands to the next, and the last one to the sums kernels of the same pass: the key
 // prefix found so far, the rank inside the keys that carry it, m candidates, k = trim_rank_of(m, overlap); after the last digit

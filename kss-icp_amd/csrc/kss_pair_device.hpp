@@ -2,6 +2,7 @@
 // ones (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
 //   gicp_source                      the same for generalized ICP (kss_gicp.hip; in a batch: pairb_gicp_rows_kernel),
+//   symm_source                      the same for symmetric ICP (single pair only: kss_symm.hip),
 //   p2l_rows_column_sum              the fixed-order column sums of the plane metric's rows,
 //   trim_key / trim_resolve_counts   the candidate test and the resolution of one radix digit from a lane's eight bin counts.
 // A pair's bits are the same alone and inside a batch because both forms run these bodies in the same order.
@@ -166,6 +167,58 @@ __device__ __forceinline__ void gicp_source(double (&acc)[P2L_NSUMS], const floa
         acc[25] += u[0]; acc[26] += u[1]; acc[27] += u[2];
         acc[28] += d2;
         acc[30] += (d0 * u[0] + d1 * u[1]) + dz * u[2];
+    }
+}
+
+// ---- symmetric ICP --------------------------------------------------------------------------------------
+// Source i as in gicp_source: the definition at kss_icp_symm in include/kssicp.h.  The plane metric's record with
+// n = nq +- m in place of the target's normal and w = p + q in place of p; the 21 + 6 products of v v^T and v r directly.
+template <int SRC>
+__device__ __forceinline__ void symm_source(double (&acc)[P2L_NSUMS], const float* __restrict__ src3, const float4* __restrict__ src4,
+                                            const int32_t* __restrict__ perm, const int32_t* __restrict__ idx,
+                                            const float* __restrict__ d2_in, const float* __restrict__ sn, const float* __restrict__ tgt,
+                                            const float* __restrict__ nrm, int64_t i, int64_t nt, double max_d2, const GicpRot& Rn, int align) {
+    const int64_t j = idx[i];
+    if (j < 0 || j >= nt) return;
+    float sx, sy, sz;
+    if constexpr (SRC == SRC_F3) {
+        sx = src3[3 * i]; sy = src3[3 * i + 1]; sz = src3[3 * i + 2];
+    } else {
+        const float4 p = src4[SRC == SRC_F4_PERM ? (int64_t)perm[i] : i];
+        sx = p.x; sy = p.y; sz = p.z;
+    }
+    const float qx = tgt[3 * j], qy = tgt[3 * j + 1], qz = tgt[3 * j + 2];
+    const float nx = nrm[3 * j], ny = nrm[3 * j + 1], nz = nrm[3 * j + 2];
+    const float ux = sn[3 * i], uy = sn[3 * i + 1], uz = sn[3 * i + 2];
+    const double d2 = (double)(d2_in ? d2_in[i] : dist2<false>(sx, sy, sz, qx, qy, qz));
+    acc[29] += d2;
+    if (!(d2 > max_d2) && isfinite(nx) && isfinite(ny) && isfinite(nz) && isfinite(ux) && isfinite(uy) && isfinite(uz)) {
+        const double nq[3] = {(double)nx, (double)ny, (double)nz};
+        const double us[3] = {(double)ux, (double)uy, (double)uz};
+        double m[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) m[k] = ((double)Rn.r[3 * k] * us[0] + (double)Rn.r[3 * k + 1] * us[1]) + (double)Rn.r[3 * k + 2] * us[2];
+        const double dot = (m[0] * nq[0] + m[1] * nq[1]) + m[2] * nq[2];
+        const bool flip = align && dot < 0.0;
+        const double n0 = flip ? nq[0] - m[0] : nq[0] + m[0];
+        const double n1 = flip ? nq[1] - m[1] : nq[1] + m[1];
+        const double n2 = flip ? nq[2] - m[2] : nq[2] + m[2];
+        const double px = (double)sx, py = (double)sy, pz = (double)sz;
+        const double qxd = (double)qx, qyd = (double)qy, qzd = (double)qz;
+        const double w0 = px + qxd, w1 = py + qyd, w2 = pz + qzd;
+        const double d0 = qxd - px, d1 = qyd - py, dz = qzd - pz;
+        const double v[6] = {w1 * n2 - w2 * n1, w2 * n0 - w0 * n2, w0 * n1 - w1 * n0, n0, n1, n2};
+        const double r = (d0 * n0 + d1 * n1) + dz * n2;
+        acc[0] += 1.0;
+        int k = 1;
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+#pragma unroll
+            for (int q = p; q < 6; ++q) acc[k++] += v[p] * v[q];
+#pragma unroll
+        for (int p = 0; p < 6; ++p) acc[22 + p] += v[p] * r;
+        acc[28] += d2;
+        acc[30] += r * r;
     }
 }
 
