@@ -129,7 +129,8 @@ int kss_knn_dev(kss_ctx *ctx, const float *d_query, int64_t nq, const float *d_t
 /* ---- surface normals: estimateNormal_PCL_MP_return, normalCompute.hpp:308-355 ----
  * pcl::NormalEstimationOMP semantics (k nearest neighbours incl. the point itself, float single-pass covariance,
  * closed-form smallest eigenvector, flipped towards the view point (0,0,0)) and the reference's renormalisation in
- * double.  normals: n * 3 doubles.  The reference uses k = 20. */
+ * double.  normals: n * 3 doubles.  1 <= k <= 64 (kss_knn's range; k above n is clamped to n).  The reference uses
+ * k = 20. */
 int kss_normals(kss_ctx *ctx, const double *pts, int64_t n, int k, double *normals);
 /* estimateNormal_RegularNormal, normalCompute.hpp:614-742 (with kss_normals: estimateNormal_PCL_MP, :358-403):
  * consistent orientation of given normals (n*3 doubles, in place) by level-synchronous propagation over the 8-NN

@@ -315,7 +315,7 @@ int kss_knn(kss_ctx* c, const float* query, int64_t nq, const float* tgt, int64_
 
 int kss_normals(kss_ctx* c, const double* pts, int64_t n, int k, double* normals) {
     if (!c || !pts || !normals) return set_err(c, KSS_ERR_ARG, "normals: null argument");
-    if (n <= 0 || k < 1 || k > 32) return set_err(c, KSS_ERR_ARG, "normals: need n > 0 and 1 <= k <= 32");
+    if (n <= 0 || k < 1 || k > 64) return set_err(c, KSS_ERR_ARG, "normals: need n > 0 and 1 <= k <= 64");
     if (k > n) k = (int)n;
     HIPCHK(c, hipSetDevice(c->device));
     KCHK(upload(c, c->scratch_a, pts, (size_t)n * 3 * sizeof(double)));
