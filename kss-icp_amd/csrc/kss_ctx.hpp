@@ -46,7 +46,7 @@ struct kss_ctx {
 
     // grow-only device workspace
     DevBuf tgt4, src0, cur[2], keys, partials, sums, nn_work, red_work, pair_red, state, cs, scratch_a,
-        scratch_b, scratch_c, stage_src, stage_tgt, stage_idx, stage_d2, stage_out, g_counts, g_start, g_cursor,
+        scratch_b, scratch_c, stage_src, stage_tgt, stage_idx, stage_d2, stage_out, g_counts, g_slot, g_start, g_cursor,
         g_bsums, g_sorted, g_list, g_count, g_bbox, g_partials, g_start2, g_pairs, g_stamps, g_pos, g_nnst, res_pos, res_wc, res_perm, pack_seg, reg_s, reg_t, reg_p, reg_all, reg_f, reg_g, oct_pts, oct_cen, oct_a, oct_b, oct_tmp, pre_partials, pre_state, g_rowpair, g_gate;
     // point-to-plane ICP (kss_p2l.hip): per-pass idx / d2, source slot of each original index, partial rows, float normals
     // (staged or computed) and their f64 form from the normals kernel
@@ -100,8 +100,9 @@ struct kss_ctx {
         bool fma = false, full = false, want_full = false; double max_d2 = 0.0;
     } gated;
     // g_count and g_counts are ZERO AT REST: every kernel that uses them leaves them zeroed (the unresolved-list length is
-    // reset when the list is consumed, the cell counts are counted back down by the scatter), so a registration needs no
-    // memset of its own.  A call that fails midway sets ws_dirty and the next one clears them first; ensure_zeroed() clears
+    // reset when the list is consumed; the cell counts are zeroed by the scan that reads them -- a single pair, whose scatter
+    // takes its slots from g_slot -- or counted back down by the scatter -- a batch), so a registration needs no memset of
+    // its own.  A call that fails midway sets ws_dirty and the next one clears them first; ensure_zeroed() clears
     // a buffer it had to (re)allocate.
     bool ws_dirty = false;
     bool defer_wait = false;   // batched fused pass: the ICP loop polls the pairs' result slots itself

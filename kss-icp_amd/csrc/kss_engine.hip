@@ -393,6 +393,7 @@ static int grid_setup(kss_ctx* c, IcpPlan& pl) {
     pl.gp = gp;
     const size_t ncells = (size_t)gp.gx * gp.gy * gp.gz;
     KCHK(ensure_zeroed(c, c->g_counts, 2 * ncells * sizeof(int32_t)));   // target cells, then source cells; zero at rest (kss_ctx.hpp)
+    KCHK(ensure(c, c->g_slot, ((size_t)nt + (size_t)ns) * sizeof(int32_t)));   // every point's slot inside its cell, from the count to the scatter
     KCHK(ensure(c, c->g_start, (2 * ncells + 8) * sizeof(int32_t)));   // [0] pad, target starts at [1 .. ncells + 1], source starts (+ nt) behind
     KCHK(ensure(c, c->g_bsums, scan_scratch_bytes((int)(2 * ncells))));
     KCHK(ensure(c, c->g_sorted, (size_t)nt * sizeof(float4)));
@@ -418,8 +419,8 @@ static int grid_setup(kss_ctx* c, IcpPlan& pl) {
     pl.gpairs[0].cell_base = 0;
     // both cell lists by shared launches; the sources end up in src0 in the target's cell order (original index in .w);
     // cur[0] is the scatter's scratch
-    launch_grid_build_pair(c->stream, tgt, nt, (float4*)c->src0.p + g.src_base, ns, gp, (int32_t*)c->g_counts.p, (int32_t*)c->g_start.p + 1,
-                           (int32_t*)c->g_bsums.p, (float4*)c->g_sorted.p, (float4*)c->cur[0].p);
+    launch_grid_build_pair(c->stream, tgt, nt, (float4*)c->src0.p + g.src_base, ns, gp, (int32_t*)c->g_counts.p, (int32_t*)c->g_slot.p,
+                           (int32_t*)c->g_start.p + 1, (int32_t*)c->g_bsums.p, (float4*)c->g_sorted.p, (float4*)c->cur[0].p);
     HIPCHK(c, hipGetLastError());
     c->grid_stats[0] = gp.h; c->grid_stats[1] = gp.gx; c->grid_stats[2] = gp.gy; c->grid_stats[3] = gp.gz;
     if (c->stats_ns != ns || c->stats_nt != nt) { c->grid_stats[4] = 0; c->grid_stats[5] = 0; }

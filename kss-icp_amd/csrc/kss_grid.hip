@@ -42,15 +42,18 @@ namespace kss {
 // counts / starts are ONE array of 2 * ncells entries: [0, ncells) the target's cells, [ncells, 2 ncells) the source's.
 // One exclusive scan over the whole array gives the target's starts directly (and start[ncells] = nt is their end
 // sentinel) and the source's starts offset by nt.  Blocks [0, nbt) handle target points, the rest source points.
+// What the count's atomic returns is the point's slot inside its cell: kept per point (slot[0, nt) the targets', slot[nt,
+// nt + ns) the sources'), it spares the scatter an atomic of its own -- these atomics execute at the memory side, ~11 us
+// per 200k of them, and one per point is enough.
 __global__ __launch_bounds__(256) void grid_count2_kernel(const float4* __restrict__ tgt, int nt, int nbt, const float4* __restrict__ src, int ns,
-                                                          GridParams gp, int32_t* __restrict__ counts) {
+                                                          GridParams gp, int32_t* __restrict__ counts, int32_t* __restrict__ slot) {
     const bool is_src = (int)blockIdx.x >= nbt;
     const int i = ((int)blockIdx.x - (is_src ? nbt : 0)) * 256 + (int)threadIdx.x;
     if (i >= (is_src ? ns : nt)) return;
     const float4 p = is_src ? src[i] : tgt[i];
     const int cx = cell_coord(p.x, gp.ox, gp.inv_h, gp.gx), cy = cell_coord(p.y, gp.oy, gp.inv_h, gp.gy),
               cz = cell_coord(p.z, gp.oz, gp.inv_h, gp.gz);
-    atomicAdd(&counts[(is_src ? gp.gx * gp.gy * gp.gz : 0) + (cz * gp.gy + cy) * gp.gx + cx], 1);
+    slot[(is_src ? nt : 0) + i] = atomicAdd(&counts[(is_src ? gp.gx * gp.gy * gp.gz : 0) + (cz * gp.gy + cy) * gp.gx + cx], 1);
 }
 
 // exclusive scan, 3 phases; each workgroup owns SCAN_CHUNK consecutive elements
@@ -103,8 +106,10 @@ __global__ __launch_bounds__(1024) void scan_of_block_sums_kernel(int32_t* __res
 // SELF = true (up to 1024 chunks): the workgroup adds up the chunk totals before its own by itself and the last element
 // also writes start[n] -- two launches (scan_of_block_sums, scan_tail) less per scan, which matters when a whole cell-list
 // build is ~20 launches of a few microseconds each.
-template <bool SELF>
-__global__ __launch_bounds__(256) void scan_apply_kernel(const int32_t* __restrict__ in, int n, const int32_t* __restrict__ block_sums,
+// CLEAR = true: every counter is written back as zero once it has been read (this launch is the last reader of the single
+// pair's counters, whose scatter takes its slots from the count: the array is zero at rest again, kss_ctx.hpp).
+template <bool SELF, bool CLEAR>
+__global__ __launch_bounds__(256) void scan_apply_kernel(int32_t* in, int n, const int32_t* __restrict__ block_sums,
                                                          int32_t* __restrict__ out_start) {
     // the chunk as four slices of 1024 elements; lane t holds elements 4t .. 4t+3 of each slice (one 16-byte load per slice,
     // consecutive lanes consecutive addresses), wave scans of the lane totals, slice / wave totals through LDS
@@ -132,6 +137,10 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(const int32_t* __restri
         const int i = base + (k * 256 + tid) * 4;
         if (i + 3 < n) v[k] = *(const int4u*)(in + i);
         else { v[k].x = i < n ? in[i] : 0; v[k].y = i + 1 < n ? in[i + 1] : 0; v[k].z = i + 2 < n ? in[i + 2] : 0; v[k].w = 0; }
+        if constexpr (CLEAR) {
+            if (i + 3 < n) { if ((v[k].x | v[k].y | v[k].z | v[k].w) != 0) *(int4u*)(in + i) = int4u{0, 0, 0, 0}; }   // (most cells of a surface cloud's grid are empty: nothing to write)
+            else { if (i < n) in[i] = 0; if (i + 1 < n) in[i + 1] = 0; if (i + 2 < n) in[i + 2] = 0; }
+        }
         int x = (v[k].x + v[k].y) + (v[k].z + v[k].w);
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
@@ -176,32 +185,38 @@ size_t scan_scratch_bytes(int n) {
     return std::max<size_t>(bytes, ((size_t)(n + SCAN_CHUNK - 1) / SCAN_CHUNK + 1) * sizeof(int32_t)) + 256;
 }
 
-static void launch_scan(hipStream_t st, const int32_t* d_counts, int ncells, int32_t* d_start, int32_t* d_scratch) {
+// clear: leave d_counts zeroed (the apply kernel writes the zeros; the library scan is followed by one memset)
+static void launch_scan(hipStream_t st, int32_t* d_counts, int ncells, int32_t* d_start, int32_t* d_scratch, bool clear) {
     static const bool lib = getenv("KSS_SCAN_LIB") != nullptr;   // A/B: rocPRIM's look-back scan for big tables
     if (lib && ncells > 1024 * SCAN_CHUNK) {
         size_t bytes = 0;
         if (rocprim::inclusive_scan<BigScanConfig>(nullptr, bytes, d_counts, d_start + 1, (size_t)ncells, rocprim::plus<int32_t>(), st) == hipSuccess) {
             hipMemsetAsync(d_start, 0, sizeof(int32_t), st);
-            if (rocprim::inclusive_scan<BigScanConfig>((void*)d_scratch, bytes, d_counts, d_start + 1, (size_t)ncells, rocprim::plus<int32_t>(), st) == hipSuccess) return;
+            if (rocprim::inclusive_scan<BigScanConfig>((void*)d_scratch, bytes, d_counts, d_start + 1, (size_t)ncells, rocprim::plus<int32_t>(), st) == hipSuccess) {
+                if (clear) hipMemsetAsync(d_counts, 0, sizeof(int32_t) * (size_t)ncells, st);
+                return;
+            }
         }
         (void)hipGetLastError();
     }
     int32_t* d_block_sums = d_scratch;
     const int nb = (ncells + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nb), dim3(256), 0, st, d_counts, ncells, d_block_sums);
+    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(nb), dim3(256), 0, st, (const int32_t*)d_counts, ncells, d_block_sums);
     if (nb <= 1024) {
-        hipLaunchKernelGGL(scan_apply_kernel<true>, dim3(nb), dim3(256), 0, st, d_counts, ncells, d_block_sums, d_start);
-    } else {
+        if (clear) hipLaunchKernelGGL((scan_apply_kernel<true, true>), dim3(nb), dim3(256), 0, st, d_counts, ncells, (const int32_t*)d_block_sums, d_start);
+        else hipLaunchKernelGGL((scan_apply_kernel<true, false>), dim3(nb), dim3(256), 0, st, d_counts, ncells, (const int32_t*)d_block_sums, d_start);
+    } else {   // (the apply kernel also writes start[n])
         hipLaunchKernelGGL(scan_of_block_sums_kernel, dim3(1), dim3(1024), 0, st, d_block_sums, nb);
-        hipLaunchKernelGGL(scan_apply_kernel<false>, dim3(nb), dim3(256), 0, st, d_counts, ncells, d_block_sums, d_start);   // (also writes start[n])
+        if (clear) hipLaunchKernelGGL((scan_apply_kernel<false, true>), dim3(nb), dim3(256), 0, st, d_counts, ncells, (const int32_t*)d_block_sums, d_start);
+        else hipLaunchKernelGGL((scan_apply_kernel<false, false>), dim3(nb), dim3(256), 0, st, d_counts, ncells, (const int32_t*)d_block_sums, d_start);
     }
 }
 
-// scatter of both clouds: the cell's count doubles as its cursor -- counting DOWN hands out the slots start + count-1 ..
-// start and leaves the array zeroed for the next build (no cursor array for the scan to write, no memset in between).
+// scatter of both clouds: a point goes to its cell's start + the slot the count handed it (no atomic, no access to the
+// counters: the scan has already zeroed them for the next build).
 // Targets go to `sorted` (.w = original index), sources to `src_tmp` (.w = original index; grid_rank_fix_kernel orders each cell).
 __global__ __launch_bounds__(256) void grid_scatter2_kernel(const float4* __restrict__ tgt, int nt, int nbt, const float4* __restrict__ src, int ns,
-                                                            GridParams gp, int32_t* __restrict__ counts, const int32_t* __restrict__ start,
+                                                            GridParams gp, const int32_t* __restrict__ slot, const int32_t* __restrict__ start,
                                                             float4* __restrict__ sorted, float4* __restrict__ src_tmp) {
     const bool is_src = (int)blockIdx.x >= nbt;
     const int i = ((int)blockIdx.x - (is_src ? nbt : 0)) * 256 + (int)threadIdx.x;
@@ -210,7 +225,7 @@ __global__ __launch_bounds__(256) void grid_scatter2_kernel(const float4* __rest
     const int cx = cell_coord(p.x, gp.ox, gp.inv_h, gp.gx), cy = cell_coord(p.y, gp.oy, gp.inv_h, gp.gy),
               cz = cell_coord(p.z, gp.oz, gp.inv_h, gp.gz);
     const int cell = (is_src ? gp.gx * gp.gy * gp.gz : 0) + (cz * gp.gy + cy) * gp.gx + cx;
-    const int pos = start[cell] + atomicSub(&counts[cell], 1) - 1 - (is_src ? nt : 0);
+    const int pos = start[cell] + slot[(is_src ? nt : 0) + i] - (is_src ? nt : 0);
     p.w = __int_as_float(i);
     (is_src ? src_tmp : sorted)[pos] = p;
 }
@@ -335,6 +350,105 @@ __device__ __forceinline__ int block_walk(const GridParams& gp, const int32_t* _
     return total;
 }
 
+// The same r = 1 step for a query that arrives WITHOUT a candidate (the first pass of a registration, kss_nn: rho = +inf,
+// so block_walk would walk all 9 rows, ~45 points per source at C2).  Two stages: the query's own x-row (t = 4: cells cx-1 ..
+// cx+1 of row (cy, cz), one contiguous range, no queue) is walked first; the best distance d0 found there, grown by the skin
+// as in skip_test, becomes rho, and the other 8 rows are queued under block_walk's rule with it -- most of them, and most
+// end cells of the rest, lie beyond it (~20 evaluations per source at C2).  All 9 bound loads are still issued up front: only
+// the decision which ranges to queue waits for row 4.  An empty own row leaves rho = +inf: block_walk's walk.  m1 / m2 run
+// over both stages (the rows are disjoint: distinct points); rho comes back as the radius that was used, for the caller's
+// bound.  A body of its own, in a kernel of its own: walk bodies inlined into the other kernels cost them 5-20 %.
+#ifndef KSS_FIRST_U1
+#define KSS_FIRST_U1 16   // points in flight for the own row (11 on average at C2: usually one step)
+#endif
+template <bool FMA, int BS, int U>
+__device__ __forceinline__ int block_walk_first(const GridParams& gp, const int32_t* __restrict__ cell_start, const float4* __restrict__ sorted,
+                                                float qx, float qy, float qz, int cx, int cy, int cz, float& rho, float skin,
+                                                int2 (*rowq)[BS], unsigned long long& key, int& kpos, float& m1, float& m2) {
+    constexpr int U1 = KSS_FIRST_U1;
+    int s0[9], s1[9], s2[9], s3[9];
+    bool ok[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const int z = cz + t / 3 - 1, y = cy + t % 3 - 1;
+        ok[t] = z >= 0 && z < gp.gz && y >= 0 && y < gp.gy;
+        const int row = ok[t] ? (z * gp.gy + y) * gp.gx : 0;
+        const int4u v = *(const int4u*)(cell_start + row + cx - 1);
+        s0[t] = cx > 0 ? v.x : v.y;
+        s1[t] = v.y;
+        s2[t] = v.z;
+        s3[t] = cx + 1 < gp.gx ? v.w : v.z;
+    }
+    m1 = __builtin_inff();
+    m2 = __builtin_inff();
+    // ---- stage 1: the own row, [s0, s3) of t = 4 ----
+    const int lo4 = s0[4], n4 = s3[4] - s0[4];
+    for (int e = 0; e < n4; e += U1) {
+        int at[U1];
+        float4 pt[U1];
+#pragma unroll
+        for (int j = 0; j < U1; ++j) at[j] = lo4 + min(e + j, n4 - 1);   // past the end: the last point again (masked below)
+#pragma unroll
+        for (int j = 0; j < U1; ++j) pt[j] = sorted[at[j]];
+#pragma unroll
+        for (int j = 0; j < U1; ++j) {
+            const unsigned long long kk = point_key<FMA>(pt[j], qx, qy, qz);
+            if (kk < key) { key = kk; kpos = at[j]; }
+            const float dd = e + j < n4 ? __uint_as_float((unsigned)(kk >> 32)) : __builtin_inff();
+            m2 = __builtin_amdgcn_fmed3f(m1, m2, dd);
+            m1 = fminf(m1, dd);
+        }
+    }
+    if (rho == __builtin_inff() && key != ~0ull) {   // a first candidate: the radius skip_test gives a walker that has one
+        const float d0 = __uint_as_float((unsigned)(key >> 32));
+        const float grown = __builtin_amdgcn_sqrtf(d0) + fmaxf(skin, 0.f) * gp.h;
+        rho = skin >= 0.f ? fmaxf(d0, grown * grown) : d0;
+    }
+    // ---- stage 2: the other 8 rows under block_walk's rule ----
+    const float exl = fmaxf((qx - (gp.ox + (float)cx * gp.h)) - gp.eps, 0.f), exr = fmaxf(((gp.ox + (float)(cx + 1) * gp.h) - qx) - gp.eps, 0.f);
+    const float eyl = fmaxf((qy - (gp.oy + (float)cy * gp.h)) - gp.eps, 0.f), eyr = fmaxf(((gp.oy + (float)(cy + 1) * gp.h) - qy) - gp.eps, 0.f);
+    const float ezl = fmaxf((qz - (gp.oz + (float)cz * gp.h)) - gp.eps, 0.f), ezr = fmaxf(((gp.oz + (float)(cz + 1) * gp.h) - qz) - gp.eps, 0.f);
+    const float exl2 = exl * exl, exr2 = exr * exr;
+    const float ey2[3] = {eyl * eyl, 0.f, eyr * eyr}, ez2[3] = {ezl * ezl, 0.f, ezr * ezr};
+    int nrow = 0, total = 0;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        if (t == 4) continue;
+        const float g2 = ey2[t % 3] + ez2[t / 3];
+        const bool need = ok[t] && !(rho < g2 * 0.999999f);
+        const bool left = !(rho < (g2 + exl2) * 0.999999f), right = !(rho < (g2 + exr2) * 0.999999f);
+        const int lo = left ? s0[t] : s1[t];
+        const int hi = right ? s3[t] : s2[t];
+        const bool take = need && hi > lo;
+        rowq[min(nrow, 7)][threadIdx.x] = make_int2(lo, hi);
+        nrow += take ? 1 : 0;
+        total += take ? hi - lo : 0;
+    }
+    int cur = 0, end = 0, nxt = 0;
+    if (nrow > 0) { const int2 v = rowq[0][threadIdx.x]; cur = v.x; end = v.y; nxt = 1; }
+    for (int e = 0; e < total; e += U) {
+        int at[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            at[j] = min(cur, end - 1);
+            ++cur;
+            if (cur >= end && nxt < nrow) { const int2 v = rowq[nxt][threadIdx.x]; cur = v.x; end = v.y; ++nxt; }
+        }
+        float4 pt[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) pt[j] = sorted[at[j]];
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const unsigned long long kk = point_key<FMA>(pt[j], qx, qy, qz);
+            if (kk < key) { key = kk; kpos = at[j]; }
+            const float dd = e + j < total ? __uint_as_float((unsigned)(kk >> 32)) : __builtin_inff();
+            m2 = __builtin_amdgcn_fmed3f(m1, m2, dd);
+            m1 = fminf(m1, dd);
+        }
+    }
+    return n4 + total;
+}
+
 // One ROW of the 3x3x3 block per lane -- or two (phase B of the fused pass when a workgroup has few walkers: 16 lanes share
 // a walker and lanes 0-8 of the group take rows 0-8, or 8 lanes share one and lane 0 also takes row 8).  Same pruning rule
 // and the same m1 / m2 bookkeeping as block_walk, but no range queue and -- for the usual <= U points -- a single step: the
@@ -415,15 +529,16 @@ __global__ __launch_bounds__(256) void grid_rank_fix_kernel(const float4* __rest
 }
 
 // Both cell lists of a single pair: count -> scan (2 launches) -> scatter -> rank fix = 5 launches (one pair of lists used to
-// be 10).  d_counts: 2 * ncells zeroed ints (zero at rest: left zeroed again); d_start: 2 * ncells + 1 ints, target starts
-// in [0, ncells], source starts + nt behind; d_src is read and, after the rank fix, rewritten in cell order (d_tmp: scratch).
+// be 10).  d_counts: 2 * ncells zeroed ints (zero at rest: left zeroed again by the scan); d_slot: nt + ns ints; d_start:
+// 2 * ncells + 1 ints, target starts in [0, ncells], source starts + nt behind; d_src is read and, after the rank fix,
+// rewritten in cell order (d_tmp: scratch).
 void launch_grid_build_pair(hipStream_t st, const float4* d_tgt, int nt, float4* d_src, int ns, const GridParams& gp, int32_t* d_counts,
-                            int32_t* d_start, int32_t* d_block_sums, float4* d_sorted, float4* d_tmp) {
+                            int32_t* d_slot, int32_t* d_start, int32_t* d_block_sums, float4* d_sorted, float4* d_tmp) {
     const int ncells = gp.gx * gp.gy * gp.gz;
     const int nbt = (nt + 255) / 256, nbs = (ns + 255) / 256;
-    hipLaunchKernelGGL(grid_count2_kernel, dim3(nbt + nbs), dim3(256), 0, st, d_tgt, nt, nbt, (const float4*)d_src, ns, gp, d_counts);
-    launch_scan(st, d_counts, 2 * ncells, d_start, d_block_sums);
-    hipLaunchKernelGGL(grid_scatter2_kernel, dim3(nbt + nbs), dim3(256), 0, st, d_tgt, nt, nbt, (const float4*)d_src, ns, gp, d_counts,
+    hipLaunchKernelGGL(grid_count2_kernel, dim3(nbt + nbs), dim3(256), 0, st, d_tgt, nt, nbt, (const float4*)d_src, ns, gp, d_counts, d_slot);
+    launch_scan(st, d_counts, 2 * ncells, d_start, d_block_sums, true);
+    hipLaunchKernelGGL(grid_scatter2_kernel, dim3(nbt + nbs), dim3(256), 0, st, d_tgt, nt, nbt, (const float4*)d_src, ns, gp, (const int32_t*)d_slot,
                        (const int32_t*)d_start, d_sorted, d_tmp);
     hipLaunchKernelGGL(grid_rank_fix_kernel, dim3(nbs), dim3(256), 0, st, (const float4*)d_tmp, ns, gp, (const int32_t*)d_start + ncells, nt,
                        d_src);
@@ -511,8 +626,9 @@ __device__ __forceinline__ void wave_row(bool have, bool kept, bool fell_back, f
 
 // Phase B of the fused pass (grid_pass_kernel, gridb_pass_kernel): the first lanes of the workgroup serve the `nwalk`
 // walkers whose lane numbers are in s_wl and whose requests are in their hand-over columns (s_ent), and overwrite every
-// column with the answer.  NT = threads of the workgroup, WQ = columns of the range queue.
-template <bool FMA, bool BATCH, int WQ, int NT, int U>
+// column with the answer.  NT = threads of the workgroup, WQ = columns of the range queue.  FIRST: the first pass of a single
+// pair (no source has a candidate): a walker served by one lane takes the two-stage walk, block_walk_first.
+template <bool FMA, bool BATCH, int WQ, int NT, int U, bool FIRST = false>
 __device__ __forceinline__ void serve_walkers(const PassArgs& a, const GridPairDev& pr, const int32_t* __restrict__ cs,
                                               const float4* __restrict__ sorted, int w, int nwalk, int2 (*rowq)[WQ],
                                               unsigned (*s_ent)[PASS_BS], const unsigned short* s_wl) {
@@ -557,6 +673,7 @@ __device__ __forceinline__ void serve_walkers(const PassArgs& a, const GridPairD
             float m1, m2;
             if (row16) row_walk<FMA, U, false>(gp, cs, sorted, wx, wy, wz, cx, cy, cz, wrho, sub < 9 ? sub : -1, -1, wkey, wpos, m1, m2);
             else if (BATCH && row8) row_walk<FMA, U, true>(gp, cs, sorted, wx, wy, wz, cx, cy, cz, wrho, sub, sub == 0 ? 8 : -1, wkey, wpos, m1, m2);
+            else if (FIRST && L == 1) evl = block_walk_first<FMA, WQ, U>(gp, cs, sorted, wx, wy, wz, cx, cy, cz, wrho, a.skin, rowq, wkey, wpos, m1, m2);   // (wrho: the radius it used)
             else evl = block_walk<FMA, WQ, U>(gp, cs, sorted, wx, wy, wz, cx, cy, cz, wrho, rowmask, rowq, wkey, wpos, m1, m2);
             if (L > 1) {   // (uniform) all lanes of a group are walkers of the same source: merge by DPP
 #define KSS_GROUP_MERGE(X)                                                                                                          \
@@ -701,9 +818,12 @@ do {                                                                            
 #ifndef KSS_SINGLE_WAVES
 #define KSS_SINGLE_WAVES 1
 #endif
-template <bool FMA, bool FULL, bool BATCH, bool SEARCH, bool CHAIN>
+// FIRST: the first pass of a single pair (PassArgs::use_prev == 0: the first pass of a registration, kss_nn), an instantiation
+// of its own that the profilers list apart.
+template <bool FMA, bool FULL, bool BATCH, bool SEARCH, bool CHAIN, bool FIRST = false>
 __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES) void grid_pass_kernel(const PassArgs a) {
     static_assert(!CHAIN || (!BATCH && SEARCH), "chained launches: single pair, search passes");
+    static_assert(!FIRST || (!BATCH && SEARCH && !CHAIN), "the first pass: single pair, a plain search launch");
     // diagnostic stamps (100 MHz s_memrealtime): [block*16 + {0 start, 13 first loads in, 9 gate open, 14 phase A done,
     // 5 phase B entered, 8 answered, 15 phase B done, 1 searched, 2 row ready, 3 row handed over, 4 result stored
     // (reducer)}]; counts: 10 = distance evaluations of the r = 1 block, 11 = evaluation slots, 12 = walkers
@@ -724,7 +844,9 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
     const GridParams& gp = pr.gp;
     const int32_t* __restrict__ cs = a.cell_start + pr.cell_base;
     const float4* __restrict__ sorted = a.sorted;
-    constexpr int WQ = 256;                // lanes that search in phase B
+    // lanes that search in phase B.  The first pass, in which every source searches, serves a whole workgroup in one round
+    // (36 KB of queue: it runs at one workgroup per compute unit anyway); afterwards a few per cent of the sources walk
+    constexpr int WQ = FIRST ? BS : 256;
     __shared__ int2 rowq[9][WQ];           // block_walk's per-lane queue of point ranges
     __shared__ double shw[BS / 64][NSUMS];
     __shared__ int s_last;
@@ -916,7 +1038,7 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
         __syncthreads();
         const int nwalk = s_nwalk;
         if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + 12] = (unsigned long long)nwalk;
-        serve_walkers<FMA, BATCH, WQ, BS, BATCH ? 4 : 8>(a, pr, cs, sorted, w, nwalk, rowq, s_ent, s_wl);
+        serve_walkers<FMA, BATCH, WQ, BS, BATCH ? 4 : 8, FIRST>(a, pr, cs, sorted, w, nwalk, rowq, s_ent, s_wl);
         KSS_STAMP(15);
         __syncthreads();
         // Phase C: every lane reads its column
@@ -1277,7 +1399,7 @@ void launch_gridb_build_targets(hipStream_t st, const float4* d_tgt, int total_t
     // d_counts: zero at rest (kss_ctx.hpp); the count-down scatters below leave it zeroed again
     const dim3 grid((total_tgt_pad + 255) / 256), block(256);
     hipLaunchKernelGGL((gridb_bin_kernel<false, false>), grid, block, 0, st, d_tgt, total_tgt_pad, d_pairs, npairs, d_counts, (const int32_t*)nullptr, (float4*)nullptr);
-    launch_scan(st, d_counts, total_cells, d_start, d_block_sums);
+    launch_scan(st, d_counts, total_cells, d_start, d_block_sums, false);
     hipLaunchKernelGGL((gridb_bin_kernel<true, false>), grid, block, 0, st, d_tgt, total_tgt_pad, d_pairs, npairs, d_counts, (const int32_t*)d_start, d_sorted);
 }
 
@@ -1287,7 +1409,7 @@ void launch_gridb_sort_sources(hipStream_t st, const float4* d_src, int total_sr
                                int total_cells, int32_t* d_counts, int32_t* d_start, int32_t* d_block_sums, float4* d_tmp, float4* d_out) {
     const dim3 grid((total_src + 255) / 256), block(256);
     hipLaunchKernelGGL((gridb_bin_kernel<false, true>), grid, block, 0, st, d_src, total_src, d_pairs, npairs, d_counts, (const int32_t*)nullptr, (float4*)nullptr);
-    launch_scan(st, d_counts, total_cells, d_start, d_block_sums);
+    launch_scan(st, d_counts, total_cells, d_start, d_block_sums, false);
     hipLaunchKernelGGL((gridb_bin_kernel<true, true>), grid, block, 0, st, d_src, total_src, d_pairs, npairs, d_counts, (const int32_t*)d_start, d_tmp);
     hipLaunchKernelGGL(gridb_rank_fix_kernel, grid, block, 0, st, d_tmp, total_src, d_pairs, npairs, d_start, d_out);
 }
@@ -1516,6 +1638,7 @@ int grid_pass_blocks(int total_rows) { return (total_rows + 7) / 8 * 8; }   // m
 void launch_grid_pass(hipStream_t st, bool fma, bool full, bool batch, bool search, const PassArgs& a) {
     if (a.total_rows <= 0) return;
     const dim3 grid(grid_pass_blocks(a.total_rows)), block(PASS_BS);
+    static const bool first_pass = getenv("KSS_FIRST_PASS") == nullptr || atoi(getenv("KSS_FIRST_PASS")) != 0;   // A/B: 0 = the plain pass first as well (same bits)
 #define KSS_PASS(F, U, B, S) hipLaunchKernelGGL((grid_pass_kernel<F, U, B, S, false>), grid, block, 0, st, a)
 #define KSS_CHAIN(F, U) hipLaunchKernelGGL((grid_pass_kernel<F, U, false, true, true>), grid, block, 0, st, a)
     if (!search) {   // sums-only relaunch after the list pass: single pair, all 20 sums
@@ -1543,6 +1666,11 @@ void launch_grid_pass(hipStream_t st, bool fma, bool full, bool batch, bool sear
     } else if (a.chain_len > 1) {
         if (fma) { if (full) KSS_CHAIN(true, true); else KSS_CHAIN(true, false); }
         else     { if (full) KSS_CHAIN(false, true); else KSS_CHAIN(false, false); }
+    } else if (first_pass && !a.use_prev) {   // no source has a candidate: the two-stage walk, one round
+#define KSS_FIRST(F, U) hipLaunchKernelGGL((grid_pass_kernel<F, U, false, true, false, true>), grid, block, 0, st, a)
+        if (fma) { if (full) KSS_FIRST(true, true); else KSS_FIRST(true, false); }
+        else     { if (full) KSS_FIRST(false, true); else KSS_FIRST(false, false); }
+#undef KSS_FIRST
     } else {
         if (fma) { if (full) KSS_PASS(true, true, false, true); else KSS_PASS(true, false, false, true); }
         else     { if (full) KSS_PASS(false, true, false, true); else KSS_PASS(false, false, false, true); }

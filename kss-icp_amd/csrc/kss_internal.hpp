@@ -240,7 +240,7 @@ void launch_nn_sweep_list(hipStream_t st, int S, bool fma, const NNWork* d_work,
                           unsigned long long* d_keys, const int32_t* d_list, const int32_t* d_count);
 // both cell lists of a single pair (count -> scan -> scatter -> rank fix, shared launches)
 void launch_grid_build_pair(hipStream_t st, const float4* d_tgt, int nt, float4* d_src, int ns, const GridParams& gp, int32_t* d_counts,
-                            int32_t* d_start, int32_t* d_block_sums, float4* d_sorted, float4* d_tmp);
+                            int32_t* d_slot, int32_t* d_start, int32_t* d_block_sums, float4* d_sorted, float4* d_tmp);
 size_t scan_scratch_bytes(int n);   // scratch of the cell-count scan over n cells
 int grid_pass_blocks(int total_rows);
 void launch_grid_pass(hipStream_t st, bool fma, bool full, bool batch, bool search, const PassArgs& a);
