@@ -519,8 +519,8 @@ int kss_icp_gicp_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *
  * the twelve entries rounded to float, last row 0 0 0 1: p -> H (H p + c t), the paper's R p + t ~ R^-1 q.
  * The loop around it is kss_icp_p2l's: fewer than min_correspondences kept -> KSS_STATE_NO_CORRESPONDENCES, PCL's criteria on
  * MSE = [28] / [0], fitness over ALL sources, p->allreduce must be NULL.  KSS_ERR_ARG: everything kss_icp_gicp refuses, and
- * align_normals outside {0, 1}.  The batched form, robust or trimmed weights on top, the C++ mirror classes and the CLI do not
- * have this metric. */
+ * align_normals outside {0, 1}.  Many pairs per call: kss_icp_symm_batch below.  Robust or trimmed weights on top, the C++ mirror
+ * classes and the CLI do not have this metric. */
 typedef struct {
     int normals_k;      /* 20: read only when a set of normals is NULL; 3..64 */
     int align_normals;  /* 1: n = nq - m where m . nq < 0;  0: always n = nq + m */
@@ -543,6 +543,27 @@ int kss_icp_symm(kss_ctx *ctx, const float *src, int64_t ns, const float *src_no
                  const float *tgt_normals, const kss_icp_params *p, const kss_symm_params *sp, kss_icp_result *res);
 int kss_icp_symm_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const float *d_tgt, int64_t nt,
                      const float *d_tgt_normals, const kss_icp_params *p, const kss_symm_params *sp, kss_icp_result *res);
+
+/* ---- symmetric ICP for MANY pairs per call ----
+ * Arguments as kss_icp_gicp_batch: packed float[n][3] clouds and npairs + 1 HOST offsets in points (the _dev form takes device clouds
+ * and normals; the offsets and aligns stay host arrays).  src_normals_all is laid out like src_all, tgt_normals_all like tgt_all;
+ * either may be NULL: then each cloud's normals are computed as kss_icp_symm computes them, per cloud, at sp->normals_k from the
+ * cloud as passed in.  aligns: one int32 per pair, 0 or 1, the pair's align_normals, or NULL for sp->align_normals everywhere.
+ * Nothing is redefined: the definition at kss_icp_symm holds for every pair -- R_F is the rotation block of the PAIR's own
+ * accumulated transform, pass by pass -- and every pair's record -- T, iterations, state, converged, last_mse, pair 0's trace_* -- is
+ * the single-pair call's BIT FOR BIT (fitness: within 2 ns 2^-53 relative, the NN engine's own summation order), in any batch order
+ * and any split over calls, under every NN engine and tuning knob; results[i].pair_id = i.  Offsets whose first entry is not 0
+ * address a sub-range of the packed arrays.  The pairs run in lockstep, one small table copy and two launches per pass behind the
+ * NN pass whatever the pair count; a pair that ends -- converged, KSS_STATE_NO_CORRESPONDENCES, KSS_STATE_DEGENERATE -- leaves the
+ * others untouched.  trace_* and fitness_idx / fitness_d2 describe pair 0.  KSS_ERR_ARG: NULL ctx (refused before anything touches
+ * the device), offsets, sp or results; npairs <= 0; an empty pair; a set allreduce; sp->align_normals or an aligns entry other
+ * than 0 or 1; normals_k outside 3..64 where a set of normals has to be computed; everything kss_icp_p2l_batch refuses. */
+int kss_icp_symm_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *src_normals_all,
+                       const float *tgt_all, const int64_t *tgt_off, const float *tgt_normals_all, int npairs,
+                       const kss_icp_params *p, const kss_symm_params *sp, const int32_t *aligns, kss_icp_result *results);
+int kss_icp_symm_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_src_normals_all,
+                           const float *d_tgt_all, const int64_t *tgt_off, const float *d_tgt_normals_all, int npairs,
+                           const kss_icp_params *p, const kss_symm_params *sp, const int32_t *aligns, kss_icp_result *results);
 
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);

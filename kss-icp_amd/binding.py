@@ -42,6 +42,7 @@ SYMBOLS = [
     "kss_gicp_default_params", "kss_gicp_metric", "kss_gicp_sums", "kss_gicp_sums_dev", "kss_icp_gicp", "kss_icp_gicp_dev",
     "kss_icp_gicp_batch", "kss_icp_gicp_batch_dev",
     "kss_symm_default_params", "kss_rigid_from_symm_sums", "kss_symm_sums", "kss_symm_sums_dev", "kss_icp_symm", "kss_icp_symm_dev",
+    "kss_icp_symm_batch", "kss_icp_symm_batch_dev",
 ]
 
 
@@ -192,6 +193,8 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, i64, vp, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(SymmParams), C.POINTER(IcpResult)]
     for n in ("kss_icp_gicp_batch", "kss_icp_gicp_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(GicpParams), vp, vp]
+    for n in ("kss_icp_symm_batch", "kss_icp_symm_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(SymmParams), vp, vp]
     for n in ("kss_trim_threshold_batch", "kss_trim_threshold_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, C.c_int, dbl, vp, vp]
     for n in ("kss_rotation_search", "kss_rotation_search_dev"):
@@ -1045,6 +1048,51 @@ class Context:
                                                       C.c_void_p(int(d_tgt_normals_all)) if d_tgt_normals_all else None, npairs,
                                                       C.byref(p), C.byref(gp), _p(ep), res),
             "kss_icp_gicp_batch_dev", p, so, P2L_NSUMS, trace_cap, False)
+
+    # ---- symmetric ICP, many pairs per call
+    @staticmethod
+    def _aligns(aligns, npairs):
+        if aligns is None:
+            return None
+        al = np.ascontiguousarray(aligns, dtype=np.int32).reshape(-1)
+        if len(al) != npairs:
+            raise ValueError("aligns must hold one entry per pair")
+        return al
+
+    def icp_symm_batch(self, src_all, src_off, tgt_all, tgt_off, src_normals_all=None, tgt_normals_all=None, aligns=None, sp=None,
+                       params=None, trace_cap=0, fitness_corr=False):
+        """kss_icp_symm_batch: symmetric ICP of npairs pairs in one call (packed clouds, npairs + 1 offsets in points; the normals
+        laid out like their clouds, either None to have them computed per cloud at sp.normals_k).  aligns: one align_normals (0 or
+        1) per pair, or None for sp.align_normals everywhere.  Returns (list of IcpResult, dictionary with pair 0's trace_sums /
+        trace_Tk / fitness_idx / fitness_d2 where asked for)."""
+        sp = sp if sp is not None else symm_params()
+        s, t = _f32(src_all), _f32(tgt_all)
+        sn, tn = self._gicp_normals(src_normals_all, len(s), "source"), self._gicp_normals(tgt_normals_all, len(t), "target")
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        al = self._aligns(aligns, npairs)
+        p = params if params is not None else self.icp_params()
+        return self._batch_call(
+            lambda res: self.L.kss_icp_symm_batch(self.h, _p(s), _p(so), _p(sn), _p(t), _p(to), _p(tn), npairs, C.byref(p), C.byref(sp),
+                                                  _p(al), res),
+            "kss_icp_symm_batch", p, so, P2L_NSUMS, trace_cap, fitness_corr)
+
+    def icp_symm_batch_dev(self, d_src_all, src_off, d_src_normals_all, d_tgt_all, tgt_off, d_tgt_normals_all, params=None, aligns=None,
+                           sp=None, trace_cap=0):
+        """kss_icp_symm_batch_dev on device pointers (either normals pointer may be 0 / None; the offsets and aligns stay host
+        arrays).  Returns (list of IcpResult, dictionary with pair 0's trace_sums / trace_Tk where asked for)."""
+        sp = sp if sp is not None else symm_params()
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        al = self._aligns(aligns, npairs)
+        p = params if params is not None else self.icp_params()
+        return self._batch_call(
+            lambda res: self.L.kss_icp_symm_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so),
+                                                      C.c_void_p(int(d_src_normals_all)) if d_src_normals_all else None,
+                                                      C.c_void_p(int(d_tgt_all)), _p(to),
+                                                      C.c_void_p(int(d_tgt_normals_all)) if d_tgt_normals_all else None, npairs,
+                                                      C.byref(p), C.byref(sp), _p(al), res),
+            "kss_icp_symm_batch_dev", p, so, P2L_NSUMS, trace_cap, False)
 
     def trim_threshold_batch(self, d2_all, off, overlaps, max_d2=1.0):
         """kss_trim_threshold_batch: {m, k, tau, kept} of every segment [off[i], off[i + 1]) of d2_all, nseg x TRIM_NINFO."""

@@ -953,7 +953,7 @@ int kss_icp_symm(kss_ctx* c, const float* src, int64_t ns, const float* src_norm
 // ---- the same for many pairs per call ------------------------------------------------
 // Every cloud's normals where the caller gave none: cloud_normals_dev at k, cloud after cloud (off: npairs + 1 offsets in points
 // from 0), into the packed buffer `out` laid out like the clouds (setup cost of the call, not optimised: a k-NN and a normals
-// launch per cloud).  The targets' go to pb_nrm at k = 20 (the plane metric) or normals_k (generalized), the sources' to pb_snrm.
+// launch per cloud).  The targets' go to pb_nrm at k = 20 (the plane metric) or normals_k (generalized, symmetric), the sources' to pb_snrm.
 static int batch_normals_dev(kss_ctx* c, const float* d_pts, const int64_t* off, int npairs, int k, DevBuf& out, const float** d_nrm) {
     KCHK(ensure(c, out, (size_t)off[npairs] * 3 * sizeof(float)));
     for (int i = 0; i < npairs; ++i) {
@@ -1141,6 +1141,62 @@ int kss_icp_gicp_batch(kss_ctx* c, const float* src, const int64_t* src_off, con
     return kss_icp_gicp_batch_dev(c, (const float*)c->stage_src.p, so.data(), src_normals ? (const float*)c->pb_snrm.p : nullptr,
                                   (const float*)c->stage_tgt.p, to.data(), tgt_normals ? (const float*)c->pb_nrm.p : nullptr, npairs, p, gp,
                                   epsilons, results);
+}
+
+// ---- symmetric ICP for many pairs per call -------------------------------------------
+// what the two entry points share: sp, allreduce, the per-pair aligns (null: sp->align_normals everywhere) and pair_check
+static int symm_batch_check(kss_ctx* c, const void* src, const float* snrm, const void* tgt, const float* tnrm, const int64_t* src_off,
+                            const int64_t* tgt_off, int npairs, const kss_icp_params* p, const kss_symm_params* sp, const int32_t* aligns,
+                            const kss_icp_result* results) {
+    KCHK(symm_check(c, "icp_symm_batch", sp, !snrm || !tnrm));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm_batch: the source-row split (allreduce) is not available for symmetric ICP");
+    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_symm_batch: bad batch");
+    if (aligns)
+        for (int i = 0; i < npairs; ++i)
+            if (aligns[i] != 0 && aligns[i] != 1) return set_err(c, KSS_ERR_ARG, "icp_symm_batch: every align must be 0 or 1");
+    return pair_check(c, "icp_symm_batch", false, src, tgt, 0, 0, tnrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr);
+}
+
+int kss_icp_symm_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
+                           const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
+                           const kss_symm_params* sp, const int32_t* aligns, kss_icp_result* results) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_batch_check(c, d_src, d_src_normals, d_tgt, d_tgt_normals, src_off, tgt_off, npairs, p, sp, aligns, results));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);   // rebased to the first pair, as in kss_icp_gicp_batch_dev
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
+    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
+    if (d_src_normals) d_src_normals += 3 * src_off[0];
+    if (d_tgt_normals) d_tgt_normals += 3 * tgt_off[0];
+    // each cloud's normals where the caller gave none, as kss_icp_symm computes them: from the cloud as passed in, at normals_k
+    if (!d_tgt_normals) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, sp->normals_k, c->pb_nrm, &d_tgt_normals));
+    if (!d_src_normals) KCHK(batch_normals_dev(c, d_src, so.data(), npairs, sp->normals_k, c->pb_snrm, &d_src_normals));
+    PairMode mode;
+    mode.plane = true;
+    mode.symm = true;
+    mode.d_src_nrm = d_src_normals;
+    std::vector<int32_t> al((size_t)npairs, sp->align_normals);
+    if (aligns) al.assign(aligns, aligns + npairs);
+    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_tgt_normals, npairs, p, mode, nullptr, results, nullptr, nullptr, nullptr,
+                         al.data());
+}
+
+int kss_icp_symm_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
+                       const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_symm_params* sp,
+                       const int32_t* aligns, kss_icp_result* results) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_batch_check(c, src, src_normals, tgt, tgt_normals, src_off, tgt_off, npairs, p, sp, aligns, results));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
+    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->pb_snrm, src_normals + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->pb_nrm, tgt_normals + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
+    return kss_icp_symm_batch_dev(c, (const float*)c->stage_src.p, so.data(), src_normals ? (const float*)c->pb_snrm.p : nullptr,
+                                  (const float*)c->stage_tgt.p, to.data(), tgt_normals ? (const float*)c->pb_nrm.p : nullptr, npairs, p, sp,
+                                  aligns, results);
 }
 
 static int trim_batch_check(kss_ctx* c, const float* d2, const int64_t* off, int nseg, const double* overlaps, const double* info_all) {

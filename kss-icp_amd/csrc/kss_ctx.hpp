@@ -63,7 +63,8 @@ struct kss_ctx {
     // robust ICP for many pairs: one RobustScale per pair, uploaded once per call
     DevBuf pb_rscale;
     // generalized ICP for many pairs: the packed source normals (staged or computed), and the per-pair GicpPass
-    // table: the host writes the pinned copy after every host step, one copy per pass takes it to the device table
+    // table: the host writes the pinned copy after every host step, one copy per pass takes it to the device table.  Symmetric ICP
+    // for many pairs (2.18) uses all of them, with a table of SymmPass: byte buffers sized per call, a call is one or the other
     DevBuf pb_snrm, pb_gicp;
     void* h_gicp = nullptr; size_t h_gicp_cap = 0;
     void* h_gicp_dev = nullptr;   // (the pinned copy as the device sees it: KSS_GICP_TABLE_MAPPED, an A/B switch)
@@ -273,13 +274,15 @@ static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both in
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                  const kss_icp_params* p, const PairMode& mode, kss_icp_result* res);
 int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info);
-// npairs >= 1 pairs in lockstep (kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch, kss_icp_gicp_batch): d_nrm laid
+// npairs >= 1 pairs in lockstep (kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch, kss_icp_gicp_batch,
+// kss_icp_symm_batch): d_nrm laid
 // out like d_tgt; overlaps: one per pair (trimmed; M.overlap is not read); rscales: one per pair (robust; M.rs is not read), all
 // with the loss of the batch; info_all: npairs * KSS_TRIM_NINFO or null; M.trace_info / M.last_info: pair 0's / unused;
-// gicp_eps: one epsilon per pair (generalized; M.gicp_epsilon is not read), M.d_src_nrm laid out like d_src
+// gicp_eps: one epsilon per pair (generalized; M.gicp_epsilon is not read), M.d_src_nrm laid out like d_src;
+// symm_aligns: one align_normals per pair (symmetric; M.symm_align is not read), M.d_src_nrm as for generalized
 int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, const float* d_nrm,
                   int npairs, const kss_icp_params* p, const PairMode& mode, const double* overlaps, kss_icp_result* results, double* info_all,
-                  const RobustScale* rscales = nullptr, const double* gicp_eps = nullptr);
+                  const RobustScale* rscales = nullptr, const double* gicp_eps = nullptr, const int32_t* symm_aligns = nullptr);
 // the selection alone for nseg segments of d_d2 in one launch
 int trim_threshold_batch_dev(kss_ctx* c, const float* d_d2, const int64_t* off, int nseg, double max_d2, const double* overlaps, double* info_all);
 // host-mapped {value, sequence number} result slots: allocate them; wait for the first nslots of launch c->seq

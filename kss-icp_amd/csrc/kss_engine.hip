@@ -2044,7 +2044,8 @@ int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, 
 
 // ---- the same metrics for MANY pairs per call: kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch
 // (2.13: behind the NN pass the key launch (plane) and the selection when any pair has the automatic scale, then two sums launches),
-// kss_icp_gicp_batch (2.15: one copy of the per-pair pass table -- the rotation of every pair's fin and its e -- then two sums launches) ----
+// kss_icp_gicp_batch (2.15: one copy of the per-pair pass table -- the rotation of every pair's fin and its e -- then two sums launches),
+// kss_icp_symm_batch (2.18: the same with the table of SymmPass -- the rotation and the pair's align_normals) ----
 // pair_loop in lockstep over npairs >= 1 pairs.  Per pass: ONE NN pass over the pairs still active (idx / d2 by global source
 // index), ONE selection launch when trimmed, TWO sums launches (kss_pairb.hip), ONE stream synchronisation, then
 // pair_host_step for every active pair (the host pool from 64 pairs up, each pair on exactly one thread).  A pair that ends
@@ -2068,6 +2069,16 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     const char* env_mapped = hgp ? getenv("KSS_GICP_TABLE_MAPPED") : nullptr;
     const bool gicp_mapped = env_mapped && atoi(env_mapped) != 0 && c->h_gicp_dev;
     const GicpPass* d_gpass = hgp ? (gicp_mapped ? (const GicpPass*)c->h_gicp_dev : (const GicpPass*)c->pb_gicp.p) : nullptr;
+    // symmetric: every pair's SymmPass in the same pinned and device buffers (a call is either generalized or
+    // symmetric; align staged by pairs_run_dev), the same rotation bits, the same copy per pass and the same A/B switch
+    SymmPass* hsp = M.symm ? (SymmPass*)c->h_gicp : nullptr;
+    auto symm_rot_of = [](SymmPass& g, const float* F) {
+        const float R[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
+        std::memcpy(g.r, R, sizeof R);
+    };
+    const char* env_smapped = hsp ? getenv("KSS_GICP_TABLE_MAPPED") : nullptr;
+    const bool symm_mapped = env_smapped && atoi(env_smapped) != 0 && c->h_gicp_dev;
+    const SymmPass* d_spass = hsp ? (symm_mapped ? (const SymmPass*)c->h_gicp_dev : (const SymmPass*)c->pb_gicp.p) : nullptr;
     const IcpPlan* plan = &pl_in;   // may change to the brute-force plan below
     IcpPlan brute_plan;
     std::vector<PairTrack> tr((size_t)np, PairTrack(P));
@@ -2080,6 +2091,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
         set_state(hs[p], I, 1, 0);
         mirror_state(bar, p, hs[p]);
         if (hgp) gicp_rot_of(hgp[p], tr[p].fin);
+        if (hsp) symm_rot_of(hsp[p], tr[p].fin);
     }
     const double max_d2 = P.max_corr_dist * P.max_corr_dist;
     int32_t* d_idx = (int32_t*)c->p2l_idx.p;
@@ -2125,6 +2137,11 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                     HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hgp, (size_t)np * sizeof(GicpPass), hipMemcpyHostToDevice, c->stream));
                 launch_pairb_gicp_sums(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
                                        d_state, d_gpass, max_d2, (double*)c->p2l_rows.p, d_rec);
+            } else if (M.symm) {   // the same ordering of the host steps' writes behind the last pass's copy
+                if (!symm_mapped)
+                    HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hsp, (size_t)np * sizeof(SymmPass), hipMemcpyHostToDevice, c->stream));
+                launch_pairb_symm_sums(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
+                                       d_state, d_spass, max_d2, (double*)c->p2l_rows.p, d_rec);
             } else {
                 if (M.trimmed) launch_pairb_select(c->stream, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
                 launch_pairb_sums(c->stream, M.plane, M.trimmed, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
@@ -2156,6 +2173,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                     set_state(hs[p], I, 0, 0);
                 }
                 if (hgp) gicp_rot_of(hgp[p], tr[p].fin);   // the source normals turn with the transform accumulated so far
+                if (hsp) symm_rot_of(hsp[p], tr[p].fin);   // (the float bits pair_loop passes as Rn)
                 mirror_state(bar, p, hs[p]);
             }
             finished.fetch_add(fin_here, std::memory_order_relaxed);
@@ -2206,13 +2224,14 @@ static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows
 // (the arguments are the entry points' to check: kss_api.hip)
 int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, const float* d_nrm,
                   int npairs, const kss_icp_params* p, const PairMode& M, const double* overlaps, kss_icp_result* results, double* info_all,
-                  const RobustScale* rscales, const double* gicp_eps) {
+                  const RobustScale* rscales, const double* gicp_eps, const int32_t* symm_aligns) {
     if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: the untrimmed point metric is kss_icp_batch's");
     if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: trimmed and robust exclude each other");
     if (M.robust && !rscales) return set_err(c, KSS_ERR_ARG, "pairs_run: robust needs the per-pair scales");
     if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm || !gicp_eps))
         return set_err(c, KSS_ERR_ARG, "pairs_run: generalized ICP is the plane record with both clouds' normals and the per-pair epsilons, neither trimmed nor robust");
-    if (M.symm) return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP has no batched form");
+    if (M.symm && (!M.plane || M.trimmed || M.robust || M.gicp || !M.d_src_nrm || !d_nrm || !symm_aligns))
+        return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP is the plane record with both clouds' normals and the per-pair aligns, neither trimmed, robust nor generalized");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> ns(npairs), nt(npairs);
     for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }
@@ -2229,7 +2248,7 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         PairbDesc& d = desc[i];
         d.src_base = pl.g[i].src_base; d.ns = ns[i];
         // (the source normals are packed like the caller's sources and read by src_base + i)
-        if (M.gicp && d.src_base != src_off[i]) return set_err(c, KSS_ERR_ARG, "pairs_run: the plan's source segments are not the caller's offsets");
+        if ((M.gicp || M.symm) && d.src_base != src_off[i]) return set_err(c, KSS_ERR_ARG, "pairs_run: the plan's source segments are not the caller's offsets");
         d.tgt_off = tgt_off[i]; d.nt = nt[i];
         d.overlap = M.trimmed ? overlaps[i] : 1.0;
         d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(ns[i]);
@@ -2255,6 +2274,14 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         GicpPass* hgp = (GicpPass*)c->h_gicp;
         std::memset(hgp, 0, (size_t)npairs * sizeof(GicpPass));
         for (int i = 0; i < npairs; ++i) hgp[i].e = 1.0 - gicp_eps[i];
+    }
+    if (M.symm) {   // the per-pair pass table in the generalized form's buffers: align as launch_symm_sums takes it; pairs_loop fills the rotations
+        KCHK(ensure(c, c->pb_gicp, (size_t)npairs * sizeof(SymmPass)));
+        KCHK(ensure_pinned(c, c->h_gicp, c->h_gicp_cap, (size_t)npairs * sizeof(SymmPass)));
+        HIPCHK(c, hipHostGetDevicePointer(&c->h_gicp_dev, c->h_gicp, 0));
+        SymmPass* hsp = (SymmPass*)c->h_gicp;
+        std::memset(hsp, 0, (size_t)npairs * sizeof(SymmPass));
+        for (int i = 0; i < npairs; ++i) hsp[i].align = symm_aligns[i];
     }
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
     KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));

@@ -449,6 +449,22 @@ void launch_pairb_gicp_sums(hipStream_t st, const float4* d_src4, const int32_t*
                             int total_rows, int npairs, const PairState* d_state, const GicpPass* d_pass, double max_d2, double* d_rows,
                             double* d_out);
 
+// ---- symmetric ICP for many pairs per call (kss_pairb.hip) ----
+// what one pass of one pair needs beyond its descriptor: the rotation block of the transform accumulated so far (row-major, the
+// float bits launch_symm_sums takes as Rn) and the pair's align_normals.  One entry per pair; the host rewrites the rotation
+// before every pass, the align is staged once per call.  The table travels as GicpPass does (the same pinned and device buffers).
+struct SymmPass {
+    float r[9];
+    int32_t align;
+};
+static_assert(sizeof(SymmPass) == 40, "the host and the device table share this layout");
+// two launches: every active pair's record into d_out[pair * KSS_P2L_NSUMS].  d_sn3: the source normals packed like the
+// sources (by global original index); d_pass: one SymmPass per pair (device memory, as of this pass)
+void launch_pairb_symm_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                            const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
+                            int total_rows, int npairs, const PairState* d_state, const SymmPass* d_pass, double max_d2, double* d_rows,
+                            double* d_out);
+
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,
                 const std::function<void*(size_t)>& scratch);

@@ -2,7 +2,7 @@
 // ones (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
 //   gicp_source                      the same for generalized ICP (kss_gicp.hip; in a batch: pairb_gicp_rows_kernel),
-//   symm_source                      the same for symmetric ICP (single pair only: kss_symm.hip),
+//   symm_source                      the same for symmetric ICP (kss_symm.hip; in a batch: pairb_symm_rows_kernel),
 //   p2l_rows_column_sum              the fixed-order column sums of the plane metric's rows,
 //   trim_key / trim_resolve_counts   the candidate test and the resolution of one radix digit from a lane's eight bin counts.
 // A pair's bits are the same alone and inside a batch because both forms run these bodies in the same order.

@@ -31,6 +31,13 @@
 //                                GicpPass that the host rewrites before every pass.  The source normals are packed like the
 //                                sources and read by global original index.
 //   pairb_final_kernel<true>     unchanged.
+//
+// Symmetric ICP for many pairs: the same two launches, the table's transport shared with the generalized form.
+//   pairb_symm_rows_kernel       pairb_rows_kernel's grid on symm_source (kss_pair_device.hpp); the rotation applied to the source
+//                                normals and align_normals are the PAIR's, read once per workgroup from a per-pair table of
+//                                SymmPass whose rotations the host rewrites before every pass.  The source normals are packed
+//                                like the sources and read by global original index.
+//   pairb_final_kernel<true>     unchanged.
 #pragma clang fp contract(off)
 
 #include "kss_robust_device.hpp"
@@ -179,6 +186,36 @@ __global__ __launch_bounds__(P2L_THREADS) void pairb_gicp_rows_kernel(const floa
     if (threadIdx.x < P2L_NSUMS) rows[(int64_t)blockIdx.x * P2L_NSUMS + threadIdx.x] = r;
 }
 
+// ---- symmetric ICP (kss_symm.hip's kernel, per pair) ------------------------------------------------------------------------
+// pass[p] as above: one uniform load per workgroup
+template <bool PERM>
+__global__ __launch_bounds__(P2L_THREADS) void pairb_symm_rows_kernel(const float4* __restrict__ src4, const int32_t* __restrict__ perm,
+                                                                      const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
+                                                                      const float* __restrict__ sn_all, const float* __restrict__ tgt_all,
+                                                                      const float* __restrict__ nrm_all, const PairbDesc* __restrict__ desc,
+                                                                      const int32_t* __restrict__ row_pair, const PairState* __restrict__ state,
+                                                                      const SymmPass* __restrict__ pass, double max_d2,
+                                                                      double* __restrict__ rows) {
+    __shared__ double sh[P2L_THREADS / 64][P2L_NSUMS];
+    const int p = row_pair[blockIdx.x];
+    if (!pairb_active(state, p)) return;
+    const PairbDesc d = desc[p];
+    const SymmPass sp = pass[p];
+    GicpRot Rn;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rn.r[k] = sp.r[k];
+    double acc[P2L_NSUMS];
+#pragma unroll
+    for (int c = 0; c < P2L_NSUMS; ++c) acc[c] = 0.0;
+    const float* tgt = tgt_all + 3 * d.tgt_off;
+    const float* nrm = nrm_all + 3 * d.tgt_off;
+    const int64_t step = (int64_t)d.nrows * P2L_THREADS;
+    for (int64_t i = (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x; i < d.ns; i += step)
+        symm_source<PERM ? SRC_F4_PERM : SRC_F4>(acc, nullptr, src4, perm, idx, d2_in, sn_all, tgt, nrm, d.src_base + i, d.nt, max_d2, Rn, sp.align);
+    const double r = block_sum<P2L_NSUMS>(acc, sh);
+    if (threadIdx.x < P2L_NSUMS) rows[(int64_t)blockIdx.x * P2L_NSUMS + threadIdx.x] = r;
+}
+
 // ---- robust ICP (kss_robust.hip's kernels, per pair) ------------------------------------------------------------------------
 __device__ __forceinline__ bool pairb_robust_selects(const PairState* __restrict__ state, const RobustScale* __restrict__ rs, int p) {
     return pairb_active(state, p) && rs[p].autoscale != 0;
@@ -322,6 +359,18 @@ void launch_pairb_gicp_sums(hipStream_t st, const float4* d_src4, const int32_t*
         hipLaunchKernelGGL(pairb_gicp_rows_kernel<true>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_pass, max_d2, d_rows);
     else
         hipLaunchKernelGGL(pairb_gicp_rows_kernel<false>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_pass, max_d2, d_rows);
+    hipLaunchKernelGGL(pairb_final_kernel<true>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_out);
+}
+
+void launch_pairb_symm_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                            const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
+                            int total_rows, int npairs, const PairState* d_state, const SymmPass* d_pass, double max_d2, double* d_rows,
+                            double* d_out) {
+    const dim3 g(total_rows), b(P2L_THREADS);
+    if (d_perm)
+        hipLaunchKernelGGL(pairb_symm_rows_kernel<true>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_pass, max_d2, d_rows);
+    else
+        hipLaunchKernelGGL(pairb_symm_rows_kernel<false>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_pass, max_d2, d_rows);
     hipLaunchKernelGGL(pairb_final_kernel<true>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_out);
 }
 
