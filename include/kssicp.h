@@ -519,8 +519,8 @@ int kss_icp_gicp_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *
  * the twelve entries rounded to float, last row 0 0 0 1: p -> H (H p + c t), the paper's R p + t ~ R^-1 q.
  * The loop around it is kss_icp_p2l's: fewer than min_correspondences kept -> KSS_STATE_NO_CORRESPONDENCES, PCL's criteria on
  * MSE = [28] / [0], fitness over ALL sources, p->allreduce must be NULL.  KSS_ERR_ARG: everything kss_icp_gicp refuses, and
- * align_normals outside {0, 1}.  Many pairs per call: kss_icp_symm_batch below.  Robust or trimmed weights on top, the C++ mirror
- * classes and the CLI do not have this metric. */
+ * align_normals outside {0, 1}.  Many pairs per call: kss_icp_symm_batch below.  Robust weights on top: kss_icp_symm_robust below
+ * (a single pair).  Trimming, the C++ mirror classes and the CLI do not have this metric. */
 typedef struct {
     int normals_k;      /* 20: read only when a set of normals is NULL; 3..64 */
     int align_normals;  /* 1: n = nq - m where m . nq < 0;  0: always n = nq + m */
@@ -564,6 +564,51 @@ int kss_icp_symm_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_of
 int kss_icp_symm_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_src_normals_all,
                            const float *d_tgt_all, const int64_t *tgt_off, const float *d_tgt_normals_all, int npairs,
                            const kss_icp_params *p, const kss_symm_params *sp, const int32_t *aligns, kss_icp_result *results);
+
+/* ---- robust symmetric ICP for one pair: kss_icp_robust's M-estimator weights on kss_icp_symm's metric ----
+ * For pairs that are far apart in angle AND carry gross outliers or overlap only in part.  The pass is kss_icp_symm's with
+ * kss_icp_robust's weighting; nothing is redefined.  Per source i, with F, R_F, p, j, q, nq, ns, m, dot, n, w, d, c, v, r exactly as
+ * written at kss_icp_symm (f64 on the widened floats, nothing fused, the same order):
+ *   candidate   j in [0, nt), 0 <= d2 <= max_d2 (ordered compares in double: the robust form, which differs from kss_icp_symm's
+ *               !(d2 > max_d2) only for a NaN d2, outside this definition), and all six normal components finite.  m of them.
+ *   residual    x = r*r (one f64 product).
+ *   key         (float)fabs(r): the f64 value rounded to nearest-even float; a source that is no candidate has a NaN key.  The
+ *               rounding is monotone, so the k-th smallest key is the rounded k-th smallest |r|.
+ *   scale       exactly kss_icp_robust's plane-metric rule.  Fixed (rp->scale > 0): c2 = scale*scale.  Automatic (rp->scale == 0):
+ *               k = kss_trim_rank(m, 0.5), med = the exact k-th smallest key, c2 = kss_robust_scale2(KSS_METRIC_PLANE, tune, med,
+ *               min_scale); m == 0: c2 = 0.  |n| <= 2 (the sum of two unit normals), so r is up to TWICE a point-to-plane distance:
+ *               a fixed scale is in those units.
+ *   weight      w = kss_robust_weight(loss, x, c2); kept by the division-free tests written at kss_icp_robust; cnt of them.
+ *   record      KSS_P2L_NSUMS doubles in the robust plane layout with the symmetric v and r and wv[p] = w*v[p]: [0] += w, upper
+ *               triangle += wv[p]*v[q], [22+p] += wv[p]*r, [28] += w*d2, [29] = m, [30] += (w*r)*r, [31] = cnt.
+ *   order       kss_icp_symm's, a function of the source count alone.
+ *   info        {m, c2, [0], cnt}.
+ * Step and loop: kss_rigid_from_symm_sums on the record as it is ([0] is the weight total); cnt < min_correspondences ->
+ * KSS_STATE_NO_CORRESPONDENCES, a failed Cholesky -> KSS_STATE_DEGENERATE, PCL's criteria on MSE = [28] / [0], fitness over ALL
+ * sources, p->allreduce must be NULL.  Two consequences:
+ *   KSS_LOSS_L2 is kss_icp_symm bit for bit: T, iterations, state, last_mse, every trace_Tk, and slots [0..28] and [30] of every
+ *   trace_sums row; only [29] (m instead of the d2 total) and [31] (cnt instead of 0) differ.
+ *   With align_normals = 1 the record, the keys and the info do not depend on the sign of any input normal, bit for bit: a flip
+ *   negates v and r together.
+ * rp->metric must be KSS_METRIC_PLANE (the residual is a signed plane distance and the scale rule the plane one);
+ * rp->trace_robust and last_info as in kss_icp_robust; either set of normals may be NULL, computed as for kss_icp_symm; the sums
+ * forms follow kss_symm_sums (Rn a HOST pointer, NULL = identity; the _dev form takes idx entries outside [0, nt) as no candidate,
+ * the host form refuses them).  KSS_ERR_ARG: NULL ctx (refused before anything touches the device); everything kss_icp_symm refuses;
+ * everything kss_icp_robust refuses in rp; rp->metric == KSS_METRIC_POINT.  The batched form, trimming on this metric, robust
+ * weights on generalized ICP, the C++ mirror classes and the CLI do not have it. */
+int kss_symm_robust_sums(kss_ctx *ctx, const float *src, const float *src_normals, const float *tgt, const float *tgt_normals,
+                         const int32_t *idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params *sp,
+                         const kss_robust_params *rp, double sums[KSS_P2L_NSUMS], double info[KSS_ROBUST_NINFO]);
+int kss_symm_robust_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_src_normals, const float *d_tgt,
+                             const float *d_tgt_normals, const int32_t *d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9],
+                             const kss_symm_params *sp, const kss_robust_params *rp, double sums[KSS_P2L_NSUMS],
+                             double info[KSS_ROBUST_NINFO]);
+int kss_icp_symm_robust(kss_ctx *ctx, const float *src, int64_t ns, const float *src_normals, const float *tgt, int64_t nt,
+                        const float *tgt_normals, const kss_icp_params *p, const kss_symm_params *sp, const kss_robust_params *rp,
+                        kss_icp_result *res, double last_info[KSS_ROBUST_NINFO]);
+int kss_icp_symm_robust_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const float *d_tgt, int64_t nt,
+                            const float *d_tgt_normals, const kss_icp_params *p, const kss_symm_params *sp,
+                            const kss_robust_params *rp, kss_icp_result *res, double last_info[KSS_ROBUST_NINFO]);
 
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);

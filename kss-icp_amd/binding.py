@@ -43,6 +43,7 @@ SYMBOLS = [
     "kss_icp_gicp_batch", "kss_icp_gicp_batch_dev",
     "kss_symm_default_params", "kss_rigid_from_symm_sums", "kss_symm_sums", "kss_symm_sums_dev", "kss_icp_symm", "kss_icp_symm_dev",
     "kss_icp_symm_batch", "kss_icp_symm_batch_dev",
+    "kss_symm_robust_sums", "kss_symm_robust_sums_dev", "kss_icp_symm_robust", "kss_icp_symm_robust_dev",
 ]
 
 
@@ -191,6 +192,11 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, dbl, vp, C.POINTER(SymmParams), vp]
     for n in ("kss_icp_symm", "kss_icp_symm_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(SymmParams), C.POINTER(IcpResult)]
+    for n in ("kss_symm_robust_sums", "kss_symm_robust_sums_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, dbl, vp, C.POINTER(SymmParams), C.POINTER(RobustParams), vp, vp]
+    for n in ("kss_icp_symm_robust", "kss_icp_symm_robust_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(SymmParams), C.POINTER(RobustParams),
+                                  C.POINTER(IcpResult), vp]
     for n in ("kss_icp_gicp_batch", "kss_icp_gicp_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(GicpParams), vp, vp]
     for n in ("kss_icp_symm_batch", "kss_icp_symm_batch_dev"):
@@ -845,6 +851,67 @@ class Context:
                                           C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
                                           C.byref(params), C.byref(sp), C.byref(res)), "kss_icp_symm_dev")
         return res
+
+    # ---- robust symmetric ICP
+    def symm_robust_sums(self, src, src_normals, tgt, tgt_normals, idx, max_d2=1.0, Rn=None, sp=None, rp=None, loss=LOSS_TUKEY):
+        """kss_symm_robust_sums: (sums, info) of one robust symmetric pass over given correspondences: symm_sums()' arguments and a
+        RobustParams of the plane metric (rp None: the defaults of loss).  sums holds P2L_NSUMS doubles in the robust plane layout,
+        info {m, c2, sum of weights, cnt}."""
+        sp = sp if sp is not None else symm_params()
+        rp = self._robust_params(rp, loss, METRIC_PLANE)
+        s, t = _f32(src), _f32(tgt)
+        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
+        i = np.ascontiguousarray(idx, dtype=np.int32)
+        r = self._gicp_rot(Rn)
+        sums = np.zeros(P2L_NSUMS, np.float64)
+        info = np.zeros(ROBUST_NINFO, np.float64)
+        self._chk(self.L.kss_symm_robust_sums(self.h, _p(s), _p(sn), _p(t), _p(tn), _p(i), len(s), len(t), float(max_d2), _p(r),
+                                              C.byref(sp), C.byref(rp), _p(sums), _p(info)), "kss_symm_robust_sums")
+        return sums, info
+
+    def symm_robust_sums_dev(self, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2=1.0, Rn=None, sp=None, rp=None,
+                             loss=LOSS_TUKEY):
+        """kss_symm_robust_sums_dev on device pointers (either normals pointer may be 0 / None; Rn stays a host array); returns
+        (sums, info)."""
+        sp = sp if sp is not None else symm_params()
+        rp = self._robust_params(rp, loss, METRIC_PLANE)
+        r = self._gicp_rot(Rn)
+        sums = np.zeros(P2L_NSUMS, np.float64)
+        info = np.zeros(ROBUST_NINFO, np.float64)
+        self._chk(self.L.kss_symm_robust_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
+                                                  C.c_void_p(int(d_tgt)), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
+                                                  C.c_void_p(int(d_idx)), int(n), int(nt), float(max_d2), _p(r), C.byref(sp), C.byref(rp),
+                                                  _p(sums), _p(info)), "kss_symm_robust_sums_dev")
+        return sums, info
+
+    def icp_symm_robust(self, src, tgt, src_normals=None, tgt_normals=None, sp=None, rp=None, loss=LOSS_TUKEY, params=None, trace_cap=0,
+                        fitness_corr=False):
+        """Robust symmetric ICP (kss_icp_symm_robust): icp_symm()'s metric with icp_robust()'s M-estimator weights, for pairs far
+        apart in angle that carry outliers or overlap in part.  Normals and sp as in icp_symm(); rp: a RobustParams of the plane
+        metric (None: the defaults of loss).  The result dictionary of icp_robust(), trace_robust and robust_info included."""
+        sp = sp if sp is not None else symm_params()
+        rp = self._robust_params(rp, loss, METRIC_PLANE)
+        s, t = _f32(src), _f32(tgt)
+        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
+        p = params if params is not None else self.icp_params()
+        info = np.zeros(ROBUST_NINFO, np.float64)
+        out = self._icp_call(lambda res: self.L.kss_icp_symm_robust(self.h, _p(s), len(s), _p(sn), _p(t), len(t), _p(tn), C.byref(p),
+                                                                    C.byref(sp), C.byref(rp), C.byref(res), _p(info)),
+                             "kss_icp_symm_robust", p, len(s), P2L_NSUMS, trace_cap, fitness_corr, rp)
+        out["robust_info"] = info
+        return out
+
+    def icp_symm_robust_dev(self, d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals, params, sp=None, rp=None, loss=LOSS_TUKEY):
+        """kss_icp_symm_robust_dev on device pointers (either normals pointer may be 0 / None); returns (IcpResult, robust_info)."""
+        sp = sp if sp is not None else symm_params()
+        rp = self._robust_params(rp, loss, METRIC_PLANE)
+        res = IcpResult()
+        info = np.zeros(ROBUST_NINFO, np.float64)
+        self._chk(self.L.kss_icp_symm_robust_dev(self.h, C.c_void_p(int(d_src)), int(ns),
+                                                 C.c_void_p(int(d_src_normals)) if d_src_normals else None, C.c_void_p(int(d_tgt)), int(nt),
+                                                 C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None, C.byref(params), C.byref(sp),
+                                                 C.byref(rp), C.byref(res), _p(info)), "kss_icp_symm_robust_dev")
+        return res, info
 
     # ---- point-to-plane and trimmed ICP, many pairs per call
     def _batch_call(self, call, where, p, so, ncol, trace_cap, fitness_corr, tp=None):

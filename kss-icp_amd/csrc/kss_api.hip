@@ -950,6 +950,112 @@ int kss_icp_symm(kss_ctx* c, const float* src, int64_t ns, const float* src_norm
                             (const float*)c->stage_tgt.p, nt, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, p, sp, res);
 }
 
+// ---- robust symmetric ICP ----------------------------------------------------------
+// symm_check and robust_check composed; the residual is a signed plane distance and the scale rule the plane metric's
+static int symm_robust_check(kss_ctx* c, const char* who, const kss_symm_params* sp, const kss_robust_params* rp, bool need_k) {
+    KCHK(symm_check(c, who, sp, need_k));
+    KCHK(robust_check(c, who, rp, nullptr));
+    if (rp->metric != KSS_METRIC_PLANE) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": the metric must be KSS_METRIC_PLANE").c_str());
+    return KSS_OK;
+}
+
+int kss_symm_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals, const float* d_tgt, const float* d_tgt_normals,
+                             const int32_t* d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp,
+                             const kss_robust_params* rp, double sums[KSS_P2L_NSUMS], double info[KSS_ROBUST_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_robust_check(c, "symm_robust_sums", sp, rp, !d_src_normals || !d_tgt_normals));
+    if (!d_src || !d_tgt || !d_idx || !sums || !info) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: cloud too large");
+    const RobustScale rs = robust_scale_of(rp);
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_ROBUST_NINFO) * sizeof(double)));
+    const TrimState* d_sel = nullptr;
+    if (rs.autoscale) {
+        KCHK(ensure(c, c->rob_keys, (size_t)n * sizeof(float)));
+        KCHK(ensure(c, c->trim_rows, trim_rows_bytes(n)));
+        KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
+        d_sel = (const TrimState*)c->trim_state.p + (TRIM_NSTATE - 1);
+    }
+    {
+        ProfScope ps(c, KSS_K_CORR_REDUCE);
+        if (rs.autoscale) {   // the keys carry the whole candidate test (a NaN is none)
+            launch_symm_robust_keys(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, d_tgt, d_tgt_normals, n, nt, max_d2, Rn,
+                                    sp->align_normals, (float*)c->rob_keys.p);
+            launch_trim_select(c->stream, (const float*)c->rob_keys.p, n, std::numeric_limits<double>::infinity(), 0.5,
+                               (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p, nullptr);
+        }
+        launch_symm_robust_sums(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, d_tgt, d_tgt_normals, n, nt, max_d2, Rn,
+                                sp->align_normals, rs, d_sel, (double*)c->p2l_rows.p, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(sums, c->h_p2l, KSS_P2L_NSUMS * sizeof(double));
+    std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_ROBUST_NINFO * sizeof(double));
+    return KSS_OK;
+}
+
+int kss_symm_robust_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals,
+                         const int32_t* idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp,
+                         const kss_robust_params* rp, double sums[KSS_P2L_NSUMS], double info[KSS_ROBUST_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_robust_check(c, "symm_robust_sums", sp, rp, !src_normals || !tgt_normals));
+    if (!src || !tgt || !idx || !sums || !info) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: cloud too large");
+    for (int64_t i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= nt) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: index out of range");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)n * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
+    return kss_symm_robust_sums_dev(c, (const float*)c->stage_src.p, src_normals ? (const float*)c->gicp_snrm.p : nullptr,
+                                    (const float*)c->stage_tgt.p, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr,
+                                    (const int32_t*)c->stage_idx.p, n, nt, max_d2, Rn, sp, rp, sums, info);
+}
+
+int kss_icp_symm_robust_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const float* d_tgt, int64_t nt,
+                            const float* d_tgt_normals, const kss_icp_params* p, const kss_symm_params* sp, const kss_robust_params* rp,
+                            kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_robust_check(c, "icp_symm_robust", sp, rp, !d_src_normals || !d_tgt_normals));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm_robust: the source-row split (allreduce) is not available for symmetric ICP");
+    KCHK(pair_check(c, "icp_symm_robust", false, d_src, d_tgt, ns, nt, d_tgt_normals, p, nullptr, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(gicp_normals_dev(c, d_src, ns, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
+    PairMode mode;
+    mode.plane = true;
+    mode.symm = true;
+    mode.symm_align = sp->align_normals;
+    mode.d_src_nrm = d_src_normals;
+    mode.robust = true;
+    mode.rs = robust_scale_of(rp);
+    mode.trace_info = rp->trace_robust;
+    mode.last_info = last_info;
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_tgt_normals, p, mode, res);
+}
+
+int kss_icp_symm_robust(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const float* tgt, int64_t nt,
+                        const float* tgt_normals, const kss_icp_params* p, const kss_symm_params* sp, const kss_robust_params* rp,
+                        kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_robust_check(c, "icp_symm_robust", sp, rp, !src_normals || !tgt_normals));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm_robust: the source-row split (allreduce) is not available for symmetric ICP");
+    KCHK(pair_check(c, "icp_symm_robust", false, src, tgt, ns, nt, tgt_normals, p, nullptr, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)ns * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_symm_robust_dev(c, (const float*)c->stage_src.p, ns, src_normals ? (const float*)c->gicp_snrm.p : nullptr,
+                                   (const float*)c->stage_tgt.p, nt, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, p, sp, rp, res,
+                                   last_info);
+}
+
 // ---- the same for many pairs per call ------------------------------------------------
 // Every cloud's normals where the caller gave none: cloud_normals_dev at k, cloud after cloud (off: npairs + 1 offsets in points
 // from 0), into the packed buffer `out` laid out like the clouds (setup cost of the call, not optimised: a k-NN and a normals

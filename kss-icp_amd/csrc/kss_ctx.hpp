@@ -267,8 +267,9 @@ struct PairMode {
     bool gicp = false;              // generalized ICP (kss_icp_gicp; with plane, not with trimmed or robust): d_nrm and the SOURCE's
     double gicp_epsilon = 0.0;      // normals d_src_nrm (device, float triples by original source index) weigh every correspondence
     const float* d_src_nrm = nullptr;
-    bool symm = false;              // symmetric ICP (kss_icp_symm; with plane, not with trimmed, robust or gicp): the plane record on
-    int symm_align = 1;             // nq +- R_F ns, ns from d_src_nrm as for gicp; the step is rigid_from_symm_sums
+    bool symm = false;              // symmetric ICP (kss_icp_symm; with plane, not with trimmed or gicp): the plane record on
+    int symm_align = 1;             // nq +- R_F ns, ns from d_src_nrm as for gicp; the step is rigid_from_symm_sums.  With robust
+                                    // (kss_icp_symm_robust, a single pair only): the weights of rs on that record
 };
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,

@@ -1871,6 +1871,8 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // the criteria are the plane metric's.
 // Symmetric (kss_icp_symm; M.symm with M.plane): the symmetric rows launch with the same rotation; the record's
 // layout and the solve are the plane metric's, the step built from the solution is rigid_from_symm_sums' (two half rotations).
+// Robust symmetric (kss_icp_symm_robust; M.symm with M.robust): the robust branch with the symmetric keys and rows
+// launches and that rotation; the selection, the final launch, the info slots and the host step (cnt, rigid_from_symm_sums) are shared.
 // What the host does for ONE pair after a pass, the same code for a single pair (pair_loop) and inside a batch (pairs_loop): the
 // min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
 // its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
@@ -1937,19 +1939,29 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
             if (M.trimmed) launch_trim_select(c->stream, d_d2, ns, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
             if (M.robust) {
                 const TrimState* d_sel = nullptr;
+                const float* F = tr.fin;   // (symmetric: the rotation of the transform accumulated so far, as in the unweighted branch below)
+                const float Rn[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
                 if (M.rs.autoscale) {   // the median key: the point metric's keys are the NN pass's d2, the plane metric's are written here
                     const float* d_keys = d_d2;
                     double bound = max_d2;
                     if (M.plane) {
-                        launch_robust_keys(c->stream, true, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, (float*)c->rob_keys.p);
+                        if (M.symm)
+                            launch_symm_robust_keys(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn,
+                                                    M.symm_align, (float*)c->rob_keys.p);
+                        else
+                            launch_robust_keys(c->stream, true, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, (float*)c->rob_keys.p);
                         d_keys = (const float*)c->rob_keys.p;
                         bound = std::numeric_limits<double>::infinity();
                     }
                     launch_trim_select(c->stream, d_keys, ns, bound, 0.5, (unsigned*)c->trim_rows.p, d_state, nullptr);
                     d_sel = d_state + (TRIM_NSTATE - 1);
                 }
-                launch_robust_sums(c->stream, M.plane, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, M.rs, d_sel, d_rows,
-                                   d_rec, d_rec + P2L_NSUMS);
+                if (M.symm)
+                    launch_symm_robust_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn, M.symm_align,
+                                            M.rs, d_sel, d_rows, d_rec, d_rec + P2L_NSUMS);
+                else
+                    launch_robust_sums(c->stream, M.plane, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, M.rs, d_sel, d_rows,
+                                       d_rec, d_rec + P2L_NSUMS);
             } else if (M.gicp) {   // the source normals turn with the transform accumulated so far
                 const float* F = tr.fin;
                 const float Rn[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
@@ -1990,8 +2002,8 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
     if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: trimmed and robust exclude each other");
     if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm))
         return set_err(c, KSS_ERR_ARG, "pair_run: generalized ICP is the plane record with both clouds' normals, neither trimmed nor robust");
-    if (M.symm && (!M.plane || M.trimmed || M.robust || M.gicp || !M.d_src_nrm || !d_nrm))
-        return set_err(c, KSS_ERR_ARG, "pair_run: symmetric ICP is the plane record with both clouds' normals, neither trimmed, robust nor generalized");
+    if (M.symm && (!M.plane || M.trimmed || M.gicp || !M.d_src_nrm || !d_nrm))
+        return set_err(c, KSS_ERR_ARG, "pair_run: symmetric ICP is the plane record with both clouds' normals, neither trimmed nor generalized");
     HIPCHK(c, hipSetDevice(c->device));
     IcpPlan pl;
     const auto t0 = std::chrono::steady_clock::now();
@@ -2231,7 +2243,7 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
     if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm || !gicp_eps))
         return set_err(c, KSS_ERR_ARG, "pairs_run: generalized ICP is the plane record with both clouds' normals and the per-pair epsilons, neither trimmed nor robust");
     if (M.symm && (!M.plane || M.trimmed || M.robust || M.gicp || !M.d_src_nrm || !d_nrm || !symm_aligns))
-        return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP is the plane record with both clouds' normals and the per-pair aligns, neither trimmed, robust nor generalized");
+        return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP is the plane record with both clouds' normals and the per-pair aligns, neither trimmed nor generalized; robust symmetric ICP is single pair only");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> ns(npairs), nt(npairs);
     for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }

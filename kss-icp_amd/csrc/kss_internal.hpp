@@ -403,6 +403,20 @@ void launch_robust_keys(hipStream_t st, bool plane, const float* d_src3, const f
 void launch_robust_sums(hipStream_t st, bool plane, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
                         const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
                         const RobustScale& rs, const TrimState* d_sel, double* d_rows, double* d_out, double* d_info);
+void launch_robust_plane_final(hipStream_t st, const double* d_rows, int nrows, const RobustScale& rs, const TrimState* d_sel, double* d_out,
+                               double* d_info);   // robust_plane_final_kernel over given rows
+
+// ---- robust symmetric ICP (kss_symm_robust.hip) ----
+// launch_symm_sums' sources, normals, Rn and align with launch_robust_sums' scale, selection, rows, record and info.
+// One launch: d_keys[i] = (float)|r| of source i on the symmetric metric, NaN where it is no candidate.
+void launch_symm_robust_keys(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
+                             const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
+                             double max_d2, const float Rn[9], int align, float* d_keys);
+// Two launches: the weighted rows, then robust_plane_final_kernel.
+void launch_symm_robust_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
+                             const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
+                             double max_d2, const float Rn[9], int align, const RobustScale& rs, const TrimState* d_sel, double* d_rows,
+                             double* d_out, double* d_info);
 
 // ---- point-to-plane and trimmed ICP for many pairs per call (kss_pairb.hip) ----
 // one pair (or one segment of kss_trim_threshold_batch) as the batched kernels see it

@@ -1,8 +1,9 @@
-// kss_pair_device.hpp -- the device code that the single-pair kernels (kss_p2l.hip, kss_trim.hip, kss_robust.hip) and the batched
+// kss_pair_device.hpp -- the device code that the single-pair kernels (kss_p2l.hip, kss_trim.hip, kss_robust.hip, kss_symm_robust.hip) and the batched
 // ones (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
 //   gicp_source                      the same for generalized ICP (kss_gicp.hip; in a batch: pairb_gicp_rows_kernel),
-//   symm_source                      the same for symmetric ICP (kss_symm.hip; in a batch: pairb_symm_rows_kernel),
+//   symm_source                      the same for symmetric ICP (kss_symm.hip; in a batch: pairb_symm_rows_kernel; weighted:
+//                                    kss_symm_robust.hip),
 //   p2l_rows_column_sum              the fixed-order column sums of the plane metric's rows,
 //   trim_key / trim_resolve_counts   the candidate test and the resolution of one radix digit from a lane's eight bin counts.
 // A pair's bits are the same alone and inside a batch because both forms run these bodies in the same order.
@@ -173,11 +174,15 @@ __device__ __forceinline__ void gicp_source(double (&acc)[P2L_NSUMS], const floa
 // ---- symmetric ICP --------------------------------------------------------------------------------------
 // Source i as in gicp_source: the definition at kss_icp_symm in include/kssicp.h.  The plane metric's record with
 // n = nq +- m in place of the target's normal and w = p + q in place of p; the 21 + 6 products of v v^T and v r directly.
-template <int SRC>
+// MODE != PAIR_PLAIN (robust symmetric ICP; the definition at kss_icp_symm_robust): the candidates are
+// 0 <= d2 <= max_d2 as in p2l_source's robust form, x = r * r, the key is (float)fabs(r), and w * v[p] is formed inside the
+// unrolled loops (v and w v are never both live as arrays).
+template <int SRC, int MODE = PAIR_PLAIN>
 __device__ __forceinline__ void symm_source(double (&acc)[P2L_NSUMS], const float* __restrict__ src3, const float4* __restrict__ src4,
                                             const int32_t* __restrict__ perm, const int32_t* __restrict__ idx,
                                             const float* __restrict__ d2_in, const float* __restrict__ sn, const float* __restrict__ tgt,
-                                            const float* __restrict__ nrm, int64_t i, int64_t nt, double max_d2, const GicpRot& Rn, int align) {
+                                            const float* __restrict__ nrm, int64_t i, int64_t nt, double max_d2, const GicpRot& Rn, int align,
+                                            const RobustArg ra = RobustArg()) {
     const int64_t j = idx[i];
     if (j < 0 || j >= nt) return;
     float sx, sy, sz;
@@ -191,8 +196,9 @@ __device__ __forceinline__ void symm_source(double (&acc)[P2L_NSUMS], const floa
     const float nx = nrm[3 * j], ny = nrm[3 * j + 1], nz = nrm[3 * j + 2];
     const float ux = sn[3 * i], uy = sn[3 * i + 1], uz = sn[3 * i + 2];
     const double d2 = (double)(d2_in ? d2_in[i] : dist2<false>(sx, sy, sz, qx, qy, qz));
-    acc[29] += d2;
-    if (!(d2 > max_d2) && isfinite(nx) && isfinite(ny) && isfinite(nz) && isfinite(ux) && isfinite(uy) && isfinite(uz)) {
+    if constexpr (MODE == PAIR_PLAIN) acc[29] += d2;
+    if ((MODE == PAIR_PLAIN ? !(d2 > max_d2) : d2 >= 0.0 && d2 <= max_d2) && isfinite(nx) && isfinite(ny) && isfinite(nz) && isfinite(ux) &&
+        isfinite(uy) && isfinite(uz)) {
         const double nq[3] = {(double)nx, (double)ny, (double)nz};
         const double us[3] = {(double)ux, (double)uy, (double)uz};
         double m[3];
@@ -207,18 +213,44 @@ __device__ __forceinline__ void symm_source(double (&acc)[P2L_NSUMS], const floa
         const double qxd = (double)qx, qyd = (double)qy, qzd = (double)qz;
         const double w0 = px + qxd, w1 = py + qyd, w2 = pz + qzd;
         const double d0 = qxd - px, d1 = qyd - py, dz = qzd - pz;
-        const double v[6] = {w1 * n2 - w2 * n1, w2 * n0 - w0 * n2, w0 * n1 - w1 * n0, n0, n1, n2};
         const double r = (d0 * n0 + d1 * n1) + dz * n2;
-        acc[0] += 1.0;
-        int k = 1;
+        if constexpr (MODE == PAIR_KEY) {
+            *ra.key = (float)fabs(r);
+            return;
+        }
+        double w = 1.0;
+        if constexpr (MODE == PAIR_ROBUST) {   // the weight first: a source that is not kept forms no v, and the division's temporaries are gone before v is live
+            acc[29] += 1.0;
+            bool kept;
+            w = robust_weight_of(ra.loss, r * r, ra.c2, kept);
+            if (!kept) return;
+        }
+        const double v[6] = {w1 * n2 - w2 * n1, w2 * n0 - w0 * n2, w0 * n1 - w1 * n0, n0, n1, n2};
+        if constexpr (MODE == PAIR_ROBUST) {
+            acc[0] += w;
+            int k = 1;
 #pragma unroll
-        for (int p = 0; p < 6; ++p)
+            for (int p = 0; p < 6; ++p) {
+                const double wvp = w * v[p];
 #pragma unroll
-            for (int q = p; q < 6; ++q) acc[k++] += v[p] * v[q];
+                for (int q = p; q < 6; ++q) acc[k++] += wvp * v[q];
+                acc[22 + p] += wvp * r;
+            }
+            acc[28] += w * d2;
+            acc[30] += (w * r) * r;
+            acc[31] += 1.0;
+        } else {
+            acc[0] += 1.0;
+            int k = 1;
 #pragma unroll
-        for (int p = 0; p < 6; ++p) acc[22 + p] += v[p] * r;
-        acc[28] += d2;
-        acc[30] += r * r;
+            for (int p = 0; p < 6; ++p)
+#pragma unroll
+                for (int q = p; q < 6; ++q) acc[k++] += v[p] * v[q];
+#pragma unroll
+            for (int p = 0; p < 6; ++p) acc[22 + p] += v[p] * r;
+            acc[28] += d2;
+            acc[30] += r * r;
+        }
     }
 }
 

@@ -120,6 +120,11 @@ __global__ __launch_bounds__(TRIM_THREADS) void robust_point_final_kernel(const 
     if (t == 19) info[3] = v;
 }
 
+void launch_robust_plane_final(hipStream_t st, const double* d_rows, int nrows, const RobustScale& rs, const TrimState* d_sel, double* d_out,
+                               double* d_info) {
+    hipLaunchKernelGGL(robust_plane_final_kernel, dim3(1), dim3(P2L_THREADS), 0, st, d_rows, nrows, rs, d_sel, d_out, d_info);
+}
+
 void launch_robust_sums(hipStream_t st, bool plane, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
                         const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
                         const RobustScale& rs, const TrimState* d_sel, double* d_rows, double* d_out, double* d_info) {
@@ -133,7 +138,7 @@ void launch_robust_sums(hipStream_t st, bool plane, const float* d_src3, const f
         else if (d_perm) KSS_ROBUST_ROWS(SRC_F4_PERM);
         else KSS_ROBUST_ROWS(SRC_F4);
 #undef KSS_ROBUST_ROWS
-        hipLaunchKernelGGL(robust_plane_final_kernel, dim3(1), b, 0, st, (const double*)d_rows, nb, rs, d_sel, d_out, d_info);
+        launch_robust_plane_final(st, d_rows, nb, rs, d_sel, d_out, d_info);
     } else {
         const dim3 b(TRIM_THREADS);
 #define KSS_ROBUST_ROWS(PERM, F3) \

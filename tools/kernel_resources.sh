@@ -4,7 +4,7 @@
 # 296 bytes per lane and C3 from 7.45 to 7.9 ms).   usage: tools/kernel_resources.sh [file.hip ...]
 cd "$(dirname "$0")/../kss-icp_amd" || exit 1
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Rpass-analysis=kernel-resource-usage"
-for f in ${@:-csrc/kss_resident.hip csrc/kss_grid.hip csrc/kss_kernels.hip csrc/kss_p2l.hip csrc/kss_trim.hip csrc/kss_robust.hip csrc/kss_gicp.hip csrc/kss_symm.hip csrc/kss_pairb.hip}; do
+for f in ${@:-csrc/kss_resident.hip csrc/kss_grid.hip csrc/kss_kernels.hip csrc/kss_p2l.hip csrc/kss_trim.hip csrc/kss_robust.hip csrc/kss_gicp.hip csrc/kss_symm.hip csrc/kss_symm_robust.hip csrc/kss_pairb.hip}; do
   /opt/rocm/bin/hipcc $FL -c $f -o /tmp/_kr.o 2> /tmp/_kr.log || { echo "compile failed: $f"; exit 1; }
   python3 - "$f" <<'PY'
 import re, sys
