@@ -594,8 +594,8 @@ int kss_icp_symm_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *
  * rp->trace_robust and last_info as in kss_icp_robust; either set of normals may be NULL, computed as for kss_icp_symm; the sums
  * forms follow kss_symm_sums (Rn a HOST pointer, NULL = identity; the _dev form takes idx entries outside [0, nt) as no candidate,
  * the host form refuses them).  KSS_ERR_ARG: NULL ctx (refused before anything touches the device); everything kss_icp_symm refuses;
- * everything kss_icp_robust refuses in rp; rp->metric == KSS_METRIC_POINT.  The batched form, trimming on this metric, robust
- * weights on generalized ICP, the C++ mirror classes and the CLI do not have it. */
+ * everything kss_icp_robust refuses in rp; rp->metric == KSS_METRIC_POINT.  Many pairs per call: kss_icp_symm_robust_batch
+ * below.  Trimming on this metric, robust weights on generalized ICP, the C++ mirror classes and the CLI do not have it. */
 int kss_symm_robust_sums(kss_ctx *ctx, const float *src, const float *src_normals, const float *tgt, const float *tgt_normals,
                          const int32_t *idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params *sp,
                          const kss_robust_params *rp, double sums[KSS_P2L_NSUMS], double info[KSS_ROBUST_NINFO]);
@@ -609,6 +609,34 @@ int kss_icp_symm_robust(kss_ctx *ctx, const float *src, int64_t ns, const float 
 int kss_icp_symm_robust_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const float *d_tgt, int64_t nt,
                             const float *d_tgt_normals, const kss_icp_params *p, const kss_symm_params *sp,
                             const kss_robust_params *rp, kss_icp_result *res, double last_info[KSS_ROBUST_NINFO]);
+
+/* ---- robust symmetric ICP for MANY pairs per call ----
+ * Arguments as kss_icp_symm_batch (packed float[n][3] clouds, npairs + 1 HOST offsets in points, a sub-range through a first offset
+ * that is not 0; the _dev form takes device clouds and normals, the offsets, aligns and scales stay host arrays; either set of
+ * normals may be NULL and is then computed per cloud at sp->normals_k) with kss_icp_robust_batch's rp, scales and info_all.
+ * Nothing is redefined: the definition at kss_icp_symm_robust holds for every pair with the PAIR's own inputs --
+ *   R_F      the rotation block of the pair's own accumulated float transform, pass by pass;
+ *   align    aligns[i] (0 or 1), or sp->align_normals for every pair when aligns is NULL;
+ *   scale    scales[i] > 0 fixed, scales[i] == 0 automatic from the pair's own median key of the pass; NULL: rp->scale for every
+ *            pair.  A batch may mix both forms; loss, tune and min_scale are the batch's.
+ * Every pair's record -- T, iterations, state, converged, last_mse, its info, pair 0's trace_Tk / trace_sums / rp->trace_robust -- is
+ * the single-pair kss_icp_symm_robust call's BIT FOR BIT (fitness: within 2 ns 2^-53 relative), in any batch order and any split
+ * over calls, under every NN engine and tuning knob; results[i].pair_id = i.  So a KSS_LOSS_L2 batch is kss_icp_symm_batch bit for
+ * bit in T, iterations, state and last_mse.  info_all: npairs * KSS_ROBUST_NINFO doubles or NULL, every pair's last
+ * {m, c2, sum of weights, cnt}, all zero for a pair that ran no pass.  The pairs run in lockstep: behind the NN pass one small table
+ * copy, the key and selection launches when at least one pair is automatic, and two sums launches, whatever the pair count; a pair
+ * that ends leaves the others untouched.  trace_*, rp->trace_robust and fitness_idx / fitness_d2 describe pair 0.
+ * KSS_ERR_ARG: NULL ctx (refused before anything touches the device); everything kss_icp_symm_batch refuses; everything
+ * kss_icp_symm_robust refuses in rp (rp->metric == KSS_METRIC_POINT among it); a scales entry that is negative or not finite; an
+ * automatic pair with a tune that is not positive and finite.  A refused or failed call leaves the context usable. */
+int kss_icp_symm_robust_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *src_normals_all,
+                              const float *tgt_all, const int64_t *tgt_off, const float *tgt_normals_all, int npairs,
+                              const kss_icp_params *p, const kss_symm_params *sp, const int32_t *aligns,
+                              const kss_robust_params *rp, const double *scales, kss_icp_result *results, double *info_all);
+int kss_icp_symm_robust_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_src_normals_all,
+                                  const float *d_tgt_all, const int64_t *tgt_off, const float *d_tgt_normals_all, int npairs,
+                                  const kss_icp_params *p, const kss_symm_params *sp, const int32_t *aligns,
+                                  const kss_robust_params *rp, const double *scales, kss_icp_result *results, double *info_all);
 
 /* ---- (a13) apply the ICP Matrix4f to a full-resolution f64 cloud, KSS_ICP.hpp:224-230 ---- */
 int kss_transform_apply(kss_ctx *ctx, const float T[16], const double *in, int64_t n, double *out);

@@ -44,6 +44,7 @@ SYMBOLS = [
     "kss_symm_default_params", "kss_rigid_from_symm_sums", "kss_symm_sums", "kss_symm_sums_dev", "kss_icp_symm", "kss_icp_symm_dev",
     "kss_icp_symm_batch", "kss_icp_symm_batch_dev",
     "kss_symm_robust_sums", "kss_symm_robust_sums_dev", "kss_icp_symm_robust", "kss_icp_symm_robust_dev",
+    "kss_icp_symm_robust_batch", "kss_icp_symm_robust_batch_dev",
 ]
 
 
@@ -201,6 +202,9 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(GicpParams), vp, vp]
     for n in ("kss_icp_symm_batch", "kss_icp_symm_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(SymmParams), vp, vp]
+    for n in ("kss_icp_symm_robust_batch", "kss_icp_symm_robust_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(SymmParams), vp,
+                                  C.POINTER(RobustParams), vp, vp, vp]
     for n in ("kss_trim_threshold_batch", "kss_trim_threshold_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, C.c_int, dbl, vp, vp]
     for n in ("kss_rotation_search", "kss_rotation_search_dev"):
@@ -1160,6 +1164,50 @@ class Context:
                                                       C.c_void_p(int(d_tgt_normals_all)) if d_tgt_normals_all else None, npairs,
                                                       C.byref(p), C.byref(sp), _p(al), res),
             "kss_icp_symm_batch_dev", p, so, P2L_NSUMS, trace_cap, False)
+
+    # ---- robust symmetric ICP, many pairs per call
+    def icp_symm_robust_batch(self, src_all, src_off, tgt_all, tgt_off, src_normals_all=None, tgt_normals_all=None, aligns=None,
+                              scales=None, sp=None, rp=None, loss=LOSS_TUKEY, params=None, trace_cap=0, fitness_corr=False):
+        """kss_icp_symm_robust_batch: robust symmetric ICP of npairs pairs in one call.  Clouds, offsets, normals, aligns and sp as in
+        icp_symm_batch(); rp as in icp_symm_robust() (loss, tune and min_scale of the whole batch); scales: one per pair (> 0 fixed,
+        0 automatic), or None for rp.scale everywhere.  Returns (list of IcpResult, robust_info of every pair as npairs x
+        ROBUST_NINFO, dictionary with pair 0's traces, trace_robust among them)."""
+        sp = sp if sp is not None else symm_params()
+        rp = self._robust_params(rp, loss, METRIC_PLANE)
+        s, t = _f32(src_all), _f32(tgt_all)
+        sn, tn = self._gicp_normals(src_normals_all, len(s), "source"), self._gicp_normals(tgt_normals_all, len(t), "target")
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        al = self._aligns(aligns, npairs)
+        sc = self._scales(scales, npairs)
+        p = params if params is not None else self.icp_params()
+        info = np.zeros((max(npairs, 0), ROBUST_NINFO), np.float64)
+        res, extra = self._batch_call(
+            lambda res: self.L.kss_icp_symm_robust_batch(self.h, _p(s), _p(so), _p(sn), _p(t), _p(to), _p(tn), npairs, C.byref(p),
+                                                         C.byref(sp), _p(al), C.byref(rp), _p(sc), res, _p(info)),
+            "kss_icp_symm_robust_batch", p, so, P2L_NSUMS, trace_cap, fitness_corr, rp)
+        return res, info, extra
+
+    def icp_symm_robust_batch_dev(self, d_src_all, src_off, d_src_normals_all, d_tgt_all, tgt_off, d_tgt_normals_all, params=None,
+                                  aligns=None, scales=None, sp=None, rp=None, loss=LOSS_TUKEY, trace_cap=0):
+        """kss_icp_symm_robust_batch_dev on device pointers (either normals pointer may be 0 / None; the offsets, aligns and scales
+        stay host arrays).  Returns (list of IcpResult, robust_info npairs x ROBUST_NINFO, dictionary with pair 0's traces)."""
+        sp = sp if sp is not None else symm_params()
+        rp = self._robust_params(rp, loss, METRIC_PLANE)
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        al = self._aligns(aligns, npairs)
+        sc = self._scales(scales, npairs)
+        p = params if params is not None else self.icp_params()
+        info = np.zeros((max(npairs, 0), ROBUST_NINFO), np.float64)
+        res, extra = self._batch_call(
+            lambda res: self.L.kss_icp_symm_robust_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so),
+                                                             C.c_void_p(int(d_src_normals_all)) if d_src_normals_all else None,
+                                                             C.c_void_p(int(d_tgt_all)), _p(to),
+                                                             C.c_void_p(int(d_tgt_normals_all)) if d_tgt_normals_all else None, npairs,
+                                                             C.byref(p), C.byref(sp), _p(al), C.byref(rp), _p(sc), res, _p(info)),
+            "kss_icp_symm_robust_batch_dev", p, so, P2L_NSUMS, trace_cap, False, rp)
+        return res, info, extra
 
     def trim_threshold_batch(self, d2_all, off, overlaps, max_d2=1.0):
         """kss_trim_threshold_batch: {m, k, tau, kept} of every segment [off[i], off[i + 1]) of d2_all, nseg x TRIM_NINFO."""

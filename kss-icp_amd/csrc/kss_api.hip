@@ -1139,20 +1139,25 @@ int kss_icp_trimmed_batch(kss_ctx* c, const float* src_all, const int64_t* src_o
 }
 
 // ---- robust ICP for many pairs per call ----------------------------------------------
+// the per-pair scales of a checked rp (null: rp->scale everywhere); kss_icp_symm_robust_batch shares it
+static int robust_scales_check(kss_ctx* c, const char* who, const kss_robust_params* rp, int npairs, const double* scales) {
+    if (!scales) return KSS_OK;
+    const std::string w = std::string(who) + ": ";
+    const bool tune_ok = rp->tune > 0.0 && std::isfinite(rp->tune);
+    for (int i = 0; i < npairs; ++i) {
+        if (!(scales[i] >= 0.0) || !std::isfinite(scales[i])) return set_err(c, KSS_ERR_ARG, (w + "a scale must be finite and >= 0").c_str());
+        if (scales[i] == 0.0 && !tune_ok) return set_err(c, KSS_ERR_ARG, (w + "tune must be finite and > 0").c_str());
+    }
+    return KSS_OK;
+}
+
 // what the two entry points share beyond pair_check: rp, allreduce and the per-pair scales (null: rp->scale everywhere)
 static int robust_batch_check(kss_ctx* c, const kss_robust_params* rp, const float* nrm, const kss_icp_params* p, const int64_t* src_off,
                               const int64_t* tgt_off, int npairs, const double* scales) {
     KCHK(robust_check(c, "icp_robust_batch", rp, nrm));
     if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: the source-row split (allreduce) is not available for robust ICP");
     if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: bad batch");
-    if (scales) {
-        const bool tune_ok = rp->tune > 0.0 && std::isfinite(rp->tune);
-        for (int i = 0; i < npairs; ++i) {
-            if (!(scales[i] >= 0.0) || !std::isfinite(scales[i])) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: a scale must be finite and >= 0");
-            if (scales[i] == 0.0 && !tune_ok) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: tune must be finite and > 0");
-        }
-    }
-    return KSS_OK;
+    return robust_scales_check(c, "icp_robust_batch", rp, npairs, scales);
 }
 
 int kss_icp_robust_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off,
@@ -1253,14 +1258,15 @@ int kss_icp_gicp_batch(kss_ctx* c, const float* src, const int64_t* src_off, con
 // what the two entry points share: sp, allreduce, the per-pair aligns (null: sp->align_normals everywhere) and pair_check
 static int symm_batch_check(kss_ctx* c, const void* src, const float* snrm, const void* tgt, const float* tnrm, const int64_t* src_off,
                             const int64_t* tgt_off, int npairs, const kss_icp_params* p, const kss_symm_params* sp, const int32_t* aligns,
-                            const kss_icp_result* results) {
-    KCHK(symm_check(c, "icp_symm_batch", sp, !snrm || !tnrm));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm_batch: the source-row split (allreduce) is not available for symmetric ICP");
-    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_symm_batch: bad batch");
+                            const kss_icp_result* results, const char* who = "icp_symm_batch") {
+    const std::string w = std::string(who) + ": ";
+    KCHK(symm_check(c, who, sp, !snrm || !tnrm));
+    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, (w + "the source-row split (allreduce) is not available for symmetric ICP").c_str());
+    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, (w + "bad batch").c_str());
     if (aligns)
         for (int i = 0; i < npairs; ++i)
-            if (aligns[i] != 0 && aligns[i] != 1) return set_err(c, KSS_ERR_ARG, "icp_symm_batch: every align must be 0 or 1");
-    return pair_check(c, "icp_symm_batch", false, src, tgt, 0, 0, tnrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr);
+            if (aligns[i] != 0 && aligns[i] != 1) return set_err(c, KSS_ERR_ARG, (w + "every align must be 0 or 1").c_str());
+    return pair_check(c, who, false, src, tgt, 0, 0, tnrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr);
 }
 
 int kss_icp_symm_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
@@ -1303,6 +1309,66 @@ int kss_icp_symm_batch(kss_ctx* c, const float* src, const int64_t* src_off, con
     return kss_icp_symm_batch_dev(c, (const float*)c->stage_src.p, so.data(), src_normals ? (const float*)c->pb_snrm.p : nullptr,
                                   (const float*)c->stage_tgt.p, to.data(), tgt_normals ? (const float*)c->pb_nrm.p : nullptr, npairs, p, sp,
                                   aligns, results);
+}
+
+// ---- robust symmetric ICP for many pairs per call ------------------------------------
+// symm_batch_check with the checks of rp (the plane metric, as for the single pair) and of the per-pair scales
+static int symm_robust_batch_check(kss_ctx* c, const void* src, const float* snrm, const void* tgt, const float* tnrm, const int64_t* src_off,
+                                   const int64_t* tgt_off, int npairs, const kss_icp_params* p, const kss_symm_params* sp,
+                                   const int32_t* aligns, const kss_robust_params* rp, const double* scales, const kss_icp_result* results) {
+    const char* who = "icp_symm_robust_batch";
+    KCHK(symm_robust_check(c, who, sp, rp, !snrm || !tnrm));
+    KCHK(symm_batch_check(c, src, snrm, tgt, tnrm, src_off, tgt_off, npairs, p, sp, aligns, results, who));
+    return robust_scales_check(c, who, rp, npairs, scales);
+}
+
+int kss_icp_symm_robust_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
+                                  const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
+                                  const kss_symm_params* sp, const int32_t* aligns, const kss_robust_params* rp, const double* scales,
+                                  kss_icp_result* results, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_robust_batch_check(c, d_src, d_src_normals, d_tgt, d_tgt_normals, src_off, tgt_off, npairs, p, sp, aligns, rp, scales, results));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);   // rebased to the first pair, as in kss_icp_symm_batch_dev
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
+    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
+    if (d_src_normals) d_src_normals += 3 * src_off[0];
+    if (d_tgt_normals) d_tgt_normals += 3 * tgt_off[0];
+    // each cloud's normals where the caller gave none, as kss_icp_symm_robust computes them: from the cloud as passed in, at normals_k
+    if (!d_tgt_normals) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, sp->normals_k, c->pb_nrm, &d_tgt_normals));
+    if (!d_src_normals) KCHK(batch_normals_dev(c, d_src, so.data(), npairs, sp->normals_k, c->pb_snrm, &d_src_normals));
+    PairMode mode;
+    mode.plane = true;
+    mode.symm = true;
+    mode.d_src_nrm = d_src_normals;
+    mode.robust = true;
+    mode.rs = robust_scale_of(rp);
+    mode.trace_info = rp->trace_robust;
+    std::vector<int32_t> al((size_t)npairs, sp->align_normals);
+    if (aligns) al.assign(aligns, aligns + npairs);
+    std::vector<RobustScale> rs((size_t)npairs);
+    for (int i = 0; i < npairs; ++i) rs[i] = robust_scale_of(rp, scales ? scales[i] : rp->scale);
+    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_tgt_normals, npairs, p, mode, nullptr, results, info_all, rs.data(), nullptr,
+                         al.data());
+}
+
+int kss_icp_symm_robust_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
+                              const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_symm_params* sp,
+                              const int32_t* aligns, const kss_robust_params* rp, const double* scales, kss_icp_result* results,
+                              double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(symm_robust_batch_check(c, src, src_normals, tgt, tgt_normals, src_off, tgt_off, npairs, p, sp, aligns, rp, scales, results));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
+    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    if (src_normals) KCHK(upload(c, c->pb_snrm, src_normals + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    if (tgt_normals) KCHK(upload(c, c->pb_nrm, tgt_normals + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
+    return kss_icp_symm_robust_batch_dev(c, (const float*)c->stage_src.p, so.data(), src_normals ? (const float*)c->pb_snrm.p : nullptr,
+                                         (const float*)c->stage_tgt.p, to.data(), tgt_normals ? (const float*)c->pb_nrm.p : nullptr, npairs, p,
+                                         sp, aligns, rp, scales, results, info_all);
 }
 
 static int trim_batch_check(kss_ctx* c, const float* d2, const int64_t* off, int nseg, const double* overlaps, const double* info_all) {

@@ -269,14 +269,14 @@ struct PairMode {
     const float* d_src_nrm = nullptr;
     bool symm = false;              // symmetric ICP (kss_icp_symm; with plane, not with trimmed or gicp): the plane record on
     int symm_align = 1;             // nq +- R_F ns, ns from d_src_nrm as for gicp; the step is rigid_from_symm_sums.  With robust
-                                    // (kss_icp_symm_robust, a single pair only): the weights of rs on that record
+                                    // (kss_icp_symm_robust, kss_icp_symm_robust_batch): the weights of rs on that record
 };
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                  const kss_icp_params* p, const PairMode& mode, kss_icp_result* res);
 int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info);
 // npairs >= 1 pairs in lockstep (kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch, kss_icp_gicp_batch,
-// kss_icp_symm_batch): d_nrm laid
+// kss_icp_symm_batch, kss_icp_symm_robust_batch -- symm with robust takes both symm_aligns and rscales): d_nrm laid
 // out like d_tgt; overlaps: one per pair (trimmed; M.overlap is not read); rscales: one per pair (robust; M.rs is not read), all
 // with the loss of the batch; info_all: npairs * KSS_TRIM_NINFO or null; M.trace_info / M.last_info: pair 0's / unused;
 // gicp_eps: one epsilon per pair (generalized; M.gicp_epsilon is not read), M.d_src_nrm laid out like d_src;

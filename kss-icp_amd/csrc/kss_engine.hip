@@ -2057,7 +2057,8 @@ int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, 
 // ---- the same metrics for MANY pairs per call: kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch
 // (2.13: behind the NN pass the key launch (plane) and the selection when any pair has the automatic scale, then two sums launches),
 // kss_icp_gicp_batch (2.15: one copy of the per-pair pass table -- the rotation of every pair's fin and its e -- then two sums launches),
-// kss_icp_symm_batch (2.18: the same with the table of SymmPass -- the rotation and the pair's align_normals) ----
+// kss_icp_symm_batch (2.18: the same with the table of SymmPass -- the rotation and the pair's align_normals),
+// kss_icp_symm_robust_batch (2.20: that table's copy, then the robust form's launches on the symmetric body) ----
 // pair_loop in lockstep over npairs >= 1 pairs.  Per pass: ONE NN pass over the pairs still active (idx / d2 by global source
 // index), ONE selection launch when trimmed, TWO sums launches (kss_pairb.hip), ONE stream synchronisation, then
 // pair_host_step for every active pair (the host pool from 64 pairs up, each pair on exactly one thread).  A pair that ends
@@ -2137,7 +2138,15 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
         const PairState* d_state = c->last_state_dev;   // (a single pair on its own cell list has none: it is active)
         {
             ProfScope ps(c, KSS_K_CORR_REDUCE);
-            if (M.robust) {
+            if (M.robust && M.symm) {   //  the symmetric form's table copy, then the robust form's launches on the symmetric body
+                if (!symm_mapped)
+                    HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hsp, (size_t)np * sizeof(SymmPass), hipMemcpyHostToDevice, c->stream));
+                if (rob_select)
+                    launch_pairb_symm_robust_select(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows,
+                                                    np, d_state, d_rs, d_spass, max_d2, (float*)c->rob_keys.p, d_ts);
+                launch_pairb_symm_robust_sums(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
+                                              d_state, d_rs, d_ts, d_spass, max_d2, (double*)c->p2l_rows.p, d_rec, d_info);
+            } else if (M.robust) {
                 if (rob_select)   // some pair takes its scale from the pass's median key
                     launch_pairb_robust_select(c->stream, M.plane, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
                                                d_state, d_rs, max_d2, (float*)c->rob_keys.p, d_ts);
@@ -2242,8 +2251,8 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
     if (M.robust && !rscales) return set_err(c, KSS_ERR_ARG, "pairs_run: robust needs the per-pair scales");
     if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm || !gicp_eps))
         return set_err(c, KSS_ERR_ARG, "pairs_run: generalized ICP is the plane record with both clouds' normals and the per-pair epsilons, neither trimmed nor robust");
-    if (M.symm && (!M.plane || M.trimmed || M.robust || M.gicp || !M.d_src_nrm || !d_nrm || !symm_aligns))
-        return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP is the plane record with both clouds' normals and the per-pair aligns, neither trimmed nor generalized; robust symmetric ICP is single pair only");
+    if (M.symm && (!M.plane || M.trimmed || M.gicp || !M.d_src_nrm || !d_nrm || !symm_aligns))
+        return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP is the plane record with both clouds' normals and the per-pair aligns, neither trimmed nor generalized; robust symmetric ICP adds the per-pair scales");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> ns(npairs), nt(npairs);
     for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }

@@ -479,6 +479,20 @@ void launch_pairb_symm_sums(hipStream_t st, const float4* d_src4, const int32_t*
                             int total_rows, int npairs, const PairState* d_state, const SymmPass* d_pass, double max_d2, double* d_rows,
                             double* d_out);
 
+// ---- robust symmetric ICP for many pairs per call (kss_pairb.hip): d_rs and d_pass hold one entry per pair ----
+// two launches: (float)|r| on the symmetric metric of every active AUTOMATIC pair's sources into d_keys by global source index
+// (NaN: no candidate), then the median key into d_ts[pair] (the others' entries are not written)
+void launch_pairb_symm_robust_select(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                                     const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc,
+                                     const int32_t* d_row_pair, int total_rows, int npairs, const PairState* d_state, const RobustScale* d_rs,
+                                     const SymmPass* d_pass, double max_d2, float* d_keys, TrimState* d_ts);
+// two launches: every active pair's weighted record into d_out[pair * KSS_P2L_NSUMS] and {m, c2, sum of weights, cnt} into
+// d_info[pair * KSS_ROBUST_NINFO]
+void launch_pairb_symm_robust_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                                   const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc,
+                                   const int32_t* d_row_pair, int total_rows, int npairs, const PairState* d_state, const RobustScale* d_rs,
+                                   const TrimState* d_ts, const SymmPass* d_pass, double max_d2, double* d_rows, double* d_out, double* d_info);
+
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,
                 const std::function<void*(size_t)>& scratch);

@@ -38,6 +38,14 @@
 //                                SymmPass whose rotations the host rewrites before every pass.  The source normals are packed
 //                                like the sources and read by global original index.
 //   pairb_final_kernel<true>     unchanged.
+//
+// Robust symmetric ICP for many pairs: the robust shape on the symmetric body, both per-pair tables at once.
+//   pairb_symm_robust_keys_kernel  automatic pairs: pairb_robust_keys_kernel's grid and exit test on symm_source's PAIR_KEY mode,
+//                                  |r| per source (NaN: no candidate) into the batch-wide key array by global original source index.
+//   pairb_robust_select_kernel     unchanged, over those keys with an infinite bound.
+//   pairb_symm_robust_rows_kernel  pairb_symm_rows_kernel's grid on symm_source's PAIR_ROBUST mode; the rotation and align from the
+//                                  pair's SymmPass, the loss and the pass's c2 from its RobustScale and TrimState.
+//   pairb_robust_final_kernel<true>  unchanged.
 #pragma clang fp contract(off)
 
 #include "kss_robust_device.hpp"
@@ -327,6 +335,71 @@ __global__ __launch_bounds__(P2L_THREADS) void pairb_robust_final_kernel(const d
     if (t == 1) info[1] = robust_pass_c2(rs[p], PLANE, ts + p);
 }
 
+// ---- robust symmetric ICP (kss_symm_robust.hip's kernels, per pair) ---------------------------------------------------------
+// pass[p] as for pairb_symm_rows_kernel: one uniform load per workgroup
+template <bool PERM>
+__global__ __launch_bounds__(P2L_THREADS) void pairb_symm_robust_keys_kernel(const float4* __restrict__ src4, const int32_t* __restrict__ perm,
+                                                                             const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
+                                                                             const float* __restrict__ sn_all, const float* __restrict__ tgt_all,
+                                                                             const float* __restrict__ nrm_all, const PairbDesc* __restrict__ desc,
+                                                                             const int32_t* __restrict__ row_pair, const PairState* __restrict__ state,
+                                                                             const RobustScale* __restrict__ rs, const SymmPass* __restrict__ pass,
+                                                                             double max_d2, float* __restrict__ keys) {
+    const int p = row_pair[blockIdx.x];
+    if (!pairb_robust_selects(state, rs, p)) return;
+    const PairbDesc d = desc[p];
+    const SymmPass sp = pass[p];
+    GicpRot Rn;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rn.r[k] = sp.r[k];
+    const float* tgt = tgt_all + 3 * d.tgt_off;
+    const float* nrm = nrm_all + 3 * d.tgt_off;
+    const int64_t step = (int64_t)d.nrows * P2L_THREADS;
+    for (int64_t i = (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x; i < d.ns; i += step) {
+        float key = __uint_as_float(0x7fc00000u);
+        RobustArg ra;
+        ra.key = &key;
+        double acc[P2L_NSUMS];   // (never read in this mode)
+        symm_source<PERM ? SRC_F4_PERM : SRC_F4, PAIR_KEY>(acc, nullptr, src4, perm, idx, d2_in, sn_all, tgt, nrm, d.src_base + i, d.nt, max_d2, Rn,
+                                                           sp.align, ra);
+        keys[d.src_base + i] = key;
+    }
+}
+
+template <bool PERM>
+__global__ __launch_bounds__(P2L_THREADS) void pairb_symm_robust_rows_kernel(const float4* __restrict__ src4, const int32_t* __restrict__ perm,
+                                                                             const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
+                                                                             const float* __restrict__ sn_all, const float* __restrict__ tgt_all,
+                                                                             const float* __restrict__ nrm_all, const PairbDesc* __restrict__ desc,
+                                                                             const int32_t* __restrict__ row_pair, const PairState* __restrict__ state,
+                                                                             const RobustScale* __restrict__ rs, const TrimState* __restrict__ ts,
+                                                                             const SymmPass* __restrict__ pass, double max_d2,
+                                                                             double* __restrict__ rows) {
+    __shared__ double sh[P2L_THREADS / 64][P2L_NSUMS];
+    const int p = row_pair[blockIdx.x];
+    if (!pairb_active(state, p)) return;
+    const PairbDesc d = desc[p];
+    const SymmPass sp = pass[p];
+    GicpRot Rn;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Rn.r[k] = sp.r[k];
+    double acc[P2L_NSUMS];
+#pragma unroll
+    for (int c = 0; c < P2L_NSUMS; ++c) acc[c] = 0.0;
+    const RobustScale s = rs[p];
+    RobustArg ra;
+    ra.loss = s.loss;
+    ra.c2 = robust_pass_c2(s, true, ts + p);
+    const float* tgt = tgt_all + 3 * d.tgt_off;
+    const float* nrm = nrm_all + 3 * d.tgt_off;
+    const int64_t step = (int64_t)d.nrows * P2L_THREADS;
+    for (int64_t i = (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x; i < d.ns; i += step)
+        symm_source<PERM ? SRC_F4_PERM : SRC_F4, PAIR_ROBUST>(acc, nullptr, src4, perm, idx, d2_in, sn_all, tgt, nrm, d.src_base + i, d.nt, max_d2, Rn,
+                                                              sp.align, ra);
+    const double r = block_sum<P2L_NSUMS>(acc, sh);
+    if (threadIdx.x < P2L_NSUMS) rows[(int64_t)blockIdx.x * P2L_NSUMS + threadIdx.x] = r;
+}
+
 void launch_pairb_select(hipStream_t st, const float* d_d2, const PairbDesc* d_desc, int npairs, const PairState* d_state, double max_d2,
                          TrimState* d_ts, double* d_info) {
     hipLaunchKernelGGL(pairb_select_kernel, dim3(npairs), dim3(TRIM_HIST_THREADS), 0, st, d_d2, d_desc, d_state, max_d2, d_ts, d_info);
@@ -406,6 +479,32 @@ void launch_pairb_robust_sums(hipStream_t st, bool plane, const float4* d_src4, 
         hipLaunchKernelGGL(pairb_robust_final_kernel<false>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_rs, d_ts, d_out, d_info);
     }
 #undef KSS_PAIRB_ROBUST_ROWS
+}
+
+void launch_pairb_symm_robust_select(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                                     const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc,
+                                     const int32_t* d_row_pair, int total_rows, int npairs, const PairState* d_state, const RobustScale* d_rs,
+                                     const SymmPass* d_pass, double max_d2, float* d_keys, TrimState* d_ts) {
+    const dim3 g(total_rows), b(P2L_THREADS);
+    if (d_perm)
+        hipLaunchKernelGGL(pairb_symm_robust_keys_kernel<true>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_rs, d_pass, max_d2, d_keys);
+    else
+        hipLaunchKernelGGL(pairb_symm_robust_keys_kernel<false>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_rs, d_pass, max_d2, d_keys);
+    // the keys carry the whole candidate test (a NaN is none): no bound
+    hipLaunchKernelGGL(pairb_robust_select_kernel, dim3(npairs), dim3(TRIM_HIST_THREADS), 0, st, (const float*)d_keys, d_desc, d_state, d_rs,
+                       __builtin_huge_val(), d_ts);
+}
+
+void launch_pairb_symm_robust_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
+                                   const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc,
+                                   const int32_t* d_row_pair, int total_rows, int npairs, const PairState* d_state, const RobustScale* d_rs,
+                                   const TrimState* d_ts, const SymmPass* d_pass, double max_d2, double* d_rows, double* d_out, double* d_info) {
+    const dim3 g(total_rows), b(P2L_THREADS);
+    if (d_perm)
+        hipLaunchKernelGGL(pairb_symm_robust_rows_kernel<true>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_rs, d_ts, d_pass, max_d2, d_rows);
+    else
+        hipLaunchKernelGGL(pairb_symm_robust_rows_kernel<false>, g, b, 0, st, d_src4, d_perm, d_idx, d_d2, d_sn3, d_tgt3, d_nrm3, d_desc, d_row_pair, d_state, d_rs, d_ts, d_pass, max_d2, d_rows);
+    hipLaunchKernelGGL(pairb_robust_final_kernel<true>, dim3(npairs), b, 0, st, (const double*)d_rows, d_desc, d_state, d_rs, d_ts, d_out, d_info);
 }
 
 }  // namespace kss
