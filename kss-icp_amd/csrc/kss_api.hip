@@ -9,6 +9,7 @@
 #include "kss_ctx.hpp"
 #include "kss_gicp.hpp"
 #include "kss_robust.hpp"
+#include "kss_pair_device.hpp"
 
 extern "C" {
 
@@ -434,8 +435,9 @@ int kss_p2l_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const f
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
     {
         ProfScope ps(c, KSS_K_CORR_REDUCE);
-        launch_p2l_sums(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_tgt, d_nrm, n, nt, max_d2, (double*)c->p2l_rows.p,
-                        (double*)c->h_p2l_dev);
+        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, nullptr, max_d2}, d_tgt, d_nrm, n, nt, (double*)c->p2l_rows.p, nullptr};
+        launch_pair_rows(c->stream, a, PlaneMetric<false>(max_d2, nullptr));
+        launch_p2l_final(c->stream, a.rows, p2l_rows_blocks(n), (double*)c->h_p2l_dev);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -676,14 +678,21 @@ int kss_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, cons
     }
     {
         ProfScope ps(c, KSS_K_CORR_REDUCE);
+        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, nullptr, max_d2}, d_tgt, d_nrm, n, nt, (double*)c->p2l_rows.p, (float*)c->rob_keys.p};
         if (rs.autoscale) {
             // the keys carry the whole candidate test (a NaN is none); the point metric's bound is applied again, to the same effect
-            launch_robust_keys(c->stream, plane, d_src, nullptr, nullptr, d_idx, nullptr, d_tgt, d_nrm, n, nt, max_d2, (float*)c->rob_keys.p);
+            if (plane) launch_pair_rows(c->stream, a, PlaneRobustMetric<PAIR_KEY>());
+            else launch_pair_rows(c->stream, a, PointRobustMetric<PAIR_KEY>());
             launch_trim_select(c->stream, (const float*)c->rob_keys.p, n, plane ? std::numeric_limits<double>::infinity() : max_d2, 0.5,
                                (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p, nullptr);
         }
-        launch_robust_sums(c->stream, plane, d_src, nullptr, nullptr, d_idx, nullptr, d_tgt, d_nrm, n, nt, max_d2, rs, d_sel,
-                           (double*)c->p2l_rows.p, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
+        if (plane) {
+            launch_pair_rows(c->stream, a, PlaneRobustMetric<PAIR_ROBUST>(rs, d_sel));
+            launch_robust_plane_final(c->stream, a.rows, p2l_rows_blocks(n), rs, d_sel, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
+        } else {
+            launch_pair_rows(c->stream, a, PointRobustMetric<PAIR_ROBUST>(rs, d_sel));
+            launch_robust_point_final(c->stream, a.rows, p2l_rows_blocks(n), rs, d_sel, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
+        }
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -791,8 +800,9 @@ int kss_gicp_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
     {
         ProfScope ps(c, KSS_K_CORR_REDUCE);
-        launch_gicp_sums(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, d_tgt, d_tgt_normals, n, nt, max_d2, Rn,
-                         gp->epsilon, (double*)c->p2l_rows.p, (double*)c->h_p2l_dev);
+        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, max_d2}, d_tgt, d_tgt_normals, n, nt, (double*)c->p2l_rows.p, nullptr};
+        launch_pair_rows(c->stream, a, GicpMetric(gicp_rot_of(Rn), 1.0 - gp->epsilon));
+        launch_p2l_final(c->stream, a.rows, p2l_rows_blocks(n), (double*)c->h_p2l_dev);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -891,8 +901,9 @@ int kss_symm_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
     {
         ProfScope ps(c, KSS_K_CORR_REDUCE);
-        launch_symm_sums(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, d_tgt, d_tgt_normals, n, nt, max_d2, Rn,
-                         sp->align_normals, (double*)c->p2l_rows.p, (double*)c->h_p2l_dev);
+        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, max_d2}, d_tgt, d_tgt_normals, n, nt, (double*)c->p2l_rows.p, nullptr};
+        launch_pair_rows(c->stream, a, SymmMetric<PAIR_PLAIN>(gicp_rot_of(Rn), sp->align_normals));
+        launch_p2l_final(c->stream, a.rows, p2l_rows_blocks(n), (double*)c->h_p2l_dev);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -981,14 +992,15 @@ int kss_symm_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_
     }
     {
         ProfScope ps(c, KSS_K_CORR_REDUCE);
+        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, max_d2}, d_tgt, d_tgt_normals, n, nt, (double*)c->p2l_rows.p,
+                            (float*)c->rob_keys.p};
         if (rs.autoscale) {   // the keys carry the whole candidate test (a NaN is none)
-            launch_symm_robust_keys(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, d_tgt, d_tgt_normals, n, nt, max_d2, Rn,
-                                    sp->align_normals, (float*)c->rob_keys.p);
+            launch_pair_rows(c->stream, a, SymmMetric<PAIR_KEY>(gicp_rot_of(Rn), sp->align_normals));
             launch_trim_select(c->stream, (const float*)c->rob_keys.p, n, std::numeric_limits<double>::infinity(), 0.5,
                                (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p, nullptr);
         }
-        launch_symm_robust_sums(c->stream, d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, d_tgt, d_tgt_normals, n, nt, max_d2, Rn,
-                                sp->align_normals, rs, d_sel, (double*)c->p2l_rows.p, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
+        launch_pair_rows(c->stream, a, SymmMetric<PAIR_ROBUST>(gicp_rot_of(Rn), sp->align_normals, rs, d_sel));
+        launch_robust_plane_final(c->stream, a.rows, p2l_rows_blocks(n), rs, d_sel, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -48,23 +48,22 @@ struct kss_ctx {
     DevBuf tgt4, src0, cur[2], keys, partials, sums, nn_work, red_work, pair_red, state, cs, scratch_a,
         scratch_b, scratch_c, stage_src, stage_tgt, stage_idx, stage_d2, stage_out, g_counts, g_slot, g_start, g_cursor,
         g_bsums, g_sorted, g_list, g_count, g_bbox, g_partials, g_start2, g_pairs, g_stamps, g_pos, g_nnst, res_pos, res_wc, res_perm, pack_seg, reg_s, reg_t, reg_p, reg_all, reg_f, reg_g, oct_pts, oct_cen, oct_a, oct_b, oct_tmp, pre_partials, pre_state, g_rowpair, g_gate;
-    // point-to-plane ICP (kss_p2l.hip): per-pass idx / d2, source slot of each original index, partial rows, float normals
+    // point-to-plane ICP (kss_pair.hip): per-pass idx / d2, source slot of each original index, partial rows, float normals
     // (staged or computed) and their f64 form from the normals kernel
     DevBuf p2l_idx, p2l_d2, p2l_perm, p2l_rows, p2l_nrm, p2l_n64;
     // trimmed ICP (kss_trim.hip): the selection's histogram rows (one per workgroup, rewritten by every digit) and its
     // TRIM_NSTATE TrimState records; neither has to hold anything between passes
     DevBuf trim_rows, trim_state;
-    // robust ICP (kss_robust.hip): the keys its median is selected over where they are not the NN pass's d2
+    // robust ICP (kss_pair.hip): the keys its median is selected over where they are not the NN pass's d2
     DevBuf rob_keys;
-    // generalized ICP (kss_gicp.hip): the source's float normals (staged or computed)
+    // generalized ICP (kss_pair.hip): the source's float normals (staged or computed)
     DevBuf gicp_snrm;
     // the same for many pairs per call (kss_pairb.hip): per-pair descriptors, row -> pair table, packed normals computed at setup
     DevBuf pb_desc, pb_rowpair, pb_nrm;
     // robust ICP for many pairs: one RobustScale per pair, uploaded once per call
     DevBuf pb_rscale;
-    // generalized ICP for many pairs: the packed source normals (staged or computed), and the per-pair GicpPass
-    // table: the host writes the pinned copy after every host step, one copy per pass takes it to the device table.  Symmetric ICP
-    // for many pairs (2.18) uses all of them, with a table of SymmPass: byte buffers sized per call, a call is one or the other
+    // generalized and symmetric ICP for many pairs: the packed source normals (staged or computed), and the
+    // per-pair PairPass table: the host writes the pinned copy after every host step, one copy per pass takes it to the device table
     DevBuf pb_snrm, pb_gicp;
     void* h_gicp = nullptr; size_t h_gicp_cap = 0;
     void* h_gicp_dev = nullptr;   // (the pinned copy as the device sees it: KSS_GICP_TABLE_MAPPED, an A/B switch)

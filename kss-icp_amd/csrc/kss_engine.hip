@@ -10,6 +10,7 @@
 #include <limits>
 
 #include "kss_ctx.hpp"
+#include "kss_pair_device.hpp"
 
 namespace kss {
 
@@ -1908,6 +1909,9 @@ static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const dou
     return true;
 }
 
+// the rotation block of a row-major 4 x 4 (the float bits of the accumulated Matrix4f)
+static GicpRot rot_of(const float* F) { return GicpRot{{F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]}}; }
+
 static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
                      const int32_t* d_perm, kss_icp_result* res) {
     const int64_t ns = pl.g[0].ns, nt = pl.g[0].nt;
@@ -1925,6 +1929,8 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
     double* d_rec = (double*)c->h_p2l_dev;
     TrimState* d_state = (TrimState*)c->trim_state.p;
     const double* d_cut = M.trimmed ? &d_state[TRIM_NSTATE - 1].cut : nullptr;
+    float* d_keys = (float*)c->rob_keys.p;
+    const int nb = stream_blocks(ns);
     if (P.trace_n) *P.trace_n = 0;
     if (M.last_info) for (int q = 0; q < KSS_TRIM_NINFO; ++q) M.last_info[q] = 0.0;
     int it = 0;
@@ -1936,46 +1942,34 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
         KCHK(nn_pass(c, pl, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false));
         {
             ProfScope ps(c, KSS_K_CORR_REDUCE);
-            if (M.trimmed) launch_trim_select(c->stream, d_d2, ns, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
+            const hipStream_t st = c->stream;
+            const PairArgs a = {{nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, max_d2}, d_tgt, d_nrm, ns, nt, d_rows, d_keys};
+            const GicpRot Rn = rot_of(tr.fin);   // generalized, symmetric: the source normals turn with the transform accumulated so far
+            if (M.trimmed) launch_trim_select(st, d_d2, ns, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
             if (M.robust) {
                 const TrimState* d_sel = nullptr;
-                const float* F = tr.fin;   // (symmetric: the rotation of the transform accumulated so far, as in the unweighted branch below)
-                const float Rn[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
                 if (M.rs.autoscale) {   // the median key: the point metric's keys are the NN pass's d2, the plane metric's are written here
-                    const float* d_keys = d_d2;
-                    double bound = max_d2;
-                    if (M.plane) {
-                        if (M.symm)
-                            launch_symm_robust_keys(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn,
-                                                    M.symm_align, (float*)c->rob_keys.p);
-                        else
-                            launch_robust_keys(c->stream, true, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, (float*)c->rob_keys.p);
-                        d_keys = (const float*)c->rob_keys.p;
-                        bound = std::numeric_limits<double>::infinity();
-                    }
-                    launch_trim_select(c->stream, d_keys, ns, bound, 0.5, (unsigned*)c->trim_rows.p, d_state, nullptr);
+                    if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_KEY>(Rn, M.symm_align));
+                    else if (M.plane) launch_pair_rows(st, a, PlaneRobustMetric<PAIR_KEY>());
+                    launch_trim_select(st, M.plane ? d_keys : d_d2, ns, M.plane ? std::numeric_limits<double>::infinity() : max_d2, 0.5,
+                                       (unsigned*)c->trim_rows.p, d_state, nullptr);
                     d_sel = d_state + (TRIM_NSTATE - 1);
                 }
-                if (M.symm)
-                    launch_symm_robust_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn, M.symm_align,
-                                            M.rs, d_sel, d_rows, d_rec, d_rec + P2L_NSUMS);
-                else
-                    launch_robust_sums(c->stream, M.plane, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, M.rs, d_sel, d_rows,
-                                       d_rec, d_rec + P2L_NSUMS);
-            } else if (M.gicp) {   // the source normals turn with the transform accumulated so far
-                const float* F = tr.fin;
-                const float Rn[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
-                launch_gicp_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn, M.gicp_epsilon,
-                                 d_rows, d_rec);
-            } else if (M.symm) {   // the same rotation for the symmetric sums
-                const float* F = tr.fin;
-                const float Rn[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
-                launch_symm_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, ns, nt, max_d2, Rn, M.symm_align,
-                                 d_rows, d_rec);
-            } else if (M.plane)
-                launch_p2l_sums(c->stream, nullptr, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, ns, nt, max_d2, d_rows, d_rec, d_cut);
-            else
-                launch_trim_point_sums(c->stream, d_out, d_perm, d_idx, d_d2, d_tgt, ns, nt, d_cut, d_rows, d_rec);
+                if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_ROBUST>(Rn, M.symm_align, M.rs, d_sel));
+                else if (M.plane) launch_pair_rows(st, a, PlaneRobustMetric<PAIR_ROBUST>(M.rs, d_sel));
+                else launch_pair_rows(st, a, PointRobustMetric<PAIR_ROBUST>(M.rs, d_sel));
+                if (M.plane) launch_robust_plane_final(st, d_rows, nb, M.rs, d_sel, d_rec, d_rec + P2L_NSUMS);
+                else launch_robust_point_final(st, d_rows, nb, M.rs, d_sel, d_rec, d_rec + P2L_NSUMS);
+            } else if (M.plane) {
+                if (M.gicp) launch_pair_rows(st, a, GicpMetric(Rn, 1.0 - M.gicp_epsilon));
+                else if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_PLAIN>(Rn, M.symm_align));
+                else if (M.trimmed) launch_pair_rows(st, a, PlaneMetric<true>(max_d2, d_cut));
+                else launch_pair_rows(st, a, PlaneMetric<false>(max_d2, nullptr));
+                launch_p2l_final(st, d_rows, nb, d_rec);
+            } else {
+                launch_pair_rows(st, a, PointTrimMetric(d_cut));
+                launch_trim_point_final(st, d_rows, nb, d_rec);
+            }
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2057,7 +2051,7 @@ int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, 
 // ---- the same metrics for MANY pairs per call: kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch
 // (2.13: behind the NN pass the key launch (plane) and the selection when any pair has the automatic scale, then two sums launches),
 // kss_icp_gicp_batch (2.15: one copy of the per-pair pass table -- the rotation of every pair's fin and its e -- then two sums launches),
-// kss_icp_symm_batch (2.18: the same with the table of SymmPass -- the rotation and the pair's align_normals),
+// kss_icp_symm_batch (2.18: the same, the table's entry carrying the pair's align_normals),
 // kss_icp_symm_robust_batch (2.20: that table's copy, then the robust form's launches on the symmetric body) ----
 // pair_loop in lockstep over npairs >= 1 pairs.  Per pass: ONE NN pass over the pairs still active (idx / d2 by global source
 // index), ONE selection launch when trimmed, TWO sums launches (kss_pairb.hip), ONE stream synchronisation, then
@@ -2072,26 +2066,15 @@ struct DeferWait {   // the NN pass does not wait for its sums: the launches beh
 static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
                       const int32_t* d_perm, bool rob_select, kss_icp_result* results, double* info_all) {
     const int np = pl_in.npairs;
-    // generalized: every pair's GicpPass (pinned; e staged by pairs_run_dev) starts from the identity and follows the pair's fin
-    GicpPass* hgp = M.gicp ? (GicpPass*)c->h_gicp : nullptr;
-    auto gicp_rot_of = [](GicpPass& g, const float* F) {
-        const float R[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
-        std::memcpy(g.r, R, sizeof R);
+    // generalized, symmetric: every pair's PairPass (pinned; e / align staged by pairs_run_dev) starts from the identity and follows
+    // the pair's fin.  A/B switch: the kernel reads the pinned table across the bus instead of a device copy made per pass
+    PairPass* hpass = M.gicp || M.symm ? (PairPass*)c->h_gicp : nullptr;
+    const char* env_mapped = hpass ? getenv("KSS_GICP_TABLE_MAPPED") : nullptr;
+    const bool pass_mapped = env_mapped && atoi(env_mapped) != 0 && c->h_gicp_dev;
+    const PairPass* d_pass = hpass ? (pass_mapped ? (const PairPass*)c->h_gicp_dev : (const PairPass*)c->pb_gicp.p) : nullptr;
+    auto pass_rot = [hpass](int p, const float* F) {   // (the float bits pair_loop passes as Rn)
+        if (hpass) std::memcpy(hpass[p].r, rot_of(F).r, sizeof hpass[p].r);
     };
-    // A/B switch: the kernel reads the pinned table across the bus instead of a device copy made per pass
-    const char* env_mapped = hgp ? getenv("KSS_GICP_TABLE_MAPPED") : nullptr;
-    const bool gicp_mapped = env_mapped && atoi(env_mapped) != 0 && c->h_gicp_dev;
-    const GicpPass* d_gpass = hgp ? (gicp_mapped ? (const GicpPass*)c->h_gicp_dev : (const GicpPass*)c->pb_gicp.p) : nullptr;
-    // symmetric: every pair's SymmPass in the same pinned and device buffers (a call is either generalized or
-    // symmetric; align staged by pairs_run_dev), the same rotation bits, the same copy per pass and the same A/B switch
-    SymmPass* hsp = M.symm ? (SymmPass*)c->h_gicp : nullptr;
-    auto symm_rot_of = [](SymmPass& g, const float* F) {
-        const float R[9] = {F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]};
-        std::memcpy(g.r, R, sizeof R);
-    };
-    const char* env_smapped = hsp ? getenv("KSS_GICP_TABLE_MAPPED") : nullptr;
-    const bool symm_mapped = env_smapped && atoi(env_smapped) != 0 && c->h_gicp_dev;
-    const SymmPass* d_spass = hsp ? (symm_mapped ? (const SymmPass*)c->h_gicp_dev : (const SymmPass*)c->pb_gicp.p) : nullptr;
     const IcpPlan* plan = &pl_in;   // may change to the brute-force plan below
     IcpPlan brute_plan;
     std::vector<PairTrack> tr((size_t)np, PairTrack(P));
@@ -2103,8 +2086,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     for (int p = 0; p < np; ++p) {
         set_state(hs[p], I, 1, 0);
         mirror_state(bar, p, hs[p]);
-        if (hgp) gicp_rot_of(hgp[p], tr[p].fin);
-        if (hsp) symm_rot_of(hsp[p], tr[p].fin);
+        pass_rot(p, tr[p].fin);
     }
     const double max_d2 = P.max_corr_dist * P.max_corr_dist;
     int32_t* d_idx = (int32_t*)c->p2l_idx.p;
@@ -2138,35 +2120,30 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
         const PairState* d_state = c->last_state_dev;   // (a single pair on its own cell list has none: it is active)
         {
             ProfScope ps(c, KSS_K_CORR_REDUCE);
-            if (M.robust && M.symm) {   //  the symmetric form's table copy, then the robust form's launches on the symmetric body
-                if (!symm_mapped)
-                    HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hsp, (size_t)np * sizeof(SymmPass), hipMemcpyHostToDevice, c->stream));
-                if (rob_select)
-                    launch_pairb_symm_robust_select(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows,
-                                                    np, d_state, d_rs, d_spass, max_d2, (float*)c->rob_keys.p, d_ts);
-                launch_pairb_symm_robust_sums(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
-                                              d_state, d_rs, d_ts, d_spass, max_d2, (double*)c->p2l_rows.p, d_rec, d_info);
-            } else if (M.robust) {
-                if (rob_select)   // some pair takes its scale from the pass's median key
-                    launch_pairb_robust_select(c->stream, M.plane, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
-                                               d_state, d_rs, max_d2, (float*)c->rob_keys.p, d_ts);
-                launch_pairb_robust_sums(c->stream, M.plane, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np, d_state,
-                                         d_rs, d_ts, max_d2, (double*)c->p2l_rows.p, d_rec, d_info);
-            } else if (M.gicp) {
-                // the table as the host steps left it: the last pass's synchronisation has ordered those writes behind its copy
-                if (!gicp_mapped)
-                    HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hgp, (size_t)np * sizeof(GicpPass), hipMemcpyHostToDevice, c->stream));
-                launch_pairb_gicp_sums(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
-                                       d_state, d_gpass, max_d2, (double*)c->p2l_rows.p, d_rec);
-            } else if (M.symm) {   // the same ordering of the host steps' writes behind the last pass's copy
-                if (!symm_mapped)
-                    HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hsp, (size_t)np * sizeof(SymmPass), hipMemcpyHostToDevice, c->stream));
-                launch_pairb_symm_sums(c->stream, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
-                                       d_state, d_spass, max_d2, (double*)c->p2l_rows.p, d_rec);
+            const hipStream_t st = c->stream;
+            const PairbArgs a = {{nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, max_d2}, d_tgt, d_nrm, d_desc, d_row_pair, d_state, d_rs, d_ts,
+                                 d_pass, (double*)c->p2l_rows.p, (float*)c->rob_keys.p};
+            // the pass table as the host steps left it: the last pass's synchronisation has ordered those writes behind its copy
+            if (hpass && !pass_mapped) HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hpass, (size_t)np * sizeof(PairPass), hipMemcpyHostToDevice, st));
+            if (M.robust) {
+                if (rob_select) {   // some pair takes its scale from the pass's median key: the point metric's keys are the NN pass's d2
+                    if (M.symm) launch_pairb_rows<SymmMetric<PAIR_KEY>>(st, total_rows, a);
+                    else if (M.plane) launch_pairb_rows<PlaneRobustMetric<PAIR_KEY>>(st, total_rows, a);
+                    // (written keys carry the whole candidate test, a NaN is none: no bound)
+                    launch_pairb_robust_select(st, np, a, M.plane ? a.keys : d_d2, M.plane ? std::numeric_limits<double>::infinity() : max_d2);
+                }
+                if (M.symm) launch_pairb_rows<SymmMetric<PAIR_ROBUST>>(st, total_rows, a);
+                else if (M.plane) launch_pairb_rows<PlaneRobustMetric<PAIR_ROBUST>>(st, total_rows, a);
+                else launch_pairb_rows<PointRobustMetric<PAIR_ROBUST>>(st, total_rows, a);
+                launch_pairb_robust_final(st, M.plane, np, a, d_rec, d_info);
             } else {
-                if (M.trimmed) launch_pairb_select(c->stream, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
-                launch_pairb_sums(c->stream, M.plane, M.trimmed, d_out, d_perm, d_idx, d_d2, d_tgt, d_nrm, d_desc, d_row_pair, total_rows, np,
-                                  d_state, d_ts, max_d2, (double*)c->p2l_rows.p, d_rec);
+                if (M.trimmed) launch_pairb_select(st, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
+                if (M.gicp) launch_pairb_rows<GicpMetric>(st, total_rows, a);
+                else if (M.symm) launch_pairb_rows<SymmMetric<PAIR_PLAIN>>(st, total_rows, a);
+                else if (!M.plane) launch_pairb_rows<PointTrimMetric>(st, total_rows, a);
+                else if (M.trimmed) launch_pairb_rows<PlaneMetric<true>>(st, total_rows, a);
+                else launch_pairb_rows<PlaneMetric<false>>(st, total_rows, a);
+                launch_pairb_final(st, M.plane, np, a, d_rec);
             }
         }
         HIPCHK(c, hipGetLastError());
@@ -2193,8 +2170,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                     active[p] = 0; ++fin_here;
                     set_state(hs[p], I, 0, 0);
                 }
-                if (hgp) gicp_rot_of(hgp[p], tr[p].fin);   // the source normals turn with the transform accumulated so far
-                if (hsp) symm_rot_of(hsp[p], tr[p].fin);   // (the float bits pair_loop passes as Rn)
+                pass_rot(p, tr[p].fin);   // the source normals turn with the transform accumulated so far
                 mirror_state(bar, p, hs[p]);
             }
             finished.fetch_add(fin_here, std::memory_order_relaxed);
@@ -2288,21 +2264,16 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's table may be pageable and short-lived)
         if (rob_select && M.plane) KCHK(ensure(c, c->rob_keys, (size_t)pl.total_src * sizeof(float)));
     }
-    if (M.gicp) {   // the per-pair pass table: e = 1 - epsilon as launch_gicp_sums forms it; pairs_loop fills the rotations
-        KCHK(ensure(c, c->pb_gicp, (size_t)npairs * sizeof(GicpPass)));
-        KCHK(ensure_pinned(c, c->h_gicp, c->h_gicp_cap, (size_t)npairs * sizeof(GicpPass)));
+    if (M.gicp || M.symm) {   // the per-pair pass table: e = 1 - epsilon as pair_loop forms it, align as it passes it; pairs_loop fills the rotations
+        KCHK(ensure(c, c->pb_gicp, (size_t)npairs * sizeof(PairPass)));
+        KCHK(ensure_pinned(c, c->h_gicp, c->h_gicp_cap, (size_t)npairs * sizeof(PairPass)));
         HIPCHK(c, hipHostGetDevicePointer(&c->h_gicp_dev, c->h_gicp, 0));
-        GicpPass* hgp = (GicpPass*)c->h_gicp;
-        std::memset(hgp, 0, (size_t)npairs * sizeof(GicpPass));
-        for (int i = 0; i < npairs; ++i) hgp[i].e = 1.0 - gicp_eps[i];
-    }
-    if (M.symm) {   // the per-pair pass table in the generalized form's buffers: align as launch_symm_sums takes it; pairs_loop fills the rotations
-        KCHK(ensure(c, c->pb_gicp, (size_t)npairs * sizeof(SymmPass)));
-        KCHK(ensure_pinned(c, c->h_gicp, c->h_gicp_cap, (size_t)npairs * sizeof(SymmPass)));
-        HIPCHK(c, hipHostGetDevicePointer(&c->h_gicp_dev, c->h_gicp, 0));
-        SymmPass* hsp = (SymmPass*)c->h_gicp;
-        std::memset(hsp, 0, (size_t)npairs * sizeof(SymmPass));
-        for (int i = 0; i < npairs; ++i) hsp[i].align = symm_aligns[i];
+        PairPass* hpass = (PairPass*)c->h_gicp;
+        std::memset(hpass, 0, (size_t)npairs * sizeof(PairPass));
+        for (int i = 0; i < npairs; ++i) {
+            if (M.gicp) hpass[i].e = 1.0 - gicp_eps[i];
+            else hpass[i].align = symm_aligns[i];
+        }
     }
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
     KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));

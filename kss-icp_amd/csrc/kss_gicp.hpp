@@ -1,5 +1,5 @@
 // kss_gicp.hpp -- generalized ICP (plane-to-plane): the metric of one correspondence, ONE body for the device
-// kernel (kss_gicp.hip through kss_pair_device.hpp) and the C-ABI's host helper (kss_gicp_metric).
+// kernels (kss_pair.hip, kss_pairb.hip through kss_pair_device.hpp) and the C-ABI's host helper (kss_gicp_metric).
 // f64 +, -, *, / in the order written down at kss_icp_gicp in include/kssicp.h; the including translation unit is compiled with
 // fp contraction off, so nothing here becomes an fma.
 #pragma once
@@ -34,5 +34,11 @@ __host__ __device__ inline bool gicp_metric_of(const double nq[3], const double 
 struct GicpRot {
     float r[9];
 };
+// ... from the row-major 3 x 3 an entry point was given (null: identity)
+inline GicpRot gicp_rot_of(const float Rn[9]) {
+    GicpRot R;
+    for (int k = 0; k < 9; ++k) R.r[k] = Rn ? Rn[k] : (k % 4 == 0 ? 1.0f : 0.0f);
+    return R;
+}
 
 }  // namespace kss

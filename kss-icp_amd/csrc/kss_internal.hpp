@@ -331,29 +331,35 @@ void launch_normals(hipStream_t st, const float4* d_pts, int n, const int32_t* d
 int preshape_blocks(int64_t n);
 int stream_blocks(int64_t n);
 
-// point-to-plane sums (kss_p2l.hip): partial rows over p2l_rows_blocks(n) workgroups, then one workgroup writes the
-// KSS_P2L_NSUMS record to d_out (device or host-mapped).  Sources: d_src3 (packed float triples, original order) or d_src4
-// (float4; with d_perm: cell order, d_perm[i] = slot of original source i).  d_d2: NN distances (null: recomputed).
-// d_cut (trimmed ICP): the threshold is read from *d_cut on the device and kept means 0 <= d2 <= *d_cut; max_d2 is unused.
+// ---- the pair metrics' correspondence sums for one pair (kss_pair.hip) ----
+// One pass = [keys launch + selection] + ONE rows launch + ONE final launch.  The rows launch is pair_rows_kernel<M, SRC> over a
+// metric functor M (kss_pair_device.hpp): stream_blocks(n) workgroups of 256, lane t of workgroup b takes the sources
+// b * 256 + t + k * 256 * grid in ORIGINAL index order, M's per-source body, then block_sum's wave tree and fixed wave order
+// into one partial row per workgroup (M::KEYS: one key per source and no rows).  The bits depend on the source count only.
+// The batch walk (kss_pairb.hip) gives every pair exactly this assignment, so a pair's bits are the same alone and in a batch.
 static_assert(P2L_NSUMS == KSS_P2L_NSUMS, "kss_host_math.hpp and include/kssicp.h disagree");
-int p2l_rows_blocks(int64_t n);
-void launch_p2l_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
-                     const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
-                     double* d_rows, double* d_out, const double* d_cut = nullptr);
+// where the sources and the correspondences are: src3 (packed float triples, original order) or src4 (float4; with perm: cell
+// order, perm[i] = slot of original source i); d2: the NN distances (null with src3: recomputed); sn: the source normals as
+// packed float triples by ORIGINAL source index (generalized and symmetric forms)
+struct PairSrc {
+    const float* src3; const float4* src4; const int32_t* perm; const int32_t* idx; const float* d2; const float* sn;
+    double max_d2;
+};
+// the single-pair walk's arguments, by value: n sources against the target tgt / nrm of nt points; rows: stream_blocks(n) rows
+// of M::NC doubles, keys: n floats (M::KEYS)
+struct PairArgs {
+    PairSrc s;
+    const float* tgt; const float* nrm;
+    int64_t n, nt;
+    double* rows; float* keys;
+};
+int p2l_rows_blocks(int64_t n);   // = stream_blocks(n)
+// one launch of pair_rows_kernel<M, SRC>, SRC from s.src3 / s.perm (a metric without a form for packed float triples reads src4)
+template <class M>
+void launch_pair_rows(hipStream_t st, const PairArgs& a, const M& m);
 void launch_p2l_perm(hipStream_t st, const float4* d_src, int64_t n, int32_t* d_perm);
-void launch_p2l_final(hipStream_t st, const double* d_rows, int nrows, double* d_out);   // p2l_final_kernel over given rows
-
-// generalized ICP sums (kss_gicp.hip): launch_p2l_sums' sources, rows and record; d_sn3: the source normals as
-// packed float triples by ORIGINAL source index; Rn: the row-major 3x3 applied to them (null: identity); 0 < epsilon <= 1.
-void launch_gicp_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
-                      const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
-                      double max_d2, const float Rn[9], double epsilon, double* d_rows, double* d_out);
-
-// symmetric ICP sums (kss_symm.hip): launch_gicp_sums' arguments; align: 1 = n = nq - m where m . nq < 0, 0 = always
-// n = nq + m.
-void launch_symm_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
-                      const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
-                      double max_d2, const float Rn[9], int align, double* d_rows, double* d_out);
+// one workgroup: the fixed-order column sums of the plane record's rows into d_out (device or host-mapped), slot 31 as 0
+void launch_p2l_final(hipStream_t st, const double* d_rows, int nrows, double* d_out);
 
 // ---- trimmed ICP (kss_trim.hip) ----
 // What one digit of the radix select hands to the next, and the last one to the sums kernels of the same pass: the key
@@ -380,118 +386,67 @@ size_t trim_rows_bytes(int64_t n);
 // null); d_rows holds trim_rows_bytes(n)
 void launch_trim_select(hipStream_t st, const float* d_d2, int64_t n, double max_d2, double overlap, unsigned* d_rows,
                         TrimState* d_state, double* d_info);
-// the KSS_NSUMS record over the correspondences with 0 <= d2 <= *d_cut (slots 17..19 are 0)
-void launch_trim_point_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
-                            const float* d_tgt3, int64_t n, int64_t nt, const double* d_cut, double* d_rows, double* d_out);
+// the KSS_NSUMS record from the point metric's rows (slots 17..19 are 0)
+void launch_trim_point_final(hipStream_t st, const double* d_rows, int nrows, double* d_out);
 void launch_f64_to_f32(hipStream_t st, const double* d_in, int64_t n, float* d_out);
 
-// ---- robust ICP (kss_robust.hip) ----
+// ---- robust ICP ----
 // The scale of a call: fixed (c2 = scale^2) or automatic (K = (tune * 1.4826)^2 and min2 = min_scale^2, all formed on the
-// host; the pass's c2 = robust_scale2_of(median key) is derived by the sums kernels from the selection's TrimState).
+// host; the pass's c2 = robust_scale2_of(median key) is derived by the rows and final kernels from the selection's TrimState).
 struct RobustScale {
     int loss = 0, autoscale = 0;
     double c2 = 0.0, K = 0.0, min2 = 0.0;
 };
-// Sources as in launch_p2l_sums (d_src3, or d_src4 with an optional d_perm); d_d2: the NN pass's distances, or null with
-// d_src3 (recomputed).  plane: d_nrm3 given.
-// One launch: d_keys[i] = the selection key of source i (point: d2, plane: |r|), NaN where it is no candidate.
-void launch_robust_keys(hipStream_t st, bool plane, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
-                        const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2, float* d_keys);
-// Two launches: the weighted record (KSS_NSUMS or KSS_P2L_NSUMS doubles) into d_out and {m, c2, sum of weights, cnt} into
-// d_info.  d_sel: the TrimState the selection's last step left (automatic scale), null for the fixed one.  d_rows holds
-// p2l_rows_blocks(n) rows of KSS_P2L_NSUMS.
-void launch_robust_sums(hipStream_t st, bool plane, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
-                        const float* d_d2, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt, double max_d2,
-                        const RobustScale& rs, const TrimState* d_sel, double* d_rows, double* d_out, double* d_info);
+// the weighted record's final launches: the column sums of d_rows (KSS_P2L_NSUMS or KSS_NSUMS doubles) into d_out and {m, c2,
+// sum of weights, cnt} into d_info.  d_sel: the TrimState the selection's last step left (automatic scale), null for the fixed one.
 void launch_robust_plane_final(hipStream_t st, const double* d_rows, int nrows, const RobustScale& rs, const TrimState* d_sel, double* d_out,
-                               double* d_info);   // robust_plane_final_kernel over given rows
+                               double* d_info);
+void launch_robust_point_final(hipStream_t st, const double* d_rows, int nrows, const RobustScale& rs, const TrimState* d_sel, double* d_out,
+                               double* d_info);
 
-// ---- robust symmetric ICP (kss_symm_robust.hip) ----
-// launch_symm_sums' sources, normals, Rn and align with launch_robust_sums' scale, selection, rows, record and info.
-// One launch: d_keys[i] = (float)|r| of source i on the symmetric metric, NaN where it is no candidate.
-void launch_symm_robust_keys(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
-                             const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
-                             double max_d2, const float Rn[9], int align, float* d_keys);
-// Two launches: the weighted rows, then robust_plane_final_kernel.
-void launch_symm_robust_sums(hipStream_t st, const float* d_src3, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
-                             const float* d_d2, const float* d_sn3, const float* d_tgt3, const float* d_nrm3, int64_t n, int64_t nt,
-                             double max_d2, const float Rn[9], int align, const RobustScale& rs, const TrimState* d_sel, double* d_rows,
-                             double* d_out, double* d_info);
 
-// ---- point-to-plane and trimmed ICP for many pairs per call (kss_pairb.hip) ----
+// ---- the same metrics for many pairs per call (kss_pairb.hip) ----
 // one pair (or one segment of kss_trim_threshold_batch) as the batched kernels see it
 struct alignas(16) PairbDesc {
     int64_t src_base, ns;      // the pair's sources in the batch-wide per-source arrays (idx, d2, perm)
     int64_t tgt_off, nt;       // its target in the caller's packed float triples (points), normals alike
     double overlap;
-    int32_t row_base, nrows;   // its partial rows: stream_blocks(ns) of them, the single-pair kernels' count
+    int32_t row_base, nrows;   // its partial rows: stream_blocks(ns) of them, the single-pair kernel's count
 };
-// one launch: every active pair's TrimState into d_ts[pair] and {m, k, tau, kept} into d_info[pair * KSS_TRIM_NINFO]
-// (d_state: the NN pass's per-pair states, null: every pair is active)
-void launch_pairb_select(hipStream_t st, const float* d_d2, const PairbDesc* d_desc, int npairs, const PairState* d_state, double max_d2,
-                         TrimState* d_ts, double* d_info);
-// two launches: every active pair's record into d_out[pair * KSS_P2L_NSUMS] (the point metric fills KSS_NSUMS of them)
-void launch_pairb_sums(hipStream_t st, bool plane, bool trimmed, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx,
-                       const float* d_d2, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
-                       int total_rows, int npairs, const PairState* d_state, const TrimState* d_ts, double max_d2, double* d_rows,
-                       double* d_out);
-// ---- robust ICP for many pairs per call (kss_pairb.hip): d_rs holds one RobustScale per pair ----
-// the median key of every active AUTOMATIC pair into d_ts[pair] (the others' entries are not written): the plane metric's key
-// launch (|r| into d_keys by global source index) and the selection over them; the point metric selects over d_d2 (one launch)
-void launch_pairb_robust_select(hipStream_t st, bool plane, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
-                                const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair, int total_rows,
-                                int npairs, const PairState* d_state, const RobustScale* d_rs, double max_d2, float* d_keys, TrimState* d_ts);
-// two launches: every active pair's weighted record into d_out[pair * KSS_P2L_NSUMS] and {m, c2, sum of weights, cnt} into
-// d_info[pair * KSS_ROBUST_NINFO]
-void launch_pairb_robust_sums(hipStream_t st, bool plane, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
-                              const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair, int total_rows,
-                              int npairs, const PairState* d_state, const RobustScale* d_rs, const TrimState* d_ts, double max_d2,
-                              double* d_rows, double* d_out, double* d_info);
-
-// ---- generalized ICP for many pairs per call (kss_pairb.hip) ----
-// what one pass of one pair needs beyond its descriptor: the rotation block of the transform accumulated so far (row-major, the
-// float bits launch_gicp_sums takes as Rn) and e = 1 - epsilon.  One entry per pair, rewritten by the host before every pass.
-struct GicpPass {
-    float r[9];
-    double e;
-};
-static_assert(sizeof(GicpPass) == 48, "the host and the device table share this layout");
-// two launches: every active pair's record into d_out[pair * KSS_P2L_NSUMS].  d_sn3: the source normals packed like the
-// sources (by global original index); d_pass: one GicpPass per pair (device memory, as of this pass)
-void launch_pairb_gicp_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
-                            const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
-                            int total_rows, int npairs, const PairState* d_state, const GicpPass* d_pass, double max_d2, double* d_rows,
-                            double* d_out);
-
-// ---- symmetric ICP for many pairs per call (kss_pairb.hip) ----
-// what one pass of one pair needs beyond its descriptor: the rotation block of the transform accumulated so far (row-major, the
-// float bits launch_symm_sums takes as Rn) and the pair's align_normals.  One entry per pair; the host rewrites the rotation
-// before every pass, the align is staged once per call.  The table travels as GicpPass does (the same pinned and device buffers).
-struct SymmPass {
+// What one pass of one pair needs beyond its descriptor (generalized and symmetric forms): the rotation block of the transform
+// accumulated so far (row-major, the float bits the single-pair call takes as Rn), the pair's align_normals (symmetric) and
+// e = 1 - epsilon (generalized).  One entry per pair; the host rewrites the rotations before every pass, align / e are staged
+// once per call.
+struct PairPass {
     float r[9];
     int32_t align;
+    double e;
 };
-static_assert(sizeof(SymmPass) == 40, "the host and the device table share this layout");
-// two launches: every active pair's record into d_out[pair * KSS_P2L_NSUMS].  d_sn3: the source normals packed like the
-// sources (by global original index); d_pass: one SymmPass per pair (device memory, as of this pass)
-void launch_pairb_symm_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
-                            const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc, const int32_t* d_row_pair,
-                            int total_rows, int npairs, const PairState* d_state, const SymmPass* d_pass, double max_d2, double* d_rows,
-                            double* d_out);
-
-// ---- robust symmetric ICP for many pairs per call (kss_pairb.hip): d_rs and d_pass hold one entry per pair ----
-// two launches: (float)|r| on the symmetric metric of every active AUTOMATIC pair's sources into d_keys by global source index
-// (NaN: no candidate), then the median key into d_ts[pair] (the others' entries are not written)
-void launch_pairb_symm_robust_select(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
-                                     const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc,
-                                     const int32_t* d_row_pair, int total_rows, int npairs, const PairState* d_state, const RobustScale* d_rs,
-                                     const SymmPass* d_pass, double max_d2, float* d_keys, TrimState* d_ts);
-// two launches: every active pair's weighted record into d_out[pair * KSS_P2L_NSUMS] and {m, c2, sum of weights, cnt} into
-// d_info[pair * KSS_ROBUST_NINFO]
-void launch_pairb_symm_robust_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
-                                   const float* d_sn3, const float* d_tgt3, const float* d_nrm3, const PairbDesc* d_desc,
-                                   const int32_t* d_row_pair, int total_rows, int npairs, const PairState* d_state, const RobustScale* d_rs,
-                                   const TrimState* d_ts, const SymmPass* d_pass, double max_d2, double* d_rows, double* d_out, double* d_info);
+static_assert(sizeof(PairPass) == 48, "the host and the device table share this layout");
+// The batch walk's arguments, by value: the sources and the clouds batch-wide (s.src3 is null; s.sn packed like the sources, by
+// global original index), the per-pair tables -- desc, state (the NN pass's per-pair states, null: every pair is active), rs
+// (robust: one RobustScale per pair), ts (trimmed: the selection's TrimState per pair; robust: the median key's, written for
+// the automatic pairs alone), pass (generalized / symmetric) --, the row -> pair table, total_rows rows and the batch-wide keys.
+struct PairbArgs {
+    PairSrc s;
+    const float* tgt; const float* nrm;
+    const PairbDesc* desc; const int32_t* row_pair; const PairState* state; const RobustScale* rs; TrimState* ts; const PairPass* pass;
+    double* rows; float* keys;
+};
+// one launch of pairb_rows_kernel<M, perm given> over total_rows = the sum of the pairs' stream_blocks(ns) workgroups:
+// every active pair's rows (M::KEYS: every active automatic pair's keys by global source index, NaN: no candidate)
+template <class M>
+void launch_pairb_rows(hipStream_t st, int total_rows, const PairbArgs& a);
+// one launch each, one workgroup per pair:
+// every active pair's TrimState into d_ts[pair] and {m, k, tau, kept} into d_info[pair * KSS_TRIM_NINFO]
+void launch_pairb_select(hipStream_t st, const float* d_d2, const PairbDesc* d_desc, int npairs, const PairState* d_state, double max_d2,
+                         TrimState* d_ts, double* d_info);
+// the median key of every active AUTOMATIC pair into a.ts[pair] (the others' entries are not written), over d_keys within bound
+void launch_pairb_robust_select(hipStream_t st, int npairs, const PairbArgs& a, const float* d_keys, double bound);
+// every active pair's record into d_out[pair * KSS_P2L_NSUMS] (the point metric fills KSS_NSUMS of them) ...
+void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out);
+// ... and the weighted one, with {m, c2, sum of weights, cnt} into d_info[pair * KSS_ROBUST_NINFO]
+void launch_pairb_robust_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out, double* d_info);
 
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,

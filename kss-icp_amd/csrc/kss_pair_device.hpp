@@ -1,12 +1,15 @@
-// kss_pair_device.hpp -- the device code that the single-pair kernels (kss_p2l.hip, kss_trim.hip, kss_robust.hip, kss_symm_robust.hip) and the batched
-// ones (kss_pairb.hip) share, so that the arithmetic of a correspondence and the logic of the selection exist ONCE:
+// kss_pair_device.hpp -- the device code of the pair metrics (point-to-plane, trimmed, robust, generalized, symmetric and robust
+// symmetric ICP), for one pair (kss_pair.hip) and for many pairs per call (kss_pairb.hip):
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
-//   gicp_source                      the same for generalized ICP (kss_gicp.hip; in a batch: pairb_gicp_rows_kernel),
-//   symm_source                      the same for symmetric ICP (kss_symm.hip; in a batch: pairb_symm_rows_kernel; weighted:
-//                                    kss_symm_robust.hip),
+//   gicp_source / symm_source        the same for generalized and for symmetric ICP,
+//   the metric functors              one small struct per metric: the uniform parameters of a pass and the call of its body,
+//   pair_walk                        the ONE walk both forms run: a lane's sources in steps of the grid, the functor's body per
+//                                    source, then block_sum and the row store (or, for a keys metric, one key per source),
 //   p2l_rows_column_sum              the fixed-order column sums of the plane metric's rows,
 //   trim_key / trim_resolve_counts   the candidate test and the resolution of one radix digit from a lane's eight bin counts.
-// A pair's bits are the same alone and inside a batch because both forms run these bodies in the same order.
+// pair_rows_kernel<M, SRC> (kss_pair.hip) gives workgroup b of stream_blocks(n) the sources b * 256 + t + k * 256 * grid;
+// pairb_rows_kernel<M, PERM> (kss_pairb.hip) gives workgroup b of a pair's stream_blocks(ns_p) the same sources of that pair.  A
+// pair's bits are the same alone and inside a batch because both are this one walk over the same bodies.
 #pragma once
 #include "kss_device.hpp"
 #include "kss_gicp.hpp"
@@ -414,6 +417,156 @@ __device__ __forceinline__ void trim_point_source(double (&acc)[NSUMS], const fl
             for (int l = 0; l < 3; ++l) acc[7 + 3 * k + l] += ws[k] * q[l];
         acc[16] += w * d2;
         acc[19] += 1.0;
+    }
+}
+
+// ---- the metric functors and the walk ----------------------------------------------------------------------
+// c2 of a robust pass, derived by every workgroup that needs it from the selection's last TrimState (sel: not read with a fixed
+// scale): one f64 product or two, the same bits everywhere
+__device__ __forceinline__ double robust_pass_c2(const RobustScale& rs, bool plane, const TrimState* __restrict__ sel) {
+    if (!rs.autoscale) return rs.c2;
+    const double med = sel->cut;   // the median key widened (-1: no candidate)
+    return med >= 0.0 ? robust_scale2_of(plane, rs.K, med, rs.min2) : 0.0;
+}
+
+// A metric M carries the uniform parameters of one pass of one pair.  It is built on the host from the values of a single pair
+// (and travels into pair_rows_kernel by value) or on the device from the per-pair tables at pair p (pairb_rows_kernel); begin()
+// then reads what the pass left in device memory (the cut, the median key), once per workgroup.  NC: the columns of its rows;
+// KEYS: it writes one selection key per source and no rows; F3: it has a form for packed float triples (PairSrc::src3).
+// source<SRC>(acc, s, tgt, nrm, i, nt, key) is the body's call, unchanged.
+template <bool TRIM>
+struct PlaneMetric {   // plane metric, untrimmed (lim = max_d2) or trimmed (lim = the pass's cut)
+    static constexpr int NC = P2L_NSUMS;
+    static constexpr bool KEYS = false, F3 = true;
+    const double* cut;
+    double lim;
+    PlaneMetric(double max_d2, const double* cut_) : cut(cut_), lim(max_d2) {}
+    __device__ PlaneMetric(const PairbArgs& a, int p) : cut(&a.ts[p].cut), lim(a.s.max_d2) {}
+    __device__ void begin() { if constexpr (TRIM) lim = *cut; }   // tau of this pass (-1: no candidate), written by the selection
+    template <int SRC>
+    __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float* nrm, int64_t i, int64_t nt, float*) const {
+        p2l_source<SRC, TRIM>(acc, s.src3, s.src4, s.perm, s.idx, s.d2, tgt, nrm, i, nt, lim);
+    }
+};
+struct PointTrimMetric {   // point metric over the correspondences at or below the pass's cut
+    static constexpr int NC = NSUMS;
+    static constexpr bool KEYS = false, F3 = false;
+    const double* cut;
+    double lim = 0.0;
+    explicit PointTrimMetric(const double* cut_) : cut(cut_) {}
+    __device__ PointTrimMetric(const PairbArgs& a, int p) : cut(&a.ts[p].cut) {}
+    __device__ void begin() { lim = *cut; }
+    template <int SRC>
+    __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float*, int64_t i, int64_t nt, float*) const {
+        trim_point_source<SRC == SRC_F4_PERM>(acc, s.src4, s.perm, s.idx, s.d2, tgt, i, nt, lim);
+    }
+};
+// the scale of a robust pass: the pair's RobustScale and where its selection left the median key
+struct RobustPass {
+    RobustScale rs;
+    const TrimState* sel = nullptr;
+    RobustArg ra;
+    __host__ __device__ RobustPass() {}
+    __host__ __device__ RobustPass(const RobustScale& rs_, const TrimState* sel_) : rs(rs_), sel(sel_) {}
+    __device__ RobustPass(const PairbArgs& a, int p) : rs(a.rs[p]), sel(a.ts + p) {}
+    __device__ void begin(bool plane) { ra.loss = rs.loss; ra.c2 = robust_pass_c2(rs, plane, sel); }
+};
+template <int MODE>
+struct PlaneRobustMetric {   // plane metric weighted (PAIR_ROBUST) or its keys |r| (PAIR_KEY)
+    static constexpr int NC = P2L_NSUMS;
+    static constexpr bool KEYS = MODE == PAIR_KEY, F3 = true;
+    RobustPass rp;
+    PlaneRobustMetric() {}
+    PlaneRobustMetric(const RobustScale& rs, const TrimState* sel) : rp(rs, sel) {}
+    __device__ PlaneRobustMetric(const PairbArgs& a, int p) : rp(a, p) {}
+    __device__ void begin() { if constexpr (!KEYS) rp.begin(true); }
+    template <int SRC>
+    __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float* nrm, int64_t i, int64_t nt, float* key) const {
+        RobustArg ra = rp.ra;
+        ra.key = key;
+        p2l_source<SRC, true, MODE>(acc, s.src3, s.src4, s.perm, s.idx, s.d2, tgt, nrm, i, nt, s.max_d2, ra);
+    }
+};
+template <int MODE>
+struct PointRobustMetric {   // point metric weighted, or its keys d2 (packed float triples: kss_robust_sums; the loops select over the NN pass's d2)
+    static constexpr int NC = NSUMS;
+    static constexpr bool KEYS = MODE == PAIR_KEY, F3 = true;
+    RobustPass rp;
+    PointRobustMetric() {}
+    PointRobustMetric(const RobustScale& rs, const TrimState* sel) : rp(rs, sel) {}
+    __device__ PointRobustMetric(const PairbArgs& a, int p) : rp(a, p) {}
+    __device__ void begin() { if constexpr (!KEYS) rp.begin(false); }
+    template <int SRC>
+    __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float*, int64_t i, int64_t nt, float* key) const {
+        RobustArg ra = rp.ra;
+        ra.key = key;
+        trim_point_source<SRC == SRC_F4_PERM, MODE, SRC == SRC_F3>(acc, s.src4, s.perm, s.idx, s.d2, tgt, i, nt, s.max_d2, s.src3, ra);
+    }
+};
+struct GicpMetric {   // generalized: the rotation applied to the source normals and e = 1 - epsilon
+    static constexpr int NC = P2L_NSUMS;
+    static constexpr bool KEYS = false, F3 = true;
+    GicpRot Rn;
+    double e;
+    GicpMetric(const GicpRot& Rn_, double e_) : Rn(Rn_), e(e_) {}
+    __device__ GicpMetric(const PairbArgs& a, int p) {   // pass[p] is the same for every lane of the workgroup: one uniform load
+        const PairPass pp = a.pass[p];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rn.r[k] = pp.r[k];
+        e = pp.e;
+    }
+    __device__ void begin() {}
+    template <int SRC>
+    __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float* nrm, int64_t i, int64_t nt, float*) const {
+        gicp_source<SRC>(acc, s.src3, s.src4, s.perm, s.idx, s.d2, s.sn, tgt, nrm, i, nt, s.max_d2, Rn, e);
+    }
+};
+template <int MODE>
+struct SymmMetric {   // symmetric: that rotation and align_normals; unweighted, weighted, or the weighted form's keys |r|
+    static constexpr int NC = P2L_NSUMS;
+    static constexpr bool KEYS = MODE == PAIR_KEY, F3 = true;
+    GicpRot Rn;
+    int align;
+    RobustPass rp;
+    SymmMetric(const GicpRot& Rn_, int align_) : Rn(Rn_), align(align_) {}
+    SymmMetric(const GicpRot& Rn_, int align_, const RobustScale& rs, const TrimState* sel) : Rn(Rn_), align(align_), rp(rs, sel) {}
+    __device__ SymmMetric(const PairbArgs& a, int p) {
+        const PairPass pp = a.pass[p];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rn.r[k] = pp.r[k];
+        align = pp.align;
+        if constexpr (MODE == PAIR_ROBUST) rp = RobustPass(a, p);
+    }
+    __device__ void begin() { if constexpr (MODE == PAIR_ROBUST) rp.begin(true); }
+    template <int SRC>
+    __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float* nrm, int64_t i, int64_t nt, float* key) const {
+        RobustArg ra = rp.ra;
+        ra.key = key;
+        symm_source<SRC, MODE>(acc, s.src3, s.src4, s.perm, s.idx, s.d2, s.sn, tgt, nrm, i, nt, s.max_d2, Rn, align, ra);
+    }
+};
+
+// The walk: this lane's sources base + first, base + first + step, ... below base + n against the target tgt / nrm of nt points.
+// Rows metric: the accumulators from zero, block_sum, row blockIdx.x of rows.  Keys metric: keys[source] = its key, preset to the
+// quiet NaN (no candidate); no accumulator is read and nothing is summed.  Needs blockDim.x == P2L_THREADS.
+template <class M, int SRC>
+__device__ __forceinline__ void pair_walk(const M& m, const PairSrc& s, const float* tgt, const float* nrm, int64_t base, int64_t first, int64_t n,
+                                          int64_t step, int64_t nt, double* __restrict__ rows, float* __restrict__ keys) {
+    constexpr int NC = M::NC;
+    double acc[NC];
+    if constexpr (M::KEYS) {
+        for (int64_t i = first; i < n; i += step) {
+            float key = __uint_as_float(0x7fc00000u);
+            m.template source<SRC>(acc, s, tgt, nrm, base + i, nt, &key);
+            keys[base + i] = key;
+        }
+    } else {
+        __shared__ double sh[P2L_THREADS / 64][NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+        for (int64_t i = first; i < n; i += step) m.template source<SRC>(acc, s, tgt, nrm, base + i, nt, nullptr);
+        const double r = block_sum<NC>(acc, sh);
+        if (threadIdx.x < NC) rows[(int64_t)blockIdx.x * NC + threadIdx.x] = r;
     }
 }
 

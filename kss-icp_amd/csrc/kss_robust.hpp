@@ -1,5 +1,5 @@
 // kss_robust.hpp -- robust ICP: the M-estimator weight and the per-pass scale, ONE body each for the device
-// kernels (kss_robust.hip through kss_pair_device.hpp) and the C-ABI's host helpers (kss_robust_weight, kss_robust_scale2).
+// kernels (kss_pair.hip, kss_pairb.hip through kss_pair_device.hpp) and the C-ABI's host helpers (kss_robust_weight, kss_robust_scale2).
 // f64 +, -, *, / and one sqrt (Huber); nothing here can be contracted into an fma.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -18,9 +18,9 @@
 // (First form: a one-workgroup scan launch behind every histogram launch, six launches of 5-8 us each = 37 us at 100k keys;
 // every launch costs that whatever it does, so the scans moved into the launches that need their answer.)
 //
-// Point-metric sums.  trim_point_rows_kernel has p2l_rows_kernel's shape (stream_blocks(n) workgroups of 256, sources in
-// original index order through perm, block_sum) on accumulate_corr's arithmetic; trim_point_final_kernel adds the rows with
-// rows_column_sum's fixed order.  The plane metric uses p2l_rows_kernel<SRC, true> (kss_p2l.hip), which reads the same cut.
+// Point-metric sums.  The rows are pair_rows_kernel<PointTrimMetric, SRC>'s (kss_pair.hip: the walk of every pair metric, on
+// accumulate_corr's arithmetic); trim_point_final_kernel adds them with rows_column_sum's fixed order.  The plane metric uses
+// pair_rows_kernel<PlaneMetric<true>, SRC>, which reads the same cut.
 #pragma clang fp contract(off)
 
 #include "kss_pair_device.hpp"
@@ -144,23 +144,7 @@ void launch_trim_select(hipStream_t st, const float* d_d2, int64_t n, double max
 
 size_t trim_rows_bytes(int64_t n) { return 2 * (size_t)trim_hist_blocks(n) * TRIM_BINS * sizeof(unsigned); }
 
-// ---- point-metric sums over the kept correspondences ---------------------------------------------------------------------
-template <bool PERM>
-__global__ __launch_bounds__(TRIM_THREADS) void trim_point_rows_kernel(const float4* __restrict__ src4, const int32_t* __restrict__ perm,
-                                                                       const int32_t* __restrict__ idx, const float* __restrict__ d2_in,
-                                                                       const float* __restrict__ tgt, int64_t n, int64_t nt,
-                                                                       const double* __restrict__ cut_ptr, double* __restrict__ rows) {
-    __shared__ double sh[TRIM_THREADS / 64][NSUMS];
-    double acc[NSUMS];
-#pragma unroll
-    for (int c = 0; c < NSUMS; ++c) acc[c] = 0.0;
-    const double cut = *cut_ptr;   // tau of this pass (-1: no candidate), written by the last selection step
-    for (int64_t i = (int64_t)blockIdx.x * TRIM_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TRIM_THREADS)
-        trim_point_source<PERM>(acc, src4, perm, idx, d2_in, tgt, i, nt, cut);   // (kss_pair_device.hpp)
-    const double r = block_sum<NSUMS>(acc, sh);
-    if (threadIdx.x < NSUMS) rows[(int64_t)blockIdx.x * NSUMS + threadIdx.x] = r;
-}
-
+// ---- point-metric sums over the kept correspondences: the final launch ----------------------------------------------------
 // slots 17 and 18 stay 0 as in an ICP iteration of kss_icp, 19 is 0
 __global__ __launch_bounds__(TRIM_THREADS) void trim_point_final_kernel(const double* __restrict__ rows, int nrows, double* __restrict__ out) {
     __shared__ double shg[ROWSUM_GROUPS][NSUMS];
@@ -168,14 +152,8 @@ __global__ __launch_bounds__(TRIM_THREADS) void trim_point_final_kernel(const do
     if (threadIdx.x < NSUMS) out[threadIdx.x] = threadIdx.x >= 17 ? 0.0 : v;
 }
 
-void launch_trim_point_sums(hipStream_t st, const float4* d_src4, const int32_t* d_perm, const int32_t* d_idx, const float* d_d2,
-                            const float* d_tgt3, int64_t n, int64_t nt, const double* d_cut, double* d_rows, double* d_out) {
-    const int nb = stream_blocks(n);
-    if (d_perm)
-        hipLaunchKernelGGL(trim_point_rows_kernel<true>, dim3(nb), dim3(TRIM_THREADS), 0, st, d_src4, d_perm, d_idx, d_d2, d_tgt3, n, nt, d_cut, d_rows);
-    else
-        hipLaunchKernelGGL(trim_point_rows_kernel<false>, dim3(nb), dim3(TRIM_THREADS), 0, st, d_src4, d_perm, d_idx, d_d2, d_tgt3, n, nt, d_cut, d_rows);
-    hipLaunchKernelGGL(trim_point_final_kernel, dim3(1), dim3(TRIM_THREADS), 0, st, (const double*)d_rows, nb, d_out);
+void launch_trim_point_final(hipStream_t st, const double* d_rows, int nrows, double* d_out) {
+    hipLaunchKernelGGL(trim_point_final_kernel, dim3(1), dim3(TRIM_THREADS), 0, st, d_rows, nrows, d_out);
 }
 
 }  // namespace kss

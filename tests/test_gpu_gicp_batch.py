@@ -137,6 +137,24 @@ def test_row_boundary_sizes(pkg, ctx):
     assert sum(r.iterations >= 2 for r in res) >= 3
 
 
+def test_pair_above_the_row_cap(pkg, ctx):
+    """stream_blocks saturates at 2048 rows: for a pair of more than 2048 * 256 sources the grid-stride term of the walk is live.
+    Two passes of a batch {300 sources, 524 800 sources} against the single-pair calls.  (The large pair's source normals are the
+    radial directions -- the surface is star-shaped --, not 524 800 computed ones: the comparison is of bits, whatever the normals.)"""
+    Sy = pkg.synth
+    src, tgt = Sy.make_pair(60, 524800, R=Sy.rot_axis_angle(Sy.sphere(7060, 1)[0], np.deg2rad(5.0)), t=(0.02, -0.01, 0.03), shape="bumpy")
+    sn = (src / np.sqrt((src.astype(F64) ** 2).sum(axis=1, keepdims=True))).astype(F32)
+    big = Pair(ctx, src, tgt[::175], sn=sn)
+    small = _halves(pkg, ctx, 61, 300, 7.0)
+    assert len(big.src) == 524800 > 2048 * 256 and len(big.tgt) <= 3000 and len(small.src) == 300
+    pairs = [small, big]
+    res, _ = _run(pkg, ctx, pairs, max_iterations=2)
+    for i, (r, pr) in enumerate(zip(res, pairs)):
+        single = pr.single(pkg, max_iterations=2)
+        assert single["iterations"] == 2
+        _check_record(r, single, len(pr.src), i)
+
+
 # ---- test 3: order and split ----
 def test_order_and_split(pkg, ctx, eight):
     n = len(eight)

@@ -371,6 +371,23 @@ def test_more_pairs_than_compute_units(pkg, ctx):
 
 
 # ---- test 8: device variants, computed normals ----
+def test_pair_above_the_row_cap(pkg, ctx):
+    """stream_blocks saturates at 2048 rows: for a pair of more than 2048 * 256 sources the grid-stride term of the walk is live.
+    Two passes each of the plane metric, the trimmed point metric and the trimmed plane metric, against the single-pair calls."""
+    src, tgt = _bumpy(pkg, 60, 524800, 5.0)
+    big = Pair(ctx, src, tgt[::175])
+    small = Pair(ctx, *_bumpy(pkg, 61, 2000, 7.0, n_src=300))
+    assert len(big.src) == 524800 > 2048 * 256 and len(big.tgt) <= 3000 and len(small.src) == 300
+    pairs = [small, big]
+    for kind in ("p2l", TR.POINT, TR.PLANE):
+        ov = None if kind == "p2l" else np.array([0.6, 0.8], F64)
+        res, info, _ = _run_batch(ctx, pairs, kind, overlaps=ov, max_iterations=2)
+        for i, (r, pr) in enumerate(zip(res, pairs)):
+            single = pr.single(kind, overlap=1.0 if ov is None else float(ov[i]), max_iterations=2)
+            assert single["iterations"] == 2
+            _check_record(r, single, len(pr.src), i, None if info is None else info[i])
+
+
 def test_dev_variants_and_computed_normals(ctx, six):
     import torch
     pairs = [six[1], six[4], six[2]]
