@@ -147,7 +147,7 @@ int kss_cov(kss_ctx *ctx, const float *src, const float *tgt, const int32_t *idx
             int64_t nt, double max_d2, double sums[KSS_NSUMS]);
 int kss_cov_dev(kss_ctx *ctx, const float *d_src, const float *d_tgt, const int32_t *d_idx, int64_t n,
                 int64_t nt, double max_d2, double sums[KSS_NSUMS]);
-/* host-side: rigid transform (Umeyama without scaling, 3x3 SVD) from the sums; row-major 4x4 */
+/* host-side: rigid transform (Umeyama without scaling, 3x3 SVD) from the sums; row-major 4x4 (with the scale: kss_sim_from_sums) */
 int kss_rigid_from_sums(const double sums[KSS_NSUMS], float T[16]);
 
 /* ---- (a4,a5) rotation search: initRegistration_Rotation(), :222-296 + :430-450 ----
@@ -209,7 +209,8 @@ enum { KSS_NN_AUTO = 0, KSS_NN_BRUTE = 1, KSS_NN_GRID = 2 };
 
 enum { KSS_STATE_NOT_CONVERGED = 0, KSS_STATE_ITERATIONS = 1, KSS_STATE_TRANSFORM = 2,
        KSS_STATE_ABS_MSE = 3, KSS_STATE_REL_MSE = 4, KSS_STATE_NO_CORRESPONDENCES = 5,
-       KSS_STATE_DEGENERATE = 6 /* point-to-plane only: the pass's normal equations were singular */ };
+       KSS_STATE_DEGENERATE = 6 /* the pass's normal equations were singular (plane metrics), or its kept sources had no spread
+                                    (kss_icp_sim) */ };
 
 typedef struct {
     float   T[16];       /* getFinalTransformation(), row-major Matrix4f  (:222) */
@@ -275,7 +276,8 @@ int kss_icp_p2l_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d
  *               by kss_rigid_from_sums (point metric), or the KSS_P2L_NSUMS record solved by kss_rigid_from_p2l_sums (plane).
  * The loop around it is kss_icp_p2l's: PCL's criteria on MSE = sum d2 kept / kept, fewer than min_correspondences kept ->
  * KSS_STATE_NO_CORRESPONDENCES, a singular plane system -> KSS_STATE_DEGENERATE, fitness over ALL sources.  overlap = 1 keeps
- * every candidate: with the plane metric that is kss_icp_p2l bit for bit.  overlap outside (0, 1] is KSS_ERR_ARG. */
+ * every candidate: with the plane metric that is kss_icp_p2l bit for bit.  overlap outside (0, 1] is KSS_ERR_ARG.  The step is rigid:
+ * kss_icp_sim below is this loop on the point metric with the scale in the solve. */
 enum { KSS_METRIC_POINT = 0, KSS_METRIC_PLANE = 1 };
 #define KSS_TRIM_NINFO 4   /* {m candidates, k rank, tau widened to double, kept} */
 /* host only, no context */
@@ -295,6 +297,73 @@ int kss_icp_trimmed(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt
                     const kss_icp_params *p, const kss_trim_params *tp, kss_icp_result *res, double last_info[KSS_TRIM_NINFO]);
 int kss_icp_trimmed_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
                         const kss_icp_params *p, const kss_trim_params *tp, kss_icp_result *res, double last_info[KSS_TRIM_NINFO]);
+
+/* ---- similarity ICP for one pair: the scale refined with the motion (Umeyama's scale in the solve, PCL's
+ *      TransformationEstimationSVDScale; bounded as in Du et al., scaling ICP), point metric with per-pass trimming ----
+ * One pass, with the NN pass's idx[i] and float d2[i], the source's current float position p and its float target point q:
+ *   candidates, rank, cut, kept   kss_icp_trimmed's point metric, not redefined: 0 <= d2 <= max_d2 in ordered double compares, m of
+ *               them, k = kss_trim_rank(m, overlap), tau the exact k-th smallest candidate d2, kept d2 <= tau with the ties at tau.
+ *   sums        KSS_NSUMS doubles in kss_icp_trimmed's fixed order (a function of ns alone): [0..16] kss_icp_trimmed's point record
+ *               bit for bit; [17] = sum over the kept set of (px*px + py*py) + pz*pz, f64 on the widened floats, nothing fused;
+ *               [18] = [19] = 0.
+ *   step        kss_sim_from_sums(sums, lo, hi, T, &s_k), host only, no context:
+ *               n, mu_s, mu_d, sigma, the SVD, sgn, R: kss_rigid_from_sums' own expressions, so R has the same bits.  The singular
+ *               values sv0 >= sv1 >= sv2 come in descending order; sv2, the smallest, is the one sgn flips.
+ *               var = sums[17]/n - ((mu_s0*mu_s0 + mu_s1*mu_s1) + mu_s2*mu_s2);  s = ((sv0 + sv1) + sgn*sv2) / var;
+ *               s_k = min(max(s, lo), hi): for the R found the error is a quadratic in s, so the clamped value is the optimum
+ *               inside [lo, hi];
+ *               T_ij = (float)(s_k*R_ij), t_i = (float)(mu_d[i] - s_k*((R_i0*mu_s0 + R_i1*mu_s1) + R_i2*mu_s2)), last row 0 0 0 1.
+ *               !(var > 0), or s not finite or not > 0: KSS_ERR_DEGENERATE, T the identity, s_k = 1 (a spread of the kept sources
+ *               below the rounding of var is outside this definition).  With s_k == 1.0, T is kss_rigid_from_sums' T bit for bit.
+ *               KSS_ERR_ARG: a NULL argument, or anything but 0 < lo <= hi.
+ *   info        {m, k, tau, kept, s_k, s_acc after the pass}; s_k = 0 where the pass made no step.
+ * The loop is kss_icp_trimmed's with the accumulated scale s_acc, 1 at the start: per pass lo = scale_min / s_acc and hi = scale_max /
+ * s_acc, after the step s_acc = min(max(s_acc*s_k, scale_min), scale_max); final = T_k * final and the next NN pass applies T_k on
+ * load, as everywhere.  MSE = [16] / [0].  PCL's criteria are read on C_k = [ (float)R | t ], the step without its scale, and
+ * KSS_STATE_TRANSFORM asks in addition for (s_k - 1)*(s_k - 1) <= transformation_epsilon.  Fewer than min_correspondences kept ->
+ * KSS_STATE_NO_CORRESPONDENCES, a degenerate step -> KSS_STATE_DEGENERATE (T as accumulated so far), fitness over ALL sources under
+ * the final T.  The scale is bounded because the one-sided NN objective has the collapsed cloud -- every source on one target point
+ * -- as a minimum.  res->T holds the accumulated similarity, which kss_transform_apply applies as it is; its scale is info[5].
+ * scale_min == scale_max == 1 is kss_icp_trimmed with KSS_METRIC_POINT at the same overlap bit for bit: T, iterations, state,
+ * last_mse, every trace_Tk and slots [0..16] of every trace_sums row.
+ * Not offered: the similarity step on the plane, generalized and symmetric metrics; robust weights on it; kss_register and
+ * kss_register_batch using it (their composite (R, t, s) assumes a rigid T_icp); the C++ mirror classes and the CLI. */
+#define KSS_SIM_NINFO 6   /* {m, k, tau, kept, s_k, s_acc after the pass} */
+typedef struct {
+    double  overlap;                /* share of the candidates kept per pass, 0 < overlap <= 1 */
+    double  scale_min, scale_max;   /* bounds of the accumulated scale, 0 < scale_min <= 1 <= scale_max < inf */
+    double *trace_sim;              /* p->trace_cap * KSS_SIM_NINFO doubles, row i beside trace_sums row i; may be NULL */
+} kss_sim_params;
+/* overlap 1, scale_min 0.5, scale_max 2, trace_sim NULL */
+int kss_sim_default_params(kss_sim_params *sp);
+int kss_sim_from_sums(const double sums[KSS_NSUMS], double lo, double hi, float T[16], double *s_k);
+/* The untrimmed record for given correspondences: packed float triples, d2 recomputed as in kss_cov, kept when 0 <= d2 <= max_d2;
+ * an idx entry outside [0, nt) is no candidate (both forms take it). */
+int kss_sim_sums(kss_ctx *ctx, const float *src, const float *tgt, const int32_t *idx, int64_t n, int64_t nt, double max_d2,
+                 double sums[KSS_NSUMS]);
+int kss_sim_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_tgt, const int32_t *d_idx, int64_t n, int64_t nt, double max_d2,
+                     double sums[KSS_NSUMS]);
+/* last_info (may be NULL): the last pass's info record, all zero when no pass ran.  p->trace_sums rows hold KSS_NSUMS doubles.
+ * KSS_ERR_ARG: a NULL ctx (refused before anything touches the device), sp, res or cloud; an overlap outside (0, 1]; anything but
+ * 0 < scale_min <= 1 <= scale_max < inf; a set p->allreduce; an empty cloud.  A refused call leaves the context usable. */
+int kss_icp_sim(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt, int64_t nt, const kss_icp_params *p,
+                const kss_sim_params *sp, kss_icp_result *res, double last_info[KSS_SIM_NINFO]);
+int kss_icp_sim_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const kss_icp_params *p,
+                    const kss_sim_params *sp, kss_icp_result *res, double last_info[KSS_SIM_NINFO]);
+/* Similarity ICP for MANY pairs per call.  Arguments as kss_icp_trimmed_batch without normals.  Nothing is redefined: every pair's
+ * record -- T, iterations, state, converged, last_mse, its info, pair 0's traces -- is the single-pair call's BIT FOR BIT (fitness: to
+ * the rounding of the NN engine's own summation order), in any batch order and any split over calls, under every nn_mode;
+ * results[i].pair_id = i.  Offsets whose first entry is not 0 address a sub-range of the packed arrays.  The pairs run in lockstep,
+ * three launches per pass behind the NN pass whatever the pair count; a pair that ends leaves the others untouched; every pair has
+ * its own accumulated scale.  overlaps: one per pair, or NULL for sp->overlap everywhere.  info_all: npairs * KSS_SIM_NINFO doubles,
+ * every pair's last info record (may be NULL).  trace_*, sp->trace_sim and fitness_idx / fitness_d2 describe pair 0.  KSS_ERR_ARG:
+ * everything kss_icp_sim refuses, NULL offsets or results, an overlaps entry outside (0, 1], an empty pair, npairs <= 0. */
+int kss_icp_sim_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *tgt_all, const int64_t *tgt_off,
+                      int npairs, const kss_icp_params *p, const kss_sim_params *sp, const double *overlaps, kss_icp_result *results,
+                      double *info_all);
+int kss_icp_sim_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_tgt_all, const int64_t *tgt_off,
+                          int npairs, const kss_icp_params *p, const kss_sim_params *sp, const double *overlaps,
+                          kss_icp_result *results, double *info_all);
 
 /* ---- robust ICP for one pair with gross outliers of unknown share (M-estimator weights, one iteratively re-weighted
  *      least-squares step per pass), both metrics ----

@@ -14,7 +14,8 @@ from .binding import (KssError, Context, IcpParams, IcpResult, RegisterResult, P
                       P2L_NSUMS, STATE_DEGENERATE, ERR_DEGENERATE, rigid_from_p2l_sums,
                       METRIC_POINT, METRIC_PLANE, TRIM_NINFO, TrimParams, trim_rank,
                       LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, ROBUST_NINFO, RobustParams, robust_params, robust_weight,
-                      robust_scale2, GicpParams, gicp_params, gicp_metric, SymmParams, symm_params, rigid_from_symm_sums)
+                      robust_scale2, GicpParams, gicp_params, gicp_metric, SymmParams, symm_params, rigid_from_symm_sums,
+                      SIM_NINFO, SimParams, sim_params, sim_from_sums)
 from . import synth
 from . import shard
 
@@ -23,4 +24,5 @@ __all__ = ["KssError", "Context", "IcpParams", "IcpResult", "RegisterResult", "P
            "P2L_NSUMS", "STATE_DEGENERATE", "ERR_DEGENERATE", "rigid_from_p2l_sums",
            "METRIC_POINT", "METRIC_PLANE", "TRIM_NINFO", "TrimParams", "trim_rank",
            "LOSS_L2", "LOSS_HUBER", "LOSS_TUKEY", "LOSS_CAUCHY", "ROBUST_NINFO", "RobustParams", "robust_params", "robust_weight",
-           "robust_scale2", "GicpParams", "gicp_params", "gicp_metric", "SymmParams", "symm_params", "rigid_from_symm_sums"]
+           "robust_scale2", "GicpParams", "gicp_params", "gicp_metric", "SymmParams", "symm_params", "rigid_from_symm_sums",
+           "SIM_NINFO", "SimParams", "sim_params", "sim_from_sums"]

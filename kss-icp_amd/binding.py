@@ -22,6 +22,7 @@ METRIC_POINT, METRIC_PLANE = 0, 1   # KSS_METRIC_*: the step of kss_icp_trimmed
 TRIM_NINFO = 4           # KSS_TRIM_NINFO: {m candidates, k rank, tau, kept} of a trimmed pass
 LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY = 0, 1, 2, 3   # KSS_LOSS_*: the weight of kss_icp_robust
 ROBUST_NINFO = 4         # KSS_ROBUST_NINFO: {m candidates, c2, sum of weights, cnt kept} of a robust pass
+SIM_NINFO = 6            # KSS_SIM_NINFO: {m, k, tau, kept, s_k, s_acc after the pass} of a similarity pass
 F32, F64 = 0, 1
 
 # every symbol include/kssicp.h declares (checked by tests/test_abi.py against the header text)
@@ -45,6 +46,8 @@ SYMBOLS = [
     "kss_icp_symm_batch", "kss_icp_symm_batch_dev",
     "kss_symm_robust_sums", "kss_symm_robust_sums_dev", "kss_icp_symm_robust", "kss_icp_symm_robust_dev",
     "kss_icp_symm_robust_batch", "kss_icp_symm_robust_batch_dev",
+    "kss_sim_default_params", "kss_sim_from_sums", "kss_sim_sums", "kss_sim_sums_dev", "kss_icp_sim", "kss_icp_sim_dev",
+    "kss_icp_sim_batch", "kss_icp_sim_batch_dev",
 ]
 
 
@@ -79,6 +82,10 @@ class IcpParams(C.Structure):
 
 class TrimParams(C.Structure):
     _fields_ = [("overlap", C.c_double), ("metric", C.c_int), ("trace_trim", C.POINTER(C.c_double))]
+
+
+class SimParams(C.Structure):
+    _fields_ = [("overlap", C.c_double), ("scale_min", C.c_double), ("scale_max", C.c_double), ("trace_sim", C.POINTER(C.c_double))]
 
 
 class RobustParams(C.Structure):
@@ -168,6 +175,14 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, i64, dbl, dbl, vp]
     for n in ("kss_icp_trimmed", "kss_icp_trimmed_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(TrimParams), C.POINTER(IcpResult), vp]
+    L.kss_sim_default_params.argtypes = [C.POINTER(SimParams)]
+    L.kss_sim_from_sums.argtypes = [vp, dbl, dbl, vp, C.POINTER(dbl)]
+    for n in ("kss_sim_sums", "kss_sim_sums_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, i64, i64, dbl, vp]
+    for n in ("kss_icp_sim", "kss_icp_sim_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, i64, C.POINTER(IcpParams), C.POINTER(SimParams), C.POINTER(IcpResult), vp]
+    for n in ("kss_icp_sim_batch", "kss_icp_sim_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(SimParams), vp, vp, vp]
     L.kss_robust_default_params.argtypes = [C.c_int, C.c_int, C.POINTER(RobustParams)]
     L.kss_robust_weight.argtypes = [C.c_int, dbl, dbl, C.POINTER(dbl)]
     L.kss_robust_scale2.argtypes = [C.c_int, dbl, C.c_float, dbl, C.POINTER(dbl)]
@@ -316,6 +331,36 @@ def trim_rank(m, overlap):
     if rc != 0:
         raise KssError(rc, "kss_trim_rank")
     return k.value
+
+
+def sim_params(**kw):
+    """kss_sim_default_params (overlap 1, scale_min 0.5, scale_max 2), then the fields given by keyword."""
+    L = load_library()
+    sp = SimParams()
+    rc = L.kss_sim_default_params(C.byref(sp))
+    if rc != 0:
+        raise KssError(rc, "kss_sim_default_params")
+    for k, v in kw.items():
+        if k in ("overlap", "scale_min", "scale_max"):
+            setattr(sp, k, float(v))
+        else:
+            raise AttributeError(k)
+    return sp
+
+
+def sim_from_sums(sums, lo=0.5, hi=2.0):
+    """kss_sim_from_sums: (T, s_k, status) -- the similarity step from an NSUMS record with the scale clamped to [lo, hi]; status 0,
+    or ERR_DEGENERATE with T the identity and s_k = 1."""
+    L = load_library()
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.size != NSUMS:
+        raise ValueError("need %d sums" % NSUMS)
+    T = np.empty(16, np.float32)
+    sk = C.c_double(0.0)
+    rc = L.kss_sim_from_sums(_p(s), float(lo), float(hi), _p(T), C.byref(sk))
+    if rc not in (0, ERR_DEGENERATE):
+        raise KssError(rc, "kss_sim_from_sums")
+    return T.reshape(4, 4), sk.value, rc
 
 
 def robust_params(loss=LOSS_HUBER, metric=METRIC_POINT, **kw):
@@ -576,7 +621,8 @@ class Context:
     def _icp_call(self, call, where, p, ns, ncol, trace_cap, fitness_corr, tp=None):
         """call(res) with the trace and fitness_corr arrays attached to the params p (and to the TrimParams or RobustParams tp),
         detached again whether it returns or raises; the result dictionary of icp()."""
-        tname = "trace_robust" if isinstance(tp, RobustParams) else "trace_trim"
+        tname = "trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else "trace_trim"
+        ninfo = SIM_NINFO if isinstance(tp, SimParams) else TRIM_NINFO
         res = IcpResult()
         tr = None
         fc = None
@@ -587,7 +633,7 @@ class Context:
                 p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
             if trace_cap > 0:
                 tr = (np.zeros((trace_cap, ncol), np.float64), np.zeros((trace_cap, 16), np.float32), C.c_int(0),
-                      np.zeros((trace_cap, TRIM_NINFO), np.float64) if tp is not None else None)
+                      np.zeros((trace_cap, ninfo), np.float64) if tp is not None else None)
                 p.trace_sums = tr[0].ctypes.data_as(C.POINTER(C.c_double))
                 p.trace_Tk = tr[1].ctypes.data_as(C.POINTER(C.c_float))
                 p.trace_cap = trace_cap
@@ -598,8 +644,8 @@ class Context:
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-                if isinstance(tp, RobustParams):
-                    tp.trace_robust = None
+                if isinstance(tp, (RobustParams, SimParams)):
+                    setattr(tp, tname, None)
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
         out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
@@ -693,6 +739,47 @@ class Context:
         self._chk(self.L.kss_icp_trimmed_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
                                              C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(tp),
                                              C.byref(res), _p(info)), "kss_icp_trimmed_dev")
+        return res, info
+
+    # ---- similarity ICP
+    def sim_sums(self, src, tgt, idx, max_d2=1.0):
+        """kss_sim_sums: the untrimmed NSUMS record of the similarity step for given correspondences ([17] = the kept sources' sum
+        of squares)."""
+        s, t = _f32(src), _f32(tgt)
+        i = np.ascontiguousarray(idx, dtype=np.int32)
+        sums = np.empty(NSUMS, np.float64)
+        self._chk(self.L.kss_sim_sums(self.h, _p(s), _p(t), _p(i), len(s), len(t), float(max_d2), _p(sums)), "kss_sim_sums")
+        return sums
+
+    def sim_sums_dev(self, d_src, d_tgt, d_idx, n, nt, max_d2=1.0):
+        sums = np.empty(NSUMS, np.float64)
+        self._chk(self.L.kss_sim_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_tgt)), C.c_void_p(int(d_idx)), int(n), int(nt),
+                                          float(max_d2), _p(sums)), "kss_sim_sums_dev")
+        return sums
+
+    def icp_sim(self, src, tgt, sp=None, params=None, trace_cap=0, fitness_corr=False):
+        """Similarity ICP (kss_icp_sim): trimmed ICP on the point metric with Umeyama's scale in the solve, the accumulated scale
+        kept in [sp.scale_min, sp.scale_max].  sp: a SimParams (sim_params()), None for the defaults.  The result dictionary of
+        icp_trimmed() with trace_sim (one {m, k, tau, kept, s_k, s_acc} row per traced pass) and sim_info (the last pass's) in
+        place of the trimmed records, plus scale = sim_info[5] (1 when no pass ran); T holds the accumulated similarity."""
+        s, t = _f32(src), _f32(tgt)
+        p = params if params is not None else self.icp_params()
+        sp = sp if sp is not None else sim_params()
+        info = np.zeros(SIM_NINFO, np.float64)
+        out = self._icp_call(lambda res: self.L.kss_icp_sim(self.h, _p(s), len(s), _p(t), len(t), C.byref(p), C.byref(sp), C.byref(res),
+                                                            _p(info)),
+                             "kss_icp_sim", p, len(s), NSUMS, trace_cap, fitness_corr, sp)
+        out["sim_info"] = info
+        out["scale"] = float(info[5]) if info[5] > 0 else 1.0
+        return out
+
+    def icp_sim_dev(self, d_src, ns, d_tgt, nt, params, sp=None):
+        """kss_icp_sim_dev on device pointers; returns (IcpResult, sim_info)."""
+        res = IcpResult()
+        sp = sp if sp is not None else sim_params()
+        info = np.zeros(SIM_NINFO, np.float64)
+        self._chk(self.L.kss_icp_sim_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt), C.byref(params),
+                                         C.byref(sp), C.byref(res), _p(info)), "kss_icp_sim_dev")
         return res, info
 
     # ---- robust ICP
@@ -921,7 +1008,8 @@ class Context:
     def _batch_call(self, call, where, p, so, ncol, trace_cap, fitness_corr, tp=None):
         """call(res) for a batch: the trace and fitness_corr arrays (pair 0's) attached to p / tp as in _icp_call, detached again
         whether it returns or raises.  Returns (list of IcpResult, extras of pair 0)."""
-        tname = "trace_robust" if isinstance(tp, RobustParams) else "trace_trim"
+        tname = "trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else "trace_trim"
+        ninfo = SIM_NINFO if isinstance(tp, SimParams) else TRIM_NINFO
         npairs = len(so) - 1
         res = (IcpResult * npairs)()
         ns0 = int(so[1] - so[0]) if npairs > 0 else 0
@@ -933,7 +1021,7 @@ class Context:
                 p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
             if trace_cap > 0:
                 tr = (np.zeros((trace_cap, ncol), np.float64), np.zeros((trace_cap, 16), np.float32), C.c_int(0),
-                      np.zeros((trace_cap, TRIM_NINFO), np.float64) if tp is not None else None)
+                      np.zeros((trace_cap, ninfo), np.float64) if tp is not None else None)
                 p.trace_sums = tr[0].ctypes.data_as(C.POINTER(C.c_double))
                 p.trace_Tk = tr[1].ctypes.data_as(C.POINTER(C.c_float))
                 p.trace_cap = trace_cap
@@ -944,8 +1032,8 @@ class Context:
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-                if isinstance(tp, RobustParams):
-                    tp.trace_robust = None
+                if isinstance(tp, (RobustParams, SimParams)):
+                    setattr(tp, tname, None)
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
         extra = {}
@@ -1029,6 +1117,35 @@ class Context:
         self._chk(self.L.kss_icp_trimmed_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
                                                    C.c_void_p(int(d_normals_all)) if d_normals_all else None, npairs, C.byref(params),
                                                    C.byref(tp), _p(ov), C.cast(res, C.c_void_p), _p(info)), "kss_icp_trimmed_batch_dev")
+        return list(res), info
+
+    def icp_sim_batch(self, src_all, src_off, tgt_all, tgt_off, overlaps=None, sp=None, params=None, trace_cap=0, fitness_corr=False):
+        """kss_icp_sim_batch: similarity ICP of npairs pairs in one call.  overlaps: one per pair, or None for sp.overlap everywhere.
+        Returns (list of IcpResult, sim_info of every pair as npairs x SIM_NINFO -- column 5 is the pair's scale --, dictionary with
+        pair 0's traces)."""
+        s, t = _f32(src_all), _f32(tgt_all)
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        ov = self._overlaps(overlaps, npairs)
+        p = params if params is not None else self.icp_params()
+        sp = sp if sp is not None else sim_params()
+        info = np.zeros((max(npairs, 0), SIM_NINFO), np.float64)
+        res, extra = self._batch_call(
+            lambda res: self.L.kss_icp_sim_batch(self.h, _p(s), _p(so), _p(t), _p(to), npairs, C.byref(p), C.byref(sp), _p(ov), res, _p(info)),
+            "kss_icp_sim_batch", p, so, NSUMS, trace_cap, fitness_corr, sp)
+        return res, info, extra
+
+    def icp_sim_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, params, overlaps=None, sp=None):
+        """kss_icp_sim_batch_dev on device pointers; returns (list of IcpResult, sim_info npairs x SIM_NINFO)."""
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        ov = self._overlaps(overlaps, npairs)
+        res = (IcpResult * npairs)()
+        sp = sp if sp is not None else sim_params()
+        info = np.zeros((npairs, SIM_NINFO), np.float64)
+        self._chk(self.L.kss_icp_sim_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to), npairs,
+                                               C.byref(params), C.byref(sp), _p(ov), C.cast(res, C.c_void_p), _p(info)),
+                  "kss_icp_sim_batch_dev")
         return list(res), info
 
     # ---- robust ICP, many pairs per call

@@ -599,6 +599,98 @@ int kss_icp_trimmed(kss_ctx* c, const float* src, int64_t ns, const float* tgt, 
                                p, tp, res, last_info);
 }
 
+// ---- similarity ICP ----------------------------------------------------------------
+int kss_sim_default_params(kss_sim_params* sp) {
+    if (!sp) return KSS_ERR_ARG;
+    sp->overlap = 1.0;
+    sp->scale_min = 0.5; sp->scale_max = 2.0;
+    sp->trace_sim = nullptr;
+    return KSS_OK;
+}
+
+int kss_sim_from_sums(const double sums[KSS_NSUMS], double lo, double hi, float T[16], double* s_k) {
+    if (!sums || !T || !s_k) return KSS_ERR_ARG;
+    if (!(lo > 0.0) || !(lo <= hi)) return KSS_ERR_ARG;
+    return sim_from_sums(sums, lo, hi, T, s_k) ? KSS_OK : KSS_ERR_DEGENERATE;
+}
+
+int kss_sim_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const int32_t* d_idx, int64_t n, int64_t nt, double max_d2,
+                     double sums[KSS_NSUMS]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!d_src || !d_tgt || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "sim_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "sim_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "sim_sums: cloud too large");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
+    {
+        ProfScope ps(c, KSS_K_CORR_REDUCE);
+        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, nullptr, max_d2}, d_tgt, nullptr, n, nt, (double*)c->p2l_rows.p, nullptr};
+        launch_pair_rows(c->stream, a, SimMetric(max_d2, nullptr));
+        launch_sim_final(c->stream, a.rows, p2l_rows_blocks(n), (double*)c->h_p2l_dev);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(sums, c->h_p2l, KSS_NSUMS * sizeof(double));
+    return KSS_OK;
+}
+
+int kss_sim_sums(kss_ctx* c, const float* src, const float* tgt, const int32_t* idx, int64_t n, int64_t nt, double max_d2,
+                 double sums[KSS_NSUMS]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!src || !tgt || !idx || !sums) return set_err(c, KSS_ERR_ARG, "sim_sums: null argument");
+    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "sim_sums: empty input");
+    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "sim_sums: cloud too large");
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
+    return kss_sim_sums_dev(c, (const float*)c->stage_src.p, (const float*)c->stage_tgt.p, (const int32_t*)c->stage_idx.p, n, nt, max_d2, sums);
+}
+
+// the checks of sp that every entry point shares, and the trimmed point metric's parameters that pair_check reads
+static int sim_check(kss_ctx* c, const char* who, const kss_sim_params* sp, kss_trim_params* tp) {
+    const std::string w = std::string(who) + ": ";
+    if (!sp) return set_err(c, KSS_ERR_ARG, (w + "null argument").c_str());
+    if (!(sp->scale_min > 0.0) || !(sp->scale_min <= 1.0) || !(sp->scale_max >= 1.0) || !std::isfinite(sp->scale_max))
+        return set_err(c, KSS_ERR_ARG, (w + "the scale bounds must satisfy 0 < scale_min <= 1 <= scale_max < inf").c_str());
+    tp->overlap = sp->overlap; tp->metric = KSS_METRIC_POINT; tp->trace_trim = nullptr;
+    return KSS_OK;
+}
+static PairMode sim_mode_of(const kss_sim_params* sp) {
+    PairMode mode;
+    mode.trimmed = true;
+    mode.sim = true;
+    mode.overlap = sp->overlap;
+    mode.scale_min = sp->scale_min; mode.scale_max = sp->scale_max;
+    mode.trace_info = sp->trace_sim;
+    return mode;
+}
+
+int kss_icp_sim_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const kss_icp_params* p,
+                    const kss_sim_params* sp, kss_icp_result* res, double last_info[KSS_SIM_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    kss_trim_params tp;
+    KCHK(sim_check(c, "icp_sim", sp, &tp));
+    KCHK(pair_check(c, "icp_sim", true, d_src, d_tgt, ns, nt, nullptr, p, &tp, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    PairMode mode = sim_mode_of(sp);
+    mode.last_info = last_info;
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, nullptr, p, mode, res);
+}
+
+int kss_icp_sim(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const kss_icp_params* p, const kss_sim_params* sp,
+                kss_icp_result* res, double last_info[KSS_SIM_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    kss_trim_params tp;
+    KCHK(sim_check(c, "icp_sim", sp, &tp));
+    KCHK(pair_check(c, "icp_sim", true, src, tgt, ns, nt, nullptr, p, &tp, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_sim_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, p, sp, res, last_info);
+}
+
 // ---- robust ICP --------------------------------------------------------------------
 static inline bool robust_loss_ok(int loss) { return loss >= KSS_LOSS_L2 && loss <= KSS_LOSS_CAUCHY; }
 static inline bool robust_metric_ok(int metric) { return metric == KSS_METRIC_POINT || metric == KSS_METRIC_PLANE; }
@@ -1148,6 +1240,40 @@ int kss_icp_trimmed_batch(kss_ctx* c, const float* src_all, const int64_t* src_o
                           kss_icp_result* results, double* info_all) {
     if (c && !tp) return set_err(c, KSS_ERR_ARG, "icp_trimmed_batch: null argument");
     return pairs_batch_host(c, "icp_trimmed_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, tp, overlaps, results, info_all);
+}
+
+// ---- similarity ICP for many pairs per call ------------------------------------------
+int kss_icp_sim_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, int npairs,
+                          const kss_icp_params* p, const kss_sim_params* sp, const double* overlaps, kss_icp_result* results, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_sim_batch: bad batch");
+    kss_trim_params tp;
+    KCHK(sim_check(c, "icp_sim_batch", sp, &tp));
+    KCHK(pair_check(c, "icp_sim_batch", true, d_src, d_tgt, 0, 0, nullptr, p, &tp, results, src_off, tgt_off, npairs, overlaps));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
+    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
+    std::vector<double> ov((size_t)npairs, sp->overlap);
+    if (overlaps) ov.assign(overlaps, overlaps + npairs);
+    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), nullptr, npairs, p, sim_mode_of(sp), ov.data(), results, info_all);
+}
+
+int kss_icp_sim_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off, int npairs,
+                      const kss_icp_params* p, const kss_sim_params* sp, const double* overlaps, kss_icp_result* results, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_sim_batch: bad batch");
+    kss_trim_params tp;
+    KCHK(sim_check(c, "icp_sim_batch", sp, &tp));
+    KCHK(pair_check(c, "icp_sim_batch", true, src, tgt, 0, 0, nullptr, p, &tp, results, src_off, tgt_off, npairs, overlaps));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
+    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
+    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
+    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
+    return kss_icp_sim_batch_dev(c, (const float*)c->stage_src.p, so.data(), (const float*)c->stage_tgt.p, to.data(), npairs, p, sp, overlaps,
+                                 results, info_all);
 }
 
 // ---- robust ICP for many pairs per call ----------------------------------------------

@@ -253,7 +253,7 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // one exact NN pass of a single pair (+ the correspondence sums when sums_out is given)
 int nn_generic_dev(kss_ctx* c, const void* d_src, int64_t ns, const void* d_tgt, int64_t nt, int dtype,
                    int32_t* d_idx, float* d_d2, double sums_out[NSUMS]);
-// ICP of one pair by kss_icp_p2l (plane, untrimmed), kss_icp_trimmed, kss_icp_robust (either metric), kss_icp_gicp or kss_icp_symm:
+// ICP of one pair by kss_icp_p2l (plane, untrimmed), kss_icp_trimmed, kss_icp_robust (either metric), kss_icp_gicp, kss_icp_symm or kss_icp_sim:
 // float clouds on the device, d_nrm the target's normals for the plane metric.  The untrimmed, unweighted point metric is icp_run_dev's.
 struct PairMode {
     bool plane = false;             // point-to-plane step (d_nrm given); otherwise point-to-point
@@ -269,6 +269,9 @@ struct PairMode {
     bool symm = false;              // symmetric ICP (kss_icp_symm; with plane, not with trimmed or gicp): the plane record on
     int symm_align = 1;             // nq +- R_F ns, ns from d_src_nrm as for gicp; the step is rigid_from_symm_sums.  With robust
                                     // (kss_icp_symm_robust, kss_icp_symm_robust_batch): the weights of rs on that record
+    bool sim = false;               // similarity ICP (kss_icp_sim; with trimmed and the point metric only): the step is sim_from_sums
+    double scale_min = 1.0;         // with the accumulated scale kept in [scale_min, scale_max]; trace_info / last_info / info_all
+    double scale_max = 1.0;         // hold KSS_SIM_NINFO doubles per record
 };
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
@@ -277,7 +280,7 @@ int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, 
 // npairs >= 1 pairs in lockstep (kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch, kss_icp_gicp_batch,
 // kss_icp_symm_batch, kss_icp_symm_robust_batch -- symm with robust takes both symm_aligns and rscales): d_nrm laid
 // out like d_tgt; overlaps: one per pair (trimmed; M.overlap is not read); rscales: one per pair (robust; M.rs is not read), all
-// with the loss of the batch; info_all: npairs * KSS_TRIM_NINFO or null; M.trace_info / M.last_info: pair 0's / unused;
+// with the loss of the batch; info_all: npairs * KSS_TRIM_NINFO (M.sim: KSS_SIM_NINFO) or null; M.trace_info / M.last_info: pair 0's / unused;
 // gicp_eps: one epsilon per pair (generalized; M.gicp_epsilon is not read), M.d_src_nrm laid out like d_src;
 // symm_aligns: one align_normals per pair (symmetric; M.symm_align is not read), M.d_src_nrm as for generalized
 int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, const float* d_nrm,

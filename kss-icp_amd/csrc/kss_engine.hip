@@ -1097,11 +1097,11 @@ static inline Convergence convergence_of(const kss_icp_params& P) {   // PCL's c
 }
 // one row of the caller's trace: the pass's sums (ncol of them), its T_k and, for a trimmed pass, its {m, k, tau, kept}
 static inline void trace_row(const kss_icp_params& P, const double* s, int ncol, const float* tk, double* trace_info = nullptr,
-                             const double* info = nullptr) {
+                             const double* info = nullptr, int ninfo = KSS_TRIM_NINFO) {
     if (!P.trace_n || *P.trace_n >= P.trace_cap) return;
     if (P.trace_sums) std::memcpy(P.trace_sums + (size_t)(*P.trace_n) * ncol, s, (size_t)ncol * sizeof(double));
     if (P.trace_Tk) std::memcpy(P.trace_Tk + (size_t)(*P.trace_n) * 16, tk, 16 * sizeof(float));
-    if (trace_info) std::memcpy(trace_info + (size_t)(*P.trace_n) * KSS_TRIM_NINFO, info, KSS_TRIM_NINFO * sizeof(double));
+    if (trace_info) std::memcpy(trace_info + (size_t)(*P.trace_n) * ninfo, info, (size_t)ninfo * sizeof(double));
     ++*P.trace_n;
 }
 static inline void fill_result(kss_icp_result& r, const float fin[16], int iterations, int converged, int state, double last_mse,
@@ -1874,6 +1874,10 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // layout and the solve are the plane metric's, the step built from the solution is rigid_from_symm_sums' (two half rotations).
 // Robust symmetric (kss_icp_symm_robust; M.symm with M.robust): the robust branch with the symmetric keys and rows
 // launches and that rotation; the selection, the final launch, the info slots and the host step (cnt, rigid_from_symm_sums) are shared.
+// Similarity (kss_icp_sim; M.sim with M.trimmed, point metric): the trimmed point metric's launches with SimMetric's
+// rows and the final launch that keeps slot 17; the host step solves by sim_from_sums inside [scale_min, scale_max] / s_acc, keeps
+// the pair's accumulated scale s_acc and reads PCL's criteria on the step without its scale; the info record grows to
+// KSS_SIM_NINFO = {m, k, tau, kept, s_k, s_acc} (s_k = 0 where the pass made no step), the last two filled here on the host.
 // What the host does for ONE pair after a pass, the same code for a single pair (pair_loop) and inside a batch (pairs_loop): the
 // min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
 // its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
@@ -1883,17 +1887,30 @@ struct PairTrack {
     float fin[16], tk[16];
     int iters = 0, state = KSS_STATE_NOT_CONVERGED, converged = 0;
     double last_mse = 0.0;
+    double s_acc = 1.0;   // similarity: the scale accumulated so far
     explicit PairTrack(const kss_icp_params& P) : cv(convergence_of(P)) { mat4_identity(fin); mat4_identity(tk); }
 };
-static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const double* s, const double* info, PairTrack& t, PairState& hs,
+static int pair_ninfo(const PairMode& M) { return M.sim ? KSS_SIM_NINFO : KSS_TRIM_NINFO; }
+static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const double* s, double* info, PairTrack& t, PairState& hs,
                            bool trace) {
+    if (M.sim) { info[4] = 0.0; info[5] = t.s_acc; }
     // PCL: "Not enough correspondences found" (robust: the count kept, [0] being the weight total)
     const double cnt = M.robust ? s[(M.plane ? P2L_NSUMS : NSUMS) - 1] : s[0];
     if ((int)cnt < P.min_correspondences) { t.state = KSS_STATE_NO_CORRESPONDENCES; return false; }
+    float ck[16];                 // similarity: the step without its scale, what the criteria read
+    const float* crit = t.tk;
+    double scale_dev2 = 0.0;
     if (M.symm) {
         if (!rigid_from_symm_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
     } else if (M.plane) {
         if (!rigid_from_p2l_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
+    } else if (M.sim) {
+        double sk;
+        if (!sim_from_sums(s, M.scale_min / t.s_acc, M.scale_max / t.s_acc, t.tk, &sk, ck)) { t.state = KSS_STATE_DEGENERATE; return false; }
+        t.s_acc = std::fmin(std::fmax(t.s_acc * sk, M.scale_min), M.scale_max);
+        info[4] = sk; info[5] = t.s_acc;
+        scale_dev2 = (sk - 1.0) * (sk - 1.0);
+        crit = ck;
     } else {
         rigid_from_sums(s, t.tk);
     }
@@ -1901,8 +1918,8 @@ static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const dou
     ++t.iters;
     const double mse = (M.plane ? s[28] : s[16]) / s[0];   // point-to-point d2 of the kept correspondences, as PCL's criteria read it
     t.last_mse = mse;
-    if (trace) trace_row(P, s, M.plane ? P2L_NSUMS : NSUMS, t.tk, M.trimmed || M.robust ? M.trace_info : nullptr, info);
-    const bool done = t.cv.has_converged(t.iters, t.tk, mse);
+    if (trace) trace_row(P, s, M.plane ? P2L_NSUMS : NSUMS, t.tk, M.trimmed || M.robust ? M.trace_info : nullptr, info, pair_ninfo(M));
+    const bool done = t.cv.has_converged(t.iters, crit, mse, scale_dev2);
     t.state = t.cv.state;
     if (done) { t.converged = 1; return false; }
     set_state(hs, t.tk, 1, 1);   // next NN pass applies T_k on load (transformCloud)
@@ -1932,7 +1949,8 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
     float* d_keys = (float*)c->rob_keys.p;
     const int nb = stream_blocks(ns);
     if (P.trace_n) *P.trace_n = 0;
-    if (M.last_info) for (int q = 0; q < KSS_TRIM_NINFO; ++q) M.last_info[q] = 0.0;
+    const int ninfo = pair_ninfo(M);
+    if (M.last_info) for (int q = 0; q < ninfo; ++q) M.last_info[q] = 0.0;
     int it = 0;
     GatedGuard gated_guard(c);
     c->gated.want_next = false;
@@ -1966,6 +1984,9 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
                 else if (M.trimmed) launch_pair_rows(st, a, PlaneMetric<true>(max_d2, d_cut));
                 else launch_pair_rows(st, a, PlaneMetric<false>(max_d2, nullptr));
                 launch_p2l_final(st, d_rows, nb, d_rec);
+            } else if (M.sim) {
+                launch_pair_rows(st, a, SimMetric(max_d2, d_cut));
+                launch_sim_final(st, d_rows, nb, d_rec);
             } else {
                 launch_pair_rows(st, a, PointTrimMetric(d_cut));
                 launch_trim_point_final(st, d_rows, nb, d_rec);
@@ -1974,14 +1995,15 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
         ++it;
-        double s[P2L_NSUMS], info[KSS_TRIM_NINFO] = {};
+        double s[P2L_NSUMS], info[KSS_SIM_NINFO] = {};
         std::memcpy(s, hp, (size_t)ncol * sizeof(double));
         if (M.trimmed || M.robust) {
-            std::memcpy(info, hp + P2L_NSUMS, sizeof info);
+            std::memcpy(info, hp + P2L_NSUMS, KSS_TRIM_NINFO * sizeof(double));
             if (M.trimmed) info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
-            if (M.last_info) std::memcpy(M.last_info, info, sizeof info);
         }
-        if (!pair_host_step(P, M, s, info, tr, hs[0], true)) break;
+        const bool goes_on = pair_host_step(P, M, s, info, tr, hs[0], true);   // (similarity: fills the scale slots of info)
+        if ((M.trimmed || M.robust) && M.last_info) std::memcpy(M.last_info, info, (size_t)ninfo * sizeof(double));
+        if (!goes_on) break;
     }
     fill_result(*res, tr.fin, tr.iters, tr.converged, tr.state, tr.last_mse, 0.0, 0);
     if (!P.compute_fitness) return KSS_OK;
@@ -1994,6 +2016,7 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
                  const kss_icp_params* p, const PairMode& M, kss_icp_result* res) {
     if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: the untrimmed point metric is kss_icp's");
     if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: trimmed and robust exclude each other");
+    if (M.sim && (M.plane || !M.trimmed)) return set_err(c, KSS_ERR_ARG, "pair_run: similarity ICP is the trimmed point metric's");
     if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm))
         return set_err(c, KSS_ERR_ARG, "pair_run: generalized ICP is the plane record with both clouds' normals, neither trimmed nor robust");
     if (M.symm && (!M.plane || M.trimmed || M.gicp || !M.d_src_nrm || !d_nrm))
@@ -2102,7 +2125,8 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     int total_rows = 0;
     for (int p = 0; p < np; ++p) total_rows += stream_blocks(pl_in.g[p].ns);
     if (P.trace_n) *P.trace_n = 0;
-    if (info_all) std::fill(info_all, info_all + (size_t)np * KSS_TRIM_NINFO, 0.0);
+    const int ninfo = pair_ninfo(M);
+    if (info_all) std::fill(info_all, info_all + (size_t)np * ninfo, 0.0);
     int n_active = P.max_iterations > 0 ? np : 0;
     if (n_active == 0) std::fill(active.begin(), active.end(), 0);
     int it = 0;
@@ -2140,10 +2164,11 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                 if (M.trimmed) launch_pairb_select(st, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
                 if (M.gicp) launch_pairb_rows<GicpMetric>(st, total_rows, a);
                 else if (M.symm) launch_pairb_rows<SymmMetric<PAIR_PLAIN>>(st, total_rows, a);
+                else if (M.sim) launch_pairb_rows<SimMetric>(st, total_rows, a);
                 else if (!M.plane) launch_pairb_rows<PointTrimMetric>(st, total_rows, a);
                 else if (M.trimmed) launch_pairb_rows<PlaneMetric<true>>(st, total_rows, a);
                 else launch_pairb_rows<PlaneMetric<false>>(st, total_rows, a);
-                launch_pairb_final(st, M.plane, np, a, d_rec);
+                launch_pairb_final(st, M.plane, np, a, d_rec, M.sim);
             }
         }
         HIPCHK(c, hipGetLastError());
@@ -2160,13 +2185,14 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
             for (int p = pb; p < pe; ++p) {
                 if (!active[p]) continue;
                 const double* s = hrec + (size_t)p * P2L_NSUMS;
-                double info[KSS_TRIM_NINFO] = {};
+                double info[KSS_SIM_NINFO] = {};
                 if (M.trimmed || M.robust) {
-                    std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, sizeof info);
+                    std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, KSS_TRIM_NINFO * sizeof(double));
                     if (M.trimmed) info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
-                    if (info_all) std::memcpy(info_all + (size_t)p * KSS_TRIM_NINFO, info, sizeof info);
                 }
-                if (!pair_host_step(P, M, s, info, tr[p], hs[p], p == 0)) {
+                const bool goes_on = pair_host_step(P, M, s, info, tr[p], hs[p], p == 0);   // (similarity: fills the scale slots of info)
+                if ((M.trimmed || M.robust) && info_all) std::memcpy(info_all + (size_t)p * ninfo, info, (size_t)ninfo * sizeof(double));
+                if (!goes_on) {
                     active[p] = 0; ++fin_here;
                     set_state(hs[p], I, 0, 0);
                 }
@@ -2224,6 +2250,7 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
                   const RobustScale* rscales, const double* gicp_eps, const int32_t* symm_aligns) {
     if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: the untrimmed point metric is kss_icp_batch's");
     if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: trimmed and robust exclude each other");
+    if (M.sim && (M.plane || !M.trimmed)) return set_err(c, KSS_ERR_ARG, "pairs_run: similarity ICP is the trimmed point metric's");
     if (M.robust && !rscales) return set_err(c, KSS_ERR_ARG, "pairs_run: robust needs the per-pair scales");
     if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm || !gicp_eps))
         return set_err(c, KSS_ERR_ARG, "pairs_run: generalized ICP is the plane record with both clouds' normals and the per-pair epsilons, neither trimmed nor robust");

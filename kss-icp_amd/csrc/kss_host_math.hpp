@@ -15,6 +15,8 @@ namespace kss {
 
 constexpr int NSUMS = 20;
 
+inline void mat4_identity(float T[16]);
+
 // ---- 3x3 SVD by one-sided (Hestenes) Jacobi: A = U diag(s) V^T, row-major ----------------
 inline double det3(const double M[9]) {
     return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) +
@@ -93,22 +95,34 @@ inline void svd3(const double A[9], double U[9], double s[3], double V[9]) {
 
 // ---- TransformationEstimationSVD -> Eigen umeyama(src, dst, with_scaling=false) -----------
 // sigma = (1/n) sum (dst - mu_d)(src - mu_s)^T, R = U diag(1,1,+-1) V^T, t = mu_d - R mu_s.
-inline void rigid_from_sums(const double sums[NSUMS], float T[16]) {
+// What the rigid and the similarity step share, up to R: svd3 returns the singular values in descending order, so sv[2] is the
+// smallest and the one sgn flips.
+struct UmeyamaRot {
+    double n, mu_s[3], mu_d[3], sv[3], sgn, R[9];
+};
+inline void umeyama_rot(const double sums[NSUMS], UmeyamaRot& u) {
     const double n = sums[0];
     const double mu_s[3] = {sums[1] / n, sums[2] / n, sums[3] / n};
     const double mu_d[3] = {sums[4] / n, sums[5] / n, sums[6] / n};
     double sigma[9];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) sigma[3 * i + j] = sums[7 + 3 * j + i] / n - mu_d[i] * mu_s[j];
-    double U[9], sv[3], V[9];
-    svd3(sigma, U, sv, V);
+    double U[9], V[9];
+    svd3(sigma, U, u.sv, V);
     const double sgn = (det3(U) * det3(V) < 0) ? -1.0 : 1.0;
-    double R[9];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j)
-            R[3 * i + j] = U[3 * i] * V[3 * j] + U[3 * i + 1] * V[3 * j + 1] + sgn * U[3 * i + 2] * V[3 * j + 2];
+            u.R[3 * i + j] = U[3 * i] * V[3 * j] + U[3 * i + 1] * V[3 * j + 1] + sgn * U[3 * i + 2] * V[3 * j + 2];
+    u.n = n; u.sgn = sgn;
+    for (int i = 0; i < 3; ++i) { u.mu_s[i] = mu_s[i]; u.mu_d[i] = mu_d[i]; }
+}
+
+inline void rigid_from_sums(const double sums[NSUMS], float T[16]) {
+    UmeyamaRot u;
+    umeyama_rot(sums, u);
+    const double* R = u.R;
     for (int i = 0; i < 3; ++i) {
-        const double ti = mu_d[i] - (R[3 * i] * mu_s[0] + R[3 * i + 1] * mu_s[1] + R[3 * i + 2] * mu_s[2]);
+        const double ti = u.mu_d[i] - (R[3 * i] * u.mu_s[0] + R[3 * i + 1] * u.mu_s[1] + R[3 * i + 2] * u.mu_s[2]);
         T[4 * i + 0] = (float)R[3 * i + 0];
         T[4 * i + 1] = (float)R[3 * i + 1];
         T[4 * i + 2] = (float)R[3 * i + 2];
@@ -116,6 +130,39 @@ inline void rigid_from_sums(const double sums[NSUMS], float T[16]) {
     }
     T[12] = T[13] = T[14] = 0.f;
     T[15] = 1.f;
+}
+
+// ---- TransformationEstimationSVDScale -> Eigen umeyama(src, dst, with_scaling=true), the scale bounded --------------------
+// (kss_icp_sim in include/kssicp.h).  sums[17] = sum |p|^2 over the kept sources.  R as above (the same bits);
+// var = sums[17]/n - |mu_s|^2, s = ((sv0 + sv1) + sgn*sv2) / var, s_k = min(max(s, lo), hi); T = [ s_k R | mu_d - s_k R mu_s ]
+// rounded to float.  Ck (may be null): [ (float)R | t ], the step without its scale, for PCL's criteria.  False -- T (and Ck) the
+// identity, s_k = 1 -- when !(var > 0) or s is not finite or not > 0.  With s_k == 1.0, T is rigid_from_sums' bit for bit:
+// 1.0 * x is x.
+inline bool sim_from_sums(const double sums[NSUMS], double lo, double hi, float T[16], double* s_k, float* Ck = nullptr) {
+    mat4_identity(T);
+    if (Ck) mat4_identity(Ck);
+    *s_k = 1.0;
+    const double n0 = sums[0];   // (var first: a record that fails here -- empty, NaN, no spread -- never reaches the SVD)
+    const double m0 = sums[1] / n0, m1 = sums[2] / n0, m2 = sums[3] / n0;
+    const double var = sums[17] / n0 - ((m0 * m0 + m1 * m1) + m2 * m2);
+    if (!(var > 0.0)) return false;
+    UmeyamaRot u;
+    umeyama_rot(sums, u);
+    const double s = ((u.sv[0] + u.sv[1]) + u.sgn * u.sv[2]) / var;
+    if (!std::isfinite(s) || !(s > 0.0)) return false;
+    const double sk = std::fmin(std::fmax(s, lo), hi);
+    const double* R = u.R;
+    for (int i = 0; i < 3; ++i) {
+        const double ti = u.mu_d[i] - sk * ((R[3 * i] * u.mu_s[0] + R[3 * i + 1] * u.mu_s[1]) + R[3 * i + 2] * u.mu_s[2]);
+        for (int j = 0; j < 3; ++j) {
+            T[4 * i + j] = (float)(sk * R[3 * i + j]);
+            if (Ck) Ck[4 * i + j] = (float)R[3 * i + j];
+        }
+        T[4 * i + 3] = (float)ti;
+        if (Ck) Ck[4 * i + 3] = (float)ti;
+    }
+    *s_k = sk;
+    return true;
 }
 
 // ---- TransformationEstimationPointToPlaneLLS from the point-to-plane sums (KSS_P2L_NSUMS in include/kssicp.h) --------
@@ -247,7 +294,9 @@ struct Convergence {
     int state = 0;
 
     // iterations = nr_iterations_ AFTER the increment; Tk = this iteration's transformation_
-    bool has_converged(int iterations, const float Tk[16], double cur_mse) {
+    // scale_dev2 (the similarity step: (s_k - 1)^2, Tk its step without the scale): the transformation test also asks for
+    // scale_dev2 <= translation_threshold, the transformation epsilon
+    bool has_converged(int iterations, const float Tk[16], double cur_mse, double scale_dev2 = 0.0) {
         state = 0;
         if (iterations >= max_iterations) { state = 1; return true; }
         if (fixed_iterations) return false;
@@ -259,7 +308,7 @@ struct Convergence {
         tsq = tsq + Tk[7] * Tk[7];
         tsq = tsq + Tk[11] * Tk[11];
         const double translation_sqr = (double)tsq;
-        if (cos_angle >= rotation_threshold && translation_sqr <= translation_threshold) { state = 2; return true; }
+        if (cos_angle >= rotation_threshold && translation_sqr <= translation_threshold && scale_dev2 <= translation_threshold) { state = 2; return true; }
         if (std::fabs(cur_mse - prev_mse) < mse_abs) { state = 3; return true; }
         if (std::fabs(cur_mse - prev_mse) / prev_mse < mse_rel) { state = 4; return true; }
         prev_mse = cur_mse;

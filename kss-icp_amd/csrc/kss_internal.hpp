@@ -388,6 +388,8 @@ void launch_trim_select(hipStream_t st, const float* d_d2, int64_t n, double max
                         TrimState* d_state, double* d_info);
 // the KSS_NSUMS record from the point metric's rows (slots 17..19 are 0)
 void launch_trim_point_final(hipStream_t st, const double* d_rows, int nrows, double* d_out);
+// the similarity step's KSS_NSUMS record from SimMetric's rows (slot 17 kept, 18 and 19 are 0)
+void launch_sim_final(hipStream_t st, const double* d_rows, int nrows, double* d_out);
 void launch_f64_to_f32(hipStream_t st, const double* d_in, int64_t n, float* d_out);
 
 // ---- robust ICP ----
@@ -444,7 +446,8 @@ void launch_pairb_select(hipStream_t st, const float* d_d2, const PairbDesc* d_d
 // the median key of every active AUTOMATIC pair into a.ts[pair] (the others' entries are not written), over d_keys within bound
 void launch_pairb_robust_select(hipStream_t st, int npairs, const PairbArgs& a, const float* d_keys, double bound);
 // every active pair's record into d_out[pair * KSS_P2L_NSUMS] (the point metric fills KSS_NSUMS of them) ...
-void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out);
+// (sim: the similarity step's record, slot 17 kept)
+void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out, bool sim = false);
 // ... and the weighted one, with {m, c2, sum of weights, cnt} into d_info[pair * KSS_ROBUST_NINFO]
 void launch_pairb_robust_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out, double* d_info);
 

@@ -1,6 +1,6 @@
 // kss_pair.hip -- the correspondence sums of the pair metrics for ONE pair: point-to-plane (pcl::registration::
 // TransformationEstimationPointToPlaneLLS, PCL 1.8.1), trimmed (2.10), robust (2.12), generalized (2.14), symmetric
-// (2.16) and robust symmetric ICP (2.19); the definitions are restated in include/kssicp.h.
+// (2.16), robust symmetric (2.19) and similarity ICP (2.22); the definitions are restated in include/kssicp.h.
 //   pair_rows_kernel<M, SRC>  the one rows kernel: pair_walk (kss_pair_device.hpp) over the metric functor M with
 //                             the sources from SRC.  Grid of stream_blocks(n) workgroups of 256, lane t of workgroup b takes the
 //                             sources b * 256 + t + k * 256 * grid in ORIGINAL index order, then block_sum's wave tree and fixed
@@ -45,6 +45,7 @@ void launch_pair_rows(hipStream_t st, const PairArgs& a, const M& m) {
 KSS_PAIR_METRIC(PlaneMetric<false>);
 KSS_PAIR_METRIC(PlaneMetric<true>);
 KSS_PAIR_METRIC(PointTrimMetric);
+KSS_PAIR_METRIC(SimMetric);
 KSS_PAIR_METRIC(PlaneRobustMetric<PAIR_ROBUST>);
 KSS_PAIR_METRIC(PlaneRobustMetric<PAIR_KEY>);
 KSS_PAIR_METRIC(PointRobustMetric<PAIR_ROBUST>);

@@ -1,7 +1,8 @@
 // kss_pair_device.hpp -- the device code of the pair metrics (point-to-plane, trimmed, robust, generalized, symmetric and robust
-// symmetric ICP), for one pair (kss_pair.hip) and for many pairs per call (kss_pairb.hip):
+// symmetric ICP, similarity ICP), for one pair (kss_pair.hip) and for many pairs per call (kss_pairb.hip):
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
 //   gicp_source / symm_source        the same for generalized and for symmetric ICP,
+//   sim_point_source                 the same for similarity ICP (the point metric and the kept sources' sum of squares),
 //   the metric functors              one small struct per metric: the uniform parameters of a pass and the call of its body,
 //   pair_walk                        the ONE walk both forms run: a lane's sources in steps of the grid, the functor's body per
 //                                    source, then block_sum and the row store (or, for a keys metric, one key per source),
@@ -420,6 +421,44 @@ __device__ __forceinline__ void trim_point_source(double (&acc)[NSUMS], const fl
     }
 }
 
+// ---- similarity ICP ---------------------------------------------------------------------------------------
+// Source i as in trim_point_source's unweighted form: slots [0..16] are that record bit for bit (accumulate_corr's terms in its
+// order), and [17] += |p|^2 of the kept source -- f64 on the widened floats, the squares exact, nothing fused -- from the p
+// already in registers for the cross terms.  [18], [19] are not touched.  SRC_F3 (kss_sim_sums): the sources are the packed
+// float triples and d2 is recomputed as kss_cov does, lim = max_d2; otherwise lim = the pass's cut tau (-1: no candidate).
+template <int SRC>
+__device__ __forceinline__ void sim_point_source(double (&acc)[NSUMS], const float* __restrict__ src3, const float4* __restrict__ src4,
+                                                 const int32_t* __restrict__ perm, const int32_t* __restrict__ idx,
+                                                 const float* __restrict__ d2_in, const float* __restrict__ tgt, int64_t i, int64_t nt,
+                                                 double lim) {
+    const int64_t j = idx[i];
+    if (j < 0 || j >= nt) return;
+    float sx, sy, sz, d2f;
+    if constexpr (SRC == SRC_F3) {
+        sx = src3[3 * i]; sy = src3[3 * i + 1]; sz = src3[3 * i + 2];
+        d2f = dist2<false>(sx, sy, sz, tgt[3 * j], tgt[3 * j + 1], tgt[3 * j + 2]);
+    } else {
+        d2f = d2_in[i];
+    }
+    const double d2 = (double)d2f;
+    if (!(d2 >= 0.0 && d2 <= lim)) return;
+    if constexpr (SRC != SRC_F3) {
+        const float4 p4 = src4[SRC == SRC_F4_PERM ? (int64_t)perm[i] : i];
+        sx = p4.x; sy = p4.y; sz = p4.z;
+    }
+    const double p[3] = {(double)sx, (double)sy, (double)sz};
+    const double q[3] = {(double)tgt[3 * j], (double)tgt[3 * j + 1], (double)tgt[3 * j + 2]};
+    acc[0] += 1.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { acc[1 + k] += p[k]; acc[4 + k] += q[k]; }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int l = 0; l < 3; ++l) acc[7 + 3 * k + l] += p[k] * q[l];
+    acc[16] += d2;
+    acc[17] += (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2];
+}
+
 // ---- the metric functors and the walk ----------------------------------------------------------------------
 // c2 of a robust pass, derived by every workgroup that needs it from the selection's last TrimState (sel: not read with a fixed
 // scale): one f64 product or two, the same bits everywhere
@@ -459,6 +498,19 @@ struct PointTrimMetric {   // point metric over the correspondences at or below 
     template <int SRC>
     __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float*, int64_t i, int64_t nt, float*) const {
         trim_point_source<SRC == SRC_F4_PERM>(acc, s.src4, s.perm, s.idx, s.d2, tgt, i, nt, lim);
+    }
+};
+struct SimMetric {   // similarity step: the point metric's record and the kept sources' sum of squares; cut null: lim = max_d2 (packed triples)
+    static constexpr int NC = NSUMS;
+    static constexpr bool KEYS = false, F3 = true;
+    const double* cut;
+    double lim;
+    SimMetric(double max_d2, const double* cut_) : cut(cut_), lim(max_d2) {}
+    __device__ SimMetric(const PairbArgs& a, int p) : cut(&a.ts[p].cut), lim(0.0) {}
+    __device__ void begin() { if (cut) lim = *cut; }   // tau of this pass (-1: no candidate), written by the selection
+    template <int SRC>
+    __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float*, int64_t i, int64_t nt, float*) const {
+        sim_point_source<SRC>(acc, s.src3, s.src4, s.perm, s.idx, s.d2, tgt, i, nt, lim);
     }
 };
 // the scale of a robust pass: the pair's RobustScale and where its selection left the median key

@@ -1,4 +1,4 @@
-// kss_pairb.hip -- the pair metrics for MANY pairs per call (DESIGN.md 2.11, 2.13, 2.15, 2.18, 2.20, 2.21): per lockstep pass a
+// kss_pairb.hip -- the pair metrics for MANY pairs per call (DESIGN.md 2.11, 2.13, 2.15, 2.18, 2.20, 2.21, 2.22): per lockstep pass a
 // handful of launches for the whole batch behind the NN pass, whatever the pair count.
 //   pairb_rows_kernel<M, PERM>   the one rows kernel: grid = the sum over the pairs of stream_blocks(ns_p) workgroups, mapped through
 //                         a row -> pair table.  Workgroup b of pair p builds the metric functor M from the per-pair tables at p
@@ -109,8 +109,9 @@ __global__ __launch_bounds__(P2L_THREADS) void pairb_rows_kernel(const PairbArgs
                                               (int64_t)d.nrows * P2L_THREADS, d.nt, a.rows, a.keys);
 }
 
-// out: KSS_P2L_NSUMS doubles per pair for either metric (the point record fills the first KSS_NSUMS; slots 17..19 are 0)
-template <bool PLANE>
+// out: KSS_P2L_NSUMS doubles per pair for either metric (the point record fills the first KSS_NSUMS; slots 17..19 are 0; SIM, the
+// similarity step's record: 17 is kept, 18 and 19 are 0)
+template <bool PLANE, bool SIM = false>
 __global__ __launch_bounds__(P2L_THREADS) void pairb_final_kernel(const double* __restrict__ rows, const PairbDesc* __restrict__ desc,
                                                                   const PairState* __restrict__ state, double* __restrict__ out) {
     constexpr int NC = PLANE ? P2L_NSUMS : NSUMS;
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(P2L_THREADS) void pairb_final_kernel(const double* 
         if (threadIdx.x < P2L_NSUMS) o[threadIdx.x] = threadIdx.x == P2L_NSUMS - 1 ? 0.0 : v;
     } else {
         const double v = rows_column_sum(r, d.nrows, shg);
-        if (threadIdx.x < NSUMS) o[threadIdx.x] = threadIdx.x >= 17 ? 0.0 : v;
+        if (threadIdx.x < NSUMS) o[threadIdx.x] = threadIdx.x >= (SIM ? 18 : 17) ? 0.0 : v;
     }
 }
 
@@ -195,6 +196,7 @@ void launch_pairb_rows(hipStream_t st, int total_rows, const PairbArgs& a) {
 KSS_PAIRB_METRIC(PlaneMetric<false>);
 KSS_PAIRB_METRIC(PlaneMetric<true>);
 KSS_PAIRB_METRIC(PointTrimMetric);   // (the untrimmed point metric is kss_icp_batch's)
+KSS_PAIRB_METRIC(SimMetric);
 KSS_PAIRB_METRIC(PlaneRobustMetric<PAIR_ROBUST>);
 KSS_PAIRB_METRIC(PlaneRobustMetric<PAIR_KEY>);
 KSS_PAIRB_METRIC(PointRobustMetric<PAIR_ROBUST>);   // (its keys are the NN pass's d2)
@@ -208,9 +210,10 @@ void launch_pairb_robust_select(hipStream_t st, int npairs, const PairbArgs& a, 
     hipLaunchKernelGGL(pairb_robust_select_kernel, dim3(npairs), dim3(TRIM_HIST_THREADS), 0, st, d_keys, a.desc, a.state, a.rs, bound, a.ts);
 }
 
-void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out) {
+void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out, bool sim) {
     const dim3 g(npairs), b(P2L_THREADS);
-    if (plane) hipLaunchKernelGGL(pairb_final_kernel<true>, g, b, 0, st, (const double*)a.rows, a.desc, a.state, d_out);
+    if (sim) hipLaunchKernelGGL((pairb_final_kernel<false, true>), g, b, 0, st, (const double*)a.rows, a.desc, a.state, d_out);
+    else if (plane) hipLaunchKernelGGL(pairb_final_kernel<true>, g, b, 0, st, (const double*)a.rows, a.desc, a.state, d_out);
     else hipLaunchKernelGGL(pairb_final_kernel<false>, g, b, 0, st, (const double*)a.rows, a.desc, a.state, d_out);
 }
 

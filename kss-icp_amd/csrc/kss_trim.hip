@@ -152,6 +152,17 @@ __global__ __launch_bounds__(TRIM_THREADS) void trim_point_final_kernel(const do
     if (threadIdx.x < NSUMS) out[threadIdx.x] = threadIdx.x >= 17 ? 0.0 : v;
 }
 
+// similarity ICP: the same column sums, slot 17 (the kept sources' sum of squares) kept, 18 and 19 are 0
+__global__ __launch_bounds__(TRIM_THREADS) void sim_final_kernel(const double* __restrict__ rows, int nrows, double* __restrict__ out) {
+    __shared__ double shg[ROWSUM_GROUPS][NSUMS];
+    const double v = rows_column_sum(rows, nrows, shg);
+    if (threadIdx.x < NSUMS) out[threadIdx.x] = threadIdx.x >= 18 ? 0.0 : v;
+}
+
+void launch_sim_final(hipStream_t st, const double* d_rows, int nrows, double* d_out) {
+    hipLaunchKernelGGL(sim_final_kernel, dim3(1), dim3(TRIM_THREADS), 0, st, d_rows, nrows, d_out);
+}
+
 void launch_trim_point_final(hipStream_t st, const double* d_rows, int nrows, double* d_out) {
     hipLaunchKernelGGL(trim_point_final_kernel, dim3(1), dim3(TRIM_THREADS), 0, st, d_rows, nrows, d_out);
 }
