@@ -474,6 +474,72 @@ int kss_trim_threshold_batch(kss_ctx *ctx, const float *d2_all, const int64_t *o
 int kss_trim_threshold_batch_dev(kss_ctx *ctx, const float *d_d2_all, const int64_t *off, int nseg, double max_d2,
                                  const double *overlaps, double *info_all);
 
+/* ---- one-to-one ICP: each target keeps its closest source (PCL's CorrespondenceRejectorOneToOne in front of kss_icp_trimmed's
+ *      pass), both metrics, one pair and MANY pairs per call ----
+ * One pass, on the NN pass's idx[i] and float d2[i], both by original source index, i counting from 0 within the pair:
+ *   candidate   idx[i] in [0, nt) and 0 <= d2[i] <= max_d2 (ordered compares in double, as in kss_icp_trimmed: a NaN is none), m of them;
+ *   key         key(i) = ((uint64)(bits(d2[i]) & 0x7fffffff) << 32) | (uint32)i: the masking makes -0.0f count as +0.0f;
+ *   winner      of target j: the candidate with idx == j and the smallest key -- the smallest d2, ties going to the lowest original
+ *               source index; u = the number of targets that have a winner;
+ *   filtered    idx_f, d2_f: a winner keeps idx[i] and d2[i] bit for bit; a losing candidate gets idx_f = -1 and d2_f = the quiet NaN
+ *               0x7fc00000; a source that is no candidate passes through unchanged;
+ *   the pass    kss_icp_trimmed's pass on (idx_f, d2_f), nothing redefined: its candidates are the u survivors, k = kss_trim_rank(u,
+ *               overlap), tau the exact k-th smallest, ties at tau kept, the KSS_NSUMS (point) or KSS_P2L_NSUMS (plane) record in the
+ *               same fixed order (the plane record's [29] runs over the sources whose idx_f is in [0, nt)), the same solve;
+ *   info        KSS_O2O_NINFO doubles {u, k, tau, kept, m}.
+ * The loop is kss_icp_trimmed's own: PCL's criteria, KSS_STATE_NO_CORRESPONDENCES, KSS_STATE_DEGENERATE, normals given or computed,
+ * p->allreduce must be NULL; fitness over ALL sources, fitness_idx / fitness_d2 the unfiltered NN.  Neither the overlap share nor a
+ * residual scale has to be known: at overlap 1 the sources outside the overlap, which all choose the few targets at its rim, lose
+ * their correspondences to the closest of them.
+ * Where no two candidates share a target in any pass the call is kss_icp_trimmed at the same overlap and metric BIT FOR BIT: T,
+ * iterations, state, last_mse, every traced T_k and sums row, and info [0..3].
+ * Behind the NN pass a pass makes three launches -- table reset, claim, resolve -- and then the trimmed pass's own: six more for one
+ * pair, three more for a batch, whatever the pair count.
+ * Not offered: the rejection in front of the robust, generalized, symmetric and similarity forms; reciprocal correspondences; the
+ * C++ mirror classes and the CLI. */
+#define KSS_O2O_NINFO 5   /* {u survivors, k rank, tau widened to double, kept, m candidates before the rejection} */
+/* The filter alone for n sources against nt targets: idx_out / d2_out receive idx_f / d2_f (either may be NULL, either may be its
+ * input), info = {m, u}.  KSS_ERR_ARG: a NULL ctx (refused before anything touches the device), idx, d2 or info; n or nt <= 0 or
+ * beyond the C-ABI's cloud size. */
+int kss_o2o_filter(kss_ctx *ctx, const int32_t *idx, const float *d2, int64_t n, int64_t nt, double max_d2, int32_t *idx_out,
+                   float *d2_out, double info[2]);
+int kss_o2o_filter_dev(kss_ctx *ctx, const int32_t *d_idx, const float *d_d2, int64_t n, int64_t nt, double max_d2, int32_t *d_idx_out,
+                       float *d_d2_out, double info[2]);
+/* nseg segments [off[i], off[i + 1]) of idx_all / d2_all (nseg + 1 HOST offsets), segment i against nts[i] targets, in the same three
+ * launches: every segment equals the single call on it.  The outputs are indexed like the inputs; info_all: nseg * 2 doubles.
+ * An empty segment or an nts entry <= 0 is KSS_ERR_ARG. */
+int kss_o2o_filter_batch(kss_ctx *ctx, const int32_t *idx_all, const float *d2_all, const int64_t *off, const int64_t *nts, int nseg,
+                         double max_d2, int32_t *idx_out_all, float *d2_out_all, double *info_all);
+int kss_o2o_filter_batch_dev(kss_ctx *ctx, const int32_t *d_idx_all, const float *d_d2_all, const int64_t *off, const int64_t *nts,
+                             int nseg, double max_d2, int32_t *d_idx_out_all, float *d_d2_out_all, double *info_all);
+typedef struct {
+    double  overlap;     /* share of the survivors kept per pass, 0 < overlap <= 1 */
+    int     metric;      /* KSS_METRIC_POINT or KSS_METRIC_PLANE */
+    double *trace_o2o;   /* p->trace_cap * KSS_O2O_NINFO doubles, row i beside trace_sums row i; may be NULL */
+} kss_o2o_params;
+/* overlap 1, KSS_METRIC_POINT, trace_o2o NULL */
+int kss_o2o_default_params(kss_o2o_params *op);
+/* Arguments as kss_icp_trimmed; last_info (may be NULL): the last pass's record, all zero when no pass ran.  KSS_ERR_ARG: everything
+ * kss_icp_trimmed refuses, a NULL op, a NULL ctx (refused before anything touches the device).  A refused call leaves the context
+ * usable. */
+int kss_icp_o2o(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt, int64_t nt, const float *tgt_normals,
+                const kss_icp_params *p, const kss_o2o_params *op, kss_icp_result *res, double last_info[KSS_O2O_NINFO]);
+int kss_icp_o2o_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
+                    const kss_icp_params *p, const kss_o2o_params *op, kss_icp_result *res, double last_info[KSS_O2O_NINFO]);
+/* One-to-one ICP for MANY pairs per call.  Arguments as kss_icp_trimmed_batch: overlaps one per pair, or NULL for op->overlap
+ * everywhere; info_all: npairs * KSS_O2O_NINFO doubles, every pair's last record (may be NULL).  Nothing is redefined: every pair's
+ * record -- T, iterations, state, converged, last_mse, its info, pair 0's traces -- is the single-pair call's BIT FOR BIT (fitness: to
+ * the rounding of the NN engine's own summation order), in any batch order and any split over calls, under every nn_mode and tuning
+ * knob; results[i].pair_id = i.  One claim table serves the whole batch; a pair that ends leaves the others untouched.  trace_*,
+ * op->trace_o2o and fitness_idx / fitness_d2 describe pair 0.  KSS_ERR_ARG: everything kss_icp_trimmed_batch refuses, a NULL op, a
+ * NULL ctx. */
+int kss_icp_o2o_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *tgt_all, const int64_t *tgt_off,
+                      const float *tgt_normals_all, int npairs, const kss_icp_params *p, const kss_o2o_params *op,
+                      const double *overlaps, kss_icp_result *results, double *info_all);
+int kss_icp_o2o_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_tgt_all, const int64_t *tgt_off,
+                          const float *d_tgt_normals_all, int npairs, const kss_icp_params *p, const kss_o2o_params *op,
+                          const double *overlaps, kss_icp_result *results, double *info_all);
+
 /* ---- generalized ICP (plane-to-plane; Segal, Haehnel, Thrun: Generalized-ICP, RSS 2009) for one pair ----
  * Both clouds carry a local surface model: PCL-style GICP replaces the eigenvalues of each point's k-NN covariance by
  * (epsilon, 1, 1), which is I - (1 - epsilon) n n^T with n the smallest eigenvector -- the normal kss_normals computes.  So the

@@ -23,6 +23,7 @@ TRIM_NINFO = 4           # KSS_TRIM_NINFO: {m candidates, k rank, tau, kept} of 
 LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY = 0, 1, 2, 3   # KSS_LOSS_*: the weight of kss_icp_robust
 ROBUST_NINFO = 4         # KSS_ROBUST_NINFO: {m candidates, c2, sum of weights, cnt kept} of a robust pass
 SIM_NINFO = 6            # KSS_SIM_NINFO: {m, k, tau, kept, s_k, s_acc after the pass} of a similarity pass
+O2O_NINFO = 5            # KSS_O2O_NINFO: {u survivors, k, tau, kept, m candidates} of a one-to-one pass
 F32, F64 = 0, 1
 
 # every symbol include/kssicp.h declares (checked by tests/test_abi.py against the header text)
@@ -48,6 +49,8 @@ SYMBOLS = [
     "kss_icp_symm_robust_batch", "kss_icp_symm_robust_batch_dev",
     "kss_sim_default_params", "kss_sim_from_sums", "kss_sim_sums", "kss_sim_sums_dev", "kss_icp_sim", "kss_icp_sim_dev",
     "kss_icp_sim_batch", "kss_icp_sim_batch_dev",
+    "kss_o2o_filter", "kss_o2o_filter_dev", "kss_o2o_filter_batch", "kss_o2o_filter_batch_dev", "kss_o2o_default_params",
+    "kss_icp_o2o", "kss_icp_o2o_dev", "kss_icp_o2o_batch", "kss_icp_o2o_batch_dev",
 ]
 
 
@@ -86,6 +89,10 @@ class TrimParams(C.Structure):
 
 class SimParams(C.Structure):
     _fields_ = [("overlap", C.c_double), ("scale_min", C.c_double), ("scale_max", C.c_double), ("trace_sim", C.POINTER(C.c_double))]
+
+
+class O2oParams(C.Structure):
+    _fields_ = [("overlap", C.c_double), ("metric", C.c_int), ("trace_o2o", C.POINTER(C.c_double))]
 
 
 class RobustParams(C.Structure):
@@ -183,6 +190,15 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, C.POINTER(IcpParams), C.POINTER(SimParams), C.POINTER(IcpResult), vp]
     for n in ("kss_icp_sim_batch", "kss_icp_sim_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(SimParams), vp, vp, vp]
+    L.kss_o2o_default_params.argtypes = [C.POINTER(O2oParams)]
+    for n in ("kss_o2o_filter", "kss_o2o_filter_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, i64, i64, dbl, vp, vp, vp]
+    for n in ("kss_o2o_filter_batch", "kss_o2o_filter_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp]
+    for n in ("kss_icp_o2o", "kss_icp_o2o_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(O2oParams), C.POINTER(IcpResult), vp]
+    for n in ("kss_icp_o2o_batch", "kss_icp_o2o_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(O2oParams), vp, vp, vp]
     L.kss_robust_default_params.argtypes = [C.c_int, C.c_int, C.POINTER(RobustParams)]
     L.kss_robust_weight.argtypes = [C.c_int, dbl, dbl, C.POINTER(dbl)]
     L.kss_robust_scale2.argtypes = [C.c_int, dbl, C.c_float, dbl, C.POINTER(dbl)]
@@ -346,6 +362,20 @@ def sim_params(**kw):
         else:
             raise AttributeError(k)
     return sp
+
+
+def o2o_params(**kw):
+    """kss_o2o_default_params (overlap 1, point metric), then the fields given by keyword."""
+    L = load_library()
+    op = O2oParams()
+    rc = L.kss_o2o_default_params(C.byref(op))
+    if rc != 0:
+        raise KssError(rc, "kss_o2o_default_params")
+    for k, v in kw.items():
+        if not hasattr(op, k):
+            raise AttributeError(k)
+        setattr(op, k, v)
+    return op
 
 
 def sim_from_sums(sums, lo=0.5, hi=2.0):
@@ -621,8 +651,9 @@ class Context:
     def _icp_call(self, call, where, p, ns, ncol, trace_cap, fitness_corr, tp=None):
         """call(res) with the trace and fitness_corr arrays attached to the params p (and to the TrimParams or RobustParams tp),
         detached again whether it returns or raises; the result dictionary of icp()."""
-        tname = "trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else "trace_trim"
-        ninfo = SIM_NINFO if isinstance(tp, SimParams) else TRIM_NINFO
+        tname = ("trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else
+                 "trace_o2o" if isinstance(tp, O2oParams) else "trace_trim")
+        ninfo = SIM_NINFO if isinstance(tp, SimParams) else O2O_NINFO if isinstance(tp, O2oParams) else TRIM_NINFO
         res = IcpResult()
         tr = None
         fc = None
@@ -644,7 +675,7 @@ class Context:
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-                if isinstance(tp, (RobustParams, SimParams)):
+                if isinstance(tp, (RobustParams, SimParams, O2oParams)):
                     setattr(tp, tname, None)
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
@@ -739,6 +770,70 @@ class Context:
         self._chk(self.L.kss_icp_trimmed_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
                                              C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(tp),
                                              C.byref(res), _p(info)), "kss_icp_trimmed_dev")
+        return res, info
+
+    # ---- one-to-one ICP
+    def o2o_filter(self, idx, d2, nt, max_d2=1.0, want_idx=True, want_d2=True, alias=False):
+        """kss_o2o_filter: (idx_f, d2_f, m, u) of the NN map idx (int32) / d2 (float32) against nt targets; an output that is not
+        wanted is None.  alias: the library writes into (copies of) the inputs themselves."""
+        i = np.array(idx, dtype=np.int32).reshape(-1)
+        d = np.array(d2, dtype=np.float32).reshape(-1)
+        if len(i) != len(d):
+            raise ValueError("idx and d2 must have one entry per source")
+        io = (i if alias else np.empty_like(i)) if want_idx else None
+        do = (d if alias else np.empty_like(d)) if want_d2 else None
+        info = np.zeros(2, np.float64)
+        self._chk(self.L.kss_o2o_filter(self.h, _p(i), _p(d), len(i), int(nt), float(max_d2), _p(io), _p(do), _p(info)), "kss_o2o_filter")
+        return io, do, int(info[0]), int(info[1])
+
+    def o2o_filter_dev(self, d_idx, d_d2, n, nt, max_d2=1.0, d_idx_out=None, d_d2_out=None):
+        """kss_o2o_filter_dev on device pointers (an output may be 0 / None, or its input); returns (m, u)."""
+        info = np.zeros(2, np.float64)
+        self._chk(self.L.kss_o2o_filter_dev(self.h, C.c_void_p(int(d_idx)), C.c_void_p(int(d_d2)), int(n), int(nt), float(max_d2),
+                                            C.c_void_p(int(d_idx_out)) if d_idx_out else None,
+                                            C.c_void_p(int(d_d2_out)) if d_d2_out else None, _p(info)), "kss_o2o_filter_dev")
+        return int(info[0]), int(info[1])
+
+    def o2o_filter_batch(self, idx_all, d2_all, off, nts, max_d2=1.0):
+        """kss_o2o_filter_batch: the filter of every segment [off[i], off[i + 1]) against nts[i] targets in one call.  Returns
+        (idx_f, d2_f, info nseg x 2 = {m, u}); entries outside the segments are left as given."""
+        i = np.array(idx_all, dtype=np.int32).reshape(-1)
+        d = np.array(d2_all, dtype=np.float32).reshape(-1)
+        o = np.ascontiguousarray(off, dtype=np.int64)
+        nt = np.ascontiguousarray(nts, dtype=np.int64)
+        if len(nt) != len(o) - 1:
+            raise ValueError("nts must hold one entry per segment")
+        io, do = i.copy(), d.copy()
+        info = np.zeros((len(nt), 2), np.float64)
+        self._chk(self.L.kss_o2o_filter_batch(self.h, _p(i), _p(d), _p(o), _p(nt), len(nt), float(max_d2), _p(io), _p(do), _p(info)),
+                  "kss_o2o_filter_batch")
+        return io, do, info
+
+    def icp_o2o(self, src, tgt, normals=None, overlap=1.0, metric=METRIC_POINT, params=None, trace_cap=0, fitness_corr=False):
+        """One-to-one ICP (kss_icp_o2o): of all sources that chose one target only the closest keeps its correspondence, then
+        icp_trimmed()'s pass at `overlap` over the survivors.  Arguments and result dictionary as icp_trimmed(), with trace_o2o
+        (one {u, k, tau, kept, m} row per traced pass) and o2o_info (the last pass's) in place of the trimmed records."""
+        s, t = _f32(src), _f32(tgt)
+        nr = _f32(normals) if normals is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        p = params if params is not None else self.icp_params()
+        op = O2oParams(float(overlap), int(metric), None)
+        info = np.zeros(O2O_NINFO, np.float64)
+        out = self._icp_call(lambda res: self.L.kss_icp_o2o(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(op),
+                                                            C.byref(res), _p(info)),
+                             "kss_icp_o2o", p, len(s), P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, op)
+        out["o2o_info"] = info
+        return out
+
+    def icp_o2o_dev(self, d_src, ns, d_tgt, nt, d_normals, params, overlap=1.0, metric=METRIC_POINT):
+        """kss_icp_o2o_dev on device pointers (d_normals may be 0 / None); returns (IcpResult, o2o_info)."""
+        res = IcpResult()
+        op = O2oParams(float(overlap), int(metric), None)
+        info = np.zeros(O2O_NINFO, np.float64)
+        self._chk(self.L.kss_icp_o2o_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
+                                         C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(op),
+                                         C.byref(res), _p(info)), "kss_icp_o2o_dev")
         return res, info
 
     # ---- similarity ICP
@@ -1008,8 +1103,9 @@ class Context:
     def _batch_call(self, call, where, p, so, ncol, trace_cap, fitness_corr, tp=None):
         """call(res) for a batch: the trace and fitness_corr arrays (pair 0's) attached to p / tp as in _icp_call, detached again
         whether it returns or raises.  Returns (list of IcpResult, extras of pair 0)."""
-        tname = "trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else "trace_trim"
-        ninfo = SIM_NINFO if isinstance(tp, SimParams) else TRIM_NINFO
+        tname = ("trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else
+                 "trace_o2o" if isinstance(tp, O2oParams) else "trace_trim")
+        ninfo = SIM_NINFO if isinstance(tp, SimParams) else O2O_NINFO if isinstance(tp, O2oParams) else TRIM_NINFO
         npairs = len(so) - 1
         res = (IcpResult * npairs)()
         ns0 = int(so[1] - so[0]) if npairs > 0 else 0
@@ -1032,7 +1128,7 @@ class Context:
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-                if isinstance(tp, (RobustParams, SimParams)):
+                if isinstance(tp, (RobustParams, SimParams, O2oParams)):
                     setattr(tp, tname, None)
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
@@ -1117,6 +1213,39 @@ class Context:
         self._chk(self.L.kss_icp_trimmed_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
                                                    C.c_void_p(int(d_normals_all)) if d_normals_all else None, npairs, C.byref(params),
                                                    C.byref(tp), _p(ov), C.cast(res, C.c_void_p), _p(info)), "kss_icp_trimmed_batch_dev")
+        return list(res), info
+
+    def icp_o2o_batch(self, src_all, src_off, tgt_all, tgt_off, normals_all=None, overlaps=None, overlap=1.0, metric=METRIC_POINT,
+                      params=None, trace_cap=0, fitness_corr=False):
+        """kss_icp_o2o_batch: one-to-one ICP of npairs pairs in one call.  Arguments as icp_trimmed_batch().  Returns (list of
+        IcpResult, o2o_info of every pair as npairs x O2O_NINFO, dictionary with pair 0's traces)."""
+        s, t = _f32(src_all), _f32(tgt_all)
+        nr = _f32(normals_all) if normals_all is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        ov = self._overlaps(overlaps, npairs)
+        p = params if params is not None else self.icp_params()
+        op = O2oParams(float(overlap), int(metric), None)
+        info = np.zeros((max(npairs, 0), O2O_NINFO), np.float64)
+        res, extra = self._batch_call(
+            lambda res: self.L.kss_icp_o2o_batch(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), npairs, C.byref(p), C.byref(op), _p(ov), res, _p(info)),
+            "kss_icp_o2o_batch", p, so, P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, op)
+        return res, info, extra
+
+    def icp_o2o_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params, overlaps=None, overlap=1.0,
+                          metric=METRIC_POINT):
+        """kss_icp_o2o_batch_dev on device pointers; returns (list of IcpResult, o2o_info npairs x O2O_NINFO)."""
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        ov = self._overlaps(overlaps, npairs)
+        res = (IcpResult * npairs)()
+        op = O2oParams(float(overlap), int(metric), None)
+        info = np.zeros((npairs, O2O_NINFO), np.float64)
+        self._chk(self.L.kss_icp_o2o_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
+                                               C.c_void_p(int(d_normals_all)) if d_normals_all else None, npairs, C.byref(params),
+                                               C.byref(op), _p(ov), C.cast(res, C.c_void_p), _p(info)), "kss_icp_o2o_batch_dev")
         return list(res), info
 
     def icp_sim_batch(self, src_all, src_off, tgt_all, tgt_off, overlaps=None, sp=None, params=None, trace_cap=0, fitness_corr=False):

@@ -1,5 +1,5 @@
 // kss_api.hip -- the C-ABI of include/kssicp.h: context and profiling entry points, and the compute entry points over
-// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_robust / kss_pairb .hip).
+// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_robust / kss_pairb / kss_o2o .hip).
 // There is no CPU compute fallback anywhere in this file.
 #pragma clang fp contract(off)
 
@@ -72,7 +72,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_slot, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp, &c->o2o_table, &c->o2o_idx, &c->o2o_d2};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -1180,7 +1180,7 @@ static int batch_normals_dev(kss_ctx* c, const float* d_pts, const int64_t* off,
 // indexed from 0.  tp: null for kss_icp_p2l_batch.
 static int pairs_batch_dev(kss_ctx* c, const char* who, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off,
                            const float* d_nrm, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
-                           kss_icp_result* results, double* info_all) {
+                           kss_icp_result* results, double* info_all, bool unique = false) {
     if (!c) return KSS_ERR_ARG;
     if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": bad batch").c_str());
     KCHK(pair_check(c, who, tp != nullptr, d_src, d_tgt, 0, 0, d_nrm, p, tp, results, src_off, tgt_off, npairs, overlaps));
@@ -1192,6 +1192,7 @@ static int pairs_batch_dev(kss_ctx* c, const char* who, const float* d_src, cons
     PairMode mode;
     mode.plane = !tp || tp->metric == KSS_METRIC_PLANE;
     mode.trimmed = tp != nullptr;
+    mode.unique = unique;   // (kss_icp_o2o_batch: tp built from its kss_o2o_params)
     mode.trace_info = tp ? tp->trace_trim : nullptr;
     std::vector<double> ov;
     if (tp) ov.assign((size_t)npairs, tp->overlap);
@@ -1203,7 +1204,7 @@ static int pairs_batch_dev(kss_ctx* c, const char* who, const float* d_src, cons
 // host clouds: the batch's slices of the packed arrays are staged, then the device form runs
 static int pairs_batch_host(kss_ctx* c, const char* who, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off,
                             const float* nrm, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
-                            kss_icp_result* results, double* info_all) {
+                            kss_icp_result* results, double* info_all, bool unique = false) {
     if (!c) return KSS_ERR_ARG;
     if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": bad batch").c_str());
     KCHK(pair_check(c, who, tp != nullptr, src, tgt, 0, 0, nrm, p, tp, results, src_off, tgt_off, npairs, overlaps));
@@ -1215,7 +1216,7 @@ static int pairs_batch_host(kss_ctx* c, const char* who, const float* src, const
     std::vector<int64_t> so(npairs + 1), to(npairs + 1);
     for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
     return pairs_batch_dev(c, who, (const float*)c->stage_src.p, so.data(), (const float*)c->stage_tgt.p, to.data(),
-                           nrm ? (const float*)c->pb_nrm.p : nullptr, npairs, p, tp, overlaps, results, info_all);
+                           nrm ? (const float*)c->pb_nrm.p : nullptr, npairs, p, tp, overlaps, results, info_all, unique);
 }
 
 int kss_icp_p2l_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
@@ -1240,6 +1241,117 @@ int kss_icp_trimmed_batch(kss_ctx* c, const float* src_all, const int64_t* src_o
                           kss_icp_result* results, double* info_all) {
     if (c && !tp) return set_err(c, KSS_ERR_ARG, "icp_trimmed_batch: null argument");
     return pairs_batch_host(c, "icp_trimmed_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, tp, overlaps, results, info_all);
+}
+
+// ---- one-to-one ICP: kss_icp_trimmed's checks, staging and loop with PairMode::unique ----
+int kss_o2o_default_params(kss_o2o_params* op) {
+    if (!op) return KSS_ERR_ARG;
+    op->overlap = 1.0;
+    op->metric = KSS_METRIC_POINT;
+    op->trace_o2o = nullptr;
+    return KSS_OK;
+}
+
+static inline kss_trim_params o2o_trim_params(const kss_o2o_params* op) { return kss_trim_params{op->overlap, op->metric, op->trace_o2o}; }
+
+int kss_icp_o2o_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                    const kss_icp_params* p, const kss_o2o_params* op, kss_icp_result* res, double last_info[KSS_O2O_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!op) return set_err(c, KSS_ERR_ARG, "icp_o2o: null argument");
+    const kss_trim_params tp = o2o_trim_params(op);
+    KCHK(pair_check(c, "icp_o2o", true, d_src, d_tgt, ns, nt, d_nrm, p, &tp, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    PairMode mode;
+    mode.plane = tp.metric == KSS_METRIC_PLANE;
+    mode.trimmed = true;
+    mode.unique = true;
+    mode.overlap = tp.overlap;
+    mode.trace_info = tp.trace_trim;
+    mode.last_info = last_info;
+    if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
+}
+
+int kss_icp_o2o(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
+                const kss_icp_params* p, const kss_o2o_params* op, kss_icp_result* res, double last_info[KSS_O2O_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!op) return set_err(c, KSS_ERR_ARG, "icp_o2o: null argument");
+    const kss_trim_params tp = o2o_trim_params(op);
+    KCHK(pair_check(c, "icp_o2o", true, src, tgt, ns, nt, nrm, p, &tp, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_o2o_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
+                           p, op, res, last_info);
+}
+
+int kss_icp_o2o_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
+                          const float* d_nrm_all, int npairs, const kss_icp_params* p, const kss_o2o_params* op, const double* overlaps,
+                          kss_icp_result* results, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    if (!op) return set_err(c, KSS_ERR_ARG, "icp_o2o_batch: null argument");
+    const kss_trim_params tp = o2o_trim_params(op);
+    return pairs_batch_dev(c, "icp_o2o_batch", d_src_all, src_off, d_tgt_all, tgt_off, d_nrm_all, npairs, p, &tp, overlaps, results, info_all, true);
+}
+
+int kss_icp_o2o_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
+                      const float* nrm_all, int npairs, const kss_icp_params* p, const kss_o2o_params* op, const double* overlaps,
+                      kss_icp_result* results, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    if (!op) return set_err(c, KSS_ERR_ARG, "icp_o2o_batch: null argument");
+    const kss_trim_params tp = o2o_trim_params(op);
+    return pairs_batch_host(c, "icp_o2o_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, &tp, overlaps, results, info_all, true);
+}
+
+// the filter alone: the arguments of the four entry points
+static int o2o_filter_check(kss_ctx* c, const void* idx, const void* d2, const int64_t* off, const int64_t* nts, int nseg, const double* info) {
+    if (!idx || !d2 || !off || !nts || !info) return set_err(c, KSS_ERR_ARG, "o2o_filter: null argument");
+    if (nseg <= 0) return set_err(c, KSS_ERR_ARG, "o2o_filter: no segment");
+    for (int i = 0; i < nseg; ++i) {
+        const int64_t n = off[i + 1] - off[i];
+        if (n <= 0 || n > 0x7fff0000ll || nts[i] <= 0 || nts[i] > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "o2o_filter: segment or target count empty or out of range");
+    }
+    if (off[nseg] - off[0] > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "o2o_filter: batch too large");
+    return KSS_OK;
+}
+
+int kss_o2o_filter_batch_dev(kss_ctx* c, const int32_t* d_idx_all, const float* d_d2_all, const int64_t* off, const int64_t* nts, int nseg,
+                             double max_d2, int32_t* d_idx_out_all, float* d_d2_out_all, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(o2o_filter_check(c, d_idx_all, d_d2_all, off, nts, nseg, info_all));
+    return o2o_filter_dev(c, d_idx_all, d_d2_all, off, nts, nseg, max_d2, d_idx_out_all, d_d2_out_all, info_all);
+}
+
+int kss_o2o_filter_batch(kss_ctx* c, const int32_t* idx_all, const float* d2_all, const int64_t* off, const int64_t* nts, int nseg,
+                         double max_d2, int32_t* idx_out_all, float* d2_out_all, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(o2o_filter_check(c, idx_all, d2_all, off, nts, nseg, info_all));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t o0 = off[0], n = off[nseg] - o0;
+    KCHK(upload(c, c->stage_idx, idx_all + o0, (size_t)n * sizeof(int32_t)));
+    KCHK(upload(c, c->stage_d2, d2_all + o0, (size_t)n * sizeof(float)));
+    std::vector<int64_t> o(nseg + 1);
+    for (int i = 0; i <= nseg; ++i) o[i] = off[i] - o0;
+    // filtered in place on the staged copies, then back to whichever outputs the caller gave
+    KCHK(o2o_filter_dev(c, (const int32_t*)c->stage_idx.p, (const float*)c->stage_d2.p, o.data(), nts, nseg, max_d2,
+                        idx_out_all ? (int32_t*)c->stage_idx.p : nullptr, d2_out_all ? (float*)c->stage_d2.p : nullptr, info_all));
+    if (idx_out_all) HIPCHK(c, hipMemcpyAsync(idx_out_all + o0, c->stage_idx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (d2_out_all) HIPCHK(c, hipMemcpyAsync(d2_out_all + o0, c->stage_d2.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KSS_OK;
+}
+
+int kss_o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, int64_t n, int64_t nt, double max_d2, int32_t* d_idx_out,
+                       float* d_d2_out, double info[2]) {
+    const int64_t off[2] = {0, n};
+    return kss_o2o_filter_batch_dev(c, d_idx, d_d2, off, &nt, 1, max_d2, d_idx_out, d_d2_out, info);
+}
+
+int kss_o2o_filter(kss_ctx* c, const int32_t* idx, const float* d2, int64_t n, int64_t nt, double max_d2, int32_t* idx_out, float* d2_out,
+                   double info[2]) {
+    const int64_t off[2] = {0, n};
+    return kss_o2o_filter_batch(c, idx, d2, off, &nt, 1, max_d2, idx_out, d2_out, info);
 }
 
 // ---- similarity ICP for many pairs per call ------------------------------------------

@@ -65,6 +65,9 @@ struct kss_ctx {
     // generalized and symmetric ICP for many pairs: the packed source normals (staged or computed), and the
     // per-pair PairPass table: the host writes the pinned copy after every host step, one copy per pass takes it to the device table
     DevBuf pb_snrm, pb_gicp;
+    // one-to-one rejection (kss_o2o.hip): the claim table (one uint64 per target of the call, two uint32 counters per
+    // pair behind it; set to all ones before every pass, so nothing has to hold between passes) and the filtered idx / d2
+    DevBuf o2o_table, o2o_idx, o2o_d2;
     void* h_gicp = nullptr; size_t h_gicp_cap = 0;
     void* h_gicp_dev = nullptr;   // (the pinned copy as the device sees it: KSS_GICP_TABLE_MAPPED, an A/B switch)
     const PairState* last_state_dev = nullptr;   // the per-pair state table the last batched NN pass read (null: none, a single pair)
@@ -272,6 +275,8 @@ struct PairMode {
     bool sim = false;               // similarity ICP (kss_icp_sim; with trimmed and the point metric only): the step is sim_from_sums
     double scale_min = 1.0;         // with the accumulated scale kept in [scale_min, scale_max]; trace_info / last_info / info_all
     double scale_max = 1.0;         // hold KSS_SIM_NINFO doubles per record
+    bool unique = false;            // one-to-one rejection in front of the trimmed pass (kss_icp_o2o; with trimmed, not with robust, gicp,
+                                    // symm or sim): the info records hold KSS_O2O_NINFO doubles, [0] = u, [4] = m
 };
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
@@ -288,6 +293,10 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
                   const RobustScale* rscales = nullptr, const double* gicp_eps = nullptr, const int32_t* symm_aligns = nullptr);
 // the selection alone for nseg segments of d_d2 in one launch
 int trim_threshold_batch_dev(kss_ctx* c, const float* d_d2, const int64_t* off, int nseg, double max_d2, const double* overlaps, double* info_all);
+// the one-to-one filter alone (kss_o2o_filter[_batch]_dev) for nseg segments [off[i], off[i + 1]) of d_idx / d_d2, segment i
+// against nts[i] targets, in the same three launches: the filtered arrays (either may be null or its input) and {m, u} per segment
+int o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, const int64_t* off, const int64_t* nts, int nseg, double max_d2,
+                   int32_t* d_idx_out, float* d_d2_out, double* info_all);
 // host-mapped {value, sequence number} result slots: allocate them; wait for the first nslots of launch c->seq
 int ensure_pub_slots(kss_ctx* c);
 int wait_slots(kss_ctx* c, int nslots, double* out);

@@ -1878,6 +1878,10 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // rows and the final launch that keeps slot 17; the host step solves by sim_from_sums inside [scale_min, scale_max] / s_acc, keeps
 // the pair's accumulated scale s_acc and reads PCL's criteria on the step without its scale; the info record grows to
 // KSS_SIM_NINFO = {m, k, tau, kept, s_k, s_acc} (s_k = 0 where the pass made no step), the last two filled here on the host.
+// One-to-one (kss_icp_o2o; M.unique with M.trimmed, either metric): three launches ahead of the selection (kss_o2o.hip:
+// table reset, claim, resolve) filter the NN pass's idx / d2 into o2o_idx / o2o_d2, which the selection and the rows launch read in
+// their place; the info record grows to KSS_O2O_NINFO = {u, k, tau, kept, m}, m published by the resolve launch behind the
+// selection's four slots.  The NN pass's own arrays stay as written: the fitness pass and fitness_idx / fitness_d2 are unfiltered.
 // What the host does for ONE pair after a pass, the same code for a single pair (pair_loop) and inside a batch (pairs_loop): the
 // min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
 // its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
@@ -1890,7 +1894,8 @@ struct PairTrack {
     double s_acc = 1.0;   // similarity: the scale accumulated so far
     explicit PairTrack(const kss_icp_params& P) : cv(convergence_of(P)) { mat4_identity(fin); mat4_identity(tk); }
 };
-static int pair_ninfo(const PairMode& M) { return M.sim ? KSS_SIM_NINFO : KSS_TRIM_NINFO; }
+static int pair_ninfo(const PairMode& M) { return M.sim ? KSS_SIM_NINFO : M.unique ? KSS_O2O_NINFO : KSS_TRIM_NINFO; }
+static_assert(KSS_O2O_NINFO <= KSS_SIM_NINFO, "the loops' info arrays hold KSS_SIM_NINFO doubles");
 static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const double* s, double* info, PairTrack& t, PairState& hs,
                            bool trace) {
     if (M.sim) { info[4] = 0.0; info[5] = t.s_acc; }
@@ -1947,6 +1952,9 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
     TrimState* d_state = (TrimState*)c->trim_state.p;
     const double* d_cut = M.trimmed ? &d_state[TRIM_NSTATE - 1].cut : nullptr;
     float* d_keys = (float*)c->rob_keys.p;
+    // one-to-one: the selection and the rows read the filtered copies; d_idx / d_d2 stay the NN pass's own
+    const int32_t* d_idx_m = M.unique ? (const int32_t*)c->o2o_idx.p : d_idx;
+    const float* d_d2_m = M.unique ? (const float*)c->o2o_d2.p : d_d2;
     const int nb = stream_blocks(ns);
     if (P.trace_n) *P.trace_n = 0;
     const int ninfo = pair_ninfo(M);
@@ -1961,9 +1969,15 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
         {
             ProfScope ps(c, KSS_K_CORR_REDUCE);
             const hipStream_t st = c->stream;
-            const PairArgs a = {{nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, max_d2}, d_tgt, d_nrm, ns, nt, d_rows, d_keys};
+            const PairArgs a = {{nullptr, d_out, d_perm, d_idx_m, d_d2_m, M.d_src_nrm, max_d2}, d_tgt, d_nrm, ns, nt, d_rows, d_keys};
             const GicpRot Rn = rot_of(tr.fin);   // generalized, symmetric: the source normals turn with the transform accumulated so far
-            if (M.trimmed) launch_trim_select(st, d_d2, ns, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
+            if (M.unique) {   // table reset, claim, resolve: m lands behind the selection's record
+                const O2oArgs oa = {d_idx, d_d2, (const PairbDesc*)c->pb_desc.p, nullptr, nullptr, max_d2, (unsigned long long*)c->o2o_table.p,
+                                    (unsigned*)((unsigned long long*)c->o2o_table.p + nt), (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p,
+                                    d_rec + P2L_NSUMS + KSS_TRIM_NINFO};
+                if (launch_o2o(st, nb, nt, 1, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
+            }
+            if (M.trimmed) launch_trim_select(st, d_d2_m, ns, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
             if (M.robust) {
                 const TrimState* d_sel = nullptr;
                 if (M.rs.autoscale) {   // the median key: the point metric's keys are the NN pass's d2, the plane metric's are written here
@@ -2000,6 +2014,7 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
         if (M.trimmed || M.robust) {
             std::memcpy(info, hp + P2L_NSUMS, KSS_TRIM_NINFO * sizeof(double));
             if (M.trimmed) info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
+            if (M.unique) info[4] = hp[P2L_NSUMS + KSS_TRIM_NINFO];   // one-to-one: m, the candidates before the rejection ([0] is u)
         }
         const bool goes_on = pair_host_step(P, M, s, info, tr, hs[0], true);   // (similarity: fills the scale slots of info)
         if ((M.trimmed || M.robust) && M.last_info) std::memcpy(M.last_info, info, (size_t)ninfo * sizeof(double));
@@ -2011,6 +2026,8 @@ static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, con
     return fitness_pass(c, pl, P, tr.fin, &tr.iters, &tr.state, true, nullptr, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, res);
 }
 
+static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows);
+
 // (the arguments are the entry points' to check: kss_api.hip)
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                  const kss_icp_params* p, const PairMode& M, kss_icp_result* res) {
@@ -2021,6 +2038,8 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
         return set_err(c, KSS_ERR_ARG, "pair_run: generalized ICP is the plane record with both clouds' normals, neither trimmed nor robust");
     if (M.symm && (!M.plane || M.trimmed || M.gicp || !M.d_src_nrm || !d_nrm))
         return set_err(c, KSS_ERR_ARG, "pair_run: symmetric ICP is the plane record with both clouds' normals, neither trimmed nor generalized");
+    if (M.unique && (!M.trimmed || M.robust || M.gicp || M.symm || M.sim))
+        return set_err(c, KSS_ERR_ARG, "pair_run: one-to-one rejection is the trimmed pass's, neither robust, generalized, symmetric nor similarity");
     HIPCHK(c, hipSetDevice(c->device));
     IcpPlan pl;
     const auto t0 = std::chrono::steady_clock::now();
@@ -2037,7 +2056,15 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
         KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
     }
     if (M.robust && M.rs.autoscale && M.plane) KCHK(ensure(c, c->rob_keys, (size_t)ns * sizeof(float)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
+    if (M.unique) {   // the claim table, the filtered idx / d2 and the pair as the filter's kernels see it
+        KCHK(ensure(c, c->o2o_table, o2o_table_bytes(nt, 1)));
+        KCHK(ensure(c, c->o2o_idx, (size_t)ns * sizeof(int32_t)));
+        KCHK(ensure(c, c->o2o_d2, (size_t)ns * sizeof(float)));
+        PairbDesc d;
+        d.src_base = 0; d.ns = ns; d.tgt_off = 0; d.nt = nt; d.overlap = M.overlap; d.row_base = 0; d.nrows = stream_blocks(ns);
+        KCHK(stage_pairb(c, std::vector<PairbDesc>(1, d), false));
+    }
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO + 1) * sizeof(double)));
     const int64_t so[2] = {0, ns}, to[2] = {0, nt};
     KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));
     KCHK(grid_setup(c, pl));
@@ -2119,6 +2146,13 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     double* d_rec = (double*)c->h_p2l_dev;
     double* d_info = d_rec + (size_t)np * P2L_NSUMS;
     TrimState* d_ts = (TrimState*)c->trim_state.p;
+    // one-to-one: every pair's m behind the selection records; the selection and the rows read the filtered copies
+    const double* hinfo_m = hinfo + (size_t)np * KSS_TRIM_NINFO;
+    double* d_info_m = d_info + (size_t)np * KSS_TRIM_NINFO;
+    const int32_t* d_idx_m = M.unique ? (const int32_t*)c->o2o_idx.p : d_idx;
+    const float* d_d2_m = M.unique ? (const float*)c->o2o_d2.p : d_d2;
+    int64_t total_tgt = 0;
+    for (int p = 0; p < np; ++p) total_tgt += pl_in.g[p].nt;
     const PairbDesc* d_desc = (const PairbDesc*)c->pb_desc.p;
     const RobustScale* d_rs = (const RobustScale*)c->pb_rscale.p;   // (robust)
     const int32_t* d_row_pair = (const int32_t*)c->pb_rowpair.p;
@@ -2145,7 +2179,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
         {
             ProfScope ps(c, KSS_K_CORR_REDUCE);
             const hipStream_t st = c->stream;
-            const PairbArgs a = {{nullptr, d_out, d_perm, d_idx, d_d2, M.d_src_nrm, max_d2}, d_tgt, d_nrm, d_desc, d_row_pair, d_state, d_rs, d_ts,
+            const PairbArgs a = {{nullptr, d_out, d_perm, d_idx_m, d_d2_m, M.d_src_nrm, max_d2}, d_tgt, d_nrm, d_desc, d_row_pair, d_state, d_rs, d_ts,
                                  d_pass, (double*)c->p2l_rows.p, (float*)c->rob_keys.p};
             // the pass table as the host steps left it: the last pass's synchronisation has ordered those writes behind its copy
             if (hpass && !pass_mapped) HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hpass, (size_t)np * sizeof(PairPass), hipMemcpyHostToDevice, st));
@@ -2161,7 +2195,13 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                 else launch_pairb_rows<PointRobustMetric<PAIR_ROBUST>>(st, total_rows, a);
                 launch_pairb_robust_final(st, M.plane, np, a, d_rec, d_info);
             } else {
-                if (M.trimmed) launch_pairb_select(st, d_d2, d_desc, np, d_state, max_d2, d_ts, d_info);
+                if (M.unique) {   // table reset, claim, resolve for the whole batch
+                    const O2oArgs oa = {d_idx, d_d2, d_desc, d_row_pair, d_state, max_d2, (unsigned long long*)c->o2o_table.p,
+                                        (unsigned*)((unsigned long long*)c->o2o_table.p + total_tgt), (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p,
+                                        d_info_m};
+                    if (launch_o2o(st, total_rows, total_tgt, np, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
+                }
+                if (M.trimmed) launch_pairb_select(st, d_d2_m, d_desc, np, d_state, max_d2, d_ts, d_info);
                 if (M.gicp) launch_pairb_rows<GicpMetric>(st, total_rows, a);
                 else if (M.symm) launch_pairb_rows<SymmMetric<PAIR_PLAIN>>(st, total_rows, a);
                 else if (M.sim) launch_pairb_rows<SimMetric>(st, total_rows, a);
@@ -2189,6 +2229,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                 if (M.trimmed || M.robust) {
                     std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, KSS_TRIM_NINFO * sizeof(double));
                     if (M.trimmed) info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
+                    if (M.unique) info[4] = hinfo_m[p];   // one-to-one: m, the candidates before the rejection ([0] is u)
                 }
                 const bool goes_on = pair_host_step(P, M, s, info, tr[p], hs[p], p == 0);   // (similarity: fills the scale slots of info)
                 if ((M.trimmed || M.robust) && info_all) std::memcpy(info_all + (size_t)p * ninfo, info, (size_t)ninfo * sizeof(double));
@@ -2256,6 +2297,8 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         return set_err(c, KSS_ERR_ARG, "pairs_run: generalized ICP is the plane record with both clouds' normals and the per-pair epsilons, neither trimmed nor robust");
     if (M.symm && (!M.plane || M.trimmed || M.gicp || !M.d_src_nrm || !d_nrm || !symm_aligns))
         return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP is the plane record with both clouds' normals and the per-pair aligns, neither trimmed nor generalized; robust symmetric ICP adds the per-pair scales");
+    if (M.unique && (!M.trimmed || M.robust || M.gicp || M.symm || M.sim))
+        return set_err(c, KSS_ERR_ARG, "pairs_run: one-to-one rejection is the trimmed pass's, neither robust, generalized, symmetric nor similarity");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> ns(npairs), nt(npairs);
     for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }
@@ -2302,7 +2345,13 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
             else hpass[i].align = symm_aligns[i];
         }
     }
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
+    if (M.unique) {   // one claim table over the batch's targets (pair p's slots at tgt_off[p], counted from 0), the filtered idx / d2
+        if (tgt_off[0] != 0) return set_err(c, KSS_ERR_ARG, "pairs_run: the target offsets must start at 0");
+        KCHK(ensure(c, c->o2o_table, o2o_table_bytes(tgt_off[npairs], npairs)));
+        KCHK(ensure(c, c->o2o_idx, (size_t)pl.total_src * sizeof(int32_t)));
+        KCHK(ensure(c, c->o2o_d2, (size_t)pl.total_src * sizeof(float)));
+    }
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO + 1) * sizeof(double)));
     KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));
     KCHK(grid_setup(c, pl));
     KCHK(grid_setup_batch(c, pl));
@@ -2338,6 +2387,35 @@ int trim_threshold_batch_dev(kss_ctx* c, const float* d_d2, const int64_t* off, 
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::memcpy(info_all, c->h_p2l, (size_t)nseg * KSS_TRIM_NINFO * sizeof(double));
+    return KSS_OK;
+}
+
+// the one-to-one filter alone (kss_o2o_filter[_batch]_dev): the loops' three launches over nseg segments, then both counters of
+// every segment read back (each holds its count minus one)
+int o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, const int64_t* off, const int64_t* nts, int nseg, double max_d2,
+                   int32_t* d_idx_out, float* d_d2_out, double* info_all) {
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<PairbDesc> desc((size_t)nseg);
+    int64_t total_rows = 0, total_tgt = 0;
+    for (int i = 0; i < nseg; ++i) {
+        PairbDesc& d = desc[i];
+        d.src_base = off[i]; d.ns = off[i + 1] - off[i];
+        d.tgt_off = total_tgt; d.nt = nts[i]; d.overlap = 1.0;
+        d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(d.ns);
+        total_rows += d.nrows; total_tgt += d.nt;
+        if (total_rows > 0x7fff0000ll || total_tgt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "o2o_filter: batch too large for 32-bit indexing");
+    }
+    KCHK(stage_pairb(c, desc, true));
+    KCHK(ensure(c, c->o2o_table, o2o_table_bytes(total_tgt, nseg)));
+    unsigned* d_counters = (unsigned*)((unsigned long long*)c->o2o_table.p + total_tgt);
+    const O2oArgs oa = {d_idx, d_d2, (const PairbDesc*)c->pb_desc.p, (const int32_t*)c->pb_rowpair.p, nullptr, max_d2,
+                        (unsigned long long*)c->o2o_table.p, d_counters, d_idx_out, d_d2_out, nullptr};
+    if (launch_o2o(c->stream, (int)total_rows, total_tgt, nseg, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
+    HIPCHK(c, hipGetLastError());
+    std::vector<unsigned> cnt((size_t)nseg * 2);
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), d_counters, cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t q = 0; q < cnt.size(); ++q) info_all[q] = (double)(cnt[q] + 1u);
     return KSS_OK;
 }
 

@@ -451,6 +451,25 @@ void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs&
 // ... and the weighted one, with {m, c2, sum of weights, cnt} into d_info[pair * KSS_ROBUST_NINFO]
 void launch_pairb_robust_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out, double* d_info);
 
+// ---- one-to-one rejection (kss_o2o.hip) ----
+// The filter's arguments, by value: idx / d2 the NN pass's, batch-wide by original source index (a pair's at desc[p].src_base, its
+// idx counting inside its own target); desc / row_pair / state as in PairbArgs (row_pair null: the one pair desc[0]; state null:
+// every pair is active); table: one uint64 per target of the batch, pair p's at desc[p].tgt_off; counters: two uint32 per pair
+// behind the table ({m, u}, each MINUS ONE: they start at all ones with the table); idx_out / d2_out: the filtered arrays, laid out
+// like idx / d2 (either may be null, either may be its input); info_m: one double per pair, m as the resolve launch publishes it
+// (device or host-mapped, may be null).
+struct O2oArgs {
+    const int32_t* idx; const float* d2;
+    const PairbDesc* desc; const int32_t* row_pair; const PairState* state;
+    double max_d2;
+    unsigned long long* table; unsigned* counters;
+    int32_t* idx_out; float* d2_out;
+    double* info_m;
+};
+size_t o2o_table_bytes(int64_t total_tgt, int npairs);
+// table reset, claim, resolve: three launches for total_rows = the sum of the pairs' nrows workgroups.  0, or the hipError_t of the reset.
+int launch_o2o(hipStream_t st, int total_rows, int64_t total_tgt, int npairs, const O2oArgs& a);
+
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,
                 const std::function<void*(size_t)>& scratch);
