@@ -4,12 +4,10 @@
 #pragma clang fp contract(off)
 
 #include <cmath>
-#include <limits>
 
 #include "kss_ctx.hpp"
 #include "kss_gicp.hpp"
 #include "kss_robust.hpp"
-#include "kss_pair_device.hpp"
 
 extern "C" {
 
@@ -431,18 +429,9 @@ int kss_p2l_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const f
     if (!c || !d_src || !d_tgt || !d_nrm || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "p2l_sums: null argument");
     if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "p2l_sums: empty input");
     HIPCHK(c, hipSetDevice(c->device));
-    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
-    {
-        ProfScope ps(c, KSS_K_CORR_REDUCE);
-        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, nullptr, max_d2}, d_tgt, d_nrm, n, nt, (double*)c->p2l_rows.p, nullptr};
-        launch_pair_rows(c->stream, a, PlaneMetric<false>(max_d2, nullptr));
-        launch_p2l_final(c->stream, a.rows, p2l_rows_blocks(n), (double*)c->h_p2l_dev);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(sums, c->h_p2l, KSS_P2L_NSUMS * sizeof(double));
-    return KSS_OK;
+    PairMode mode;
+    mode.plane = true;
+    return pair_record_dev(c, d_src, d_tgt, d_nrm, d_idx, n, nt, max_d2, mode, nullptr, sums, nullptr);
 }
 
 int kss_p2l_sums(kss_ctx* c, const float* src, const float* tgt, const float* nrm, const int32_t* idx, int64_t n, int64_t nt,
@@ -621,18 +610,9 @@ int kss_sim_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const i
     if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "sim_sums: empty input");
     if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "sim_sums: cloud too large");
     HIPCHK(c, hipSetDevice(c->device));
-    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
-    {
-        ProfScope ps(c, KSS_K_CORR_REDUCE);
-        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, nullptr, max_d2}, d_tgt, nullptr, n, nt, (double*)c->p2l_rows.p, nullptr};
-        launch_pair_rows(c->stream, a, SimMetric(max_d2, nullptr));
-        launch_sim_final(c->stream, a.rows, p2l_rows_blocks(n), (double*)c->h_p2l_dev);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(sums, c->h_p2l, KSS_NSUMS * sizeof(double));
-    return KSS_OK;
+    PairMode mode;   // (no trimming: the record of every correspondence within max_d2, no selection)
+    mode.sim = true;
+    return pair_record_dev(c, d_src, d_tgt, nullptr, d_idx, n, nt, max_d2, mode, nullptr, sums, nullptr);
 }
 
 int kss_sim_sums(kss_ctx* c, const float* src, const float* tgt, const int32_t* idx, int64_t n, int64_t nt, double max_d2,
@@ -759,38 +739,11 @@ int kss_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, cons
     if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "robust_sums: empty input");
     if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "robust_sums: cloud too large");
     HIPCHK(c, hipSetDevice(c->device));
-    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_ROBUST_NINFO) * sizeof(double)));
-    const TrimState* d_sel = nullptr;
-    if (rs.autoscale) {
-        KCHK(ensure(c, c->rob_keys, (size_t)n * sizeof(float)));
-        KCHK(ensure(c, c->trim_rows, trim_rows_bytes(n)));
-        KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
-        d_sel = (const TrimState*)c->trim_state.p + (TRIM_NSTATE - 1);
-    }
-    {
-        ProfScope ps(c, KSS_K_CORR_REDUCE);
-        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, nullptr, max_d2}, d_tgt, d_nrm, n, nt, (double*)c->p2l_rows.p, (float*)c->rob_keys.p};
-        if (rs.autoscale) {
-            // the keys carry the whole candidate test (a NaN is none); the point metric's bound is applied again, to the same effect
-            if (plane) launch_pair_rows(c->stream, a, PlaneRobustMetric<PAIR_KEY>());
-            else launch_pair_rows(c->stream, a, PointRobustMetric<PAIR_KEY>());
-            launch_trim_select(c->stream, (const float*)c->rob_keys.p, n, plane ? std::numeric_limits<double>::infinity() : max_d2, 0.5,
-                               (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p, nullptr);
-        }
-        if (plane) {
-            launch_pair_rows(c->stream, a, PlaneRobustMetric<PAIR_ROBUST>(rs, d_sel));
-            launch_robust_plane_final(c->stream, a.rows, p2l_rows_blocks(n), rs, d_sel, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
-        } else {
-            launch_pair_rows(c->stream, a, PointRobustMetric<PAIR_ROBUST>(rs, d_sel));
-            launch_robust_point_final(c->stream, a.rows, p2l_rows_blocks(n), rs, d_sel, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
-        }
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(sums, c->h_p2l, (size_t)(plane ? KSS_P2L_NSUMS : KSS_NSUMS) * sizeof(double));
-    std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_ROBUST_NINFO * sizeof(double));
-    return KSS_OK;
+    PairMode mode;   // (the point metric's keys are written here and carry the whole candidate test; the bound is applied again, to the same effect)
+    mode.plane = plane;
+    mode.robust = true;
+    mode.rs = rs;
+    return pair_record_dev(c, d_src, d_tgt, d_nrm, d_idx, n, nt, max_d2, mode, nullptr, sums, info);
 }
 
 int kss_robust_sums(kss_ctx* c, const float* src, const float* tgt, const float* nrm, const int32_t* idx, int64_t n, int64_t nt,
@@ -888,18 +841,12 @@ int kss_gicp_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals
     if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "gicp_sums: cloud too large");
     HIPCHK(c, hipSetDevice(c->device));
     KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, gp->normals_k));
-    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
-    {
-        ProfScope ps(c, KSS_K_CORR_REDUCE);
-        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, max_d2}, d_tgt, d_tgt_normals, n, nt, (double*)c->p2l_rows.p, nullptr};
-        launch_pair_rows(c->stream, a, GicpMetric(gicp_rot_of(Rn), 1.0 - gp->epsilon));
-        launch_p2l_final(c->stream, a.rows, p2l_rows_blocks(n), (double*)c->h_p2l_dev);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(sums, c->h_p2l, KSS_P2L_NSUMS * sizeof(double));
-    return KSS_OK;
+    PairMode mode;
+    mode.plane = true;
+    mode.gicp = true;
+    mode.gicp_epsilon = gp->epsilon;
+    mode.d_src_nrm = d_src_normals;
+    return pair_record_dev(c, d_src, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, mode, Rn, sums, nullptr);
 }
 
 int kss_gicp_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals, const int32_t* idx,
@@ -989,18 +936,12 @@ int kss_symm_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals
     if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_sums: cloud too large");
     HIPCHK(c, hipSetDevice(c->device));
     KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
-    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, P2L_NSUMS * sizeof(double)));
-    {
-        ProfScope ps(c, KSS_K_CORR_REDUCE);
-        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, max_d2}, d_tgt, d_tgt_normals, n, nt, (double*)c->p2l_rows.p, nullptr};
-        launch_pair_rows(c->stream, a, SymmMetric<PAIR_PLAIN>(gicp_rot_of(Rn), sp->align_normals));
-        launch_p2l_final(c->stream, a.rows, p2l_rows_blocks(n), (double*)c->h_p2l_dev);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(sums, c->h_p2l, KSS_P2L_NSUMS * sizeof(double));
-    return KSS_OK;
+    PairMode mode;
+    mode.plane = true;
+    mode.symm = true;
+    mode.symm_align = sp->align_normals;
+    mode.d_src_nrm = d_src_normals;
+    return pair_record_dev(c, d_src, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, mode, Rn, sums, nullptr);
 }
 
 int kss_symm_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals, const int32_t* idx,
@@ -1073,32 +1014,14 @@ int kss_symm_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_
     const RobustScale rs = robust_scale_of(rp);
     HIPCHK(c, hipSetDevice(c->device));
     KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
-    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_ROBUST_NINFO) * sizeof(double)));
-    const TrimState* d_sel = nullptr;
-    if (rs.autoscale) {
-        KCHK(ensure(c, c->rob_keys, (size_t)n * sizeof(float)));
-        KCHK(ensure(c, c->trim_rows, trim_rows_bytes(n)));
-        KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
-        d_sel = (const TrimState*)c->trim_state.p + (TRIM_NSTATE - 1);
-    }
-    {
-        ProfScope ps(c, KSS_K_CORR_REDUCE);
-        const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, d_src_normals, max_d2}, d_tgt, d_tgt_normals, n, nt, (double*)c->p2l_rows.p,
-                            (float*)c->rob_keys.p};
-        if (rs.autoscale) {   // the keys carry the whole candidate test (a NaN is none)
-            launch_pair_rows(c->stream, a, SymmMetric<PAIR_KEY>(gicp_rot_of(Rn), sp->align_normals));
-            launch_trim_select(c->stream, (const float*)c->rob_keys.p, n, std::numeric_limits<double>::infinity(), 0.5,
-                               (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p, nullptr);
-        }
-        launch_pair_rows(c->stream, a, SymmMetric<PAIR_ROBUST>(gicp_rot_of(Rn), sp->align_normals, rs, d_sel));
-        launch_robust_plane_final(c->stream, a.rows, p2l_rows_blocks(n), rs, d_sel, (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS);
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(sums, c->h_p2l, KSS_P2L_NSUMS * sizeof(double));
-    std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_ROBUST_NINFO * sizeof(double));
-    return KSS_OK;
+    PairMode mode;
+    mode.plane = true;
+    mode.symm = true;
+    mode.symm_align = sp->align_normals;
+    mode.d_src_nrm = d_src_normals;
+    mode.robust = true;
+    mode.rs = rs;
+    return pair_record_dev(c, d_src, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, mode, Rn, sums, info);
 }
 
 int kss_symm_robust_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals,

@@ -281,6 +281,10 @@ struct PairMode {
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                  const kss_icp_params* p, const PairMode& mode, kss_icp_result* res);
+// one pass of that loop over given correspondences d_idx (the *_sums_dev entry points): the launches of the mode (sim alone: the
+// untrimmed similarity record) into sums and, robust, info; Rn: the row-major 3 x 3 the source normals turn with (null: identity)
+int pair_record_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n, int64_t nt,
+                    double max_d2, const PairMode& mode, const float* Rn, double* sums, double* info);
 int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info);
 // npairs >= 1 pairs in lockstep (kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch, kss_icp_gicp_batch,
 // kss_icp_symm_batch, kss_icp_symm_robust_batch -- symm with robust takes both symm_aligns and rscales): d_nrm laid

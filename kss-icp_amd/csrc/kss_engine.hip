@@ -3,7 +3,8 @@
 // pass (fused cell-list launch, batched cell lists, or sweep + reduce + finalize) and the ICP loop around it.
 // Host code only orchestrates: per iteration it launches the pass, takes 20 doubles per pair back, solves the 3x3 SVD
 // (kss_host_math.hpp) and evaluates the PCL convergence criteria.  There is no CPU compute fallback in this file.
-// Point-to-plane and trimmed ICP run pair_loop (one pair) or pairs_loop (many pairs in lockstep, kss_pairb.hip) on the same host step.
+// The pair metrics (point-to-plane, trimmed, robust, generalized, symmetric, similarity, one-to-one) run pairs_loop, one pair or many in
+// lockstep; what a pass launches for a mode is said once per kernel family: pair_pass_launch (kss_pair.hip), pairb_pass_launch (kss_pairb.hip).
 #pragma clang fp contract(off)
 
 #include <emmintrin.h>
@@ -1882,7 +1883,7 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // table reset, claim, resolve) filter the NN pass's idx / d2 into o2o_idx / o2o_d2, which the selection and the rows launch read in
 // their place; the info record grows to KSS_O2O_NINFO = {u, k, tau, kept, m}, m published by the resolve launch behind the
 // selection's four slots.  The NN pass's own arrays stay as written: the fitness pass and fitness_idx / fitness_d2 are unfiltered.
-// What the host does for ONE pair after a pass, the same code for a single pair (pair_loop) and inside a batch (pairs_loop): the
+// What the host does for ONE pair after a pass, a single pair's and every pair's of a batch (pairs_loop): the
 // min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
 // its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
 // ended (state / converged say how) and hs is left as it was.  trace: the pair whose passes the caller's trace receives.
@@ -1934,195 +1935,163 @@ static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const dou
 // the rotation block of a row-major 4 x 4 (the float bits of the accumulated Matrix4f)
 static GicpRot rot_of(const float* F) { return GicpRot{{F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]}}; }
 
-static int pair_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
-                     const int32_t* d_perm, kss_icp_result* res) {
-    const int64_t ns = pl.g[0].ns, nt = pl.g[0].nt;
-    const int ncol = M.plane ? P2L_NSUMS : NSUMS;
-    PairTrack tr(P);
-    float I[16];
-    mat4_identity(I);
-    PairState* hs = (PairState*)c->h_state;
-    set_state(hs[0], I, 1, 0);
-    const double max_d2 = P.max_corr_dist * P.max_corr_dist;
-    int32_t* d_idx = (int32_t*)c->p2l_idx.p;
-    float* d_d2 = (float*)c->p2l_d2.p;
-    double* d_rows = (double*)c->p2l_rows.p;
-    const double* hp = (const double*)c->h_p2l;
-    double* d_rec = (double*)c->h_p2l_dev;
-    TrimState* d_state = (TrimState*)c->trim_state.p;
-    const double* d_cut = M.trimmed ? &d_state[TRIM_NSTATE - 1].cut : nullptr;
-    float* d_keys = (float*)c->rob_keys.p;
-    // one-to-one (DESIGN.md 2.23): the selection and the rows read the filtered copies; d_idx / d_d2 stay the NN pass's own
-    const int32_t* d_idx_m = M.unique ? (const int32_t*)c->o2o_idx.p : d_idx;
-    const float* d_d2_m = M.unique ? (const float*)c->o2o_d2.p : d_d2;
-    const int nb = stream_blocks(ns);
-    if (P.trace_n) *P.trace_n = 0;
-    const int ninfo = pair_ninfo(M);
-    if (M.last_info) for (int q = 0; q < ninfo; ++q) M.last_info[q] = 0.0;
-    int it = 0;
-    GatedGuard gated_guard(c);
-    c->gated.want_next = false;
-    while (P.max_iterations > 0) {
-        const float4* d_in = it == 0 ? (const float4*)c->src0.p : (const float4*)c->cur[(it - 1) & 1].p;
-        float4* d_out = (float4*)c->cur[it & 1].p;
-        KCHK(nn_pass(c, pl, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false));
-        {
-            ProfScope ps(c, KSS_K_CORR_REDUCE);
-            const hipStream_t st = c->stream;
-            const PairArgs a = {{nullptr, d_out, d_perm, d_idx_m, d_d2_m, M.d_src_nrm, max_d2}, d_tgt, d_nrm, ns, nt, d_rows, d_keys};
-            const GicpRot Rn = rot_of(tr.fin);   // generalized, symmetric: the source normals turn with the transform accumulated so far
-            if (M.unique) {   // table reset, claim, resolve: m lands behind the selection's record
-                const O2oArgs oa = {d_idx, d_d2, (const PairbDesc*)c->pb_desc.p, nullptr, nullptr, max_d2, (unsigned long long*)c->o2o_table.p,
-                                    (unsigned*)((unsigned long long*)c->o2o_table.p + nt), (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p,
-                                    d_rec + P2L_NSUMS + KSS_TRIM_NINFO};
-                if (launch_o2o(st, nb, nt, 1, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
-            }
-            if (M.trimmed) launch_trim_select(st, d_d2_m, ns, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_rec + P2L_NSUMS);
-            if (M.robust) {
-                const TrimState* d_sel = nullptr;
-                if (M.rs.autoscale) {   // the median key: the point metric's keys are the NN pass's d2, the plane metric's are written here
-                    if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_KEY>(Rn, M.symm_align));
-                    else if (M.plane) launch_pair_rows(st, a, PlaneRobustMetric<PAIR_KEY>());
-                    launch_trim_select(st, M.plane ? d_keys : d_d2, ns, M.plane ? std::numeric_limits<double>::infinity() : max_d2, 0.5,
-                                       (unsigned*)c->trim_rows.p, d_state, nullptr);
-                    d_sel = d_state + (TRIM_NSTATE - 1);
-                }
-                if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_ROBUST>(Rn, M.symm_align, M.rs, d_sel));
-                else if (M.plane) launch_pair_rows(st, a, PlaneRobustMetric<PAIR_ROBUST>(M.rs, d_sel));
-                else launch_pair_rows(st, a, PointRobustMetric<PAIR_ROBUST>(M.rs, d_sel));
-                if (M.plane) launch_robust_plane_final(st, d_rows, nb, M.rs, d_sel, d_rec, d_rec + P2L_NSUMS);
-                else launch_robust_point_final(st, d_rows, nb, M.rs, d_sel, d_rec, d_rec + P2L_NSUMS);
-            } else if (M.plane) {
-                if (M.gicp) launch_pair_rows(st, a, GicpMetric(Rn, 1.0 - M.gicp_epsilon));
-                else if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_PLAIN>(Rn, M.symm_align));
-                else if (M.trimmed) launch_pair_rows(st, a, PlaneMetric<true>(max_d2, d_cut));
-                else launch_pair_rows(st, a, PlaneMetric<false>(max_d2, nullptr));
-                launch_p2l_final(st, d_rows, nb, d_rec);
-            } else if (M.sim) {
-                launch_pair_rows(st, a, SimMetric(max_d2, d_cut));
-                launch_sim_final(st, d_rows, nb, d_rec);
-            } else {
-                launch_pair_rows(st, a, PointTrimMetric(d_cut));
-                launch_trim_point_final(st, d_rows, nb, d_rec);
-            }
-        }
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        ++it;
-        double s[P2L_NSUMS], info[KSS_SIM_NINFO] = {};
-        std::memcpy(s, hp, (size_t)ncol * sizeof(double));
-        if (M.trimmed || M.robust) {
-            std::memcpy(info, hp + P2L_NSUMS, KSS_TRIM_NINFO * sizeof(double));
-            if (M.trimmed) info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
-            if (M.unique) info[4] = hp[P2L_NSUMS + KSS_TRIM_NINFO];   // one-to-one: m, the candidates before the rejection ([0] is u)
-        }
-        const bool goes_on = pair_host_step(P, M, s, info, tr, hs[0], true);   // (similarity: fills the scale slots of info)
-        if ((M.trimmed || M.robust) && M.last_info) std::memcpy(M.last_info, info, (size_t)ninfo * sizeof(double));
-        if (!goes_on) break;
-    }
-    fill_result(*res, tr.fin, tr.iters, tr.converged, tr.state, tr.last_mse, 0.0, 0);
-    if (!P.compute_fitness) return KSS_OK;
-    const bool corr = P.fitness_idx || P.fitness_d2;
-    return fitness_pass(c, pl, P, tr.fin, &tr.iters, &tr.state, true, nullptr, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, res);
-}
-
-static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows);
-
-// (the arguments are the entry points' to check: kss_api.hip)
-int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
-                 const kss_icp_params* p, const PairMode& M, kss_icp_result* res) {
-    if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: the untrimmed point metric is kss_icp's");
-    if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pair_run: trimmed and robust exclude each other");
-    if (M.sim && (M.plane || !M.trimmed)) return set_err(c, KSS_ERR_ARG, "pair_run: similarity ICP is the trimmed point metric's");
-    if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm))
-        return set_err(c, KSS_ERR_ARG, "pair_run: generalized ICP is the plane record with both clouds' normals, neither trimmed nor robust");
-    if (M.symm && (!M.plane || M.trimmed || M.gicp || !M.d_src_nrm || !d_nrm))
-        return set_err(c, KSS_ERR_ARG, "pair_run: symmetric ICP is the plane record with both clouds' normals, neither trimmed nor generalized");
-    if (M.unique && (!M.trimmed || M.robust || M.gicp || M.symm || M.sim))
-        return set_err(c, KSS_ERR_ARG, "pair_run: one-to-one rejection is the trimmed pass's, neither robust, generalized, symmetric nor similarity");
-    HIPCHK(c, hipSetDevice(c->device));
-    IcpPlan pl;
-    const auto t0 = std::chrono::steady_clock::now();
-    KCHK(restore_zero_at_rest(c));
-    DirtyGuard guard(c);
-    c->timing = false;
-    KCHK(build_plan(c, &ns, &nt, 1, false, p->nn_sources_per_thread, p->nn_target_splits, p->nn_mode, pl));
-    KCHK(stage_plan(c, pl));
-    KCHK(ensure(c, c->p2l_idx, (size_t)ns * sizeof(int32_t)));
-    KCHK(ensure(c, c->p2l_d2, (size_t)ns * sizeof(float)));
-    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(ns) * P2L_NSUMS * sizeof(double)));
+// ---- what a pass launches behind its correspondences, by PairMode.  pair_pass_launch (kss_pair.hip's kernels,
+// one pair) and pairb_pass_launch (kss_pairb.hip's, npairs >= 1) are the only places that turn a mode into launches: a new metric
+// adds one line to each. ----
+// the buffers pair_pass_launch uses for n sources; have_d2: its PairArgs will carry the NN pass's d2
+static int pair_pass_ensure(kss_ctx* c, const PairMode& M, int64_t n, bool have_d2) {
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
     if (M.trimmed || (M.robust && M.rs.autoscale)) {
-        KCHK(ensure(c, c->trim_rows, trim_rows_bytes(ns)));
+        KCHK(ensure(c, c->trim_rows, trim_rows_bytes(n)));
         KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
     }
-    if (M.robust && M.rs.autoscale && M.plane) KCHK(ensure(c, c->rob_keys, (size_t)ns * sizeof(float)));
-    if (M.unique) {   // the claim table, the filtered idx / d2 and the pair as the filter's kernels see it
-        KCHK(ensure(c, c->o2o_table, o2o_table_bytes(nt, 1)));
-        KCHK(ensure(c, c->o2o_idx, (size_t)ns * sizeof(int32_t)));
-        KCHK(ensure(c, c->o2o_d2, (size_t)ns * sizeof(float)));
-        PairbDesc d;
-        d.src_base = 0; d.ns = ns; d.tgt_off = 0; d.nt = nt; d.overlap = M.overlap; d.row_base = 0; d.nrows = stream_blocks(ns);
-        KCHK(stage_pairb(c, std::vector<PairbDesc>(1, d), false));
-    }
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO + 1) * sizeof(double)));
-    const int64_t so[2] = {0, ns}, to[2] = {0, nt};
-    KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));
-    KCHK(grid_setup(c, pl));
-    const int32_t* d_perm = nullptr;
-    if (pl.src_in_cell_order) {   // the cell-list setup re-ordered the sources (original index in .w): where each one went
-        KCHK(ensure(c, c->p2l_perm, (size_t)ns * sizeof(int32_t)));
-        launch_p2l_perm(c->stream, (const float4*)c->src0.p + pl.g[0].src_base, ns, (int32_t*)c->p2l_perm.p);
-        HIPCHK(c, hipGetLastError());
-        d_perm = (const int32_t*)c->p2l_perm.p;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    const int rc = pair_loop(c, pl, *p, M, d_tgt, d_nrm, d_perm, res);
-    guard.ok = rc == KSS_OK;
-    const auto t2 = std::chrono::steady_clock::now();
-    c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    return rc;
+    if (M.robust && M.rs.autoscale && (M.plane || !have_d2)) KCHK(ensure(c, c->rob_keys, (size_t)n * sizeof(float)));
+    return ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO + 1) * sizeof(double));
 }
 
-// tau / m / k / kept of n squared distances on the device (kss_trim_threshold_dev)
-int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info) {
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(ensure(c, c->trim_rows, trim_rows_bytes(n)));
-    KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
-    launch_trim_select(c->stream, d_d2, n, max_d2, overlap, (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p,
-                       (double*)c->h_p2l_dev + P2L_NSUMS);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_TRIM_NINFO * sizeof(double));
+// One pair: [one-to-one's three launches] [selection] [keys launch + the 0.5 selection] rows launch, final launch.  Rn: the
+// rotation the source normals turn with (generalized, symmetric); d_rec: the record, d_info: the selection's or the weights' four
+// slots, the one-to-one's m behind them (device or host-mapped).  One-to-one filters the context's p2l_idx / p2l_d2 (the NN
+// pass's own) into o2o_idx / o2o_d2, which a.s.idx / a.s.d2 then are.  The automatic scale's median key: the plane metrics write
+// their keys; a point-metric pass that carries d2 selects on it, one without d2 writes its keys first.
+static int pair_pass_launch(kss_ctx* c, const PairArgs& a, const PairMode& M, const GicpRot& Rn, double* d_rec, double* d_info) {
+    ProfScope ps(c, KSS_K_CORR_REDUCE);
+    const hipStream_t st = c->stream;
+    const double max_d2 = a.s.max_d2;
+    const int nb = stream_blocks(a.n);
+    TrimState* d_state = (TrimState*)c->trim_state.p;
+    if (M.unique) {   // table reset, claim, resolve: m lands behind the selection's record
+        const O2oArgs oa = {(const int32_t*)c->p2l_idx.p, (const float*)c->p2l_d2.p, (const PairbDesc*)c->pb_desc.p, nullptr, nullptr, max_d2,
+                            (unsigned long long*)c->o2o_table.p, (unsigned*)((unsigned long long*)c->o2o_table.p + a.nt),
+                            (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + KSS_TRIM_NINFO};
+        if (launch_o2o(st, nb, a.nt, 1, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
+    }
+    if (M.trimmed) launch_trim_select(st, a.s.d2, a.n, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_info);
+    const double* d_cut = M.trimmed ? &d_state[TRIM_NSTATE - 1].cut : nullptr;
+    if (M.robust) {
+        const TrimState* d_sel = nullptr;
+        if (M.rs.autoscale) {   // (written keys carry the whole candidate test, a NaN is none: no bound; d2 takes the pass's)
+            const float* d_keys = a.keys;
+            if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_KEY>(Rn, M.symm_align));
+            else if (M.plane) launch_pair_rows(st, a, PlaneRobustMetric<PAIR_KEY>());
+            else if (a.s.d2) d_keys = a.s.d2;
+            else launch_pair_rows(st, a, PointRobustMetric<PAIR_KEY>());
+            launch_trim_select(st, d_keys, a.n, M.plane ? std::numeric_limits<double>::infinity() : max_d2, 0.5, (unsigned*)c->trim_rows.p,
+                               d_state, nullptr);
+            d_sel = d_state + (TRIM_NSTATE - 1);
+        }
+        if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_ROBUST>(Rn, M.symm_align, M.rs, d_sel));
+        else if (M.plane) launch_pair_rows(st, a, PlaneRobustMetric<PAIR_ROBUST>(M.rs, d_sel));
+        else launch_pair_rows(st, a, PointRobustMetric<PAIR_ROBUST>(M.rs, d_sel));
+        if (M.plane) launch_robust_plane_final(st, a.rows, nb, M.rs, d_sel, d_rec, d_info);
+        else launch_robust_point_final(st, a.rows, nb, M.rs, d_sel, d_rec, d_info);
+    } else if (M.plane) {
+        if (M.gicp) launch_pair_rows(st, a, GicpMetric(Rn, 1.0 - M.gicp_epsilon));
+        else if (M.symm) launch_pair_rows(st, a, SymmMetric<PAIR_PLAIN>(Rn, M.symm_align));
+        else if (M.trimmed) launch_pair_rows(st, a, PlaneMetric<true>(max_d2, d_cut));
+        else launch_pair_rows(st, a, PlaneMetric<false>(max_d2, nullptr));
+        launch_p2l_final(st, a.rows, nb, d_rec);
+    } else if (M.sim) {
+        launch_pair_rows(st, a, SimMetric(max_d2, d_cut));
+        launch_sim_final(st, a.rows, nb, d_rec);
+    } else {
+        launch_pair_rows(st, a, PointTrimMetric(d_cut));
+        launch_trim_point_final(st, a.rows, nb, d_rec);
+    }
     return KSS_OK;
 }
 
-// ---- the same metrics for MANY pairs per call: kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch
-// (2.13: behind the NN pass the key launch (plane) and the selection when any pair has the automatic scale, then two sums launches),
-// kss_icp_gicp_batch (2.15: one copy of the per-pair pass table -- the rotation of every pair's fin and its e -- then two sums launches),
-// kss_icp_symm_batch (2.18: the same, the table's entry carrying the pair's align_normals),
-// kss_icp_symm_robust_batch (2.20: that table's copy, then the robust form's launches on the symmetric body) ----
-// pair_loop in lockstep over npairs >= 1 pairs.  Per pass: ONE NN pass over the pairs still active (idx / d2 by global source
-// index), ONE selection launch when trimmed, TWO sums launches (kss_pairb.hip), ONE stream synchronisation, then
-// pair_host_step for every active pair (the host pool from 64 pairs up, each pair on exactly one thread).  A pair that ends
-// goes inactive in the per-pair state table; the workgroups of the later passes' launches leave at once for it and its rows
-// of the host-mapped tables are not written again: no ending touches another pair's record.  icp_loop's engine switch applies.
+// npairs >= 1 pairs, the same order of launches over the per-pair tables of a: d_rec: np records of P2L_NSUMS doubles, d_info: np
+// info records of four slots, the one-to-one's np m's behind them.  rob_select: some pair takes its scale from the pass's median
+// key (the point metric's keys are the NN pass's d2).  A pass table on the device is first copied from the pinned one as the host
+// steps left it: the last pass's synchronisation has ordered those writes behind its copy.
+static int pairb_pass_launch(kss_ctx* c, const PairbArgs& a, const PairMode& M, int np, int total_rows, int64_t total_tgt, bool rob_select,
+                             double* d_rec, double* d_info) {
+    ProfScope ps(c, KSS_K_CORR_REDUCE);
+    const hipStream_t st = c->stream;
+    const double max_d2 = a.s.max_d2;
+    if (a.pass && a.pass == (const PairPass*)c->pb_gicp.p)
+        HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, c->h_gicp, (size_t)np * sizeof(PairPass), hipMemcpyHostToDevice, st));
+    if (M.unique) {   // table reset, claim, resolve for the whole batch
+        const O2oArgs oa = {(const int32_t*)c->p2l_idx.p, (const float*)c->p2l_d2.p, a.desc, a.row_pair, a.state, max_d2,
+                            (unsigned long long*)c->o2o_table.p, (unsigned*)((unsigned long long*)c->o2o_table.p + total_tgt),
+                            (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + (size_t)np * KSS_TRIM_NINFO};
+        if (launch_o2o(st, total_rows, total_tgt, np, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
+    }
+    if (M.trimmed) launch_pairb_select(st, a.s.d2, a.desc, np, a.state, max_d2, a.ts, d_info);
+    if (M.robust) {
+        if (rob_select) {   // (written keys carry the whole candidate test, a NaN is none: no bound)
+            if (M.symm) launch_pairb_rows<SymmMetric<PAIR_KEY>>(st, total_rows, a);
+            else if (M.plane) launch_pairb_rows<PlaneRobustMetric<PAIR_KEY>>(st, total_rows, a);
+            launch_pairb_robust_select(st, np, a, M.plane ? a.keys : a.s.d2, M.plane ? std::numeric_limits<double>::infinity() : max_d2);
+        }
+        if (M.symm) launch_pairb_rows<SymmMetric<PAIR_ROBUST>>(st, total_rows, a);
+        else if (M.plane) launch_pairb_rows<PlaneRobustMetric<PAIR_ROBUST>>(st, total_rows, a);
+        else launch_pairb_rows<PointRobustMetric<PAIR_ROBUST>>(st, total_rows, a);
+        launch_pairb_robust_final(st, M.plane, np, a, d_rec, d_info);
+    } else {
+        if (M.gicp) launch_pairb_rows<GicpMetric>(st, total_rows, a);
+        else if (M.symm) launch_pairb_rows<SymmMetric<PAIR_PLAIN>>(st, total_rows, a);
+        else if (M.sim) launch_pairb_rows<SimMetric>(st, total_rows, a);
+        else if (!M.plane) launch_pairb_rows<PointTrimMetric>(st, total_rows, a);
+        else if (M.trimmed) launch_pairb_rows<PlaneMetric<true>>(st, total_rows, a);
+        else launch_pairb_rows<PlaneMetric<false>>(st, total_rows, a);
+        launch_pairb_final(st, M.plane, np, a, d_rec, M.sim);
+    }
+    return KSS_OK;
+}
+
+// One pass over given correspondences (the *_sums_dev entry points, which check their arguments: kss_api.hip): the record of mode M
+// for n packed float triples d_src with the targets d_idx, into sums (KSS_P2L_NSUMS or KSS_NSUMS doubles by metric) and, robust, its
+// {m, c2, sum of weights, cnt} into info.  Rn: the row-major 3 x 3 the source normals turn with (null: identity).  No NN pass has
+// run: the distances are recomputed, the point metric writes its keys.
+int pair_record_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n, int64_t nt,
+                    double max_d2, const PairMode& M, const float* Rn, double* sums, double* info) {
+    KCHK(pair_pass_ensure(c, M, n, false));
+    const PairArgs a = {{d_src, nullptr, nullptr, d_idx, nullptr, M.d_src_nrm, max_d2}, d_tgt, d_nrm, n, nt, (double*)c->p2l_rows.p,
+                        (float*)c->rob_keys.p};
+    KCHK(pair_pass_launch(c, a, M, gicp_rot_of(Rn), (double*)c->h_p2l_dev, (double*)c->h_p2l_dev + P2L_NSUMS));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(sums, c->h_p2l, (size_t)(M.plane ? P2L_NSUMS : NSUMS) * sizeof(double));
+    if (M.robust) std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_ROBUST_NINFO * sizeof(double));
+    return KSS_OK;
+}
+
+// ---- the loop of every pair metric: kss_icp_p2l, kss_icp_trimmed, kss_icp_robust, kss_icp_gicp, kss_icp_symm,
+// kss_icp_symm_robust, kss_icp_sim, kss_icp_o2o and their _batch forms ----
+// npairs >= 1 pairs in lockstep.  Per pass: ONE NN pass over the pairs still active (idx / d2 by global source index), the
+// launches of the call's kernel family (above), ONE stream synchronisation, then pair_host_step for every active pair (the host
+// pool from 64 pairs up, each pair on exactly one thread).  A pair that ends goes inactive in the per-pair state table; the
+// workgroups of the later passes' launches leave at once for it and its rows of the host-mapped tables are not written again: no
+// ending touches another pair's record.  icp_loop's engine switch applies.
+// single: the call is pair_run_dev's.  It decides how the NN pass is called (the single pair's waits for its own sums, gated /
+// chained machinery and all; the batch's wait is deferred to the launches behind it) and which family's launches follow -- nothing
+// else.  A batch of one runs the batched kernels; the host-mapped layouts of both families coincide at np == 1.
 struct DeferWait {   // the NN pass does not wait for its sums: the launches behind it are waited for instead
     kss_ctx* c;
     explicit DeferWait(kss_ctx* c_) : c(c_) { c->defer_wait = true; }
     ~DeferWait() { c->defer_wait = false; }
 };
+// pair p's info record behind a pass, from the host-mapped tables h: np records, np selection records, np m's (one-to-one)
+static void pair_info_read(const PairMode& M, const double* h, int np, int p, double* info) {
+    if (!M.trimmed && !M.robust) return;
+    const double* hinfo = h + (size_t)np * P2L_NSUMS;
+    std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, KSS_TRIM_NINFO * sizeof(double));
+    if (M.trimmed) info[3] = h[(size_t)p * P2L_NSUMS];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
+    if (M.unique) info[4] = hinfo[(size_t)np * KSS_TRIM_NINFO + p];   // one-to-one: m, the candidates before the rejection ([0] is u)
+}
 static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
-                      const int32_t* d_perm, bool rob_select, kss_icp_result* results, double* info_all) {
+                      const int32_t* d_perm, bool single, bool rob_select, kss_icp_result* results, double* info_all) {
     const int np = pl_in.npairs;
-    // generalized, symmetric: every pair's PairPass (pinned; e / align staged by pairs_run_dev) starts from the identity and follows
-    // the pair's fin.  A/B switch: the kernel reads the pinned table across the bus instead of a device copy made per pass
+    // generalized, symmetric: every pair's PairPass (pinned; staged by stage_pass_table) starts from the identity and follows the
+    // pair's fin: the rotation the source normals turn with.  The single pair's launches take it from there by value; the batched
+    // kernels read a device copy made per pass or, A/B switch, the pinned table across the bus
     PairPass* hpass = M.gicp || M.symm ? (PairPass*)c->h_gicp : nullptr;
     const char* env_mapped = hpass ? getenv("KSS_GICP_TABLE_MAPPED") : nullptr;
     const bool pass_mapped = env_mapped && atoi(env_mapped) != 0 && c->h_gicp_dev;
     const PairPass* d_pass = hpass ? (pass_mapped ? (const PairPass*)c->h_gicp_dev : (const PairPass*)c->pb_gicp.p) : nullptr;
-    auto pass_rot = [hpass](int p, const float* F) {   // (the float bits pair_loop passes as Rn)
+    auto pass_rot = [hpass](int p, const float* F) {
         if (hpass) std::memcpy(hpass[p].r, rot_of(F).r, sizeof hpass[p].r);
     };
     const IcpPlan* plan = &pl_in;   // may change to the brute-force plan below
@@ -2141,23 +2110,15 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     const double max_d2 = P.max_corr_dist * P.max_corr_dist;
     int32_t* d_idx = (int32_t*)c->p2l_idx.p;
     float* d_d2 = (float*)c->p2l_d2.p;
-    const double* hrec = (const double*)c->h_p2l;                          // np records of P2L_NSUMS doubles ...
-    const double* hinfo = hrec + (size_t)np * P2L_NSUMS;                   // ... and np selection records behind them
+    const double* hrec = (const double*)c->h_p2l;   // np records of P2L_NSUMS doubles, the info records behind them (pair_info_read)
     double* d_rec = (double*)c->h_p2l_dev;
     double* d_info = d_rec + (size_t)np * P2L_NSUMS;
-    TrimState* d_ts = (TrimState*)c->trim_state.p;
-    // one-to-one: every pair's m behind the selection records; the selection and the rows read the filtered copies
-    const double* hinfo_m = hinfo + (size_t)np * KSS_TRIM_NINFO;
-    double* d_info_m = d_info + (size_t)np * KSS_TRIM_NINFO;
-    const int32_t* d_idx_m = M.unique ? (const int32_t*)c->o2o_idx.p : d_idx;
-    const float* d_d2_m = M.unique ? (const float*)c->o2o_d2.p : d_d2;
+    // one-to-one (DESIGN.md 2.23): the selection and the rows read the filtered copies; d_idx / d_d2 stay the NN pass's own
+    const PairSrc src = {nullptr, nullptr, d_perm, M.unique ? (const int32_t*)c->o2o_idx.p : d_idx, M.unique ? (const float*)c->o2o_d2.p : d_d2,
+                         M.d_src_nrm, max_d2};
     int64_t total_tgt = 0;
-    for (int p = 0; p < np; ++p) total_tgt += pl_in.g[p].nt;
-    const PairbDesc* d_desc = (const PairbDesc*)c->pb_desc.p;
-    const RobustScale* d_rs = (const RobustScale*)c->pb_rscale.p;   // (robust)
-    const int32_t* d_row_pair = (const int32_t*)c->pb_rowpair.p;
     int total_rows = 0;
-    for (int p = 0; p < np; ++p) total_rows += stream_blocks(pl_in.g[p].ns);
+    for (int p = 0; p < np; ++p) { total_tgt += pl_in.g[p].nt; total_rows += stream_blocks(pl_in.g[p].ns); }
     if (P.trace_n) *P.trace_n = 0;
     const int ninfo = pair_ninfo(M);
     if (info_all) std::fill(info_all, info_all + (size_t)np * ninfo, 0.0);
@@ -2170,46 +2131,24 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
         const float4* d_in = it == 0 ? (const float4*)c->src0.p : (const float4*)c->cur[(it - 1) & 1].p;
         float4* d_out = (float4*)c->cur[it & 1].p;
         c->last_state_dev = nullptr;
-        {
-            DeferWait defer(c);
-            KCHK(nn_pass(c, *plan, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false, active.data()));
-        }
-        const unsigned long long pass_seq = c->seq;
-        const PairState* d_state = c->last_state_dev;   // (a single pair on its own cell list has none: it is active)
-        {
-            ProfScope ps(c, KSS_K_CORR_REDUCE);
-            const hipStream_t st = c->stream;
-            const PairbArgs a = {{nullptr, d_out, d_perm, d_idx_m, d_d2_m, M.d_src_nrm, max_d2}, d_tgt, d_nrm, d_desc, d_row_pair, d_state, d_rs, d_ts,
-                                 d_pass, (double*)c->p2l_rows.p, (float*)c->rob_keys.p};
-            // the pass table as the host steps left it: the last pass's synchronisation has ordered those writes behind its copy
-            if (hpass && !pass_mapped) HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hpass, (size_t)np * sizeof(PairPass), hipMemcpyHostToDevice, st));
-            if (M.robust) {
-                if (rob_select) {   // some pair takes its scale from the pass's median key: the point metric's keys are the NN pass's d2
-                    if (M.symm) launch_pairb_rows<SymmMetric<PAIR_KEY>>(st, total_rows, a);
-                    else if (M.plane) launch_pairb_rows<PlaneRobustMetric<PAIR_KEY>>(st, total_rows, a);
-                    // (written keys carry the whole candidate test, a NaN is none: no bound)
-                    launch_pairb_robust_select(st, np, a, M.plane ? a.keys : d_d2, M.plane ? std::numeric_limits<double>::infinity() : max_d2);
-                }
-                if (M.symm) launch_pairb_rows<SymmMetric<PAIR_ROBUST>>(st, total_rows, a);
-                else if (M.plane) launch_pairb_rows<PlaneRobustMetric<PAIR_ROBUST>>(st, total_rows, a);
-                else launch_pairb_rows<PointRobustMetric<PAIR_ROBUST>>(st, total_rows, a);
-                launch_pairb_robust_final(st, M.plane, np, a, d_rec, d_info);
-            } else {
-                if (M.unique) {   // table reset, claim, resolve for the whole batch
-                    const O2oArgs oa = {d_idx, d_d2, d_desc, d_row_pair, d_state, max_d2, (unsigned long long*)c->o2o_table.p,
-                                        (unsigned*)((unsigned long long*)c->o2o_table.p + total_tgt), (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p,
-                                        d_info_m};
-                    if (launch_o2o(st, total_rows, total_tgt, np, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
-                }
-                if (M.trimmed) launch_pairb_select(st, d_d2_m, d_desc, np, d_state, max_d2, d_ts, d_info);
-                if (M.gicp) launch_pairb_rows<GicpMetric>(st, total_rows, a);
-                else if (M.symm) launch_pairb_rows<SymmMetric<PAIR_PLAIN>>(st, total_rows, a);
-                else if (M.sim) launch_pairb_rows<SimMetric>(st, total_rows, a);
-                else if (!M.plane) launch_pairb_rows<PointTrimMetric>(st, total_rows, a);
-                else if (M.trimmed) launch_pairb_rows<PlaneMetric<true>>(st, total_rows, a);
-                else launch_pairb_rows<PlaneMetric<false>>(st, total_rows, a);
-                launch_pairb_final(st, M.plane, np, a, d_rec, M.sim);
+        PairSrc s = src;
+        s.src4 = d_out;
+        unsigned long long pass_seq = 0;
+        if (single) {
+            KCHK(nn_pass(c, *plan, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false));
+            const PairArgs a = {s, d_tgt, d_nrm, plan->g[0].ns, plan->g[0].nt, (double*)c->p2l_rows.p, (float*)c->rob_keys.p};
+            KCHK(pair_pass_launch(c, a, M, gicp_rot_of(hpass ? hpass[0].r : nullptr), d_rec, d_info));
+        } else {
+            {
+                DeferWait defer(c);
+                KCHK(nn_pass(c, *plan, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false, active.data()));
             }
+            pass_seq = c->seq;
+            // (state: the table the NN pass read; a single pair on its own cell list has none: it is active)
+            const PairbArgs a = {s, d_tgt, d_nrm, (const PairbDesc*)c->pb_desc.p, (const int32_t*)c->pb_rowpair.p, c->last_state_dev,
+                                 (const RobustScale*)c->pb_rscale.p, (TrimState*)c->trim_state.p, d_pass, (double*)c->p2l_rows.p,
+                                 (float*)c->rob_keys.p};
+            KCHK(pairb_pass_launch(c, a, M, np, total_rows, total_tgt, rob_select, d_rec, d_info));
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2224,14 +2163,9 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
             int fin_here = 0;
             for (int p = pb; p < pe; ++p) {
                 if (!active[p]) continue;
-                const double* s = hrec + (size_t)p * P2L_NSUMS;
                 double info[KSS_SIM_NINFO] = {};
-                if (M.trimmed || M.robust) {
-                    std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, KSS_TRIM_NINFO * sizeof(double));
-                    if (M.trimmed) info[3] = s[0];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
-                    if (M.unique) info[4] = hinfo_m[p];   // one-to-one: m, the candidates before the rejection ([0] is u)
-                }
-                const bool goes_on = pair_host_step(P, M, s, info, tr[p], hs[p], p == 0);   // (similarity: fills the scale slots of info)
+                pair_info_read(M, hrec, np, p, info);
+                const bool goes_on = pair_host_step(P, M, hrec + (size_t)p * P2L_NSUMS, info, tr[p], hs[p], p == 0);   // (similarity: fills the scale slots of info)
                 if ((M.trimmed || M.robust) && info_all) std::memcpy(info_all + (size_t)p * ninfo, info, (size_t)ninfo * sizeof(double));
                 if (!goes_on) {
                     active[p] = 0; ++fin_here;
@@ -2270,6 +2204,111 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     return fitness_pass(c, *plan, P, fin.data(), iters.data(), state.data(), plan == &pl_in, bar, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, results);
 }
 
+static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows);
+
+// ---- what pair_run_dev and pairs_run_dev share around the loop ----
+// the mode's consistency (the arguments are the entry points' to check: kss_api.hip); batch: with the per-pair tables its forms need
+static int pair_mode_check(kss_ctx* c, const char* who, const PairMode& M, const float* d_nrm, bool batch = false,
+                           const RobustScale* rscales = nullptr, const double* gicp_eps = nullptr, const int32_t* symm_aligns = nullptr) {
+    const std::string w = std::string(who) + ": ";
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
+    if (!M.plane && !M.trimmed && !M.robust) return bad("the untrimmed point metric is kss_icp's");
+    if (M.trimmed && M.robust) return bad("trimmed and robust exclude each other");
+    if (M.sim && (M.plane || !M.trimmed)) return bad("similarity ICP is the trimmed point metric's");
+    if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm))
+        return bad("generalized ICP is the plane record with both clouds' normals, neither trimmed nor robust");
+    if (M.symm && (!M.plane || M.trimmed || M.gicp || !M.d_src_nrm || !d_nrm))
+        return bad("symmetric ICP is the plane record with both clouds' normals, neither trimmed nor generalized");
+    if (M.unique && (!M.trimmed || M.robust || M.gicp || M.symm || M.sim))
+        return bad("one-to-one rejection is the trimmed pass's, neither robust, generalized, symmetric nor similarity");
+    if (!batch) return KSS_OK;
+    if (M.robust && !rscales) return bad("robust needs the per-pair scales");
+    if (M.gicp && !gicp_eps) return bad("generalized ICP needs the per-pair epsilons");
+    if (M.symm && !symm_aligns) return bad("symmetric ICP needs the per-pair aligns");
+    return KSS_OK;
+}
+
+// generalized, symmetric: the per-pair pass table, pinned and on the device: e = 1 - epsilon as pair_pass_launch forms it, align
+// as it passes it; pairs_loop fills the rotations
+static int stage_pass_table(kss_ctx* c, const PairMode& M, int npairs, const double* gicp_eps, const int32_t* symm_aligns) {
+    KCHK(ensure(c, c->pb_gicp, (size_t)npairs * sizeof(PairPass)));
+    KCHK(ensure_pinned(c, c->h_gicp, c->h_gicp_cap, (size_t)npairs * sizeof(PairPass)));
+    HIPCHK(c, hipHostGetDevicePointer(&c->h_gicp_dev, c->h_gicp, 0));
+    PairPass* hpass = (PairPass*)c->h_gicp;
+    std::memset(hpass, 0, (size_t)npairs * sizeof(PairPass));
+    for (int i = 0; i < npairs; ++i) {
+        if (M.gicp) hpass[i].e = 1.0 - gicp_eps[i];
+        else hpass[i].align = symm_aligns[i];
+    }
+    return KSS_OK;
+}
+
+// the end of both: where the cell-list setup put each source (it re-orders them, .w: the global original index), the loop, and
+// the call's two timings from t0
+static int pair_run_loop(kss_ctx* c, const IcpPlan& pl, std::chrono::steady_clock::time_point t0, DirtyGuard& guard, const kss_icp_params& P,
+                         const PairMode& M, const float* d_tgt, const float* d_nrm, bool single, bool rob_select, kss_icp_result* results,
+                         double* info_all) {
+    const int32_t* d_perm = nullptr;
+    if (pl.src_in_cell_order) {
+        KCHK(ensure(c, c->p2l_perm, (size_t)pl.total_src * sizeof(int32_t)));
+        launch_p2l_perm(c->stream, (const float4*)c->src0.p, pl.total_src, (int32_t*)c->p2l_perm.p);
+        HIPCHK(c, hipGetLastError());
+        d_perm = (const int32_t*)c->p2l_perm.p;
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    const int rc = pairs_loop(c, pl, P, M, d_tgt, d_nrm, d_perm, single, rob_select, results, info_all);
+    guard.ok = rc == KSS_OK;
+    const auto t2 = std::chrono::steady_clock::now();
+    c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return rc;
+}
+
+int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                 const kss_icp_params* p, const PairMode& M, kss_icp_result* res) {
+    KCHK(pair_mode_check(c, "pair_run", M, d_nrm));
+    HIPCHK(c, hipSetDevice(c->device));
+    IcpPlan pl;
+    const auto t0 = std::chrono::steady_clock::now();
+    KCHK(restore_zero_at_rest(c));
+    DirtyGuard guard(c);
+    c->timing = false;
+    KCHK(build_plan(c, &ns, &nt, 1, false, p->nn_sources_per_thread, p->nn_target_splits, p->nn_mode, pl));
+    KCHK(stage_plan(c, pl));
+    KCHK(ensure(c, c->p2l_idx, (size_t)ns * sizeof(int32_t)));
+    KCHK(ensure(c, c->p2l_d2, (size_t)ns * sizeof(float)));
+    KCHK(pair_pass_ensure(c, M, ns, true));
+    if (M.gicp || M.symm) KCHK(stage_pass_table(c, M, 1, &M.gicp_epsilon, &M.symm_align));
+    if (M.unique) {   // the claim table, the filtered idx / d2 and the pair as the filter's kernels see it
+        KCHK(ensure(c, c->o2o_table, o2o_table_bytes(nt, 1)));
+        KCHK(ensure(c, c->o2o_idx, (size_t)ns * sizeof(int32_t)));
+        KCHK(ensure(c, c->o2o_d2, (size_t)ns * sizeof(float)));
+        PairbDesc d;
+        d.src_base = 0; d.ns = ns; d.tgt_off = 0; d.nt = nt; d.overlap = M.overlap; d.row_base = 0; d.nrows = stream_blocks(ns);
+        KCHK(stage_pairb(c, std::vector<PairbDesc>(1, d), false));
+    }
+    const int64_t so[2] = {0, ns}, to[2] = {0, nt};
+    KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));
+    KCHK(grid_setup(c, pl));
+    return pair_run_loop(c, pl, t0, guard, *p, M, d_tgt, d_nrm, true, false, res, M.last_info);
+}
+
+
+// tau / m / k / kept of n squared distances on the device (kss_trim_threshold_dev)
+int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info) {
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(ensure(c, c->trim_rows, trim_rows_bytes(n)));
+    KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO) * sizeof(double)));
+    launch_trim_select(c->stream, d_d2, n, max_d2, overlap, (unsigned*)c->trim_rows.p, (TrimState*)c->trim_state.p,
+                       (double*)c->h_p2l_dev + P2L_NSUMS);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memcpy(info, (const double*)c->h_p2l + P2L_NSUMS, KSS_TRIM_NINFO * sizeof(double));
+    return KSS_OK;
+}
+
+
 // per-pair descriptors (and the row -> pair table) of the batched kernels, uploaded once per call
 static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows) {
     std::vector<int32_t> row_pair;
@@ -2285,20 +2324,10 @@ static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows
     return KSS_OK;
 }
 
-// (the arguments are the entry points' to check: kss_api.hip)
 int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, const float* d_nrm,
                   int npairs, const kss_icp_params* p, const PairMode& M, const double* overlaps, kss_icp_result* results, double* info_all,
                   const RobustScale* rscales, const double* gicp_eps, const int32_t* symm_aligns) {
-    if (!M.plane && !M.trimmed && !M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: the untrimmed point metric is kss_icp_batch's");
-    if (M.trimmed && M.robust) return set_err(c, KSS_ERR_ARG, "pairs_run: trimmed and robust exclude each other");
-    if (M.sim && (M.plane || !M.trimmed)) return set_err(c, KSS_ERR_ARG, "pairs_run: similarity ICP is the trimmed point metric's");
-    if (M.robust && !rscales) return set_err(c, KSS_ERR_ARG, "pairs_run: robust needs the per-pair scales");
-    if (M.gicp && (!M.plane || M.trimmed || M.robust || !M.d_src_nrm || !d_nrm || !gicp_eps))
-        return set_err(c, KSS_ERR_ARG, "pairs_run: generalized ICP is the plane record with both clouds' normals and the per-pair epsilons, neither trimmed nor robust");
-    if (M.symm && (!M.plane || M.trimmed || M.gicp || !M.d_src_nrm || !d_nrm || !symm_aligns))
-        return set_err(c, KSS_ERR_ARG, "pairs_run: symmetric ICP is the plane record with both clouds' normals and the per-pair aligns, neither trimmed nor generalized; robust symmetric ICP adds the per-pair scales");
-    if (M.unique && (!M.trimmed || M.robust || M.gicp || M.symm || M.sim))
-        return set_err(c, KSS_ERR_ARG, "pairs_run: one-to-one rejection is the trimmed pass's, neither robust, generalized, symmetric nor similarity");
+    KCHK(pair_mode_check(c, "pairs_run", M, d_nrm, true, rscales, gicp_eps, symm_aligns));
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> ns(npairs), nt(npairs);
     for (int i = 0; i < npairs; ++i) { ns[i] = src_off[i + 1] - src_off[i]; nt[i] = tgt_off[i + 1] - tgt_off[i]; }
@@ -2334,17 +2363,7 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (the caller's table may be pageable and short-lived)
         if (rob_select && M.plane) KCHK(ensure(c, c->rob_keys, (size_t)pl.total_src * sizeof(float)));
     }
-    if (M.gicp || M.symm) {   // the per-pair pass table: e = 1 - epsilon as pair_loop forms it, align as it passes it; pairs_loop fills the rotations
-        KCHK(ensure(c, c->pb_gicp, (size_t)npairs * sizeof(PairPass)));
-        KCHK(ensure_pinned(c, c->h_gicp, c->h_gicp_cap, (size_t)npairs * sizeof(PairPass)));
-        HIPCHK(c, hipHostGetDevicePointer(&c->h_gicp_dev, c->h_gicp, 0));
-        PairPass* hpass = (PairPass*)c->h_gicp;
-        std::memset(hpass, 0, (size_t)npairs * sizeof(PairPass));
-        for (int i = 0; i < npairs; ++i) {
-            if (M.gicp) hpass[i].e = 1.0 - gicp_eps[i];
-            else hpass[i].align = symm_aligns[i];
-        }
-    }
+    if (M.gicp || M.symm) KCHK(stage_pass_table(c, M, npairs, gicp_eps, symm_aligns));
     if (M.unique) {   // one claim table over the batch's targets (pair p's slots at tgt_off[p], counted from 0), the filtered idx / d2
         if (tgt_off[0] != 0) return set_err(c, KSS_ERR_ARG, "pairs_run: the target offsets must start at 0");
         KCHK(ensure(c, c->o2o_table, o2o_table_bytes(tgt_off[npairs], npairs)));
@@ -2355,20 +2374,7 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
     KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));
     KCHK(grid_setup(c, pl));
     KCHK(grid_setup_batch(c, pl));
-    const int32_t* d_perm = nullptr;
-    if (pl.src_in_cell_order) {   // the cell-list setup re-ordered the sources (.w: the global original index): where each one went
-        KCHK(ensure(c, c->p2l_perm, (size_t)pl.total_src * sizeof(int32_t)));
-        launch_p2l_perm(c->stream, (const float4*)c->src0.p, pl.total_src, (int32_t*)c->p2l_perm.p);
-        HIPCHK(c, hipGetLastError());
-        d_perm = (const int32_t*)c->p2l_perm.p;
-    }
-    const auto t1 = std::chrono::steady_clock::now();
-    const int rc = pairs_loop(c, pl, *p, M, d_tgt, d_nrm, d_perm, rob_select, results, info_all);
-    guard.ok = rc == KSS_OK;
-    const auto t2 = std::chrono::steady_clock::now();
-    c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    return rc;
+    return pair_run_loop(c, pl, t0, guard, *p, M, d_tgt, d_nrm, false, rob_select, results, info_all);
 }
 
 // tau / m / k / kept of nseg segments of squared distances in one launch (kss_trim_threshold_batch_dev)
