@@ -495,8 +495,8 @@ int kss_trim_threshold_batch_dev(kss_ctx *ctx, const float *d_d2_all, const int6
  * iterations, state, last_mse, every traced T_k and sums row, and info [0..3].
  * Behind the NN pass a pass makes three launches -- table reset, claim, resolve -- and then the trimmed pass's own: six more for one
  * pair, three more for a batch, whatever the pair count.
- * Not offered: the rejection in front of the robust, generalized, symmetric and similarity forms; reciprocal correspondences; the
- * C++ mirror classes and the CLI. */
+ * Not offered: the rejection in front of the robust, generalized, symmetric and similarity forms; the C++ mirror classes and the
+ * CLI.  Keeping only reciprocal correspondences is kss_icp_recip's, below. */
 #define KSS_O2O_NINFO 5   /* {u survivors, k rank, tau widened to double, kept, m candidates before the rejection} */
 /* The filter alone for n sources against nt targets: idx_out / d2_out receive idx_f / d2_f (either may be NULL, either may be its
  * input), info = {m, u}.  KSS_ERR_ARG: a NULL ctx (refused before anything touches the device), idx, d2 or info; n or nt <= 0 or
@@ -539,6 +539,60 @@ int kss_icp_o2o_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off
 int kss_icp_o2o_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_tgt_all, const int64_t *tgt_off,
                           const float *d_tgt_normals_all, int npairs, const kss_icp_params *p, const kss_o2o_params *op,
                           const double *overlaps, kss_icp_result *results, double *info_all);
+
+/* ---- reciprocal ICP: a correspondence is kept only where source and target are each other's nearest (PCL's
+ *      setUseReciprocalCorrespondences(true) in front of kss_icp_trimmed's pass), both metrics, ONE pair per call ----
+ * One pass, on the NN pass's idx[i] and float d2[i] (by original source index), the sources' CURRENT float positions p_k -- the ones
+ * the NN pass measured from and wrote out -- and the float targets q_j:
+ *   candidate, key(i)   exactly kss_icp_o2o's: idx[i] in [0, nt) and 0 <= d2[i] <= max_d2 in ordered double compares, m of them;
+ *               key(i) = ((uint64)(bits(d2[i]) & 0x7fffffff) << 32) | (uint32)i;
+ *   winner      kss_icp_o2o's: of the candidates with idx == j the one with the smallest key wins target j, u winners;
+ *   rkey(k, j)  ((uint64)(bits(dist2<nn_fma>(p_k, q_j)) & 0x7fffffff) << 32) | (uint32)k, for EVERY source k in [0, ns), candidate or
+ *               not: dist2 is the NN engines' own float arithmetic ((dx*dx + dy*dy) + dz*dz, or with p->nn_fma
+ *               fma(dx, dx, fma(dy, dy, dz*dz))), d = p_k - q_j, the source first as the engines call it.  A NaN distance masks to a
+ *               key above every finite one: it beats nothing;
+ *   mutual      a winner i of target j is mutual iff NO source k has rkey(k, j) < key(i).  This is an existence statement: which
+ *               sources an implementation examines, and in what order, cannot change a bit of the result.  With the engines' exact
+ *               NN, rkey(i, j) == key(i), and the condition reads "i is the nearest source of its nearest target, ties to the
+ *               lowest source index"; r = the number of mutual winners;
+ *   filtered    idx_f, d2_f: a mutual winner keeps idx[i] and d2[i] bit for bit; every other candidate gets idx_f = -1 and d2_f = the
+ *               quiet NaN 0x7fc00000; a source that is no candidate passes through unchanged;
+ *   the pass    kss_icp_trimmed's pass on (idx_f, d2_f), nothing redefined, exactly as kss_icp_o2o does it;
+ *   info        KSS_RECIP_NINFO doubles {r, k, tau, kept, m, u}.
+ * A source position that is not finite is outside the definition; it neither faults nor takes part in the reverse search.
+ * The loop, the endings, the normals given or computed, the fitness over ALL sources with the unfiltered fitness_idx / fitness_d2, and
+ * p->allreduce must be NULL are kss_icp_o2o's.  Neither a residual scale nor an overlap has to be known: a stray source that is alone
+ * on its target -- which one-to-one keeps -- goes wherever that target has a nearer source.
+ * Where every winner is mutual in every pass the call is kss_icp_o2o at the same overlap and metric BIT FOR BIT: T, iterations, state,
+ * last_mse, every traced T_k and sums row, and info [0..4]; where the NN map is also injective it is kss_icp_trimmed bit for bit.
+ * Behind the NN pass a pass makes five launches -- workspace reset, claim + cell count, scan, scatter, resolve + check -- and then the
+ * trimmed pass's six.  Once per call the target's bounding box is taken (one launch, one synchronisation) for the cell grid the
+ * moving sources are binned into.
+ * Not built: the batch (kss_icp_recip_batch is the named follow-up); the check in front of the robust, generalized, symmetric and
+ * similarity forms; the C++ mirror classes and the CLI. */
+#define KSS_RECIP_NINFO 6   /* {r mutual winners, k rank, tau widened to double, kept, m candidates, u winners before the check} */
+/* The filter alone on packed float triples: n sources src with the map idx / d2 against nt targets tgt; d2 is taken as given, so the
+ * definition above holds for any d2 the caller passes; nn_fma != 0: the reverse distances by the fma form.  idx_out / d2_out receive
+ * idx_f / d2_f (either may be NULL, either may be its input), info = {m, u, r}.  KSS_ERR_ARG: a NULL ctx (refused before anything
+ * touches the device), src, tgt, idx, d2 or info; n or nt <= 0 or beyond the C-ABI's cloud size. */
+int kss_recip_filter(kss_ctx *ctx, const float *src, int64_t n, const float *tgt, int64_t nt, const int32_t *idx, const float *d2,
+                     double max_d2, int nn_fma, int32_t *idx_out, float *d2_out, double info[3]);
+int kss_recip_filter_dev(kss_ctx *ctx, const float *d_src, int64_t n, const float *d_tgt, int64_t nt, const int32_t *d_idx,
+                         const float *d_d2, double max_d2, int nn_fma, int32_t *d_idx_out, float *d_d2_out, double info[3]);
+typedef struct {
+    double  overlap;       /* share of the mutual winners kept per pass, 0 < overlap <= 1 */
+    int     metric;        /* KSS_METRIC_POINT or KSS_METRIC_PLANE */
+    double *trace_recip;   /* p->trace_cap * KSS_RECIP_NINFO doubles, row i beside trace_sums row i; may be NULL */
+} kss_recip_params;
+/* overlap 1, KSS_METRIC_POINT, trace_recip NULL */
+int kss_recip_default_params(kss_recip_params *rp);
+/* Arguments as kss_icp_o2o; last_info (may be NULL): the last pass's record, all zero when no pass ran.  KSS_ERR_ARG: everything
+ * kss_icp_o2o refuses -- a NULL ctx (refused before anything touches the device), a NULL rp.  A refused call leaves the context
+ * usable. */
+int kss_icp_recip(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt, int64_t nt, const float *tgt_normals,
+                  const kss_icp_params *p, const kss_recip_params *rp, kss_icp_result *res, double last_info[KSS_RECIP_NINFO]);
+int kss_icp_recip_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
+                      const kss_icp_params *p, const kss_recip_params *rp, kss_icp_result *res, double last_info[KSS_RECIP_NINFO]);
 
 /* ---- generalized ICP (plane-to-plane; Segal, Haehnel, Thrun: Generalized-ICP, RSS 2009) for one pair ----
  * Both clouds carry a local surface model: PCL-style GICP replaces the eigenvalues of each point's k-NN covariance by

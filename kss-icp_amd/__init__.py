@@ -15,7 +15,8 @@ from .binding import (KssError, Context, IcpParams, IcpResult, RegisterResult, P
                       METRIC_POINT, METRIC_PLANE, TRIM_NINFO, TrimParams, trim_rank,
                       LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, ROBUST_NINFO, RobustParams, robust_params, robust_weight,
                       robust_scale2, GicpParams, gicp_params, gicp_metric, SymmParams, symm_params, rigid_from_symm_sums,
-                      SIM_NINFO, SimParams, sim_params, sim_from_sums, O2O_NINFO, O2oParams, o2o_params)
+                      SIM_NINFO, SimParams, sim_params, sim_from_sums, O2O_NINFO, O2oParams, o2o_params,
+                      RECIP_NINFO, RecipParams, recip_params)
 from . import synth
 from . import shard
 
@@ -25,4 +26,5 @@ __all__ = ["KssError", "Context", "IcpParams", "IcpResult", "RegisterResult", "P
            "METRIC_POINT", "METRIC_PLANE", "TRIM_NINFO", "TrimParams", "trim_rank",
            "LOSS_L2", "LOSS_HUBER", "LOSS_TUKEY", "LOSS_CAUCHY", "ROBUST_NINFO", "RobustParams", "robust_params", "robust_weight",
            "robust_scale2", "GicpParams", "gicp_params", "gicp_metric", "SymmParams", "symm_params", "rigid_from_symm_sums",
-           "SIM_NINFO", "SimParams", "sim_params", "sim_from_sums", "O2O_NINFO", "O2oParams", "o2o_params"]
+           "SIM_NINFO", "SimParams", "sim_params", "sim_from_sums", "O2O_NINFO", "O2oParams", "o2o_params",
+           "RECIP_NINFO", "RecipParams", "recip_params"]

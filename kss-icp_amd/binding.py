@@ -24,6 +24,7 @@ LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY = 0, 1, 2, 3   # KSS_LOSS_*: the we
 ROBUST_NINFO = 4         # KSS_ROBUST_NINFO: {m candidates, c2, sum of weights, cnt kept} of a robust pass
 SIM_NINFO = 6            # KSS_SIM_NINFO: {m, k, tau, kept, s_k, s_acc after the pass} of a similarity pass
 O2O_NINFO = 5            # KSS_O2O_NINFO: {u survivors, k, tau, kept, m candidates} of a one-to-one pass
+RECIP_NINFO = 6          # KSS_RECIP_NINFO: {r mutual winners, k, tau, kept, m candidates, u winners} of a reciprocal pass
 F32, F64 = 0, 1
 
 # every symbol include/kssicp.h declares (checked by tests/test_abi.py against the header text)
@@ -51,6 +52,7 @@ SYMBOLS = [
     "kss_icp_sim_batch", "kss_icp_sim_batch_dev",
     "kss_o2o_filter", "kss_o2o_filter_dev", "kss_o2o_filter_batch", "kss_o2o_filter_batch_dev", "kss_o2o_default_params",
     "kss_icp_o2o", "kss_icp_o2o_dev", "kss_icp_o2o_batch", "kss_icp_o2o_batch_dev",
+    "kss_recip_filter", "kss_recip_filter_dev", "kss_recip_default_params", "kss_icp_recip", "kss_icp_recip_dev",
 ]
 
 
@@ -93,6 +95,10 @@ class SimParams(C.Structure):
 
 class O2oParams(C.Structure):
     _fields_ = [("overlap", C.c_double), ("metric", C.c_int), ("trace_o2o", C.POINTER(C.c_double))]
+
+
+class RecipParams(C.Structure):
+    _fields_ = [("overlap", C.c_double), ("metric", C.c_int), ("trace_recip", C.POINTER(C.c_double))]
 
 
 class RobustParams(C.Structure):
@@ -199,6 +205,11 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(O2oParams), C.POINTER(IcpResult), vp]
     for n in ("kss_icp_o2o_batch", "kss_icp_o2o_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(O2oParams), vp, vp, vp]
+    L.kss_recip_default_params.argtypes = [C.POINTER(RecipParams)]
+    for n in ("kss_recip_filter", "kss_recip_filter_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, vp, dbl, C.c_int, vp, vp, vp]
+    for n in ("kss_icp_recip", "kss_icp_recip_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(RecipParams), C.POINTER(IcpResult), vp]
     L.kss_robust_default_params.argtypes = [C.c_int, C.c_int, C.POINTER(RobustParams)]
     L.kss_robust_weight.argtypes = [C.c_int, dbl, dbl, C.POINTER(dbl)]
     L.kss_robust_scale2.argtypes = [C.c_int, dbl, C.c_float, dbl, C.POINTER(dbl)]
@@ -376,6 +387,20 @@ def o2o_params(**kw):
             raise AttributeError(k)
         setattr(op, k, v)
     return op
+
+
+def recip_params(**kw):
+    """kss_recip_default_params (overlap 1, point metric), then the fields given by keyword."""
+    L = load_library()
+    rp = RecipParams()
+    rc = L.kss_recip_default_params(C.byref(rp))
+    if rc != 0:
+        raise KssError(rc, "kss_recip_default_params")
+    for k, v in kw.items():
+        if not hasattr(rp, k):
+            raise AttributeError(k)
+        setattr(rp, k, v)
+    return rp
 
 
 def sim_from_sums(sums, lo=0.5, hi=2.0):
@@ -652,8 +677,9 @@ class Context:
         """call(res) with the trace and fitness_corr arrays attached to the params p (and to the TrimParams or RobustParams tp),
         detached again whether it returns or raises; the result dictionary of icp()."""
         tname = ("trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else
-                 "trace_o2o" if isinstance(tp, O2oParams) else "trace_trim")
-        ninfo = SIM_NINFO if isinstance(tp, SimParams) else O2O_NINFO if isinstance(tp, O2oParams) else TRIM_NINFO
+                 "trace_o2o" if isinstance(tp, O2oParams) else "trace_recip" if isinstance(tp, RecipParams) else "trace_trim")
+        ninfo = (SIM_NINFO if isinstance(tp, SimParams) else O2O_NINFO if isinstance(tp, O2oParams) else
+                 RECIP_NINFO if isinstance(tp, RecipParams) else TRIM_NINFO)
         res = IcpResult()
         tr = None
         fc = None
@@ -675,7 +701,7 @@ class Context:
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-                if isinstance(tp, (RobustParams, SimParams, O2oParams)):
+                if isinstance(tp, (RobustParams, SimParams, O2oParams, RecipParams)):
                     setattr(tp, tname, None)
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
@@ -834,6 +860,58 @@ class Context:
         self._chk(self.L.kss_icp_o2o_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
                                          C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(op),
                                          C.byref(res), _p(info)), "kss_icp_o2o_dev")
+        return res, info
+
+    # ---- reciprocal ICP
+    def recip_filter(self, src, tgt, idx, d2, max_d2=1.0, nn_fma=0, want_idx=True, want_d2=True, alias=False):
+        """kss_recip_filter: (idx_f, d2_f, m, u, r) of the map idx (int32) / d2 (float32) from the sources src to the targets tgt
+        (float32 triples); an output that is not wanted is None.  alias: the library writes into (copies of) the inputs themselves."""
+        s, t = _f32(src), _f32(tgt)
+        i = np.array(idx, dtype=np.int32).reshape(-1)
+        d = np.array(d2, dtype=np.float32).reshape(-1)
+        if len(i) != len(d) or len(i) != len(s):
+            raise ValueError("idx and d2 must have one entry per source")
+        io = (i if alias else np.empty_like(i)) if want_idx else None
+        do = (d if alias else np.empty_like(d)) if want_d2 else None
+        info = np.zeros(3, np.float64)
+        self._chk(self.L.kss_recip_filter(self.h, _p(s), len(s), _p(t), len(t), _p(i), _p(d), float(max_d2), int(nn_fma), _p(io), _p(do),
+                                          _p(info)), "kss_recip_filter")
+        return io, do, int(info[0]), int(info[1]), int(info[2])
+
+    def recip_filter_dev(self, d_src, n, d_tgt, nt, d_idx, d_d2, max_d2=1.0, nn_fma=0, d_idx_out=None, d_d2_out=None):
+        """kss_recip_filter_dev on device pointers (an output may be 0 / None, or its input); returns (m, u, r)."""
+        info = np.zeros(3, np.float64)
+        self._chk(self.L.kss_recip_filter_dev(self.h, C.c_void_p(int(d_src)), int(n), C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_idx)),
+                                              C.c_void_p(int(d_d2)), float(max_d2), int(nn_fma),
+                                              C.c_void_p(int(d_idx_out)) if d_idx_out else None,
+                                              C.c_void_p(int(d_d2_out)) if d_d2_out else None, _p(info)), "kss_recip_filter_dev")
+        return int(info[0]), int(info[1]), int(info[2])
+
+    def icp_recip(self, src, tgt, normals=None, overlap=1.0, metric=METRIC_POINT, params=None, trace_cap=0, fitness_corr=False):
+        """Reciprocal ICP (kss_icp_recip): a correspondence is kept only where source and target are each other's nearest, then
+        icp_trimmed()'s pass at `overlap` over the mutual winners.  Arguments and result dictionary as icp_o2o(), with trace_recip
+        (one {r, k, tau, kept, m, u} row per traced pass) and recip_info (the last pass's)."""
+        s, t = _f32(src), _f32(tgt)
+        nr = _f32(normals) if normals is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        p = params if params is not None else self.icp_params()
+        rp = RecipParams(float(overlap), int(metric), None)
+        info = np.zeros(RECIP_NINFO, np.float64)
+        out = self._icp_call(lambda res: self.L.kss_icp_recip(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(rp),
+                                                              C.byref(res), _p(info)),
+                             "kss_icp_recip", p, len(s), P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, rp)
+        out["recip_info"] = info
+        return out
+
+    def icp_recip_dev(self, d_src, ns, d_tgt, nt, d_normals, params, overlap=1.0, metric=METRIC_POINT):
+        """kss_icp_recip_dev on device pointers (d_normals may be 0 / None); returns (IcpResult, recip_info)."""
+        res = IcpResult()
+        rp = RecipParams(float(overlap), int(metric), None)
+        info = np.zeros(RECIP_NINFO, np.float64)
+        self._chk(self.L.kss_icp_recip_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
+                                           C.c_void_p(int(d_normals)) if d_normals else None, C.byref(params), C.byref(rp),
+                                           C.byref(res), _p(info)), "kss_icp_recip_dev")
         return res, info
 
     # ---- similarity ICP

@@ -1,5 +1,5 @@
 // kss_api.hip -- the C-ABI of include/kssicp.h: context and profiling entry points, and the compute entry points over
-// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_robust / kss_pairb / kss_o2o .hip).
+// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_robust / kss_pairb / kss_o2o / kss_recip .hip).
 // There is no CPU compute fallback anywhere in this file.
 #pragma clang fp contract(off)
 
@@ -70,7 +70,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_slot, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp, &c->o2o_table, &c->o2o_idx, &c->o2o_d2};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp, &c->o2o_table, &c->o2o_idx, &c->o2o_d2, &c->recip_sorted, &c->recip_box};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -1275,6 +1275,82 @@ int kss_o2o_filter(kss_ctx* c, const int32_t* idx, const float* d2, int64_t n, i
                    double info[2]) {
     const int64_t off[2] = {0, n};
     return kss_o2o_filter_batch(c, idx, d2, off, &nt, 1, max_d2, idx_out, d2_out, info);
+}
+
+// ---- reciprocal ICP: kss_icp_trimmed's checks, staging and loop with PairMode::mutual ----
+int kss_recip_default_params(kss_recip_params* rp) {
+    if (!rp) return KSS_ERR_ARG;
+    rp->overlap = 1.0;
+    rp->metric = KSS_METRIC_POINT;
+    rp->trace_recip = nullptr;
+    return KSS_OK;
+}
+
+static inline kss_trim_params recip_trim_params(const kss_recip_params* rp) { return kss_trim_params{rp->overlap, rp->metric, rp->trace_recip}; }
+
+int kss_icp_recip_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                      const kss_icp_params* p, const kss_recip_params* rp, kss_icp_result* res, double last_info[KSS_RECIP_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!rp) return set_err(c, KSS_ERR_ARG, "icp_recip: null argument");
+    const kss_trim_params tp = recip_trim_params(rp);
+    KCHK(pair_check(c, "icp_recip", true, d_src, d_tgt, ns, nt, d_nrm, p, &tp, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    PairMode mode;
+    mode.plane = tp.metric == KSS_METRIC_PLANE;
+    mode.trimmed = true;
+    mode.mutual = true;
+    mode.overlap = tp.overlap;
+    mode.trace_info = tp.trace_trim;
+    mode.last_info = last_info;
+    if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
+    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
+}
+
+int kss_icp_recip(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
+                  const kss_icp_params* p, const kss_recip_params* rp, kss_icp_result* res, double last_info[KSS_RECIP_NINFO]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!rp) return set_err(c, KSS_ERR_ARG, "icp_recip: null argument");
+    const kss_trim_params tp = recip_trim_params(rp);
+    KCHK(pair_check(c, "icp_recip", true, src, tgt, ns, nt, nrm, p, &tp, res));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
+    return kss_icp_recip_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
+                             p, rp, res, last_info);
+}
+
+// the filter alone: the arguments of both entry points
+static int recip_filter_check(kss_ctx* c, const void* src, const void* tgt, const void* idx, const void* d2, int64_t n, int64_t nt, const double* info) {
+    if (!src || !tgt || !idx || !d2 || !info) return set_err(c, KSS_ERR_ARG, "recip_filter: null argument");
+    if (n <= 0 || n > 0x7fff0000ll || nt <= 0 || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "recip_filter: source or target count empty or out of range");
+    return KSS_OK;
+}
+
+int kss_recip_filter_dev(kss_ctx* c, const float* d_src, int64_t n, const float* d_tgt, int64_t nt, const int32_t* d_idx, const float* d_d2,
+                         double max_d2, int nn_fma, int32_t* d_idx_out, float* d_d2_out, double info[3]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(recip_filter_check(c, d_src, d_tgt, d_idx, d_d2, n, nt, info));
+    return recip_filter_dev(c, d_src, n, d_tgt, nt, d_idx, d_d2, max_d2, nn_fma != 0, d_idx_out, d_d2_out, info);
+}
+
+int kss_recip_filter(kss_ctx* c, const float* src, int64_t n, const float* tgt, int64_t nt, const int32_t* idx, const float* d2, double max_d2,
+                     int nn_fma, int32_t* idx_out, float* d2_out, double info[3]) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(recip_filter_check(c, src, tgt, idx, d2, n, nt, info));
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
+    KCHK(upload(c, c->stage_d2, d2, (size_t)n * sizeof(float)));
+    // filtered in place on the staged copies, then back to whichever outputs the caller gave
+    KCHK(recip_filter_dev(c, (const float*)c->stage_src.p, n, (const float*)c->stage_tgt.p, nt, (const int32_t*)c->stage_idx.p,
+                          (const float*)c->stage_d2.p, max_d2, nn_fma != 0, idx_out ? (int32_t*)c->stage_idx.p : nullptr,
+                          d2_out ? (float*)c->stage_d2.p : nullptr, info));
+    if (idx_out) HIPCHK(c, hipMemcpyAsync(idx_out, c->stage_idx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (d2_out) HIPCHK(c, hipMemcpyAsync(d2_out, c->stage_d2.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KSS_OK;
 }
 
 // ---- similarity ICP for many pairs per call ------------------------------------------

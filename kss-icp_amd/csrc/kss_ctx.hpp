@@ -68,6 +68,11 @@ struct kss_ctx {
     // one-to-one rejection (kss_o2o.hip): the claim table (one uint64 per target of the call, two uint32 counters per
     // pair behind it; set to all ones before every pass, so nothing has to hold between passes) and the filtered idx / d2
     DevBuf o2o_table, o2o_idx, o2o_d2;
+    // reciprocal rejection (kss_recip.hip): its workspace is o2o_table's buffer (the claim table, four counters, the
+    // cell counts; set to all ones before every pass) and the filtered idx / d2 are o2o_idx / o2o_d2; the sources in cell order,
+    // rewritten by every pass, the bounding-box partials of the call's target and the cell grid derived from them
+    DevBuf recip_sorted, recip_box;
+    RecipGrid recip_grid = {0.0f, 0.0f, 0.0f, 0.0f, 1, 1, 1};
     void* h_gicp = nullptr; size_t h_gicp_cap = 0;
     void* h_gicp_dev = nullptr;   // (the pinned copy as the device sees it: KSS_GICP_TABLE_MAPPED, an A/B switch)
     const PairState* last_state_dev = nullptr;   // the per-pair state table the last batched NN pass read (null: none, a single pair)
@@ -277,6 +282,8 @@ struct PairMode {
     double scale_max = 1.0;         // hold KSS_SIM_NINFO doubles per record
     bool unique = false;            // one-to-one rejection in front of the trimmed pass (kss_icp_o2o; with trimmed, not with robust, gicp,
                                     // symm or sim): the info records hold KSS_O2O_NINFO doubles, [0] = u, [4] = m
+    bool mutual = false;            // reciprocal rejection in front of the trimmed pass (kss_icp_recip; with trimmed, never with unique,
+                                    // robust, gicp, symm or sim, one pair only): KSS_RECIP_NINFO doubles, [0] = r, [4] = m, [5] = u
 };
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
@@ -301,6 +308,10 @@ int trim_threshold_batch_dev(kss_ctx* c, const float* d_d2, const int64_t* off, 
 // against nts[i] targets, in the same three launches: the filtered arrays (either may be null or its input) and {m, u} per segment
 int o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, const int64_t* off, const int64_t* nts, int nseg, double max_d2,
                    int32_t* d_idx_out, float* d_d2_out, double* info_all);
+// the reciprocal filter alone (kss_recip_filter_dev): n packed float triples d_src with the map d_idx / d_d2 against the nt triples
+// d_tgt, reverse distances by dist2<nn_fma>; the filtered arrays (either may be null or its input) and info = {m, u, r}
+int recip_filter_dev(kss_ctx* c, const float* d_src, int64_t n, const float* d_tgt, int64_t nt, const int32_t* d_idx, const float* d_d2,
+                     double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out, double* info);
 // host-mapped {value, sequence number} result slots: allocate them; wait for the first nslots of launch c->seq
 int ensure_pub_slots(kss_ctx* c);
 int wait_slots(kss_ctx* c, int nslots, double* out);

@@ -1883,6 +1883,9 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // table reset, claim, resolve) filter the NN pass's idx / d2 into o2o_idx / o2o_d2, which the selection and the rows launch read in
 // their place; the info record grows to KSS_O2O_NINFO = {u, k, tau, kept, m}, m published by the resolve launch behind the
 // selection's four slots.  The NN pass's own arrays stay as written: the fitness pass and fitness_idx / fitness_d2 are unfiltered.
+// Reciprocal (kss_icp_recip; M.mutual with M.trimmed, either metric, one pair only): five launches ahead of the
+// selection (kss_recip.hip: reset, claim + count, scan, scatter, resolve + check) filter the same arrays the same way, against the
+// positions the NN pass wrote; the info record grows to KSS_RECIP_NINFO = {r, k, tau, kept, m, u}, m and u published by the resolve launch.
 // What the host does for ONE pair after a pass, a single pair's and every pair's of a batch (pairs_loop): the
 // min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
 // its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
@@ -1895,8 +1898,8 @@ struct PairTrack {
     double s_acc = 1.0;   // similarity: the scale accumulated so far
     explicit PairTrack(const kss_icp_params& P) : cv(convergence_of(P)) { mat4_identity(fin); mat4_identity(tk); }
 };
-static int pair_ninfo(const PairMode& M) { return M.sim ? KSS_SIM_NINFO : M.unique ? KSS_O2O_NINFO : KSS_TRIM_NINFO; }
-static_assert(KSS_O2O_NINFO <= KSS_SIM_NINFO, "the loops' info arrays hold KSS_SIM_NINFO doubles");
+static int pair_ninfo(const PairMode& M) { return M.sim ? KSS_SIM_NINFO : M.mutual ? KSS_RECIP_NINFO : M.unique ? KSS_O2O_NINFO : KSS_TRIM_NINFO; }
+static_assert(KSS_O2O_NINFO <= KSS_SIM_NINFO && KSS_RECIP_NINFO <= KSS_SIM_NINFO, "the loops' info arrays hold KSS_SIM_NINFO doubles");
 static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const double* s, double* info, PairTrack& t, PairState& hs,
                            bool trace) {
     if (M.sim) { info[4] = 0.0; info[5] = t.s_acc; }
@@ -1946,15 +1949,17 @@ static int pair_pass_ensure(kss_ctx* c, const PairMode& M, int64_t n, bool have_
         KCHK(ensure(c, c->trim_state, TRIM_NSTATE * sizeof(TrimState)));
     }
     if (M.robust && M.rs.autoscale && (M.plane || !have_d2)) KCHK(ensure(c, c->rob_keys, (size_t)n * sizeof(float)));
-    return ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO + 1) * sizeof(double));
+    return ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO + 2) * sizeof(double));   // (+ m, or m and u)
 }
 
-// One pair: [one-to-one's three launches] [selection] [keys launch + the 0.5 selection] rows launch, final launch.  Rn: the
+// One pair: [one-to-one's three launches | reciprocal's five] [selection] [keys launch + the 0.5 selection] rows launch, final launch.  Rn: the
 // rotation the source normals turn with (generalized, symmetric); d_rec: the record, d_info: the selection's or the weights' four
 // slots, the one-to-one's m behind them (device or host-mapped).  One-to-one filters the context's p2l_idx / p2l_d2 (the NN
 // pass's own) into o2o_idx / o2o_d2, which a.s.idx / a.s.d2 then are.  The automatic scale's median key: the plane metrics write
-// their keys; a point-metric pass that carries d2 selects on it, one without d2 writes its keys first.
-static int pair_pass_launch(kss_ctx* c, const PairArgs& a, const PairMode& M, const GicpRot& Rn, double* d_rec, double* d_info) {
+// their keys; a point-metric pass that carries d2 selects on it, one without d2 writes its keys first.  Reciprocal filters the same
+// arrays against a.s's positions, the reverse distances by dist2<nn_fma>; m and u land behind the selection's record.
+static int pair_pass_launch(kss_ctx* c, const PairArgs& a, const PairMode& M, const GicpRot& Rn, double* d_rec, double* d_info,
+                            bool nn_fma = false) {
     ProfScope ps(c, KSS_K_CORR_REDUCE);
     const hipStream_t st = c->stream;
     const double max_d2 = a.s.max_d2;
@@ -1965,6 +1970,12 @@ static int pair_pass_launch(kss_ctx* c, const PairArgs& a, const PairMode& M, co
                             (unsigned long long*)c->o2o_table.p, (unsigned*)((unsigned long long*)c->o2o_table.p + a.nt),
                             (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + KSS_TRIM_NINFO};
         if (launch_o2o(st, nb, a.nt, 1, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
+    }
+    if (M.mutual) {   // reset, claim + count, scan, scatter, resolve + check
+        RecipArgs ra = {a.s, a.tgt, a.n, a.nt, c->recip_grid, c->o2o_table.p, (float4*)c->recip_sorted.p,
+                        (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + KSS_TRIM_NINFO};
+        ra.s.idx = (const int32_t*)c->p2l_idx.p; ra.s.d2 = (const float*)c->p2l_d2.p;
+        if (launch_recip(st, ra, nn_fma) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
     }
     if (M.trimmed) launch_trim_select(st, a.s.d2, a.n, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_info);
     const double* d_cut = M.trimmed ? &d_state[TRIM_NSTATE - 1].cut : nullptr;
@@ -2080,6 +2091,10 @@ static void pair_info_read(const PairMode& M, const double* h, int np, int p, do
     std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, KSS_TRIM_NINFO * sizeof(double));
     if (M.trimmed) info[3] = h[(size_t)p * P2L_NSUMS];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
     if (M.unique) info[4] = hinfo[(size_t)np * KSS_TRIM_NINFO + p];   // one-to-one: m, the candidates before the rejection ([0] is u)
+    if (M.mutual) {   // reciprocal (one pair): m and u ([0] is r)
+        info[4] = hinfo[KSS_TRIM_NINFO];
+        info[5] = hinfo[KSS_TRIM_NINFO + 1];
+    }
 }
 static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
                       const int32_t* d_perm, bool single, bool rob_select, kss_icp_result* results, double* info_all) {
@@ -2114,7 +2129,8 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     double* d_rec = (double*)c->h_p2l_dev;
     double* d_info = d_rec + (size_t)np * P2L_NSUMS;
     // one-to-one: the selection and the rows read the filtered copies; d_idx / d_d2 stay the NN pass's own
-    const PairSrc src = {nullptr, nullptr, d_perm, M.unique ? (const int32_t*)c->o2o_idx.p : d_idx, M.unique ? (const float*)c->o2o_d2.p : d_d2,
+    const bool filtered = M.unique || M.mutual;   // (reciprocal, DESIGN.md 2.25: the same hand-over)
+    const PairSrc src = {nullptr, nullptr, d_perm, filtered ? (const int32_t*)c->o2o_idx.p : d_idx, filtered ? (const float*)c->o2o_d2.p : d_d2,
                          M.d_src_nrm, max_d2};
     int64_t total_tgt = 0;
     int total_rows = 0;
@@ -2137,7 +2153,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
         if (single) {
             KCHK(nn_pass(c, *plan, P.nn_fma != 0, d_in, d_out, max_d2, d_idx, d_d2, false));
             const PairArgs a = {s, d_tgt, d_nrm, plan->g[0].ns, plan->g[0].nt, (double*)c->p2l_rows.p, (float*)c->rob_keys.p};
-            KCHK(pair_pass_launch(c, a, M, gicp_rot_of(hpass ? hpass[0].r : nullptr), d_rec, d_info));
+            KCHK(pair_pass_launch(c, a, M, gicp_rot_of(hpass ? hpass[0].r : nullptr), d_rec, d_info, P.nn_fma != 0));
         } else {
             {
                 DeferWait defer(c);
@@ -2221,6 +2237,9 @@ static int pair_mode_check(kss_ctx* c, const char* who, const PairMode& M, const
         return bad("symmetric ICP is the plane record with both clouds' normals, neither trimmed nor generalized");
     if (M.unique && (!M.trimmed || M.robust || M.gicp || M.symm || M.sim))
         return bad("one-to-one rejection is the trimmed pass's, neither robust, generalized, symmetric nor similarity");
+    if (M.mutual && (!M.trimmed || M.unique || M.robust || M.gicp || M.symm || M.sim))
+        return bad("reciprocal rejection is the trimmed pass's, neither one-to-one, robust, generalized, symmetric nor similarity");
+    if (M.mutual && batch) return bad("reciprocal rejection for many pairs per call is not built (kss_icp_recip_batch is the follow-up)");
     if (!batch) return KSS_OK;
     if (M.robust && !rscales) return bad("robust needs the per-pair scales");
     if (M.gicp && !gicp_eps) return bad("generalized ICP needs the per-pair epsilons");
@@ -2264,6 +2283,24 @@ static int pair_run_loop(kss_ctx* c, const IcpPlan& pl, std::chrono::steady_cloc
     return rc;
 }
 
+// reciprocal, once per call: the bounding box of the nt packed float triples d_tgt (a launch, a copy of at most
+// RECIP_BOX_BLOCKS partials and ONE synchronisation), the cell grid for n sources over it into c->recip_grid, the workspace and
+// the cell-ordered source array
+static int recip_setup(kss_ctx* c, const float* d_tgt, int64_t nt, int64_t n) {
+    KCHK(ensure(c, c->recip_box, (size_t)RECIP_BOX_BLOCKS * 6 * sizeof(float)));
+    const int nb = launch_recip_bbox(c->stream, d_tgt, nt, (float*)c->recip_box.p);
+    HIPCHK(c, hipGetLastError());
+    std::vector<float> hb((size_t)nb * 6);
+    HIPCHK(c, hipMemcpyAsync(hb.data(), c->recip_box.p, hb.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int b = 0; b < nb; ++b)
+        for (int k = 0; k < 3; ++k) { mn[k] = std::fmin(mn[k], hb[(size_t)b * 6 + k]); mx[k] = std::fmax(mx[k], hb[(size_t)b * 6 + 3 + k]); }
+    c->recip_grid = recip_grid_of(mn, mx, n);
+    KCHK(ensure(c, c->o2o_table, recip_work_bytes(nt, recip_cells(c->recip_grid))));
+    return ensure(c, c->recip_sorted, (size_t)n * sizeof(float4));
+}
+
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                  const kss_icp_params* p, const PairMode& M, kss_icp_result* res) {
     KCHK(pair_mode_check(c, "pair_run", M, d_nrm));
@@ -2286,6 +2323,11 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
         PairbDesc d;
         d.src_base = 0; d.ns = ns; d.tgt_off = 0; d.nt = nt; d.overlap = M.overlap; d.row_base = 0; d.nrows = stream_blocks(ns);
         KCHK(stage_pairb(c, std::vector<PairbDesc>(1, d), false));
+    }
+    if (M.mutual) {   // the filtered idx / d2, the cell grid over the target's box, the workspace and the cell-ordered sources
+        KCHK(ensure(c, c->o2o_idx, (size_t)ns * sizeof(int32_t)));
+        KCHK(ensure(c, c->o2o_d2, (size_t)ns * sizeof(float)));
+        KCHK(recip_setup(c, d_tgt, nt, ns));
     }
     const int64_t so[2] = {0, ns}, to[2] = {0, nt};
     KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));
@@ -2422,6 +2464,23 @@ int o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, const in
     HIPCHK(c, hipMemcpyAsync(cnt.data(), d_counters, cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t q = 0; q < cnt.size(); ++q) info_all[q] = (double)(cnt[q] + 1u);
+    return KSS_OK;
+}
+
+// the reciprocal filter alone (kss_recip_filter_dev): the loop's setup and five launches on packed float triples, then the three
+// counters read back (each holds its count minus one)
+int recip_filter_dev(kss_ctx* c, const float* d_src, int64_t n, const float* d_tgt, int64_t nt, const int32_t* d_idx, const float* d_d2,
+                     double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out, double* info) {
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(recip_setup(c, d_tgt, nt, n));
+    const RecipArgs ra = {{d_src, nullptr, nullptr, d_idx, d_d2, nullptr, max_d2}, d_tgt, n, nt, c->recip_grid, c->o2o_table.p,
+                          (float4*)c->recip_sorted.p, d_idx_out, d_d2_out, nullptr};
+    if (launch_recip(c->stream, ra, nn_fma) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
+    HIPCHK(c, hipGetLastError());
+    unsigned cnt[3];
+    HIPCHK(c, hipMemcpyAsync(cnt, recip_counters(c->o2o_table.p, nt), sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int q = 0; q < 3; ++q) info[q] = (double)(cnt[q] + 1u);
     return KSS_OK;
 }
 

@@ -470,6 +470,38 @@ size_t o2o_table_bytes(int64_t total_tgt, int npairs);
 // table reset, claim, resolve: three launches for total_rows = the sum of the pairs' nrows workgroups.  0, or the hipError_t of the reset.
 int launch_o2o(hipStream_t st, int total_rows, int64_t total_tgt, int npairs, const O2oArgs& a);
 
+// ---- reciprocal rejection (kss_recip.hip) ----
+// The uniform cell grid the moving sources are binned into every pass: fixed on the host once per call from the target's bounding
+// box (recip_grid_of); a coordinate's cell is clamp(floor((v - o) * inv_h), 0, g - 1) per axis, x fastest in the linear index.
+struct RecipGrid {
+    float ox, oy, oz, inv_h;
+    int32_t gx, gy, gz;
+};
+constexpr int RECIP_BOX_BLOCKS = 256;   // recip_bbox partials at most: 6 floats {min xyz, max xyz} each
+// The filter's arguments, by value.  s: the sources' CURRENT positions (src3, or src4 with perm: pair_walk's three forms) and the
+// NN pass's idx / d2 by original source index; tgt: nt packed float triples; work: recip_work_bytes(nt, cells) of workspace --
+// the claim table (nt uint64), four uint32 counters {m, u, r, unused}, each MINUS ONE, and one uint32 per cell -- set to all
+// ones before every pass; sorted: n float4 {x, y, z, bits(original index)} in cell order; idx_out / d2_out: the filtered arrays
+// (either may be null, either may be its input); info_mu: two doubles {m, u} (device or host-mapped, may be null).
+struct RecipArgs {
+    PairSrc s;
+    const float* tgt;
+    int64_t n, nt;
+    RecipGrid g;
+    void* work; float4* sorted;
+    int32_t* idx_out; float* d2_out;
+    double* info_mu;
+};
+__host__ __device__ inline int64_t recip_cells(const RecipGrid& g) { return (int64_t)g.gx * g.gy * g.gz; }
+size_t recip_work_bytes(int64_t nt, int64_t cells);
+__host__ __device__ inline unsigned* recip_counters(void* work, int64_t nt) { return (unsigned*)((unsigned long long*)work + nt); }
+// partial bounding boxes of nt packed float triples: returns the number of partials written to d_box (<= RECIP_BOX_BLOCKS)
+int launch_recip_bbox(hipStream_t st, const float* d_tgt, int64_t nt, float* d_box);
+// the grid for n sources over the box [mn, mx] (a box that is not finite, or a point: one cell)
+RecipGrid recip_grid_of(const float mn[3], const float mx[3], int64_t n);
+// reset, claim + count, scan, scatter, resolve + check: five launches.  0, or the hipError_t of the reset.
+int launch_recip(hipStream_t st, const RecipArgs& a, bool nn_fma);
+
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,
                 const std::function<void*(size_t)>& scratch);
