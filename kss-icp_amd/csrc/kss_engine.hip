@@ -16,7 +16,6 @@
 namespace kss {
 
 static int restore_zero_at_rest(kss_ctx* c);
-static bool resident_gate_available(kss_ctx* c, int npairs);
 
 // Workgroups of ONE launch that are certainly on the chip at the same time: one per compute unit of THIS device (the fused
 // single-pair kernels need at most one CU's registers and LDS each).  Chained launches and the batches whose reducers wait
@@ -97,15 +96,14 @@ static int build_plan(kss_ctx* c, const int64_t* ns, const int64_t* nt, int npai
     if (nn_mode == KSS_NN_AUTO) nn_mode = c->nn_mode;
     // AUTO: the fused cell-list pass (one launch + a spin per iteration) beats sweep + reduce + finalize (three launches)
     // down to a few hundred points (1.4k x 1.4k: 22 vs 36 us per iteration); below that the build (~0.1 ms) is not paid
-    // back.  KSS_GRID_MIN_* : tuning hooks.  Pairs sharing one target (the candidate batch of kss_register, badly posed
-    // by construction) stay on the brute-force engine.
-    static const int64_t min_nt = [] { const char* e = getenv("KSS_GRID_MIN_NT"); return e ? (int64_t)atoll(e) : (int64_t)512; }();
-    static const int64_t min_ns = [] { const char* e = getenv("KSS_GRID_MIN_NS"); return e ? (int64_t)atoll(e) : (int64_t)512; }();
+    // back.
+    constexpr int64_t min_nt = 512, min_ns = 512;
     pl.grid = nn_mode == KSS_NN_GRID || (nn_mode == KSS_NN_AUTO && npairs == 1 && nt[0] >= min_nt && ns[0] >= min_ns);
     if (npairs != 1) pl.grid = false;
-    // (Pairs sharing ONE target -- the candidate batch of kss_register -- stay on the brute-force engine: measured this round
+    // (Pairs sharing ONE target -- the candidate batch of kss_register -- stay on the brute-force engine: measured
     // on the fused batch kernel too, 14 candidates x 1406 points: the candidates start from local minima of the rotation
-    // search, a few percent of their sources need the in-wave fallback EVERY pass, 123 us per pass against 25 us: 14.3 vs 4.5 ms.)
+    // search, a few percent of their sources need the in-wave fallback EVERY pass, 123 us per pass against 25 us: 14.3 vs 4.5 ms.
+    // On the pair-resident engine, 1406 searches per pass on ONE compute unit: kss_register 24.3 ms against 4.5 ms.)
     if (npairs > 1 && !shared_target) {
         // batch: one cell list per pair.  Measured against the brute-force batch (tools/batch_small.py): brute force wins
         // at 16 pairs x 600 points, they tie at 4 x 1500, the cell lists win from 16 x 1500 and 8 x 4000 up; badly posed
@@ -113,18 +111,6 @@ static int build_plan(kss_ctx* c, const int64_t* ns, const int64_t* nt, int npai
         int64_t least_nt = nt[0], tot_ns = 0;
         for (int p = 0; p < npairs; ++p) { least_nt = std::min(least_nt, nt[p]); tot_ns += ns[p]; }
         pl.gridb = nn_mode == KSS_NN_GRID || (nn_mode == KSS_NN_AUTO && least_nt >= 2 * min_nt && tot_ns >= 32 * min_ns);
-    }
-    if (npairs > 1 && shared_target && nn_mode != KSS_NN_BRUTE) {
-        // Pairs sharing ONE target (the candidate batch of kss_register) on the pair-resident engine -- every candidate a workgroup
-        // of its own with the (small) target in LDS, no lockstep between candidates -- was built and measured in round 3: Bunny,
-        // 14 candidates x 1406 points: kss_register 24.3 ms against 4.5 ms on the brute-force engine.  The candidates start from
-        // local minima of the rotation search and move far in every pass: nearly every source searches in every pass, and 1406
-        // cell-list searches on ONE compute unit (50-100 us) lose to the tiled sweep of the same candidate spread over the chip
-        // (25 us).  KSS_RESIDENT_SHARED=1 runs it anyway (A/B; same results).
-        static const bool want_res = getenv("KSS_RESIDENT_SHARED") != nullptr && atoi(getenv("KSS_RESIDENT_SHARED")) != 0;
-        bool fits = want_res && nt[0] >= 64 && nt[0] <= 12000;
-        for (int p = 0; p < npairs; ++p) fits = fits && ns[p] <= (int64_t)RES_SMAX * RES_THREADS;
-        pl.gridb = fits && resident_gate_available(c, npairs);
     }
     const bool any_grid = pl.grid || pl.gridb;
     pl.src_in_cell_order = any_grid;
@@ -345,7 +331,6 @@ static void choose_cells(const float mn[3], const float mx[3], int64_t nt, GridP
     const float mag = std::max(std::max(std::fabs(mn[0]), std::fabs(mx[0])), std::max(std::max(std::fabs(mn[1]), std::fabs(mx[1])), std::max(std::fabs(mn[2]), std::fabs(mx[2]))));
     gp.eps = 2e-6f * (mag + emax) + 1e-30f;
     gp.rcap = 4;   // shells before a query goes to the brute-force list (measured on badly initialised pairs: tools/hard_case.py)
-    if (const char* e = getenv("KSS_GRID_RCAP")) { const int v = atoi(e); if (v >= 1 && v <= 64) gp.rcap = v; }   // tuning hook
 }
 
 // Build the uniform cell list over the (single) target: bbox -> cell size -> counting sort.
@@ -480,13 +465,10 @@ static int grid_setup_batch(kss_ctx* c, IcpPlan& pl) {
     KCHK(ensure(c, c->g_nnst, (size_t)pl.total_src * sizeof(float2)));
     KCHK(ensure(c, c->g_rowpair, pl.row_pair.size() * sizeof(int32_t)));
     HIPCHK(c, hipMemcpyAsync(c->g_rowpair.p, pl.row_pair.data(), pl.row_pair.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    static const bool no_lds = getenv("KSS_GRIDB_NOLDS") != nullptr;   // A/B switch: always the global-atomic build
     bool half = true;   // 16-bit counters: counts and in-pair positions of every pair fit
     for (int p = 0; p < np; ++p) half = half && pl.g[p].nt < 65536 && pl.g[p].ns < 65536;
-    static const bool no_half = getenv("KSS_GRIDB_NOHALF") != nullptr;   // A/B switch: 32-bit counters
-    if (no_half) half = false;
     // every pair's counters fit a CU's LDS: one workgroup per pair builds both of its lists (kss_grid.hip)
-    const bool built_in_lds = most_cells <= gridb_lds_max_cells(half) && !no_lds &&
+    const bool built_in_lds = most_cells <= gridb_lds_max_cells(half) &&
         launch_gridb_build_lds(c->stream, (const float4*)c->tgt4.p, (float4*)c->src0.p, (float4*)c->cur[0].p, (const GridPairDev*)c->g_pairs.p, np,
                                (int32_t*)c->g_start.p + 1, (float4*)c->g_sorted.p, (int)most_cells, half);
     if (!built_in_lds) {
@@ -725,6 +707,16 @@ struct GatedGuard {   // no exit from the ICP loop leaves a gate closed
     ~GatedGuard() { gated_cancel(c); c->gated.want_next = false; }
 };
 
+// settings two engines share, each read once (at its first use)
+static float skin_setting() {   // KSS_SKIN=-1: every source searches in every pass
+    static const float skin = getenv("KSS_SKIN") ? (float)atof(getenv("KSS_SKIN")) : 0.25f;
+    return skin;
+}
+static int gate_polls_setting() {   // bound of a waiting kernel's poll (~1 us each)
+    static const int gate_polls = getenv("KSS_GATE_POLLS") ? atoi(getenv("KSS_GATE_POLLS")) : (1 << 22);
+    return gate_polls;
+}
+
 // arguments of the fused cell-list pass for this plan (single pair or batch)
 static PassArgs pass_args(kss_ctx* c, const IcpPlan& pl, const float4* d_in, float4* d_out, double max_d2,
                           int32_t* d_idx_out, float* d_d2_out) {
@@ -736,18 +728,15 @@ static PassArgs pass_args(kss_ctx* c, const IcpPlan& pl, const float4* d_in, flo
     a.tgt4 = (const float4*)c->tgt4.p;
     a.nn_win = (float4*)c->g_pos.p;
     a.nn_state = (float2*)c->g_nnst.p;
-    static const float skin = getenv("KSS_SKIN") ? (float)atof(getenv("KSS_SKIN")) : 0.25f;   // KSS_SKIN=-1: every source searches in every pass
-    a.skin = skin;
+    a.skin = skin_setting();
     a.chain_len = 1;
-    static const int gate_polls = getenv("KSS_GATE_POLLS") ? atoi(getenv("KSS_GATE_POLLS")) : (1 << 22);   // bound of a waiting kernel's poll (~1 us each)
-    a.gate_polls = gate_polls;
+    a.gate_polls = gate_polls_setting();
     a.chained = d_in != (const float4*)c->src0.p ? 1 : c->fit_last ? 2 : 0;   // (the first pass and the fitness pass read the original cloud)
     a.src_last0 = (const float4*)c->cur[0].p; a.src_last1 = (const float4*)c->cur[1].p;
     a.keys = (unsigned long long*)c->keys.p;
     a.list = (int32_t*)c->g_list.p; a.list_count = (int32_t*)c->g_count.p;
     a.total_rows = pl.total_rows;
-    static const bool noprev = getenv("KSS_GRID_NOPREV") != nullptr;   // A/B switch: the previous winner is stored but not used as a bound
-    a.use_prev = !noprev && c->nn_have ? 1 : 0;   // (nn_have: a search pass of this registration has written the per-source state)
+    a.use_prev = c->nn_have ? 1 : 0;   // (nn_have: a search pass of this registration has written the per-source state)
     a.max_d2 = max_d2;
     a.rows = (Granule*)c->partials.p;
     a.pub = c->h_seq_dev;
@@ -769,230 +758,267 @@ static PassArgs pass_args(kss_ctx* c, const IcpPlan& pl, const float4* d_in, flo
     return a;
 }
 
-// One NN pass (search + correspondence sums) over every active pair.  h_sums receives npairs*NSUMS.
-// full: all 20 sums (the fitness / PCR_QM pass, traced runs); otherwise slots 17 and 18 stay 0 (an ICP iteration never
-// reads them: one f64 sqrt per source and two reduction columns less).  active: which pairs take part (null: all).
-static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, float4* d_out, double max_d2,
-            int32_t* d_idx_out, float* d_d2_out, bool full, const int* active = nullptr) {
+// ---- the fused single pair's pass (pl.grid): the gated chain as five steps, in this order ----
+// what the steps hand on: the pass as nn_pass was asked for it, the plain launch's arguments, which launch is waited for
+struct GridPass {
+    const IcpPlan& pl;
+    bool fma, full;
+    const float4* d_in; float4* d_out;
+    double max_d2;
+    int32_t* d_idx_out; float* d_d2_out;
+    PassArgs a;                               // the pass as a plain launch
+    int nblk;
+    unsigned long long* stamps2 = nullptr;    // KSS_GRID_STAMPS=2: two buffers that alternate with the launch's sequence number
+    bool plain_args = false;                  // nothing a pre-enqueued launch could not have been given
+    unsigned long long want_seq = 0;          // the launch whose sums this pass waits for
+    bool via_gate = false;                    // ... was enqueued earlier and released by step 1
+};
+
+// search + correspondence sums + final reduction in ONE launch; sums land in host-mapped memory
+static void grid_launch_plain(kss_ctx* c, GridPass& g) {
+    ProfScope ps(c, KSS_K_GRID_NN);
+    g.a.ps0 = ((const PairState*)c->h_state)[0];
+    g.a.seq = ++c->seq;
+    if (g.stamps2) g.a.stamps = g.stamps2 + (size_t)(g.a.seq & 1) * g.nblk * 16;
+    launch_grid_pass(c->stream, g.fma, g.full, false, true, g.a);
+    c->nn_have = true;
+    g.want_seq = c->seq;
+}
+
+// step 1: release the pending launch if it is this pass, or launch plain
+static void grid_release_or_launch(kss_ctx* c, GridPass& g) {
+    kss_ctx::Gated& G = c->gated;
+    if (G.pending && G.d_in == (const void*)g.d_in && G.d_out == (void*)g.d_out && G.fma == g.fma && G.full == g.full && G.max_d2 == g.max_d2 && g.plain_args) {
+        // this pass was enqueued while the previous one ran: hand it its transform and open the gate
+        g.want_seq = G.seq;
+        c->seq = std::max(c->seq, G.seq);   // (sequence numbers of a chain are taken as its passes are released)
+        if (G.chain && c->prof > 0) c->prof_n[KSS_K_GRID_CHAIN_PASS] += 1;
+        g.via_gate = true;
+        // (test hook: the n-th answer is never written -- a host thread that stalls for longer than the kernel's bounded
+        // poll.  The waiting kernel gives up at the gate, having touched nothing, and the pass is launched again by step 3.)
+        static const long drop_at = getenv("KSS_TEST_DROP_GATE") ? atol(getenv("KSS_TEST_DROP_GATE")) : -1;
+        static long releases = 0;
+        if (++releases == drop_at) { G.pending = false; G.steps_left = 0; }
+        else gated_release(c, ((const PairState*)c->h_state)[0], 0);
+    } else {
+        gated_cancel(c);   // (a pre-enqueued kernel that does not fit this pass, e.g. before the fitness pass)
+        grid_launch_plain(c, g);
+    }
+}
+
+// step 2: decide how many iterations the next pre-enqueued launch may run, and enqueue it behind the gate while this pass runs
+static void grid_enqueue_next(kss_ctx* c, const GridPass& g) {
+    kss_ctx::Gated& G = c->gated;
+    // HIP-event timing: a bracket behind the gate would also time the dispatch that follows the wait, so the launches
+    // the profiler samples (every n-th) are plain launches; the others advance its tick here
+    const bool next_sampled = c->prof == 1 || (c->prof > 1 && c->prof_tick[KSS_K_GRID_NN] % (unsigned)c->prof == 0);
+    // how many iterations a pre-enqueued launch may run: all that can still follow (KSS_CHAIN=0: one, the form of every
+    // system without a large BAR).  A single gated launch stays out of the way of the launches the profiler samples; a
+    // chain is bracketed as a whole instead.
+    static const bool want_chain = getenv("KSS_CHAIN") == nullptr || atoi(getenv("KSS_CHAIN")) != 0;
+    int len = 1;
+    if (G.want_next && !G.pending && g.plain_args && gated_available(c) && want_chain && c->gate_bar &&
+        (g.pl.total_rows <= resident_rows_limit(c) || g.pl.total_rows == 1))   // (every workgroup of a chain waits at its gates: resident at once)
+        len = std::max(1, std::min(G.max_steps, 1 << 16));
+    if (!(G.want_next && !G.pending && g.plain_args && gated_available(c) && (len > 1 || !next_sampled))) return;
+    if (c->prof > 1 && len == 1) ++c->prof_tick[KSS_K_GRID_NN];
+    // the NEXT iteration reads what this pass writes (d_out) and writes the other ping-pong buffer
+    float4* nxt_out = g.d_out == (float4*)c->cur[0].p ? (float4*)c->cur[1].p : (float4*)c->cur[0].p;
+    G.slot ^= 1;
+    G.stamp = (G.stamp + 1) & 0x7fffffff;
+    if (G.stamp == 0 || G.stamp > 0x7fffffff - len - 1) G.stamp = 1;   // (0 is what a fresh record holds; a chain's stamps do not wrap)
+    PassArgs n = pass_args(c, g.pl, g.d_out, nxt_out, g.max_d2, nullptr, nullptr);
+    n.ps0 = ((const PairState*)c->h_state)[0];
+    n.gate_seq = G.stamp;
+    if (c->gate_bar) {   // the host writes the granules itself
+        n.state = nullptr;
+        n.gate_dev = c->gate_bar;    // two records, 128 bytes apart: pass k of the launch polls record (slot + k) & 1
+        n.gate_slot = G.slot;
+        n.chain_len = len;
+        n.src_alt = g.d_out;
+    } else {             // workgroup 0 asks the host-mapped record and re-publishes
+        n.state = c->h_xf_dev + G.slot;
+        n.gate_dev = (unsigned int*)c->g_gate.p;
+    }
+    n.seq = c->seq + 1;          // (taken when the pass is released)
+    if (g.stamps2) n.stamps = g.stamps2 + (size_t)(n.seq & 1) * g.nblk * 16;
+    if (len > 1) {   // bracketed as a whole whenever profiling is on (KSS_K_GRID_CHAIN; per pass: KSS_K_GRID_CHAIN_PASS)
+        ProfScope ps(c, KSS_K_GRID_CHAIN, true);
+        launch_grid_pass(c->stream, g.fma, G.want_full, false, true, n);
+    } else {
+        launch_grid_pass(c->stream, g.fma, G.want_full, false, true, n);
+    }
+    G.chain = len > 1;
+    G.pending = true; G.steps_left = len; G.seq = n.seq; G.d_in = g.d_out; G.d_out = nxt_out; G.fma = g.fma; G.full = G.want_full; G.max_d2 = g.max_d2;
+    if (hipGetLastError() != hipSuccess) { gated_cancel(c); G.supported = 0; }   // (if it did get queued it is answered; gating is given up)
+}
+
+// step 3: wait for the pass's sums; a waiting kernel that left unanswered is launched again as a plain pass
+static int grid_wait(kss_ctx* c, GridPass& g) {
+    bool not_published = false;
+    const int rcw = wait_seq(c, 1, g.want_seq, nullptr, &not_published);
+    if (rcw == KSS_OK || !g.via_gate || !not_published) return rcw;
+    // The waiting kernel left at its gate (bounded poll: this thread was stalled, or the answer never arrived) and
+    // the stream has drained.  Nothing of this pass has been written: launch it as a plain pass.
+    c->gated.pending = false; c->gated.steps_left = 0;
+    c->err.clear();
+    std::fprintf(stderr, "[kss] a waiting kernel was not answered in time and left; the pass is launched again\n");
+    // With more rows than resident workgroups the launch may have left in part only: workgroups that started after
+    // the answer finally arrived have run, written their sources and may have put sources on the fallback list.
+    // The stream has drained (wait_seq synchronised): re-arm everything that is zero at rest before the plain launch.
+    c->ws_dirty = true;
+    KCHK(restore_zero_at_rest(c));
+    grid_launch_plain(c, g);
+    HIPCHK(c, hipGetLastError());
+    return wait_seq(c, 1, g.want_seq);
+}
+
+// step 4, and its arming ahead of step 1: diagnostic builds of the timeline (tools/grid_stamps.py).  KSS_GRID_STAMPS=1: plain
+// launches, buffer cleared and read back every pass.  =2: the gated chain as it runs in production; two buffers alternate with
+// the launch sequence number (the launch pre-enqueued behind the last real one is cancelled but has stamped its start) and
+// kss_debug_grid_stamps fetches the one of the last launch that was waited for.
+static int grid_stamps_arm(kss_ctx* c, GridPass& g) {
+    static const int stamps_mode = getenv("KSS_GRID_STAMPS") ? atoi(getenv("KSS_GRID_STAMPS")) : 0;
+    if (stamps_mode == 1) {
+        KCHK(ensure(c, c->g_stamps, (size_t)g.nblk * 16 * sizeof(unsigned long long)));
+        HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)g.nblk * 16 * sizeof(unsigned long long), c->stream));
+        g.a.stamps = (unsigned long long*)c->g_stamps.p;
+    } else if (stamps_mode == 2) {
+        KCHK(ensure(c, c->g_stamps, (size_t)g.nblk * 32 * sizeof(unsigned long long)));
+        g.stamps2 = (unsigned long long*)c->g_stamps.p;
+        c->stamps_nblk = g.nblk;
+    }
+    return KSS_OK;
+}
+static int grid_stamps_read(kss_ctx* c, const GridPass& g) {
+    if (g.stamps2) { c->stamps_seq = g.want_seq; return KSS_OK; }
+    if (!g.a.stamps) return KSS_OK;
+    c->last_stamps.resize((size_t)g.nblk * 16);
+    HIPCHK(c, hipMemcpy(c->last_stamps.data(), g.a.stamps, c->last_stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int b = 0; b < g.nblk; ++b) c->evals_sum += (double)c->last_stamps[(size_t)b * 16 + 10];
+    c->evals_launches += 1.0;
+    return KSS_OK;
+}
+
+// step 5: sources the cell search gave up on (far from the target): brute-force sweep over the list, then the sums
+// again by a SEARCH = false launch of the fused pass -- same rows, same order, so the result does not depend
+// on WHICH sources needed the list
+static int grid_list_fallback(kss_ctx* c, const GridPass& g) {
+    const IcpPlan& pl = g.pl;
+    gated_cancel(c);              // the list pass must not queue up behind a closed gate
+    c->gated.want_next = false;   // (clouds this far apart: plain launches until the loop says otherwise)
+    KCHK(stage_tables(c, pl));
+    {   // the list sweep reads the pair's device-side state (active, identity): uploaded here, on the rare path only
+        PairState one;
+        std::memset(&one, 0, sizeof one);
+        one.active = 1;
+        HIPCHK(c, hipMemcpy(c->state.p, &one, sizeof one, hipMemcpyHostToDevice));
+    }
+    if (getenv("KSS_LIST_CHECK")) {   // diagnostic: the list the search pass has left, checked on the host before it is used
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        int32_t cnt = -1;
+        HIPCHK(c, hipMemcpy(&cnt, c->g_count.p, sizeof cnt, hipMemcpyDeviceToHost));
+        const int64_t ns0 = pl.g[0].ns;
+        std::vector<int32_t> l((size_t)std::max<int64_t>(0, std::min<int64_t>(cnt, ns0)));
+        if (!l.empty()) HIPCHK(c, hipMemcpy(l.data(), c->g_list.p, l.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        int64_t bad = 0;
+        for (int32_t v : l) bad += v < 0 || v >= ns0;
+        std::fprintf(stderr, "[kss] list check: count %d of %lld sources (column 19 said %.0f), %lld entries out of range, nn table %zu items, S %d\n",
+                     cnt, (long long)ns0, ((const double*)c->h_sums)[NSUMS - 1], (long long)bad, pl.nn.size(), pl.S);
+        if (cnt < 0 || cnt > ns0 || bad) return set_err(c, KSS_ERR_HIP, "list check failed");
+    }
+    {
+        ProfScope ps(c, KSS_K_NN_SWEEP);
+        launch_nn_sweep_list(c->stream, pl.S, g.fma, (const NNWork*)c->nn_work.p, (int)pl.nn.size(), (const PairState*)c->state.p,
+                             g.d_out, (const float4*)c->tgt4.p, (unsigned long long*)c->keys.p, (const int32_t*)c->g_list.p,
+                             (const int32_t*)c->g_count.p);
+    }
+    HIPCHK(c, hipMemsetAsync(c->g_count.p, 0, sizeof(int32_t), c->stream));   // the list is consumed
+    {
+        ProfScope ps(c, KSS_K_CORR_REDUCE);
+        PassArgs r = pass_args(c, pl, g.d_in, g.d_out, g.max_d2, g.d_idx_out, g.d_d2_out);
+        r.ps0 = ((const PairState*)c->h_state)[0];
+        r.seq = ++c->seq;
+        launch_grid_pass(c->stream, g.fma, true, false, false, r);
+    }
+    HIPCHK(c, hipGetLastError());
+    return wait_seq(c, 1, c->seq);
+}
+
+// single pair on its cell list: the transform rides in the kernel arguments
+static int nn_pass_grid(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, float4* d_out, double max_d2,
+                        int32_t* d_idx_out, float* d_d2_out, bool full) {
+    GridPass g = {pl, fma, full, d_in, d_out, max_d2, d_idx_out, d_d2_out, pass_args(c, pl, d_in, d_out, max_d2, d_idx_out, d_d2_out),
+                  grid_pass_blocks(pl.total_rows)};
+    KCHK(grid_stamps_arm(c, g));
+    g.plain_args = !g.a.stamps && !d_idx_out && !d_d2_out;
+    const auto tl0 = c->timing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+    grid_release_or_launch(c, g);
+    HIPCHK(c, hipGetLastError());
+    grid_enqueue_next(c, g);
+    const auto tl1 = c->timing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+    KCHK(grid_wait(c, g));
+    if (c->timing) {
+        const auto tl2 = std::chrono::steady_clock::now();
+        c->t_launch_us += std::chrono::duration<double, std::micro>(tl1 - tl0).count();
+        c->t_wait_us += std::chrono::duration<double, std::micro>(tl2 - tl1).count();
+    }
+    KCHK(grid_stamps_read(c, g));
+    if (((const double*)c->h_sums)[NSUMS - 1] > 0.0) KCHK(grid_list_fallback(c, g));
+    ((double*)c->h_sums)[NSUMS - 1] = 0.0;
+    return KSS_OK;
+}
+
+// batched cell lists
+static int nn_pass_gridb(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, float4* d_out, double max_d2,
+                         int32_t* d_idx_out, float* d_d2_out, bool full, const int* active) {
     PairState* hs = (PairState*)c->h_state;
-    if (pl.grid) {
-        // single pair: the transform rides in the kernel arguments
-        PassArgs a = pass_args(c, pl, d_in, d_out, max_d2, d_idx_out, d_d2_out);
-        const int nblk = grid_pass_blocks(pl.total_rows);
-        // diagnostic builds of the timeline (tools/grid_stamps.py).  KSS_GRID_STAMPS=1: plain launches, buffer cleared and read
-        // back every pass.  =2: the gated chain as it runs in production; two buffers alternate with the launch sequence number
-        // (the launch pre-enqueued behind the last real one is cancelled but has stamped its start) and kss_debug_grid_stamps
-        // fetches the one of the last launch that was waited for.
-        static const int stamps_mode = getenv("KSS_GRID_STAMPS") ? atoi(getenv("KSS_GRID_STAMPS")) : 0;
-        unsigned long long* stamps2 = nullptr;
-        if (stamps_mode == 1) {
-            KCHK(ensure(c, c->g_stamps, (size_t)nblk * 16 * sizeof(unsigned long long)));
-            HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)nblk * 16 * sizeof(unsigned long long), c->stream));
-            a.stamps = (unsigned long long*)c->g_stamps.p;
-        } else if (stamps_mode == 2) {
-            KCHK(ensure(c, c->g_stamps, (size_t)nblk * 32 * sizeof(unsigned long long)));
-            stamps2 = (unsigned long long*)c->g_stamps.p;
-            c->stamps_nblk = nblk;
-        }
-        const auto tl0 = c->timing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-        unsigned long long want_seq = 0;
-        bool via_gate = false;
-        kss_ctx::Gated& G = c->gated;
-        const bool plain_args = !a.stamps && !d_idx_out && !d_d2_out;
-        if (G.pending && G.d_in == (const void*)d_in && G.d_out == (void*)d_out && G.fma == fma && G.full == full && G.max_d2 == max_d2 && plain_args) {
-            // this pass was enqueued while the previous one ran: hand it its transform and open the gate
-            want_seq = G.seq;
-            c->seq = std::max(c->seq, G.seq);   // (sequence numbers of a chain are taken as its passes are released)
-            if (G.chain && c->prof > 0) c->prof_n[KSS_K_GRID_CHAIN_PASS] += 1;
-            via_gate = true;
-            // (test hook: the n-th answer is never written -- a host thread that stalls for longer than the kernel's bounded
-            // poll.  The waiting kernel gives up at the gate, having touched nothing, and the pass is launched again below.)
-            static const long drop_at = getenv("KSS_TEST_DROP_GATE") ? atol(getenv("KSS_TEST_DROP_GATE")) : -1;
-            static long releases = 0;
-            if (++releases == drop_at) { G.pending = false; G.steps_left = 0; }
-            else gated_release(c, hs[0], 0);
-        } else {
-            gated_cancel(c);   // (a pre-enqueued kernel that does not fit this pass, e.g. before the fitness pass)
-            ProfScope ps(c, KSS_K_GRID_NN);
-            // search + correspondence sums + final reduction in ONE launch; sums land in host-mapped memory
-            a.ps0 = hs[0];
-            a.seq = ++c->seq;
-            if (stamps2) a.stamps = stamps2 + (size_t)(a.seq & 1) * nblk * 16;
-            launch_grid_pass(c->stream, fma, full, false, true, a);
-            c->nn_have = true;
-            want_seq = c->seq;
-        }
-        HIPCHK(c, hipGetLastError());
-        // HIP-event timing: a bracket behind the gate would also time the dispatch that follows the wait, so the launches
-        // the profiler samples (every n-th) are plain launches; the others advance its tick here
-        const bool next_sampled = c->prof == 1 || (c->prof > 1 && c->prof_tick[KSS_K_GRID_NN] % (unsigned)c->prof == 0);
-        // how many iterations a pre-enqueued launch may run: all that can still follow (KSS_CHAIN=0: one, the form of every
-        // system without a large BAR).  A single gated launch stays out of the way of the launches the profiler samples; a
-        // chain is bracketed as a whole instead.
-        static const bool want_chain = getenv("KSS_CHAIN") == nullptr || atoi(getenv("KSS_CHAIN")) != 0;
-        int len = 1;
-        if (G.want_next && !G.pending && plain_args && gated_available(c) && want_chain && c->gate_bar &&
-            (pl.total_rows <= resident_rows_limit(c) || pl.total_rows == 1))   // (every workgroup of a chain waits at its gates: resident at once)
-            len = std::max(1, std::min(G.max_steps, 1 << 16));
-        if (G.want_next && !G.pending && plain_args && gated_available(c) && (len > 1 || !next_sampled)) {
-            if (c->prof > 1 && len == 1) ++c->prof_tick[KSS_K_GRID_NN];
-            // enqueue the NEXT iteration behind the gate while this one runs: it reads what this pass writes (d_out) and
-            // writes the other ping-pong buffer
-            float4* nxt_out = d_out == (float4*)c->cur[0].p ? (float4*)c->cur[1].p : (float4*)c->cur[0].p;
-            G.slot ^= 1;
-            G.stamp = (G.stamp + 1) & 0x7fffffff;
-            if (G.stamp == 0 || G.stamp > 0x7fffffff - len - 1) G.stamp = 1;   // (0 is what a fresh record holds; a chain's stamps do not wrap)
-            PassArgs n = pass_args(c, pl, d_out, nxt_out, max_d2, nullptr, nullptr);
-            n.ps0 = hs[0];
-            n.gate_seq = G.stamp;
-            if (c->gate_bar) {   // the host writes the granules itself
-                n.state = nullptr;
-                n.gate_dev = c->gate_bar;    // two records, 128 bytes apart: pass k of the launch polls record (slot + k) & 1
-                n.gate_slot = G.slot;
-                n.chain_len = len;
-                n.src_alt = d_out;
-            } else {             // workgroup 0 asks the host-mapped record and re-publishes
-                n.state = c->h_xf_dev + G.slot;
-                n.gate_dev = (unsigned int*)c->g_gate.p;
-            }
-            n.seq = c->seq + 1;          // (taken when the pass is released)
-            if (stamps2) n.stamps = stamps2 + (size_t)(n.seq & 1) * nblk * 16;
-            if (len > 1) {   // bracketed as a whole whenever profiling is on (KSS_K_GRID_CHAIN; per pass: KSS_K_GRID_CHAIN_PASS)
-                ProfScope ps(c, KSS_K_GRID_CHAIN, true);
-                launch_grid_pass(c->stream, fma, G.want_full, false, true, n);
-            } else {
-                launch_grid_pass(c->stream, fma, G.want_full, false, true, n);
-            }
-            G.chain = len > 1;
-            G.pending = true; G.steps_left = len; G.seq = n.seq; G.d_in = d_out; G.d_out = nxt_out; G.fma = fma; G.full = G.want_full; G.max_d2 = max_d2;
-            if (hipGetLastError() != hipSuccess) { gated_cancel(c); G.supported = 0; }   // (if it did get queued it is answered; gating is given up)
-        }
-        const auto tl1 = c->timing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-        {
-            bool not_published = false;
-            int rcw = wait_seq(c, 1, want_seq, nullptr, &not_published);
-            if (rcw != KSS_OK && via_gate && not_published) {
-                // The waiting kernel left at its gate (bounded poll: this thread was stalled, or the answer never arrived) and
-                // the stream has drained.  Nothing of this pass has been written: launch it as a plain pass.
-                G.pending = false; G.steps_left = 0;
-                c->err.clear();
-                std::fprintf(stderr, "[kss] a waiting kernel was not answered in time and left; the pass is launched again\n");
-                // With more rows than resident workgroups the launch may have left in part only: workgroups that started after
-                // the answer finally arrived have run, written their sources and may have put sources on the fallback list.
-                // The stream has drained (wait_seq synchronised): re-arm everything that is zero at rest before the plain launch.
-                c->ws_dirty = true;
-                KCHK(restore_zero_at_rest(c));
-                ProfScope ps(c, KSS_K_GRID_NN);
-                a.ps0 = hs[0];
-                a.seq = ++c->seq;
-                launch_grid_pass(c->stream, fma, full, false, true, a);
-                HIPCHK(c, hipGetLastError());
-                want_seq = c->seq;
-                rcw = wait_seq(c, 1, want_seq);
-            }
-            KCHK(rcw);
-        }
-        if (stamps2) c->stamps_seq = want_seq;
-        if (c->timing) {
-            const auto tl2 = std::chrono::steady_clock::now();
-            c->t_launch_us += std::chrono::duration<double, std::micro>(tl1 - tl0).count();
-            c->t_wait_us += std::chrono::duration<double, std::micro>(tl2 - tl1).count();
-        }
-        if (a.stamps && !stamps2) {
-            c->last_stamps.resize((size_t)nblk * 16);
-            HIPCHK(c, hipMemcpy(c->last_stamps.data(), a.stamps, c->last_stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            for (int b = 0; b < nblk; ++b) c->evals_sum += (double)c->last_stamps[(size_t)b * 16 + 10];
-            c->evals_launches += 1.0;
-        }
-        if (((const double*)c->h_sums)[NSUMS - 1] > 0.0) {
-            // sources the cell search gave up on (far from the target): brute-force sweep over the list, then the sums
-            // again by a SEARCH = false launch of the fused pass -- same rows, same order, so the result does not depend
-            // on WHICH sources needed the list
-            gated_cancel(c);              // the list pass must not queue up behind a closed gate
-            c->gated.want_next = false;   // (clouds this far apart: plain launches until the loop says otherwise)
-            KCHK(stage_tables(c, pl));
-            {   // the list sweep reads the pair's device-side state (active, identity): uploaded here, on the rare path only
-                PairState one;
-                std::memset(&one, 0, sizeof one);
-                one.active = 1;
-                HIPCHK(c, hipMemcpy(c->state.p, &one, sizeof one, hipMemcpyHostToDevice));
-            }
-            if (getenv("KSS_LIST_CHECK")) {   // diagnostic: the list the search pass has left, checked on the host before it is used
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                int32_t cnt = -1;
-                HIPCHK(c, hipMemcpy(&cnt, c->g_count.p, sizeof cnt, hipMemcpyDeviceToHost));
-                const int64_t ns0 = pl.g[0].ns;
-                std::vector<int32_t> l((size_t)std::max<int64_t>(0, std::min<int64_t>(cnt, ns0)));
-                if (!l.empty()) HIPCHK(c, hipMemcpy(l.data(), c->g_list.p, l.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-                int64_t bad = 0;
-                for (int32_t v : l) bad += v < 0 || v >= ns0;
-                std::fprintf(stderr, "[kss] list check: count %d of %lld sources (column 19 said %.0f), %lld entries out of range, nn table %zu items, S %d\n",
-                             cnt, (long long)ns0, ((const double*)c->h_sums)[NSUMS - 1], (long long)bad, pl.nn.size(), pl.S);
-                if (cnt < 0 || cnt > ns0 || bad) return set_err(c, KSS_ERR_HIP, "list check failed");
-            }
-            {
-                ProfScope ps(c, KSS_K_NN_SWEEP);
-                launch_nn_sweep_list(c->stream, pl.S, fma, (const NNWork*)c->nn_work.p, (int)pl.nn.size(), (const PairState*)c->state.p,
-                                     d_out, (const float4*)c->tgt4.p, (unsigned long long*)c->keys.p, (const int32_t*)c->g_list.p,
-                                     (const int32_t*)c->g_count.p);
-            }
-            HIPCHK(c, hipMemsetAsync(c->g_count.p, 0, sizeof(int32_t), c->stream));   // the list is consumed
-            {
-                ProfScope ps(c, KSS_K_CORR_REDUCE);
-                PassArgs r = pass_args(c, pl, d_in, d_out, max_d2, d_idx_out, d_d2_out);
-                r.ps0 = hs[0];
-                r.seq = ++c->seq;
-                launch_grid_pass(c->stream, fma, true, false, false, r);
-            }
-            HIPCHK(c, hipGetLastError());
-            KCHK(wait_seq(c, 1, c->seq));
-        }
-        ((double*)c->h_sums)[NSUMS - 1] = 0.0;
-        return KSS_OK;
+    // batch: one launch searches every active pair; each pair's sums are published as soon as its rows are added up --
+    // inside the launch by the pair's first workgroup, or, with more pairs than compute units, by the finalize launch
+    // right after it (then every pair lands only once the whole pass is done).
+    // The per-pair states (transform to apply, active flag) are read by every workgroup: a small batch reads them
+    // straight from the pinned host-mapped table (no copy operation on the stream), a large one (thousands of
+    // workgroups) gets the table copied to device memory once per pass.
+    PassArgs a = pass_args(c, pl, d_in, d_out, max_d2, d_idx_out, d_d2_out);
+    a.state = (const PairState*)c->state.p;
+    if (c->bar_state && c->bar_state_cap >= pl.npairs) {   // the host has stored the states there itself (mirror_state)
+        _mm_sfence();
+        a.state = c->bar_state;
     }
-    if (pl.gridb) {
-        // batch: one launch searches every active pair; each pair's sums are published as soon as its rows are added up --
-        // inside the launch by the pair's first workgroup, or, with more pairs than compute units, by the finalize launch
-        // right after it (then every pair lands only once the whole pass is done).
-        // The per-pair states (transform to apply, active flag) are read by every workgroup: a small batch reads them
-        // straight from the pinned host-mapped table (no copy operation on the stream), a large one (thousands of
-        // workgroups) gets the table copied to device memory once per pass.
-        PassArgs a = pass_args(c, pl, d_in, d_out, max_d2, d_idx_out, d_d2_out);
-        a.state = (const PairState*)c->state.p;
-        if (c->bar_state && c->bar_state_cap >= pl.npairs) {   // the host has stored the states there itself (mirror_state)
-            _mm_sfence();
-            a.state = c->bar_state;
-        }
-        static const int host_state_rows = [] { const char* e = getenv("KSS_BATCH_HOST_STATE_ROWS"); return e ? atoi(e) : 32768; }();   // tuning hook (measured at C3, 20480 workgroups: 9.71 ms from host memory vs 9.85 ms with the copy)
-        if (a.state != c->bar_state && pl.total_rows <= host_state_rows) {
-            void* dev = nullptr;
-            if (hipHostGetDevicePointer(&dev, c->h_state, 0) == hipSuccess && dev) a.state = (const PairState*)dev;
-        }
-        if (a.state == (const PairState*)c->state.p)
-            HIPCHK(c, hipMemcpyAsync(c->state.p, hs, (size_t)pl.npairs * sizeof(PairState), hipMemcpyHostToDevice, c->stream));
-        c->last_state_dev = a.state;
-        const int nblk = grid_pass_blocks(pl.total_rows);
-        if (getenv("KSS_GRID_STAMPS")) {   // diagnostic build of the timeline (tools/batch_stamps.py)
-            KCHK(ensure(c, c->g_stamps, (size_t)nblk * 16 * sizeof(unsigned long long)));
-            HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)nblk * 16 * sizeof(unsigned long long), c->stream));
-            a.stamps = (unsigned long long*)c->g_stamps.p;
-        }
-        {
-            ProfScope ps(c, KSS_K_GRID_NN);
-            a.seq = ++c->seq;
-            launch_grid_pass(c->stream, fma, full, true, true, a);
-            c->nn_have = true;
-        }
-        HIPCHK(c, hipGetLastError());
-        if (a.stamps) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));   // (the stream does not synchronise with the null stream)
-            c->last_stamps.resize((size_t)nblk * 16);
-            HIPCHK(c, hipMemcpy(c->last_stamps.data(), a.stamps, c->last_stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        }
-        if (!c->defer_wait) KCHK(wait_seq(c, pl.npairs, c->seq, active));
-        return KSS_OK;
+    constexpr int host_state_rows = 32768;   // (measured at C3, 20480 workgroups: 9.71 ms from host memory vs 9.85 ms with the copy)
+    if (a.state != c->bar_state && pl.total_rows <= host_state_rows) {
+        void* dev = nullptr;
+        if (hipHostGetDevicePointer(&dev, c->h_state, 0) == hipSuccess && dev) a.state = (const PairState*)dev;
     }
-    // brute-force engine.  Per-pair states as above.
+    if (a.state == (const PairState*)c->state.p)
+        HIPCHK(c, hipMemcpyAsync(c->state.p, hs, (size_t)pl.npairs * sizeof(PairState), hipMemcpyHostToDevice, c->stream));
+    c->last_state_dev = a.state;
+    const int nblk = grid_pass_blocks(pl.total_rows);
+    if (getenv("KSS_GRID_STAMPS")) {   // diagnostic build of the timeline (tools/batch_stamps.py)
+        KCHK(ensure(c, c->g_stamps, (size_t)nblk * 16 * sizeof(unsigned long long)));
+        HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)nblk * 16 * sizeof(unsigned long long), c->stream));
+        a.stamps = (unsigned long long*)c->g_stamps.p;
+    }
+    {
+        ProfScope ps(c, KSS_K_GRID_NN);
+        a.seq = ++c->seq;
+        launch_grid_pass(c->stream, fma, full, true, true, a);
+        c->nn_have = true;
+    }
+    HIPCHK(c, hipGetLastError());
+    if (a.stamps) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (the stream does not synchronise with the null stream)
+        c->last_stamps.resize((size_t)nblk * 16);
+        HIPCHK(c, hipMemcpy(c->last_stamps.data(), a.stamps, c->last_stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+    if (!c->defer_wait) KCHK(wait_seq(c, pl.npairs, c->seq, active));
+    return KSS_OK;
+}
+
+// brute-force engine.  Per-pair states as above.
+static int nn_pass_brute(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, float4* d_out, double max_d2,
+                         int32_t* d_idx_out, float* d_d2_out, const int* active) {
+    PairState* hs = (PairState*)c->h_state;
     const PairState* d_state = (const PairState*)c->state.p;
     if (pl.npairs <= PUB_PAIRS) {
         void* dev = nullptr;
@@ -1050,6 +1076,16 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
     if (spin) KCHK(wait_seq(c, pl.npairs));
     else HIPCHK(c, hipStreamSynchronize(c->stream));
     return KSS_OK;
+}
+
+// One NN pass (search + correspondence sums) over every active pair.  h_sums receives npairs*NSUMS.
+// full: all 20 sums (the fitness / PCR_QM pass, traced runs); otherwise slots 17 and 18 stay 0 (an ICP iteration never
+// reads them: one f64 sqrt per source and two reduction columns less).  active: which pairs take part (null: all).
+static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, float4* d_out, double max_d2,
+            int32_t* d_idx_out, float* d_d2_out, bool full, const int* active = nullptr) {
+    if (pl.grid) return nn_pass_grid(c, pl, fma, d_in, d_out, max_d2, d_idx_out, d_d2_out, full);
+    if (pl.gridb) return nn_pass_gridb(c, pl, fma, d_in, d_out, max_d2, d_idx_out, d_d2_out, full, active);
+    return nn_pass_brute(c, pl, fma, d_in, d_out, max_d2, d_idx_out, d_d2_out, active);
 }
 
 // the batched pass's per-pair state table in fine-grained device memory the host can store into (null: no large BAR)
@@ -1111,23 +1147,70 @@ static inline void fill_result(kss_icp_result& r, const float fin[16], int itera
     r.iterations = iterations; r.converged = converged; r.state = state;
     r.last_mse = last_mse; r.fitness = fitness; r.pair_id = pair;
 }
+// What the host does for ONE pair after a pass, in every loop below (icp_loop, resident_loop, pairs_loop): the
+// min_correspondences test, the solve by metric (a default PairMode: the plain point metric, info unused), final <- T_k * final,
+// the MSE and PCL's criteria.  s: the pass's record, info: its {m, k, tau, kept} (trimmed).  True: the pair goes on, t.tk is what
+// the next NN pass applies on load; false: it has ended (state / converged say how).  What the engine is told is the caller's.
+// trace: the pair whose passes the caller's trace receives (pair 0).
+struct PairTrack {
+    Convergence cv;
+    float fin[16], tk[16];
+    int iters = 0, state = KSS_STATE_NOT_CONVERGED, converged = 0;
+    double last_mse = 0.0;
+    double s_acc = 1.0;   // similarity: the scale accumulated so far
+    explicit PairTrack(const kss_icp_params& P) : cv(convergence_of(P)) { mat4_identity(fin); mat4_identity(tk); }
+};
+static int pair_ninfo(const PairMode& M) { return M.sim ? KSS_SIM_NINFO : M.mutual ? KSS_RECIP_NINFO : M.unique ? KSS_O2O_NINFO : KSS_TRIM_NINFO; }
+static_assert(KSS_O2O_NINFO <= KSS_SIM_NINFO && KSS_RECIP_NINFO <= KSS_SIM_NINFO, "the loops' info arrays hold KSS_SIM_NINFO doubles");
+static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const double* s, double* info, PairTrack& t, bool trace) {
+    if (M.sim) { info[4] = 0.0; info[5] = t.s_acc; }
+    // PCL: "Not enough correspondences found" (robust: the count kept, [0] being the weight total)
+    const double cnt = M.robust ? s[(M.plane ? P2L_NSUMS : NSUMS) - 1] : s[0];
+    if ((int)cnt < P.min_correspondences) { t.state = KSS_STATE_NO_CORRESPONDENCES; return false; }
+    float ck[16];                 // similarity: the step without its scale, what the criteria read
+    const float* crit = t.tk;
+    double scale_dev2 = 0.0;
+    if (M.symm) {
+        if (!rigid_from_symm_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
+    } else if (M.plane) {
+        if (!rigid_from_p2l_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
+    } else if (M.sim) {
+        double sk;
+        if (!sim_from_sums(s, M.scale_min / t.s_acc, M.scale_max / t.s_acc, t.tk, &sk, ck)) { t.state = KSS_STATE_DEGENERATE; return false; }
+        t.s_acc = std::fmin(std::fmax(t.s_acc * sk, M.scale_min), M.scale_max);
+        info[4] = sk; info[5] = t.s_acc;
+        scale_dev2 = (sk - 1.0) * (sk - 1.0);
+        crit = ck;
+    } else {
+        rigid_from_sums(s, t.tk);
+    }
+    mat4_mul(t.tk, t.fin, t.fin);   // final = transformation_ * final
+    ++t.iters;
+    const double mse = (M.plane ? s[28] : s[16]) / s[0];   // point-to-point d2 of the kept correspondences, as PCL's criteria read it
+    t.last_mse = mse;
+    if (trace) trace_row(P, s, M.plane ? P2L_NSUMS : NSUMS, t.tk, M.trimmed || M.robust ? M.trace_info : nullptr, info, pair_ninfo(M));
+    const bool done = t.cv.has_converged(t.iters, crit, mse, scale_dev2);
+    t.state = t.cv.state;
+    if (done) t.converged = 1;
+    return !done;
+}
 // getFitnessScore(): NN of final * ORIGINAL input, mean d2 over ALL source points of each pair, into results[p].fitness.
-// fin / iters / state: per pair, as the loop left them.  claim_last: the plan is the one every pass of the loop ran on.
+// tr: per pair, as the loop left it.  claim_last: the plan is the one every pass of the loop ran on.
 // d_idx / d_d2 (pl.total_src each; null: not wanted): the pass's correspondences by original source index, pair 0's copied to
 // P.fitness_idx / P.fitness_d2.
-static int fitness_pass(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, const float* fin, const int* iters, const int* state,
-                        bool claim_last, PairState* bar, int32_t* d_idx, float* d_d2, kss_icp_result* results) {
+static int fitness_pass(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, const PairTrack* tr, bool claim_last,
+                        PairState* bar, int32_t* d_idx, float* d_d2, kss_icp_result* results) {
     const int np = pl.npairs;
     PairState* hs = (PairState*)c->h_state;
     // (pad[0]: which work buffer holds the positions of the pair's last pass -- pass k writes cur[k & 1] -- so that the
     // cell-list pass can measure how far each source is from where its skip state was last brought up to date)
     const bool claim = claim_last && (pl.grid || pl.gridb);
     for (int p = 0; p < np; ++p) {
-        set_state(hs[p], fin + (size_t)p * 16, 1, 1);
+        set_state(hs[p], tr[p].fin, 1, 1);
         // (a pair that ended without correspondences, or on a singular system, took part in one more pass than it counted: its
         // last position is in the other buffer -- no claim is made for it, its sources simply search)
-        if (claim && iters[p] >= 1 && state[p] != KSS_STATE_NO_CORRESPONDENCES && state[p] != KSS_STATE_DEGENERATE)
-            hs[p].pad[0] = 1 + ((iters[p] - 1) & 1);
+        if (claim && tr[p].iters >= 1 && tr[p].state != KSS_STATE_NO_CORRESPONDENCES && tr[p].state != KSS_STATE_DEGENERATE)
+            hs[p].pad[0] = 1 + ((tr[p].iters - 1) & 1);
         mirror_state(bar, p, hs[p]);
     }
     c->fit_last = claim;
@@ -1201,8 +1284,6 @@ static unsigned int* resident_gate(kss_ctx* c, int npairs) {
     return c->res_gate;
 }
 
-static bool resident_gate_available(kss_ctx* c, int npairs) { return resident_gate(c, npairs) != nullptr; }
-
 // the 20 sums of pair p under sequence number `want`, if they have all landed
 static inline bool resident_collect(const unsigned long long* h_seq, int p, unsigned long long want, double* out) {
     const unsigned long long* sl = h_seq + (size_t)2 * NSUMS * p;
@@ -1228,6 +1309,141 @@ struct CandReservation {
     ~CandReservation() { if (n > 0) g_cand_in_flight[dev].fetch_sub(n); }
 };
 
+// ---- the two launches of the resident engines.  Each fills what the serving loop needs to know about the launch, whichever
+// kernel it is; launched == false with KSS_OK: declined (the plan does not qualify, or the launch failed): nothing touched ----
+struct ResLaunch {
+    bool launched = false;
+    unsigned long long seq0 = 0; unsigned stamp0 = 0;
+    int32_t* idx_out = nullptr; float* d2_out = nullptr;
+    unsigned long long* stamps = nullptr;   // diagnostic timeline (KSS_GRID_STAMPS: tools/resident_stamps.py, tools/cand_stamps.py)
+    unsigned int* gate = nullptr;
+};
+// the launch's numbers, the correspondence buffers if the caller wants them, the stamp buffer: once nothing can decline any more
+static int resident_launch_prepare(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, int max_passes, ResLaunch& a) {
+    a.seq0 = c->seq + 1;
+    c->seq += (unsigned long long)max_passes + 1;
+    c->res_launches = c->res_launches % 500000u + 1u;
+    a.stamp0 = c->res_launches * 4096u;          // every launch has its own 4096 stamps: a record of an earlier launch never matches
+    if (P.compute_fitness && (P.fitness_idx || P.fitness_d2)) {
+        KCHK(ensure(c, c->stage_idx, (size_t)pl.total_src * sizeof(int32_t)));
+        KCHK(ensure(c, c->stage_d2, (size_t)pl.total_src * sizeof(float)));
+        a.idx_out = (int32_t*)c->stage_idx.p; a.d2_out = (float*)c->stage_d2.p;
+    }
+    static const bool stamps_on = getenv("KSS_GRID_STAMPS") != nullptr;
+    if (stamps_on) {
+        KCHK(ensure(c, c->g_stamps, (size_t)pl.npairs * 16 * sizeof(unsigned long long)));
+        HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)pl.npairs * 16 * sizeof(unsigned long long), c->stream));
+        a.stamps = (unsigned long long*)c->g_stamps.p;
+    }
+    return KSS_OK;
+}
+
+// batched cell lists: one workgroup per pair.  ra stays with the caller for the second launch of a split batch.
+// A batch of more pairs than the device runs at once ends with a tail: 1024 uneven registrations on 256 compute units take
+// 6.5 ms for 4.8 ms of work per unit (a tenth of C3's pairs keep hundreds of searches per pass going and run twice as long;
+// whichever of them starts last is the kernel's end).  Such a batch runs as TWO launches: every pair's passes 0 .. split_at - 1
+// (default: passes 0 and 1 -- the first, where every source searches, is the same work for every pair), then the rest with
+// the pairs in the order of DECREASING cost as the first launch predicts it -- longest first, the classic rule for this
+// scheduling problem.  The predictor: the searches the pair asked for in pass 1 (its exit flag carries the count): a pair
+// that is still moving then keeps moving, and searching, for the passes to come.  (With pass 0 alone in the first launch the
+// host orders by the mean squared distance of the first correspondences instead: on C3 as good -- 6.53 vs 6.59 ms -- but by
+// accident: that distance saturates at the point spacing, the long pairs are those rotated by 2-4 degrees, one to two
+// spacings, which creep for all twenty passes, and they merely end up in the middle of that order.  The size of the first
+// ICP step predicts nothing: 7.4.)  Measured at C3 (ms per batch): one launch 7.39-7.45; split after pass 0: 6.51-6.64,
+// after pass 1: 6.59-6.66, 2: 6.83, 3: 7.05, 5: 7.15, 7: 7.63.  Between the launches a pair's registers rest in memory (20 bytes per source).
+// Same passes, same host protocol, same bits.  KSS_RESIDENT_SPLIT=0: one launch (A/B); =k: split after pass k - 1.
+static int resident_launch_cells(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, int max_passes, ResArgs& ra, int* split_at, ResLaunch& a) {
+    const int np = pl.npairs;
+    static const int split_env = getenv("KSS_RESIDENT_SPLIT") ? atoi(getenv("KSS_RESIDENT_SPLIT")) : 2;
+    int ntc = 0, tabc = 0;
+    if (!resident_capacities(pl, &ntc, &tabc)) return KSS_OK;
+    a.gate = resident_gate(c, np);
+    if (!a.gate) return KSS_OK;
+    if (split_env > 0 && np >= 2 * resident_rows_limit(c) && P.max_iterations >= split_env + 4 &&
+        ensure(c, c->res_pos, (size_t)pl.total_src * sizeof(float4)) == KSS_OK && ensure(c, c->res_wc, (size_t)pl.total_src * sizeof(unsigned)) == KSS_OK &&
+        ensure(c, c->res_perm, (size_t)np * sizeof(int32_t)) == KSS_OK)
+        *split_at = split_env;
+    KCHK(resident_launch_prepare(c, pl, P, max_passes, a));
+    ra.pairs = (const GridPairDev*)c->g_pairs.p;
+    ra.cell_start = (const int32_t*)c->g_start.p + 1;
+    ra.sorted = (const float4*)c->g_sorted.p;
+    ra.src0 = (const float4*)c->src0.p;
+    ra.gate = a.gate;
+    ra.pub = c->h_seq_dev;
+    ra.exit_flags = c->h_seq_dev + (size_t)2 * NSUMS * np;
+    ra.max_passes = max_passes;
+    ra.seq0 = a.seq0; ra.stamp0 = a.stamp0;
+    ra.exit_tag = a.stamp0;
+    ra.split_at = *split_at;
+    ra.st_pos = (float4*)c->res_pos.p; ra.st_wc = (unsigned*)c->res_wc.p;
+    ra.max_d2 = P.max_corr_dist * P.max_corr_dist;
+    ra.skin = skin_setting();
+    ra.gate_polls = gate_polls_setting();
+    ra.full_always = P.trace_sums != nullptr ? 1 : 0;
+    ra.ntc = ntc; ra.tabc = tabc;
+    ra.idx_out = a.idx_out; ra.d2_out = a.d2_out;
+    ra.stamps = a.stamps;
+    ProfScope ps(c, KSS_K_RESIDENT, true);
+    std::string lerr;
+    if (launch_resident(c->stream, P.nn_fma != 0, np, ra, lerr) != KSS_OK) (void)hipGetLastError();   // (not launched: nothing touched, the other engine runs)
+    else a.launched = true;
+    return KSS_OK;
+}
+
+// candidates of one registration: equal sizes, packed one after the other, original order (what cand_pass_kernel asks
+// for), and the whole launch resident at once -- up to CAND_TPW tiles of 32 sources per workgroup.  reserve: the caller's, given
+// back only after the kernel has drained.
+static int resident_launch_cands(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, int max_passes, CandReservation& reserve, ResLaunch& a) {
+    const int np = pl.npairs;
+    for (int p = 0; p < np; ++p)
+        if (pl.g[p].ns != pl.g[0].ns || pl.g[p].src_base != (int64_t)p * pl.g[0].ns) return KSS_OK;
+    const int nt_pad = (int)pl.g[0].tgt_pad;
+    const bool fma = P.nn_fma != 0;
+    if (c->cand_cap_pad != nt_pad || c->cand_cap_fma != (fma ? 1 : 0)) {
+        c->cand_cap = cand_resident_capacity(fma, nt_pad);
+        c->cand_cap_pad = nt_pad; c->cand_cap_fma = fma ? 1 : 0;
+    }
+    // Every workgroup of the launch has to be on the chip at once, and so do those of the launches other contexts of this
+    // process (the workers of kss_register_batch) have in flight on the same device: each launch RESERVES its workgroups
+    // out of the device's capacity, takes more tiles per workgroup when little is left, and goes to the launch-per-pass
+    // form when that is not enough.  (KSS_CAND_CAP: a smaller capacity, to exercise exactly that.)
+    static const int cap_env = getenv("KSS_CAND_CAP") ? atoi(getenv("KSS_CAND_CAP")) : 0;
+    const int cap = cap_env > 0 ? std::min(c->cand_cap, cap_env) : c->cand_cap;
+    const int bpp = cand_pass_blocks_per_pair(pl.g[0].ns);
+    if (cap <= 0 || bpp <= 0) return KSS_OK;
+    int tpw = 0;
+    for (int t = 1; t <= CAND_TPW && !tpw; ++t) {
+        const int want_wg = np * ((bpp + t - 1) / t);
+        if (want_wg > cap) continue;
+        if (reserve.take(c->device, want_wg, cap)) tpw = t;
+    }
+    if (!tpw) return KSS_OK;
+    a.gate = resident_gate(c, np);
+    if (!a.gate) return KSS_OK;
+    if (ensure_zeroed(c, c->partials, (size_t)np * bpp * NSUMS * sizeof(Granule)) != KSS_OK) return KSS_OK;
+    KCHK(resident_launch_prepare(c, pl, P, max_passes, a));
+    CandArgs ca;
+    std::memset(&ca, 0, sizeof ca);
+    ca.src0 = (const float4*)c->src0.p;
+    ca.tgt = (const float4*)c->tgt4.p + pl.g[0].tgt_base;
+    ca.nt_pad = nt_pad; ca.ns = (int)pl.g[0].ns;
+    ca.bpp = bpp; ca.tpw = tpw; ca.wpp = (bpp + tpw - 1) / tpw;
+    ca.max_d2 = P.max_corr_dist * P.max_corr_dist;
+    ca.rows = (Granule*)c->partials.p;   // (zeroed when (re)allocated: no granule of the block's earlier owner; pass numbers start at 1)
+    ca.gate = a.gate;
+    ca.pub = c->h_seq_dev;
+    ca.exit_flags = c->h_seq_dev + (size_t)2 * NSUMS * np;
+    ca.seq0 = a.seq0; ca.stamp0 = a.stamp0;
+    ca.gate_polls = gate_polls_setting(); ca.max_passes = max_passes;
+    ca.idx_out = a.idx_out; ca.d2_out = a.d2_out;
+    ca.stamps = a.stamps;
+    ProfScope ps(c, KSS_K_RESIDENT, true);
+    std::string lerr;
+    if (launch_cand_resident(c->stream, fma, np, ca, lerr) != KSS_OK) (void)hipGetLastError();
+    else a.launched = true;
+    return KSS_OK;
+}
+
 // *handled = false with KSS_OK: the plan does not qualify (or the engine gave up before touching any result): the caller
 // runs the launch-per-pass loop
 static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, kss_icp_result* results, bool* handled, bool cand = false) {
@@ -1238,147 +1454,27 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
     if (cand ? (pl.grid || pl.gridb || !pl.shared_target || pl.src_in_cell_order || pl.g[0].tgt_pad > 8192) : !pl.gridb) return KSS_OK;
     if (std::chrono::steady_clock::now() < c->res_backoff[cand ? 1 : 0]) return KSS_OK;   // given up recently: see below
     const int np = pl.npairs;
-    // what the serving loop needs to know about the launch, whichever kernel it is
-    struct { unsigned long long seq0 = 0; unsigned stamp0 = 0; int32_t* idx_out = nullptr; float* d2_out = nullptr; unsigned long long* stamps = nullptr; } a;
-    static const int gate_polls = getenv("KSS_GATE_POLLS") ? atoi(getenv("KSS_GATE_POLLS")) : (1 << 22);
-    static const bool stamps_on = getenv("KSS_GRID_STAMPS") != nullptr;   // diagnostic timeline (tools/resident_stamps.py)
-    unsigned int* gate = nullptr;
     const int max_passes = P.max_iterations + 2;
     CandReservation cand_reserve;   // (given back when this function returns: the kernel has drained by then on every path)
-    auto number_launch = [&]() {
-        a.seq0 = c->seq + 1;
-        c->seq += (unsigned long long)max_passes + 1;
-        c->res_launches = c->res_launches % 500000u + 1u;
-        a.stamp0 = c->res_launches * 4096u;          // every launch has its own 4096 stamps: a record of an earlier launch never matches
-    };
-    auto want_correspondences = [&]() -> int {
-        if (P.compute_fitness && (P.fitness_idx || P.fitness_d2)) {
-            KCHK(ensure(c, c->stage_idx, (size_t)pl.total_src * sizeof(int32_t)));
-            KCHK(ensure(c, c->stage_d2, (size_t)pl.total_src * sizeof(float)));
-            a.idx_out = (int32_t*)c->stage_idx.p; a.d2_out = (float*)c->stage_d2.p;
-        }
-        return KSS_OK;
-    };
-    // A batch of more pairs than the device runs at once ends with a tail: 1024 uneven registrations on 256 compute units take
-    // 6.5 ms for 4.8 ms of work per unit (a tenth of C3's pairs keep hundreds of searches per pass going and run twice as long;
-    // whichever of them starts last is the kernel's end).  Such a batch runs as TWO launches: every pair's passes 0 .. split_at - 1
-    // (default: passes 0 and 1 -- the first, where every source searches, is the same work for every pair), then the rest with
-    // the pairs in the order of DECREASING cost as the first launch predicts it -- longest first, the classic rule for this
-    // scheduling problem.  The predictor: the searches the pair asked for in pass 1 (its exit flag carries the count): a pair
-    // that is still moving then keeps moving, and searching, for the passes to come.  (With pass 0 alone in the first launch the
-    // host orders by the mean squared distance of the first correspondences instead: on C3 as good -- 6.53 vs 6.59 ms -- but by
-    // accident: that distance saturates at the point spacing, the long pairs are those rotated by 2-4 degrees, one to two
-    // spacings, which creep for all twenty passes, and they merely end up in the middle of that order.  The size of the first
-    // ICP step predicts nothing: 7.4.)  Measured at C3 (ms per batch): one launch 7.39-7.45; split after pass 0: 6.51-6.64,
-    // after pass 1: 6.59-6.66, 2: 6.83, 3: 7.05, 5: 7.15, 7: 7.63.  Between the launches a pair's registers rest in memory (20 bytes per source).
-    // Same passes, same host protocol, same bits.  KSS_RESIDENT_SPLIT=0: one launch (A/B); =k: split after pass k - 1.
-    static const int split_env = getenv("KSS_RESIDENT_SPLIT") ? atoi(getenv("KSS_RESIDENT_SPLIT")) : 2;
+    ResLaunch a;
     int split_at = 0;
     ResArgs ra;
     std::memset(&ra, 0, sizeof ra);
-    if (!cand) {
-        int ntc = 0, tabc = 0;
-        if (!resident_capacities(pl, &ntc, &tabc)) return KSS_OK;
-        gate = resident_gate(c, np);
-        if (!gate) return KSS_OK;
-        if (split_env > 0 && np >= 2 * resident_rows_limit(c) && P.max_iterations >= split_env + 4 &&
-            ensure(c, c->res_pos, (size_t)pl.total_src * sizeof(float4)) == KSS_OK && ensure(c, c->res_wc, (size_t)pl.total_src * sizeof(unsigned)) == KSS_OK &&
-            ensure(c, c->res_perm, (size_t)np * sizeof(int32_t)) == KSS_OK)
-            split_at = split_env;
-        ra.pairs = (const GridPairDev*)c->g_pairs.p;
-        ra.cell_start = (const int32_t*)c->g_start.p + 1;
-        ra.sorted = (const float4*)c->g_sorted.p;
-        ra.src0 = (const float4*)c->src0.p;
-        ra.gate = gate;
-        ra.pub = c->h_seq_dev;
-        ra.exit_flags = c->h_seq_dev + (size_t)2 * NSUMS * np;
-        ra.max_passes = max_passes;
-        number_launch();
-        ra.seq0 = a.seq0; ra.stamp0 = a.stamp0;
-        ra.exit_tag = a.stamp0;
-        ra.split_at = split_at;
-        ra.st_pos = (float4*)c->res_pos.p; ra.st_wc = (unsigned*)c->res_wc.p;
-        ra.max_d2 = P.max_corr_dist * P.max_corr_dist;
-        static const float skin = getenv("KSS_SKIN") ? (float)atof(getenv("KSS_SKIN")) : 0.25f;
-        ra.skin = skin;
-        ra.gate_polls = gate_polls;
-        ra.full_always = P.trace_sums != nullptr ? 1 : 0;
-        ra.ntc = ntc; ra.tabc = tabc;
-        KCHK(want_correspondences());
-        ra.idx_out = a.idx_out; ra.d2_out = a.d2_out;
-        if (stamps_on) {
-            KCHK(ensure(c, c->g_stamps, (size_t)np * 16 * sizeof(unsigned long long)));
-            HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)np * 16 * sizeof(unsigned long long), c->stream));
-            ra.stamps = a.stamps = (unsigned long long*)c->g_stamps.p;
-        }
-        ProfScope ps(c, KSS_K_RESIDENT, true);
-        std::string lerr;
-        const int rc = launch_resident(c->stream, P.nn_fma != 0, np, ra, lerr);
-        if (rc != KSS_OK) { (void)hipGetLastError(); return KSS_OK; }   // (not launched: nothing touched, the other engine runs)
-    } else {
-        // candidates of one registration: equal sizes, packed one after the other, original order (what cand_pass_kernel asks
-        // for), and the whole launch resident at once -- up to CAND_TPW tiles of 32 sources per workgroup
-        for (int p = 0; p < np; ++p)
-            if (pl.g[p].ns != pl.g[0].ns || pl.g[p].src_base != (int64_t)p * pl.g[0].ns) return KSS_OK;
-        const int nt_pad = (int)pl.g[0].tgt_pad;
-        const bool fma = P.nn_fma != 0;
-        if (c->cand_cap_pad != nt_pad || c->cand_cap_fma != (fma ? 1 : 0)) {
-            c->cand_cap = cand_resident_capacity(fma, nt_pad);
-            c->cand_cap_pad = nt_pad; c->cand_cap_fma = fma ? 1 : 0;
-        }
-        // Every workgroup of the launch has to be on the chip at once, and so do those of the launches other contexts of this
-        // process (the workers of kss_register_batch) have in flight on the same device: each launch RESERVES its workgroups
-        // out of the device's capacity, takes more tiles per workgroup when little is left, and goes to the launch-per-pass
-        // form when that is not enough.  (KSS_CAND_CAP: a smaller capacity, to exercise exactly that.)
-        static const int cap_env = getenv("KSS_CAND_CAP") ? atoi(getenv("KSS_CAND_CAP")) : 0;
-        const int cap = cap_env > 0 ? std::min(c->cand_cap, cap_env) : c->cand_cap;
-        const int bpp = cand_pass_blocks_per_pair(pl.g[0].ns);
-        if (cap <= 0 || bpp <= 0) return KSS_OK;
-        int tpw = 0;
-        for (int t = 1; t <= CAND_TPW && !tpw; ++t) {
-            const int want_wg = np * ((bpp + t - 1) / t);
-            if (want_wg > cap) continue;
-            if (cand_reserve.take(c->device, want_wg, cap)) tpw = t;
-        }
-        if (!tpw) return KSS_OK;
-        gate = resident_gate(c, np);
-        if (!gate) return KSS_OK;
-        if (ensure_zeroed(c, c->partials, (size_t)np * bpp * NSUMS * sizeof(Granule)) != KSS_OK) return KSS_OK;
-        CandArgs ca;
-        std::memset(&ca, 0, sizeof ca);
-        ca.src0 = (const float4*)c->src0.p;
-        ca.tgt = (const float4*)c->tgt4.p + pl.g[0].tgt_base;
-        ca.nt_pad = nt_pad; ca.ns = (int)pl.g[0].ns;
-        ca.bpp = bpp; ca.tpw = tpw; ca.wpp = (bpp + tpw - 1) / tpw;
-        ca.max_d2 = P.max_corr_dist * P.max_corr_dist;
-        ca.rows = (Granule*)c->partials.p;   // (zeroed when (re)allocated: no granule of the block's earlier owner; pass numbers start at 1)
-        ca.gate = gate;
-        ca.pub = c->h_seq_dev;
-        ca.exit_flags = c->h_seq_dev + (size_t)2 * NSUMS * np;
-        number_launch();
-        ca.seq0 = a.seq0; ca.stamp0 = a.stamp0;
-        ca.gate_polls = gate_polls; ca.max_passes = max_passes;
-        KCHK(want_correspondences());
-        ca.idx_out = a.idx_out; ca.d2_out = a.d2_out;
-        if (stamps_on) {   // (tools/cand_stamps.py)
-            KCHK(ensure(c, c->g_stamps, (size_t)np * 16 * sizeof(unsigned long long)));
-            HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)np * 16 * sizeof(unsigned long long), c->stream));
-            ca.stamps = a.stamps = (unsigned long long*)c->g_stamps.p;
-        }
-        ProfScope ps(c, KSS_K_RESIDENT, true);
-        std::string lerr;
-        const int rc = launch_cand_resident(c->stream, fma, np, ca, lerr);
-        if (rc != KSS_OK) { (void)hipGetLastError(); return KSS_OK; }
-    }
+    KCHK(cand ? resident_launch_cands(c, pl, P, max_passes, cand_reserve, a) : resident_launch_cells(c, pl, P, max_passes, ra, &split_at, a));
+    if (!a.launched) return KSS_OK;
+    unsigned int* const gate = a.gate;
+    const bool stamps_on = a.stamps != nullptr;
 
-    // ---- per-pair host state (what icp_loop keeps in its vectors) ----
+    // ---- per-pair host state: icp_loop's record and what the serving protocol adds ----
     enum { PH_ITER = 0, PH_FIT = 1, PH_DONE = 2 };
-    struct PairHost { Convergence cv; float fin[16]; int iters = 0, converged = 0, state = 0, k = 0, phase = PH_ITER, cancelled = 0, parked = 0; double last_mse = 0.0, fitness = 0.0, step0 = 0.0; };
-    std::vector<PairHost> H((size_t)np);
-    for (int p = 0; p < np; ++p) {
-        H[p].cv = convergence_of(P);
-        mat4_identity(H[p].fin);
-    }
+    struct PairHost {
+        PairTrack t;
+        int k = 0, phase = PH_ITER, cancelled = 0, parked = 0;
+        double fitness = 0.0;
+        explicit PairHost(const kss_icp_params& P) : t(P) {}
+    };
+    std::vector<PairHost> H((size_t)np, PairHost(P));
+    const PairMode plain;   // the untrimmed, unweighted point metric
     if (P.trace_n) *P.trace_n = 0;
     std::atomic<int> failed{0}, kernel_done{0}, pairs_left{np}, cancel_all{0};
     int split_now = split_at;                  // > 0 while the first launch of a split batch is being served
@@ -1447,27 +1543,11 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
                     if (p == judge && h.fitness <= judge_threshold) cancel_all.store(1, std::memory_order_relaxed);
                     continue;
                 }
-                bool finished = false;
-                float tk[16];
-                if ((int)s[0] < P.min_correspondences) {   // PCL: "Not enough correspondences found"
-                    h.state = KSS_STATE_NO_CORRESPONDENCES; h.converged = 0; finished = true;
-                } else {
-                    rigid_from_sums(s, tk);
-                    mat4_mul(tk, h.fin, h.fin);            // final = transformation_ * final
-                    ++h.iters;
-                    const double mse = s[16] / s[0];
-                    h.last_mse = mse;
-                    if (h.iters == 1) h.step0 = (3.0 - ((double)tk[0] + (double)tk[5] + (double)tk[10])) + std::sqrt((double)tk[3] * tk[3] + (double)tk[7] * tk[7] + (double)tk[11] * tk[11]);   // how far the first step went: 2 (1 - cos angle) + |t|
-                    if (p == 0) trace_row(P, s, NSUMS, tk);
-                    const bool done = h.cv.has_converged(h.iters, tk, mse);
-                    h.state = h.cv.state;
-                    if (done) { h.converged = 1; finished = true; }
-                }
-                if (!finished) {
-                    send(p, tk, 1, 0);                     // the next pass applies T_k on load (transformCloud)
+                if (pair_host_step(P, plain, s, nullptr, h.t, p == 0)) {
+                    send(p, h.t.tk, 1, 0);                 // the next pass applies T_k on load (transformCloud)
                     ++h.k;
                 } else if (P.compute_fitness) {
-                    send(p, h.fin, 1, 1);                  // final * original input, all 20 sums
+                    send(p, h.t.fin, 1, 1);                // final * original input, all 20 sums
                     ++h.k;
                     h.phase = PH_FIT;
                 } else {
@@ -1526,15 +1606,14 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
         // ---- the second launch of a split batch: the parked pairs, longest first ----
         HIPCHK(c, hipStreamSynchronize(c->stream));   // every workgroup of the first launch has left (its registers are in memory)
         // cost predictor: the searches the pair asked for in passes 1 .. split_at - 1 (its exit flag carries the count); with
-        // only pass 0 in the first launch, the mean squared distance of its first correspondences (KSS_RESIDENT_SPLIT_KEY=mse)
+        // only pass 0 in the first launch, or with KSS_RESIDENT_SPLIT_KEY=mse, the mean squared distance of its first correspondences
         static const bool key_mse = getenv("KSS_RESIDENT_SPLIT_KEY") != nullptr && std::string(getenv("KSS_RESIDENT_SPLIT_KEY")) == "mse";
         std::vector<std::pair<double, int>> order;
         const unsigned long long* fl = h_seq + (size_t)2 * NSUMS * np;
         for (int p = 0; p < np; ++p) {
             in_launch[p] = 0;
             if (!H[p].parked) continue;
-            static const bool key_step = getenv("KSS_RESIDENT_SPLIT_KEY") != nullptr && std::string(getenv("KSS_RESIDENT_SPLIT_KEY")) == "step";
-            order.emplace_back(key_step ? H[p].step0 : key_mse || split_at < 2 ? H[p].last_mse : (double)(unsigned)(fl[2 * p + 1] & 0xffffffffull), p);
+            order.emplace_back(key_mse || split_at < 2 ? H[p].t.last_mse : (double)(unsigned)(fl[2 * p + 1] & 0xffffffffull), p);
         }
         std::stable_sort(order.begin(), order.end(), [](const std::pair<double, int>& x, const std::pair<double, int>& y) { return x.first > y.first; });
         const int np2 = (int)order.size();
@@ -1564,16 +1643,16 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
         for (int p = 0; p < np; ++p)
             if (H[p].phase != PH_DONE) send(p, nullptr, 0, 2, true);
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        static const int backoff_s = getenv("KSS_RES_BACKOFF_S") ? atoi(getenv("KSS_RES_BACKOFF_S")) : 30;
+        constexpr int backoff_s = 30;
         c->res_backoff[cand ? 1 : 0] = std::chrono::steady_clock::now() + std::chrono::seconds(backoff_s);   // not again for a while: each failure costs the polls' bound (~1 s)
         {
             int unfinished = 0, k_min = 1 << 30, k_max = 0;
             for (int p = 0; p < np; ++p)
                 if (H[p].phase != PH_DONE) { ++unfinished; k_min = std::min(k_min, H[p].k); k_max = std::max(k_max, H[p].k); }
             std::fprintf(stderr, "[kss] the pair-resident kernel left before every pair was finished (a stalled host thread?); running the launch-per-pass engine"
-                                 " (and for the next 30 s on this context)"
+                                 " (and for the next %d s on this context)"
                                  " [%s, %d of %d pairs unfinished, waiting for passes %d..%d, %d host threads, stream query: %s]\n",
-                         cand ? "candidates" : "cell lists", unfinished, np, k_min, k_max, nthreads, hipGetErrorName((hipError_t)query_said.load()));
+                         backoff_s, cand ? "candidates" : "cell lists", unfinished, np, k_min, k_max, nthreads, hipGetErrorName((hipError_t)query_said.load()));
             if (getenv("KSS_DEBUG_RES")) {   // what each unfinished pair was waiting for, and what is there
                 for (int p = 0; p < np; ++p) {
                     if (H[p].phase == PH_DONE) continue;
@@ -1591,7 +1670,7 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
     if (c->prof > 0) { c->prof_n[KSS_K_RESIDENT_PASS] += units.load(); }
     for (int p = 0; p < np; ++p) {
         const PairHost& h = H[p];   // (a cancelled candidate: its result will not be looked at)
-        fill_result(results[p], h.fin, h.iters, h.cancelled ? 0 : h.converged, h.cancelled ? KSS_STATE_NOT_CONVERGED : h.state, h.last_mse,
+        fill_result(results[p], h.t.fin, h.t.iters, h.cancelled ? 0 : h.t.converged, h.cancelled ? KSS_STATE_NOT_CONVERGED : h.t.state, h.t.last_mse,
                     P.compute_fitness && !h.cancelled ? h.fitness : 0.0, p);
     }
     if (judge >= 0) { c->spec_ran = true; c->spec_cancelled = cancel_all.load() != 0; }
@@ -1614,7 +1693,7 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
 // the call runs on the brute-force engine, whose tiled sweep is several times faster at that job; the engines agree bit for
 // bit on every correspondence, so the switch only changes speed.  The packed clouds stay where they are.  plan: the batched
 // cell-list plan the pass ran on, replaced by brute_plan (built and staged here) when the rule fires.
-static int switch_engine_on_fallback(kss_ctx* c, const IcpPlan*& plan, IcpPlan& brute_plan, bool shared_target, const kss_icp_params& P,
+static int switch_engine_on_fallback(kss_ctx* c, const IcpPlan*& plan, IcpPlan& brute_plan, const kss_icp_params& P,
                                      const std::vector<int>& was_active) {
     const int np = plan->npairs;
     const double* hsum = (const double*)c->h_sums;
@@ -1624,7 +1703,7 @@ static int switch_engine_on_fallback(kss_ctx* c, const IcpPlan*& plan, IcpPlan& 
     if (!(fallback > 0.10 * act) || getenv("KSS_GRID_NOSWITCH")) return KSS_OK;
     std::vector<int64_t> ns(np), nt(np);
     for (int p = 0; p < np; ++p) { ns[p] = plan->g[p].ns; nt[p] = plan->g[p].nt; }
-    KCHK(build_plan(c, ns.data(), nt.data(), np, shared_target, P.nn_sources_per_thread, P.nn_target_splits, KSS_NN_BRUTE, brute_plan));
+    KCHK(build_plan(c, ns.data(), nt.data(), np, false, P.nn_sources_per_thread, P.nn_target_splits, KSS_NN_BRUTE, brute_plan));
     brute_plan.src_in_cell_order = true;
     KCHK(stage_plan(c, brute_plan));
     plan = &brute_plan;
@@ -1637,19 +1716,6 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
         bool handled = false;
         KCHK(resident_loop(c, pl_in, P, results, &handled));
         if (handled) return KSS_OK;
-        if (pl_in.shared_target) {
-            // candidates of one target that the resident engine declined: the brute-force engine (the packed clouds stay where
-            // they are, in cell order; the engines agree on every correspondence)
-            std::vector<int64_t> ns(pl_in.npairs), nt(pl_in.npairs);
-            for (int p = 0; p < pl_in.npairs; ++p) { ns[p] = pl_in.g[p].ns; nt[p] = pl_in.g[p].nt; }
-            IcpPlan bp;
-            KCHK(build_plan(c, ns.data(), nt.data(), pl_in.npairs, true, P.nn_sources_per_thread, P.nn_target_splits, KSS_NN_BRUTE, bp));
-            bp.src_in_cell_order = true;
-            KCHK(stage_plan(c, bp));
-            kss_icp_params Pb = P;
-            Pb.nn_mode = KSS_NN_BRUTE;
-            return icp_loop(c, bp, Pb, results);
-        }
     }
     if (!pl_in.grid && !pl_in.gridb && pl_in.shared_target) {   // the candidate batch of a registration: one launch, every workgroup resident
         bool handled = false;
@@ -1660,17 +1726,15 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
     const IcpPlan* plan = &pl_in;   // may change to the brute-force plan below
     IcpPlan brute_plan;
     const int np = pl_in.npairs;
-    std::vector<Convergence> conv(np, convergence_of(P));
-    std::vector<float> fin((size_t)np * 16), Tk((size_t)np * 16);
-    std::vector<int> iters(np, 0), active(np, 1), converged(np, 0), state(np, 0), solved(np, 0), was_active;
-    std::vector<double> last_mse(np, 0.0);
+    std::vector<PairTrack> tr((size_t)np, PairTrack(P));
+    std::vector<int> active(np, 1), solved(np, 0), was_active;
+    const PairMode plain;   // the untrimmed, unweighted point metric
     const bool full = P.trace_sums != nullptr;   // traced runs report all 20 sums of every pass
     PairState* hs = (PairState*)c->h_state;
     PairState* bar = pl_in.gridb ? bar_state_table(c, np) : nullptr;   // (null without a large BAR)
     float I[16];
     mat4_identity(I);
     for (int p = 0; p < np; ++p) {
-        mat4_identity(&fin[(size_t)p * 16]);
         set_state(hs[p], I, 1, 0);
         mirror_state(bar, p, hs[p]);
     }
@@ -1696,28 +1760,15 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
             for (int p = pb; p < pe; ++p) {
                 if (!active[p] || solved[p]) continue;
                 if (poll && wait_pair(c, p, pass_seq) != KSS_OK) { stuck.fetch_add(1); continue; }   // (retried below after a stream sync)
-                const double* s = hsum + (size_t)p * NSUMS;
-                if ((int)s[0] < P.min_correspondences) {   // PCL: "Not enough correspondences found"
-                    state[p] = KSS_STATE_NO_CORRESPONDENCES; converged[p] = 0; active[p] = 0; ++fin_here; solved[p] = 1;
-                    set_state(hs[p], I, 0, 0);
-                    mirror_state(bar, p, hs[p]);
-                    continue;
-                }
-                float* tk = &Tk[(size_t)p * 16];
-                rigid_from_sums(s, tk);
-                mat4_mul(tk, &fin[(size_t)p * 16], &fin[(size_t)p * 16]);   // final = transformation_ * final
-                ++iters[p];
-                const double mse = s[16] / s[0];
-                last_mse[p] = mse;
-                if (p == 0) trace_row(P, s, NSUMS, tk);
-                const bool done = conv[p].has_converged(iters[p], tk, mse);
-                state[p] = conv[p].state;
+                PairTrack& t = tr[p];
+                const bool goes_on = pair_host_step(P, plain, hsum + (size_t)p * NSUMS, nullptr, t, p == 0);
                 solved[p] = 1;
-                if (done) {
-                    converged[p] = 1; active[p] = 0; ++fin_here;
-                    set_state(hs[p], tk, 0, 1);
+                if (goes_on) {
+                    set_state(hs[p], t.tk, 1, 1);   // next sweep applies T_k on load (transformCloud)
                 } else {
-                    set_state(hs[p], tk, 1, 1);   // next sweep applies T_k on load (transformCloud)
+                    active[p] = 0; ++fin_here;
+                    if (t.state == KSS_STATE_NO_CORRESPONDENCES) set_state(hs[p], I, 0, 0);
+                    else set_state(hs[p], t.tk, 0, 1);
                 }
                 mirror_state(bar, p, hs[p]);
             }
@@ -1726,7 +1777,7 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
         const int n = p1 - p0;
         if (n >= 64) {
             std::atomic<int> next{0};
-            static const int kBlock = [] { const char* e = getenv("KSS_SOLVE_BLOCK"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 64; }();   // pairs claimed at a time, in launch order: the first threads start while the GPU is still on later pairs.  Tuning hook; measured at C3: blocks of 4 pairs 11.7 ms (threads share cache lines of the per-pair arrays), 16: 9.85, 64: 9.5
+            constexpr int kBlock = 64;   // pairs claimed at a time, in launch order: the first threads start while the GPU is still on later pairs.  Measured at C3: blocks of 4 pairs 11.7 ms (threads share cache lines of the per-pair records), 16: 9.85, 64: 9.5
             c->pool.parallel_for(n, [&](int, int) {
                 for (;;) {
                     const int pb = p0 + next.fetch_add(1) * kBlock;
@@ -1779,11 +1830,11 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
             c->t_launch_us += std::chrono::duration<double, std::micro>(tb1 - tb0).count();
             c->t_wait_us += std::chrono::duration<double, std::micro>(tb2 - tb1).count();
         }
-        if (plan->gridb) KCHK(switch_engine_on_fallback(c, plan, brute_plan, pl_in.shared_target, P, was_active));
+        if (plan->gridb) KCHK(switch_engine_on_fallback(c, plan, brute_plan, P, was_active));
         n_active -= fin_now;
         ++it;
     }
-    for (int p = 0; p < np; ++p) fill_result(results[p], &fin[(size_t)p * 16], iters[p], converged[p], state[p], last_mse[p], 0.0, p);
+    for (int p = 0; p < np; ++p) fill_result(results[p], tr[p].fin, tr[p].iters, tr[p].converged, tr[p].state, tr[p].last_mse, 0.0, p);
     if (!P.compute_fitness) return KSS_OK;
     int32_t* d_idx = nullptr;
     float* d_d2 = nullptr;
@@ -1792,7 +1843,7 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
         KCHK(ensure(c, c->stage_d2, (size_t)plan->total_src * sizeof(float)));
         d_idx = (int32_t*)c->stage_idx.p; d_d2 = (float*)c->stage_d2.p;
     }
-    return fitness_pass(c, *plan, P, fin.data(), iters.data(), state.data(), plan == &pl_in, bar, d_idx, d_d2, results);
+    return fitness_pass(c, *plan, P, tr.data(), plan == &pl_in, bar, d_idx, d_d2, results);
 }
 
 // zero-at-rest buffers (kss_ctx.hpp): cleared here when the previous call on this context did not finish
@@ -1886,55 +1937,6 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // Reciprocal (kss_icp_recip; M.mutual with M.trimmed, either metric, one pair only): five launches ahead of the
 // selection (kss_recip.hip: reset, claim + count, scan, scatter, resolve + check) filter the same arrays the same way, against the
 // positions the NN pass wrote; the info record grows to KSS_RECIP_NINFO = {r, k, tau, kept, m, u}, m and u published by the resolve launch.
-// What the host does for ONE pair after a pass, a single pair's and every pair's of a batch (pairs_loop): the
-// min_correspondences test, the solve by metric, final <- T_k * final, the MSE and PCL's criteria.  s: the pass's record, info:
-// its {m, k, tau, kept} (trimmed).  True: the pair goes on, hs holds T_k for the next NN pass to apply on load; false: it has
-// ended (state / converged say how) and hs is left as it was.  trace: the pair whose passes the caller's trace receives.
-struct PairTrack {
-    Convergence cv;
-    float fin[16], tk[16];
-    int iters = 0, state = KSS_STATE_NOT_CONVERGED, converged = 0;
-    double last_mse = 0.0;
-    double s_acc = 1.0;   // similarity: the scale accumulated so far
-    explicit PairTrack(const kss_icp_params& P) : cv(convergence_of(P)) { mat4_identity(fin); mat4_identity(tk); }
-};
-static int pair_ninfo(const PairMode& M) { return M.sim ? KSS_SIM_NINFO : M.mutual ? KSS_RECIP_NINFO : M.unique ? KSS_O2O_NINFO : KSS_TRIM_NINFO; }
-static_assert(KSS_O2O_NINFO <= KSS_SIM_NINFO && KSS_RECIP_NINFO <= KSS_SIM_NINFO, "the loops' info arrays hold KSS_SIM_NINFO doubles");
-static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const double* s, double* info, PairTrack& t, PairState& hs,
-                           bool trace) {
-    if (M.sim) { info[4] = 0.0; info[5] = t.s_acc; }
-    // PCL: "Not enough correspondences found" (robust: the count kept, [0] being the weight total)
-    const double cnt = M.robust ? s[(M.plane ? P2L_NSUMS : NSUMS) - 1] : s[0];
-    if ((int)cnt < P.min_correspondences) { t.state = KSS_STATE_NO_CORRESPONDENCES; return false; }
-    float ck[16];                 // similarity: the step without its scale, what the criteria read
-    const float* crit = t.tk;
-    double scale_dev2 = 0.0;
-    if (M.symm) {
-        if (!rigid_from_symm_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
-    } else if (M.plane) {
-        if (!rigid_from_p2l_sums(s, t.tk)) { t.state = KSS_STATE_DEGENERATE; return false; }
-    } else if (M.sim) {
-        double sk;
-        if (!sim_from_sums(s, M.scale_min / t.s_acc, M.scale_max / t.s_acc, t.tk, &sk, ck)) { t.state = KSS_STATE_DEGENERATE; return false; }
-        t.s_acc = std::fmin(std::fmax(t.s_acc * sk, M.scale_min), M.scale_max);
-        info[4] = sk; info[5] = t.s_acc;
-        scale_dev2 = (sk - 1.0) * (sk - 1.0);
-        crit = ck;
-    } else {
-        rigid_from_sums(s, t.tk);
-    }
-    mat4_mul(t.tk, t.fin, t.fin);   // final = transformation_ * final
-    ++t.iters;
-    const double mse = (M.plane ? s[28] : s[16]) / s[0];   // point-to-point d2 of the kept correspondences, as PCL's criteria read it
-    t.last_mse = mse;
-    if (trace) trace_row(P, s, M.plane ? P2L_NSUMS : NSUMS, t.tk, M.trimmed || M.robust ? M.trace_info : nullptr, info, pair_ninfo(M));
-    const bool done = t.cv.has_converged(t.iters, crit, mse, scale_dev2);
-    t.state = t.cv.state;
-    if (done) { t.converged = 1; return false; }
-    set_state(hs, t.tk, 1, 1);   // next NN pass applies T_k on load (transformCloud)
-    return true;
-}
-
 // the rotation block of a row-major 4 x 4 (the float bits of the accumulated Matrix4f)
 static GicpRot rot_of(const float* F) { return GicpRot{{F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]}}; }
 
@@ -2181,9 +2183,11 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
                 if (!active[p]) continue;
                 double info[KSS_SIM_NINFO] = {};
                 pair_info_read(M, hrec, np, p, info);
-                const bool goes_on = pair_host_step(P, M, hrec + (size_t)p * P2L_NSUMS, info, tr[p], hs[p], p == 0);   // (similarity: fills the scale slots of info)
+                const bool goes_on = pair_host_step(P, M, hrec + (size_t)p * P2L_NSUMS, info, tr[p], p == 0);   // (similarity: fills the scale slots of info)
                 if ((M.trimmed || M.robust) && info_all) std::memcpy(info_all + (size_t)p * ninfo, info, (size_t)ninfo * sizeof(double));
-                if (!goes_on) {
+                if (goes_on) {
+                    set_state(hs[p], tr[p].tk, 1, 1);   // next NN pass applies T_k on load (transformCloud)
+                } else {
                     active[p] = 0; ++fin_here;
                     set_state(hs[p], I, 0, 0);
                 }
@@ -2206,18 +2210,12 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
             solve(0, np);
         }
         n_active -= finished.load(std::memory_order_relaxed);
-        if (plan->gridb && n_active > 0) KCHK(switch_engine_on_fallback(c, plan, brute_plan, false, P, was_active));
+        if (plan->gridb && n_active > 0) KCHK(switch_engine_on_fallback(c, plan, brute_plan, P, was_active));
     }
-    std::vector<float> fin((size_t)np * 16);
-    std::vector<int> iters(np), state(np);
-    for (int p = 0; p < np; ++p) {
-        std::memcpy(&fin[(size_t)p * 16], tr[p].fin, sizeof tr[p].fin);
-        iters[p] = tr[p].iters; state[p] = tr[p].state;
-        fill_result(results[p], tr[p].fin, tr[p].iters, tr[p].converged, tr[p].state, tr[p].last_mse, 0.0, p);
-    }
+    for (int p = 0; p < np; ++p) fill_result(results[p], tr[p].fin, tr[p].iters, tr[p].converged, tr[p].state, tr[p].last_mse, 0.0, p);
     if (!P.compute_fitness) return KSS_OK;
     const bool corr = P.fitness_idx || P.fitness_d2;
-    return fitness_pass(c, *plan, P, fin.data(), iters.data(), state.data(), plan == &pl_in, bar, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, results);
+    return fitness_pass(c, *plan, P, tr.data(), plan == &pl_in, bar, corr ? d_idx : nullptr, corr ? d_d2 : nullptr, results);
 }
 
 static int stage_pairb(kss_ctx* c, const std::vector<PairbDesc>& desc, bool rows);

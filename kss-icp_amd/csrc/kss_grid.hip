@@ -790,40 +790,37 @@ do {                                                                            
 }
 
 // =============================================================================================
-// The fused cell-list pass: ONE kernel for a single pair (C2 / C4) and for a batch of pairs (C3 / C5).
-//   - one workgroup = one CHUNK of 512 consecutive cell-sorted sources of one pair, one lane per source; workgroups
-//     are laid out pair by pair and handed to XCDs in contiguous runs (blockIdx % 8 remap), so the workgroups of a
-//     pair -- and with them that pair's cell list -- stay in one XCD's L2;
+// The fused cell-list pass of a single pair (C2 / C4); a batch of pairs (C3 / C5) runs the same phases with two sources
+// per lane (gridb_pass_kernel, below).
+//   - one workgroup = one CHUNK of 512 consecutive cell-sorted sources of the pair, one lane per source; workgroups
+//     are handed to XCDs in contiguous runs (blockIdx % 8 remap), so neighbouring chunks -- and with them their part of
+//     the cell list -- stay in one XCD's L2;
 //   - search in three phases.  A: every lane moves its source and tries to keep its last winner (the skip test above);
 //     the lanes that must search ("walkers", a few per cent near convergence) queue up in LDS.  B: the first lanes of
 //     the workgroup serve the walkers, 16 / 8 / 4 lanes per walker when there are few (one row or a few rows of the
 //     3x3x3 block each, merged by DPP), one lane each otherwise: last winner first, the block pruned by its distance
-//     (block_walk / row_walk), further shells up to GridParams::rcap, then the fallback -- BATCH: the wave sweeps the
-//     pair's targets by brute force for its unresolved lanes (uniform addresses, no barrier); single pair: the source
+//     (block_walk / row_walk), further shells up to GridParams::rcap, then the fallback (serve_walkers) -- the batch's
+//     wave sweeps the pair's targets by brute force for its unresolved lanes (uniform addresses, no barrier); here the source
 //     goes to a device list that nn_sweep_kernel<LIST> resolves, after which a SEARCH = false launch of this kernel
 //     (same rows, same order) redoes the sums from the stored winners.  C: every lane picks its answer up from LDS;
 //   - sums: every lane contributes its correspondence to 16 f64 columns (+ 2 in FULL mode: sum of all d2 and of
 //     sqrt(d2) for getFitnessScore / PCR_QM; counts are ballots), reduced in the canonical order of kss_device.hpp:
 //     in-wave tree by permlane swaps + DPP (no LDS, no barrier), 8 wave totals through LDS, one row per workgroup;
 //   - rows are handed over as granules tagged with the launch's sequence number (kss_device.hpp, rows_take); the pair's
-//     first workgroup adds them up in the canonical order -- in this launch, or in gridb_finalize_kernel right after it
-//     when a batch has more pairs than compute units -- and publishes the 20 sums of the pair as {bits(sum), seq} 16-byte
+//     first workgroup adds them up in the canonical order and publishes the 20 sums of the pair as {bits(sum), seq} 16-byte
 //     stores into host-mapped memory, where the host spins on the sequence numbers (no completion flag, no stream sync);
 //   - a pair of a single chunk skips the hand-over (0.0 + row: the same bits as the general path).
 // The result of a pair is a function of its own clouds only: alone or in a batch of any size, bit for bit.
 // =============================================================================================
-#ifndef KSS_BATCH_WAVES
-#define KSS_BATCH_WAVES 6   // waves per SIMD the batched variant is compiled for (3 workgroups per CU; 8 spills)
-#endif
 #ifndef KSS_SINGLE_WAVES
 #define KSS_SINGLE_WAVES 1
 #endif
 // FIRST: the first pass of a single pair (PassArgs::use_prev == 0: the first pass of a registration, kss_nn), an instantiation
 // of its own that the profilers list apart.
-template <bool FMA, bool FULL, bool BATCH, bool SEARCH, bool CHAIN, bool FIRST = false>
-__global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES) void grid_pass_kernel(const PassArgs a) {
-    static_assert(!CHAIN || (!BATCH && SEARCH), "chained launches: single pair, search passes");
-    static_assert(!FIRST || (!BATCH && SEARCH && !CHAIN), "the first pass: single pair, a plain search launch");
+template <bool FMA, bool FULL, bool SEARCH, bool CHAIN, bool FIRST = false>
+__global__ __launch_bounds__(PASS_BS, KSS_SINGLE_WAVES) void grid_pass_kernel(const PassArgs a) {
+    static_assert(!CHAIN || SEARCH, "chained launches: search passes");
+    static_assert(!FIRST || (SEARCH && !CHAIN), "the first pass: a plain search launch");
     // diagnostic stamps (100 MHz s_memrealtime): [block*16 + {0 start, 13 first loads in, 9 gate open, 14 phase A done,
     // 5 phase B entered, 8 answered, 15 phase B done, 1 searched, 2 row ready, 3 row handed over, 4 result stored
     // (reducer)}]; counts: 10 = distance evaluations of the r = 1 block, 11 = evaluation slots, 12 = walkers
@@ -833,14 +830,8 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
     const int per_xcd = (int)gridDim.x / 8;                                   // the launcher makes gridDim.x a multiple of 8
     const int w = ((int)blockIdx.x % 8) * per_xcd + (int)blockIdx.x / 8;      // bijection on [0, gridDim.x): XCD-contiguous runs
     if (w >= a.total_rows) return;
-    int pi = 0;
-    if constexpr (BATCH) pi = a.row_pair[w];
-    const GridPairDev pr = BATCH ? a.pairs[pi] : a.pair0;
+    const GridPairDev pr = a.pair0;
     PairState ps = a.ps0;
-    if constexpr (BATCH) {
-        ps = a.state[pi];
-        if (!ps.active) return;            // uniform: a converged pair costs one table read per workgroup
-    }
     const GridParams& gp = pr.gp;
     const int32_t* __restrict__ cs = a.cell_start + pr.cell_base;
     const float4* __restrict__ sorted = a.sorted;
@@ -906,7 +897,7 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
         __syncthreads();
     }
     KSS_STAMP(13);
-    if constexpr (!BATCH && SEARCH) {
+    if constexpr (SEARCH) {
         if (gate_k != 0) {
             // GATED launch (kss_engine.hip): this kernel was enqueued while the previous iteration was still running, before
             // its transform existed.  It polls five self-validating 16-byte granules {3 words, stamp} in DEVICE memory (one
@@ -1038,7 +1029,7 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
         __syncthreads();
         const int nwalk = s_nwalk;
         if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + 12] = (unsigned long long)nwalk;
-        serve_walkers<FMA, BATCH, WQ, BS, BATCH ? 4 : 8, FIRST>(a, pr, cs, sorted, w, nwalk, rowq, s_ent, s_wl);
+        serve_walkers<FMA, false, WQ, BS, 8, FIRST>(a, pr, cs, sorted, w, nwalk, rowq, s_ent, s_wl);
         KSS_STAMP(15);
         __syncthreads();
         // Phase C: every lane reads its column
@@ -1058,11 +1049,6 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
                     st = make_float2(0.f, 0.f);
                 }
             }
-        }
-        if constexpr (BATCH) {   // (the query comes back from memory rather than staying in registers across the search)
-            p = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (valid) p = src_out_k[i];
-            qx = p.x; qy = p.y; qz = p.z;
         }
     }
     if (valid && have) {
@@ -1087,8 +1073,8 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
     double v = 0.0 + r;                    // a single-chunk pair: exactly what the reducer computes from one row
     if (pr.n_rows > 1) {
         // the row goes out as granules (kss_device.hpp); the pair's FIRST workgroup, once its own row is out, adds the rows up
-        // -- in this launch, or in gridb_finalize_kernel after it (a.defer_pairs: more pairs than compute units).  Every
-        // other workgroup is done the moment its row is stored.  The reducer's poll is bounded.
+        // (a.defer_pairs is a batch's, for gridb_finalize_kernel: 0 here).  Every other workgroup is done the moment its row is
+        // stored.  The reducer's poll is bounded.
         Granule* const rows = a.rows + (int64_t)pr.row_base * NSUMS;
         if (threadIdx.x < NSUMS) row_put(rows + (int64_t)(w - pr.row_base) * NSUMS, threadIdx.x, r, seq_k);
         KSS_STAMP(3);
@@ -1100,7 +1086,7 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
     }
     if (threadIdx.x < NSUMS) {
         if (!FULL && (threadIdx.x == 17 || threadIdx.x == 18)) v = 0.0;
-        const int64_t slot = (int64_t)pi * NSUMS + threadIdx.x;
+        const int64_t slot = threadIdx.x;
         if (a.test_torn && threadIdx.x == 5) {   // test hook: first a slot whose data does not fit its check word, the real one a while later
             pub_put(a.pub, slot, v, seq_k, 0x00100000u);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1116,7 +1102,7 @@ __global__ __launch_bounds__(PASS_BS, BATCH ? KSS_BATCH_WAVES : KSS_SINGLE_WAVES
 
 // =============================================================================================
 // The batched form of the fused pass with TWO sources per lane: a workgroup of 256 threads (4 waves) serves the same
-// row of 512 sources as a 512-thread workgroup of grid_pass_kernel<BATCH = true>, same phases, same hand-over columns, same
+// row of 512 sources as a 512-thread workgroup of grid_pass_kernel would, same phases, same hand-over columns, same
 // sums in the same order -- lane l of wave v holds the sources that lane l of "waves" v and v + 4 hold there, and the wave
 // tree runs once per half -- so every bit of the result is the same.  Why: the batched pass is RESIDENCY-bound (a
 // workgroup's life is a chain of dependent memory round trips, ~12 us, while its instructions fit in ~1.5 us); with half
@@ -1639,41 +1625,35 @@ void launch_grid_pass(hipStream_t st, bool fma, bool full, bool batch, bool sear
     if (a.total_rows <= 0) return;
     const dim3 grid(grid_pass_blocks(a.total_rows)), block(PASS_BS);
     static const bool first_pass = getenv("KSS_FIRST_PASS") == nullptr || atoi(getenv("KSS_FIRST_PASS")) != 0;   // A/B: 0 = the plain pass first as well (same bits)
-#define KSS_PASS(F, U, B, S) hipLaunchKernelGGL((grid_pass_kernel<F, U, B, S, false>), grid, block, 0, st, a)
-#define KSS_CHAIN(F, U) hipLaunchKernelGGL((grid_pass_kernel<F, U, false, true, true>), grid, block, 0, st, a)
+#define KSS_PASS(F, U, S) hipLaunchKernelGGL((grid_pass_kernel<F, U, S, false>), grid, block, 0, st, a)
+#define KSS_CHAIN(F, U) hipLaunchKernelGGL((grid_pass_kernel<F, U, true, true>), grid, block, 0, st, a)
     if (!search) {   // sums-only relaunch after the list pass: single pair, all 20 sums
-        if (fma) KSS_PASS(true, true, false, false); else KSS_PASS(false, true, false, false);
+        if (fma) KSS_PASS(true, true, false); else KSS_PASS(false, true, false);
     } else if (batch) {
         // two sources per lane (gridb_pass_kernel); the first pass of a registration (every source searches) with the wide
-        // range queue.  KSS_BATCH_OLD: the one-source-per-lane form of grid_pass_kernel (A/B; same bits).
-        static const bool old_form = getenv("KSS_BATCH_OLD") != nullptr;
-        if (old_form) {
-            if (fma) { if (full) KSS_PASS(true, true, true, true); else KSS_PASS(true, false, true, true); }
-            else     { if (full) KSS_PASS(false, true, true, true); else KSS_PASS(false, false, true, true); }
-        } else {
-            const dim3 block2(256);
+        // range queue
+        const dim3 block2(256);
 #define KSS_PASSB(F, U, Q) hipLaunchKernelGGL((gridb_pass_kernel<F, U, Q>), grid, block2, 0, st, a)
-            if (!a.use_prev) {
-                if (fma) { if (full) KSS_PASSB(true, true, 256); else KSS_PASSB(true, false, 256); }
-                else     { if (full) KSS_PASSB(false, true, 256); else KSS_PASSB(false, false, 256); }
-            } else {
-                if (fma) { if (full) KSS_PASSB(true, true, 128); else KSS_PASSB(true, false, 128); }
-                else     { if (full) KSS_PASSB(false, true, 128); else KSS_PASSB(false, false, 128); }
-            }
-#undef KSS_PASSB
+        if (!a.use_prev) {
+            if (fma) { if (full) KSS_PASSB(true, true, 256); else KSS_PASSB(true, false, 256); }
+            else     { if (full) KSS_PASSB(false, true, 256); else KSS_PASSB(false, false, 256); }
+        } else {
+            if (fma) { if (full) KSS_PASSB(true, true, 128); else KSS_PASSB(true, false, 128); }
+            else     { if (full) KSS_PASSB(false, true, 128); else KSS_PASSB(false, false, 128); }
         }
+#undef KSS_PASSB
         if (a.defer_pairs) hipLaunchKernelGGL(gridb_finalize_kernel, dim3(a.defer_pairs), dim3(256), 0, st, a, full ? 1 : 0);
     } else if (a.chain_len > 1) {
         if (fma) { if (full) KSS_CHAIN(true, true); else KSS_CHAIN(true, false); }
         else     { if (full) KSS_CHAIN(false, true); else KSS_CHAIN(false, false); }
     } else if (first_pass && !a.use_prev) {   // no source has a candidate: the two-stage walk, one round
-#define KSS_FIRST(F, U) hipLaunchKernelGGL((grid_pass_kernel<F, U, false, true, false, true>), grid, block, 0, st, a)
+#define KSS_FIRST(F, U) hipLaunchKernelGGL((grid_pass_kernel<F, U, true, false, true>), grid, block, 0, st, a)
         if (fma) { if (full) KSS_FIRST(true, true); else KSS_FIRST(true, false); }
         else     { if (full) KSS_FIRST(false, true); else KSS_FIRST(false, false); }
 #undef KSS_FIRST
     } else {
-        if (fma) { if (full) KSS_PASS(true, true, false, true); else KSS_PASS(true, false, false, true); }
-        else     { if (full) KSS_PASS(false, true, false, true); else KSS_PASS(false, false, false, true); }
+        if (fma) { if (full) KSS_PASS(true, true, true); else KSS_PASS(true, false, true); }
+        else     { if (full) KSS_PASS(false, true, true); else KSS_PASS(false, false, true); }
     }
 #undef KSS_PASS
 #undef KSS_CHAIN

@@ -622,3 +622,77 @@ def test_growing_registrations_on_one_context(pkg):
             assert np.array_equal(r["T"], one["T"]) and r["iterations"] == one["iterations"] and r["fitness"] == one["fitness"]
     finally:
         del os.environ["KSS_COUNTS_CHECK"]
+
+
+# ---- the four endings of plain kss_icp / kss_icp_batch on every engine of the point-to-point path ----
+_ENDINGS = ("zero", "few", "conv", "limit")
+_ENDINGS_CODE = r"""
+import sys, json, numpy as np
+sys.path.insert(0, %r)
+import __graft_entry__ as g
+pkg = g.load_package(); S = pkg.synth; ctx = pkg.Context(0)
+pairs = []
+for i, (ns, nt) in enumerate(((600, 640), (513, 590), (530, 520))):
+    s, t = S.make_pair(760 + i, max(ns, nt), R=S.rot_axis_angle([0.2, 0.1, 1.0], np.deg2rad(5.0 + 2 * i)), t=(0.02, -0.01, 0.01 * i), shape="bumpy")
+    pairs.append((s[:ns].copy(), t[:nt].copy()))
+src_all = np.concatenate([p[0] for p in pairs]); tgt_all = np.concatenate([p[1] for p in pairs])
+so = np.concatenate([[0], np.cumsum([len(p[0]) for p in pairs])]).astype(np.int64)
+to = np.concatenate([[0], np.cumsum([len(p[1]) for p in pairs])]).astype(np.int64)
+kws = {"zero": dict(max_iterations=0), "few": dict(min_correspondences=601), "conv": dict(), "limit": dict(max_iterations=4)}
+out = {}
+for name, kw in kws.items():
+    o = {}
+    for eng, mode in (("grid", pkg.NN_GRID), ("brute", pkg.NN_BRUTE)):
+        r = ctx.icp(pairs[0][0], pairs[0][1], ctx.icp_params(nn_mode=mode, **kw), trace_cap=64, fitness_corr=True)
+        o[eng + "_single"] = [r["T"].tolist(), r["iterations"], r["state"], int(r["converged"]), r["fitness"], r["last_mse"],
+                              r["trace_sums"].tolist(), r["trace_Tk"].tolist(), r["fitness_idx"].tolist(), r["fitness_d2"].tolist()]
+        res = ctx.icp_batch(src_all, so, tgt_all, to, ctx.icp_params(nn_mode=mode, **kw))
+        o[eng + "_batch"] = [[np.array(list(b.T), np.float32).reshape(4, 4).tolist(), b.iterations, b.state, int(b.converged), b.fitness, b.last_mse] for b in res]
+    out[name] = o
+print("RESULT" + json.dumps(out))
+"""
+_endings_cache = {}
+
+
+def _endings_runs():
+    """Every ending on every engine, once: the chain and the resident batch as they run by default, plain launches per pass for the
+    single pair and the batch (KSS_GATED=0, KSS_RESIDENT=0); brute force by nn_mode."""
+    import subprocess, sys, json
+    if not _endings_cache:
+        for name, extra in (("default", {}), ("per_pass", {"KSS_GATED": "0", "KSS_RESIDENT": "0"})):
+            r = subprocess.run([sys.executable, "-c", _ENDINGS_CODE % ROOT], capture_output=True, text=True, timeout=120, env=dict(os.environ, **extra))
+            assert r.returncode == 0, name + r.stdout + r.stderr
+            _endings_cache[name] = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT")][0][6:])
+    return _endings_cache
+
+
+@pytest.mark.parametrize("ending", _ENDINGS)
+def test_icp_endings_same_record_on_every_engine(ending):
+    """max_iterations = 0, too few correspondences, converged and the iteration limit, for one 600 x 640 pair and a batch of three
+    small pairs forced onto the cell lists (nn_mode = GRID): the chain, plain launches per pass, the resident batch and the
+    launch-per-pass batch give the same record bit for bit -- the traced rows and the fitness pass's
+    correspondences of the single pair included --, the batch's first record is the single pair's, and brute force, whose f64
+    sums are grouped differently, ends the same way within test_grid_icp_bitwise_equals_brute's bars (same NN bits: T 1e-6,
+    fitness and MSE 1e-12)."""
+    runs = _endings_runs()
+    base = runs["default"][ending]
+    per_pass = runs["per_pass"][ending]
+    assert per_pass["grid_single"] == base["grid_single"] and per_pass["grid_batch"] == base["grid_batch"]
+    assert per_pass["brute_single"] == base["brute_single"] and per_pass["brute_batch"] == base["brute_batch"]
+    assert base["grid_batch"][0] == base["grid_single"][:6]
+    assert base["brute_batch"][0] == base["brute_single"][:6]
+    for grid, brute in zip([base["grid_single"][:6]] + base["grid_batch"], [base["brute_single"][:6]] + base["brute_batch"]):
+        assert grid[1:4] == brute[1:4]
+        assert np.abs(np.array(grid[0]) - np.array(brute[0])).max() < 1e-6
+        assert abs(grid[4] - brute[4]) < 1e-12 and abs(grid[5] - brute[5]) < 1e-12
+    assert base["grid_single"][8] == base["brute_single"][8] and len(base["grid_single"][8]) == 600   # the fitness pass's correspondences
+    T, iters, state, conv = base["grid_single"][:4]
+    ident = np.eye(4).tolist()
+    if ending == "zero":
+        assert (iters, state, conv) == (0, 0, 0) and T == ident and base["grid_single"][6] == []
+    elif ending == "few":
+        assert (iters, state, conv) == (0, 5, 0) and T == ident and all(b[1:4] == [0, 5, 0] for b in base["grid_batch"])
+    elif ending == "conv":
+        assert conv == 1 and state in (2, 3, 4) and 1 <= iters < 64 and len(base["grid_single"][6]) == iters
+    else:
+        assert (iters, state, conv) == (4, 1, 1) and all(b[1:4] == [4, 1, 1] for b in base["grid_batch"])
