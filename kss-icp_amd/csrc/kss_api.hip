@@ -423,74 +423,131 @@ int kss_rigid_from_sums(const double sums[KSS_NSUMS], float T[16]) {
     return KSS_OK;
 }
 
-// ---- point-to-plane ---------------------------------------------------------------------------------
-int kss_p2l_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n,
-                     int64_t nt, double max_d2, double sums[KSS_P2L_NSUMS]) {
-    if (!c || !d_src || !d_tgt || !d_nrm || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "p2l_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "p2l_sums: empty input");
-    HIPCHK(c, hipSetDevice(c->device));
-    PairMode mode;
-    mode.plane = true;
-    return pair_record_dev(c, d_src, d_tgt, d_nrm, d_idx, n, nt, max_d2, mode, nullptr, sums, nullptr);
-}
-
-int kss_p2l_sums(kss_ctx* c, const float* src, const float* tgt, const float* nrm, const int32_t* idx, int64_t n, int64_t nt,
-                 double max_d2, double sums[KSS_P2L_NSUMS]) {
-    if (!c || !src || !tgt || !nrm || !idx || !sums) return set_err(c, KSS_ERR_ARG, "p2l_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "p2l_sums: empty input");
-    for (int64_t i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= nt) return set_err(c, KSS_ERR_ARG, "p2l_sums: index out of range");
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
-    return kss_p2l_sums_dev(c, (const float*)c->stage_src.p, (const float*)c->stage_tgt.p, (const float*)c->p2l_nrm.p,
-                            (const int32_t*)c->stage_idx.p, n, nt, max_d2, sums);
-}
-
-int kss_rigid_from_p2l_sums(const double sums[KSS_P2L_NSUMS], float T[16]) {
-    if (!sums || !T) return KSS_ERR_ARG;
-    if (!rigid_from_p2l_sums(sums, T)) {
-        mat4_identity(T);
-        return KSS_ERR_DEGENERATE;
-    }
-    return KSS_OK;
-}
-
-// ---- what kss_icp_p2l[_dev] and kss_icp_trimmed[_dev] share ----
+// ---- the pair metrics --------------------------------------------------------------
+// What the 46 entry points kss_*_sums, kss_icp_* and kss_icp_*_batch of p2l, trimmed, sim, robust, gicp, symm, symm_robust, o2o and
+// recip share.  A host entry and its _dev twin call one internal function with `host` set or not, and that function reads: family
+// check, shared check (pair_check / sums_check), pair_enter, pair_normals, the family's mode, the run (pair_go / pair_record_dev).
 static inline bool trim_overlap_ok(double overlap) { return overlap > 0.0 && overlap <= 1.0; }   // (a NaN fails both)
 
-// the argument check of both families, single pair and batch.  who: the name the messages carry; tp: null for kss_icp_p2l.
-// Batch (src_off given): ns / nt are not read, every pair's counts come from the npairs + 1 offsets, and overlaps (may be null:
-// tp->overlap for every pair) holds one overlap per pair.
-static int pair_check(kss_ctx* c, const char* who, bool trimmed, const void* src, const void* tgt, int64_t ns, int64_t nt, const float* nrm,
-                      const kss_icp_params* p, const kss_trim_params* tp, const kss_icp_result* res,
-                      const int64_t* src_off = nullptr, const int64_t* tgt_off = nullptr, int npairs = 1, const double* overlaps = nullptr) {
+// What a call brings.  Host pointers at a host entry until pair_enter has staged them, device pointers otherwise.
+struct PairClouds {
+    const float* src = nullptr;
+    const float* tgt = nullptr;
+    const float* snrm = nullptr;          // the source's normals (generalized, symmetric) and the target's; null: none given
+    const float* tnrm = nullptr;
+    int64_t ns = 0, nt = 0;               // one pair (*_sums: n, nt); a batch behind pair_rebase: the totals
+    bool batch = false;                   // a batch: npairs + 1 offsets in points per side, from 0 behind pair_rebase
+    const int64_t* src_off = nullptr;
+    const int64_t* tgt_off = nullptr;
+    int npairs = 1;
+    std::vector<int64_t> so, to;          // (pair_rebase's offsets)
+};
+static PairClouds one_pair(const float* src, int64_t ns, const float* snrm, const float* tgt, int64_t nt, const float* tnrm) {
+    PairClouds P;
+    P.src = src; P.ns = ns; P.snrm = snrm; P.tgt = tgt; P.nt = nt; P.tnrm = tnrm;
+    return P;
+}
+static PairClouds many_pairs(const float* src, const int64_t* src_off, const float* snrm, const float* tgt, const int64_t* tgt_off,
+                             const float* tnrm, int npairs) {
+    PairClouds P;
+    P.src = src; P.src_off = src_off; P.snrm = snrm; P.tgt = tgt; P.tgt_off = tgt_off; P.tnrm = tnrm; P.npairs = npairs; P.batch = true;
+    return P;
+}
+
+// the family check of the families whose parameters hold nothing to check beyond what pair_check reads
+static int params_check(kss_ctx* c, const char* who, const void* params) {
+    return params ? KSS_OK : set_err(c, KSS_ERR_ARG, (std::string(who) + ": null argument").c_str());
+}
+
+// The shared check of every kss_icp_* entry, single pair and batch.  who: the name the messages carry; out: the result(s); noun: the
+// family as the allreduce refusal names it; overlap (null: not a trimmed family), metric, overlaps (may be null: *overlap for every
+// pair): what the trimmed families' parameters hold.  A batch's counts come from the npairs + 1 offsets; ns / nt are not read.
+static int pair_check(kss_ctx* c, const char* who, const PairClouds& P, const kss_icp_params* p, const void* out, const char* noun,
+                      const double* overlap = nullptr, int metric = KSS_METRIC_PLANE, const double* overlaps = nullptr) {
+    if (!c) return KSS_ERR_ARG;
     const std::string w = std::string(who) + ": ";
     auto bad = [&](const std::string& what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
-    if (!src || !tgt || !p || !res || (trimmed && !tp)) return bad("null argument");
-    if (src_off) {
-        if (!tgt_off || npairs <= 0) return bad("bad batch");
-        for (int i = 0; i < npairs; ++i) {
-            const int64_t n = src_off[i + 1] - src_off[i], m = tgt_off[i + 1] - tgt_off[i];
+    if (P.batch && (!P.src_off || !P.tgt_off || P.npairs <= 0)) return bad("bad batch");
+    if (!P.src || !P.tgt || !p || !out) return bad("null argument");
+    if (P.batch) {
+        for (int i = 0; i < P.npairs; ++i) {
+            const int64_t n = P.src_off[i + 1] - P.src_off[i], m = P.tgt_off[i + 1] - P.tgt_off[i];
             if (n <= 0 || m <= 0) return bad("empty pair");
             if (n > 0x7fff0000ll || m > 0x7fff0000ll) return bad("cloud too large");
         }
-        if (src_off[npairs] - src_off[0] > 0x7fff0000ll || tgt_off[npairs] - tgt_off[0] > 0x7fff0000ll) return bad("batch too large");
+        if (P.src_off[P.npairs] - P.src_off[0] > 0x7fff0000ll || P.tgt_off[P.npairs] - P.tgt_off[0] > 0x7fff0000ll) return bad("batch too large");
     } else {
-        if (ns <= 0 || nt <= 0) return bad("empty cloud");
-        if (ns > 0x7fff0000ll || nt > 0x7fff0000ll) return bad("cloud too large");
+        if (P.ns <= 0 || P.nt <= 0) return bad("empty cloud");
+        if (P.ns > 0x7fff0000ll || P.nt > 0x7fff0000ll) return bad("cloud too large");
     }
-    if (p->allreduce) return bad(std::string("the source-row split (allreduce) is not available for ") + (trimmed ? "trimmed ICP" : "point-to-plane"));
-    if (!trimmed) return KSS_OK;
+    if (p->allreduce) return bad(std::string("the source-row split (allreduce) is not available for ") + noun);
+    if (!overlap) return KSS_OK;
     if (overlaps) {
-        for (int i = 0; i < npairs; ++i)
+        for (int i = 0; i < P.npairs; ++i)
             if (!trim_overlap_ok(overlaps[i])) return bad("overlap must be in (0, 1]");
-    } else if (!trim_overlap_ok(tp->overlap)) return bad("overlap must be in (0, 1]");
-    if (tp->metric != KSS_METRIC_POINT && tp->metric != KSS_METRIC_PLANE) return bad("unknown metric");
-    if (tp->metric == KSS_METRIC_POINT && nrm) return bad("the point metric takes no normals");
+    } else if (!trim_overlap_ok(*overlap)) return bad("overlap must be in (0, 1]");
+    if (metric != KSS_METRIC_POINT && metric != KSS_METRIC_PLANE) return bad("unknown metric");
+    if (metric == KSS_METRIC_POINT && P.tnrm) return bad("the point metric takes no normals");
     return KSS_OK;
+}
+
+// the same of every kss_*_sums entry; also: the entry's further required pointers are there
+static int sums_check(kss_ctx* c, const char* who, const PairClouds& P, const int32_t* idx, const double* sums, bool also = true) {
+    if (!c) return KSS_ERR_ARG;
+    const std::string w = std::string(who) + ": ";
+    if (!P.src || !P.tgt || !idx || !sums || !also) return set_err(c, KSS_ERR_ARG, (w + "null argument").c_str());
+    if (P.ns <= 0 || P.nt <= 0) return set_err(c, KSS_ERR_ARG, (w + "empty input").c_str());
+    if (P.ns > 0x7fff0000ll || P.nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, (w + "cloud too large").c_str());
+    return KSS_OK;
+}
+
+// A batch's offsets rebased to its first pair and its pointers advanced to it, so that every buffer of the call is indexed from 0
+// (pointer arithmetic only: host and device pointers alike); P.ns / P.nt become the totals.
+static void pair_rebase(PairClouds& P) {
+    if (!P.batch) return;
+    const int64_t s0 = P.src_off[0], t0 = P.tgt_off[0];
+    P.so.resize((size_t)P.npairs + 1); P.to.resize((size_t)P.npairs + 1);
+    for (int i = 0; i <= P.npairs; ++i) { P.so[i] = P.src_off[i] - s0; P.to[i] = P.tgt_off[i] - t0; }
+    P.src_off = P.so.data(); P.tgt_off = P.to.data();
+    P.ns = P.so[P.npairs]; P.nt = P.to[P.npairs];
+    P.src += 3 * s0; P.tgt += 3 * t0;
+    if (P.snrm) P.snrm += 3 * s0;
+    if (P.tnrm) P.tnrm += 3 * t0;
+}
+
+// Host callers: the clouds, the normals given and (*_sums) the correspondences go to the device, and P / *idx hold device pointers.
+// One pair: stage_src, stage_tgt, gicp_snrm, p2l_nrm; a batch: its slice of the packed arrays into stage_src, stage_tgt, pb_snrm, pb_nrm.
+static int pair_stage(kss_ctx* c, PairClouds& P, const int32_t** idx) {
+    const size_t sb = (size_t)P.ns * 3 * sizeof(float), tb = (size_t)P.nt * 3 * sizeof(float);
+    KCHK(upload(c, c->stage_src, P.src, sb));
+    KCHK(upload(c, c->stage_tgt, P.tgt, tb));
+    P.src = (const float*)c->stage_src.p; P.tgt = (const float*)c->stage_tgt.p;
+    if (P.snrm) {
+        DevBuf& b = P.batch ? c->pb_snrm : c->gicp_snrm;
+        KCHK(upload(c, b, P.snrm, sb));
+        P.snrm = (const float*)b.p;
+    }
+    if (P.tnrm) {
+        DevBuf& b = P.batch ? c->pb_nrm : c->p2l_nrm;
+        KCHK(upload(c, b, P.tnrm, tb));
+        P.tnrm = (const float*)b.p;
+    }
+    if (idx) {
+        KCHK(upload(c, c->stage_idx, *idx, (size_t)P.ns * sizeof(int32_t)));
+        *idx = (const int32_t*)c->stage_idx.p;
+    }
+    return KSS_OK;
+}
+
+// Behind the checks: the call's clouds on the device, indexed from 0.  range_who: a host *_sums entry that refuses correspondences
+// outside the target under that name (kss_sim_sums and kss_robust_sums never looked at theirs).
+static int pair_enter(kss_ctx* c, bool host, PairClouds& P, const int32_t** idx = nullptr, const char* range_who = nullptr) {
+    if (host && range_who)
+        for (int64_t i = 0; i < P.ns; ++i)
+            if ((*idx)[i] < 0 || (*idx)[i] >= P.nt) return set_err(c, KSS_ERR_ARG, (std::string(range_who) + ": index out of range").c_str());
+    HIPCHK(c, hipSetDevice(c->device));
+    pair_rebase(P);
+    return host ? pair_stage(c, P, idx) : KSS_OK;
 }
 
 // A cloud's normals where the caller gave none: kss_normals' definition (k incl. the point itself, view-point flip, renormalised
@@ -508,35 +565,108 @@ static int cloud_normals_dev(kss_ctx* c, const float* d_pts, int64_t n, int kk, 
     *d_nrm = (const float*)out.p;
     return KSS_OK;
 }
-// the target's, k = 20 (kss_icp_p2l, kss_icp_trimmed, kss_icp_robust)
-static int target_normals_dev(kss_ctx* c, const float* d_tgt, int64_t nt, const float** d_nrm) {
-    return cloud_normals_dev(c, d_tgt, nt, 20, c->p2l_nrm, d_nrm);
+// The same for every cloud of a batch, cloud after cloud (off: npairs + 1 offsets in points from 0), into the packed buffer `out`
+// laid out like the clouds (setup cost of the call, not optimised: a k-NN and a normals launch per cloud); p2l_nrm is the scratch.
+static int batch_normals_dev(kss_ctx* c, const float* d_pts, const int64_t* off, int npairs, int k, DevBuf& out, const float** d_nrm) {
+    KCHK(ensure(c, out, (size_t)off[npairs] * 3 * sizeof(float)));
+    for (int i = 0; i < npairs; ++i) {
+        const int64_t n = off[i + 1] - off[i];
+        const float* one = nullptr;
+        KCHK(cloud_normals_dev(c, d_pts + 3 * off[i], n, k, c->p2l_nrm, &one));
+        HIPCHK(c, hipMemcpyAsync((float*)out.p + 3 * off[i], one, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    }
+    *d_nrm = (const float*)out.p;
+    return KSS_OK;
+}
+// Whichever normals of the call are missing, at k (20 for the plane metric, normals_k for generalized and symmetric), from the clouds
+// as passed in: the target's into p2l_nrm (a batch: pb_nrm) and, source set, the source's into gicp_snrm (pb_snrm).
+static int pair_normals(kss_ctx* c, PairClouds& P, int k, bool source) {
+    if (!P.tnrm) KCHK(P.batch ? batch_normals_dev(c, P.tgt, P.tgt_off, P.npairs, k, c->pb_nrm, &P.tnrm)
+                              : cloud_normals_dev(c, P.tgt, P.nt, k, c->p2l_nrm, &P.tnrm));
+    if (source && !P.snrm) KCHK(P.batch ? batch_normals_dev(c, P.src, P.src_off, P.npairs, k, c->pb_snrm, &P.snrm)
+                                        : cloud_normals_dev(c, P.src, P.ns, k, c->gicp_snrm, &P.snrm));
+    return KSS_OK;
 }
 
-int kss_icp_p2l_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
-                    const kss_icp_params* p, kss_icp_result* res) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(pair_check(c, "icp_p2l", false, d_src, d_tgt, ns, nt, d_nrm, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
+static RobustScale robust_scale_of(const kss_robust_params* rp, double scale);
+
+// The run.  One pair: pair_run_dev, info its last_info.  A batch: pairs_run_dev, info its info_all, with the per-pair tables of the
+// mode: the mode's own value for every pair unless the caller's array (overlaps, scales of rp, epsilons, aligns) gives each its own.
+static int pair_go(kss_ctx* c, const PairClouds& P, const kss_icp_params* p, PairMode mode, kss_icp_result* res, double* info,
+                   const double* overlaps = nullptr, const kss_robust_params* rp = nullptr, const double* scales = nullptr,
+                   const double* epsilons = nullptr, const int32_t* aligns = nullptr) {
+    if (!P.batch) {
+        mode.last_info = info;
+        return pair_run_dev(c, P.src, P.ns, P.tgt, P.nt, P.tnrm, p, mode, res);
+    }
+    const size_t np = (size_t)P.npairs;
+    std::vector<double> ov(np, mode.overlap), eps(np, mode.gicp_epsilon);
+    std::vector<RobustScale> rs(np, mode.rs);
+    std::vector<int32_t> al(np, mode.symm_align);
+    if (overlaps) ov.assign(overlaps, overlaps + np);
+    if (scales)
+        for (size_t i = 0; i < np; ++i) rs[i] = robust_scale_of(rp, scales[i]);
+    if (epsilons) eps.assign(epsilons, epsilons + np);
+    if (aligns) al.assign(aligns, aligns + np);
+    return pairs_run_dev(c, P.src, P.src_off, P.tgt, P.tgt_off, P.tnrm, P.npairs, p, mode, mode.trimmed ? ov.data() : nullptr, res, info,
+                         mode.robust ? rs.data() : nullptr, mode.gicp ? eps.data() : nullptr, mode.symm ? al.data() : nullptr);
+}
+
+// ---- point-to-plane -------------------------------------------------------------
+static PairMode p2l_mode_of() {
     PairMode mode;
     mode.plane = true;
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
+    return mode;
 }
 
+static int p2l_sums_any(kss_ctx* c, bool host, PairClouds P, const int32_t* idx, double max_d2, double* sums) {
+    KCHK(sums_check(c, "p2l_sums", P, idx, sums, P.tnrm != nullptr));
+    KCHK(pair_enter(c, host, P, &idx, "p2l_sums"));
+    return pair_record_dev(c, P.src, P.tgt, P.tnrm, idx, P.ns, P.nt, max_d2, p2l_mode_of(), nullptr, sums, nullptr);
+}
+int kss_p2l_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n,
+                     int64_t nt, double max_d2, double sums[KSS_P2L_NSUMS]) {
+    return p2l_sums_any(c, false, one_pair(d_src, n, nullptr, d_tgt, nt, d_nrm), d_idx, max_d2, sums);
+}
+int kss_p2l_sums(kss_ctx* c, const float* src, const float* tgt, const float* nrm, const int32_t* idx, int64_t n, int64_t nt,
+                 double max_d2, double sums[KSS_P2L_NSUMS]) {
+    return p2l_sums_any(c, true, one_pair(src, n, nullptr, tgt, nt, nrm), idx, max_d2, sums);
+}
+
+int kss_rigid_from_p2l_sums(const double sums[KSS_P2L_NSUMS], float T[16]) {
+    if (!sums || !T) return KSS_ERR_ARG;
+    if (!rigid_from_p2l_sums(sums, T)) {
+        mat4_identity(T);
+        return KSS_ERR_DEGENERATE;
+    }
+    return KSS_OK;
+}
+
+static int icp_p2l_any(kss_ctx* c, const char* who, bool host, PairClouds P, const kss_icp_params* p, kss_icp_result* res) {
+    KCHK(pair_check(c, who, P, p, res, "point-to-plane"));
+    KCHK(pair_enter(c, host, P));
+    KCHK(pair_normals(c, P, 20, false));
+    return pair_go(c, P, p, p2l_mode_of(), res, nullptr);
+}
+int kss_icp_p2l_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                    const kss_icp_params* p, kss_icp_result* res) {
+    return icp_p2l_any(c, "icp_p2l", false, one_pair(d_src, ns, nullptr, d_tgt, nt, d_nrm), p, res);
+}
 int kss_icp_p2l(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
                 const kss_icp_params* p, kss_icp_result* res) {
-    if (!c || !src || !tgt) return set_err(c, KSS_ERR_ARG, "icp_p2l: null cloud");
-    KCHK(pair_check(c, "icp_p2l", false, src, tgt, ns, nt, nrm, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_p2l_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
-                           p, res);
+    if (!c || !src || !tgt) return set_err(c, KSS_ERR_ARG, "icp_p2l: null cloud");   // (its own wording, kept)
+    return icp_p2l_any(c, "icp_p2l", true, one_pair(src, ns, nullptr, tgt, nt, nrm), p, res);
+}
+int kss_icp_p2l_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
+                          const float* d_nrm_all, int npairs, const kss_icp_params* p, kss_icp_result* results) {
+    return icp_p2l_any(c, "icp_p2l_batch", false, many_pairs(d_src_all, src_off, nullptr, d_tgt_all, tgt_off, d_nrm_all, npairs), p, results);
+}
+int kss_icp_p2l_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
+                      const float* nrm_all, int npairs, const kss_icp_params* p, kss_icp_result* results) {
+    return icp_p2l_any(c, "icp_p2l_batch", true, many_pairs(src_all, src_off, nullptr, tgt_all, tgt_off, nrm_all, npairs), p, results);
 }
 
-// ---- trimmed ICP -------------------------------------------------------------------
+// ---- trimmed ICP ---------------------------------------------------------------
 int kss_trim_rank(int64_t m, double overlap, int64_t* k) {
     if (!k || m < 0 || !trim_overlap_ok(overlap)) return KSS_ERR_ARG;
     *k = (int64_t)trim_rank_of((long long)m, overlap);
@@ -561,31 +691,50 @@ int kss_trim_threshold(kss_ctx* c, const float* d2, int64_t n, double max_d2, do
     return trim_threshold_dev(c, (const float*)c->stage_d2.p, n, max_d2, overlap, info);
 }
 
+// the trimmed pass of kss_icp_trimmed; kss_icp_o2o and kss_icp_recip put their rejection in front of it (o2o_mode_of, recip_mode_of)
+static PairMode trimmed_mode(double overlap, int metric, double* trace) {
+    PairMode mode;
+    mode.plane = metric == KSS_METRIC_PLANE;
+    mode.trimmed = true;
+    mode.overlap = overlap;
+    mode.trace_info = trace;
+    return mode;
+}
+static PairMode trim_mode_of(const kss_trim_params* tp) { return trimmed_mode(tp->overlap, tp->metric, tp->trace_trim); }
+
+// the entries of the four families on the trimmed pass (trimmed, sim, o2o, recip) behind their family check; metric: as given
+static int icp_trimmed_any(kss_ctx* c, const char* who, bool host, PairClouds P, const kss_icp_params* p, const PairMode& mode, int metric,
+                           const double* overlaps, kss_icp_result* res, double* info) {
+    KCHK(pair_check(c, who, P, p, res, "trimmed ICP", &mode.overlap, metric, overlaps));
+    KCHK(pair_enter(c, host, P));
+    if (mode.plane) KCHK(pair_normals(c, P, 20, false));
+    return pair_go(c, P, p, mode, res, info, overlaps);
+}
 int kss_icp_trimmed_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                         const kss_icp_params* p, const kss_trim_params* tp, kss_icp_result* res, double last_info[KSS_TRIM_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(pair_check(c, "icp_trimmed", true, d_src, d_tgt, ns, nt, d_nrm, p, tp, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    PairMode mode;
-    mode.plane = tp->metric == KSS_METRIC_PLANE;
-    mode.trimmed = true;
-    mode.overlap = tp->overlap;
-    mode.trace_info = tp->trace_trim;
-    mode.last_info = last_info;
-    if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
+    KCHK(params_check(c, "icp_trimmed", tp));
+    return icp_trimmed_any(c, "icp_trimmed", false, one_pair(d_src, ns, nullptr, d_tgt, nt, d_nrm), p, trim_mode_of(tp), tp->metric, nullptr, res,
+                           last_info);
 }
-
 int kss_icp_trimmed(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
                     const kss_icp_params* p, const kss_trim_params* tp, kss_icp_result* res, double last_info[KSS_TRIM_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(pair_check(c, "icp_trimmed", true, src, tgt, ns, nt, nrm, p, tp, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_trimmed_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
-                               p, tp, res, last_info);
+    KCHK(params_check(c, "icp_trimmed", tp));
+    return icp_trimmed_any(c, "icp_trimmed", true, one_pair(src, ns, nullptr, tgt, nt, nrm), p, trim_mode_of(tp), tp->metric, nullptr, res,
+                           last_info);
+}
+int kss_icp_trimmed_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
+                              const float* d_nrm_all, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
+                              kss_icp_result* results, double* info_all) {
+    KCHK(params_check(c, "icp_trimmed_batch", tp));
+    return icp_trimmed_any(c, "icp_trimmed_batch", false, many_pairs(d_src_all, src_off, nullptr, d_tgt_all, tgt_off, d_nrm_all, npairs), p,
+                           trim_mode_of(tp), tp->metric, overlaps, results, info_all);
+}
+int kss_icp_trimmed_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
+                          const float* nrm_all, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
+                          kss_icp_result* results, double* info_all) {
+    KCHK(params_check(c, "icp_trimmed_batch", tp));
+    return icp_trimmed_any(c, "icp_trimmed_batch", true, many_pairs(src_all, src_off, nullptr, tgt_all, tgt_off, nrm_all, npairs), p,
+                           trim_mode_of(tp), tp->metric, overlaps, results, info_all);
 }
 
 // ---- similarity ICP ----------------------------------------------------------------
@@ -603,75 +752,62 @@ int kss_sim_from_sums(const double sums[KSS_NSUMS], double lo, double hi, float 
     return sim_from_sums(sums, lo, hi, T, s_k) ? KSS_OK : KSS_ERR_DEGENERATE;
 }
 
-int kss_sim_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const int32_t* d_idx, int64_t n, int64_t nt, double max_d2,
-                     double sums[KSS_NSUMS]) {
-    if (!c) return KSS_ERR_ARG;
-    if (!d_src || !d_tgt || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "sim_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "sim_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "sim_sums: cloud too large");
-    HIPCHK(c, hipSetDevice(c->device));
-    PairMode mode;   // (no trimming: the record of every correspondence within max_d2, no selection)
-    mode.sim = true;
-    return pair_record_dev(c, d_src, d_tgt, nullptr, d_idx, n, nt, max_d2, mode, nullptr, sums, nullptr);
-}
-
-int kss_sim_sums(kss_ctx* c, const float* src, const float* tgt, const int32_t* idx, int64_t n, int64_t nt, double max_d2,
-                 double sums[KSS_NSUMS]) {
-    if (!c) return KSS_ERR_ARG;
-    if (!src || !tgt || !idx || !sums) return set_err(c, KSS_ERR_ARG, "sim_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "sim_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "sim_sums: cloud too large");
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
-    return kss_sim_sums_dev(c, (const float*)c->stage_src.p, (const float*)c->stage_tgt.p, (const int32_t*)c->stage_idx.p, n, nt, max_d2, sums);
-}
-
-// the checks of sp that every entry point shares, and the trimmed point metric's parameters that pair_check reads
-static int sim_check(kss_ctx* c, const char* who, const kss_sim_params* sp, kss_trim_params* tp) {
+// the checks of sp; the overlap is the trimmed point metric's and pair_check's
+static int sim_check(kss_ctx* c, const char* who, const kss_sim_params* sp) {
     const std::string w = std::string(who) + ": ";
     if (!sp) return set_err(c, KSS_ERR_ARG, (w + "null argument").c_str());
     if (!(sp->scale_min > 0.0) || !(sp->scale_min <= 1.0) || !(sp->scale_max >= 1.0) || !std::isfinite(sp->scale_max))
         return set_err(c, KSS_ERR_ARG, (w + "the scale bounds must satisfy 0 < scale_min <= 1 <= scale_max < inf").c_str());
-    tp->overlap = sp->overlap; tp->metric = KSS_METRIC_POINT; tp->trace_trim = nullptr;
     return KSS_OK;
 }
+// sp null: kss_sim_sums' record of every correspondence within max_d2 (no trimming, no selection)
 static PairMode sim_mode_of(const kss_sim_params* sp) {
-    PairMode mode;
-    mode.trimmed = true;
+    PairMode mode = sp ? trimmed_mode(sp->overlap, KSS_METRIC_POINT, sp->trace_sim) : PairMode();
     mode.sim = true;
-    mode.overlap = sp->overlap;
-    mode.scale_min = sp->scale_min; mode.scale_max = sp->scale_max;
-    mode.trace_info = sp->trace_sim;
+    if (sp) { mode.scale_min = sp->scale_min; mode.scale_max = sp->scale_max; }
     return mode;
+}
+
+static int sim_sums_any(kss_ctx* c, bool host, PairClouds P, const int32_t* idx, double max_d2, double* sums) {
+    KCHK(sums_check(c, "sim_sums", P, idx, sums));
+    KCHK(pair_enter(c, host, P, &idx));
+    return pair_record_dev(c, P.src, P.tgt, nullptr, idx, P.ns, P.nt, max_d2, sim_mode_of(nullptr), nullptr, sums, nullptr);
+}
+int kss_sim_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const int32_t* d_idx, int64_t n, int64_t nt, double max_d2,
+                     double sums[KSS_NSUMS]) {
+    return sim_sums_any(c, false, one_pair(d_src, n, nullptr, d_tgt, nt, nullptr), d_idx, max_d2, sums);
+}
+int kss_sim_sums(kss_ctx* c, const float* src, const float* tgt, const int32_t* idx, int64_t n, int64_t nt, double max_d2,
+                 double sums[KSS_NSUMS]) {
+    return sim_sums_any(c, true, one_pair(src, n, nullptr, tgt, nt, nullptr), idx, max_d2, sums);
 }
 
 int kss_icp_sim_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const kss_icp_params* p,
                     const kss_sim_params* sp, kss_icp_result* res, double last_info[KSS_SIM_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    kss_trim_params tp;
-    KCHK(sim_check(c, "icp_sim", sp, &tp));
-    KCHK(pair_check(c, "icp_sim", true, d_src, d_tgt, ns, nt, nullptr, p, &tp, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    PairMode mode = sim_mode_of(sp);
-    mode.last_info = last_info;
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, nullptr, p, mode, res);
+    KCHK(sim_check(c, "icp_sim", sp));
+    return icp_trimmed_any(c, "icp_sim", false, one_pair(d_src, ns, nullptr, d_tgt, nt, nullptr), p, sim_mode_of(sp), KSS_METRIC_POINT, nullptr,
+                           res, last_info);
 }
-
 int kss_icp_sim(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const kss_icp_params* p, const kss_sim_params* sp,
                 kss_icp_result* res, double last_info[KSS_SIM_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    kss_trim_params tp;
-    KCHK(sim_check(c, "icp_sim", sp, &tp));
-    KCHK(pair_check(c, "icp_sim", true, src, tgt, ns, nt, nullptr, p, &tp, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_sim_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, p, sp, res, last_info);
+    KCHK(sim_check(c, "icp_sim", sp));
+    return icp_trimmed_any(c, "icp_sim", true, one_pair(src, ns, nullptr, tgt, nt, nullptr), p, sim_mode_of(sp), KSS_METRIC_POINT, nullptr, res,
+                           last_info);
+}
+int kss_icp_sim_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, int npairs,
+                          const kss_icp_params* p, const kss_sim_params* sp, const double* overlaps, kss_icp_result* results, double* info_all) {
+    KCHK(sim_check(c, "icp_sim_batch", sp));
+    return icp_trimmed_any(c, "icp_sim_batch", false, many_pairs(d_src, src_off, nullptr, d_tgt, tgt_off, nullptr, npairs), p, sim_mode_of(sp),
+                           KSS_METRIC_POINT, overlaps, results, info_all);
+}
+int kss_icp_sim_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off, int npairs,
+                      const kss_icp_params* p, const kss_sim_params* sp, const double* overlaps, kss_icp_result* results, double* info_all) {
+    KCHK(sim_check(c, "icp_sim_batch", sp));
+    return icp_trimmed_any(c, "icp_sim_batch", true, many_pairs(src, src_off, nullptr, tgt, tgt_off, nullptr, npairs), p, sim_mode_of(sp),
+                           KSS_METRIC_POINT, overlaps, results, info_all);
 }
 
-// ---- robust ICP --------------------------------------------------------------------
+// ---- robust ICP ----------------------------------------------------------------
 static inline bool robust_loss_ok(int loss) { return loss >= KSS_LOSS_L2 && loss <= KSS_LOSS_CAUCHY; }
 static inline bool robust_metric_ok(int metric) { return metric == KSS_METRIC_POINT || metric == KSS_METRIC_PLANE; }
 
@@ -703,17 +839,22 @@ int kss_robust_scale2(int metric, double tune, float med_key, double min_scale, 
     return KSS_OK;
 }
 
-// the checks of rp that kss_robust_sums and kss_icp_robust share
-static int robust_check(kss_ctx* c, const char* who, const kss_robust_params* rp, const float* nrm) {
+// the checks of rp, and of a batch's per-pair scales (null: rp->scale everywhere)
+static int robust_check(kss_ctx* c, const char* who, const kss_robust_params* rp, const float* nrm, int npairs = 0, const double* scales = nullptr) {
     const std::string w = std::string(who) + ": ";
     auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
     if (!rp) return bad("null argument");
     if (!robust_loss_ok(rp->loss)) return bad("unknown loss");
     if (!robust_metric_ok(rp->metric)) return bad("unknown metric");
     if (!(rp->scale >= 0.0) || !std::isfinite(rp->scale)) return bad("scale must be finite and >= 0");
-    if (rp->scale == 0.0 && (!(rp->tune > 0.0) || !std::isfinite(rp->tune))) return bad("tune must be finite and > 0");
+    const bool tune_ok = rp->tune > 0.0 && std::isfinite(rp->tune);
+    if (rp->scale == 0.0 && !tune_ok) return bad("tune must be finite and > 0");
     if (!(rp->min_scale >= 0.0)) return bad("min_scale must be >= 0");
     if (rp->metric == KSS_METRIC_POINT && nrm) return bad("the point metric takes no normals");
+    for (int i = 0; scales && i < npairs; ++i) {
+        if (!(scales[i] >= 0.0) || !std::isfinite(scales[i])) return bad("a scale must be finite and >= 0");
+        if (scales[i] == 0.0 && !tune_ok) return bad("tune must be finite and > 0");
+    }
     return KSS_OK;
 }
 
@@ -727,73 +868,63 @@ static RobustScale robust_scale_of(const kss_robust_params* rp, double scale) {
     rs.min2 = rp->min_scale * rp->min_scale;
     return rs;
 }
-static RobustScale robust_scale_of(const kss_robust_params* rp) { return robust_scale_of(rp, rp->scale); }
-
-int kss_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n, int64_t nt,
-                        double max_d2, const kss_robust_params* rp, double* sums, double info[KSS_ROBUST_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(robust_check(c, "robust_sums", rp, d_nrm));
-    const RobustScale rs = robust_scale_of(rp);
-    const bool plane = rp->metric == KSS_METRIC_PLANE;
-    if (!d_src || !d_tgt || !d_idx || !sums || !info || (plane && !d_nrm)) return set_err(c, KSS_ERR_ARG, "robust_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "robust_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "robust_sums: cloud too large");
-    HIPCHK(c, hipSetDevice(c->device));
-    PairMode mode;   // (the point metric's keys are written here and carry the whole candidate test; the bound is applied again, to the same effect)
-    mode.plane = plane;
-    mode.robust = true;
-    mode.rs = rs;
-    return pair_record_dev(c, d_src, d_tgt, d_nrm, d_idx, n, nt, max_d2, mode, nullptr, sums, info);
-}
-
-int kss_robust_sums(kss_ctx* c, const float* src, const float* tgt, const float* nrm, const int32_t* idx, int64_t n, int64_t nt,
-                    double max_d2, const kss_robust_params* rp, double* sums, double info[KSS_ROBUST_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(robust_check(c, "robust_sums", rp, nrm));
-    if (!src || !tgt || !idx || !sums || !info || (rp->metric == KSS_METRIC_PLANE && !nrm)) return set_err(c, KSS_ERR_ARG, "robust_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "robust_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "robust_sums: cloud too large");
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
-    return kss_robust_sums_dev(c, (const float*)c->stage_src.p, (const float*)c->stage_tgt.p, nrm ? (const float*)c->p2l_nrm.p : nullptr,
-                               (const int32_t*)c->stage_idx.p, n, nt, max_d2, rp, sums, info);
-}
-
-int kss_icp_robust_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
-                       const kss_icp_params* p, const kss_robust_params* rp, kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(robust_check(c, "icp_robust", rp, d_nrm));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_robust: the source-row split (allreduce) is not available for robust ICP");
-    KCHK(pair_check(c, "icp_robust", false, d_src, d_tgt, ns, nt, d_nrm, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
+static PairMode robust_mode_of(const kss_robust_params* rp) {
     PairMode mode;
     mode.plane = rp->metric == KSS_METRIC_PLANE;
     mode.robust = true;
-    mode.rs = robust_scale_of(rp);
+    mode.rs = robust_scale_of(rp, rp->scale);
     mode.trace_info = rp->trace_robust;
-    mode.last_info = last_info;
-    if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
+    return mode;
 }
 
+// (the point metric's keys are written by the record and carry the whole candidate test; the bound is applied again, to the same effect)
+static int robust_sums_any(kss_ctx* c, bool host, PairClouds P, const int32_t* idx, double max_d2, const kss_robust_params* rp, double* sums,
+                           double* info) {
+    KCHK(robust_check(c, "robust_sums", rp, P.tnrm));
+    KCHK(sums_check(c, "robust_sums", P, idx, sums, info && (rp->metric != KSS_METRIC_PLANE || P.tnrm)));
+    KCHK(pair_enter(c, host, P, &idx));
+    return pair_record_dev(c, P.src, P.tgt, P.tnrm, idx, P.ns, P.nt, max_d2, robust_mode_of(rp), nullptr, sums, info);
+}
+int kss_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n, int64_t nt,
+                        double max_d2, const kss_robust_params* rp, double* sums, double info[KSS_ROBUST_NINFO]) {
+    return robust_sums_any(c, false, one_pair(d_src, n, nullptr, d_tgt, nt, d_nrm), d_idx, max_d2, rp, sums, info);
+}
+int kss_robust_sums(kss_ctx* c, const float* src, const float* tgt, const float* nrm, const int32_t* idx, int64_t n, int64_t nt,
+                    double max_d2, const kss_robust_params* rp, double* sums, double info[KSS_ROBUST_NINFO]) {
+    return robust_sums_any(c, true, one_pair(src, n, nullptr, tgt, nt, nrm), idx, max_d2, rp, sums, info);
+}
+
+static int icp_robust_any(kss_ctx* c, const char* who, bool host, PairClouds P, const kss_icp_params* p, const kss_robust_params* rp,
+                          const double* scales, kss_icp_result* res, double* info) {
+    KCHK(robust_check(c, who, rp, P.tnrm, P.npairs, scales));
+    KCHK(pair_check(c, who, P, p, res, "robust ICP"));
+    KCHK(pair_enter(c, host, P));
+    const PairMode mode = robust_mode_of(rp);
+    if (mode.plane) KCHK(pair_normals(c, P, 20, false));
+    return pair_go(c, P, p, mode, res, info, nullptr, rp, scales);
+}
+int kss_icp_robust_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
+                       const kss_icp_params* p, const kss_robust_params* rp, kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
+    return icp_robust_any(c, "icp_robust", false, one_pair(d_src, ns, nullptr, d_tgt, nt, d_nrm), p, rp, nullptr, res, last_info);
+}
 int kss_icp_robust(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm, const kss_icp_params* p,
                    const kss_robust_params* rp, kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(robust_check(c, "icp_robust", rp, nrm));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_robust: the source-row split (allreduce) is not available for robust ICP");
-    KCHK(pair_check(c, "icp_robust", false, src, tgt, ns, nt, nrm, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_robust_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
-                              p, rp, res, last_info);
+    return icp_robust_any(c, "icp_robust", true, one_pair(src, ns, nullptr, tgt, nt, nrm), p, rp, nullptr, res, last_info);
+}
+int kss_icp_robust_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off,
+                             const float* d_nrm, int npairs, const kss_icp_params* p, const kss_robust_params* rp, const double* scales,
+                             kss_icp_result* results, double* info_all) {
+    return icp_robust_any(c, "icp_robust_batch", false, many_pairs(d_src, src_off, nullptr, d_tgt, tgt_off, d_nrm, npairs), p, rp, scales, results,
+                          info_all);
+}
+int kss_icp_robust_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off, const float* nrm,
+                         int npairs, const kss_icp_params* p, const kss_robust_params* rp, const double* scales, kss_icp_result* results,
+                         double* info_all) {
+    return icp_robust_any(c, "icp_robust_batch", true, many_pairs(src, src_off, nullptr, tgt, tgt_off, nrm, npairs), p, rp, scales, results,
+                          info_all);
 }
 
-// ---- generalized ICP ---------------------------------------------------------------
+// ---- generalized ICP -----------------------------------------------------------
 static inline bool gicp_epsilon_ok(double e) { return e > 0.0 && e <= 1.0; }   // (a NaN fails both)
 
 int kss_gicp_default_params(kss_gicp_params* gp) {
@@ -813,93 +944,75 @@ int kss_gicp_metric(const float nq[3], const double m[3], double epsilon, double
     return KSS_OK;
 }
 
-// the checks of gp that kss_gicp_sums and kss_icp_gicp share; need_k: a set of normals is to be computed
-static int gicp_check(kss_ctx* c, const char* who, const kss_gicp_params* gp, bool need_k) {
+// the checks of gp (need_k: a set of normals is to be computed), and of a batch's per-pair epsilons (null: gp->epsilon everywhere)
+static int gicp_check(kss_ctx* c, const char* who, const kss_gicp_params* gp, bool need_k, int npairs = 0, const double* epsilons = nullptr) {
     const std::string w = std::string(who) + ": ";
     auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
     if (!gp) return bad("null argument");
     if (!gicp_epsilon_ok(gp->epsilon)) return bad("epsilon must be in (0, 1]");
     if (need_k && (gp->normals_k < 3 || gp->normals_k > 64)) return bad("normals_k must be in 3..64");
+    for (int i = 0; epsilons && i < npairs; ++i)
+        if (!gicp_epsilon_ok(epsilons[i])) return bad("every epsilon must be in (0, 1]");
     return KSS_OK;
 }
-
-// both clouds' normals where the caller gave none (the target's into p2l_nrm, the source's into gicp_snrm)
-static int gicp_normals_dev(kss_ctx* c, const float* d_src, int64_t ns, const float** d_snrm, const float* d_tgt, int64_t nt,
-                            const float** d_tnrm, int k) {
-    if (!*d_tnrm) KCHK(cloud_normals_dev(c, d_tgt, nt, k, c->p2l_nrm, d_tnrm));
-    if (!*d_snrm) KCHK(cloud_normals_dev(c, d_src, ns, k, c->gicp_snrm, d_snrm));
-    return KSS_OK;
+// d_snrm: the source's normals on the device, given or computed
+static PairMode gicp_mode_of(const kss_gicp_params* gp, const float* d_snrm) {
+    PairMode mode;
+    mode.plane = true;
+    mode.gicp = true;
+    mode.gicp_epsilon = gp->epsilon;
+    mode.d_src_nrm = d_snrm;
+    return mode;
 }
 
+static int gicp_sums_any(kss_ctx* c, bool host, PairClouds P, const int32_t* idx, double max_d2, const float* Rn, const kss_gicp_params* gp,
+                         double* sums) {
+    KCHK(gicp_check(c, "gicp_sums", gp, !P.snrm || !P.tnrm));
+    KCHK(sums_check(c, "gicp_sums", P, idx, sums));
+    KCHK(pair_enter(c, host, P, &idx, "gicp_sums"));
+    KCHK(pair_normals(c, P, gp->normals_k, true));
+    return pair_record_dev(c, P.src, P.tgt, P.tnrm, idx, P.ns, P.nt, max_d2, gicp_mode_of(gp, P.snrm), Rn, sums, nullptr);
+}
 int kss_gicp_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals, const float* d_tgt, const float* d_tgt_normals,
                       const int32_t* d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_gicp_params* gp,
                       double sums[KSS_P2L_NSUMS]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(gicp_check(c, "gicp_sums", gp, !d_src_normals || !d_tgt_normals));
-    if (!d_src || !d_tgt || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "gicp_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "gicp_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "gicp_sums: cloud too large");
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, gp->normals_k));
-    PairMode mode;
-    mode.plane = true;
-    mode.gicp = true;
-    mode.gicp_epsilon = gp->epsilon;
-    mode.d_src_nrm = d_src_normals;
-    return pair_record_dev(c, d_src, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, mode, Rn, sums, nullptr);
+    return gicp_sums_any(c, false, one_pair(d_src, n, d_src_normals, d_tgt, nt, d_tgt_normals), d_idx, max_d2, Rn, gp, sums);
 }
-
 int kss_gicp_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals, const int32_t* idx,
                   int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_gicp_params* gp, double sums[KSS_P2L_NSUMS]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(gicp_check(c, "gicp_sums", gp, !src_normals || !tgt_normals));
-    if (!src || !tgt || !idx || !sums) return set_err(c, KSS_ERR_ARG, "gicp_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "gicp_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "gicp_sums: cloud too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= nt) return set_err(c, KSS_ERR_ARG, "gicp_sums: index out of range");
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)n * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
-    return kss_gicp_sums_dev(c, (const float*)c->stage_src.p, src_normals ? (const float*)c->gicp_snrm.p : nullptr, (const float*)c->stage_tgt.p,
-                             tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, (const int32_t*)c->stage_idx.p, n, nt, max_d2, Rn, gp, sums);
+    return gicp_sums_any(c, true, one_pair(src, n, src_normals, tgt, nt, tgt_normals), idx, max_d2, Rn, gp, sums);
 }
 
+static int icp_gicp_any(kss_ctx* c, const char* who, bool host, PairClouds P, const kss_icp_params* p, const kss_gicp_params* gp,
+                        const double* epsilons, kss_icp_result* res) {
+    KCHK(gicp_check(c, who, gp, !P.snrm || !P.tnrm, P.npairs, epsilons));
+    KCHK(pair_check(c, who, P, p, res, "generalized ICP"));
+    KCHK(pair_enter(c, host, P));
+    KCHK(pair_normals(c, P, gp->normals_k, true));
+    return pair_go(c, P, p, gicp_mode_of(gp, P.snrm), res, nullptr, nullptr, nullptr, nullptr, epsilons);
+}
 int kss_icp_gicp_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const float* d_tgt, int64_t nt,
                      const float* d_tgt_normals, const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* res) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(gicp_check(c, "icp_gicp", gp, !d_src_normals || !d_tgt_normals));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_gicp: the source-row split (allreduce) is not available for generalized ICP");
-    KCHK(pair_check(c, "icp_gicp", false, d_src, d_tgt, ns, nt, d_tgt_normals, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(gicp_normals_dev(c, d_src, ns, &d_src_normals, d_tgt, nt, &d_tgt_normals, gp->normals_k));
-    PairMode mode;
-    mode.plane = true;
-    mode.gicp = true;
-    mode.gicp_epsilon = gp->epsilon;
-    mode.d_src_nrm = d_src_normals;
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_tgt_normals, p, mode, res);
+    return icp_gicp_any(c, "icp_gicp", false, one_pair(d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals), p, gp, nullptr, res);
 }
-
 int kss_icp_gicp(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const float* tgt, int64_t nt, const float* tgt_normals,
                  const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* res) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(gicp_check(c, "icp_gicp", gp, !src_normals || !tgt_normals));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_gicp: the source-row split (allreduce) is not available for generalized ICP");
-    KCHK(pair_check(c, "icp_gicp", false, src, tgt, ns, nt, tgt_normals, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)ns * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_gicp_dev(c, (const float*)c->stage_src.p, ns, src_normals ? (const float*)c->gicp_snrm.p : nullptr,
-                            (const float*)c->stage_tgt.p, nt, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, p, gp, res);
+    return icp_gicp_any(c, "icp_gicp", true, one_pair(src, ns, src_normals, tgt, nt, tgt_normals), p, gp, nullptr, res);
+}
+int kss_icp_gicp_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
+                           const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
+                           const kss_gicp_params* gp, const double* epsilons, kss_icp_result* results) {
+    return icp_gicp_any(c, "icp_gicp_batch", false, many_pairs(d_src, src_off, d_src_normals, d_tgt, tgt_off, d_tgt_normals, npairs), p, gp,
+                        epsilons, results);
+}
+int kss_icp_gicp_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
+                       const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_gicp_params* gp,
+                       const double* epsilons, kss_icp_result* results) {
+    return icp_gicp_any(c, "icp_gicp_batch", true, many_pairs(src, src_off, src_normals, tgt, tgt_off, tgt_normals, npairs), p, gp, epsilons,
+                        results);
 }
 
-// ---- symmetric ICP -----------------------------------------------------------------
+// ---- symmetric ICP and its robust form -----------------------------
 int kss_symm_default_params(kss_symm_params* sp) {
     if (!sp) return KSS_ERR_ARG;
     sp->normals_k = 20;
@@ -916,257 +1029,128 @@ int kss_rigid_from_symm_sums(const double sums[KSS_P2L_NSUMS], float T[16]) {
     return KSS_OK;
 }
 
-// the checks of sp that kss_symm_sums and kss_icp_symm share; need_k: a set of normals is to be computed
-static int symm_check(kss_ctx* c, const char* who, const kss_symm_params* sp, bool need_k) {
+// the checks of sp (need_k: a set of normals is to be computed), and of a batch's per-pair aligns (null: sp->align_normals everywhere)
+static int symm_check(kss_ctx* c, const char* who, const kss_symm_params* sp, bool need_k, int npairs = 0, const int32_t* aligns = nullptr) {
     const std::string w = std::string(who) + ": ";
     auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
     if (!sp) return bad("null argument");
     if (sp->align_normals != 0 && sp->align_normals != 1) return bad("align_normals must be 0 or 1");
     if (need_k && (sp->normals_k < 3 || sp->normals_k > 64)) return bad("normals_k must be in 3..64");
+    for (int i = 0; aligns && i < npairs; ++i)
+        if (aligns[i] != 0 && aligns[i] != 1) return bad("every align must be 0 or 1");
     return KSS_OK;
 }
-
-int kss_symm_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals, const float* d_tgt, const float* d_tgt_normals,
-                      const int32_t* d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp,
-                      double sums[KSS_P2L_NSUMS]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_check(c, "symm_sums", sp, !d_src_normals || !d_tgt_normals));
-    if (!d_src || !d_tgt || !d_idx || !sums) return set_err(c, KSS_ERR_ARG, "symm_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "symm_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_sums: cloud too large");
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
-    PairMode mode;
-    mode.plane = true;
-    mode.symm = true;
-    mode.symm_align = sp->align_normals;
-    mode.d_src_nrm = d_src_normals;
-    return pair_record_dev(c, d_src, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, mode, Rn, sums, nullptr);
-}
-
-int kss_symm_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals, const int32_t* idx,
-                  int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp, double sums[KSS_P2L_NSUMS]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_check(c, "symm_sums", sp, !src_normals || !tgt_normals));
-    if (!src || !tgt || !idx || !sums) return set_err(c, KSS_ERR_ARG, "symm_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "symm_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_sums: cloud too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= nt) return set_err(c, KSS_ERR_ARG, "symm_sums: index out of range");
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)n * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
-    return kss_symm_sums_dev(c, (const float*)c->stage_src.p, src_normals ? (const float*)c->gicp_snrm.p : nullptr, (const float*)c->stage_tgt.p,
-                             tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, (const int32_t*)c->stage_idx.p, n, nt, max_d2, Rn, sp, sums);
-}
-
-int kss_icp_symm_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const float* d_tgt, int64_t nt,
-                     const float* d_tgt_normals, const kss_icp_params* p, const kss_symm_params* sp, kss_icp_result* res) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_check(c, "icp_symm", sp, !d_src_normals || !d_tgt_normals));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm: the source-row split (allreduce) is not available for symmetric ICP");
-    KCHK(pair_check(c, "icp_symm", false, d_src, d_tgt, ns, nt, d_tgt_normals, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(gicp_normals_dev(c, d_src, ns, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
-    PairMode mode;
-    mode.plane = true;
-    mode.symm = true;
-    mode.symm_align = sp->align_normals;
-    mode.d_src_nrm = d_src_normals;
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_tgt_normals, p, mode, res);
-}
-
-int kss_icp_symm(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const float* tgt, int64_t nt, const float* tgt_normals,
-                 const kss_icp_params* p, const kss_symm_params* sp, kss_icp_result* res) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_check(c, "icp_symm", sp, !src_normals || !tgt_normals));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm: the source-row split (allreduce) is not available for symmetric ICP");
-    KCHK(pair_check(c, "icp_symm", false, src, tgt, ns, nt, tgt_normals, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)ns * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_symm_dev(c, (const float*)c->stage_src.p, ns, src_normals ? (const float*)c->gicp_snrm.p : nullptr,
-                            (const float*)c->stage_tgt.p, nt, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, p, sp, res);
-}
-
-// ---- robust symmetric ICP ----------------------------------------------------------
-// symm_check and robust_check composed; the residual is a signed plane distance and the scale rule the plane metric's
-static int symm_robust_check(kss_ctx* c, const char* who, const kss_symm_params* sp, const kss_robust_params* rp, bool need_k) {
-    KCHK(symm_check(c, who, sp, need_k));
-    KCHK(robust_check(c, who, rp, nullptr));
+// symm_check and, rp given, robust_check composed; the residual is a signed plane distance and the scale rule the plane metric's
+static int symm_robust_check(kss_ctx* c, const char* who, const kss_symm_params* sp, const kss_robust_params* rp, bool robust, bool need_k,
+                      int npairs = 0, const int32_t* aligns = nullptr, const double* scales = nullptr) {
+    KCHK(symm_check(c, who, sp, need_k, npairs, aligns));
+    if (!robust) return KSS_OK;
+    KCHK(robust_check(c, who, rp, nullptr, npairs, scales));
     if (rp->metric != KSS_METRIC_PLANE) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": the metric must be KSS_METRIC_PLANE").c_str());
     return KSS_OK;
 }
+// d_snrm: the source's normals on the device, given or computed; robust: the weights of rp on the symmetric record
+static PairMode symm_mode_of(const kss_symm_params* sp, const float* d_snrm, const kss_robust_params* rp, bool robust) {
+    PairMode mode = robust ? robust_mode_of(rp) : PairMode();
+    mode.plane = true;
+    mode.symm = true;
+    mode.symm_align = sp->align_normals;
+    mode.d_src_nrm = d_snrm;
+    return mode;
+}
 
+// kss_symm_sums (robust false: rp and info are not read) and kss_symm_robust_sums
+static int symm_sums_any(kss_ctx* c, const char* who, bool host, PairClouds P, const int32_t* idx, double max_d2, const float* Rn,
+                         const kss_symm_params* sp, const kss_robust_params* rp, bool robust, double* sums, double* info) {
+    KCHK(symm_robust_check(c, who, sp, rp, robust, !P.snrm || !P.tnrm));
+    KCHK(sums_check(c, who, P, idx, sums, info || !robust));
+    KCHK(pair_enter(c, host, P, &idx, who));
+    KCHK(pair_normals(c, P, sp->normals_k, true));
+    return pair_record_dev(c, P.src, P.tgt, P.tnrm, idx, P.ns, P.nt, max_d2, symm_mode_of(sp, P.snrm, rp, robust), Rn, sums, info);
+}
+int kss_symm_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals, const float* d_tgt, const float* d_tgt_normals,
+                      const int32_t* d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp,
+                      double sums[KSS_P2L_NSUMS]) {
+    return symm_sums_any(c, "symm_sums", false, one_pair(d_src, n, d_src_normals, d_tgt, nt, d_tgt_normals), d_idx, max_d2, Rn, sp, nullptr, false,
+                         sums, nullptr);
+}
+int kss_symm_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals, const int32_t* idx,
+                  int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp, double sums[KSS_P2L_NSUMS]) {
+    return symm_sums_any(c, "symm_sums", true, one_pair(src, n, src_normals, tgt, nt, tgt_normals), idx, max_d2, Rn, sp, nullptr, false, sums,
+                         nullptr);
+}
 int kss_symm_robust_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals, const float* d_tgt, const float* d_tgt_normals,
                              const int32_t* d_idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp,
                              const kss_robust_params* rp, double sums[KSS_P2L_NSUMS], double info[KSS_ROBUST_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_robust_check(c, "symm_robust_sums", sp, rp, !d_src_normals || !d_tgt_normals));
-    if (!d_src || !d_tgt || !d_idx || !sums || !info) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: cloud too large");
-    const RobustScale rs = robust_scale_of(rp);
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(gicp_normals_dev(c, d_src, n, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
-    PairMode mode;
-    mode.plane = true;
-    mode.symm = true;
-    mode.symm_align = sp->align_normals;
-    mode.d_src_nrm = d_src_normals;
-    mode.robust = true;
-    mode.rs = rs;
-    return pair_record_dev(c, d_src, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, mode, Rn, sums, info);
+    return symm_sums_any(c, "symm_robust_sums", false, one_pair(d_src, n, d_src_normals, d_tgt, nt, d_tgt_normals), d_idx, max_d2, Rn, sp, rp,
+                         true, sums, info);
 }
-
 int kss_symm_robust_sums(kss_ctx* c, const float* src, const float* src_normals, const float* tgt, const float* tgt_normals,
                          const int32_t* idx, int64_t n, int64_t nt, double max_d2, const float Rn[9], const kss_symm_params* sp,
                          const kss_robust_params* rp, double sums[KSS_P2L_NSUMS], double info[KSS_ROBUST_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_robust_check(c, "symm_robust_sums", sp, rp, !src_normals || !tgt_normals));
-    if (!src || !tgt || !idx || !sums || !info) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: null argument");
-    if (n <= 0 || nt <= 0) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: empty input");
-    if (n > 0x7fff0000ll || nt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: cloud too large");
-    for (int64_t i = 0; i < n; ++i)
-        if (idx[i] < 0 || idx[i] >= nt) return set_err(c, KSS_ERR_ARG, "symm_robust_sums: index out of range");
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)n * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)n * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
-    return kss_symm_robust_sums_dev(c, (const float*)c->stage_src.p, src_normals ? (const float*)c->gicp_snrm.p : nullptr,
-                                    (const float*)c->stage_tgt.p, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr,
-                                    (const int32_t*)c->stage_idx.p, n, nt, max_d2, Rn, sp, rp, sums, info);
+    return symm_sums_any(c, "symm_robust_sums", true, one_pair(src, n, src_normals, tgt, nt, tgt_normals), idx, max_d2, Rn, sp, rp, true, sums,
+                         info);
 }
 
+// kss_icp_symm[_batch] (robust false: rp, scales and info are not read) and kss_icp_symm_robust[_batch]
+static int icp_symm_any(kss_ctx* c, const char* who, bool host, PairClouds P, const kss_icp_params* p, const kss_symm_params* sp,
+                        const int32_t* aligns, const kss_robust_params* rp, bool robust, const double* scales, kss_icp_result* res, double* info) {
+    KCHK(symm_robust_check(c, who, sp, rp, robust, !P.snrm || !P.tnrm, P.npairs, aligns, scales));
+    KCHK(pair_check(c, who, P, p, res, "symmetric ICP"));
+    KCHK(pair_enter(c, host, P));
+    KCHK(pair_normals(c, P, sp->normals_k, true));
+    return pair_go(c, P, p, symm_mode_of(sp, P.snrm, rp, robust), res, info, nullptr, rp, scales, nullptr, aligns);
+}
+int kss_icp_symm_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const float* d_tgt, int64_t nt,
+                     const float* d_tgt_normals, const kss_icp_params* p, const kss_symm_params* sp, kss_icp_result* res) {
+    return icp_symm_any(c, "icp_symm", false, one_pair(d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals), p, sp, nullptr, nullptr, false, nullptr,
+                        res, nullptr);
+}
+int kss_icp_symm(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const float* tgt, int64_t nt, const float* tgt_normals,
+                 const kss_icp_params* p, const kss_symm_params* sp, kss_icp_result* res) {
+    return icp_symm_any(c, "icp_symm", true, one_pair(src, ns, src_normals, tgt, nt, tgt_normals), p, sp, nullptr, nullptr, false, nullptr, res,
+                        nullptr);
+}
+int kss_icp_symm_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
+                           const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
+                           const kss_symm_params* sp, const int32_t* aligns, kss_icp_result* results) {
+    return icp_symm_any(c, "icp_symm_batch", false, many_pairs(d_src, src_off, d_src_normals, d_tgt, tgt_off, d_tgt_normals, npairs), p, sp,
+                        aligns, nullptr, false, nullptr, results, nullptr);
+}
+int kss_icp_symm_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
+                       const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_symm_params* sp,
+                       const int32_t* aligns, kss_icp_result* results) {
+    return icp_symm_any(c, "icp_symm_batch", true, many_pairs(src, src_off, src_normals, tgt, tgt_off, tgt_normals, npairs), p, sp, aligns,
+                        nullptr, false, nullptr, results, nullptr);
+}
 int kss_icp_symm_robust_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const float* d_tgt, int64_t nt,
                             const float* d_tgt_normals, const kss_icp_params* p, const kss_symm_params* sp, const kss_robust_params* rp,
                             kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_robust_check(c, "icp_symm_robust", sp, rp, !d_src_normals || !d_tgt_normals));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm_robust: the source-row split (allreduce) is not available for symmetric ICP");
-    KCHK(pair_check(c, "icp_symm_robust", false, d_src, d_tgt, ns, nt, d_tgt_normals, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(gicp_normals_dev(c, d_src, ns, &d_src_normals, d_tgt, nt, &d_tgt_normals, sp->normals_k));
-    PairMode mode;
-    mode.plane = true;
-    mode.symm = true;
-    mode.symm_align = sp->align_normals;
-    mode.d_src_nrm = d_src_normals;
-    mode.robust = true;
-    mode.rs = robust_scale_of(rp);
-    mode.trace_info = rp->trace_robust;
-    mode.last_info = last_info;
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_tgt_normals, p, mode, res);
+    return icp_symm_any(c, "icp_symm_robust", false, one_pair(d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals), p, sp, nullptr, rp, true,
+                        nullptr, res, last_info);
 }
-
 int kss_icp_symm_robust(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const float* tgt, int64_t nt,
                         const float* tgt_normals, const kss_icp_params* p, const kss_symm_params* sp, const kss_robust_params* rp,
                         kss_icp_result* res, double last_info[KSS_ROBUST_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_robust_check(c, "icp_symm_robust", sp, rp, !src_normals || !tgt_normals));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_symm_robust: the source-row split (allreduce) is not available for symmetric ICP");
-    KCHK(pair_check(c, "icp_symm_robust", false, src, tgt, ns, nt, tgt_normals, p, nullptr, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->gicp_snrm, src_normals, (size_t)ns * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->p2l_nrm, tgt_normals, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_symm_robust_dev(c, (const float*)c->stage_src.p, ns, src_normals ? (const float*)c->gicp_snrm.p : nullptr,
-                                   (const float*)c->stage_tgt.p, nt, tgt_normals ? (const float*)c->p2l_nrm.p : nullptr, p, sp, rp, res,
-                                   last_info);
+    return icp_symm_any(c, "icp_symm_robust", true, one_pair(src, ns, src_normals, tgt, nt, tgt_normals), p, sp, nullptr, rp, true, nullptr, res,
+                        last_info);
+}
+int kss_icp_symm_robust_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
+                                  const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
+                                  const kss_symm_params* sp, const int32_t* aligns, const kss_robust_params* rp, const double* scales,
+                                  kss_icp_result* results, double* info_all) {
+    return icp_symm_any(c, "icp_symm_robust_batch", false, many_pairs(d_src, src_off, d_src_normals, d_tgt, tgt_off, d_tgt_normals, npairs), p,
+                        sp, aligns, rp, true, scales, results, info_all);
+}
+int kss_icp_symm_robust_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
+                              const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_symm_params* sp,
+                              const int32_t* aligns, const kss_robust_params* rp, const double* scales, kss_icp_result* results,
+                              double* info_all) {
+    return icp_symm_any(c, "icp_symm_robust_batch", true, many_pairs(src, src_off, src_normals, tgt, tgt_off, tgt_normals, npairs), p, sp,
+                        aligns, rp, true, scales, results, info_all);
 }
 
-// ---- the same for many pairs per call ------------------------------------------------
-// Every cloud's normals where the caller gave none: cloud_normals_dev at k, cloud after cloud (off: npairs + 1 offsets in points
-// from 0), into the packed buffer `out` laid out like the clouds (setup cost of the call, not optimised: a k-NN and a normals
-// launch per cloud).  The targets' go to pb_nrm at k = 20 (the plane metric) or normals_k (generalized, symmetric), the sources' to pb_snrm.
-static int batch_normals_dev(kss_ctx* c, const float* d_pts, const int64_t* off, int npairs, int k, DevBuf& out, const float** d_nrm) {
-    KCHK(ensure(c, out, (size_t)off[npairs] * 3 * sizeof(float)));
-    for (int i = 0; i < npairs; ++i) {
-        const int64_t n = off[i + 1] - off[i];
-        const float* one = nullptr;
-        KCHK(cloud_normals_dev(c, d_pts + 3 * off[i], n, k, c->p2l_nrm, &one));
-        HIPCHK(c, hipMemcpyAsync((float*)out.p + 3 * off[i], one, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    }
-    *d_nrm = (const float*)out.p;
-    return KSS_OK;
-}
-
-// what the four ICP entry points below share.  The offsets are rebased to the first pair, so that every buffer of the call is
-// indexed from 0.  tp: null for kss_icp_p2l_batch.
-static int pairs_batch_dev(kss_ctx* c, const char* who, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off,
-                           const float* d_nrm, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
-                           kss_icp_result* results, double* info_all, bool unique = false) {
-    if (!c) return KSS_ERR_ARG;
-    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": bad batch").c_str());
-    KCHK(pair_check(c, who, tp != nullptr, d_src, d_tgt, 0, 0, d_nrm, p, tp, results, src_off, tgt_off, npairs, overlaps));
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
-    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
-    if (d_nrm) d_nrm += 3 * tgt_off[0];
-    PairMode mode;
-    mode.plane = !tp || tp->metric == KSS_METRIC_PLANE;
-    mode.trimmed = tp != nullptr;
-    mode.unique = unique;   // (kss_icp_o2o_batch: tp built from its kss_o2o_params)
-    mode.trace_info = tp ? tp->trace_trim : nullptr;
-    std::vector<double> ov;
-    if (tp) ov.assign((size_t)npairs, tp->overlap);
-    if (tp && overlaps) ov.assign(overlaps, overlaps + npairs);
-    if (mode.plane && !d_nrm) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, 20, c->pb_nrm, &d_nrm));
-    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_nrm, npairs, p, mode, tp ? ov.data() : nullptr, results, info_all);
-}
-
-// host clouds: the batch's slices of the packed arrays are staged, then the device form runs
-static int pairs_batch_host(kss_ctx* c, const char* who, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off,
-                            const float* nrm, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
-                            kss_icp_result* results, double* info_all, bool unique = false) {
-    if (!c) return KSS_ERR_ARG;
-    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": bad batch").c_str());
-    KCHK(pair_check(c, who, tp != nullptr, src, tgt, 0, 0, nrm, p, tp, results, src_off, tgt_off, npairs, overlaps));
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
-    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    if (nrm) KCHK(upload(c, c->pb_nrm, nrm + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
-    return pairs_batch_dev(c, who, (const float*)c->stage_src.p, so.data(), (const float*)c->stage_tgt.p, to.data(),
-                           nrm ? (const float*)c->pb_nrm.p : nullptr, npairs, p, tp, overlaps, results, info_all, unique);
-}
-
-int kss_icp_p2l_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
-                          const float* d_nrm_all, int npairs, const kss_icp_params* p, kss_icp_result* results) {
-    return pairs_batch_dev(c, "icp_p2l_batch", d_src_all, src_off, d_tgt_all, tgt_off, d_nrm_all, npairs, p, nullptr, nullptr, results, nullptr);
-}
-
-int kss_icp_p2l_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
-                      const float* nrm_all, int npairs, const kss_icp_params* p, kss_icp_result* results) {
-    return pairs_batch_host(c, "icp_p2l_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, nullptr, nullptr, results, nullptr);
-}
-
-int kss_icp_trimmed_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
-                              const float* d_nrm_all, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
-                              kss_icp_result* results, double* info_all) {
-    if (c && !tp) return set_err(c, KSS_ERR_ARG, "icp_trimmed_batch: null argument");
-    return pairs_batch_dev(c, "icp_trimmed_batch", d_src_all, src_off, d_tgt_all, tgt_off, d_nrm_all, npairs, p, tp, overlaps, results, info_all);
-}
-
-int kss_icp_trimmed_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
-                          const float* nrm_all, int npairs, const kss_icp_params* p, const kss_trim_params* tp, const double* overlaps,
-                          kss_icp_result* results, double* info_all) {
-    if (c && !tp) return set_err(c, KSS_ERR_ARG, "icp_trimmed_batch: null argument");
-    return pairs_batch_host(c, "icp_trimmed_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, tp, overlaps, results, info_all);
-}
-
-// ---- one-to-one ICP: kss_icp_trimmed's checks, staging and loop with PairMode::unique ----
+// ---- one-to-one ICP: the trimmed families' path with PairMode::unique ----------------
 int kss_o2o_default_params(kss_o2o_params* op) {
     if (!op) return KSS_ERR_ARG;
     op->overlap = 1.0;
@@ -1175,56 +1159,36 @@ int kss_o2o_default_params(kss_o2o_params* op) {
     return KSS_OK;
 }
 
-static inline kss_trim_params o2o_trim_params(const kss_o2o_params* op) { return kss_trim_params{op->overlap, op->metric, op->trace_o2o}; }
+static PairMode o2o_mode_of(const kss_o2o_params* op) {
+    PairMode mode = trimmed_mode(op->overlap, op->metric, op->trace_o2o);
+    mode.unique = true;
+    return mode;
+}
 
 int kss_icp_o2o_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                     const kss_icp_params* p, const kss_o2o_params* op, kss_icp_result* res, double last_info[KSS_O2O_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    if (!op) return set_err(c, KSS_ERR_ARG, "icp_o2o: null argument");
-    const kss_trim_params tp = o2o_trim_params(op);
-    KCHK(pair_check(c, "icp_o2o", true, d_src, d_tgt, ns, nt, d_nrm, p, &tp, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    PairMode mode;
-    mode.plane = tp.metric == KSS_METRIC_PLANE;
-    mode.trimmed = true;
-    mode.unique = true;
-    mode.overlap = tp.overlap;
-    mode.trace_info = tp.trace_trim;
-    mode.last_info = last_info;
-    if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
+    KCHK(params_check(c, "icp_o2o", op));
+    return icp_trimmed_any(c, "icp_o2o", false, one_pair(d_src, ns, nullptr, d_tgt, nt, d_nrm), p, o2o_mode_of(op), op->metric, nullptr, res,
+                           last_info);
 }
-
 int kss_icp_o2o(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
                 const kss_icp_params* p, const kss_o2o_params* op, kss_icp_result* res, double last_info[KSS_O2O_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    if (!op) return set_err(c, KSS_ERR_ARG, "icp_o2o: null argument");
-    const kss_trim_params tp = o2o_trim_params(op);
-    KCHK(pair_check(c, "icp_o2o", true, src, tgt, ns, nt, nrm, p, &tp, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_o2o_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
-                           p, op, res, last_info);
+    KCHK(params_check(c, "icp_o2o", op));
+    return icp_trimmed_any(c, "icp_o2o", true, one_pair(src, ns, nullptr, tgt, nt, nrm), p, o2o_mode_of(op), op->metric, nullptr, res, last_info);
 }
-
 int kss_icp_o2o_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
                           const float* d_nrm_all, int npairs, const kss_icp_params* p, const kss_o2o_params* op, const double* overlaps,
                           kss_icp_result* results, double* info_all) {
-    if (!c) return KSS_ERR_ARG;
-    if (!op) return set_err(c, KSS_ERR_ARG, "icp_o2o_batch: null argument");
-    const kss_trim_params tp = o2o_trim_params(op);
-    return pairs_batch_dev(c, "icp_o2o_batch", d_src_all, src_off, d_tgt_all, tgt_off, d_nrm_all, npairs, p, &tp, overlaps, results, info_all, true);
+    KCHK(params_check(c, "icp_o2o_batch", op));
+    return icp_trimmed_any(c, "icp_o2o_batch", false, many_pairs(d_src_all, src_off, nullptr, d_tgt_all, tgt_off, d_nrm_all, npairs), p,
+                           o2o_mode_of(op), op->metric, overlaps, results, info_all);
 }
-
 int kss_icp_o2o_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
                       const float* nrm_all, int npairs, const kss_icp_params* p, const kss_o2o_params* op, const double* overlaps,
                       kss_icp_result* results, double* info_all) {
-    if (!c) return KSS_ERR_ARG;
-    if (!op) return set_err(c, KSS_ERR_ARG, "icp_o2o_batch: null argument");
-    const kss_trim_params tp = o2o_trim_params(op);
-    return pairs_batch_host(c, "icp_o2o_batch", src_all, src_off, tgt_all, tgt_off, nrm_all, npairs, p, &tp, overlaps, results, info_all, true);
+    KCHK(params_check(c, "icp_o2o_batch", op));
+    return icp_trimmed_any(c, "icp_o2o_batch", true, many_pairs(src_all, src_off, nullptr, tgt_all, tgt_off, nrm_all, npairs), p, o2o_mode_of(op),
+                           op->metric, overlaps, results, info_all);
 }
 
 // the filter alone: the arguments of the four entry points
@@ -1277,7 +1241,7 @@ int kss_o2o_filter(kss_ctx* c, const int32_t* idx, const float* d2, int64_t n, i
     return kss_o2o_filter_batch(c, idx, d2, off, &nt, 1, max_d2, idx_out, d2_out, info);
 }
 
-// ---- reciprocal ICP: kss_icp_trimmed's checks, staging and loop with PairMode::mutual ----
+// ---- reciprocal ICP: the trimmed families' path with PairMode::mutual, one pair only --
 int kss_recip_default_params(kss_recip_params* rp) {
     if (!rp) return KSS_ERR_ARG;
     rp->overlap = 1.0;
@@ -1286,38 +1250,23 @@ int kss_recip_default_params(kss_recip_params* rp) {
     return KSS_OK;
 }
 
-static inline kss_trim_params recip_trim_params(const kss_recip_params* rp) { return kss_trim_params{rp->overlap, rp->metric, rp->trace_recip}; }
+static PairMode recip_mode_of(const kss_recip_params* rp) {
+    PairMode mode = trimmed_mode(rp->overlap, rp->metric, rp->trace_recip);
+    mode.mutual = true;
+    return mode;
+}
 
 int kss_icp_recip_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
                       const kss_icp_params* p, const kss_recip_params* rp, kss_icp_result* res, double last_info[KSS_RECIP_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    if (!rp) return set_err(c, KSS_ERR_ARG, "icp_recip: null argument");
-    const kss_trim_params tp = recip_trim_params(rp);
-    KCHK(pair_check(c, "icp_recip", true, d_src, d_tgt, ns, nt, d_nrm, p, &tp, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    PairMode mode;
-    mode.plane = tp.metric == KSS_METRIC_PLANE;
-    mode.trimmed = true;
-    mode.mutual = true;
-    mode.overlap = tp.overlap;
-    mode.trace_info = tp.trace_trim;
-    mode.last_info = last_info;
-    if (mode.plane && !d_nrm) KCHK(target_normals_dev(c, d_tgt, nt, &d_nrm));
-    return pair_run_dev(c, d_src, ns, d_tgt, nt, d_nrm, p, mode, res);
+    KCHK(params_check(c, "icp_recip", rp));
+    return icp_trimmed_any(c, "icp_recip", false, one_pair(d_src, ns, nullptr, d_tgt, nt, d_nrm), p, recip_mode_of(rp), rp->metric, nullptr, res,
+                           last_info);
 }
-
 int kss_icp_recip(kss_ctx* c, const float* src, int64_t ns, const float* tgt, int64_t nt, const float* nrm,
                   const kss_icp_params* p, const kss_recip_params* rp, kss_icp_result* res, double last_info[KSS_RECIP_NINFO]) {
-    if (!c) return KSS_ERR_ARG;
-    if (!rp) return set_err(c, KSS_ERR_ARG, "icp_recip: null argument");
-    const kss_trim_params tp = recip_trim_params(rp);
-    KCHK(pair_check(c, "icp_recip", true, src, tgt, ns, nt, nrm, p, &tp, res));
-    HIPCHK(c, hipSetDevice(c->device));
-    KCHK(upload(c, c->stage_src, src, (size_t)ns * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt, (size_t)nt * 3 * sizeof(float)));
-    if (nrm) KCHK(upload(c, c->p2l_nrm, nrm, (size_t)nt * 3 * sizeof(float)));
-    return kss_icp_recip_dev(c, (const float*)c->stage_src.p, ns, (const float*)c->stage_tgt.p, nt, nrm ? (const float*)c->p2l_nrm.p : nullptr,
-                             p, rp, res, last_info);
+    KCHK(params_check(c, "icp_recip", rp));
+    return icp_trimmed_any(c, "icp_recip", true, one_pair(src, ns, nullptr, tgt, nt, nrm), p, recip_mode_of(rp), rp->metric, nullptr, res,
+                           last_info);
 }
 
 // the filter alone: the arguments of both entry points
@@ -1351,273 +1300,6 @@ int kss_recip_filter(kss_ctx* c, const float* src, int64_t n, const float* tgt, 
     if (d2_out) HIPCHK(c, hipMemcpyAsync(d2_out, c->stage_d2.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KSS_OK;
-}
-
-// ---- similarity ICP for many pairs per call ------------------------------------------
-int kss_icp_sim_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off, int npairs,
-                          const kss_icp_params* p, const kss_sim_params* sp, const double* overlaps, kss_icp_result* results, double* info_all) {
-    if (!c) return KSS_ERR_ARG;
-    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_sim_batch: bad batch");
-    kss_trim_params tp;
-    KCHK(sim_check(c, "icp_sim_batch", sp, &tp));
-    KCHK(pair_check(c, "icp_sim_batch", true, d_src, d_tgt, 0, 0, nullptr, p, &tp, results, src_off, tgt_off, npairs, overlaps));
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
-    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
-    std::vector<double> ov((size_t)npairs, sp->overlap);
-    if (overlaps) ov.assign(overlaps, overlaps + npairs);
-    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), nullptr, npairs, p, sim_mode_of(sp), ov.data(), results, info_all);
-}
-
-int kss_icp_sim_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off, int npairs,
-                      const kss_icp_params* p, const kss_sim_params* sp, const double* overlaps, kss_icp_result* results, double* info_all) {
-    if (!c) return KSS_ERR_ARG;
-    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_sim_batch: bad batch");
-    kss_trim_params tp;
-    KCHK(sim_check(c, "icp_sim_batch", sp, &tp));
-    KCHK(pair_check(c, "icp_sim_batch", true, src, tgt, 0, 0, nullptr, p, &tp, results, src_off, tgt_off, npairs, overlaps));
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
-    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
-    return kss_icp_sim_batch_dev(c, (const float*)c->stage_src.p, so.data(), (const float*)c->stage_tgt.p, to.data(), npairs, p, sp, overlaps,
-                                 results, info_all);
-}
-
-// ---- robust ICP for many pairs per call ----------------------------------------------
-// the per-pair scales of a checked rp (null: rp->scale everywhere); kss_icp_symm_robust_batch shares it
-static int robust_scales_check(kss_ctx* c, const char* who, const kss_robust_params* rp, int npairs, const double* scales) {
-    if (!scales) return KSS_OK;
-    const std::string w = std::string(who) + ": ";
-    const bool tune_ok = rp->tune > 0.0 && std::isfinite(rp->tune);
-    for (int i = 0; i < npairs; ++i) {
-        if (!(scales[i] >= 0.0) || !std::isfinite(scales[i])) return set_err(c, KSS_ERR_ARG, (w + "a scale must be finite and >= 0").c_str());
-        if (scales[i] == 0.0 && !tune_ok) return set_err(c, KSS_ERR_ARG, (w + "tune must be finite and > 0").c_str());
-    }
-    return KSS_OK;
-}
-
-// what the two entry points share beyond pair_check: rp, allreduce and the per-pair scales (null: rp->scale everywhere)
-static int robust_batch_check(kss_ctx* c, const kss_robust_params* rp, const float* nrm, const kss_icp_params* p, const int64_t* src_off,
-                              const int64_t* tgt_off, int npairs, const double* scales) {
-    KCHK(robust_check(c, "icp_robust_batch", rp, nrm));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: the source-row split (allreduce) is not available for robust ICP");
-    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_robust_batch: bad batch");
-    return robust_scales_check(c, "icp_robust_batch", rp, npairs, scales);
-}
-
-int kss_icp_robust_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_tgt, const int64_t* tgt_off,
-                             const float* d_nrm, int npairs, const kss_icp_params* p, const kss_robust_params* rp, const double* scales,
-                             kss_icp_result* results, double* info_all) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(robust_batch_check(c, rp, d_nrm, p, src_off, tgt_off, npairs, scales));
-    KCHK(pair_check(c, "icp_robust_batch", false, d_src, d_tgt, 0, 0, d_nrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr));
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);   // rebased to the first pair, as in pairs_batch_dev
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
-    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
-    if (d_nrm) d_nrm += 3 * tgt_off[0];
-    PairMode mode;
-    mode.plane = rp->metric == KSS_METRIC_PLANE;
-    mode.robust = true;
-    mode.rs = robust_scale_of(rp);
-    mode.trace_info = rp->trace_robust;
-    std::vector<RobustScale> rs((size_t)npairs);
-    for (int i = 0; i < npairs; ++i) rs[i] = robust_scale_of(rp, scales ? scales[i] : rp->scale);
-    if (mode.plane && !d_nrm) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, 20, c->pb_nrm, &d_nrm));
-    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_nrm, npairs, p, mode, nullptr, results, info_all, rs.data());
-}
-
-int kss_icp_robust_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* tgt, const int64_t* tgt_off, const float* nrm,
-                         int npairs, const kss_icp_params* p, const kss_robust_params* rp, const double* scales, kss_icp_result* results,
-                         double* info_all) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(robust_batch_check(c, rp, nrm, p, src_off, tgt_off, npairs, scales));
-    KCHK(pair_check(c, "icp_robust_batch", false, src, tgt, 0, 0, nrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr));
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
-    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    if (nrm) KCHK(upload(c, c->pb_nrm, nrm + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
-    return kss_icp_robust_batch_dev(c, (const float*)c->stage_src.p, so.data(), (const float*)c->stage_tgt.p, to.data(),
-                                    nrm ? (const float*)c->pb_nrm.p : nullptr, npairs, p, rp, scales, results, info_all);
-}
-
-// ---- generalized ICP for many pairs per call -----------------------------------------
-// what the two entry points share: gp, allreduce, the per-pair epsilons (null: gp->epsilon everywhere) and pair_check
-static int gicp_batch_check(kss_ctx* c, const void* src, const float* snrm, const void* tgt, const float* tnrm, const int64_t* src_off,
-                            const int64_t* tgt_off, int npairs, const kss_icp_params* p, const kss_gicp_params* gp, const double* epsilons,
-                            const kss_icp_result* results) {
-    KCHK(gicp_check(c, "icp_gicp_batch", gp, !snrm || !tnrm));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, "icp_gicp_batch: the source-row split (allreduce) is not available for generalized ICP");
-    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, "icp_gicp_batch: bad batch");
-    if (epsilons)
-        for (int i = 0; i < npairs; ++i)
-            if (!gicp_epsilon_ok(epsilons[i])) return set_err(c, KSS_ERR_ARG, "icp_gicp_batch: every epsilon must be in (0, 1]");
-    return pair_check(c, "icp_gicp_batch", false, src, tgt, 0, 0, tnrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr);
-}
-
-int kss_icp_gicp_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
-                           const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
-                           const kss_gicp_params* gp, const double* epsilons, kss_icp_result* results) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(gicp_batch_check(c, d_src, d_src_normals, d_tgt, d_tgt_normals, src_off, tgt_off, npairs, p, gp, epsilons, results));
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);   // rebased to the first pair, as in pairs_batch_dev
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
-    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
-    if (d_src_normals) d_src_normals += 3 * src_off[0];
-    if (d_tgt_normals) d_tgt_normals += 3 * tgt_off[0];
-    // each cloud's normals where the caller gave none, as kss_icp_gicp computes them: from the cloud as passed in, at normals_k
-    if (!d_tgt_normals) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, gp->normals_k, c->pb_nrm, &d_tgt_normals));
-    if (!d_src_normals) KCHK(batch_normals_dev(c, d_src, so.data(), npairs, gp->normals_k, c->pb_snrm, &d_src_normals));
-    PairMode mode;
-    mode.plane = true;
-    mode.gicp = true;
-    mode.d_src_nrm = d_src_normals;
-    std::vector<double> eps((size_t)npairs, gp->epsilon);
-    if (epsilons) eps.assign(epsilons, epsilons + npairs);
-    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_tgt_normals, npairs, p, mode, nullptr, results, nullptr, nullptr, eps.data());
-}
-
-int kss_icp_gicp_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
-                       const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_gicp_params* gp,
-                       const double* epsilons, kss_icp_result* results) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(gicp_batch_check(c, src, src_normals, tgt, tgt_normals, src_off, tgt_off, npairs, p, gp, epsilons, results));
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
-    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->pb_snrm, src_normals + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->pb_nrm, tgt_normals + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
-    return kss_icp_gicp_batch_dev(c, (const float*)c->stage_src.p, so.data(), src_normals ? (const float*)c->pb_snrm.p : nullptr,
-                                  (const float*)c->stage_tgt.p, to.data(), tgt_normals ? (const float*)c->pb_nrm.p : nullptr, npairs, p, gp,
-                                  epsilons, results);
-}
-
-// ---- symmetric ICP for many pairs per call -------------------------------------------
-// what the two entry points share: sp, allreduce, the per-pair aligns (null: sp->align_normals everywhere) and pair_check
-static int symm_batch_check(kss_ctx* c, const void* src, const float* snrm, const void* tgt, const float* tnrm, const int64_t* src_off,
-                            const int64_t* tgt_off, int npairs, const kss_icp_params* p, const kss_symm_params* sp, const int32_t* aligns,
-                            const kss_icp_result* results, const char* who = "icp_symm_batch") {
-    const std::string w = std::string(who) + ": ";
-    KCHK(symm_check(c, who, sp, !snrm || !tnrm));
-    if (p && p->allreduce) return set_err(c, KSS_ERR_ARG, (w + "the source-row split (allreduce) is not available for symmetric ICP").c_str());
-    if (!src_off || !tgt_off || npairs <= 0) return set_err(c, KSS_ERR_ARG, (w + "bad batch").c_str());
-    if (aligns)
-        for (int i = 0; i < npairs; ++i)
-            if (aligns[i] != 0 && aligns[i] != 1) return set_err(c, KSS_ERR_ARG, (w + "every align must be 0 or 1").c_str());
-    return pair_check(c, who, false, src, tgt, 0, 0, tnrm, p, nullptr, results, src_off, tgt_off, npairs, nullptr);
-}
-
-int kss_icp_symm_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
-                           const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
-                           const kss_symm_params* sp, const int32_t* aligns, kss_icp_result* results) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_batch_check(c, d_src, d_src_normals, d_tgt, d_tgt_normals, src_off, tgt_off, npairs, p, sp, aligns, results));
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);   // rebased to the first pair, as in kss_icp_gicp_batch_dev
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
-    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
-    if (d_src_normals) d_src_normals += 3 * src_off[0];
-    if (d_tgt_normals) d_tgt_normals += 3 * tgt_off[0];
-    // each cloud's normals where the caller gave none, as kss_icp_symm computes them: from the cloud as passed in, at normals_k
-    if (!d_tgt_normals) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, sp->normals_k, c->pb_nrm, &d_tgt_normals));
-    if (!d_src_normals) KCHK(batch_normals_dev(c, d_src, so.data(), npairs, sp->normals_k, c->pb_snrm, &d_src_normals));
-    PairMode mode;
-    mode.plane = true;
-    mode.symm = true;
-    mode.d_src_nrm = d_src_normals;
-    std::vector<int32_t> al((size_t)npairs, sp->align_normals);
-    if (aligns) al.assign(aligns, aligns + npairs);
-    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_tgt_normals, npairs, p, mode, nullptr, results, nullptr, nullptr, nullptr,
-                         al.data());
-}
-
-int kss_icp_symm_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
-                       const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_symm_params* sp,
-                       const int32_t* aligns, kss_icp_result* results) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_batch_check(c, src, src_normals, tgt, tgt_normals, src_off, tgt_off, npairs, p, sp, aligns, results));
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
-    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->pb_snrm, src_normals + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->pb_nrm, tgt_normals + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
-    return kss_icp_symm_batch_dev(c, (const float*)c->stage_src.p, so.data(), src_normals ? (const float*)c->pb_snrm.p : nullptr,
-                                  (const float*)c->stage_tgt.p, to.data(), tgt_normals ? (const float*)c->pb_nrm.p : nullptr, npairs, p, sp,
-                                  aligns, results);
-}
-
-// ---- robust symmetric ICP for many pairs per call ------------------------------------
-// symm_batch_check with the checks of rp (the plane metric, as for the single pair) and of the per-pair scales
-static int symm_robust_batch_check(kss_ctx* c, const void* src, const float* snrm, const void* tgt, const float* tnrm, const int64_t* src_off,
-                                   const int64_t* tgt_off, int npairs, const kss_icp_params* p, const kss_symm_params* sp,
-                                   const int32_t* aligns, const kss_robust_params* rp, const double* scales, const kss_icp_result* results) {
-    const char* who = "icp_symm_robust_batch";
-    KCHK(symm_robust_check(c, who, sp, rp, !snrm || !tnrm));
-    KCHK(symm_batch_check(c, src, snrm, tgt, tnrm, src_off, tgt_off, npairs, p, sp, aligns, results, who));
-    return robust_scales_check(c, who, rp, npairs, scales);
-}
-
-int kss_icp_symm_robust_batch_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_src_normals, const float* d_tgt,
-                                  const int64_t* tgt_off, const float* d_tgt_normals, int npairs, const kss_icp_params* p,
-                                  const kss_symm_params* sp, const int32_t* aligns, const kss_robust_params* rp, const double* scales,
-                                  kss_icp_result* results, double* info_all) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_robust_batch_check(c, d_src, d_src_normals, d_tgt, d_tgt_normals, src_off, tgt_off, npairs, p, sp, aligns, rp, scales, results));
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);   // rebased to the first pair, as in kss_icp_symm_batch_dev
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - src_off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
-    d_src += 3 * src_off[0]; d_tgt += 3 * tgt_off[0];
-    if (d_src_normals) d_src_normals += 3 * src_off[0];
-    if (d_tgt_normals) d_tgt_normals += 3 * tgt_off[0];
-    // each cloud's normals where the caller gave none, as kss_icp_symm_robust computes them: from the cloud as passed in, at normals_k
-    if (!d_tgt_normals) KCHK(batch_normals_dev(c, d_tgt, to.data(), npairs, sp->normals_k, c->pb_nrm, &d_tgt_normals));
-    if (!d_src_normals) KCHK(batch_normals_dev(c, d_src, so.data(), npairs, sp->normals_k, c->pb_snrm, &d_src_normals));
-    PairMode mode;
-    mode.plane = true;
-    mode.symm = true;
-    mode.d_src_nrm = d_src_normals;
-    mode.robust = true;
-    mode.rs = robust_scale_of(rp);
-    mode.trace_info = rp->trace_robust;
-    std::vector<int32_t> al((size_t)npairs, sp->align_normals);
-    if (aligns) al.assign(aligns, aligns + npairs);
-    std::vector<RobustScale> rs((size_t)npairs);
-    for (int i = 0; i < npairs; ++i) rs[i] = robust_scale_of(rp, scales ? scales[i] : rp->scale);
-    return pairs_run_dev(c, d_src, so.data(), d_tgt, to.data(), d_tgt_normals, npairs, p, mode, nullptr, results, info_all, rs.data(), nullptr,
-                         al.data());
-}
-
-int kss_icp_symm_robust_batch(kss_ctx* c, const float* src, const int64_t* src_off, const float* src_normals, const float* tgt,
-                              const int64_t* tgt_off, const float* tgt_normals, int npairs, const kss_icp_params* p, const kss_symm_params* sp,
-                              const int32_t* aligns, const kss_robust_params* rp, const double* scales, kss_icp_result* results,
-                              double* info_all) {
-    if (!c) return KSS_ERR_ARG;
-    KCHK(symm_robust_batch_check(c, src, src_normals, tgt, tgt_normals, src_off, tgt_off, npairs, p, sp, aligns, rp, scales, results));
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t s0 = src_off[0], s1 = src_off[npairs], t0 = tgt_off[0], t1 = tgt_off[npairs];
-    KCHK(upload(c, c->stage_src, src + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    KCHK(upload(c, c->stage_tgt, tgt + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    if (src_normals) KCHK(upload(c, c->pb_snrm, src_normals + 3 * s0, (size_t)(s1 - s0) * 3 * sizeof(float)));
-    if (tgt_normals) KCHK(upload(c, c->pb_nrm, tgt_normals + 3 * t0, (size_t)(t1 - t0) * 3 * sizeof(float)));
-    std::vector<int64_t> so(npairs + 1), to(npairs + 1);
-    for (int i = 0; i <= npairs; ++i) { so[i] = src_off[i] - s0; to[i] = tgt_off[i] - t0; }
-    return kss_icp_symm_robust_batch_dev(c, (const float*)c->stage_src.p, so.data(), src_normals ? (const float*)c->pb_snrm.p : nullptr,
-                                         (const float*)c->stage_tgt.p, to.data(), tgt_normals ? (const float*)c->pb_nrm.p : nullptr, npairs, p,
-                                         sp, aligns, rp, scales, results, info_all);
 }
 
 static int trim_batch_check(kss_ctx* c, const float* d2, const int64_t* off, int nseg, const double* overlaps, const double* info_all) {
