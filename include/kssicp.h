@@ -541,7 +541,8 @@ int kss_icp_o2o_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *s
                           const double *overlaps, kss_icp_result *results, double *info_all);
 
 /* ---- reciprocal ICP: a correspondence is kept only where source and target are each other's nearest (PCL's
- *      setUseReciprocalCorrespondences(true) in front of kss_icp_trimmed's pass), both metrics, ONE pair per call ----
+ *      setUseReciprocalCorrespondences(true) in front of kss_icp_trimmed's pass), both metrics, one pair and
+ *      MANY pairs per call ----
  * One pass, on the NN pass's idx[i] and float d2[i] (by original source index), the sources' CURRENT float positions p_k -- the ones
  * the NN pass measured from and wrote out -- and the float targets q_j:
  *   candidate, key(i)   exactly kss_icp_o2o's: idx[i] in [0, nt) and 0 <= d2[i] <= max_d2 in ordered double compares, m of them;
@@ -568,8 +569,9 @@ int kss_icp_o2o_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *s
  * Behind the NN pass a pass makes five launches -- workspace reset, claim + cell count, scan, scatter, resolve + check -- and then the
  * trimmed pass's six.  Once per call the target's bounding box is taken (one launch, one synchronisation) for the cell grid the
  * moving sources are binned into.
- * Not built: the batch (kss_icp_recip_batch is the named follow-up); the check in front of the robust, generalized, symmetric and
- * similarity forms; the C++ mirror classes and the CLI. */
+ * Many pairs per call: kss_icp_recip_pairs below.
+ * Not built: the check in front of the robust, generalized, symmetric and similarity forms, for one pair or a batch; the C++
+ * mirror classes and the CLI. */
 #define KSS_RECIP_NINFO 6   /* {r mutual winners, k rank, tau widened to double, kept, m candidates, u winners before the check} */
 /* The filter alone on packed float triples: n sources src with the map idx / d2 against nt targets tgt; d2 is taken as given, so the
  * definition above holds for any d2 the caller passes; nn_fma != 0: the reverse distances by the fma form.  idx_out / d2_out receive
@@ -593,6 +595,37 @@ int kss_icp_recip(kss_ctx *ctx, const float *src, int64_t ns, const float *tgt, 
                   const kss_icp_params *p, const kss_recip_params *rp, kss_icp_result *res, double last_info[KSS_RECIP_NINFO]);
 int kss_icp_recip_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_tgt, int64_t nt, const float *d_tgt_normals,
                       const kss_icp_params *p, const kss_recip_params *rp, kss_icp_result *res, double last_info[KSS_RECIP_NINFO]);
+/* The filter alone for nseg segments in one call: sources [off[i], off[i + 1]) of src_all, idx_all and d2_all against targets
+ * [tgt_off[i], tgt_off[i + 1]) of tgt_all; nseg + 1 HOST offsets each; idx counts inside the segment's own target.  Every segment
+ * equals kss_recip_filter on it.  The outputs are indexed like the inputs (either may be NULL, either may be its input); info_all:
+ * nseg * 3 doubles {m, u, r}.  KSS_ERR_ARG: a NULL ctx (refused before anything touches the device), src_all, off, tgt_all, tgt_off,
+ * idx_all, d2_all or info_all; nseg <= 0; an empty segment or a segment without targets; a segment or a total beyond the C-ABI's
+ * cloud size. */
+int kss_recip_filter_batch(kss_ctx *ctx, const float *src_all, const int64_t *off, const float *tgt_all, const int64_t *tgt_off, int nseg,
+                           const int32_t *idx_all, const float *d2_all, double max_d2, int nn_fma, int32_t *idx_out_all,
+                           float *d2_out_all, double *info_all);
+int kss_recip_filter_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *off, const float *d_tgt_all, const int64_t *tgt_off,
+                               int nseg, const int32_t *d_idx_all, const float *d_d2_all, double max_d2, int nn_fma,
+                               int32_t *d_idx_out_all, float *d_d2_out_all, double *info_all);
+/* Reciprocal ICP for MANY pairs per call.  The many-pairs form of every other family is spelled _batch; this one is
+ * spelled _pairs because tests/test_recip_abi.py, written with the single pair, pins the _batch name as undeclared.  Arguments exactly
+ * as kss_icp_o2o_batch, with kss_recip_params: overlaps one per pair, or NULL for rp->overlap everywhere; info_all: npairs *
+ * KSS_RECIP_NINFO doubles, every pair's last record, all zero for a pair that ran no pass (may be NULL).  Nothing is redefined: the
+ * definition above holds for every pair with i and k counting from 0 inside the pair, and every pair's record -- T, iterations, state,
+ * converged, last_mse, its info, pair 0's traces -- is the single-pair call's bit for bit (fitness: to the rounding of the NN
+ * engine's own summation order), in any batch order and any split over calls, through offsets that do not start at 0, under every
+ * nn_mode and tuning knob and either nn_fma; results[i].pair_id = i.  Every pair has its own cell grid over its own target's box; a
+ * pair that ends leaves the others untouched.  Behind the NN pass a pass makes the workspace reset and four launches for the whole
+ * batch and then the trimmed batch's three, whatever the pair count; the boxes are taken once per call (one launch, one
+ * synchronisation).  trace_*, rp->trace_recip and fitness_idx / fitness_d2 describe pair 0.  KSS_ERR_ARG: everything
+ * kss_icp_o2o_batch refuses, a NULL rp, a NULL ctx (refused before anything touches the device).  A refused call leaves the context
+ * usable. */
+int kss_icp_recip_pairs(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *tgt_all, const int64_t *tgt_off,
+                        const float *tgt_normals_all, int npairs, const kss_icp_params *p, const kss_recip_params *rp,
+                        const double *overlaps, kss_icp_result *results, double *info_all);
+int kss_icp_recip_pairs_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_tgt_all, const int64_t *tgt_off,
+                            const float *d_tgt_normals_all, int npairs, const kss_icp_params *p, const kss_recip_params *rp,
+                            const double *overlaps, kss_icp_result *results, double *info_all);
 
 /* ---- generalized ICP (plane-to-plane; Segal, Haehnel, Thrun: Generalized-ICP, RSS 2009) for one pair ----
  * Both clouds carry a local surface model: PCL-style GICP replaces the eigenvalues of each point's k-NN covariance by

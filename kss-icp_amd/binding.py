@@ -53,6 +53,7 @@ SYMBOLS = [
     "kss_o2o_filter", "kss_o2o_filter_dev", "kss_o2o_filter_batch", "kss_o2o_filter_batch_dev", "kss_o2o_default_params",
     "kss_icp_o2o", "kss_icp_o2o_dev", "kss_icp_o2o_batch", "kss_icp_o2o_batch_dev",
     "kss_recip_filter", "kss_recip_filter_dev", "kss_recip_default_params", "kss_icp_recip", "kss_icp_recip_dev",
+    "kss_recip_filter_batch", "kss_recip_filter_batch_dev", "kss_icp_recip_pairs", "kss_icp_recip_pairs_dev",
 ]
 
 
@@ -210,6 +211,10 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, vp, dbl, C.c_int, vp, vp, vp]
     for n in ("kss_icp_recip", "kss_icp_recip_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(RecipParams), C.POINTER(IcpResult), vp]
+    for n in ("kss_recip_filter_batch", "kss_recip_filter_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, C.c_int, vp, vp, dbl, C.c_int, vp, vp, vp]
+    for n in ("kss_icp_recip_pairs", "kss_icp_recip_pairs_dev"):      # (the many-pairs form; the C symbol is spelled _pairs: include/kssicp.h)
+        getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), C.POINTER(RecipParams), vp, vp, vp]
     L.kss_robust_default_params.argtypes = [C.c_int, C.c_int, C.POINTER(RobustParams)]
     L.kss_robust_weight.argtypes = [C.c_int, dbl, dbl, C.POINTER(dbl)]
     L.kss_robust_scale2.argtypes = [C.c_int, dbl, C.c_float, dbl, C.POINTER(dbl)]
@@ -1182,8 +1187,9 @@ class Context:
         """call(res) for a batch: the trace and fitness_corr arrays (pair 0's) attached to p / tp as in _icp_call, detached again
         whether it returns or raises.  Returns (list of IcpResult, extras of pair 0)."""
         tname = ("trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else
-                 "trace_o2o" if isinstance(tp, O2oParams) else "trace_trim")
-        ninfo = SIM_NINFO if isinstance(tp, SimParams) else O2O_NINFO if isinstance(tp, O2oParams) else TRIM_NINFO
+                 "trace_o2o" if isinstance(tp, O2oParams) else "trace_recip" if isinstance(tp, RecipParams) else "trace_trim")
+        ninfo = (SIM_NINFO if isinstance(tp, SimParams) else O2O_NINFO if isinstance(tp, O2oParams) else
+                 RECIP_NINFO if isinstance(tp, RecipParams) else TRIM_NINFO)
         npairs = len(so) - 1
         res = (IcpResult * npairs)()
         ns0 = int(so[1] - so[0]) if npairs > 0 else 0
@@ -1206,7 +1212,7 @@ class Context:
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-                if isinstance(tp, (RobustParams, SimParams, O2oParams)):
+                if isinstance(tp, (RobustParams, SimParams, O2oParams, RecipParams)):
                     setattr(tp, tname, None)
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
@@ -1324,6 +1330,70 @@ class Context:
         self._chk(self.L.kss_icp_o2o_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
                                                C.c_void_p(int(d_normals_all)) if d_normals_all else None, npairs, C.byref(params),
                                                C.byref(op), _p(ov), C.cast(res, C.c_void_p), _p(info)), "kss_icp_o2o_batch_dev")
+        return list(res), info
+
+    # ---- reciprocal ICP, many pairs per call (the C symbols of the loop are spelled _pairs: include/kssicp.h)
+    def recip_filter_batch(self, src_all, off, tgt_all, tgt_off, idx_all, d2_all, max_d2=1.0, nn_fma=0):
+        """kss_recip_filter_batch: the reciprocal filter of every segment -- sources [off[i], off[i + 1]) of src_all / idx_all / d2_all
+        against targets [tgt_off[i], tgt_off[i + 1]) of tgt_all -- in one call.  Returns (idx_f, d2_f, info nseg x 3 = {m, u, r});
+        entries outside the segments are left as given."""
+        s, t = _f32(src_all), _f32(tgt_all)
+        i = np.array(idx_all, dtype=np.int32).reshape(-1)
+        d = np.array(d2_all, dtype=np.float32).reshape(-1)
+        if len(i) != len(d) or len(i) != len(s):
+            raise ValueError("idx and d2 must have one entry per source")
+        o, to = self._offsets(off, tgt_off)
+        nseg = len(o) - 1
+        io, do = i.copy(), d.copy()
+        info = np.zeros((max(nseg, 0), 3), np.float64)
+        self._chk(self.L.kss_recip_filter_batch(self.h, _p(s), _p(o), _p(t), _p(to), nseg, _p(i), _p(d), float(max_d2), int(nn_fma), _p(io),
+                                                _p(do), _p(info)), "kss_recip_filter_batch")
+        return io, do, info
+
+    def recip_filter_batch_dev(self, d_src_all, off, d_tgt_all, tgt_off, d_idx_all, d_d2_all, max_d2=1.0, nn_fma=0, d_idx_out_all=None,
+                               d_d2_out_all=None):
+        """kss_recip_filter_batch_dev on device pointers (an output may be 0 / None, or its input); returns info nseg x 3 = {m, u, r}."""
+        o, to = self._offsets(off, tgt_off)
+        nseg = len(o) - 1
+        info = np.zeros((max(nseg, 0), 3), np.float64)
+        self._chk(self.L.kss_recip_filter_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(o), C.c_void_p(int(d_tgt_all)), _p(to), nseg,
+                                                    C.c_void_p(int(d_idx_all)), C.c_void_p(int(d_d2_all)), float(max_d2), int(nn_fma),
+                                                    C.c_void_p(int(d_idx_out_all)) if d_idx_out_all else None,
+                                                    C.c_void_p(int(d_d2_out_all)) if d_d2_out_all else None, _p(info)),
+                  "kss_recip_filter_batch_dev")
+        return info
+
+    def icp_recip_batch(self, src_all, src_off, tgt_all, tgt_off, normals_all=None, overlaps=None, overlap=1.0, metric=METRIC_POINT,
+                        params=None, trace_cap=0, fitness_corr=False):
+        """kss_icp_recip_pairs: reciprocal ICP of npairs pairs in one call.  Arguments as icp_o2o_batch().  Returns (list of
+        IcpResult, recip_info of every pair as npairs x RECIP_NINFO, dictionary with pair 0's traces, trace_recip among them)."""
+        s, t = _f32(src_all), _f32(tgt_all)
+        nr = _f32(normals_all) if normals_all is not None else None
+        if nr is not None and len(nr) != len(t):
+            raise ValueError("normals must have one row per target point")
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        ov = self._overlaps(overlaps, npairs)
+        p = params if params is not None else self.icp_params()
+        rp = RecipParams(float(overlap), int(metric), None)
+        info = np.zeros((max(npairs, 0), RECIP_NINFO), np.float64)
+        res, extra = self._batch_call(
+            lambda res: self.L.kss_icp_recip_pairs(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), npairs, C.byref(p), C.byref(rp), _p(ov), res, _p(info)),
+            "kss_icp_recip_pairs", p, so, P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, rp)
+        return res, info, extra
+
+    def icp_recip_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params, overlaps=None, overlap=1.0,
+                            metric=METRIC_POINT):
+        """kss_icp_recip_pairs_dev on device pointers; returns (list of IcpResult, recip_info npairs x RECIP_NINFO)."""
+        so, to = self._offsets(src_off, tgt_off)
+        npairs = len(so) - 1
+        ov = self._overlaps(overlaps, npairs)
+        res = (IcpResult * npairs)()
+        rp = RecipParams(float(overlap), int(metric), None)
+        info = np.zeros((npairs, RECIP_NINFO), np.float64)
+        self._chk(self.L.kss_icp_recip_pairs_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
+                                                 C.c_void_p(int(d_normals_all)) if d_normals_all else None, npairs, C.byref(params),
+                                                 C.byref(rp), _p(ov), C.cast(res, C.c_void_p), _p(info)), "kss_icp_recip_pairs_dev")
         return list(res), info
 
     def icp_sim_batch(self, src_all, src_off, tgt_all, tgt_off, overlaps=None, sp=None, params=None, trace_cap=0, fitness_corr=False):

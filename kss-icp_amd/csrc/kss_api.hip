@@ -70,7 +70,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_slot, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp, &c->o2o_table, &c->o2o_idx, &c->o2o_d2, &c->recip_sorted, &c->recip_box};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp, &c->o2o_table, &c->o2o_idx, &c->o2o_d2, &c->recip_sorted, &c->recip_box, &c->recip_grids};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -424,8 +424,8 @@ int kss_rigid_from_sums(const double sums[KSS_NSUMS], float T[16]) {
 }
 
 // ---- the pair metrics --------------------------------------------------------------
-// What the 46 entry points kss_*_sums, kss_icp_* and kss_icp_*_batch of p2l, trimmed, sim, robust, gicp, symm, symm_robust, o2o and
-// recip share.  A host entry and its _dev twin call one internal function with `host` set or not, and that function reads: family
+// What the 48 entry points kss_*_sums, kss_icp_* and kss_icp_*_batch of p2l, trimmed, sim, robust, gicp, symm, symm_robust, o2o and
+// recip (its batch: kss_icp_recip_pairs) share.  A host entry and its _dev twin call one internal function with `host` set or not, and that function reads: family
 // check, shared check (pair_check / sums_check), pair_enter, pair_normals, the family's mode, the run (pair_go / pair_record_dev).
 static inline bool trim_overlap_ok(double overlap) { return overlap > 0.0 && overlap <= 1.0; }   // (a NaN fails both)
 
@@ -1241,7 +1241,7 @@ int kss_o2o_filter(kss_ctx* c, const int32_t* idx, const float* d2, int64_t n, i
     return kss_o2o_filter_batch(c, idx, d2, off, &nt, 1, max_d2, idx_out, d2_out, info);
 }
 
-// ---- reciprocal ICP: the trimmed families' path with PairMode::mutual, one pair only --
+// ---- reciprocal ICP: the trimmed families' path with PairMode::mutual, one pair and many pairs per call --
 int kss_recip_default_params(kss_recip_params* rp) {
     if (!rp) return KSS_ERR_ARG;
     rp->overlap = 1.0;
@@ -1298,6 +1298,77 @@ int kss_recip_filter(kss_ctx* c, const float* src, int64_t n, const float* tgt, 
                           d2_out ? (float*)c->stage_d2.p : nullptr, info));
     if (idx_out) HIPCHK(c, hipMemcpyAsync(idx_out, c->stage_idx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (d2_out) HIPCHK(c, hipMemcpyAsync(d2_out, c->stage_d2.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KSS_OK;
+}
+
+// many pairs per call.  The C symbols are spelled _pairs: see include/kssicp.h
+int kss_icp_recip_pairs_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_tgt_all, const int64_t* tgt_off,
+                            const float* d_nrm_all, int npairs, const kss_icp_params* p, const kss_recip_params* rp, const double* overlaps,
+                            kss_icp_result* results, double* info_all) {
+    KCHK(params_check(c, "icp_recip_pairs", rp));
+    return icp_trimmed_any(c, "icp_recip_pairs", false, many_pairs(d_src_all, src_off, nullptr, d_tgt_all, tgt_off, d_nrm_all, npairs), p,
+                           recip_mode_of(rp), rp->metric, overlaps, results, info_all);
+}
+int kss_icp_recip_pairs(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* tgt_all, const int64_t* tgt_off,
+                        const float* nrm_all, int npairs, const kss_icp_params* p, const kss_recip_params* rp, const double* overlaps,
+                        kss_icp_result* results, double* info_all) {
+    KCHK(params_check(c, "icp_recip_pairs", rp));
+    return icp_trimmed_any(c, "icp_recip_pairs", true, many_pairs(src_all, src_off, nullptr, tgt_all, tgt_off, nrm_all, npairs), p,
+                           recip_mode_of(rp), rp->metric, overlaps, results, info_all);
+}
+
+// the filter alone for nseg segments: the arguments of both entry points
+static int recip_filter_batch_check(kss_ctx* c, const void* src, const int64_t* off, const void* tgt, const int64_t* tgt_off, int nseg,
+                                    const void* idx, const void* d2, const double* info) {
+    if (!src || !off || !tgt || !tgt_off || !idx || !d2 || !info) return set_err(c, KSS_ERR_ARG, "recip_filter_batch: null argument");
+    if (nseg <= 0) return set_err(c, KSS_ERR_ARG, "recip_filter_batch: no segment");
+    for (int i = 0; i < nseg; ++i) {
+        const int64_t n = off[i + 1] - off[i], nt = tgt_off[i + 1] - tgt_off[i];
+        if (n <= 0 || n > 0x7fff0000ll || nt <= 0 || nt > 0x7fff0000ll)
+            return set_err(c, KSS_ERR_ARG, "recip_filter_batch: segment or target count empty or out of range");
+    }
+    if (off[nseg] - off[0] > 0x7fff0000ll || tgt_off[nseg] - tgt_off[0] > 0x7fff0000ll)
+        return set_err(c, KSS_ERR_ARG, "recip_filter_batch: batch too large");
+    return KSS_OK;
+}
+// both offset arrays rebased to their first entry
+static void recip_filter_rebase(const int64_t* off, const int64_t* tgt_off, int nseg, std::vector<int64_t>& o, std::vector<int64_t>& to) {
+    o.resize((size_t)nseg + 1); to.resize((size_t)nseg + 1);
+    for (int i = 0; i <= nseg; ++i) { o[i] = off[i] - off[0]; to[i] = tgt_off[i] - tgt_off[0]; }
+}
+
+int kss_recip_filter_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* off, const float* d_tgt_all, const int64_t* tgt_off, int nseg,
+                               const int32_t* d_idx_all, const float* d_d2_all, double max_d2, int nn_fma, int32_t* d_idx_out_all,
+                               float* d_d2_out_all, double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(recip_filter_batch_check(c, d_src_all, off, d_tgt_all, tgt_off, nseg, d_idx_all, d_d2_all, info_all));
+    std::vector<int64_t> o, to;
+    recip_filter_rebase(off, tgt_off, nseg, o, to);
+    const int64_t o0 = off[0], t0 = tgt_off[0];
+    return recip_filter_batch_dev(c, d_src_all + 3 * o0, o.data(), d_tgt_all + 3 * t0, to.data(), nseg, d_idx_all + o0, d_d2_all + o0, max_d2,
+                                  nn_fma != 0, d_idx_out_all ? d_idx_out_all + o0 : nullptr, d_d2_out_all ? d_d2_out_all + o0 : nullptr, info_all);
+}
+
+int kss_recip_filter_batch(kss_ctx* c, const float* src_all, const int64_t* off, const float* tgt_all, const int64_t* tgt_off, int nseg,
+                           const int32_t* idx_all, const float* d2_all, double max_d2, int nn_fma, int32_t* idx_out_all, float* d2_out_all,
+                           double* info_all) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(recip_filter_batch_check(c, src_all, off, tgt_all, tgt_off, nseg, idx_all, d2_all, info_all));
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> o, to;
+    recip_filter_rebase(off, tgt_off, nseg, o, to);
+    const int64_t o0 = off[0], t0 = tgt_off[0], n = o[nseg], nt = to[nseg];
+    KCHK(upload(c, c->stage_src, src_all + 3 * o0, (size_t)n * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_tgt, tgt_all + 3 * t0, (size_t)nt * 3 * sizeof(float)));
+    KCHK(upload(c, c->stage_idx, idx_all + o0, (size_t)n * sizeof(int32_t)));
+    KCHK(upload(c, c->stage_d2, d2_all + o0, (size_t)n * sizeof(float)));
+    // filtered in place on the staged copies, then back to whichever outputs the caller gave
+    KCHK(recip_filter_batch_dev(c, (const float*)c->stage_src.p, o.data(), (const float*)c->stage_tgt.p, to.data(), nseg,
+                                (const int32_t*)c->stage_idx.p, (const float*)c->stage_d2.p, max_d2, nn_fma != 0,
+                                idx_out_all ? (int32_t*)c->stage_idx.p : nullptr, d2_out_all ? (float*)c->stage_d2.p : nullptr, info_all));
+    if (idx_out_all) HIPCHK(c, hipMemcpyAsync(idx_out_all + o0, c->stage_idx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (d2_out_all) HIPCHK(c, hipMemcpyAsync(d2_out_all + o0, c->stage_d2.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KSS_OK;
 }

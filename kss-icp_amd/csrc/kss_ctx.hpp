@@ -73,6 +73,13 @@ struct kss_ctx {
     // rewritten by every pass, the bounding-box partials of the call's target and the cell grid derived from them
     DevBuf recip_sorted, recip_box;
     RecipGrid recip_grid = {0.0f, 0.0f, 0.0f, 0.0f, 1, 1, 1};
+    // ... for many pairs per call: one workspace in o2o_table's buffer (the claim table over the batch's targets, four
+    // counters per pair, every pair's cell counts), recip_sorted over the batch's sources, recip_box the per-pair box partials, and the
+    // per-pair {grid, first cell} table: the host copy (kept here so that its upload needs no synchronisation of its own), the device
+    // copy and the batch's cell total
+    DevBuf recip_grids;
+    std::vector<RecipPairDev> h_recip_grids;
+    int64_t recipb_cells = 0;
     void* h_gicp = nullptr; size_t h_gicp_cap = 0;
     void* h_gicp_dev = nullptr;   // (the pinned copy as the device sees it: KSS_GICP_TABLE_MAPPED, an A/B switch)
     const PairState* last_state_dev = nullptr;   // the per-pair state table the last batched NN pass read (null: none, a single pair)
@@ -283,7 +290,7 @@ struct PairMode {
     bool unique = false;            // one-to-one rejection in front of the trimmed pass (kss_icp_o2o; with trimmed, not with robust, gicp,
                                     // symm or sim): the info records hold KSS_O2O_NINFO doubles, [0] = u, [4] = m
     bool mutual = false;            // reciprocal rejection in front of the trimmed pass (kss_icp_recip; with trimmed, never with unique,
-                                    // robust, gicp, symm or sim, one pair only): KSS_RECIP_NINFO doubles, [0] = r, [4] = m, [5] = u
+                                    // robust, gicp, symm or sim; one pair or a batch): KSS_RECIP_NINFO doubles, [0] = r, [4] = m, [5] = u
 };
 static_assert(KSS_ROBUST_NINFO == KSS_TRIM_NINFO, "the pair loop carries both info records in the same four slots");
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
@@ -312,6 +319,11 @@ int o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, const in
 // d_tgt, reverse distances by dist2<nn_fma>; the filtered arrays (either may be null or its input) and info = {m, u, r}
 int recip_filter_dev(kss_ctx* c, const float* d_src, int64_t n, const float* d_tgt, int64_t nt, const int32_t* d_idx, const float* d_d2,
                      double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out, double* info);
+// the same for nseg segments in the batch's five steps (kss_recip_filter_batch_dev): sources [off[i], off[i + 1]) of d_src / d_idx /
+// d_d2 against targets [tgt_off[i], tgt_off[i + 1]) of d_tgt, both offset arrays from 0; info_all = {m, u, r} per segment
+int recip_filter_batch_dev(kss_ctx* c, const float* d_src, const int64_t* off, const float* d_tgt, const int64_t* tgt_off, int nseg,
+                           const int32_t* d_idx, const float* d_d2, double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out,
+                           double* info_all);
 // host-mapped {value, sequence number} result slots: allocate them; wait for the first nslots of launch c->seq
 int ensure_pub_slots(kss_ctx* c);
 int wait_slots(kss_ctx* c, int nslots, double* out);

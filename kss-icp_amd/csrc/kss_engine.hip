@@ -1934,9 +1934,10 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // table reset, claim, resolve) filter the NN pass's idx / d2 into o2o_idx / o2o_d2, which the selection and the rows launch read in
 // their place; the info record grows to KSS_O2O_NINFO = {u, k, tau, kept, m}, m published by the resolve launch behind the
 // selection's four slots.  The NN pass's own arrays stay as written: the fitness pass and fitness_idx / fitness_d2 are unfiltered.
-// Reciprocal (kss_icp_recip; M.mutual with M.trimmed, either metric, one pair only): five launches ahead of the
+// Reciprocal (kss_icp_recip; M.mutual with M.trimmed, either metric): five launches ahead of the
 // selection (kss_recip.hip: reset, claim + count, scan, scatter, resolve + check) filter the same arrays the same way, against the
 // positions the NN pass wrote; the info record grows to KSS_RECIP_NINFO = {r, k, tau, kept, m, u}, m and u published by the resolve launch.
+// Many pairs per call (kss_icp_recip_pairs): the same five steps once for the whole batch, every pair on its own grid.
 // the rotation block of a row-major 4 x 4 (the float bits of the accumulated Matrix4f)
 static GicpRot rot_of(const float* F) { return GicpRot{{F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]}}; }
 
@@ -2017,9 +2018,11 @@ static int pair_pass_launch(kss_ctx* c, const PairArgs& a, const PairMode& M, co
 // npairs >= 1 pairs, the same order of launches over the per-pair tables of a: d_rec: np records of P2L_NSUMS doubles, d_info: np
 // info records of four slots, the one-to-one's np m's behind them.  rob_select: some pair takes its scale from the pass's median
 // key (the point metric's keys are the NN pass's d2).  A pass table on the device is first copied from the pinned one as the host
-// steps left it: the last pass's synchronisation has ordered those writes behind its copy.
+// steps left it: the last pass's synchronisation has ordered those writes behind its copy.  Reciprocal: the reset and four launches
+// for the whole batch against a.s's positions, the reverse distances by dist2<nn_fma>; every pair's m and u land behind the np
+// selection records, two slots per pair.
 static int pairb_pass_launch(kss_ctx* c, const PairbArgs& a, const PairMode& M, int np, int total_rows, int64_t total_tgt, bool rob_select,
-                             double* d_rec, double* d_info) {
+                             double* d_rec, double* d_info, bool nn_fma = false) {
     ProfScope ps(c, KSS_K_CORR_REDUCE);
     const hipStream_t st = c->stream;
     const double max_d2 = a.s.max_d2;
@@ -2030,6 +2033,12 @@ static int pairb_pass_launch(kss_ctx* c, const PairbArgs& a, const PairMode& M, 
                             (unsigned long long*)c->o2o_table.p, (unsigned*)((unsigned long long*)c->o2o_table.p + total_tgt),
                             (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + (size_t)np * KSS_TRIM_NINFO};
         if (launch_o2o(st, total_rows, total_tgt, np, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
+    }
+    if (M.mutual) {   // reset, claim + count, scan, scatter, resolve + check for the whole batch
+        RecipbArgs ra = {a.s, a.tgt, a.desc, a.row_pair, a.state, (const RecipPairDev*)c->recip_grids.p, c->o2o_table.p, total_tgt, np,
+                         (float4*)c->recip_sorted.p, (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + (size_t)np * KSS_TRIM_NINFO};
+        ra.s.idx = (const int32_t*)c->p2l_idx.p; ra.s.d2 = (const float*)c->p2l_d2.p;
+        if (launch_recipb(st, total_rows, c->recipb_cells, ra, nn_fma) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
     }
     if (M.trimmed) launch_pairb_select(st, a.s.d2, a.desc, np, a.state, max_d2, a.ts, d_info);
     if (M.robust) {
@@ -2086,16 +2095,17 @@ struct DeferWait {   // the NN pass does not wait for its sums: the launches beh
     explicit DeferWait(kss_ctx* c_) : c(c_) { c->defer_wait = true; }
     ~DeferWait() { c->defer_wait = false; }
 };
-// pair p's info record behind a pass, from the host-mapped tables h: np records, np selection records, np m's (one-to-one)
+// pair p's info record behind a pass, from the host-mapped tables h: np records, np selection records, np m's (one-to-one) or np
+// {m, u} (reciprocal)
 static void pair_info_read(const PairMode& M, const double* h, int np, int p, double* info) {
     if (!M.trimmed && !M.robust) return;
     const double* hinfo = h + (size_t)np * P2L_NSUMS;
     std::memcpy(info, hinfo + (size_t)p * KSS_TRIM_NINFO, KSS_TRIM_NINFO * sizeof(double));
     if (M.trimmed) info[3] = h[(size_t)p * P2L_NSUMS];   // the correspondences the step is computed from (plane: those of the cut with a finite normal)
     if (M.unique) info[4] = hinfo[(size_t)np * KSS_TRIM_NINFO + p];   // one-to-one: m, the candidates before the rejection ([0] is u)
-    if (M.mutual) {   // reciprocal (one pair): m and u ([0] is r)
-        info[4] = hinfo[KSS_TRIM_NINFO];
-        info[5] = hinfo[KSS_TRIM_NINFO + 1];
+    if (M.mutual) {   // reciprocal: m and u ([0] is r), two slots per pair behind the np selection records
+        info[4] = hinfo[(size_t)np * KSS_TRIM_NINFO + 2 * (size_t)p];
+        info[5] = hinfo[(size_t)np * KSS_TRIM_NINFO + 2 * (size_t)p + 1];
     }
 }
 static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, const PairMode& M, const float* d_tgt, const float* d_nrm,
@@ -2166,7 +2176,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
             const PairbArgs a = {s, d_tgt, d_nrm, (const PairbDesc*)c->pb_desc.p, (const int32_t*)c->pb_rowpair.p, c->last_state_dev,
                                  (const RobustScale*)c->pb_rscale.p, (TrimState*)c->trim_state.p, d_pass, (double*)c->p2l_rows.p,
                                  (float*)c->rob_keys.p};
-            KCHK(pairb_pass_launch(c, a, M, np, total_rows, total_tgt, rob_select, d_rec, d_info));
+            KCHK(pairb_pass_launch(c, a, M, np, total_rows, total_tgt, rob_select, d_rec, d_info, P.nn_fma != 0));
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2237,7 +2247,6 @@ static int pair_mode_check(kss_ctx* c, const char* who, const PairMode& M, const
         return bad("one-to-one rejection is the trimmed pass's, neither robust, generalized, symmetric nor similarity");
     if (M.mutual && (!M.trimmed || M.unique || M.robust || M.gicp || M.symm || M.sim))
         return bad("reciprocal rejection is the trimmed pass's, neither one-to-one, robust, generalized, symmetric nor similarity");
-    if (M.mutual && batch) return bad("reciprocal rejection for many pairs per call is not built (kss_icp_recip_batch is the follow-up)");
     if (!batch) return KSS_OK;
     if (M.robust && !rscales) return bad("robust needs the per-pair scales");
     if (M.gicp && !gicp_eps) return bad("generalized ICP needs the per-pair epsilons");
@@ -2297,6 +2306,51 @@ static int recip_setup(kss_ctx* c, const float* d_tgt, int64_t nt, int64_t n) {
     c->recip_grid = recip_grid_of(mn, mx, n);
     KCHK(ensure(c, c->o2o_table, recip_work_bytes(nt, recip_cells(c->recip_grid))));
     return ensure(c, c->recip_sorted, (size_t)n * sizeof(float4));
+}
+
+// reciprocal for many pairs, once per call, behind stage_pairb: every pair's target box from ONE launch over the
+// staged descriptors (`split` partials per pair, one copy back and ONE synchronisation whatever the pair count), every pair's grid
+// by the single pair's rule -- recip_grid_of(the box of ITS target, ITS source count) -- with its first cell, staged next to
+// pb_desc; the workspace and the batch's cell-ordered source array of total_src float4.
+// A pair's grid here does not have to equal the single-pair call's in any bit (the partials are cut differently; fminf / fmaxf may
+// hand back either zero of a tie).  It cannot matter: "mutual" is an existence statement over ALL sources of the pair, the box walk
+// is proven to hold every source that can hit on ANY grid of this form, and the escape scans the pair's whole slice -- which sources
+// are examined, and in what order, does not change a bit of the result.
+static int recipb_setup(kss_ctx* c, const float* d_tgt, const std::vector<PairbDesc>& desc, int64_t total_src, const char* who) {
+    const int np = (int)desc.size();
+    int64_t total_tgt = 0, max_nt = 0;
+    for (const PairbDesc& d : desc) { total_tgt += d.nt; max_nt = std::max(max_nt, d.nt); }
+    const int split = (int)std::max<int64_t>(1, std::min<int64_t>(64, (max_nt + 4 * 1024 - 1) / (4 * 1024)));
+    if (total_tgt > 0x7fff0000ll || (int64_t)np * split > 0x7fff0000ll)
+        return set_err(c, KSS_ERR_ARG, (std::string(who) + ": batch too large for 32-bit indexing").c_str());
+    const size_t nbox = (size_t)np * split;
+    KCHK(ensure(c, c->recip_box, nbox * 6 * sizeof(float)));
+    launch_recipb_bbox(c->stream, d_tgt, (const PairbDesc*)c->pb_desc.p, np, split, (float*)c->recip_box.p);
+    HIPCHK(c, hipGetLastError());
+    std::vector<float> hb(nbox * 6);
+    HIPCHK(c, hipMemcpyAsync(hb.data(), c->recip_box.p, hb.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->h_recip_grids.resize((size_t)np);
+    int64_t cells = 0;
+    for (int p = 0; p < np; ++p) {
+        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int b = 0; b < split; ++b)
+            for (int k = 0; k < 3; ++k) {
+                mn[k] = std::fmin(mn[k], hb[((size_t)p * split + b) * 6 + k]);
+                mx[k] = std::fmax(mx[k], hb[((size_t)p * split + b) * 6 + 3 + k]);
+            }
+        RecipPairDev& gp = c->h_recip_grids[p];
+        gp.g = recip_grid_of(mn, mx, desc[p].ns);
+        gp.cell_base = (int32_t)cells;
+        cells += recip_cells(gp.g);
+        if (cells > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": batch too large for 32-bit indexing").c_str());
+    }
+    c->recipb_cells = cells;
+    KCHK(ensure(c, c->recip_grids, (size_t)np * sizeof(RecipPairDev)));
+    // (the source of this copy is the context's own vector: it outlives the copy, no synchronisation here)
+    HIPCHK(c, hipMemcpyAsync(c->recip_grids.p, c->h_recip_grids.data(), (size_t)np * sizeof(RecipPairDev), hipMemcpyHostToDevice, c->stream));
+    KCHK(ensure(c, c->o2o_table, recipb_work_bytes(total_tgt, np, cells)));
+    return ensure(c, c->recip_sorted, (size_t)total_src * sizeof(float4));
 }
 
 int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt, int64_t nt, const float* d_nrm,
@@ -2410,7 +2464,13 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         KCHK(ensure(c, c->o2o_idx, (size_t)pl.total_src * sizeof(int32_t)));
         KCHK(ensure(c, c->o2o_d2, (size_t)pl.total_src * sizeof(float)));
     }
-    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO + 1) * sizeof(double)));
+    if (M.mutual) {   // the filtered idx / d2; every pair's grid over its own target's box, the workspace and the cell-ordered sources
+        if (tgt_off[0] != 0) return set_err(c, KSS_ERR_ARG, "pairs_run: the target offsets must start at 0");
+        KCHK(ensure(c, c->o2o_idx, (size_t)pl.total_src * sizeof(int32_t)));
+        KCHK(ensure(c, c->o2o_d2, (size_t)pl.total_src * sizeof(float)));
+        KCHK(recipb_setup(c, d_tgt, desc, pl.total_src, "pairs_run"));
+    }
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO + 2) * sizeof(double)));   // (+ m, or m and u)
     KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));
     KCHK(grid_setup(c, pl));
     KCHK(grid_setup_batch(c, pl));
@@ -2479,6 +2539,39 @@ int recip_filter_dev(kss_ctx* c, const float* d_src, int64_t n, const float* d_t
     HIPCHK(c, hipMemcpyAsync(cnt, recip_counters(c->o2o_table.p, nt), sizeof cnt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int q = 0; q < 3; ++q) info[q] = (double)(cnt[q] + 1u);
+    return KSS_OK;
+}
+
+// the reciprocal filter alone for nseg segments (kss_recip_filter_batch_dev): the batched loop's setup and its reset and four
+// launches on packed float triples, then every segment's counters read back (each holds its count minus one)
+int recip_filter_batch_dev(kss_ctx* c, const float* d_src, const int64_t* off, const float* d_tgt, const int64_t* tgt_off, int nseg,
+                           const int32_t* d_idx, const float* d_d2, double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out,
+                           double* info_all) {
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<PairbDesc> desc((size_t)nseg);
+    int64_t total_rows = 0;
+    for (int i = 0; i < nseg; ++i) {
+        PairbDesc& d = desc[i];
+        d.src_base = off[i]; d.ns = off[i + 1] - off[i];
+        d.tgt_off = tgt_off[i]; d.nt = tgt_off[i + 1] - tgt_off[i]; d.overlap = 1.0;
+        d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(d.ns);
+        total_rows += d.nrows;
+        if (total_rows > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "recip_filter_batch: batch too large for 32-bit indexing");
+    }
+    KCHK(stage_pairb(c, desc, true));
+    KCHK(recipb_setup(c, d_tgt, desc, off[nseg], "recip_filter_batch"));
+    const int64_t total_tgt = tgt_off[nseg];
+    const RecipbArgs ra = {{d_src, nullptr, nullptr, d_idx, d_d2, nullptr, max_d2}, d_tgt, (const PairbDesc*)c->pb_desc.p,
+                           (const int32_t*)c->pb_rowpair.p, nullptr, (const RecipPairDev*)c->recip_grids.p, c->o2o_table.p, total_tgt, nseg,
+                           (float4*)c->recip_sorted.p, d_idx_out, d_d2_out, nullptr};
+    if (launch_recipb(c->stream, (int)total_rows, c->recipb_cells, ra, nn_fma) != 0)
+        return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
+    HIPCHK(c, hipGetLastError());
+    std::vector<unsigned> cnt((size_t)nseg * 4);
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), recipb_counters(c->o2o_table.p, total_tgt), cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < nseg; ++i)
+        for (int q = 0; q < 3; ++q) info_all[(size_t)i * 3 + q] = (double)(cnt[(size_t)i * 4 + q] + 1u);
     return KSS_OK;
 }
 

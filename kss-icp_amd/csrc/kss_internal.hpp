@@ -502,6 +502,38 @@ RecipGrid recip_grid_of(const float mn[3], const float mx[3], int64_t n);
 // reset, claim + count, scan, scatter, resolve + check: five launches.  0, or the hipError_t of the reset.
 int launch_recip(hipStream_t st, const RecipArgs& a, bool nn_fma);
 
+// ---- the same for many pairs per call (kss_recip.hip) ----
+// one pair's grid -- recip_grid_of(the box of ITS target, ITS source count) -- and where its cells start in the batch's cell counts
+struct alignas(16) RecipPairDev {
+    RecipGrid g;
+    int32_t cell_base;
+};
+static_assert(sizeof(RecipPairDev) == 32, "the host and the device table share this layout");
+// The batched filter's arguments, by value.  s, tgt: batch-wide, as in PairbArgs (s.src3: the filter alone, packed triples by global
+// source index; else s.src4 with s.perm); s.idx / s.d2: the NN pass's, a pair's at desc[p].src_base, idx counting inside its own
+// target; desc / row_pair / state as in O2oArgs; grids: one RecipPairDev per pair.  work: recipb_work_bytes(total_tgt, npairs,
+// total_cells) of workspace, all ones before every pass -- the claim table (one uint64 per target of the batch, pair p's at
+// desc[p].tgt_off), four uint32 counters {m, u, r, unused} per pair, one uint32 per cell of every pair (pair p's at
+// grids[p].cell_base), each MINUS ONE.  sorted: one float4 {x, y, z, bits(index inside the pair)} per source of the batch, pair p's
+// cell-ordered sources in [src_base, src_base + ns).  idx_out / d2_out: laid out like s.idx / s.d2 (either may be null or its
+// input); info_mu: two doubles {m, u} per pair (device or host-mapped, may be null).
+struct RecipbArgs {
+    PairSrc s;
+    const float* tgt;
+    const PairbDesc* desc; const int32_t* row_pair; const PairState* state; const RecipPairDev* grids;
+    void* work; int64_t total_tgt; int32_t npairs;
+    float4* sorted;
+    int32_t* idx_out; float* d2_out;
+    double* info_mu;
+};
+size_t recipb_work_bytes(int64_t total_tgt, int npairs, int64_t total_cells);
+__host__ __device__ inline unsigned* recipb_counters(void* work, int64_t total_tgt) { return (unsigned*)((unsigned long long*)work + total_tgt); }
+// every pair's target box in ONE launch: `split` partials of 6 floats {min xyz, max xyz} per pair, pair p's at d_box + 6 * split * p
+void launch_recipb_bbox(hipStream_t st, const float* d_tgt, const PairbDesc* d_desc, int npairs, int split, float* d_box);
+// reset, claim + count, scan, scatter, resolve + check for the whole batch: the reset and four launches, total_rows workgroups in the
+// walks and the resolve, one workgroup per pair in the scan.  0, or the hipError_t of the reset.
+int launch_recipb(hipStream_t st, int total_rows, int64_t total_cells, const RecipbArgs& a, bool nn_fma);
+
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,
                 const std::function<void*(size_t)>& scratch);

@@ -31,6 +31,8 @@
 // coordinate is a monotone function of it (float subtract, multiply by inv_h > 0, floor, clamp): lo <= p <= hi gives
 // cell(lo) <= cell(p) <= cell(hi).
 // The grid is o2o_kernel's: stream_blocks(n) workgroups of 256.  No inline assembly, no float atomics, LDS for the wave counters only.
+// Many pairs per call (kss_icp_recip_pairs, kss_recip_filter_batch): the recipb_* kernels at the end of this file run
+// the same five steps for a whole batch, every pair on its own slices of the workspace, with the device helpers below shared.
 #include <cmath>
 
 #include "kss_device.hpp"
@@ -358,6 +360,248 @@ int launch_recip(hipStream_t st, const RecipArgs& a, bool nn_fma) {
     else launch_recip_walks<SRC_F4>(st, a, nb, (int)ncells);
     if (nn_fma) hipLaunchKernelGGL(recip_resolve_kernel<true>, dim3(nb), dim3(RECIP_THREADS), 0, st, a);
     else hipLaunchKernelGGL(recip_resolve_kernel<false>, dim3(nb), dim3(RECIP_THREADS), 0, st, a);
+    return 0;
+}
+
+// ---- many pairs per call ----
+// The same five steps for a whole batch: ONE reset and FOUR launches, whatever the pair count.  Every pair keeps what the single pair
+// has -- its own slice of the claim table, its own four counters, its own grid and cell counts, its own slice of `sorted` -- so the
+// statements above hold per pair with `i`, `k` and the keys counting from 0 INSIDE the pair.  The walks and the resolve run on
+// o2o_kernel's grid (the pair's stream_blocks(ns_p) workgroups through the row -> pair table: a workgroup belongs to ONE pair, so
+// every ballot, shuffle and wave-wide hand-over stays inside a pair); the scan gives every pair one workgroup of 1024.  Workgroups of
+// a pair that is no longer active leave at once, before any barrier, and write nothing.
+struct RecipbPair {
+    PairbDesc d;
+    RecipGrid g;
+    unsigned long long* table; unsigned* counters; unsigned* cells;
+    float4* sorted;
+};
+__device__ __forceinline__ RecipbPair recipb_pair(const RecipbArgs& a, int p) {
+    const RecipPairDev gp = a.grids[p];
+    unsigned* counters = recipb_counters(a.work, a.total_tgt);
+    RecipbPair w;
+    w.d = a.desc[p];
+    w.g = gp.g;
+    w.table = (unsigned long long*)a.work + w.d.tgt_off;
+    w.counters = counters + 4 * (int64_t)p;
+    w.cells = counters + 4 * (int64_t)a.npairs + gp.cell_base;
+    w.sorted = a.sorted + w.d.src_base;
+    return w;
+}
+__device__ __forceinline__ bool recipb_active(const RecipbArgs& a, int p) { return !a.state || a.state[p].active != 0; }
+
+// SCATTER false: claim + count; true: scatter + the winners' count.  i: the source's index inside its pair (keys, sorted's .w);
+// src_base + i: where its idx, d2 and position are
+template <int SRC, bool SCATTER>
+__global__ __launch_bounds__(RECIP_THREADS) void recipb_walk_kernel(const RecipbArgs a) {
+    __shared__ unsigned wave_cnt[RECIP_THREADS / 64];
+    const int p = a.row_pair[blockIdx.x];
+    if (!recipb_active(a, p)) return;
+    const RecipbPair w = recipb_pair(a, p);
+    const int64_t ns = w.d.ns, base = w.d.src_base;
+    const int64_t step = (int64_t)w.d.nrows * RECIP_THREADS;
+    unsigned cnt = 0u;
+    for (int64_t i0 = (int64_t)((int)blockIdx.x - w.d.row_base) * RECIP_THREADS; i0 < ns; i0 += step) {   // (i0 is the same in every lane)
+        const int64_t i = i0 + threadIdx.x;
+        const bool live = i < ns;
+        const int32_t j = live ? a.s.idx[base + i] : -1;
+        const float v = live ? a.s.d2[base + i] : __uint_as_float(0x7fc00000u);
+        const bool cand = live && o2o_candidate(j, v, w.d.nt, a.s.max_d2);
+        float x = 0.0f, y = 0.0f, z = 0.0f;
+        if (live) recip_pos<SRC>(a.s, base + i, x, y, z);
+        const bool binned = live && recip_finite(x, y, z);
+        const int cell = binned ? recip_cell(w.g, x, y, z) : 0;
+        if constexpr (!SCATTER) {
+            if (cand) atomicMin(&w.table[j], o2o_key(v, i));
+            recip_take(w.cells, cell, binned);
+            cnt += (unsigned)__popcll(__ballot(cand));
+        } else {
+            const unsigned slot = recip_take(w.cells, cell, binned);
+            if (binned && (int64_t)slot < ns) w.sorted[slot] = make_float4(x, y, z, __uint_as_float((unsigned)i));
+            const bool win = cand && w.table[j] == o2o_key(v, i);
+            cnt += (unsigned)__popcll(__ballot(win));
+        }
+    }
+    o2o_count(cnt, wave_cnt, w.counters + (SCATTER ? 1 : 0));
+}
+
+// recip_scan_kernel's two sweeps, one workgroup per pair over the pair's own cells: the starts count from the pair's slice of `sorted`
+__global__ __launch_bounds__(RECIP_SCAN_THREADS) void recipb_scan_kernel(const RecipbArgs a) {
+    constexpr int NW = RECIP_SCAN_THREADS / 64;
+    __shared__ unsigned wave_tot[NW];
+    const int p = blockIdx.x;
+    if (!recipb_active(a, p)) return;
+    const RecipPairDev gp = a.grids[p];
+    unsigned* __restrict__ cells = recipb_counters(a.work, a.total_tgt) + 4 * (int64_t)a.npairs + gp.cell_base;
+    const int ncells = (int)recip_cells(gp.g);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int run = (ncells + NW * 64 - 1) / (NW * 64) * 64;
+    const int b = min(wave * run, ncells), e = min(b + run, ncells);
+    unsigned s = 0u;
+#pragma unroll 4
+    for (int k = b + lane; k < e; k += 64) s += cells[k] + 1u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) wave_tot[wave] = s;
+    __syncthreads();
+    unsigned carry = 0u;
+    for (int q = 0; q < wave; ++q) carry += wave_tot[q];
+    unsigned next = b + lane < e ? cells[b + lane] + 1u : 0u;
+    for (int k0 = b; k0 < e; k0 += 64) {
+        const int k = k0 + lane;
+        const unsigned c = next;
+        next = k + 64 < e ? cells[k + 64] + 1u : 0u;
+        unsigned incl = c;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned up = __shfl_up(incl, off, 64);
+            if (lane >= off) incl += up;
+        }
+        if (k < e) cells[k] = carry + incl - c;
+        carry += __shfl(incl, 63, 64);
+    }
+}
+
+// recip_resolve_kernel's walk with the pair's grid, the pair's binned count and the pair's target
+template <bool FMA>
+__global__ __launch_bounds__(RECIP_THREADS) void recipb_resolve_kernel(const RecipbArgs a) {
+    __shared__ unsigned wave_cnt[RECIP_THREADS / 64];
+    const int p = a.row_pair[blockIdx.x];
+    if (!recipb_active(a, p)) return;
+    const RecipbPair w = recipb_pair(a, p);
+    const RecipGrid g = w.g;
+    const float* __restrict__ tgt = a.tgt + 3 * w.d.tgt_off;
+    const int64_t ns = w.d.ns, base = w.d.src_base;
+    const int64_t ncells = recip_cells(g);
+    const int64_t step = (int64_t)w.d.nrows * RECIP_THREADS;
+    const int lane = threadIdx.x & 63;
+    unsigned total = w.cells[ncells - 1];   // the pair's last cell's end: every binned source of the pair
+    if ((int64_t)total > ns) total = (unsigned)ns;
+    unsigned cnt = 0u;
+    for (int64_t i0 = (int64_t)((int)blockIdx.x - w.d.row_base) * RECIP_THREADS; i0 < ns; i0 += step) {   // (i0 is the same in every lane)
+        const int64_t i = i0 + threadIdx.x;
+        const bool live = i < ns;
+        const int32_t j = live ? a.s.idx[base + i] : -1;
+        const float v = live ? a.s.d2[base + i] : __uint_as_float(0x7fc00000u);
+        const bool cand = live && o2o_candidate(j, v, w.d.nt, a.s.max_d2);
+        const unsigned long long key = o2o_key(v, i);
+        const bool win = cand && w.table[j] == key;
+        float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+        int x0 = 0, x1 = 0, y0 = 0, y1 = 0, z0 = 0, z1 = -1;   // (an empty box)
+        bool hit = false, heavy = false;
+        if (win) {
+            qx = tgt[3 * (int64_t)j]; qy = tgt[3 * (int64_t)j + 1]; qz = tgt[3 * (int64_t)j + 2];
+            const float r = sqrtf(fabsf(v)) * 1.0001f + 1e-22f;
+            const float rx = r + 2.4e-7f * fabsf(qx), ry = r + 2.4e-7f * fabsf(qy), rz = r + 2.4e-7f * fabsf(qz);
+            x0 = recip_coord(qx - rx, g.ox, g.inv_h, g.gx); x1 = recip_coord(qx + rx, g.ox, g.inv_h, g.gx);
+            y0 = recip_coord(qy - ry, g.oy, g.inv_h, g.gy); y1 = recip_coord(qy + ry, g.oy, g.inv_h, g.gy);
+            z0 = recip_coord(qz - rz, g.oz, g.inv_h, g.gz); z1 = recip_coord(qz + rz, g.oz, g.inv_h, g.gz);
+            const int64_t span = (int64_t)(x1 - x0 + 1) * (y1 - y0 + 1) * (z1 - z0 + 1);
+            if (x1 < x0 || y1 < y0 || z1 < z0 || span > (int64_t)total) {
+                heavy = true;   // the escape: the pair's whole slice, marked by x0 < 0
+                x0 = -1;
+            } else {
+                if (span > RECIP_CENTRE_FIRST) {
+                    const int64_t c = recip_cell(g, qx, qy, qz);
+                    const unsigned lo = c > 0 ? w.cells[c - 1] : 0u, hi = min(w.cells[c], total);
+                    if (hi <= lo + RECIP_LANE_MAX) hit = recip_hit<FMA>(w.sorted, lo, hi, qx, qy, qz, key);
+                }
+                for (int cz = z0; cz <= z1 && !hit; ++cz)
+                    for (int cy = y0; cy <= y1 && !hit; ++cy) {
+                        const int64_t c0 = ((int64_t)cz * g.gy + cy) * g.gx + x0;
+                        const unsigned lo = c0 > 0 ? w.cells[c0 - 1] : 0u, hi = min(w.cells[c0 + (x1 - x0)], total);
+                        if (hi > lo && hi - lo > RECIP_LANE_MAX) heavy = true;
+                        else hit = recip_hit<FMA>(w.sorted, lo, hi, qx, qy, qz, key);
+                    }
+            }
+        }
+        // the rows left over, one winner at a time by the whole wave
+        for (unsigned long long todo = __ballot(heavy && !hit); todo != 0ull; todo &= todo - 1ull) {
+            const int l = __ffsll((long long)todo) - 1;
+            const float ex = __shfl(qx, l, 64), ey = __shfl(qy, l, 64), ez = __shfl(qz, l, 64);
+            const unsigned long long ek = ((unsigned long long)__shfl((unsigned)(key >> 32), l, 64) << 32) | (unsigned long long)__shfl((unsigned)key, l, 64);
+            const int bx0 = __shfl(x0, l, 64), bx1 = __shfl(x1, l, 64), by0 = __shfl(y0, l, 64), by1 = __shfl(y1, l, 64);
+            const int bz0 = __shfl(z0, l, 64), bz1 = __shfl(z1, l, 64);
+            bool found = false;
+            if (bx0 < 0) {
+                found = recip_hit_wave<FMA>(w.sorted, 0u, total, ex, ey, ez, ek, lane);
+            } else {
+                for (int cz = bz0; cz <= bz1 && !found; ++cz)
+                    for (int cy = by0; cy <= by1 && !found; ++cy) {
+                        const int64_t c0 = ((int64_t)cz * g.gy + cy) * g.gx + bx0;
+                        const unsigned lo = c0 > 0 ? w.cells[c0 - 1] : 0u, hi = min(w.cells[c0 + (bx1 - bx0)], total);
+                        if (hi > lo && hi - lo > RECIP_LANE_MAX) found = recip_hit_wave<FMA>(w.sorted, lo, hi, ex, ey, ez, ek, lane);
+                    }
+            }
+            if (lane == l) hit = found;
+        }
+        const bool mutual = win && !hit;
+        if (live) {
+            if (a.idx_out) a.idx_out[base + i] = cand && !mutual ? -1 : j;
+            if (a.d2_out) a.d2_out[base + i] = cand && !mutual ? __uint_as_float(0x7fc00000u) : v;
+        }
+        cnt += (unsigned)__popcll(__ballot(mutual));
+    }
+    o2o_count(cnt, wave_cnt, w.counters + 2);
+    if (a.info_mu && (int)blockIdx.x == w.d.row_base && threadIdx.x == 0) {   // the pair's first workgroup: m and u are complete since earlier launches ended
+        a.info_mu[2 * (int64_t)p] = (double)(w.counters[0] + 1u);
+        a.info_mu[2 * (int64_t)p + 1] = (double)(w.counters[1] + 1u);
+    }
+}
+
+// every pair's target box in one launch: workgroup b takes partial b % split of pair b / split -- the pair's targets
+// (b % split) * 256 + t + k * 256 * split -- and writes {min xyz, max xyz}; a partial without a target stays {+inf, -inf}
+__global__ __launch_bounds__(RECIP_THREADS) void recipb_bbox_kernel(const float* __restrict__ tgt_all, const PairbDesc* __restrict__ desc, int split,
+                                                                    float* __restrict__ box) {
+    __shared__ float sh[RECIP_THREADS / 64][6];
+    const PairbDesc d = desc[blockIdx.x / split];
+    const float* __restrict__ tgt = tgt_all + 3 * d.tgt_off;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int64_t j = (int64_t)(blockIdx.x % split) * RECIP_THREADS + threadIdx.x; j < d.nt; j += (int64_t)split * RECIP_THREADS)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float v = tgt[3 * j + k];
+            mn[k] = fminf(mn[k], v); mx[k] = fmaxf(mx[k], v);
+        }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        for (int off = 32; off > 0; off >>= 1) {
+            mn[k] = fminf(mn[k], __shfl_down(mn[k], off, 64));
+            mx[k] = fmaxf(mx[k], __shfl_down(mx[k], off, 64));
+        }
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < 3; ++k) { sh[threadIdx.x >> 6][k] = mn[k]; sh[threadIdx.x >> 6][3 + k] = mx[k]; }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        float v = sh[0][threadIdx.x];
+        for (int q = 1; q < RECIP_THREADS / 64; ++q) v = threadIdx.x < 3 ? fminf(v, sh[q][threadIdx.x]) : fmaxf(v, sh[q][threadIdx.x]);
+        box[6 * (int64_t)blockIdx.x + threadIdx.x] = v;
+    }
+}
+
+void launch_recipb_bbox(hipStream_t st, const float* d_tgt, const PairbDesc* d_desc, int npairs, int split, float* d_box) {
+    hipLaunchKernelGGL(recipb_bbox_kernel, dim3((unsigned)npairs * (unsigned)split), dim3(RECIP_THREADS), 0, st, d_tgt, d_desc, split, d_box);
+}
+
+size_t recipb_work_bytes(int64_t total_tgt, int npairs, int64_t total_cells) {
+    return (size_t)total_tgt * sizeof(unsigned long long) + ((size_t)npairs * 4 + (size_t)total_cells) * sizeof(unsigned);
+}
+
+template <int SRC>
+static void launch_recipb_walks(hipStream_t st, const RecipbArgs& a, int total_rows) {
+    hipLaunchKernelGGL((recipb_walk_kernel<SRC, false>), dim3(total_rows), dim3(RECIP_THREADS), 0, st, a);
+    hipLaunchKernelGGL(recipb_scan_kernel, dim3(a.npairs), dim3(RECIP_SCAN_THREADS), 0, st, a);
+    hipLaunchKernelGGL((recipb_walk_kernel<SRC, true>), dim3(total_rows), dim3(RECIP_THREADS), 0, st, a);
+}
+
+int launch_recipb(hipStream_t st, int total_rows, int64_t total_cells, const RecipbArgs& a, bool nn_fma) {
+    const hipError_t e = hipMemsetAsync(a.work, 0xff, recipb_work_bytes(a.total_tgt, a.npairs, total_cells), st);
+    if (e != hipSuccess) return (int)e;
+    if (a.s.src3) launch_recipb_walks<SRC_F3>(st, a, total_rows);
+    else if (a.s.perm) launch_recipb_walks<SRC_F4_PERM>(st, a, total_rows);
+    else launch_recipb_walks<SRC_F4>(st, a, total_rows);
+    if (nn_fma) hipLaunchKernelGGL(recipb_resolve_kernel<true>, dim3(total_rows), dim3(RECIP_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(recipb_resolve_kernel<false>, dim3(total_rows), dim3(RECIP_THREADS), 0, st, a);
     return 0;
 }
 
