@@ -1280,7 +1280,8 @@ int kss_recip_filter_dev(kss_ctx* c, const float* d_src, int64_t n, const float*
                          double max_d2, int nn_fma, int32_t* d_idx_out, float* d_d2_out, double info[3]) {
     if (!c) return KSS_ERR_ARG;
     KCHK(recip_filter_check(c, d_src, d_tgt, d_idx, d_d2, n, nt, info));
-    return recip_filter_dev(c, d_src, n, d_tgt, nt, d_idx, d_d2, max_d2, nn_fma != 0, d_idx_out, d_d2_out, info);
+    const int64_t off[2] = {0, n}, tgt_off[2] = {0, nt};   // (one segment: info_all is the three doubles)
+    return recip_filter_dev(c, d_src, off, d_tgt, tgt_off, 1, d_idx, d_d2, max_d2, nn_fma != 0, d_idx_out, d_d2_out, info, true);
 }
 
 int kss_recip_filter(kss_ctx* c, const float* src, int64_t n, const float* tgt, int64_t nt, const int32_t* idx, const float* d2, double max_d2,
@@ -1293,9 +1294,10 @@ int kss_recip_filter(kss_ctx* c, const float* src, int64_t n, const float* tgt, 
     KCHK(upload(c, c->stage_idx, idx, (size_t)n * sizeof(int32_t)));
     KCHK(upload(c, c->stage_d2, d2, (size_t)n * sizeof(float)));
     // filtered in place on the staged copies, then back to whichever outputs the caller gave
-    KCHK(recip_filter_dev(c, (const float*)c->stage_src.p, n, (const float*)c->stage_tgt.p, nt, (const int32_t*)c->stage_idx.p,
+    const int64_t off[2] = {0, n}, tgt_off[2] = {0, nt};
+    KCHK(recip_filter_dev(c, (const float*)c->stage_src.p, off, (const float*)c->stage_tgt.p, tgt_off, 1, (const int32_t*)c->stage_idx.p,
                           (const float*)c->stage_d2.p, max_d2, nn_fma != 0, idx_out ? (int32_t*)c->stage_idx.p : nullptr,
-                          d2_out ? (float*)c->stage_d2.p : nullptr, info));
+                          d2_out ? (float*)c->stage_d2.p : nullptr, info, true));
     if (idx_out) HIPCHK(c, hipMemcpyAsync(idx_out, c->stage_idx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (d2_out) HIPCHK(c, hipMemcpyAsync(d2_out, c->stage_d2.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1346,8 +1348,8 @@ int kss_recip_filter_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t
     std::vector<int64_t> o, to;
     recip_filter_rebase(off, tgt_off, nseg, o, to);
     const int64_t o0 = off[0], t0 = tgt_off[0];
-    return recip_filter_batch_dev(c, d_src_all + 3 * o0, o.data(), d_tgt_all + 3 * t0, to.data(), nseg, d_idx_all + o0, d_d2_all + o0, max_d2,
-                                  nn_fma != 0, d_idx_out_all ? d_idx_out_all + o0 : nullptr, d_d2_out_all ? d_d2_out_all + o0 : nullptr, info_all);
+    return recip_filter_dev(c, d_src_all + 3 * o0, o.data(), d_tgt_all + 3 * t0, to.data(), nseg, d_idx_all + o0, d_d2_all + o0, max_d2,
+                            nn_fma != 0, d_idx_out_all ? d_idx_out_all + o0 : nullptr, d_d2_out_all ? d_d2_out_all + o0 : nullptr, info_all);
 }
 
 int kss_recip_filter_batch(kss_ctx* c, const float* src_all, const int64_t* off, const float* tgt_all, const int64_t* tgt_off, int nseg,
@@ -1364,9 +1366,9 @@ int kss_recip_filter_batch(kss_ctx* c, const float* src_all, const int64_t* off,
     KCHK(upload(c, c->stage_idx, idx_all + o0, (size_t)n * sizeof(int32_t)));
     KCHK(upload(c, c->stage_d2, d2_all + o0, (size_t)n * sizeof(float)));
     // filtered in place on the staged copies, then back to whichever outputs the caller gave
-    KCHK(recip_filter_batch_dev(c, (const float*)c->stage_src.p, o.data(), (const float*)c->stage_tgt.p, to.data(), nseg,
-                                (const int32_t*)c->stage_idx.p, (const float*)c->stage_d2.p, max_d2, nn_fma != 0,
-                                idx_out_all ? (int32_t*)c->stage_idx.p : nullptr, d2_out_all ? (float*)c->stage_d2.p : nullptr, info_all));
+    KCHK(recip_filter_dev(c, (const float*)c->stage_src.p, o.data(), (const float*)c->stage_tgt.p, to.data(), nseg,
+                          (const int32_t*)c->stage_idx.p, (const float*)c->stage_d2.p, max_d2, nn_fma != 0,
+                          idx_out_all ? (int32_t*)c->stage_idx.p : nullptr, d2_out_all ? (float*)c->stage_d2.p : nullptr, info_all));
     if (idx_out_all) HIPCHK(c, hipMemcpyAsync(idx_out_all + o0, c->stage_idx.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (d2_out_all) HIPCHK(c, hipMemcpyAsync(d2_out_all + o0, c->stage_d2.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

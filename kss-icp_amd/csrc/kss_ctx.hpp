@@ -68,18 +68,14 @@ struct kss_ctx {
     // one-to-one rejection (kss_o2o.hip): the claim table (one uint64 per target of the call, two uint32 counters per
     // pair behind it; set to all ones before every pass, so nothing has to hold between passes) and the filtered idx / d2
     DevBuf o2o_table, o2o_idx, o2o_d2;
-    // reciprocal rejection (kss_recip.hip): its workspace is o2o_table's buffer (the claim table, four counters, the
-    // cell counts; set to all ones before every pass) and the filtered idx / d2 are o2o_idx / o2o_d2; the sources in cell order,
-    // rewritten by every pass, the bounding-box partials of the call's target and the cell grid derived from them
-    DevBuf recip_sorted, recip_box;
-    RecipGrid recip_grid = {0.0f, 0.0f, 0.0f, 0.0f, 1, 1, 1};
-    // ... for many pairs per call: one workspace in o2o_table's buffer (the claim table over the batch's targets, four
-    // counters per pair, every pair's cell counts), recip_sorted over the batch's sources, recip_box the per-pair box partials, and the
-    // per-pair {grid, first cell} table: the host copy (kept here so that its upload needs no synchronisation of its own), the device
-    // copy and the batch's cell total
-    DevBuf recip_grids;
+    // reciprocal rejection, one pair or many (kss_recip.hip): its workspace is o2o_table's buffer (the claim table
+    // over the call's targets, four counters per pair, every pair's cell counts; set to all ones before every pass) and the filtered
+    // idx / d2 are o2o_idx / o2o_d2; recip_sorted: the call's sources in cell order, rewritten by every pass; recip_box: the per-pair
+    // box partials of the call's targets; the per-pair {grid, first cell} table derived from them: the host copy (kept here so that
+    // its upload needs no synchronisation of its own), the device copy and the call's cell total.  A single pair is entry 0.
+    DevBuf recip_sorted, recip_box, recip_grids;
     std::vector<RecipPairDev> h_recip_grids;
-    int64_t recipb_cells = 0;
+    int64_t recip_total_cells = 0;
     void* h_gicp = nullptr; size_t h_gicp_cap = 0;
     void* h_gicp_dev = nullptr;   // (the pinned copy as the device sees it: KSS_GICP_TABLE_MAPPED, an A/B switch)
     const PairState* last_state_dev = nullptr;   // the per-pair state table the last batched NN pass read (null: none, a single pair)
@@ -315,15 +311,13 @@ int trim_threshold_batch_dev(kss_ctx* c, const float* d_d2, const int64_t* off, 
 // against nts[i] targets, in the same three launches: the filtered arrays (either may be null or its input) and {m, u} per segment
 int o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, const int64_t* off, const int64_t* nts, int nseg, double max_d2,
                    int32_t* d_idx_out, float* d_d2_out, double* info_all);
-// the reciprocal filter alone (kss_recip_filter_dev): n packed float triples d_src with the map d_idx / d_d2 against the nt triples
-// d_tgt, reverse distances by dist2<nn_fma>; the filtered arrays (either may be null or its input) and info = {m, u, r}
-int recip_filter_dev(kss_ctx* c, const float* d_src, int64_t n, const float* d_tgt, int64_t nt, const int32_t* d_idx, const float* d_d2,
-                     double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out, double* info);
-// the same for nseg segments in the batch's five steps (kss_recip_filter_batch_dev): sources [off[i], off[i + 1]) of d_src / d_idx /
-// d_d2 against targets [tgt_off[i], tgt_off[i + 1]) of d_tgt, both offset arrays from 0; info_all = {m, u, r} per segment
-int recip_filter_batch_dev(kss_ctx* c, const float* d_src, const int64_t* off, const float* d_tgt, const int64_t* tgt_off, int nseg,
-                           const int32_t* d_idx, const float* d_d2, double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out,
-                           double* info_all);
+// the reciprocal filter alone (kss_recip_filter[_batch]_dev): for nseg >= 1 segments, sources [off[i], off[i + 1]) of the packed float
+// triples d_src with the map d_idx / d_d2 against targets [tgt_off[i], tgt_off[i + 1]) of d_tgt, both offset arrays from 0, reverse
+// distances by dist2<nn_fma>; the filtered arrays (either may be null or its input) and info_all = {m, u, r} per segment.
+// lone: the single-pair entry's one segment (no row -> pair table, the box partials cut by the single pair's rule)
+int recip_filter_dev(kss_ctx* c, const float* d_src, const int64_t* off, const float* d_tgt, const int64_t* tgt_off, int nseg,
+                     const int32_t* d_idx, const float* d_d2, double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out,
+                     double* info_all, bool lone = false);
 // host-mapped {value, sequence number} result slots: allocate them; wait for the first nslots of launch c->seq
 int ensure_pub_slots(kss_ctx* c);
 int wait_slots(kss_ctx* c, int nslots, double* out);

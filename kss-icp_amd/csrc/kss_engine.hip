@@ -1937,7 +1937,7 @@ int icp_run_dev(kss_ctx* c, const void* d_src, const int64_t* src_off, const voi
 // Reciprocal (kss_icp_recip; M.mutual with M.trimmed, either metric): five launches ahead of the
 // selection (kss_recip.hip: reset, claim + count, scan, scatter, resolve + check) filter the same arrays the same way, against the
 // positions the NN pass wrote; the info record grows to KSS_RECIP_NINFO = {r, k, tau, kept, m, u}, m and u published by the resolve launch.
-// Many pairs per call (kss_icp_recip_pairs): the same five steps once for the whole batch, every pair on its own grid.
+// One pair or many per call (kss_icp_recip_pairs), the same kernels: every pair on its own grid.
 // the rotation block of a row-major 4 x 4 (the float bits of the accumulated Matrix4f)
 static GicpRot rot_of(const float* F) { return GicpRot{{F[0], F[1], F[2], F[4], F[5], F[6], F[8], F[9], F[10]}}; }
 
@@ -1953,6 +1953,25 @@ static int pair_pass_ensure(kss_ctx* c, const PairMode& M, int64_t n, bool have_
     }
     if (M.robust && M.rs.autoscale && (M.plane || !have_d2)) KCHK(ensure(c, c->rob_keys, (size_t)n * sizeof(float)));
     return ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO + 2) * sizeof(double));   // (+ m, or m and u)
+}
+
+// a single pair as the filters' kernels see it: a batch of one descriptor
+static PairbDesc lone_desc(int64_t ns, int64_t nt, double overlap) {
+    PairbDesc d;
+    d.src_base = 0; d.ns = ns; d.tgt_off = 0; d.nt = nt; d.overlap = overlap; d.row_base = 0; d.nrows = stream_blocks(ns);
+    return d;
+}
+
+// reciprocal's reset and four launches for np pairs against s's positions, the reverse distances by dist2<nn_fma>: the NN pass's own
+// p2l_idx / p2l_d2 filtered into o2o_idx / o2o_d2, {m, u} per pair into d_info_mu.  One pair: np = 1, total_rows = stream_blocks(n),
+// total_tgt = nt, no tables: the pair's descriptor `lone` and its grid go inside the arguments.
+static int recip_pass_launch(kss_ctx* c, const PairSrc& s, const float* tgt, const PairbDesc* desc, const int32_t* row_pair, const PairState* state,
+                             int np, int total_rows, int64_t total_tgt, double* d_info_mu, bool nn_fma, const PairbDesc& lone = PairbDesc()) {
+    RecipArgs ra = {s, tgt, desc, row_pair, state, (const RecipPairDev*)c->recip_grids.p, c->o2o_table.p, total_tgt, np,
+                    (float4*)c->recip_sorted.p, (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info_mu, lone, c->h_recip_grids[0]};
+    ra.s.idx = (const int32_t*)c->p2l_idx.p; ra.s.d2 = (const float*)c->p2l_d2.p;
+    if (launch_recip(c->stream, total_rows, c->recip_total_cells, ra, nn_fma) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
+    return KSS_OK;
 }
 
 // One pair: [one-to-one's three launches | reciprocal's five] [selection] [keys launch + the 0.5 selection] rows launch, final launch.  Rn: the
@@ -1974,12 +1993,8 @@ static int pair_pass_launch(kss_ctx* c, const PairArgs& a, const PairMode& M, co
                             (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + KSS_TRIM_NINFO};
         if (launch_o2o(st, nb, a.nt, 1, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
     }
-    if (M.mutual) {   // reset, claim + count, scan, scatter, resolve + check
-        RecipArgs ra = {a.s, a.tgt, a.n, a.nt, c->recip_grid, c->o2o_table.p, (float4*)c->recip_sorted.p,
-                        (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + KSS_TRIM_NINFO};
-        ra.s.idx = (const int32_t*)c->p2l_idx.p; ra.s.d2 = (const float*)c->p2l_d2.p;
-        if (launch_recip(st, ra, nn_fma) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
-    }
+    if (M.mutual)   // reset, claim + count, scan, scatter, resolve + check
+        KCHK(recip_pass_launch(c, a.s, a.tgt, nullptr, nullptr, nullptr, 1, nb, a.nt, d_info + KSS_TRIM_NINFO, nn_fma, lone_desc(a.n, a.nt, M.overlap)));
     if (M.trimmed) launch_trim_select(st, a.s.d2, a.n, max_d2, M.overlap, (unsigned*)c->trim_rows.p, d_state, d_info);
     const double* d_cut = M.trimmed ? &d_state[TRIM_NSTATE - 1].cut : nullptr;
     if (M.robust) {
@@ -2034,12 +2049,8 @@ static int pairb_pass_launch(kss_ctx* c, const PairbArgs& a, const PairMode& M, 
                             (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + (size_t)np * KSS_TRIM_NINFO};
         if (launch_o2o(st, total_rows, total_tgt, np, oa) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(claim table)");
     }
-    if (M.mutual) {   // reset, claim + count, scan, scatter, resolve + check for the whole batch
-        RecipbArgs ra = {a.s, a.tgt, a.desc, a.row_pair, a.state, (const RecipPairDev*)c->recip_grids.p, c->o2o_table.p, total_tgt, np,
-                         (float4*)c->recip_sorted.p, (int32_t*)c->o2o_idx.p, (float*)c->o2o_d2.p, d_info + (size_t)np * KSS_TRIM_NINFO};
-        ra.s.idx = (const int32_t*)c->p2l_idx.p; ra.s.d2 = (const float*)c->p2l_d2.p;
-        if (launch_recipb(st, total_rows, c->recipb_cells, ra, nn_fma) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
-    }
+    if (M.mutual)   // reset, claim + count, scan, scatter, resolve + check for the whole batch
+        KCHK(recip_pass_launch(c, a.s, a.tgt, a.desc, a.row_pair, a.state, np, total_rows, total_tgt, d_info + (size_t)np * KSS_TRIM_NINFO, nn_fma));
     if (M.trimmed) launch_pairb_select(st, a.s.d2, a.desc, np, a.state, max_d2, a.ts, d_info);
     if (M.robust) {
         if (rob_select) {   // (written keys carry the whole candidate test, a NaN is none: no bound)
@@ -2290,66 +2301,36 @@ static int pair_run_loop(kss_ctx* c, const IcpPlan& pl, std::chrono::steady_cloc
     return rc;
 }
 
-// reciprocal, once per call: the bounding box of the nt packed float triples d_tgt (a launch, a copy of at most
-// RECIP_BOX_BLOCKS partials and ONE synchronisation), the cell grid for n sources over it into c->recip_grid, the workspace and
-// the cell-ordered source array
-static int recip_setup(kss_ctx* c, const float* d_tgt, int64_t nt, int64_t n) {
-    KCHK(ensure(c, c->recip_box, (size_t)RECIP_BOX_BLOCKS * 6 * sizeof(float)));
-    const int nb = launch_recip_bbox(c->stream, d_tgt, nt, (float*)c->recip_box.p);
-    HIPCHK(c, hipGetLastError());
-    std::vector<float> hb((size_t)nb * 6);
-    HIPCHK(c, hipMemcpyAsync(hb.data(), c->recip_box.p, hb.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = 0; b < nb; ++b)
-        for (int k = 0; k < 3; ++k) { mn[k] = std::fmin(mn[k], hb[(size_t)b * 6 + k]); mx[k] = std::fmax(mx[k], hb[(size_t)b * 6 + 3 + k]); }
-    c->recip_grid = recip_grid_of(mn, mx, n);
-    KCHK(ensure(c, c->o2o_table, recip_work_bytes(nt, recip_cells(c->recip_grid))));
-    return ensure(c, c->recip_sorted, (size_t)n * sizeof(float4));
-}
-
-// reciprocal for many pairs, once per call, behind stage_pairb: every pair's target box from ONE launch over the
-// staged descriptors (`split` partials per pair, one copy back and ONE synchronisation whatever the pair count), every pair's grid
-// by the single pair's rule -- recip_grid_of(the box of ITS target, ITS source count) -- with its first cell, staged next to
-// pb_desc; the workspace and the batch's cell-ordered source array of total_src float4.
-// A pair's grid here does not have to equal the single-pair call's in any bit (the partials are cut differently; fminf / fmaxf may
-// hand back either zero of a tie).  It cannot matter: "mutual" is an existence statement over ALL sources of the pair, the box walk
-// is proven to hold every source that can hit on ANY grid of this form, and the escape scans the pair's whole slice -- which sources
-// are examined, and in what order, does not change a bit of the result.
-static int recipb_setup(kss_ctx* c, const float* d_tgt, const std::vector<PairbDesc>& desc, int64_t total_src, const char* who) {
+// reciprocal, once per call, behind stage_pairb: every pair's target box from ONE launch over the staged
+// descriptors (`split` partials per pair, one copy back and ONE synchronisation whatever the pair count), every pair's grid --
+// recip_grid_of(the box of ITS target, ITS source count) -- with its first cell, staged next to pb_desc; the workspace and the
+// call's cell-ordered source array of total_src float4.  lone: the single-pair entries' desc[0], whose partials are cut finer and
+// which stages nothing: descriptor and grid travel in the launches' arguments.
+// How the partials are cut may move a bit of a grid (fminf / fmaxf may hand back either zero of a tie).  It cannot matter: "mutual"
+// is an existence statement over ALL sources of the pair, the box walk is proven to hold every source that can hit on ANY grid of
+// this form, and the escape scans the pair's whole slice.
+static int recip_setup(kss_ctx* c, const float* d_tgt, const std::vector<PairbDesc>& desc, int64_t total_src, const char* who, bool lone = false) {
     const int np = (int)desc.size();
     int64_t total_tgt = 0, max_nt = 0;
     for (const PairbDesc& d : desc) { total_tgt += d.nt; max_nt = std::max(max_nt, d.nt); }
-    const int split = (int)std::max<int64_t>(1, std::min<int64_t>(64, (max_nt + 4 * 1024 - 1) / (4 * 1024)));
-    if (total_tgt > 0x7fff0000ll || (int64_t)np * split > 0x7fff0000ll)
-        return set_err(c, KSS_ERR_ARG, (std::string(who) + ": batch too large for 32-bit indexing").c_str());
+    const int split = lone ? (int)std::max<int64_t>(1, std::min<int64_t>(RECIP_BOX_BLOCKS, (max_nt + 1023) / 1024))
+                           : (int)std::max<int64_t>(1, std::min<int64_t>(64, (max_nt + 4 * 1024 - 1) / (4 * 1024)));
+    const std::string large = std::string(who) + ": batch too large for 32-bit indexing";
+    if (total_tgt > PAIRB_INDEX_MAX || (int64_t)np * split > PAIRB_INDEX_MAX) return set_err(c, KSS_ERR_ARG, large.c_str());
     const size_t nbox = (size_t)np * split;
     KCHK(ensure(c, c->recip_box, nbox * 6 * sizeof(float)));
-    launch_recipb_bbox(c->stream, d_tgt, (const PairbDesc*)c->pb_desc.p, np, split, (float*)c->recip_box.p);
+    launch_recip_bbox(c->stream, d_tgt, lone ? nullptr : (const PairbDesc*)c->pb_desc.p, desc[0], np, split, (float*)c->recip_box.p);
     HIPCHK(c, hipGetLastError());
     std::vector<float> hb(nbox * 6);
     HIPCHK(c, hipMemcpyAsync(hb.data(), c->recip_box.p, hb.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->h_recip_grids.resize((size_t)np);
-    int64_t cells = 0;
-    for (int p = 0; p < np; ++p) {
-        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int b = 0; b < split; ++b)
-            for (int k = 0; k < 3; ++k) {
-                mn[k] = std::fmin(mn[k], hb[((size_t)p * split + b) * 6 + k]);
-                mx[k] = std::fmax(mx[k], hb[((size_t)p * split + b) * 6 + 3 + k]);
-            }
-        RecipPairDev& gp = c->h_recip_grids[p];
-        gp.g = recip_grid_of(mn, mx, desc[p].ns);
-        gp.cell_base = (int32_t)cells;
-        cells += recip_cells(gp.g);
-        if (cells > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": batch too large for 32-bit indexing").c_str());
+    c->recip_total_cells = recip_grids_of(hb.data(), split, desc, c->h_recip_grids);
+    if (c->recip_total_cells < 0) return set_err(c, KSS_ERR_ARG, large.c_str());
+    if (!lone) {   // (the source of this copy is the context's own vector: it outlives the copy, no synchronisation here)
+        KCHK(ensure(c, c->recip_grids, (size_t)np * sizeof(RecipPairDev)));
+        HIPCHK(c, hipMemcpyAsync(c->recip_grids.p, c->h_recip_grids.data(), (size_t)np * sizeof(RecipPairDev), hipMemcpyHostToDevice, c->stream));
     }
-    c->recipb_cells = cells;
-    KCHK(ensure(c, c->recip_grids, (size_t)np * sizeof(RecipPairDev)));
-    // (the source of this copy is the context's own vector: it outlives the copy, no synchronisation here)
-    HIPCHK(c, hipMemcpyAsync(c->recip_grids.p, c->h_recip_grids.data(), (size_t)np * sizeof(RecipPairDev), hipMemcpyHostToDevice, c->stream));
-    KCHK(ensure(c, c->o2o_table, recipb_work_bytes(total_tgt, np, cells)));
+    KCHK(ensure(c, c->o2o_table, recip_work_bytes(total_tgt, np, c->recip_total_cells)));
     return ensure(c, c->recip_sorted, (size_t)total_src * sizeof(float4));
 }
 
@@ -2368,18 +2349,16 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
     KCHK(ensure(c, c->p2l_d2, (size_t)ns * sizeof(float)));
     KCHK(pair_pass_ensure(c, M, ns, true));
     if (M.gicp || M.symm) KCHK(stage_pass_table(c, M, 1, &M.gicp_epsilon, &M.symm_align));
-    if (M.unique) {   // the claim table, the filtered idx / d2 and the pair as the filter's kernels see it
-        KCHK(ensure(c, c->o2o_table, o2o_table_bytes(nt, 1)));
+    if (M.unique || M.mutual) {   // the filtered idx / d2 and the pair as the filters' kernels see it: a batch of one descriptor
         KCHK(ensure(c, c->o2o_idx, (size_t)ns * sizeof(int32_t)));
         KCHK(ensure(c, c->o2o_d2, (size_t)ns * sizeof(float)));
-        PairbDesc d;
-        d.src_base = 0; d.ns = ns; d.tgt_off = 0; d.nt = nt; d.overlap = M.overlap; d.row_base = 0; d.nrows = stream_blocks(ns);
-        KCHK(stage_pairb(c, std::vector<PairbDesc>(1, d), false));
-    }
-    if (M.mutual) {   // the filtered idx / d2, the cell grid over the target's box, the workspace and the cell-ordered sources
-        KCHK(ensure(c, c->o2o_idx, (size_t)ns * sizeof(int32_t)));
-        KCHK(ensure(c, c->o2o_d2, (size_t)ns * sizeof(float)));
-        KCHK(recip_setup(c, d_tgt, nt, ns));
+        const std::vector<PairbDesc> desc(1, lone_desc(ns, nt, M.overlap));
+        if (M.unique) {   // staged, and the claim table
+            KCHK(stage_pairb(c, desc, false));
+            KCHK(ensure(c, c->o2o_table, o2o_table_bytes(nt, 1)));
+        } else {          // in the launches' arguments: the cell grid over the target's box, the workspace and the cell-ordered sources
+            KCHK(recip_setup(c, d_tgt, desc, ns, "pair_run", true));
+        }
     }
     const int64_t so[2] = {0, ns}, to[2] = {0, nt};
     KCHK(pack_clouds(c, pl, d_src, so, d_tgt, to, KSS_F32));
@@ -2468,7 +2447,7 @@ int pairs_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const 
         if (tgt_off[0] != 0) return set_err(c, KSS_ERR_ARG, "pairs_run: the target offsets must start at 0");
         KCHK(ensure(c, c->o2o_idx, (size_t)pl.total_src * sizeof(int32_t)));
         KCHK(ensure(c, c->o2o_d2, (size_t)pl.total_src * sizeof(float)));
-        KCHK(recipb_setup(c, d_tgt, desc, pl.total_src, "pairs_run"));
+        KCHK(recip_setup(c, d_tgt, desc, pl.total_src, "pairs_run"));
     }
     KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)npairs * (P2L_NSUMS + KSS_TRIM_NINFO + 2) * sizeof(double)));   // (+ m, or m and u)
     KCHK(pack_clouds(c, pl, d_src, src_off, d_tgt, tgt_off, KSS_F32));
@@ -2501,16 +2480,12 @@ int trim_threshold_batch_dev(kss_ctx* c, const float* d_d2, const int64_t* off, 
 int o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, const int64_t* off, const int64_t* nts, int nseg, double max_d2,
                    int32_t* d_idx_out, float* d_d2_out, double* info_all) {
     HIPCHK(c, hipSetDevice(c->device));
-    std::vector<PairbDesc> desc((size_t)nseg);
-    int64_t total_rows = 0, total_tgt = 0;
-    for (int i = 0; i < nseg; ++i) {
-        PairbDesc& d = desc[i];
-        d.src_base = off[i]; d.ns = off[i + 1] - off[i];
-        d.tgt_off = total_tgt; d.nt = nts[i]; d.overlap = 1.0;
-        d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(d.ns);
-        total_rows += d.nrows; total_tgt += d.nt;
-        if (total_rows > 0x7fff0000ll || total_tgt > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "o2o_filter: batch too large for 32-bit indexing");
-    }
+    std::vector<int64_t> tgt_off((size_t)nseg + 1, 0);   // (one table over all segments' targets, counted from 0)
+    for (int i = 0; i < nseg; ++i) tgt_off[i + 1] = tgt_off[i] + nts[i];
+    std::vector<PairbDesc> desc;
+    int64_t total_rows = 0;
+    if (!pairb_desc_of(off, tgt_off.data(), nseg, desc, total_rows)) return set_err(c, KSS_ERR_ARG, "o2o_filter: batch too large for 32-bit indexing");
+    const int64_t total_tgt = tgt_off[nseg];
     KCHK(stage_pairb(c, desc, true));
     KCHK(ensure(c, c->o2o_table, o2o_table_bytes(total_tgt, nseg)));
     unsigned* d_counters = (unsigned*)((unsigned long long*)c->o2o_table.p + total_tgt);
@@ -2525,50 +2500,29 @@ int o2o_filter_dev(kss_ctx* c, const int32_t* d_idx, const float* d_d2, const in
     return KSS_OK;
 }
 
-// the reciprocal filter alone (kss_recip_filter_dev): the loop's setup and five launches on packed float triples, then the three
-// counters read back (each holds its count minus one)
-int recip_filter_dev(kss_ctx* c, const float* d_src, int64_t n, const float* d_tgt, int64_t nt, const int32_t* d_idx, const float* d_d2,
-                     double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out, double* info) {
+// the reciprocal filter alone (kss_recip_filter[_batch]_dev) over nseg >= 1 segments: the loops' setup and their reset and four
+// launches on packed float triples, then every segment's counters read back (each holds its count minus one).  lone: the single-pair
+// entry's one segment, launched as the single-pair loop launches it
+int recip_filter_dev(kss_ctx* c, const float* d_src, const int64_t* off, const float* d_tgt, const int64_t* tgt_off, int nseg,
+                     const int32_t* d_idx, const float* d_d2, double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out,
+                     double* info_all, bool lone) {
     HIPCHK(c, hipSetDevice(c->device));
-    KCHK(recip_setup(c, d_tgt, nt, n));
-    const RecipArgs ra = {{d_src, nullptr, nullptr, d_idx, d_d2, nullptr, max_d2}, d_tgt, n, nt, c->recip_grid, c->o2o_table.p,
-                          (float4*)c->recip_sorted.p, d_idx_out, d_d2_out, nullptr};
-    if (launch_recip(c->stream, ra, nn_fma) != 0) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
-    HIPCHK(c, hipGetLastError());
-    unsigned cnt[3];
-    HIPCHK(c, hipMemcpyAsync(cnt, recip_counters(c->o2o_table.p, nt), sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int q = 0; q < 3; ++q) info[q] = (double)(cnt[q] + 1u);
-    return KSS_OK;
-}
-
-// the reciprocal filter alone for nseg segments (kss_recip_filter_batch_dev): the batched loop's setup and its reset and four
-// launches on packed float triples, then every segment's counters read back (each holds its count minus one)
-int recip_filter_batch_dev(kss_ctx* c, const float* d_src, const int64_t* off, const float* d_tgt, const int64_t* tgt_off, int nseg,
-                           const int32_t* d_idx, const float* d_d2, double max_d2, bool nn_fma, int32_t* d_idx_out, float* d_d2_out,
-                           double* info_all) {
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<PairbDesc> desc((size_t)nseg);
+    const char* who = lone ? "recip_filter" : "recip_filter_batch";
+    std::vector<PairbDesc> desc;
     int64_t total_rows = 0;
-    for (int i = 0; i < nseg; ++i) {
-        PairbDesc& d = desc[i];
-        d.src_base = off[i]; d.ns = off[i + 1] - off[i];
-        d.tgt_off = tgt_off[i]; d.nt = tgt_off[i + 1] - tgt_off[i]; d.overlap = 1.0;
-        d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(d.ns);
-        total_rows += d.nrows;
-        if (total_rows > 0x7fff0000ll) return set_err(c, KSS_ERR_ARG, "recip_filter_batch: batch too large for 32-bit indexing");
-    }
-    KCHK(stage_pairb(c, desc, true));
-    KCHK(recipb_setup(c, d_tgt, desc, off[nseg], "recip_filter_batch"));
+    if (!pairb_desc_of(off, tgt_off, nseg, desc, total_rows))
+        return set_err(c, KSS_ERR_ARG, (std::string(who) + ": batch too large for 32-bit indexing").c_str());
+    if (!lone) KCHK(stage_pairb(c, desc, true));
+    KCHK(recip_setup(c, d_tgt, desc, off[nseg], who, lone));
     const int64_t total_tgt = tgt_off[nseg];
-    const RecipbArgs ra = {{d_src, nullptr, nullptr, d_idx, d_d2, nullptr, max_d2}, d_tgt, (const PairbDesc*)c->pb_desc.p,
-                           (const int32_t*)c->pb_rowpair.p, nullptr, (const RecipPairDev*)c->recip_grids.p, c->o2o_table.p, total_tgt, nseg,
-                           (float4*)c->recip_sorted.p, d_idx_out, d_d2_out, nullptr};
-    if (launch_recipb(c->stream, (int)total_rows, c->recipb_cells, ra, nn_fma) != 0)
+    const RecipArgs ra = {{d_src, nullptr, nullptr, d_idx, d_d2, nullptr, max_d2}, d_tgt, (const PairbDesc*)c->pb_desc.p,
+                          lone ? nullptr : (const int32_t*)c->pb_rowpair.p, nullptr, (const RecipPairDev*)c->recip_grids.p, c->o2o_table.p,
+                          total_tgt, nseg, (float4*)c->recip_sorted.p, d_idx_out, d_d2_out, nullptr, desc[0], c->h_recip_grids[0]};
+    if (launch_recip(c->stream, (int)total_rows, c->recip_total_cells, ra, nn_fma) != 0)
         return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(reciprocal workspace)");
     HIPCHK(c, hipGetLastError());
     std::vector<unsigned> cnt((size_t)nseg * 4);
-    HIPCHK(c, hipMemcpyAsync(cnt.data(), recipb_counters(c->o2o_table.p, total_tgt), cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), recip_counters(c->o2o_table.p, total_tgt), cnt.size() * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < nseg; ++i)
         for (int q = 0; q < 3; ++q) info_all[(size_t)i * 3 + q] = (double)(cnt[(size_t)i * 4 + q] + 1u);

@@ -329,7 +329,9 @@ void launch_knn_sweep(hipStream_t st, const float4* d_qry, int nq, const float4*
 void launch_normals(hipStream_t st, const float4* d_pts, int n, const int32_t* d_knn, int k, double* d_normals);
 
 int preshape_blocks(int64_t n);
-int stream_blocks(int64_t n);
+inline int stream_blocks(int64_t n) {   // streaming kernels without a hand-over: 256 CUs x 8 workgroups, grid-stride beyond
+    return (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + 255) / 256));
+}
 
 // ---- the pair metrics' correspondence sums for one pair (kss_pair.hip) ----
 // One pass = [keys launch + selection] + ONE rows launch + ONE final launch.  The rows launch is pair_rows_kernel<M, SRC> over a
@@ -470,54 +472,36 @@ size_t o2o_table_bytes(int64_t total_tgt, int npairs);
 // table reset, claim, resolve: three launches for total_rows = the sum of the pairs' nrows workgroups.  0, or the hipError_t of the reset.
 int launch_o2o(hipStream_t st, int total_rows, int64_t total_tgt, int npairs, const O2oArgs& a);
 
-// ---- reciprocal rejection (kss_recip.hip) ----
-// The uniform cell grid the moving sources are binned into every pass: fixed on the host once per call from the target's bounding
-// box (recip_grid_of); a coordinate's cell is clamp(floor((v - o) * inv_h), 0, g - 1) per axis, x fastest in the linear index.
+// ---- reciprocal rejection, one pair or many per call (kss_recip.hip) ----
+// The uniform cell grid a pair's moving sources are binned into every pass: fixed on the host once per call from the bounding box
+// of the pair's target (recip_grid_of); a coordinate's cell is clamp(floor((v - o) * inv_h), 0, g - 1) per axis, x fastest in the
+// linear index.
 struct RecipGrid {
     float ox, oy, oz, inv_h;
     int32_t gx, gy, gz;
 };
-constexpr int RECIP_BOX_BLOCKS = 256;   // recip_bbox partials at most: 6 floats {min xyz, max xyz} each
-// The filter's arguments, by value.  s: the sources' CURRENT positions (src3, or src4 with perm: pair_walk's three forms) and the
-// NN pass's idx / d2 by original source index; tgt: nt packed float triples; work: recip_work_bytes(nt, cells) of workspace --
-// the claim table (nt uint64), four uint32 counters {m, u, r, unused}, each MINUS ONE, and one uint32 per cell -- set to all
-// ones before every pass; sorted: n float4 {x, y, z, bits(original index)} in cell order; idx_out / d2_out: the filtered arrays
-// (either may be null, either may be its input); info_mu: two doubles {m, u} (device or host-mapped, may be null).
-struct RecipArgs {
-    PairSrc s;
-    const float* tgt;
-    int64_t n, nt;
-    RecipGrid g;
-    void* work; float4* sorted;
-    int32_t* idx_out; float* d2_out;
-    double* info_mu;
-};
-__host__ __device__ inline int64_t recip_cells(const RecipGrid& g) { return (int64_t)g.gx * g.gy * g.gz; }
-size_t recip_work_bytes(int64_t nt, int64_t cells);
-__host__ __device__ inline unsigned* recip_counters(void* work, int64_t nt) { return (unsigned*)((unsigned long long*)work + nt); }
-// partial bounding boxes of nt packed float triples: returns the number of partials written to d_box (<= RECIP_BOX_BLOCKS)
-int launch_recip_bbox(hipStream_t st, const float* d_tgt, int64_t nt, float* d_box);
-// the grid for n sources over the box [mn, mx] (a box that is not finite, or a point: one cell)
-RecipGrid recip_grid_of(const float mn[3], const float mx[3], int64_t n);
-// reset, claim + count, scan, scatter, resolve + check: five launches.  0, or the hipError_t of the reset.
-int launch_recip(hipStream_t st, const RecipArgs& a, bool nn_fma);
-
-// ---- the same for many pairs per call (kss_recip.hip) ----
-// one pair's grid -- recip_grid_of(the box of ITS target, ITS source count) -- and where its cells start in the batch's cell counts
+constexpr int RECIP_BOX_BLOCKS = 256;   // box partials of a single pair at most: 6 floats {min xyz, max xyz} each
+constexpr int RECIP_GMAX = 64;          // cells per axis at most
+constexpr int RECIP_CELLS = 32768;      // cells aimed at at most per pair (the pair's one scan workgroup walks them all every pass)
+// one pair's grid -- recip_grid_of(the box of ITS target, ITS source count) -- and where its cells start in the call's cell counts
 struct alignas(16) RecipPairDev {
     RecipGrid g;
     int32_t cell_base;
 };
 static_assert(sizeof(RecipPairDev) == 32, "the host and the device table share this layout");
-// The batched filter's arguments, by value.  s, tgt: batch-wide, as in PairbArgs (s.src3: the filter alone, packed triples by global
-// source index; else s.src4 with s.perm); s.idx / s.d2: the NN pass's, a pair's at desc[p].src_base, idx counting inside its own
-// target; desc / row_pair / state as in O2oArgs; grids: one RecipPairDev per pair.  work: recipb_work_bytes(total_tgt, npairs,
-// total_cells) of workspace, all ones before every pass -- the claim table (one uint64 per target of the batch, pair p's at
-// desc[p].tgt_off), four uint32 counters {m, u, r, unused} per pair, one uint32 per cell of every pair (pair p's at
-// grids[p].cell_base), each MINUS ONE.  sorted: one float4 {x, y, z, bits(index inside the pair)} per source of the batch, pair p's
-// cell-ordered sources in [src_base, src_base + ns).  idx_out / d2_out: laid out like s.idx / s.d2 (either may be null or its
-// input); info_mu: two doubles {m, u} per pair (device or host-mapped, may be null).
-struct RecipbArgs {
+// The filter's arguments, by value.  s: the sources' CURRENT positions call-wide (s.src3: the filter alone, packed triples by global
+// source index; else s.src4, with s.perm where the cell-list setup re-ordered them) and the NN pass's s.idx / s.d2 by original source
+// index, a pair's at desc[p].src_base, idx counting inside its own target; tgt: the call's packed float triples; desc / row_pair /
+// state as in O2oArgs (state null: every pair is active); grids: one RecipPairDev per pair.  row_pair null: ONE pair, whose
+// descriptor and grid are lone_desc and lone_grid here in the struct -- desc and grids are not read (launch_recip takes the
+// kernels' LONE instances).
+// work: recip_work_bytes(total_tgt, npairs, total_cells) of workspace, all ones before every pass -- the claim table (one uint64
+// per target of the call, pair p's at desc[p].tgt_off), four uint32 counters {m, u, r, unused} per pair, one uint32 per cell of
+// every pair (pair p's at grids[p].cell_base), each MINUS ONE.  sorted: one float4 {x, y, z, bits(index inside the pair)} per source
+// of the call, pair p's cell-ordered sources in [src_base, src_base + ns).  idx_out / d2_out: the filtered arrays, laid out like
+// s.idx / s.d2 (either may be null, either may be its input); info_mu: two doubles {m, u} per pair (device or host-mapped, may be
+// null).
+struct RecipArgs {
     PairSrc s;
     const float* tgt;
     const PairbDesc* desc; const int32_t* row_pair; const PairState* state; const RecipPairDev* grids;
@@ -525,14 +509,78 @@ struct RecipbArgs {
     float4* sorted;
     int32_t* idx_out; float* d2_out;
     double* info_mu;
+    PairbDesc lone_desc; RecipPairDev lone_grid;
 };
-size_t recipb_work_bytes(int64_t total_tgt, int npairs, int64_t total_cells);
-__host__ __device__ inline unsigned* recipb_counters(void* work, int64_t total_tgt) { return (unsigned*)((unsigned long long*)work + total_tgt); }
+__host__ __device__ inline int64_t recip_cells(const RecipGrid& g) { return (int64_t)g.gx * g.gy * g.gz; }
+size_t recip_work_bytes(int64_t total_tgt, int npairs, int64_t total_cells);
+__host__ __device__ inline unsigned* recip_counters(void* work, int64_t total_tgt) { return (unsigned*)((unsigned long long*)work + total_tgt); }
 // every pair's target box in ONE launch: `split` partials of 6 floats {min xyz, max xyz} per pair, pair p's at d_box + 6 * split * p
-void launch_recipb_bbox(hipStream_t st, const float* d_tgt, const PairbDesc* d_desc, int npairs, int split, float* d_box);
-// reset, claim + count, scan, scatter, resolve + check for the whole batch: the reset and four launches, total_rows workgroups in the
-// walks and the resolve, one workgroup per pair in the scan.  0, or the hipError_t of the reset.
-int launch_recipb(hipStream_t st, int total_rows, int64_t total_cells, const RecipbArgs& a, bool nn_fma);
+// (d_desc null: the one pair `lone`)
+void launch_recip_bbox(hipStream_t st, const float* d_tgt, const PairbDesc* d_desc, const PairbDesc& lone, int npairs, int split, float* d_box);
+// reset, claim + count, scan, scatter, resolve + check: the reset and four launches, total_rows workgroups in the walks and the
+// resolve, one workgroup per pair in the scan.  0, or the hipError_t of the reset.
+int launch_recip(hipStream_t st, int total_rows, int64_t total_cells, const RecipArgs& a, bool nn_fma);
+
+// The host arithmetic of the filters' setup, free of the device (tools/recip_host_check.hip runs it under the host sanitizers).
+constexpr int64_t PAIRB_INDEX_MAX = 0x7fff0000ll;   // rows, targets, cells and box partials of a call are 32-bit indices
+// nseg segments as the batched kernels see them: sources [off[i], off[i + 1]), targets [tgt_off[i], tgt_off[i + 1]), the rows
+// numbered in order.  false: more rows or targets than PAIRB_INDEX_MAX.
+inline bool pairb_desc_of(const int64_t* off, const int64_t* tgt_off, int nseg, std::vector<PairbDesc>& desc, int64_t& total_rows) {
+    desc.resize((size_t)nseg);
+    total_rows = 0;
+    for (int i = 0; i < nseg; ++i) {
+        PairbDesc& d = desc[i];
+        d.src_base = off[i]; d.ns = off[i + 1] - off[i];
+        d.tgt_off = tgt_off[i]; d.nt = tgt_off[i + 1] - tgt_off[i]; d.overlap = 1.0;
+        d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(d.ns);
+        total_rows += d.nrows;
+        if (total_rows > PAIRB_INDEX_MAX || tgt_off[i + 1] - tgt_off[0] > PAIRB_INDEX_MAX) return false;
+    }
+    return true;
+}
+// The grid for n sources over the box [mn, mx] (a box that is not finite, or a point: one cell).  The cell edge aims at
+// min(n / 2, RECIP_CELLS) cells over the axes of non-zero extent -- a few sources per cell for a cloud that fills its box, some tens
+// for a surface -- with at most RECIP_GMAX cells per axis; an axis of zero extent gets one cell.
+inline RecipGrid recip_grid_of(const float mn[3], const float mx[3], int64_t n) {
+    RecipGrid g = {0.0f, 0.0f, 0.0f, 0.0f, 1, 1, 1};
+    double ext[3], vol = 1.0, emax = 0.0;
+    int k = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(mn[a]) || !std::isfinite(mx[a]) || mx[a] < mn[a]) return g;
+        ext[a] = (double)mx[a] - (double)mn[a];
+        if (ext[a] > 0.0) { ++k; vol *= ext[a]; emax = std::max(emax, ext[a]); }
+    }
+    if (k == 0) return g;
+    const double want = (double)std::max<int64_t>(1, std::min<int64_t>(n / 2, RECIP_CELLS));
+    const float h = (float)std::max(std::pow(vol / want, 1.0 / k), emax / (RECIP_GMAX - 0.5));
+    const float inv_h = 1.0f / h;
+    if (!(h > 0.0f) || !std::isfinite(inv_h) || !std::isfinite(h)) return g;
+    g.ox = mn[0]; g.oy = mn[1]; g.oz = mn[2];
+    g.inv_h = inv_h;
+    int* gg[3] = {&g.gx, &g.gy, &g.gz};
+    for (int a = 0; a < 3; ++a)
+        *gg[a] = ext[a] > 0.0 ? (int)std::max(1.0, std::min((double)RECIP_GMAX, std::floor(ext[a] / (double)h) + 1.0)) : 1;
+    return g;
+}
+// Every pair's {grid, first cell} from the box partials as launch_recip_bbox wrote them (`split` per pair): the cell total, or -1
+// where it passes PAIRB_INDEX_MAX.
+inline int64_t recip_grids_of(const float* box, int split, const std::vector<PairbDesc>& desc, std::vector<RecipPairDev>& grids) {
+    grids.resize(desc.size());
+    int64_t cells = 0;
+    for (size_t p = 0; p < desc.size(); ++p) {
+        float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int b = 0; b < split; ++b)
+            for (int k = 0; k < 3; ++k) {
+                mn[k] = std::fmin(mn[k], box[(p * split + b) * 6 + k]);
+                mx[k] = std::fmax(mx[k], box[(p * split + b) * 6 + 3 + k]);
+            }
+        grids[p].g = recip_grid_of(mn, mx, desc[p].ns);
+        grids[p].cell_base = (int32_t)cells;
+        cells += recip_cells(grids[p].g);
+        if (cells > PAIRB_INDEX_MAX) return -1;
+    }
+    return cells;
+}
 
 // AIVS down-sampler (kss_aivs.hip): indices of the selected points in the reference's output order
 int aivs_device(hipStream_t st, const double* d_xyz, int n, int point_num, std::vector<int32_t>& out_idx, std::string& err,

@@ -825,12 +825,6 @@ void launch_finalize_sums(hipStream_t st, const PairRed* d_pairs, int n_pairs, c
 // The block decomposition of a cloud depends on its size only, so "both clouds in one call" and "one call per cloud"
 // give the same bits.
 // ---------------------------------------------------------------------------------------------
-int stream_blocks(int64_t n) {   // streaming kernels without a hand-over: 256 CUs x 8 workgroups, grid-stride beyond
-    int64_t b = (n + 255) / 256;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 int preshape_blocks(int64_t n) {
     // >= 16 points per lane before another workgroup is added: every workgroup costs a row hand-over (round 3, when each

@@ -180,6 +180,136 @@ def test_pairs_of_a_batch_do_not_see_each_other(ctx, O):
         assert tuple(int(x) for x in info[1 - b_at]) == (257, 257, 257)
 
 
+@pytest.mark.parametrize("s", [0, 1, 2, 3], ids=["n%d" % n for n in SIZES[:4]])
+def test_one_segment_through_the_batch_entry(ctx, segments, s):
+    """nseg = 1 at n = 1, 64, 65, 257 through offsets that do not start at 0, with rows in front and behind that nobody owns: the
+    restatement is the witness (the single call runs the same kernels), and the padding comes back untouched."""
+    segs, refs = segments
+    assert len(segs[s][0]) == SIZES[s]
+    pad_s, pad_t = 5, 7
+    src, so, tgt, to, idx, d2 = _pack_segments(segs, [s], pad_s, pad_t)
+    assert so[0] == pad_s and to[0] == pad_t and len(so) == 2
+    got_i, got_d, info = ctx.recip_filter_batch(src, so, tgt, to, idx, d2, MAX_D2)
+    assert info.shape == (1, 3)
+    _check_segments(got_i, got_d, info, so, [s], refs)
+    for part in (slice(0, pad_s), slice(len(idx) - pad_s, len(idx))):
+        assert np.array_equal(got_i[part], idx[part]) and np.array_equal(_bits(got_d[part]), _bits(d2[part]))
+
+
+# ---- above the row cap, the filter alone ----
+CAP_N = 2048 * 256 + 257
+
+
+@pytest.fixture(scope="module")
+def capped(O):
+    """More sources than stream_blocks' 2048 rows of 256 hold: the grid-stride term of the walks and of the resolve is live.  128
+    targets -- 64 random points and a twin of each at distance 1.7e-3 -- tiled CAP_N / 128 times plus N(0, 0.05) jitter: every target
+    has thousands of candidates and one winner, and of two twins the winner of the one is often nearer to the other than that one's
+    own winner, which then is not mutual.  The restatement visits 128 x CAP_N pairs: about three seconds, computed once."""
+    rng = np.random.default_rng(2029)
+    half = rng.uniform(-1, 1, (64, 3)).astype(F32)
+    tgt = np.concatenate([half, half + F32(1e-3)]).astype(F32)
+    src = (np.tile(tgt, (CAP_N // 128 + 1, 1))[:CAP_N] + rng.normal(0, 0.05, (CAP_N, 3))).astype(F32)
+    idx, d2 = O.nn_brute(src, tgt)
+    ref = RR.filter_direct(src, tgt, idx, d2, 4.0, chunk=16)
+    return (src, tgt, idx, d2), ref
+
+
+def test_filter_above_the_row_cap(ctx, capped):
+    (src, tgt, idx, d2), ref = capped
+    m, u, r = ref[2:]
+    print("above the row cap: m %d u %d r %d" % (m, u, r))
+    assert m == CAP_N and u == 128 and 1 <= r < u              # winners and mutual winners both exist and differ
+    one = ctx.recip_filter(src, tgt, idx, d2, 4.0)
+    assert one[2:] == ref[2:] and np.array_equal(one[0], ref[0]) and np.array_equal(_bits(one[1]), _bits(ref[1]))
+    # as the second of two segments: its rows start behind the small segment's
+    rng = np.random.default_rng(7)
+    s_src, s_tgt = rng.uniform(-1, 1, (300, 3)).astype(F32), rng.uniform(-1, 1, (220, 3)).astype(F32)
+    s_idx = rng.integers(0, 220, 300).astype(np.int32)
+    small = (s_src, s_tgt, s_idx, RR.dist2(s_src, s_tgt[s_idx]))
+    s_ref = RR.filter_direct(*small, 4.0)
+    segs = [small, (src, tgt, idx, d2)]
+    p_src, so, p_tgt, to, p_idx, p_d2 = _pack_segments(segs, [0, 1])
+    got_i, got_d, info = ctx.recip_filter_batch(p_src, so, p_tgt, to, p_idx, p_d2, 4.0)
+    _check_segments(got_i, got_d, info, so, [0, 1], [s_ref, ref])
+
+
+# ---- stale tables on a shared context ----
+def _same_filter(a, b):
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        if isinstance(x, np.ndarray):
+            assert x.dtype == y.dtype and np.array_equal(_bits(x) if x.dtype in (F32, F64) else x, _bits(y) if y.dtype in (F32, F64) else y)
+        else:
+            assert x == y
+
+
+def _same_icp(a, b):
+    assert a["iterations"] == b["iterations"] and a["state"] == b["state"] and a["converged"] == b["converged"]
+    for k in ("T", "trace_Tk", "trace_sums"):
+        assert np.array_equal(_bits(a[k]), _bits(b[k])), k
+    for k in ("trace_recip", "recip_info", "trace_o2o", "o2o_info"):
+        if k in a:
+            assert np.array_equal(_bits(a[k]), _bits(b[k])), k
+    assert _f64_bits(a["fitness"]) == _f64_bits(b["fitness"]) and _f64_bits(a["last_mse"]) == _f64_bits(b["last_mse"])
+
+
+def _same_batch(a, b):
+    for x, y in zip(a[0], b[0]):
+        assert x.iterations == y.iterations and x.state == y.state and x.pair_id == y.pair_id
+        assert np.array_equal(_bits(x.matrix()), _bits(y.matrix()))
+        assert _f64_bits(x.fitness) == _f64_bits(y.fitness) and _f64_bits(x.last_mse) == _f64_bits(y.last_mse)
+    assert np.array_equal(_bits(a[1]), _bits(b[1]))
+    assert np.array_equal(_bits(a[2]["trace_recip"]), _bits(b[2]["trace_recip"]))
+
+
+def test_stale_tables_on_a_shared_context(pkg, ctx, segments):
+    """The single pair reads the staged descriptor, the staged grids and the cell total that the batch also writes, and one-to-one
+    shares the descriptors and the claim table's buffer: eight calls in a row on ONE context, each of which must give what it gives
+    on a context that has run nothing before it -- and, for the filters, what the restatement gives."""
+    segs, refs = segments
+    rng = np.random.default_rng(11)
+    o_idx, o_d2 = rng.integers(0, 190, 300).astype(np.int32), rng.uniform(0, 1, 300).astype(F32)
+    a_src, a_tgt = _bumpy(pkg, 71, 1500, 6.0, n_src=900)
+    b_src, b_tgt = _bumpy(pkg, 72, 700, 8.0, n_src=333)
+    so, to = np.array([0, 900, 1233], np.int64), np.array([0, 1500, 2200], np.int64)
+    p3 = lambda c: c.icp_params(max_iterations=3, fixed_iterations=1)
+    order_a, order_b = list(range(len(SIZES))), [4, 0, 3, 5, 1, 2]
+    pack_a, pack_b = _pack_segments(segs, order_a), _pack_segments(segs, order_b)
+    calls = [
+        ("filter_batch", lambda c: c.recip_filter_batch(*pack_a, MAX_D2)),
+        ("filter", lambda c: c.recip_filter(*segs[3], MAX_D2)),
+        ("o2o_filter", lambda c: c.o2o_filter(o_idx, o_d2, 190, 1.0)),
+        ("icp", lambda c: c.icp_recip(a_src, a_tgt, None, overlap=0.9, metric=RR.POINT, params=p3(c), trace_cap=8)),
+        ("icp", lambda c: c.icp_o2o(a_src, a_tgt, None, overlap=0.9, metric=RR.POINT, params=p3(c), trace_cap=8)),
+        ("batch", lambda c: c.icp_recip_batch(np.concatenate([a_src, b_src]), so, np.concatenate([a_tgt, b_tgt]), to, None,
+                                              overlaps=np.array([0.9, 0.8]), metric=RR.POINT, params=p3(c), trace_cap=8)),
+        ("filter", lambda c: c.recip_filter(*segs[2], MAX_D2)),
+        ("filter_batch", lambda c: c.recip_filter_batch(*pack_b, MAX_D2)),
+    ]
+    shared = [fn(ctx) for _, fn in calls]
+    for q, ((kind, fn), got) in enumerate(zip(calls, shared)):
+        fresh_ctx = pkg.Context(0)
+        try:
+            want = fn(fresh_ctx)
+        finally:
+            fresh_ctx.close()
+        if kind == "icp":
+            assert want["iterations"] == 3
+            _same_icp(got, want)
+        elif kind == "batch":
+            assert [r.iterations for r in want[0]] == [3, 3]
+            _same_batch(got, want)
+        else:
+            _same_filter(got, want)
+    # the filters against the restatement
+    _check_segments(shared[0][0], shared[0][1], shared[0][2], pack_a[1], order_a, refs)
+    _check_segments(shared[7][0], shared[7][1], shared[7][2], pack_b[1], order_b, refs)
+    for got, s in ((shared[1], 3), (shared[6], 2)):
+        assert got[2:] == refs[s][2:] and np.array_equal(got[0], refs[s][0]) and np.array_equal(_bits(got[1]), _bits(refs[s][1]))
+    assert len(segs[3][0]) == 257 and len(segs[2][0]) == 65
+
+
 # ---- the loop ----
 class Pair:
     """One pair with its normals and, computed once and kept, the single-pair calls' results on it."""

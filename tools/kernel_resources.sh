@@ -12,14 +12,14 @@ name = None; rows = {}
 for l in open('/tmp/_kr.log'):
     m = re.search(r'Function Name: (\S+)', l)
     if m: name = m.group(1); rows[name] = {}
-    m = re.search(r'remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\d+)', l)
+    m = re.search(r'remark:\s+(VGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill|LDS Size \[bytes/block\]): (\d+)', l)
     if m and name: rows[name][m.group(1).split(' [')[0]] = int(m.group(2))
 import subprocess
 print(sys.argv[1])
 for n, r in rows.items():
-    if not any(k in n for k in ("resident_icp", "grid_pass_kernel", "gridb_pass", "cand_", "nn_sweep_kernelILi4ELb0ELb0", "rot_search_kernelILi4ELi256", "preshape", "corr_reduce", "finalize", "pair_rows", "p2l_final", "trim_", "robust_", "gicp_", "symm_", "sim_", "pairb_", "o2o_", "recip_", "recipb_")): continue
+    if not any(k in n for k in ("resident_icp", "grid_pass_kernel", "gridb_pass", "cand_", "nn_sweep_kernelILi4ELb0ELb0", "rot_search_kernelILi4ELi256", "preshape", "corr_reduce", "finalize", "pair_rows", "p2l_final", "trim_", "robust_", "gicp_", "symm_", "sim_", "pairb_", "o2o_", "recip_")): continue
     try: d = subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip().split('(')[0]
     except OSError: d = n
-    print("  %-110s VGPRs %3d  spilled %3d  scratch %4d B  waves/SIMD %d  LDS %6d" % (d[:110], r.get("VGPRs", -1), r.get("VGPRs Spill", 0), r.get("ScratchSize", 0), r.get("Occupancy", 0), r.get("LDS Size", 0)))
+    print("  %-110s VGPRs %3d  SGPRs %3d  spilled %3d + %d  scratch %4d B  waves/SIMD %d  LDS %6d" % (d[:110], r.get("VGPRs", -1), r.get("TotalSGPRs", -1), r.get("VGPRs Spill", 0), r.get("SGPRs Spill", 0), r.get("ScratchSize", 0), r.get("Occupancy", 0), r.get("LDS Size", 0)))
 PY
 done

@@ -9,7 +9,10 @@ behind the NN pass is what reciprocal's is set beside, and the 
   2  the filter alone (kss_recip_filter_dev) on 100 000 sources: a converged map (the source is the target plus 1e-3 jitter), a
      far-apart map (the same source moved by 3 along x: the balls span the whole grid and most winners take the escape), and every
      source at one point (one cell holds them all).
-usage: python tools/recip_time.py [--rounds 5] [--passes 20] [--only 12]"""
+With --baseline LIB every variant also runs on a second context on that library (the parent commit's build), "parent " in front of its
+name, alternating with this build's in the same process: the one-to-one rows, whose code a change to the reciprocal filter does not
+touch, are the control for what the machine itself moves.
+usage: python tools/recip_time.py [--baseline path/to/parent/libkssicp.so] [--rounds 5] [--passes 20] [--only 12]"""
 import argparse, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,9 +22,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--passes", type=int, default=20)
 ap.add_argument("--only", default="12")
+ap.add_argument("--baseline", default=None)
 args = ap.parse_args()
 pkg = g.load_package(); S = pkg.synth
 ctx = pkg.Context(0)
+# name prefix -> context: every run below is a (context, function of that context) pair
+CTXS = {"": ctx}
+if args.baseline:
+    CTXS["parent "] = pkg.Context(0, lib=pkg.binding.load_library(args.baseline))
 POINT = pkg.METRIC_POINT
 
 
@@ -51,12 +59,13 @@ def alternating(runs, measure):
 def per_pass(runs, passes):
     """us per whole pass of each run, from the difference of two fixed-iteration runs"""
     P = [ctx.icp_params(max_iterations=it, fixed_iterations=1, compute_fitness=0) for it in (passes, 2 * passes)]
-    for run in runs.values():      # warm-up of every variant and shape (allocations, cell list sizes)
+    for cx, run in runs.values():      # warm-up of every variant and shape (allocations, cell list sizes)
         for p in P:
-            run(p)
+            run(cx, p)
 
-    def measure(run):
-        ts = [timed(lambda: run(p))[1] for p in P]
+    def measure(cr):
+        cx, run = cr
+        ts = [timed(lambda: run(cx, p))[1] for p in P]
         return (ts[1] - ts[0]) / passes * 1e6
     per = alternating(runs, measure)
     report(per, "us per pass")
@@ -67,15 +76,18 @@ def behind_nn(runs, passes):
     """us per pass of the launches behind the NN pass alone (kss_profile_get of KSS_K_CORR_REDUCE)"""
     p = ctx.icp_params(max_iterations=passes, fixed_iterations=1, compute_fitness=0)
 
-    def measure(run):
-        ctx.profile_reset()
-        run(p)
-        ctx.synchronize()
-        ms, n = ctx.profile_get(pkg.K_CORR_REDUCE)
+    def measure(cr):
+        cx, run = cr
+        cx.profile_reset()
+        run(cx, p)
+        cx.synchronize()
+        ms, n = cx.profile_get(pkg.K_CORR_REDUCE)
         return ms / max(n, 1) * 1e3
-    ctx.profile_enable(1)
+    for cx in CTXS.values():
+        cx.profile_enable(1)
     per = alternating(runs, measure)
-    ctx.profile_enable(0)
+    for cx in CTXS.values():
+        cx.profile_enable(0)
     report({k + ", behind the NN pass": v for k, v in per.items()}, "us per pass")
     return {k: float(np.median(v)) for k, v in per.items()}
 
@@ -88,8 +100,10 @@ if "1" in args.only:
         torch.cuda.synchronize()
         print("== 1: %s, %d x %d" % (name, ns, nt), flush=True)
         a = (ds.data_ptr(), ns, dt.data_ptr(), nt, None)
-        runs = {"o2o point 1.0": lambda p: ctx.icp_o2o_dev(*a, p, overlap=1.0, metric=POINT)[0],
-                "recip point 1.0": lambda p: ctx.icp_recip_dev(*a, p, overlap=1.0, metric=POINT)[0]}
+        runs = {}
+        for pre, cx in CTXS.items():
+            runs[pre + "o2o point 1.0"] = (cx, lambda cx, p: cx.icp_o2o_dev(*a, p, overlap=1.0, metric=POINT)[0])
+            runs[pre + "recip point 1.0"] = (cx, lambda cx, p: cx.icp_recip_dev(*a, p, overlap=1.0, metric=POINT)[0])
         med = per_pass(runs, args.passes)
         beh = behind_nn(runs, args.passes)
         print("%s: recip - o2o = %.1f us per whole pass, %.1f us behind the NN pass" % (
@@ -113,16 +127,18 @@ if "2" in args.only:
         dev[k] = (torch.from_numpy(np.ascontiguousarray(src)).cuda(), torch.from_numpy(idx).cuda(), torch.from_numpy(d2).cuda(), max_d2)
     torch.cuda.synchronize()
 
-    def call(k, recip):
+    def call(cx, k, recip):
         ds, di, dd, max_d2 = dev[k]
         if recip:
-            return ctx.recip_filter_dev(ds.data_ptr(), n, dt.data_ptr(), len(tgt), di.data_ptr(), dd.data_ptr(), max_d2, 0, oi.data_ptr(), od.data_ptr())
-        return ctx.o2o_filter_dev(di.data_ptr(), dd.data_ptr(), n, len(tgt), max_d2, oi.data_ptr(), od.data_ptr())
+            return cx.recip_filter_dev(ds.data_ptr(), n, dt.data_ptr(), len(tgt), di.data_ptr(), dd.data_ptr(), max_d2, 0, oi.data_ptr(), od.data_ptr())
+        return cx.o2o_filter_dev(di.data_ptr(), dd.data_ptr(), n, len(tgt), max_d2, oi.data_ptr(), od.data_ptr())
     runs = {}
     for k in dev:
-        print("%-28s {m, u, r} = %s" % (k, call(k, True)), flush=True)
-        call(k, False)
-        runs["o2o filter, " + k] = lambda k=k: call(k, False)
-        runs["recip filter, " + k] = lambda k=k: call(k, True)
-    report(alternating(runs, lambda run: timed(lambda: [run() for _ in range(20)])[1] / 20 * 1e6), "us per call")
-ctx.close()
+        for pre, cx in CTXS.items():
+            print("%-28s {m, u, r} = %s" % (pre + k, call(cx, k, True)), flush=True)
+            call(cx, k, False)
+            runs[pre + "o2o filter, " + k] = (cx, lambda cx, k=k: call(cx, k, False))
+            runs[pre + "recip filter, " + k] = (cx, lambda cx, k=k: call(cx, k, True))
+    report(alternating(runs, lambda cr: timed(lambda: [cr[1](cr[0]) for _ in range(20)])[1] / 20 * 1e6), "us per call")
+for cx in CTXS.values():
+    cx.close()
