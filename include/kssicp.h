@@ -709,6 +709,81 @@ int kss_icp_gicp_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *
                            const float *d_tgt_all, const int64_t *tgt_off, const float *d_tgt_normals_all, int npairs,
                            const kss_icp_params *p, const kss_gicp_params *gp, const double *epsilons, kss_icp_result *results);
 
+/* ---- voxelized generalized ICP against a reusable voxel map (Koide, Yokozuka, Oishi, Banno: Voxelized GICP, ICRA 2021;
+ *      DESIGN.md 2.30), one pair ----
+ * The target is summarised ONCE as one Gaussian per occupied voxel -- the mean of the voxel's points and the average n n^T of
+ * their normals -- and a scan is registered against that summary: no nearest-neighbour search, a pass whose cost does not depend
+ * on the target's size, and a map that serves as many scans and start poses as the caller likes.
+ *
+ * The map (kss_vmap).  It belongs to the context it was created on and owns its device memory apart from the context's grow-only
+ * workspace: any other call on the context, one that grows the workspace included, leaves it intact.  It keeps the dense cell ->
+ * voxel table (4 bytes per cell) and the packed voxel records, not the target's points or normals.
+ *   normals     tgt_normals NULL: computed as in kss_gicp_sums (kss_normals' definition at k = min(normals_k, nt), rounded to float);
+ *   mapped      a target is mapped if all three coordinates and all three normal components are finite; the others are not in the map;
+ *   origin      lo_a = the float minimum of the mapped targets on axis a, a zero minimum taken as +0;
+ *   cell        inv = 1.0f / (float)leaf;  f_a = floorf((x_a - lo_a) * inv), a float subtraction then a float multiplication, nothing
+ *               fused;  dims_a = 1 + max f_a over the mapped targets;  lin = (c_z * dims_y + c_y) * dims_x + c_x in int64;
+ *   record      over the voxel's mapped targets IN ASCENDING ORIGINAL INDEX, serially in f64, nothing fused: N = their count,
+ *               s_a += (double)q_a, P_ab += (double)n_a * (double)n_b for the six a <= b; mean_a = s_a / (double)N, S_ab = P_ab /
+ *               (double)N.  The order is part of the definition: every bit of the record follows from the cloud alone.
+ * KSS_ERR_ARG: a NULL argument; nt <= 0; leaf not finite or not > 0; normals_k outside 3..64 where the normals are computed; no
+ * mapped target; a max f_a that is not finite (an inv of infinity) or dims_x * dims_y * dims_z > 2^26.
+ * kss_ctx_destroy frees the maps of the context that are still alive; their handles are dead with it.  kss_vmap_destroy waits for
+ * the context's stream first.  An entry point takes a handle only if it is a live map of the context it is called on: NULL, a
+ * destroyed map and a map of another context are KSS_ERR_ARG (kss_vmap_info has no context to ask: it trusts its handle). */
+typedef struct kss_vmap kss_vmap;
+typedef struct {
+    double leaf;        /* the voxel edge; no default: kss_vmap_default_params sets 0 and the caller must set it */
+    int    normals_k;   /* 20: read only when tgt_normals is NULL; 3..64 */
+} kss_vmap_params;
+int kss_vmap_default_params(kss_vmap_params *vp);
+int kss_vmap_create(kss_ctx *ctx, const float *tgt, int64_t nt, const float *tgt_normals, const kss_vmap_params *vp, kss_vmap **out);
+int kss_vmap_create_dev(kss_ctx *ctx, const float *d_tgt, int64_t nt, const float *d_tgt_normals, const kss_vmap_params *vp, kss_vmap **out);
+int kss_vmap_destroy(kss_ctx *ctx, kss_vmap *map);
+#define KSS_VMAP_NINFO 10   /* {mapped targets, voxels, dims x y z, leaf, origin x y z, inv widened} */
+int kss_vmap_info(const kss_vmap *map, double info[KSS_VMAP_NINFO]);
+#define KSS_VMAP_NSTAT 10   /* {N, mean x y z, S00 S01 S02 S11 S12 S22} */
+/* The voxels in ascending lin: lin[v] and stats[v * KSS_VMAP_NSTAT ..] (either may be NULL), *nvox their count.  Both NULL: the count
+ * alone.  KSS_ERR_CAPACITY (*nvox set) when capacity < *nvox. */
+int kss_vmap_read(kss_ctx *ctx, const kss_vmap *map, int64_t *lin, double *stats, int64_t capacity, int64_t *nvox);
+
+/* One pass.  F and R_F as in kss_icp_gicp.  For source i: its current float position p and its float normal ns = src_normals[i]
+ * (by ORIGINAL index).  Everything after the lookup is f64 on the widened floats, nothing fused, in kss_icp_gicp's order:
+ *   voxel       f_a from p by the map's expression above; the source has a voxel iff 0 <= f_a < dims_a on all three axes --
+ *               compared in float, so a NaN has none -- and the cell is occupied;
+ *   candidate   it has a voxel, ns is finite, and !(dd > max_d2) with d = mean - p, dd = (d[0]*d[0] + d[1]*d[1]) + d[2]*d[2];
+ *   metric      m, C, M, d, u, B, UL and the dropped rule are kss_icp_gicp's text with g(a,b) = S_ab + m[a]*m[b] and q = mean.  No
+ *               count weight.  A voxel of ONE target has mean = q and S = nq nq^T exactly: the correspondence's terms are then
+ *               kss_icp_gicp's bit for bit;
+ *   record      kss_icp_gicp's KSS_P2L_NSUMS slots in kss_icp_p2l's fixed summation order, a function of n alone: [28] = sum of dd
+ *               over the kept sources, [29] = 0, [30] = sum d^T M d, [31] = 0.
+ * kss_vgicp_sums[_dev]: the record of one pass at the positions passed in.  Rn: HOST pointer to the row-major 3x3 float applied to
+ * the source normals in place of R_F, NULL = identity.  src_normals NULL: computed as in kss_gicp_sums at gp->normals_k.
+ * KSS_ERR_ARG: a NULL src, gp or sums; n <= 0; not a live map of ctx; epsilon outside (0, 1] or NaN; normals_k outside 3..64
+ * where the normals are computed. */
+int kss_vgicp_sums(kss_ctx *ctx, const float *src, const float *src_normals, int64_t n, const kss_vmap *map, double max_d2,
+                   const float Rn[9], const kss_gicp_params *gp, double sums[KSS_P2L_NSUMS]);
+int kss_vgicp_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_src_normals, int64_t n, const kss_vmap *map, double max_d2,
+                       const float Rn[9], const kss_gicp_params *gp, double sums[KSS_P2L_NSUMS]);
+/* The loop is kss_icp_gicp's -- step kss_rigid_from_p2l_sums, fewer than min_correspondences kept -> KSS_STATE_NO_CORRESPONDENCES, a
+ * failed Cholesky -> KSS_STATE_DEGENERATE, PCL's criteria on MSE = [28] / [0], trace_sums (trace_cap * KSS_P2L_NSUMS doubles) and
+ * trace_Tk -- with NO nearest-neighbour pass in it: pass 0 works on the positions passed in, and behind every step T_k the sources
+ * move by T_k in float as every pair loop moves them (pcl transformCloud: ((T00*x + T01*y) + T02*z) + T03, no fma).
+ * res->fitness (p->compute_fitness): [28] / [0] of one more evaluation at F * the ORIGINAL source, F the final float 4x4 applied
+ * the same way and R_F turning the normals: the mean squared distance to the voxel mean over the kept sources of that evaluation,
+ * NaN when there is none.  This is NOT getFitnessScore: sources without a voxel do not count, and the distance is to a voxel's
+ * mean, not to a nearest target point.
+ * last_info (may be NULL): {kept in the last pass of the loop, ns, [30] of that pass, voxels of the map}.
+ * p->nn_mode, p->nn_fma and the nn_* tuning fields are not read.  KSS_ERR_ARG: everything kss_vgicp_sums refuses, a NULL p or res,
+ * a set p->allreduce, a set p->fitness_idx or p->fitness_d2 (there are no correspondences to return).  Many pairs per call, a
+ * count weight, a 7- or 27-voxel neighbourhood, robust or trimmed weights, the C++ mirror classes and the CLI do not have this
+ * method. */
+#define KSS_VGICP_NINFO 4
+int kss_icp_vgicp(kss_ctx *ctx, const float *src, int64_t ns, const float *src_normals, const kss_vmap *map, const kss_icp_params *p,
+                  const kss_gicp_params *gp, kss_icp_result *res, double last_info[KSS_VGICP_NINFO]);
+int kss_icp_vgicp_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const kss_vmap *map,
+                      const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res, double last_info[KSS_VGICP_NINFO]);
+
 /* ---- symmetric ICP (point-to-plane on the sum of both normals; Rusinkiewicz: A Symmetric Objective Function for ICP, SIGGRAPH
  * 2019; PCL's TransformationEstimationSymmetricPointToPlaneLLS) for one pair ----
  * The point-to-plane residual is taken against nq + ns and each cloud is turned by half the step towards the other: the residual

@@ -24,6 +24,9 @@ LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY = 0, 1, 2, 3   # KSS_LOSS_*: the we
 ROBUST_NINFO = 4         # KSS_ROBUST_NINFO: {m candidates, c2, sum of weights, cnt kept} of a robust pass
 SIM_NINFO = 6            # KSS_SIM_NINFO: {m, k, tau, kept, s_k, s_acc after the pass} of a similarity pass
 O2O_NINFO = 5            # KSS_O2O_NINFO: {u survivors, k, tau, kept, m candidates} of a one-to-one pass
+VMAP_NINFO = 10          # KSS_VMAP_NINFO: {mapped targets, voxels, dims x y z, leaf, origin x y z, inv widened} of a voxel map
+VMAP_NSTAT = 10          # KSS_VMAP_NSTAT: {N, mean x y z, S00 S01 S02 S11 S12 S22} of a voxel
+VGICP_NINFO = 4          # KSS_VGICP_NINFO: {kept in the last pass, ns, [30] of the last pass, voxels of the map}
 RECIP_NINFO = 6          # KSS_RECIP_NINFO: {r mutual winners, k, tau, kept, m candidates, u winners} of a reciprocal pass
 F32, F64 = 0, 1
 
@@ -54,6 +57,8 @@ SYMBOLS = [
     "kss_icp_o2o", "kss_icp_o2o_dev", "kss_icp_o2o_batch", "kss_icp_o2o_batch_dev",
     "kss_recip_filter", "kss_recip_filter_dev", "kss_recip_default_params", "kss_icp_recip", "kss_icp_recip_dev",
     "kss_recip_filter_batch", "kss_recip_filter_batch_dev", "kss_icp_recip_pairs", "kss_icp_recip_pairs_dev",
+    "kss_vmap_default_params", "kss_vmap_create", "kss_vmap_create_dev", "kss_vmap_destroy", "kss_vmap_info", "kss_vmap_read",
+    "kss_vgicp_sums", "kss_vgicp_sums_dev", "kss_icp_vgicp", "kss_icp_vgicp_dev",
 ]
 
 
@@ -109,6 +114,10 @@ class RobustParams(C.Structure):
 
 class GicpParams(C.Structure):
     _fields_ = [("epsilon", C.c_double), ("normals_k", C.c_int)]
+
+
+class VmapParams(C.Structure):
+    _fields_ = [("leaf", C.c_double), ("normals_k", C.c_int)]
 
 
 class SymmParams(C.Structure):
@@ -228,6 +237,16 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, dbl, vp, C.POINTER(GicpParams), vp]
     for n in ("kss_icp_gicp", "kss_icp_gicp_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, vp, i64, vp, C.POINTER(IcpParams), C.POINTER(GicpParams), C.POINTER(IcpResult)]
+    L.kss_vmap_default_params.argtypes = [C.POINTER(VmapParams)]
+    for n in ("kss_vmap_create", "kss_vmap_create_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, C.POINTER(VmapParams), C.POINTER(vp)]
+    L.kss_vmap_destroy.argtypes = [vp, vp]
+    L.kss_vmap_info.argtypes = [vp, vp]
+    L.kss_vmap_read.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64)]
+    for n in ("kss_vgicp_sums", "kss_vgicp_sums_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, i64, vp, dbl, vp, C.POINTER(GicpParams), vp]
+    for n in ("kss_icp_vgicp", "kss_icp_vgicp_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, vp, C.POINTER(IcpParams), C.POINTER(GicpParams), C.POINTER(IcpResult), vp]
     for n in ("kss_icp_p2l_batch", "kss_icp_p2l_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), vp]
     for n in ("kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev"):
@@ -472,6 +491,50 @@ def gicp_params(**kw):
         else:
             raise AttributeError(k)
     return gp
+
+
+def vmap_params(**kw):
+    """kss_vmap_default_params (leaf 0: the caller sets it, normals_k 20), then the fields given by keyword."""
+    L = load_library()
+    vp = VmapParams()
+    rc = L.kss_vmap_default_params(C.byref(vp))
+    if rc != 0:
+        raise KssError(rc, "kss_vmap_default_params")
+    for k, v in kw.items():
+        if not hasattr(vp, k):
+            raise AttributeError(k)
+        setattr(vp, k, v)
+    return vp
+
+
+class VoxelMap:
+    """A voxel map of one target cloud (kss_vmap): made by Context.vmap() / vmap_dev(), it lives on the device until close() -- or
+    until its context is closed, which frees it -- and serves any number of Context.icp_vgicp() / vgicp_sums() calls."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    def info(self):
+        """kss_vmap_info: the VMAP_NINFO doubles {mapped targets, voxels, dims x y z, leaf, origin x y z, inv widened}."""
+        out = np.zeros(VMAP_NINFO, np.float64)
+        rc = self.ctx.L.kss_vmap_info(self.h, _p(out))
+        if rc != 0:
+            raise KssError(rc, "kss_vmap_info")
+        return out
+
+    def read(self):
+        """kss_vmap_read: (lin [nvox] int64 ascending, stats [nvox, VMAP_NSTAT] float64)."""
+        n = C.c_int64(0)
+        self.ctx._chk(self.ctx.L.kss_vmap_read(self.ctx.h, self.h, None, None, 0, C.byref(n)), "kss_vmap_read")
+        lin = np.zeros(n.value, np.int64)
+        stats = np.zeros((n.value, VMAP_NSTAT), np.float64)
+        self.ctx._chk(self.ctx.L.kss_vmap_read(self.ctx.h, self.h, _p(lin), _p(stats), n.value, C.byref(n)), "kss_vmap_read")
+        return lin, stats
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx._chk(self.ctx.L.kss_vmap_destroy(self.ctx.h, self.h), "kss_vmap_destroy")
+        self.h = None
 
 
 def gicp_metric(nq, m, epsilon=1e-3):
@@ -1074,6 +1137,72 @@ class Context:
                                           C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
                                           C.byref(params), C.byref(gp), C.byref(res)), "kss_icp_gicp_dev")
         return res
+
+    # ---- voxelized generalized ICP against a voxel map
+    def vmap(self, tgt, leaf, normals=None, normals_k=20):
+        """kss_vmap_create: the VoxelMap of the target (nt x 3) at voxel edge `leaf`; normals: nt x 3, or None to compute them at
+        normals_k as icp_gicp does."""
+        t = _f32(tgt)
+        tn = self._gicp_normals(normals, len(t), "target")
+        vp = vmap_params(leaf=float(leaf), normals_k=int(normals_k))
+        h = C.c_void_p()
+        self._chk(self.L.kss_vmap_create(self.h, _p(t), len(t), _p(tn), C.byref(vp), C.byref(h)), "kss_vmap_create")
+        return VoxelMap(self, h)
+
+    def vmap_dev(self, d_tgt, nt, leaf, d_normals=None, normals_k=20):
+        """kss_vmap_create_dev on device pointers (the normals pointer may be 0 / None)."""
+        vp = vmap_params(leaf=float(leaf), normals_k=int(normals_k))
+        h = C.c_void_p()
+        self._chk(self.L.kss_vmap_create_dev(self.h, C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_normals)) if d_normals else None,
+                                             C.byref(vp), C.byref(h)), "kss_vmap_create_dev")
+        return VoxelMap(self, h)
+
+    def vgicp_sums(self, src, src_normals, vmap, max_d2=1.0, Rn=None, gp=None):
+        """kss_vgicp_sums: the P2L_NSUMS record of one voxelized generalized-ICP pass at the positions passed in.  Rn: the 3 x 3
+        applied to the source normals (None: identity); src_normals may be None (computed); gp: a GicpParams (gicp_params())."""
+        gp = gp if gp is not None else gicp_params()
+        s = _f32(src)
+        sn = self._gicp_normals(src_normals, len(s), "source")
+        r = self._gicp_rot(Rn)
+        sums = np.zeros(P2L_NSUMS, np.float64)
+        self._chk(self.L.kss_vgicp_sums(self.h, _p(s), _p(sn), len(s), vmap.h if vmap is not None else None, float(max_d2), _p(r),
+                                        C.byref(gp), _p(sums)), "kss_vgicp_sums")
+        return sums
+
+    def vgicp_sums_dev(self, d_src, d_src_normals, n, vmap, max_d2=1.0, Rn=None, gp=None):
+        """kss_vgicp_sums_dev on device pointers (the normals pointer may be 0 / None; Rn stays a host array)."""
+        gp = gp if gp is not None else gicp_params()
+        r = self._gicp_rot(Rn)
+        sums = np.zeros(P2L_NSUMS, np.float64)
+        self._chk(self.L.kss_vgicp_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_src_normals)) if d_src_normals else None, int(n),
+                                            vmap.h, float(max_d2), _p(r), C.byref(gp), _p(sums)), "kss_vgicp_sums_dev")
+        return sums
+
+    def icp_vgicp(self, src, vmap, src_normals=None, gp=None, params=None, trace_cap=0):
+        """Voxelized generalized ICP (kss_icp_vgicp) of the source (ns x 3) against a VoxelMap: icp_gicp's metric with the voxel's
+        mean and average n n^T in the target's place, and no nearest-neighbour search.  src_normals: ns x 3, or None (computed at
+        gp.normals_k).  The result dictionary of icp_gicp() plus "info", the VGICP_NINFO doubles {kept in the last pass, ns, [30]
+        of the last pass, voxels}.  "fitness" is the mean squared distance to the voxel mean over the sources kept at the final
+        pose, not icp()'s."""
+        gp = gp if gp is not None else gicp_params()
+        s = _f32(src)
+        sn = self._gicp_normals(src_normals, len(s), "source")
+        p = params if params is not None else self.icp_params()
+        info = np.zeros(VGICP_NINFO, np.float64)
+        out = self._icp_call(lambda res: self.L.kss_icp_vgicp(self.h, _p(s), len(s), _p(sn), vmap.h if vmap is not None else None, C.byref(p),
+                                                              C.byref(gp), C.byref(res), _p(info)),
+                             "kss_icp_vgicp", p, len(s), P2L_NSUMS, trace_cap, False)
+        out["info"] = info
+        return out
+
+    def icp_vgicp_dev(self, d_src, ns, d_src_normals, vmap, params, gp=None):
+        """kss_icp_vgicp_dev on device pointers (the normals pointer may be 0 / None); returns (IcpResult, info)."""
+        gp = gp if gp is not None else gicp_params()
+        res = IcpResult()
+        info = np.zeros(VGICP_NINFO, np.float64)
+        self._chk(self.L.kss_icp_vgicp_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
+                                           vmap.h, C.byref(params), C.byref(gp), C.byref(res), _p(info)), "kss_icp_vgicp_dev")
+        return res, info
 
     # ---- symmetric ICP
     def symm_sums(self, src, src_normals, tgt, tgt_normals, idx, max_d2=1.0, Rn=None, sp=None):

@@ -1,5 +1,5 @@
 // kss_api.hip -- the C-ABI of include/kssicp.h: context and profiling entry points, and the compute entry points over
-// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_robust / kss_pairb / kss_o2o / kss_recip .hip).
+// the engine (kss_engine.hip) and the kernel launchers (kss_kernels / kss_grid / kss_aivs / kss_knn / kss_octree / kss_p2l / kss_trim / kss_robust / kss_pairb / kss_o2o / kss_recip / kss_vmap .hip).
 // There is no CPU compute fallback anywhere in this file.
 #pragma clang fp contract(off)
 
@@ -83,6 +83,8 @@ int kss_ctx_destroy(kss_ctx* c) {
     if (c->res_gate) hipFree(c->res_gate);
     if (c->bar_state) hipFree(c->bar_state);
     if (c->h_state) hipHostFree(c->h_state);
+    for (kss_vmap* m : c->vmaps) { vmap_free(m->b); delete m; }   // voxel maps still alive go with their context (include/kssicp.h)
+    c->vmaps.clear();
     for (kss_ctx* w : c->workers) kss_ctx_destroy(w);
     c->workers.clear();
     if (c->own_stream) hipStreamDestroy(c->stream);
@@ -1010,6 +1012,154 @@ int kss_icp_gicp_batch(kss_ctx* c, const float* src, const int64_t* src_off, con
                        const double* epsilons, kss_icp_result* results) {
     return icp_gicp_any(c, "icp_gicp_batch", true, many_pairs(src, src_off, src_normals, tgt, tgt_off, tgt_normals, npairs), p, gp, epsilons,
                         results);
+}
+
+// ---- voxelized generalized ICP against a voxel map ------------------------------------
+// There is no target cloud in a registration here, so these entries have a path of their own: the map's check (vmap_live), the
+// source's staging and normals as pair_stage / cloud_normals_dev do them, then vgicp_record_dev / vgicp_run_dev.
+int kss_vmap_default_params(kss_vmap_params* vp) {
+    if (!vp) return KSS_ERR_ARG;
+    vp->leaf = 0.0;   // no default: the caller sets it
+    vp->normals_k = 20;
+    return KSS_OK;
+}
+
+// the handle is one of this context's live maps (a map of another context, a destroyed one and null are not)
+static bool vmap_live(const kss_ctx* c, const kss_vmap* m) {
+    return m && std::find(c->vmaps.begin(), c->vmaps.end(), m) != c->vmaps.end();
+}
+
+static int vmap_create_any(kss_ctx* c, bool host, const float* tgt, int64_t nt, const float* nrm, const kss_vmap_params* vp, kss_vmap** out) {
+    if (!c) return KSS_ERR_ARG;
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string("vmap_create: ") + what).c_str()); };
+    if (out) *out = nullptr;
+    if (!tgt || !vp || !out) return bad("null argument");
+    if (nt <= 0) return bad("empty cloud");
+    if (nt > 0x7fff0000ll) return bad("cloud too large");
+    if (!(vp->leaf > 0.0) || !std::isfinite(vp->leaf)) return bad("leaf must be finite and > 0");
+    if (!nrm && (vp->normals_k < 3 || vp->normals_k > 64)) return bad("normals_k must be in 3..64");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (host) {
+        const size_t tb = (size_t)nt * 3 * sizeof(float);
+        KCHK(upload(c, c->stage_tgt, tgt, tb));
+        tgt = (const float*)c->stage_tgt.p;
+        if (nrm) {
+            KCHK(upload(c, c->p2l_nrm, nrm, tb));
+            nrm = (const float*)c->p2l_nrm.p;
+        }
+    }
+    if (!nrm) KCHK(cloud_normals_dev(c, tgt, nt, vp->normals_k, c->p2l_nrm, &nrm));
+    kss_vmap* m = new (std::nothrow) kss_vmap();
+    if (!m) return KSS_ERR_NOMEM;
+    const int rc = vmap_build(c->stream, tgt, nrm, nt, 1.0f / (float)vp->leaf, m->b);
+    if (rc != 0) {
+        delete m;
+        if (rc == 1) return bad("no target with finite coordinates and normal, or a grid that is not finite or has more than 2^26 cells");
+        return rc == 2 ? set_err(c, KSS_ERR_NOMEM, "vmap_create: hipMalloc") : set_err(c, KSS_ERR_HIP, "vmap_create: the build failed");
+    }
+    m->ctx = c;
+    m->leaf = vp->leaf;
+    c->vmaps.push_back(m);
+    *out = m;
+    return KSS_OK;
+}
+int kss_vmap_create_dev(kss_ctx* c, const float* d_tgt, int64_t nt, const float* d_tgt_normals, const kss_vmap_params* vp, kss_vmap** out) {
+    return vmap_create_any(c, false, d_tgt, nt, d_tgt_normals, vp, out);
+}
+int kss_vmap_create(kss_ctx* c, const float* tgt, int64_t nt, const float* tgt_normals, const kss_vmap_params* vp, kss_vmap** out) {
+    return vmap_create_any(c, true, tgt, nt, tgt_normals, vp, out);
+}
+
+int kss_vmap_destroy(kss_ctx* c, kss_vmap* m) {
+    if (!c) return KSS_ERR_ARG;
+    if (!vmap_live(c, m)) return set_err(c, KSS_ERR_ARG, "vmap_destroy: not a live map of this context");
+    hipSetDevice(c->device);
+    hipStreamSynchronize(c->stream);
+    c->vmaps.erase(std::find(c->vmaps.begin(), c->vmaps.end(), m));
+    vmap_free(m->b);
+    delete m;
+    return KSS_OK;
+}
+
+int kss_vmap_info(const kss_vmap* m, double info[KSS_VMAP_NINFO]) {
+    if (!m || !info) return KSS_ERR_ARG;
+    info[0] = (double)m->b.mapped; info[1] = (double)m->b.nvox;
+    for (int a = 0; a < 3; ++a) { info[2 + a] = (double)m->b.dims[a]; info[6 + a] = (double)m->b.lo[a]; }
+    info[5] = m->leaf;
+    info[9] = (double)m->b.inv;
+    return KSS_OK;
+}
+
+int kss_vmap_read(kss_ctx* c, const kss_vmap* m, int64_t* lin, double* stats, int64_t capacity, int64_t* nvox) {
+    if (!c) return KSS_ERR_ARG;
+    if (!vmap_live(c, m)) return set_err(c, KSS_ERR_ARG, "vmap_read: not a live map of this context");
+    if (!nvox) return set_err(c, KSS_ERR_ARG, "vmap_read: null argument");
+    *nvox = m->b.nvox;
+    if (!lin && !stats) return KSS_OK;   // the count alone
+    if (capacity < m->b.nvox) return set_err(c, KSS_ERR_CAPACITY, "vmap_read: output buffer too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (lin) HIPCHK(c, hipMemcpyAsync(lin, m->b.lin, (size_t)m->b.nvox * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    if (stats) HIPCHK(c, hipMemcpyAsync(stats, m->b.rec, (size_t)m->b.nvox * KSS_VMAP_NSTAT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KSS_OK;
+}
+
+// what both the record and the loop check and stage: the source on the device with its normals, given or computed
+static int vgicp_enter(kss_ctx* c, const char* who, bool host, const float*& src, const float*& snrm, int64_t n, const kss_vmap* m,
+                       const kss_gicp_params* gp, const void* out) {
+    if (!c) return KSS_ERR_ARG;
+    const std::string w = std::string(who) + ": ";
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (w + what).c_str()); };
+    if (!src || !out) return bad("null argument");
+    if (!vmap_live(c, m)) return bad("not a live map of this context");
+    if (n <= 0) return bad("empty cloud");
+    if (n > 0x7fff0000ll) return bad("cloud too large");
+    KCHK(gicp_check(c, who, gp, !snrm));
+    HIPCHK(c, hipSetDevice(c->device));
+    if (host) {
+        const size_t sb = (size_t)n * 3 * sizeof(float);
+        KCHK(upload(c, c->stage_src, src, sb));
+        src = (const float*)c->stage_src.p;
+        if (snrm) {
+            KCHK(upload(c, c->gicp_snrm, snrm, sb));
+            snrm = (const float*)c->gicp_snrm.p;
+        }
+    }
+    if (!snrm) KCHK(cloud_normals_dev(c, src, n, gp->normals_k, c->gicp_snrm, &snrm));
+    return KSS_OK;
+}
+
+static int vgicp_sums_any(kss_ctx* c, bool host, const float* src, const float* snrm, int64_t n, const kss_vmap* m, double max_d2, const float* Rn,
+                          const kss_gicp_params* gp, double* sums) {
+    KCHK(vgicp_enter(c, "vgicp_sums", host, src, snrm, n, m, gp, sums));
+    return vgicp_record_dev(c, src, snrm, n, m, max_d2, Rn, gp->epsilon, sums);
+}
+int kss_vgicp_sums_dev(kss_ctx* c, const float* d_src, const float* d_src_normals, int64_t n, const kss_vmap* m, double max_d2, const float Rn[9],
+                       const kss_gicp_params* gp, double sums[KSS_P2L_NSUMS]) {
+    return vgicp_sums_any(c, false, d_src, d_src_normals, n, m, max_d2, Rn, gp, sums);
+}
+int kss_vgicp_sums(kss_ctx* c, const float* src, const float* src_normals, int64_t n, const kss_vmap* m, double max_d2, const float Rn[9],
+                   const kss_gicp_params* gp, double sums[KSS_P2L_NSUMS]) {
+    return vgicp_sums_any(c, true, src, src_normals, n, m, max_d2, Rn, gp, sums);
+}
+
+static int icp_vgicp_any(kss_ctx* c, bool host, const float* src, int64_t ns, const float* snrm, const kss_vmap* m, const kss_icp_params* p,
+                         const kss_gicp_params* gp, kss_icp_result* res, double* last_info) {
+    if (!c) return KSS_ERR_ARG;
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string("icp_vgicp: ") + what).c_str()); };
+    if (!p) return bad("null argument");
+    if (p->allreduce) return bad("the source-row split (allreduce) is not available for voxelized generalized ICP");
+    if (p->fitness_idx || p->fitness_d2) return bad("there are no correspondences to return: fitness_idx and fitness_d2 must be NULL");
+    KCHK(vgicp_enter(c, "icp_vgicp", host, src, snrm, ns, m, gp, res));
+    return vgicp_run_dev(c, src, ns, snrm, m, p, gp->epsilon, res, last_info);
+}
+int kss_icp_vgicp_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const kss_vmap* m, const kss_icp_params* p,
+                      const kss_gicp_params* gp, kss_icp_result* res, double last_info[KSS_VGICP_NINFO]) {
+    return icp_vgicp_any(c, false, d_src, ns, d_src_normals, m, p, gp, res, last_info);
+}
+int kss_icp_vgicp(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const kss_vmap* m, const kss_icp_params* p,
+                  const kss_gicp_params* gp, kss_icp_result* res, double last_info[KSS_VGICP_NINFO]) {
+    return icp_vgicp_any(c, true, src, ns, src_normals, m, p, gp, res, last_info);
 }
 
 // ---- symmetric ICP and its robust form -----------------------------

@@ -30,6 +30,16 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// A voxel map (kss_vmap_create): its own device arrays, never part of a context's grow-only workspace, so no other call on the
+// context can move or overwrite them.  The context lists its live maps: an entry point takes a handle only when it is on the
+// list of the context it is called on, and kss_ctx_destroy frees what is still listed.
+struct kss_vmap {
+    kss_ctx* ctx = nullptr;
+    VmapBuilt b;
+    double leaf = 0.0;
+    VmapDev dev() const { return VmapDev{b.cell, b.rec, {b.lo[0], b.lo[1], b.lo[2]}, b.inv, {b.dims[0], b.dims[1], b.dims[2]}}; }
+};
+
 struct kss_ctx {
     int device = 0;
     int cu_count = 0;                   // compute units of the device (0: not asked yet)
@@ -80,6 +90,7 @@ struct kss_ctx {
     void* h_gicp_dev = nullptr;   // (the pinned copy as the device sees it: KSS_GICP_TABLE_MAPPED, an A/B switch)
     const PairState* last_state_dev = nullptr;   // the per-pair state table the last batched NN pass read (null: none, a single pair)
     HostPool pool;   // per-pair host work of batched iterations
+    std::vector<kss_vmap*> vmaps;   // the live voxel maps created on this context (kss_vmap_create .. kss_vmap_destroy)
     std::vector<kss_ctx*> workers;   // contexts of kss_register_batch's worker threads (same device, own streams)
     std::vector<unsigned long long> last_stamps;
     int stamps_nblk = 0; unsigned long long stamps_seq = 0;   // KSS_GRID_STAMPS=2
@@ -296,6 +307,13 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
 int pair_record_dev(kss_ctx* c, const float* d_src, const float* d_tgt, const float* d_nrm, const int32_t* d_idx, int64_t n, int64_t nt,
                     double max_d2, const PairMode& mode, const float* Rn, double* sums, double* info);
 int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info);
+// voxelized generalized ICP (kss_vgicp_sums_dev, kss_icp_vgicp_dev; the entry points check their arguments): n packed float triples
+// d_src with the normals d_snrm against the map.  One record: rows + final launch, Rn as for pair_record_dev.  The loop:
+// kss_icp_gicp's host step on a pass of two launches and no NN pass; info: KSS_VGICP_NINFO doubles or null.
+int vgicp_record_dev(kss_ctx* c, const float* d_src, const float* d_snrm, int64_t n, const kss_vmap* map, double max_d2, const float* Rn,
+                     double epsilon, double* sums);
+int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* map, const kss_icp_params* p, double epsilon,
+                  kss_icp_result* res, double* info);
 // npairs >= 1 pairs in lockstep (kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch, kss_icp_gicp_batch,
 // kss_icp_symm_batch, kss_icp_symm_robust_batch -- symm with robust takes both symm_aligns and rscales): d_nrm laid
 // out like d_tgt; overlaps: one per pair (trimmed; M.overlap is not read); rscales: one per pair (robust; M.rs is not read), all

@@ -2366,6 +2366,83 @@ int pair_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_tgt,
     return pair_run_loop(c, pl, t0, guard, *p, M, d_tgt, d_nrm, true, false, res, M.last_info);
 }
 
+// ---- voxelized generalized ICP against a voxel map (kss_icp_vgicp) ----
+// No plan, no packed clouds, no cell list, no NN pass: a pass is VgicpMetric's rows launch -- which moves the sources by the last
+// step on the way in (pass k >= 1 reads the positions of pass k - 1, pass 1 the caller's cloud, and writes cur[k & 1]) -- and the plane
+// record's final launch into h_p2l, ONE synchronisation, then pair_host_step as for kss_icp_gicp (M.plane with M.gicp: the
+// Cholesky step, MSE = [28] / [0], the trace).  Nothing here touches a zero-at-rest buffer.
+// KSS_VGICP_UNFUSED=1 (A/B, tools/vgicp_time.py): the move as a launch of its own in front of a rows launch that does not move.
+static PairArgs vgicp_args(kss_ctx* c, const float* d_snrm, int64_t n, double max_d2) {
+    return PairArgs{{nullptr, nullptr, nullptr, nullptr, nullptr, d_snrm, max_d2}, nullptr, nullptr, n, 0, (double*)c->p2l_rows.p, nullptr};
+}
+static int vgicp_ensure(kss_ctx* c, int64_t n) {
+    KCHK(ensure(c, c->p2l_rows, (size_t)p2l_rows_blocks(n) * P2L_NSUMS * sizeof(double)));
+    return ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (P2L_NSUMS + KSS_TRIM_NINFO + 2) * sizeof(double));
+}
+// rows + final into h_p2l: T null: the positions d_in as they are; else moved by T (a row-major 4 x 4) into d_out first
+static int vgicp_pass_launch(kss_ctx* c, const PairArgs& a, const kss_vmap* map, const float* T, const float* d_in, float* d_out,
+                             const GicpRot& Rn, double epsilon, bool unfused) {
+    ProfScope ps(c, KSS_K_CORR_REDUCE);
+    VmapMove mv;
+    if (T) std::memcpy(mv.m, T, sizeof mv.m);
+    if (T && unfused) {
+        launch_transform_apply_f32(c->stream, T, d_in, a.n, d_out);
+        launch_vgicp_rows(c->stream, a, map->dev(), nullptr, d_out, nullptr, Rn, 1.0 - epsilon);
+    } else {
+        launch_vgicp_rows(c->stream, a, map->dev(), T ? &mv : nullptr, d_in, d_out, Rn, 1.0 - epsilon);
+    }
+    launch_p2l_final(c->stream, a.rows, stream_blocks(a.n), (double*)c->h_p2l_dev);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KSS_OK;
+}
+
+int vgicp_record_dev(kss_ctx* c, const float* d_src, const float* d_snrm, int64_t n, const kss_vmap* map, double max_d2, const float* Rn,
+                     double epsilon, double* sums) {
+    HIPCHK(c, hipSetDevice(c->device));
+    KCHK(vgicp_ensure(c, n));
+    KCHK(vgicp_pass_launch(c, vgicp_args(c, d_snrm, n, max_d2), map, nullptr, d_src, nullptr, gicp_rot_of(Rn), epsilon, false));
+    std::memcpy(sums, c->h_p2l, P2L_NSUMS * sizeof(double));
+    return KSS_OK;
+}
+
+int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* map, const kss_icp_params* p, double epsilon,
+                  kss_icp_result* res, double* info) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const kss_icp_params& P = *p;
+    const auto t0 = std::chrono::steady_clock::now();
+    KCHK(vgicp_ensure(c, ns));
+    for (DevBuf& b : c->cur) KCHK(ensure(c, b, (size_t)ns * 3 * sizeof(float)));
+    static const bool unfused = getenv("KSS_VGICP_UNFUSED") != nullptr && atoi(getenv("KSS_VGICP_UNFUSED")) != 0;
+    PairMode M;
+    M.plane = true; M.gicp = true;
+    const PairArgs a = vgicp_args(c, d_snrm, ns, P.max_corr_dist * P.max_corr_dist);
+    float* d_cur[2] = {(float*)c->cur[0].p, (float*)c->cur[1].p};   // pass k >= 1 writes [k & 1] and reads what pass k - 1 wrote
+    const double* hrec = (const double*)c->h_p2l;
+    PairTrack t(P);
+    double last[KSS_VGICP_NINFO] = {0.0, (double)ns, 0.0, (double)map->b.nvox};
+    if (P.trace_n) *P.trace_n = 0;
+    const auto t1 = std::chrono::steady_clock::now();
+    for (int it = 0; P.max_iterations > 0; ++it) {
+        // pass it works on T_{it-1} ... T_0 * source: the last step is applied on the way in
+        KCHK(vgicp_pass_launch(c, a, map, it == 0 ? nullptr : t.tk, it <= 1 ? d_src : d_cur[(it - 1) & 1], d_cur[it & 1], rot_of(t.fin), epsilon,
+                               unfused));
+        last[0] = hrec[0]; last[2] = hrec[30];
+        double unused[KSS_SIM_NINFO] = {};
+        if (!pair_host_step(P, M, hrec, unused, t, true)) break;
+    }
+    fill_result(*res, t.fin, t.iters, t.converged, t.state, t.last_mse, 0.0, 0);
+    if (P.compute_fitness) {   // one more evaluation at fin * source: [28] / [0], over the sources that have a voxel (kept ones)
+        KCHK(vgicp_pass_launch(c, a, map, t.fin, d_src, d_cur[0], rot_of(t.fin), epsilon, unfused));
+        res->fitness = hrec[28] / hrec[0];
+    }
+    if (info) std::memcpy(info, last, sizeof last);
+    const auto t2 = std::chrono::steady_clock::now();
+    c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return KSS_OK;
+}
+
 
 // tau / m / k / kept of n squared distances on the device (kss_trim_threshold_dev)
 int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info) {

@@ -186,7 +186,7 @@ size_t scan_scratch_bytes(int n) {
 }
 
 // clear: leave d_counts zeroed (the apply kernel writes the zeros; the library scan is followed by one memset)
-static void launch_scan(hipStream_t st, int32_t* d_counts, int ncells, int32_t* d_start, int32_t* d_scratch, bool clear) {
+void launch_scan(hipStream_t st, int32_t* d_counts, int ncells, int32_t* d_start, int32_t* d_scratch, bool clear) {
     static const bool lib = getenv("KSS_SCAN_LIB") != nullptr;   // A/B: rocPRIM's look-back scan for big tables
     if (lib && ncells > 1024 * SCAN_CHUNK) {
         size_t bytes = 0;

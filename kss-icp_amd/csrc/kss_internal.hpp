@@ -363,6 +363,38 @@ void launch_p2l_perm(hipStream_t st, const float4* d_src, int64_t n, int32_t* d_
 // one workgroup: the fixed-order column sums of the plane record's rows into d_out (device or host-mapped), slot 31 as 0
 void launch_p2l_final(hipStream_t st, const double* d_rows, int nrows, double* d_out);
 
+// ---- voxelized generalized ICP (kss_vmap.hip, kss_pair.hip) ----
+// A voxel map as the kernels see it, by value: the dense cell -> voxel table over dims[0] * dims[1] * dims[2] cells (-1: empty,
+// lin = (cz * dims[1] + cy) * dims[0] + cx), the packed voxel records in ascending lin and the float origin and 1 / leaf of
+// f_a = floorf((x_a - lo[a]) * inv).
+constexpr int VMAP_NSTAT = 10;                   // {N, mean x y z, S00 S01 S02 S11 S12 S22}
+constexpr int64_t VMAP_MAX_CELLS = 1ll << 26;
+static_assert(VMAP_NSTAT == KSS_VMAP_NSTAT, "kss_internal.hpp and include/kssicp.h disagree");
+struct VmapDev {
+    const int32_t* cell; const double* rec;
+    float lo[3]; float inv;
+    int dims[3];
+};
+struct VmapMove { float m[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}; };   // the upper three rows of a row-major float 4 x 4
+// What the build hands back: the device arrays the map owns (hipMalloc, freed by the caller) and its header.
+struct VmapBuilt {
+    int32_t* cell = nullptr; double* rec = nullptr; int64_t* lin = nullptr;
+    int64_t mapped = 0, nvox = 0;
+    int dims[3] = {0, 0, 0};
+    float lo[3] = {0, 0, 0}, inv = 0;
+};
+// The build: eleven to thirteen launches and three synchronisations on st; its scratch is allocated and freed inside.  0: built; 1: no mapped
+// target, or a grid that is not finite or has more than VMAP_MAX_CELLS cells; 2: out of memory; 3: a HIP error (1 - 3: nothing is held).
+int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t nt, float inv, VmapBuilt& out);
+void vmap_free(VmapBuilt& b);
+struct GicpRot;
+// one rows launch of pair_rows_kernel over VgicpMetric: a.n sources (packed float triples d_in, normals a.s.sn) against the map;
+// T set: every source is first moved by *T and stored to d_out (not d_in)
+void launch_vgicp_rows(hipStream_t st, const PairArgs& a, const VmapDev& v, const VmapMove* T, const float* d_in, float* d_out, const GicpRot& Rn,
+                       double e);
+// exclusive scan of d_counts[0 .. n) into d_start[0 .. n] (kss_grid.hip); d_scratch holds scan_scratch_bytes(n)
+void launch_scan(hipStream_t st, int32_t* d_counts, int ncells, int32_t* d_start, int32_t* d_scratch, bool clear);
+
 // ---- trimmed ICP (kss_trim.hip) ----
 // What one digit of the radix select hands to the next, and the last one to the sums kernels of the same pass: the key
 // prefix found so far, the rank inside the keys that carry it, m candidates, k = trim_rank_of(m, overlap); after the last digit

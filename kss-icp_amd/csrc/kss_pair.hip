@@ -1,6 +1,7 @@
 // kss_pair.hip -- the correspondence sums of the pair metrics for ONE pair: point-to-plane (pcl::registration::
 // TransformationEstimationPointToPlaneLLS, PCL 1.8.1), trimmed (2.10), robust (2.12), generalized (2.14), symmetric
-// (2.16), robust symmetric (2.19) and similarity ICP (2.22); the definitions are restated in include/kssicp.h.
+// (2.16), robust symmetric (2.19), similarity ICP (2.22) and voxelized generalized ICP against a voxel map (2.30; the map itself is
+// kss_vmap.hip's); the definitions are restated in include/kssicp.h.
 //   pair_rows_kernel<M, SRC>  the one rows kernel: pair_walk (kss_pair_device.hpp) over the metric functor M with
 //                             the sources from SRC.  Grid of stream_blocks(n) workgroups of 256, lane t of workgroup b takes the
 //                             sources b * 256 + t + k * 256 * grid in ORIGINAL index order, then block_sum's wave tree and fixed
@@ -55,6 +56,17 @@ KSS_PAIR_METRIC(SymmMetric<PAIR_PLAIN>);
 KSS_PAIR_METRIC(SymmMetric<PAIR_ROBUST>);
 KSS_PAIR_METRIC(SymmMetric<PAIR_KEY>);
 #undef KSS_PAIR_METRIC
+
+// voxelized generalized ICP: the same kernel over VgicpMetric, which has the packed-triple form only
+template <bool MOVE>
+void launch_vgicp_rows(hipStream_t st, const PairArgs& a, const VgicpMetric<MOVE>& m) {
+    hipLaunchKernelGGL((pair_rows_kernel<VgicpMetric<MOVE>, SRC_F3>), dim3(stream_blocks(a.n)), dim3(P2L_THREADS), 0, st, a, m);
+}
+void launch_vgicp_rows(hipStream_t st, const PairArgs& a, const VmapDev& v, const VmapMove* T, const float* d_in, float* d_out, const GicpRot& Rn,
+                       double e) {
+    if (T) launch_vgicp_rows<true>(st, a, VgicpMetric<true>(v, *T, d_in, d_out, Rn, e));
+    else launch_vgicp_rows<false>(st, a, VgicpMetric<false>(v, VmapMove(), d_in, nullptr, Rn, e));
+}
 
 // ---- the final launches -----------------------------------------------------------------------------------------------------
 // the rows' column sums in p2l_rows_column_sum's fixed order (kss_pair_device.hpp); slot 31 is written as 0

@@ -1,7 +1,8 @@
 // kss_pair_device.hpp -- the device code of the pair metrics (point-to-plane, trimmed, robust, generalized, symmetric and robust
-// symmetric ICP, similarity ICP), for one pair (kss_pair.hip) and for many pairs per call (kss_pairb.hip):
+// symmetric ICP, similarity ICP, voxelized generalized ICP), for one pair (kss_pair.hip) and for many pairs per call (kss_pairb.hip):
 //   p2l_source / trim_point_source   what one source adds to its lane's accumulators (plane / point metric),
 //   gicp_source / symm_source        the same for generalized and for symmetric ICP,
+//   vgicp_source                     the same for voxelized generalized ICP: the voxel is looked up from the source's position,
 //   sim_point_source                 the same for similarity ICP (the point metric and the kept sources' sum of squares),
 //   the metric functors              one small struct per metric: the uniform parameters of a pass and the call of its body,
 //   pair_walk                        the ONE walk both forms run: a lane's sources in steps of the grid, the functor's body per
@@ -110,6 +111,43 @@ __device__ __forceinline__ void p2l_source(double (&acc)[P2L_NSUMS], const float
 }
 
 // ---- generalized ICP ------------------------------------------------------------------------------------
+// What one kept correspondence adds to the record: its metric M (upper triangle), the source's widened position p, d = q - p and
+// the pass's squared distance d2 for slot [28].  Shared by gicp_source (q a target point) and vgicp_source (q a voxel's mean).
+__device__ __forceinline__ void gicp_accumulate(double (&acc)[P2L_NSUMS], const double (&M)[6], double px, double py, double pz, double d0,
+                                                double d1, double dz, double d2) {
+    // M as rows (symmetric)
+    const double Mr[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
+    double u[3], B[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) u[a] = (Mr[a][0] * d0 + Mr[a][1] * d1) + Mr[a][2] * dz;
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        B[0][b] = py * Mr[2][b] - pz * Mr[1][b];
+        B[1][b] = pz * Mr[0][b] - px * Mr[2][b];
+        B[2][b] = px * Mr[1][b] - py * Mr[0][b];
+    }
+    acc[0] += 1.0;
+    // row 0: UL00 UL01 UL02 B00 B01 B02; row 1: UL11 UL12 B10 B11 B12; row 2: UL22 B20 B21 B22; then M
+    acc[1] += B[0][2] * py - B[0][1] * pz;
+    acc[2] += B[0][0] * pz - B[0][2] * px;
+    acc[3] += B[0][1] * px - B[0][0] * py;
+    acc[4] += B[0][0]; acc[5] += B[0][1]; acc[6] += B[0][2];
+    acc[7] += B[1][0] * pz - B[1][2] * px;
+    acc[8] += B[1][1] * px - B[1][0] * py;
+    acc[9] += B[1][0]; acc[10] += B[1][1]; acc[11] += B[1][2];
+    acc[12] += B[2][1] * px - B[2][0] * py;
+    acc[13] += B[2][0]; acc[14] += B[2][1]; acc[15] += B[2][2];
+    acc[16] += M[0]; acc[17] += M[1]; acc[18] += M[2];
+    acc[19] += M[3]; acc[20] += M[4];
+    acc[21] += M[5];
+    acc[22] += py * u[2] - pz * u[1];
+    acc[23] += pz * u[0] - px * u[2];
+    acc[24] += px * u[1] - py * u[0];
+    acc[25] += u[0]; acc[26] += u[1]; acc[27] += u[2];
+    acc[28] += d2;
+    acc[30] += (d0 * u[0] + d1 * u[1]) + dz * u[2];
+}
+
 // Source i as in p2l_source, with the source's own normal sn[3 * i ..] (by ORIGINAL index; in a batch the global one) turned by Rn: the definition at
 // kss_icp_gicp in include/kssicp.h.  The 6 x 6 block A^T M A of A = [ -[p]x | I ] is formed by blocks -- lower right M, upper
 // right B = [p]x M, upper left B [p]x^T -- and not by a generic triple product: 54 f64 multiplications instead of 162.
@@ -140,39 +178,45 @@ __device__ __forceinline__ void gicp_source(double (&acc)[P2L_NSUMS], const floa
         for (int k = 0; k < 3; ++k) m[k] = ((double)Rn.r[3 * k] * us[0] + (double)Rn.r[3 * k + 1] * us[1]) + (double)Rn.r[3 * k + 2] * us[2];
         if (!gicp_metric_of(nq, m, e, M)) return;
         const double px = (double)sx, py = (double)sy, pz = (double)sz;
-        const double d0 = (double)qx - px, d1 = (double)qy - py, dz = (double)qz - pz;
-        // M as rows (symmetric)
-        const double Mr[3][3] = {{M[0], M[1], M[2]}, {M[1], M[3], M[4]}, {M[2], M[4], M[5]}};
-        double u[3], B[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) u[a] = (Mr[a][0] * d0 + Mr[a][1] * d1) + Mr[a][2] * dz;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            B[0][b] = py * Mr[2][b] - pz * Mr[1][b];
-            B[1][b] = pz * Mr[0][b] - px * Mr[2][b];
-            B[2][b] = px * Mr[1][b] - py * Mr[0][b];
-        }
-        acc[0] += 1.0;
-        // row 0: UL00 UL01 UL02 B00 B01 B02; row 1: UL11 UL12 B10 B11 B12; row 2: UL22 B20 B21 B22; then M
-        acc[1] += B[0][2] * py - B[0][1] * pz;
-        acc[2] += B[0][0] * pz - B[0][2] * px;
-        acc[3] += B[0][1] * px - B[0][0] * py;
-        acc[4] += B[0][0]; acc[5] += B[0][1]; acc[6] += B[0][2];
-        acc[7] += B[1][0] * pz - B[1][2] * px;
-        acc[8] += B[1][1] * px - B[1][0] * py;
-        acc[9] += B[1][0]; acc[10] += B[1][1]; acc[11] += B[1][2];
-        acc[12] += B[2][1] * px - B[2][0] * py;
-        acc[13] += B[2][0]; acc[14] += B[2][1]; acc[15] += B[2][2];
-        acc[16] += M[0]; acc[17] += M[1]; acc[18] += M[2];
-        acc[19] += M[3]; acc[20] += M[4];
-        acc[21] += M[5];
-        acc[22] += py * u[2] - pz * u[1];
-        acc[23] += pz * u[0] - px * u[2];
-        acc[24] += px * u[1] - py * u[0];
-        acc[25] += u[0]; acc[26] += u[1]; acc[27] += u[2];
-        acc[28] += d2;
-        acc[30] += (d0 * u[0] + d1 * u[1]) + dz * u[2];
+        gicp_accumulate(acc, M, px, py, pz, (double)qx - px, (double)qy - py, (double)qz - pz, d2);
     }
+}
+
+// ---- voxelized generalized ICP ---------------------------------------------------------------------------
+// Source i against the voxel map v: the definition at kss_icp_vgicp in include/kssicp.h.  No idx is read: the voxel is looked up
+// from the source's own position -- f_a = floorf((p_a - lo_a) * inv), the build's expression, compared in float so that a NaN
+// has no voxel -- and the voxel's mean and average n n^T stand where gicp_source has q and nq nq^T.  MOVE: the position read
+// from `in` is first moved by the float 3 x 4 T as transform_apply_f32_kernel moves it and stored to `out` (another array), so a
+// pass needs no launch for the move.
+template <bool MOVE>
+__device__ __forceinline__ void vgicp_source(double (&acc)[P2L_NSUMS], const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ sn,
+                                             const VmapDev& v, const VmapMove& T, int64_t i, double max_d2, const GicpRot& Rn, double e) {
+    float sx = in[3 * i], sy = in[3 * i + 1], sz = in[3 * i + 2];
+    if constexpr (MOVE) {
+        const float x = sx, y = sy, z = sz;
+        sx = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+        sy = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+        sz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+        out[3 * i] = sx; out[3 * i + 1] = sy; out[3 * i + 2] = sz;
+    }
+    const float fx = floorf((sx - v.lo[0]) * v.inv), fy = floorf((sy - v.lo[1]) * v.inv), fz = floorf((sz - v.lo[2]) * v.inv);
+    if (!(fx >= 0.0f && fx < (float)v.dims[0] && fy >= 0.0f && fy < (float)v.dims[1] && fz >= 0.0f && fz < (float)v.dims[2])) return;
+    const int32_t vox = v.cell[((int64_t)fz * v.dims[1] + (int64_t)fy) * v.dims[0] + (int64_t)fx];   // (inside the table: the test above)
+    if (vox < 0) return;
+    const float ux = sn[3 * i], uy = sn[3 * i + 1], uz = sn[3 * i + 2];
+    if (!(isfinite(ux) && isfinite(uy) && isfinite(uz))) return;
+    const double* __restrict__ rec = v.rec + (int64_t)vox * VMAP_NSTAT;   // {N, mean x y z, S00 S01 S02 S11 S12 S22}
+    const double px = (double)sx, py = (double)sy, pz = (double)sz;
+    const double d0 = rec[1] - px, d1 = rec[2] - py, dz = rec[3] - pz;
+    const double dd = (d0 * d0 + d1 * d1) + dz * dz;
+    if (dd > max_d2) return;
+    const double us[3] = {(double)ux, (double)uy, (double)uz};
+    const double Q[6] = {rec[4], rec[5], rec[6], rec[7], rec[8], rec[9]};
+    double m[3], M[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) m[k] = ((double)Rn.r[3 * k] * us[0] + (double)Rn.r[3 * k + 1] * us[1]) + (double)Rn.r[3 * k + 2] * us[2];
+    if (!gicp_metric_of_g(Q, m, e, M)) return;
+    gicp_accumulate(acc, M, px, py, pz, d0, d1, dz, dd);
 }
 
 // ---- symmetric ICP --------------------------------------------------------------------------------------
@@ -571,6 +615,25 @@ struct GicpMetric {   // generalized: the rotation applied to the source normals
     template <int SRC>
     __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float* tgt, const float* nrm, int64_t i, int64_t nt, float*) const {
         gicp_source<SRC>(acc, s.src3, s.src4, s.perm, s.idx, s.d2, s.sn, tgt, nrm, i, nt, s.max_d2, Rn, e);
+    }
+};
+template <bool MOVE>
+struct VgicpMetric {   // voxelized generalized: the map, GicpMetric's rotation and e, and (MOVE) the step the sources take on the way in
+    static constexpr int NC = P2L_NSUMS;
+    static constexpr bool KEYS = false, F3 = true;
+    VmapDev v;
+    VmapMove T;
+    const float* in;   // packed float triples by original index: the positions before the move
+    float* out;        // MOVE: where the moved positions go (not `in`)
+    GicpRot Rn;
+    double e;
+    VgicpMetric(const VmapDev& v_, const VmapMove& T_, const float* in_, float* out_, const GicpRot& Rn_, double e_)
+        : v(v_), T(T_), in(in_), out(out_), Rn(Rn_), e(e_) {}
+    __device__ void begin() {}
+    template <int SRC>
+    __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float*, const float*, int64_t i, int64_t, float*) const {
+        static_assert(SRC == SRC_F3, "the voxel lookup reads packed float triples");
+        vgicp_source<MOVE>(acc, in, out, s.sn, v, T, i, s.max_d2, Rn, e);
     }
 };
 template <int MODE>
