@@ -70,7 +70,7 @@ int kss_ctx_destroy(kss_ctx* c) {
     DevBuf* bufs[] = {&c->tgt4, &c->src0, &c->cur[0], &c->cur[1], &c->keys, &c->partials, &c->sums, &c->nn_work,
                       &c->red_work, &c->pair_red, &c->state, &c->cs, &c->scratch_a, &c->scratch_b, &c->scratch_c,
                       &c->stage_src, &c->stage_tgt, &c->stage_idx, &c->stage_d2, &c->stage_out, &c->g_counts, &c->g_slot, &c->g_start,
-                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp, &c->o2o_table, &c->o2o_idx, &c->o2o_d2, &c->recip_sorted, &c->recip_box, &c->recip_grids};
+                      &c->g_cursor, &c->g_bsums, &c->g_sorted, &c->g_list, &c->g_count, &c->g_bbox, &c->g_partials, &c->g_start2, &c->g_pairs, &c->g_stamps, &c->g_pos, &c->g_nnst, &c->res_pos, &c->res_wc, &c->res_perm, &c->pack_seg, &c->reg_s, &c->reg_t, &c->reg_p, &c->reg_all, &c->reg_f, &c->reg_g, &c->oct_pts, &c->oct_cen, &c->oct_a, &c->oct_b, &c->oct_tmp, &c->pre_partials, &c->pre_state, &c->g_rowpair, &c->g_gate, &c->p2l_idx, &c->p2l_d2, &c->p2l_perm, &c->p2l_rows, &c->p2l_nrm, &c->p2l_n64, &c->trim_rows, &c->trim_state, &c->rob_keys, &c->gicp_snrm, &c->pb_desc, &c->pb_rowpair, &c->pb_nrm, &c->pb_rscale, &c->pb_snrm, &c->pb_gicp, &c->o2o_table, &c->o2o_idx, &c->o2o_d2, &c->recip_sorted, &c->recip_box, &c->recip_grids, &c->gate_bar, &c->res_gate, &c->bar_state};
     for (DevBuf* b : bufs)
         if (b->p) hipFree(b->p);
     if (c->h_sums) hipHostFree(c->h_sums);
@@ -79,9 +79,6 @@ int kss_ctx_destroy(kss_ctx* c) {
     if (c->h_gicp) hipHostFree(c->h_gicp);
     if (c->h_box) hipHostFree(c->h_box);
     if (c->h_xf) hipHostFree(c->h_xf);
-    if (c->gate_bar) hipFree(c->gate_bar);
-    if (c->res_gate) hipFree(c->res_gate);
-    if (c->bar_state) hipFree(c->bar_state);
     if (c->h_state) hipHostFree(c->h_state);
     for (kss_vmap* m : c->vmaps) { vmap_free(m->b); delete m; }   // voxel maps still alive go with their context (include/kssicp.h)
     c->vmaps.clear();

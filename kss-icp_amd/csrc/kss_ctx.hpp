@@ -29,6 +29,7 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
 };
+struct BarBuf : DevBuf { bool failed = false; };   // fine-grained device memory the host stores into (bar_ensure)
 
 // A voxel map (kss_vmap_create): its own device arrays, never part of a context's grow-only workspace, so no other call on the
 // context can move or overwrite them.  The context lists its live maps: an entry point takes a handle only when it is on the
@@ -131,10 +132,10 @@ struct kss_ctx {
     PairState* h_xf = nullptr; PairState* h_xf_dev = nullptr;
     bool fit_last = false;            // the fitness pass: PairState::pad[0] names the buffer of each pair's last pass
     bool nn_have = false;             // the cell-list pass has written nn_win / nn_state for the current lists
-    PairState* bar_state = nullptr; int bar_state_cap = 0; bool bar_state_failed = false;   // batched pass: per-pair states, same kind of memory
-    unsigned int* gate_bar = nullptr;   // fine-grained device memory the host stores into through the BAR (large-BAR systems)
-    unsigned int* res_gate = nullptr; int res_gate_cap = 0; bool res_gate_failed = false;   // pair-resident engine: one 128-byte gate record per pair, same kind of memory
-    unsigned res_launches = 0;          // ... its launches so far (every launch has its own range of gate stamps)
+    // the single pair's two gate records, 128 bytes apart; the pair-resident engines' 128-byte record per pair; the batched pass's per-pair states
+    BarBuf gate_bar, res_gate, bar_state;
+    int large_bar = -1;                 // the device property, asked once per context (-1: not yet)
+    unsigned res_launches = 0;          // the pair-resident engines' launches so far (every launch has its own range of gate stamps)
     double res_passes = 0.0;            // ... (pair, pass) units its profiled launches ran
     int cand_cap = 0, cand_cap_pad = -1, cand_cap_fma = -1;   // candidate-resident kernel: workgroups resident at once for this target size
     // kss_register runs the judge ICP and the candidate ICPs as ONE speculative batch: pair spec_judge is the judge; once its
@@ -191,6 +192,30 @@ static inline int ensure_zeroed(kss_ctx* c, DevBuf& b, size_t bytes) {
     if (rc != KSS_OK) return rc;
     if (b.cap != before && hipMemsetAsync(b.p, 0, b.cap, c->stream) != hipSuccess) return set_err(c, KSS_ERR_HIP, "hipMemsetAsync(zero-at-rest buffer)");
     return KSS_OK;
+}
+
+// At least `bytes` of fine-grained device memory the host can store into directly; null without a large BAR, with KSS_GATE_BAR=0,
+// or after a failure (latched: the caller's other form runs from then on).  Growing waits for the stream first (nothing may still
+// read the old block); a new block is zeroed, and a device-wide synchronise puts the zeroes there before the host's first store
+// (on allocation only).  bar_state needs no zeroes -- mirror_state stores every entry before a kernel reads it -- and gets them too.
+inline void* bar_ensure(kss_ctx* c, BarBuf& b, size_t bytes) {
+    static const bool want_bar = getenv("KSS_GATE_BAR") == nullptr || atoi(getenv("KSS_GATE_BAR")) != 0;
+    if (!want_bar || b.failed) return nullptr;
+    if (b.p && b.cap >= bytes) return b.p;
+    hipDeviceProp_t prop;
+    if (c->large_bar < 0) c->large_bar = hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.isLargeBar ? 1 : 0;
+    if (b.p) { hipStreamSynchronize(c->stream); hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    const size_t cap = (bytes + bytes / 4 + 4095) / 4096 * 4096;
+    void* p = nullptr;
+    if (!c->large_bar || hipExtMallocWithFlags(&p, cap, hipDeviceMallocFinegrained) != hipSuccess || !p || hipMemset(p, 0, cap) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) hipFree(p);
+        b.failed = true;
+        return nullptr;
+    }
+    b.p = p; b.cap = cap;
+    return p;
 }
 
 static inline int ensure_pinned(kss_ctx* c, void*& p, size_t& cap, size_t bytes) {

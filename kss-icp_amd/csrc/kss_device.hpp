@@ -91,8 +91,6 @@ __device__ __forceinline__ double rows_column_sum(const double* __restrict__ row
 // start at 1).  A reducer that waits inside its launch holds a workgroup slot while it polls: it may wait there only where
 // the launch has at most one waiter per compute unit -- the other workgroups never wait, so they all get to run (HIP
 // promises no dispatch order).  Otherwise the rows are added up by the next launch.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 // granule `col` of a row: `row` is the same in every lane (a scalar base; the lane's offset is formed inside the asm, where
 // the compiler cannot hoist it and keep it live across the kernel: two registers and one wave per SIMD in cand_pass_kernel)
 __device__ __forceinline__ void row_put(Granule* row, int col, double v, unsigned long long seq) {
@@ -166,7 +164,7 @@ __device__ __forceinline__ bool rows_total(const Granule* __restrict__ rows, int
 
 // One published value: {bits(v), low word of seq, check word of those three} as ONE aligned 16-byte system-scope store into
 // host-mapped memory (slot `slot` of pub).  The host takes a slot when the number matches and the check word fits, so no
-// flag has to be ordered after the data and no L2 write-back is needed.  torn_xor != 0 (test hook only): the bits are
+// flag has to be ordered after the data and no L2 write-back is needed (the reader: slots_collect, kss_handover.hpp).  torn_xor != 0 (test hook only): the bits are
 // stored altered, the check word of the true ones -- a slot as a torn read would see it.
 __device__ __forceinline__ void pub_put(unsigned long long* pub, int64_t slot, double v, unsigned long long seq, unsigned torn_xor = 0u) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);

@@ -520,29 +520,12 @@ static int ensure_pub(kss_ctx* c, int npairs) {
 // without progress it falls back to the stream sync, which also surfaces a faulted kernel instead of spinning forever.
 static void gated_cancel(kss_ctx* c);
 
-// A result slot is ONE 16-byte device store {bits of the f64, low half of the launch number, check word of those three}.  The
-// host reads it as two 8-byte loads; it takes the value when the number matches AND the check word fits the bits it read -- a
-// slot seen torn (new number, old bits or the reverse) fails the check and is simply read again.
-static inline bool slot_value(const unsigned long long* sl, int k, unsigned long long want, unsigned long long* bits_out) {
-    const unsigned long long w = __atomic_load_n(&sl[2 * k + 1], __ATOMIC_ACQUIRE);
-    if ((unsigned)w != (unsigned)want) return false;
-    const unsigned long long bits = __atomic_load_n(&sl[2 * k], __ATOMIC_RELAXED);
-    if ((unsigned)(w >> 32) != kss_mix3((unsigned)bits, (unsigned)(bits >> 32), (unsigned)w)) return false;
-    *bits_out = bits;
-    return true;
-}
-
-// the 20 sums of pair p of launch `want`, if they have all landed
+// the 20 sums of pair p of launch `want`, if they have all landed (the slots' format and their reader: kss_handover.hpp)
 static inline bool collect_pair(kss_ctx* c, int p, unsigned long long want) {
     const unsigned long long* sl = c->h_seq + (size_t)2 * NSUMS * p;
-    unsigned long long bits;
-    if (!slot_value(sl, NSUMS - 1, want, &bits)) return false;   // the highest slot is usually the last to land
     double* out = (double*)c->h_sums + (size_t)NSUMS * p;
-    for (int k = NSUMS - 1; k >= 0; --k) {
-        if (!slot_value(sl, k, want, &bits)) return false;
-        std::memcpy(&out[k], &bits, sizeof(double));
-    }
-    return true;
+    if (!slots_collect(sl + 2 * (NSUMS - 1), 1, want, out + NSUMS - 1)) return false;   // the highest slot is usually the last to land
+    return slots_collect(sl, NSUMS, want, out);
 }
 
 // wait for pair p's sums (spin; after ~2 ms without them: open any gate, synchronize the stream, look once more)
@@ -579,20 +562,12 @@ static int wait_seq(kss_ctx* c, int npairs = 1, unsigned long long want = 0, con
 int ensure_pub_slots(kss_ctx* c) { return ensure_pub(c); }
 int wait_slots(kss_ctx* c, int nslots, double* out) {
     const unsigned long long want = c->seq;
-    auto collect = [&]() -> bool {
-        for (int k = nslots - 1; k >= 0; --k) {
-            unsigned long long bits;
-            if (!slot_value(c->h_seq, k, want, &bits)) return false;
-            std::memcpy(&out[k], &bits, sizeof(double));
-        }
-        return true;
-    };
     for (long spin = 0; spin < 2000000; ++spin) {
-        if (collect()) return KSS_OK;
+        if (slots_collect(c->h_seq, nslots, want, out)) return KSS_OK;
         __builtin_ia32_pause();
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));   // surfaces a faulted kernel instead of spinning forever
-    if (!collect()) return set_err(c, KSS_ERR_HIP, "kernel finished without publishing its result");
+    if (!slots_collect(c->h_seq, nslots, want, out)) return set_err(c, KSS_ERR_HIP, "kernel finished without publishing its result");
     return KSS_OK;
 }
 
@@ -620,19 +595,10 @@ static bool gated_available(kss_ctx* c) {
         // the device-side granules: on a large-BAR system in FINE-GRAINED device memory, which the host can store into directly
         // (tools/bar_probe.hip: same 2.1 us host -> kernel -> host round trip as a kernel polling host memory, but every
         // workgroup can poll it: no asking workgroup, no re-publication hop).  KSS_GATE_BAR=0: always the re-publishing form.
-        static const bool want_bar = getenv("KSS_GATE_BAR") == nullptr || atoi(getenv("KSS_GATE_BAR")) != 0;
-        hipDeviceProp_t prop;
-        void* bar = nullptr;
-        if (want_bar && hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.isLargeBar &&
-            hipExtMallocWithFlags(&bar, 4096, hipDeviceMallocFinegrained) == hipSuccess && bar) {
-            if (hipMemset(bar, 0, 4096) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
-                c->gate_bar = (unsigned int*)bar;
-                c->gated.supported = 1;
-                return true;
-            }
-            hipFree(bar);
+        if (bar_ensure(c, c->gate_bar, 256)) {   // two records, 128 bytes apart
+            c->gated.supported = 1;
+            return true;
         }
-        (void)hipGetLastError();
         void *x = nullptr, *xd = nullptr;
         if (ensure(c, c->g_gate, 256) == KSS_OK && hipMemsetAsync(c->g_gate.p, 0, 256, c->stream) == hipSuccess &&
             hipHostMalloc(&x, 2 * sizeof(PairState), hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(&xd, x, 0) == hipSuccess) {
@@ -648,32 +614,15 @@ static bool gated_available(kss_ctx* c) {
 }
 
 static void gated_release(kss_ctx* c, const PairState& st, int skip) {   // transform (or the cancel mark), stamped
-    if (c->gate_bar) {
-        // five 16-byte granules {3 words, stamp} straight into device memory through the BAR; each is one aligned 16-byte
-        // store (never seen torn), so their order does not matter; the fence pushes them out of the write-combining buffers
-        int words[16];
+    if (c->gate_bar.p) {
+        // the record straight into device memory through the BAR (kss_handover.hpp)
+        unsigned words[16];
         std::memcpy(words, &st, sizeof st);
-        words[14] = skip;                       // pad[0]
-        unsigned int* slot = c->gate_bar + 32 * c->gated.slot;   // two records, 128 bytes apart
-        // (test hook: the n-th record first arrives with a granule whose words do not fit its check -- what a torn 16-byte
-        // store would look like -- and only a while later as it should be; the kernel must not take the first for data)
+        words[14] = (unsigned)skip;             // pad[0]
+        // (test hook: the n-th record of the process first arrives torn)
         static const long torn_at = getenv("KSS_TEST_TORN_GATE") ? atol(getenv("KSS_TEST_TORN_GATE")) : -1;
         static long released = 0;
-        const bool torn = ++released == torn_at;
-        for (int pass = torn ? 0 : 1; pass < 2; ++pass) {
-            for (int g = 0; g < 5; ++g) {
-                // the stamp word carries the check of the granule's three data words
-                const unsigned tag = (unsigned)c->gated.stamp + kss_mix3((unsigned)words[3 * g], (unsigned)words[3 * g + 1], (unsigned)words[3 * g + 2]);
-                const int w1 = pass == 0 && g == 1 ? words[3 * g + 1] ^ 0x00010000 : words[3 * g + 1];
-                const __m128i v = _mm_set_epi32((int)tag, words[3 * g + 2], w1, words[3 * g]);
-                _mm_store_si128((__m128i*)(slot + 4 * g), v);
-            }
-            _mm_sfence();
-            if (pass == 0) {
-                const auto t0 = std::chrono::steady_clock::now();
-                while (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() < 200.0) __builtin_ia32_pause();
-            }
-        }
+        gate_record_store((unsigned*)c->gate_bar.p + 32 * c->gated.slot, words, (unsigned)c->gated.stamp, ++released == torn_at);   // two records, 128 bytes apart
     } else {
         PairState* rec = &c->h_xf[c->gated.slot];
         for (int k = 0; k < 12; ++k) rec->m[k] = st.m[k];
@@ -817,7 +766,7 @@ static void grid_enqueue_next(kss_ctx* c, const GridPass& g) {
     // chain is bracketed as a whole instead.
     static const bool want_chain = getenv("KSS_CHAIN") == nullptr || atoi(getenv("KSS_CHAIN")) != 0;
     int len = 1;
-    if (G.want_next && !G.pending && g.plain_args && gated_available(c) && want_chain && c->gate_bar &&
+    if (G.want_next && !G.pending && g.plain_args && gated_available(c) && want_chain && c->gate_bar.p &&
         (g.pl.total_rows <= resident_rows_limit(c) || g.pl.total_rows == 1))   // (every workgroup of a chain waits at its gates: resident at once)
         len = std::max(1, std::min(G.max_steps, 1 << 16));
     if (!(G.want_next && !G.pending && g.plain_args && gated_available(c) && (len > 1 || !next_sampled))) return;
@@ -830,9 +779,9 @@ static void grid_enqueue_next(kss_ctx* c, const GridPass& g) {
     PassArgs n = pass_args(c, g.pl, g.d_out, nxt_out, g.max_d2, nullptr, nullptr);
     n.ps0 = ((const PairState*)c->h_state)[0];
     n.gate_seq = G.stamp;
-    if (c->gate_bar) {   // the host writes the granules itself
+    if (c->gate_bar.p) {   // the host writes the granules itself
         n.state = nullptr;
-        n.gate_dev = c->gate_bar;    // two records, 128 bytes apart: pass k of the launch polls record (slot + k) & 1
+        n.gate_dev = (unsigned int*)c->gate_bar.p;    // two records, 128 bytes apart: pass k of the launch polls record (slot + k) & 1
         n.gate_slot = G.slot;
         n.chain_len = len;
         n.src_alt = g.d_out;
@@ -981,12 +930,12 @@ static int nn_pass_gridb(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* 
     // workgroups) gets the table copied to device memory once per pass.
     PassArgs a = pass_args(c, pl, d_in, d_out, max_d2, d_idx_out, d_d2_out);
     a.state = (const PairState*)c->state.p;
-    if (c->bar_state && c->bar_state_cap >= pl.npairs) {   // the host has stored the states there itself (mirror_state)
+    if (c->bar_state.p && c->bar_state.cap >= (size_t)pl.npairs * sizeof(PairState)) {   // the host has stored the states there itself (mirror_state)
         _mm_sfence();
-        a.state = c->bar_state;
+        a.state = (const PairState*)c->bar_state.p;
     }
     constexpr int host_state_rows = 32768;   // (measured at C3, 20480 workgroups: 9.71 ms from host memory vs 9.85 ms with the copy)
-    if (a.state != c->bar_state && pl.total_rows <= host_state_rows) {
+    if (a.state != (const PairState*)c->bar_state.p && pl.total_rows <= host_state_rows) {
         void* dev = nullptr;
         if (hipHostGetDevicePointer(&dev, c->h_state, 0) == hipSuccess && dev) a.state = (const PairState*)dev;
     }
@@ -1088,25 +1037,6 @@ static int nn_pass(kss_ctx* c, const IcpPlan& pl, bool fma, const float4* d_in, 
     return nn_pass_brute(c, pl, fma, d_in, d_out, max_d2, d_idx_out, d_d2_out, active);
 }
 
-// the batched pass's per-pair state table in fine-grained device memory the host can store into (null: no large BAR)
-static PairState* bar_state_table(kss_ctx* c, int npairs) {
-    static const bool want_bar = getenv("KSS_GATE_BAR") == nullptr || atoi(getenv("KSS_GATE_BAR")) != 0;
-    if (!want_bar || c->bar_state_failed) return nullptr;
-    if (c->bar_state && c->bar_state_cap >= npairs) return c->bar_state;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess || !prop.isLargeBar) { c->bar_state_failed = true; return nullptr; }
-    if (c->bar_state) { hipStreamSynchronize(c->stream); hipFree(c->bar_state); c->bar_state = nullptr; c->bar_state_cap = 0; }
-    void* p = nullptr;
-    const int cap = npairs + npairs / 4 + 64;
-    if (hipExtMallocWithFlags(&p, (size_t)cap * sizeof(PairState), hipDeviceMallocFinegrained) != hipSuccess || !p) {
-        (void)hipGetLastError();
-        c->bar_state_failed = true;
-        return nullptr;
-    }
-    c->bar_state = (PairState*)p; c->bar_state_cap = cap;
-    return c->bar_state;
-}
-
 static void set_state(PairState& s, const float T[16], int active, int apply) {
     for (int k = 0; k < 12; ++k) s.m[k] = T[k];
     s.active = active; s.apply = apply; s.pad[0] = s.pad[1] = 0;
@@ -1194,6 +1124,13 @@ static bool pair_host_step(const kss_icp_params& P, const PairMode& M, const dou
     if (done) t.converged = 1;
     return !done;
 }
+// pair 0's correspondences of the fitness pass into the caller's arrays
+static int fitness_corr_out(kss_ctx* c, const kss_icp_params& P, const int32_t* d_idx, const float* d_d2, size_t n0) {
+    if (P.fitness_idx) HIPCHK(c, hipMemcpyAsync(P.fitness_idx, d_idx, n0 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (P.fitness_d2) HIPCHK(c, hipMemcpyAsync(P.fitness_d2, d_d2, n0 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return KSS_OK;
+}
 // getFitnessScore(): NN of final * ORIGINAL input, mean d2 over ALL source points of each pair, into results[p].fitness.
 // tr: per pair, as the loop left it.  claim_last: the plan is the one every pass of the loop ran on.
 // d_idx / d_d2 (pl.total_src each; null: not wanted): the pass's correspondences by original source index, pair 0's copied to
@@ -1225,12 +1162,7 @@ static int fitness_pass(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, 
     } else {
         for (int p = 0; p < np; ++p) results[p].fitness = hsum[(size_t)p * NSUMS + 17] / (double)pl.g[p].ns;
     }
-    if (d_idx) {
-        const size_t n0 = (size_t)pl.g[0].ns;
-        if (P.fitness_idx) HIPCHK(c, hipMemcpyAsync(P.fitness_idx, d_idx, n0 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (P.fitness_d2) HIPCHK(c, hipMemcpyAsync(P.fitness_d2, d_d2, n0 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    if (d_idx) KCHK(fitness_corr_out(c, P, d_idx, d_d2, (size_t)pl.g[0].ns));
     return KSS_OK;
 }
 
@@ -1261,37 +1193,6 @@ static bool resident_capacities(const IcpPlan& pl, int* ntc_out, int* tabc_out) 
     }
     *ntc_out = ntc;
     *tabc_out = (int)((want + 7) / 8 * 8);
-    return true;
-}
-
-static unsigned int* resident_gate(kss_ctx* c, int npairs) {
-    static const bool want_bar = getenv("KSS_GATE_BAR") == nullptr || atoi(getenv("KSS_GATE_BAR")) != 0;
-    if (!want_bar || c->res_gate_failed) return nullptr;
-    if (c->res_gate && c->res_gate_cap >= npairs) return c->res_gate;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess || !prop.isLargeBar) { c->res_gate_failed = true; return nullptr; }
-    if (c->res_gate) { hipStreamSynchronize(c->stream); hipFree(c->res_gate); c->res_gate = nullptr; c->res_gate_cap = 0; }
-    void* p = nullptr;
-    const int cap = npairs + npairs / 4 + 64;
-    if (hipExtMallocWithFlags(&p, (size_t)cap * 128, hipDeviceMallocFinegrained) != hipSuccess || !p || hipMemset(p, 0, (size_t)cap * 128) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess) {
-        (void)hipGetLastError();
-        if (p) hipFree(p);
-        c->res_gate_failed = true;
-        return nullptr;
-    }
-    c->res_gate = (unsigned int*)p; c->res_gate_cap = cap;
-    return c->res_gate;
-}
-
-// the 20 sums of pair p under sequence number `want`, if they have all landed
-static inline bool resident_collect(const unsigned long long* h_seq, int p, unsigned long long want, double* out) {
-    const unsigned long long* sl = h_seq + (size_t)2 * NSUMS * p;
-    for (int k = NSUMS - 1; k >= 0; --k) {
-        unsigned long long bits;
-        if (!slot_value(sl, k, want, &bits)) return false;
-        std::memcpy(&out[k], &bits, sizeof(double));
-    }
     return true;
 }
 
@@ -1357,7 +1258,7 @@ static int resident_launch_cells(kss_ctx* c, const IcpPlan& pl, const kss_icp_pa
     static const int split_env = getenv("KSS_RESIDENT_SPLIT") ? atoi(getenv("KSS_RESIDENT_SPLIT")) : 2;
     int ntc = 0, tabc = 0;
     if (!resident_capacities(pl, &ntc, &tabc)) return KSS_OK;
-    a.gate = resident_gate(c, np);
+    a.gate = (unsigned int*)bar_ensure(c, c->res_gate, (size_t)np * 128);   // one 128-byte gate record per pair
     if (!a.gate) return KSS_OK;
     if (split_env > 0 && np >= 2 * resident_rows_limit(c) && P.max_iterations >= split_env + 4 &&
         ensure(c, c->res_pos, (size_t)pl.total_src * sizeof(float4)) == KSS_OK && ensure(c, c->res_wc, (size_t)pl.total_src * sizeof(unsigned)) == KSS_OK &&
@@ -1418,7 +1319,7 @@ static int resident_launch_cands(kss_ctx* c, const IcpPlan& pl, const kss_icp_pa
         if (reserve.take(c->device, want_wg, cap)) tpw = t;
     }
     if (!tpw) return KSS_OK;
-    a.gate = resident_gate(c, np);
+    a.gate = (unsigned int*)bar_ensure(c, c->res_gate, (size_t)np * 128);   // one 128-byte gate record per pair
     if (!a.gate) return KSS_OK;
     if (ensure_zeroed(c, c->partials, (size_t)np * bpp * NSUMS * sizeof(Granule)) != KSS_OK) return KSS_OK;
     KCHK(resident_launch_prepare(c, pl, P, max_passes, a));
@@ -1444,79 +1345,77 @@ static int resident_launch_cands(kss_ctx* c, const IcpPlan& pl, const kss_icp_pa
     return KSS_OK;
 }
 
-// *handled = false with KSS_OK: the plan does not qualify (or the engine gave up before touching any result): the caller
-// runs the launch-per-pass loop
-static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, kss_icp_result* results, bool* handled, bool cand = false) {
-    *handled = false;
-    static const bool want = getenv("KSS_RESIDENT") == nullptr || atoi(getenv("KSS_RESIDENT")) != 0;
-    static const bool want_cand = getenv("KSS_CAND_RESIDENT") == nullptr || atoi(getenv("KSS_CAND_RESIDENT")) != 0;
-    if (!(cand ? want_cand : want) || P.allreduce || P.max_iterations < 1 || P.max_iterations > 4000) return KSS_OK;
-    if (cand ? (pl.grid || pl.gridb || !pl.shared_target || pl.src_in_cell_order || pl.g[0].tgt_pad > 8192) : !pl.gridb) return KSS_OK;
-    if (std::chrono::steady_clock::now() < c->res_backoff[cand ? 1 : 0]) return KSS_OK;   // given up recently: see below
-    const int np = pl.npairs;
-    const int max_passes = P.max_iterations + 2;
-    CandReservation cand_reserve;   // (given back when this function returns: the kernel has drained by then on every path)
-    ResLaunch a;
-    int split_at = 0;
-    ResArgs ra;
-    std::memset(&ra, 0, sizeof ra);
-    KCHK(cand ? resident_launch_cands(c, pl, P, max_passes, cand_reserve, a) : resident_launch_cells(c, pl, P, max_passes, ra, &split_at, a));
-    if (!a.launched) return KSS_OK;
-    unsigned int* const gate = a.gate;
-    const bool stamps_on = a.stamps != nullptr;
-
-    // ---- per-pair host state: icp_loop's record and what the serving protocol adds ----
-    enum { PH_ITER = 0, PH_FIT = 1, PH_DONE = 2 };
-    struct PairHost {
-        PairTrack t;
-        int k = 0, phase = PH_ITER, cancelled = 0, parked = 0;
-        double fitness = 0.0;
-        explicit PairHost(const kss_icp_params& P) : t(P) {}
-    };
-    std::vector<PairHost> H((size_t)np, PairHost(P));
-    const PairMode plain;   // the untrimmed, unweighted point metric
-    if (P.trace_n) *P.trace_n = 0;
-    std::atomic<int> failed{0}, kernel_done{0}, pairs_left{np}, cancel_all{0};
-    int split_now = split_at;                  // > 0 while the first launch of a split batch is being served
-    unsigned exit_tag_now = a.stamp0;
-    std::vector<char> in_launch((size_t)np, 1);
-    const int judge = cand ? c->spec_judge : -1;
-    const double judge_threshold = c->spec_threshold;
+// ---- serving a resident launch: the per-pair host state (icp_loop's record and what the serving protocol adds), the launch's
+// description, what the serving threads share, and the steps in resident_loop's order ----
+enum { PH_ITER = 0, PH_FIT = 1, PH_DONE = 2 };
+struct PairHost {
+    PairTrack t;
+    int k = 0, phase = PH_ITER, cancelled = 0, parked = 0;
+    double fitness = 0.0;
+    explicit PairHost(const kss_icp_params& P) : t(P) {}
+};
+struct ResidentServe {
+    kss_ctx* const c; const IcpPlan& pl; const kss_icp_params& P; const bool cand;
+    const int np;
+    const ResLaunch a;
+    ResArgs ra;                     // cell lists: the first launch's arguments, changed into the second's
+    const int split_at;
+    int split_now;                  // > 0 while the first launch of a split batch is being served
+    unsigned exit_tag_now;
+    std::vector<PairHost> H;
+    std::vector<char> in_launch;
+    const PairMode plain{};         // the untrimmed, unweighted point metric
+    const int judge; const double judge_threshold;
+    const unsigned long long* const h_seq;
+    const unsigned long long* const exit_flags;   // one per pair, behind the launch's slots
+    std::atomic<int> failed{0}, kernel_done{0}, pairs_left, cancel_all{0}, query_said{0};
     std::atomic<long long> units{0};
-    std::atomic<int> query_said{0};
-    const unsigned long long* h_seq = c->h_seq;
-    // test hooks: the n-th record first arrives with a granule whose words do not fit its check word (what a torn 16-byte store
-    // would look like), the right one 200 us later; the n-th answer is held back for 300 ms (a stalled host thread: with a small
-    // KSS_GATE_POLLS the workgroup leaves, and the call starts over on the other engine)
-    static const long torn_at = getenv("KSS_TEST_TORN_RES_GATE") ? atol(getenv("KSS_TEST_TORN_RES_GATE")) : -1;
-    static const long stall_at = getenv("KSS_TEST_RES_STALL") ? atol(getenv("KSS_TEST_RES_STALL")) : -1;
     std::atomic<long> sent{0};
-    auto send = [&](int p, const float* T, int apply, int mode, bool any_pass = false) {   // the gate record of pair p's NEXT pass (number H[p].k + 1)
+    std::chrono::steady_clock::time_point last_progress;   // (the calling thread's alone)
+    const int nthreads;             // of the first launch
+    const long torn_at, stall_at;   // test hooks (resident_loop)
+
+    ResidentServe(kss_ctx* c_, const IcpPlan& pl_, const kss_icp_params& P_, bool cand_, const ResLaunch& a_, const ResArgs& ra_, int split_at_, long torn_at_, long stall_at_)
+        : c(c_), pl(pl_), P(P_), cand(cand_), np(pl_.npairs), a(a_), ra(ra_), split_at(split_at_), split_now(split_at_), exit_tag_now(a_.stamp0),
+          H((size_t)pl_.npairs, PairHost(P_)), in_launch((size_t)pl_.npairs, 1), judge(cand_ ? c_->spec_judge : -1), judge_threshold(c_->spec_threshold),
+          h_seq(c_->h_seq), exit_flags(c_->h_seq + (size_t)2 * NSUMS * pl_.npairs), pairs_left(pl_.npairs), nthreads(threads_for(pl_.npairs)), torn_at(torn_at_), stall_at(stall_at_) {
+        if (P.trace_n) *P.trace_n = 0;
+    }
+
+    int threads_for(int pairs) const {
+        static const int res_threads = [] {
+            int v = (int)std::thread::hardware_concurrency();
+            v = std::max(1, std::min(v, 12));
+            if (const char* e = getenv("KSS_HOST_THREADS")) { const int u = atoi(e); if (u >= 1 && u <= 64) v = u; }
+            return v;
+        }();
+        // (eight pairs a thread: one, two, four and eight candidates per thread were measured alike on a registration's 15 -- an
+        // answer is a microsecond of host work -- and several registrations at once, kss_register_batch, must not bring more
+        // spinning threads than the machine has cores)
+        static const int cand_div = getenv("KSS_CAND_PAIRS_PER_THREAD") ? std::max(1, atoi(getenv("KSS_CAND_PAIRS_PER_THREAD"))) : 8;
+        return std::max(1, std::min(res_threads, cand ? (pairs + cand_div - 1) / cand_div : (pairs + 7) / 8));
+    }
+    void run(int threads) { c->pool.run_threads(threads, [this](int t, int nt) { serve(t, nt); }); }
+
+    // the gate record of pair p's NEXT pass (number H[p].k + 1); inlined: serve's answers are on every resident batch's critical path
+    __attribute__((always_inline)) void send(int p, const float* T, int apply, int mode, bool any_pass = false) {
         unsigned w[15];
         if (T) std::memcpy(w, T, 12 * sizeof(float)); else std::memset(w, 0, 12 * sizeof(float));
         w[12] = 1u; w[13] = (unsigned)apply; w[14] = (unsigned)mode;
         // (any_pass: an order to stop that may land while some workgroups still wait for an EARLIER record -- one record per pair)
         const unsigned stamp = a.stamp0 + (any_pass ? RES_STAMP_ANY : (unsigned)(H[p].k + 1));
-        unsigned int* slot = gate + (size_t)p * 32;
         const long nth = sent.fetch_add(1) + 1;
         if (nth == stall_at) std::this_thread::sleep_for(std::chrono::milliseconds(300));
-        for (int pass = nth == torn_at ? 0 : 1; pass < 2; ++pass) {
-            for (int g = 0; g < 5; ++g) {
-                const unsigned tag = stamp + kss_mix3(w[3 * g], w[3 * g + 1], w[3 * g + 2]);   // stamp + check of the granule's three words
-                const unsigned w1 = pass == 0 && g == 2 ? w[3 * g + 1] ^ 0x00010000u : w[3 * g + 1];
-                _mm_store_si128((__m128i*)(slot + 4 * g), _mm_set_epi32((int)tag, (int)w[3 * g + 2], (int)w1, (int)w[3 * g]));
-            }
-            _mm_sfence();
-            if (pass == 0) std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-    };
-    auto serve = [&](int t, int nt) {
+        gate_record_store(a.gate + (size_t)p * 32, w, stamp, nth == torn_at);
+    }
+
+    void serve(int t, int nt) {
+        if (t == 0) last_progress = std::chrono::steady_clock::now();
         int remaining = 0;
         for (int p = t; p < np; p += nt)
             if (H[p].phase != PH_DONE && !H[p].parked) ++remaining;
         long idle = 0, grace = 0;
         double s[NSUMS];
-        auto last_progress = std::chrono::steady_clock::now();
         long long my_units = 0;
         // (the calling thread stays until EVERY pair is done: it is the one that asks HIP whether the kernel is still there)
         while ((remaining > 0 || (t == 0 && pairs_left.load(std::memory_order_relaxed) > 0)) && !failed.load(std::memory_order_relaxed)) {
@@ -1534,7 +1433,7 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
                     progress = true;
                     continue;
                 }
-                if (!resident_collect(h_seq, p, a.seq0 + (unsigned long long)h.k, s)) continue;
+                if (!slots_collect(h_seq + (size_t)2 * NSUMS * p, NSUMS, a.seq0 + (unsigned long long)h.k, s)) continue;
                 progress = true;
                 ++my_units;
                 if (h.phase == PH_FIT) {   // getFitnessScore(): mean d2 over ALL source points
@@ -1567,123 +1466,137 @@ static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P,
                 // nothing for a while: has the kernel gone?  (Only the calling thread talks to HIP.)  A workgroup that was not
                 // answered within its bounded poll has left; its pair will never publish.  After the kernel has ended every
                 // result is in host memory already: a thread that still finds nothing for ~10 ms of polling gives up.
-                if (t == 0 && !kernel_done.load()) {
-                    // every pair's workgroups have stored their exit flag (no HIP call here: one can wait on locks that other
-                    // threads of the process hold for as long as THEIR kernels run -- and this thread has pairs to answer);
-                    // after two seconds of nothing, HIP is asked all the same: a faulted kernel sets no flags
-                    bool gone = true;
-                    const unsigned long long* fl = h_seq + (size_t)2 * NSUMS * np;
-                    for (int p = 0; p < np && gone; ++p) {
-                        if (!in_launch[p]) continue;
-                        const unsigned long long w0 = __atomic_load_n(&fl[2 * p], __ATOMIC_ACQUIRE), w1 = __atomic_load_n(&fl[2 * p + 1], __ATOMIC_RELAXED);
-                        gone = (unsigned)w0 == exit_tag_now && (unsigned)(w0 >> 32) == (unsigned)p && (unsigned)(w1 >> 32) == kss_mix3((unsigned)w0, (unsigned)(w0 >> 32), (unsigned)w1);
-                    }
-                    if (gone) kernel_done.store(1);
-                    else if (std::chrono::duration<double>(std::chrono::steady_clock::now() - last_progress).count() > 2.0) {
-                        const hipError_t q = hipStreamQuery(c->stream);
-                        if (q != hipErrorNotReady) { query_said.store((int)q); kernel_done.store(1); }
-                        last_progress = std::chrono::steady_clock::now();
-                    }
-                }
+                if (t == 0 && !kernel_done.load()) kernel_gone();
                 if (kernel_done.load() && ++grace > 64) failed.store(1);
             }
         }
         units.fetch_add(my_units);
-    };
-    static const int res_threads = [] {
-        int v = (int)std::thread::hardware_concurrency();
-        v = std::max(1, std::min(v, 12));
-        if (const char* e = getenv("KSS_HOST_THREADS")) { const int u = atoi(e); if (u >= 1 && u <= 64) v = u; }
-        return v;
-    }();
-    // (eight pairs a thread: one, two, four and eight candidates per thread were measured alike on a registration's 15 -- an
-    // answer is a microsecond of host work -- and several registrations at once, kss_register_batch, must not bring more
-    // spinning threads than the machine has cores)
-    static const int cand_div = getenv("KSS_CAND_PAIRS_PER_THREAD") ? std::max(1, atoi(getenv("KSS_CAND_PAIRS_PER_THREAD"))) : 8;
-    const int nthreads = std::max(1, std::min(res_threads, cand ? (np + cand_div - 1) / cand_div : (np + 7) / 8));
-    c->pool.run_threads(nthreads, serve);
-    if (split_at > 0 && !failed.load()) {
-        // ---- the second launch of a split batch: the parked pairs, longest first ----
+    }
+
+    // has the kernel gone?  Every pair's workgroups have stored their exit flag (no HIP call here: one can wait on locks that
+    // other threads of the process hold for as long as THEIR kernels run -- and this thread has pairs to answer); after two
+    // seconds of nothing, HIP is asked all the same: a faulted kernel sets no flags
+    void kernel_gone() {
+        bool gone = true;
+        for (int p = 0; p < np && gone; ++p)
+            if (in_launch[p]) gone = exit_flag_read(exit_flags, p, exit_tag_now, nullptr);
+        if (gone) kernel_done.store(1);
+        else if (std::chrono::duration<double>(std::chrono::steady_clock::now() - last_progress).count() > 2.0) {
+            const hipError_t q = hipStreamQuery(c->stream);
+            if (q != hipErrorNotReady) { query_said.store((int)q); kernel_done.store(1); }
+            last_progress = std::chrono::steady_clock::now();
+        }
+    }
+
+    // the second launch of a split batch: the parked pairs, longest first
+    int second_launch() {
         HIPCHK(c, hipStreamSynchronize(c->stream));   // every workgroup of the first launch has left (its registers are in memory)
         // cost predictor: the searches the pair asked for in passes 1 .. split_at - 1 (its exit flag carries the count); with
         // only pass 0 in the first launch, or with KSS_RESIDENT_SPLIT_KEY=mse, the mean squared distance of its first correspondences
         static const bool key_mse = getenv("KSS_RESIDENT_SPLIT_KEY") != nullptr && std::string(getenv("KSS_RESIDENT_SPLIT_KEY")) == "mse";
         std::vector<std::pair<double, int>> order;
-        const unsigned long long* fl = h_seq + (size_t)2 * NSUMS * np;
         for (int p = 0; p < np; ++p) {
             in_launch[p] = 0;
             if (!H[p].parked) continue;
-            order.emplace_back(key_mse || split_at < 2 ? H[p].t.last_mse : (double)(unsigned)(fl[2 * p + 1] & 0xffffffffull), p);
+            unsigned searches = 0;   // (every parked pair's flag is there and fits: kernel_gone has seen it, the stream is drained)
+            exit_flag_read(exit_flags, p, a.stamp0, &searches);
+            order.emplace_back(key_mse || split_at < 2 ? H[p].t.last_mse : (double)searches, p);
         }
         std::stable_sort(order.begin(), order.end(), [](const std::pair<double, int>& x, const std::pair<double, int>& y) { return x.first > y.first; });
         const int np2 = (int)order.size();
-        if (np2 > 0) {
-            std::vector<int32_t> perm((size_t)np2);
-            for (int i = 0; i < np2; ++i) { perm[i] = order[i].second; in_launch[order[i].second] = 1; H[order[i].second].parked = 0; }
-            HIPCHK(c, hipMemcpyAsync(c->res_perm.p, perm.data(), (size_t)np2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));   // (pageable source)
-            ra.perm = (const int32_t*)c->res_perm.p;
-            ra.first_pass = split_at; ra.split_at = 0;
-            ra.exit_tag = a.stamp0 + 1u;
-            if (stamps_on) HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)np * 16 * sizeof(unsigned long long), c->stream));   // (the timeline of the SECOND launch)
-            split_now = 0; exit_tag_now = ra.exit_tag;
-            kernel_done.store(0); pairs_left.store(np2);
-            {
-                ProfScope ps(c, KSS_K_RESIDENT, true);
-                std::string lerr;
-                if (launch_resident(c->stream, P.nn_fma != 0, np2, ra, lerr) != KSS_OK) return set_err(c, KSS_ERR_HIP, "resident: the second launch of a split batch failed");
-            }
-            c->pool.run_threads(std::max(1, std::min(res_threads, (np2 + 7) / 8)), serve);
+        if (np2 == 0) return KSS_OK;
+        std::vector<int32_t> perm((size_t)np2);
+        for (int i = 0; i < np2; ++i) { perm[i] = order[i].second; in_launch[order[i].second] = 1; H[order[i].second].parked = 0; }
+        HIPCHK(c, hipMemcpyAsync(c->res_perm.p, perm.data(), (size_t)np2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (pageable source)
+        ra.perm = (const int32_t*)c->res_perm.p;
+        ra.first_pass = split_at; ra.split_at = 0;
+        ra.exit_tag = a.stamp0 + 1u;
+        if (a.stamps) HIPCHK(c, hipMemsetAsync(c->g_stamps.p, 0, (size_t)np * 16 * sizeof(unsigned long long), c->stream));   // (the timeline of the SECOND launch)
+        split_now = 0; exit_tag_now = ra.exit_tag;
+        kernel_done.store(0); pairs_left.store(np2);
+        {
+            ProfScope ps(c, KSS_K_RESIDENT, true);
+            std::string lerr;
+            if (launch_resident(c->stream, P.nn_fma != 0, np2, ra, lerr) != KSS_OK) return set_err(c, KSS_ERR_HIP, "resident: the second launch of a split batch failed");
         }
+        run(threads_for(np2));
+        return KSS_OK;
     }
-    if (failed.load()) {
-        // let every workgroup that still waits (or has not started yet) leave, then report: the caller starts over on the
-        // launch-per-pass engine (the resident kernel has written nothing but its result slots -- and, for candidates, rows
-        // that carry this launch's numbers)
+
+    // let every workgroup that still waits (or has not started yet) leave, then report: the caller starts over on the
+    // launch-per-pass engine (the resident kernel has written nothing but its result slots -- and, for candidates, rows
+    // that carry this launch's numbers)
+    int give_up() {
         for (int p = 0; p < np; ++p)
             if (H[p].phase != PH_DONE) send(p, nullptr, 0, 2, true);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         constexpr int backoff_s = 30;
         c->res_backoff[cand ? 1 : 0] = std::chrono::steady_clock::now() + std::chrono::seconds(backoff_s);   // not again for a while: each failure costs the polls' bound (~1 s)
-        {
-            int unfinished = 0, k_min = 1 << 30, k_max = 0;
-            for (int p = 0; p < np; ++p)
-                if (H[p].phase != PH_DONE) { ++unfinished; k_min = std::min(k_min, H[p].k); k_max = std::max(k_max, H[p].k); }
-            std::fprintf(stderr, "[kss] the pair-resident kernel left before every pair was finished (a stalled host thread?); running the launch-per-pass engine"
-                                 " (and for the next %d s on this context)"
-                                 " [%s, %d of %d pairs unfinished, waiting for passes %d..%d, %d host threads, stream query: %s]\n",
-                         backoff_s, cand ? "candidates" : "cell lists", unfinished, np, k_min, k_max, nthreads, hipGetErrorName((hipError_t)query_said.load()));
-            if (getenv("KSS_DEBUG_RES")) {   // what each unfinished pair was waiting for, and what is there
-                for (int p = 0; p < np; ++p) {
-                    if (H[p].phase == PH_DONE) continue;
-                    const unsigned long long want = a.seq0 + (unsigned long long)H[p].k;
-                    std::fprintf(stderr, "[kss]   pair %d: phase %d, waiting for the sums of pass %d (seq %llu); slots hold seq:", p, H[p].phase, H[p].k, want & 0xffffffffull);
-                    const unsigned long long* sl = h_seq + (size_t)2 * NSUMS * p;
-                    for (int k = 0; k < NSUMS; ++k) std::fprintf(stderr, " %llu", sl[2 * k + 1] & 0xffffffffull);
-                    std::fprintf(stderr, "\n");
-                }
+        int unfinished = 0, k_min = 1 << 30, k_max = 0;
+        for (int p = 0; p < np; ++p)
+            if (H[p].phase != PH_DONE) { ++unfinished; k_min = std::min(k_min, H[p].k); k_max = std::max(k_max, H[p].k); }
+        std::fprintf(stderr, "[kss] the pair-resident kernel left before every pair was finished (a stalled host thread?); running the launch-per-pass engine"
+                             " (and for the next %d s on this context)"
+                             " [%s, %d of %d pairs unfinished, waiting for passes %d..%d, %d host threads, stream query: %s]\n",
+                     backoff_s, cand ? "candidates" : "cell lists", unfinished, np, k_min, k_max, nthreads, hipGetErrorName((hipError_t)query_said.load()));
+        if (getenv("KSS_DEBUG_RES")) {   // what each unfinished pair was waiting for, and what is there
+            for (int p = 0; p < np; ++p) {
+                if (H[p].phase == PH_DONE) continue;
+                const unsigned long long want = a.seq0 + (unsigned long long)H[p].k;
+                std::fprintf(stderr, "[kss]   pair %d: phase %d, waiting for the sums of pass %d (seq %llu); slots hold seq:", p, H[p].phase, H[p].k, want & 0xffffffffull);
+                const unsigned long long* sl = h_seq + (size_t)2 * NSUMS * p;
+                for (int k = 0; k < NSUMS; ++k) std::fprintf(stderr, " %llu", sl[2 * k + 1] & 0xffffffffull);
+                std::fprintf(stderr, "\n");
             }
         }
         return KSS_OK;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // every workgroup has left (its last act was the publication just consumed)
-    if (c->prof > 0) { c->prof_n[KSS_K_RESIDENT_PASS] += units.load(); }
-    for (int p = 0; p < np; ++p) {
-        const PairHost& h = H[p];   // (a cancelled candidate: its result will not be looked at)
-        fill_result(results[p], h.t.fin, h.t.iters, h.cancelled ? 0 : h.t.converged, h.cancelled ? KSS_STATE_NOT_CONVERGED : h.t.state, h.t.last_mse,
-                    P.compute_fitness && !h.cancelled ? h.fitness : 0.0, p);
+
+    // results, the fitness pass's correspondences, the diagnostic timeline
+    int finish(kss_icp_result* results) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // every workgroup has left (its last act was the publication just consumed)
+        if (c->prof > 0) { c->prof_n[KSS_K_RESIDENT_PASS] += units.load(); }
+        for (int p = 0; p < np; ++p) {
+            const PairHost& h = H[p];   // (a cancelled candidate: its result will not be looked at)
+            fill_result(results[p], h.t.fin, h.t.iters, h.cancelled ? 0 : h.t.converged, h.cancelled ? KSS_STATE_NOT_CONVERGED : h.t.state, h.t.last_mse,
+                        P.compute_fitness && !h.cancelled ? h.fitness : 0.0, p);
+        }
+        if (judge >= 0) { c->spec_ran = true; c->spec_cancelled = cancel_all.load() != 0; }
+        if (a.idx_out) KCHK(fitness_corr_out(c, P, a.idx_out, a.d2_out, (size_t)pl.g[0].ns));
+        if (a.stamps) {
+            c->last_stamps.resize((size_t)np * 16);
+            HIPCHK(c, hipMemcpy(c->last_stamps.data(), a.stamps, c->last_stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        }
+        return KSS_OK;
     }
-    if (judge >= 0) { c->spec_ran = true; c->spec_cancelled = cancel_all.load() != 0; }
-    if (a.idx_out) {
-        const size_t n0 = (size_t)pl.g[0].ns;
-        if (P.fitness_idx) HIPCHK(c, hipMemcpyAsync(P.fitness_idx, a.idx_out, n0 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (P.fitness_d2) HIPCHK(c, hipMemcpyAsync(P.fitness_d2, a.d2_out, n0 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (stamps_on) {
-        c->last_stamps.resize((size_t)np * 16);
-        HIPCHK(c, hipMemcpy(c->last_stamps.data(), a.stamps, c->last_stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    }
+};
+
+// *handled = false with KSS_OK: the plan does not qualify (or the engine gave up before touching any result): the caller
+// runs the launch-per-pass loop
+static int resident_loop(kss_ctx* c, const IcpPlan& pl, const kss_icp_params& P, kss_icp_result* results, bool* handled, bool cand = false) {
+    *handled = false;
+    static const bool want = getenv("KSS_RESIDENT") == nullptr || atoi(getenv("KSS_RESIDENT")) != 0;
+    static const bool want_cand = getenv("KSS_CAND_RESIDENT") == nullptr || atoi(getenv("KSS_CAND_RESIDENT")) != 0;
+    if (!(cand ? want_cand : want) || P.allreduce || P.max_iterations < 1 || P.max_iterations > 4000) return KSS_OK;
+    if (cand ? (pl.grid || pl.gridb || !pl.shared_target || pl.src_in_cell_order || pl.g[0].tgt_pad > 8192) : !pl.gridb) return KSS_OK;
+    if (std::chrono::steady_clock::now() < c->res_backoff[cand ? 1 : 0]) return KSS_OK;   // given up recently: ResidentServe::give_up
+    const int max_passes = P.max_iterations + 2;
+    CandReservation cand_reserve;   // (given back when this function returns: the kernel has drained by then on every path)
+    ResLaunch a;
+    int split_at = 0;
+    ResArgs ra{};
+    KCHK(cand ? resident_launch_cands(c, pl, P, max_passes, cand_reserve, a) : resident_launch_cells(c, pl, P, max_passes, ra, &split_at, a));
+    if (!a.launched) return KSS_OK;
+    // test hooks: the n-th record of the call first arrives torn (kss_handover.hpp); the n-th answer is held back for 300 ms (a
+    // stalled host thread: with a small KSS_GATE_POLLS the workgroup leaves, and the call starts over on the other engine)
+    static const long torn_at = getenv("KSS_TEST_TORN_RES_GATE") ? atol(getenv("KSS_TEST_TORN_RES_GATE")) : -1;
+    static const long stall_at = getenv("KSS_TEST_RES_STALL") ? atol(getenv("KSS_TEST_RES_STALL")) : -1;
+    ResidentServe S(c, pl, P, cand, a, ra, split_at, torn_at, stall_at);
+    S.run(S.nthreads);
+    if (split_at > 0 && !S.failed.load()) KCHK(S.second_launch());
+    if (S.failed.load()) return S.give_up();
+    KCHK(S.finish(results));
     *handled = true;
     return KSS_OK;
 }
@@ -1731,7 +1644,7 @@ static int icp_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P, k
     const PairMode plain;   // the untrimmed, unweighted point metric
     const bool full = P.trace_sums != nullptr;   // traced runs report all 20 sums of every pass
     PairState* hs = (PairState*)c->h_state;
-    PairState* bar = pl_in.gridb ? bar_state_table(c, np) : nullptr;   // (null without a large BAR)
+    PairState* bar = pl_in.gridb ? (PairState*)bar_ensure(c, c->bar_state, (size_t)np * sizeof(PairState)) : nullptr;   // (null without a large BAR)
     float I[16];
     mat4_identity(I);
     for (int p = 0; p < np; ++p) {
@@ -2137,7 +2050,7 @@ static int pairs_loop(kss_ctx* c, const IcpPlan& pl_in, const kss_icp_params& P,
     std::vector<PairTrack> tr((size_t)np, PairTrack(P));
     std::vector<int> active(np, 1), was_active;
     PairState* hs = (PairState*)c->h_state;
-    PairState* bar = pl_in.gridb ? bar_state_table(c, np) : nullptr;   // (null without a large BAR)
+    PairState* bar = pl_in.gridb ? (PairState*)bar_ensure(c, c->bar_state, (size_t)np * sizeof(PairState)) : nullptr;   // (null without a large BAR)
     float I[16];
     mat4_identity(I);
     for (int p = 0; p < np; ++p) {

@@ -907,7 +907,7 @@ __global__ __launch_bounds__(PASS_BS, KSS_SINGLE_WAVES) void grid_pass_kernel(co
             // last and a line is read as a whole) and re-publishes it.  (All 200 workgroups polling HOST memory at once were
             // measured: 45 us per iteration.)  Both polls are bounded: a host that never answers makes the kernel leave
             // without publishing, which the host's own wait reports.  pad[0] != 0: cancelled.  (The loads above are
-            // already in flight while this waits.)
+            // already in flight while this waits.)  The host's writer and the resident kernels' form of this poll: kss_handover.hpp.
             typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
             if (a.state && w == 0 && threadIdx.x < 16) {
                 // the ONE workgroup that asks the host: lanes 0-15 read the 64-byte record as one request per poll

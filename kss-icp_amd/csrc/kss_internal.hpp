@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/kssicp.h"
+#include "kss_handover.hpp"
 #include "kss_host_math.hpp"
 
 namespace kss {
@@ -54,19 +55,6 @@ struct PairRed {            // final reduce: rows [first, first+count) of partia
     int32_t first;
     int32_t count;
 };
-
-// 32-bit check word of three data words: folded into the stamp / sequence word of every 16-byte granule that crosses
-// between host and device without a flag (gate records, result slots), so that a granule seen TORN -- some words of the
-// previous write, some of the new one -- fails the check and is simply polled again instead of being taken for data.
-__host__ __device__ inline unsigned kss_mix3(unsigned a, unsigned b, unsigned c) {
-    unsigned h = (a + 0x9E3779B1u) * 0x85EBCA77u;
-    h ^= h >> 15;
-    h = (h ^ (b + 0x7F4A7C15u)) * 0xC2B2AE3Du;
-    h ^= h >> 13;
-    h = (h ^ (c + 0x165667B1u)) * 0x27D4EB2Fu;
-    h ^= h >> 16;
-    return h;
-}
 
 // Uniform cell list over the target's bounding box (kss_grid.hip)
 struct GridParams {
@@ -139,18 +127,6 @@ constexpr int RES_NQ = 640;           // search requests queued per round (the r
 constexpr int RES_QW = 4;             // words per request {query, pruning radius}; answered in place {winner | runner-up << 16, bound, fell back}
 constexpr int RES_G = 4;              // source slots whose wave totals are in LDS at a time
 constexpr int RES_LDS_MAX = 160 * 1024 - 256;   // dynamic LDS of a workgroup (the rest: its few static words)
-// gate stamps: every launch owns 4096; stamp0 + k opens pass k (k <= 4002), stamp0 + RES_STAMP_ANY is accepted at ANY pass --
-// the host's order to stop, which may overwrite a record some workgroups have not read yet
-constexpr unsigned RES_STAMP_ANY = 4095u;
-// "this pair's workgroups have all left": the host learns that a resident kernel is gone from these flags, not from HIP (a
-// HIP call of a serving thread can wait on locks other threads hold for as long as THEIR kernels run)
-__device__ __forceinline__ void res_store_exit_flag(unsigned long long* flags, int pair, unsigned tag, unsigned note = 0u) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 o;
-    o.x = tag; o.y = (unsigned)pair; o.z = note; o.w = kss_mix3(o.x, o.y, o.z);
-    unsigned long long* dst = flags + 2 * (int64_t)pair;
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(o) : "memory");
-}
 struct ResArgs {
     const GridPairDev* pairs;                   // per-pair table (cell grid, segments, rows)
     const int32_t* cell_start;                  // exclusive prefix of the cell counts (global positions in `sorted`)

@@ -623,21 +623,8 @@ __global__ __launch_bounds__(256) void cand_resident_kernel(const CandArgs a) {
     int apply = 0, mode = 0;      // mode 0: a regular pass; 1: the getFitnessScore() pass (the last one); 2: stop
     for (int pass = 0; pass < a.max_passes; ++pass) {
         if (pass > 0) {
-            if (tid < 8) {
-                const unsigned expect = a.stamp0 + (unsigned)pass;
-                const unsigned int* src = a.gate + (size_t)pair * 32 + 4 * min(tid, 4);
-                u32x4 v;
-                int n = 0;
-                bool ok = true;
-                for (;;) {
-                    asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(src) : "memory");   // system scope: the writer is the host
-                    const unsigned tag = v.w - kss_mix3(v.x, v.y, v.z);
-                    if (__builtin_amdgcn_ballot_w64(tag == expect) == 0xffull) break;
-                    if (__builtin_amdgcn_ballot_w64(tag == a.stamp0 + RES_STAMP_ANY) == 0xffull) break;   // "whatever pass you wait for": a stop order
-                    __builtin_amdgcn_s_sleep(2);
-                    if (++n > a.gate_polls) { ok = false; break; }
-                }
-                if (tid < 5) { s_ps[3 * tid] = (int)v.x; s_ps[3 * tid + 1] = (int)v.y; s_ps[3 * tid + 2] = (int)v.z; }
+            if (tid < 8) {   // the gate (kss_handover.hpp)
+                const bool ok = gate_record_take(a.gate + (size_t)pair * 32, a.stamp0 + (unsigned)pass, a.stamp0 + RES_STAMP_ANY, a.gate_polls, s_ps, tid);
                 if (tid == 0) s_ctl[0] = ok ? 1 : 0;
             }
             __syncthreads();
@@ -702,11 +689,7 @@ __global__ __launch_bounds__(256) void cand_resident_kernel(const CandArgs a) {
             // a stop order "at whatever pass" may have taken some of the candidate's workgroups away before this pass: every 32
             // polls a waiting lane looks at the candidate's gate record and gives up when it reads one
             const unsigned int* stop_rec = a.gate + (size_t)pair * 32;
-            auto stop = [&]() {
-                u32x4 g;
-                asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(g) : "v"(stop_rec) : "memory");
-                return g.w - kss_mix3(g.x, g.y, g.z) == a.stamp0 + RES_STAMP_ANY;
-            };
+            auto stop = [&]() { return gate_record_stopped(stop_rec, a.stamp0 + RES_STAMP_ANY); };
             double v;
             const bool sum_it = rows_total<ROWSUM_GROUPS>(a.rows + (int64_t)row0 * NSUMS, a.bpp, seq, a.gate_polls, shg, &s_ctl[1], v, stop);
             KSS_CLAP(11);

@@ -358,23 +358,9 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_icp_kernel(const ResA
         int tv = tid;
         asm volatile("" : "+v"(tv));
         if (pass > 0) {
-            // ---- the gate: five granules {3 words, stamp + check} the host stores through the BAR; a granule whose check
-            // fails (stale, or seen torn) is simply read again ----
+            // ---- the gate: five granules {3 words, stamp + check} the host stores through the BAR (kss_handover.hpp) ----
             if (tid < 8) {
-                const unsigned expect = a.stamp0 + (unsigned)pass;
-                const unsigned int* src = a.gate + (size_t)pi * 32 + 4 * min(tid, 4);
-                u32x4 v;
-                int n = 0;
-                bool ok = true;
-                for (;;) {
-                    asm volatile("global_load_dwordx4 %0, %1, off sc0 sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(src) : "memory");   // system scope: the writer is the host
-                    const unsigned tag = v.w - kss_mix3(v.x, v.y, v.z);
-                    if (__builtin_amdgcn_ballot_w64(tag == expect) == 0xffull) break;
-                    if (__builtin_amdgcn_ballot_w64(tag == a.stamp0 + RES_STAMP_ANY) == 0xffull) break;   // "whatever pass you wait for": a stop order
-                    __builtin_amdgcn_s_sleep(2);
-                    if (++n > a.gate_polls) { ok = false; break; }
-                }
-                if (tid < 5) { s_ps[3 * tid] = (int)v.x; s_ps[3 * tid + 1] = (int)v.y; s_ps[3 * tid + 2] = (int)v.z; }
+                const bool ok = gate_record_take(a.gate + (size_t)pi * 32, a.stamp0 + (unsigned)pass, a.stamp0 + RES_STAMP_ANY, a.gate_polls, s_ps, tid);
                 if (tid == 0) s_ctl[1] = ok ? 1 : 0;
             }
             __syncthreads();

@@ -168,3 +168,43 @@ def test_split_batch_equals_one_launch():
         got, err = run({"KSS_TEST_RES_STALL": stall, "KSS_GATE_POLLS": "3000"})
         assert got == base, stall
         assert "launch-per-pass" in err, stall
+
+
+_BAR_CODE = r"""
+import sys, json, numpy as np
+sys.path.insert(0, %r)
+import __graft_entry__ as g
+pkg = g.load_package(); S = pkg.synth; ctx = pkg.Context(0)
+pairs = []
+for i, (ns, nt) in enumerate(((1, 64), (65, 200), (300, 300), (513, 1000), (1100, 3000), (2049, 2500))):
+    R = S.rot_axis_angle([0.3, -0.2 + 0.1 * i, 1.0], np.deg2rad(2.0 + 1.6 * i))
+    pairs.append(S.make_pair(2600 + i, nt, R=R, t=(0.01, -0.005 * i, 0.004), shape="bumpy" if i %% 2 else "sphere", n_src=ns))
+src_all = np.concatenate([p[0] for p in pairs]); tgt_all = np.concatenate([p[1] for p in pairs])
+so = np.concatenate([[0], np.cumsum([len(p[0]) for p in pairs])]).astype(np.int64)
+to = np.concatenate([[0], np.cumsum([len(p[1]) for p in pairs])]).astype(np.int64)
+out = []
+ctx.profile_enable(True)   # (counts the resident launches; the records do not depend on it)
+for kw in (dict(), dict(max_iterations=6, fixed_iterations=1)):
+    res = ctx.icp_batch(src_all, so, tgt_all, to, ctx.icp_params(nn_mode=pkg.NN_GRID, **kw))
+    out.append([[list(r.T), r.iterations, r.state, r.converged, r.fitness, r.last_mse] for r in res])
+print("RESIDENT_LAUNCHES %%d" %% ctx.profile_get(pkg.K_RESIDENT)[1])
+print("RESULT" + json.dumps(out))
+"""
+
+
+def test_small_ragged_batch_is_the_same_with_and_without_bar_memory():
+    """Six ragged pairs (1 to 2049 sources against 64 to 3000 targets, rotated by 2 to 10 degrees), default parameters and six
+    fixed passes: the same records bit for bit from the resident engine, without fine-grained BAR memory (KSS_GATE_BAR=0: the
+    resident engine declines silently and the per-pair state table has no mirror), from the launch-per-pass engine with and
+    without its mirror, and with a gate record once seen torn.  No run gives a resident launch up, and the runs that are meant
+    to go through the resident engine do: one resident launch per call there, none in the others."""
+    def run(env, resident_launches):
+        r = subprocess.run([sys.executable, "-c", _BAR_CODE % ROOT], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert "left before every pair" not in r.stderr, env
+        assert "RESIDENT_LAUNCHES %d" % resident_launches in r.stdout.splitlines(), (env, r.stdout[:200])
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT")][0][6:])
+    base = run({}, 2)
+    for env, launches in (({"KSS_GATE_BAR": "0"}, 0), ({"KSS_RESIDENT": "0"}, 0), ({"KSS_RESIDENT": "0", "KSS_GATE_BAR": "0"}, 0),
+                          ({"KSS_TEST_TORN_RES_GATE": "3"}, 2)):
+        assert run(env, launches) == base, env
