@@ -3,7 +3,9 @@
 Host pointers are numpy arrays; device pointers are integers (e.g. torch `tensor.data_ptr()`).
 No CPU fallback: a missing library or GPU raises KssError.
 """
+import collections
 import ctypes as C
+import operator
 import os
 import subprocess
 import sys
@@ -593,6 +595,84 @@ def rigid_from_symm_sums(sums):
     return T.reshape(4, 4), rc
 
 
+# ---- the pair metrics: marshalling vocabulary and one record per metric ------------------
+def _dp(a):
+    """A device address (an integer, e.g. tensor.data_ptr()) as a C pointer; 0 / None is NULL."""
+    return C.c_void_p(int(a)) if a else None
+
+
+def _normals(normals, n, what=""):
+    """normals as float32 triples of n rows, None staying None.  what: "source" / "target" where an entry takes both clouds'
+    normals, "" where it takes the target's alone."""
+    if normals is None:
+        return None
+    nr = _f32(normals)
+    if len(nr) != n:
+        raise ValueError(("%s normals must have one row per point" % what) if what else "normals must have one row per target point")
+    return nr
+
+
+def _per_pair(a, dtype, npairs, noun):
+    """The per-pair array of a batch (overlaps, scales, epsilons as float64; aligns as int32), None staying None."""
+    if a is None:
+        return None
+    v = np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+    if len(v) != npairs:
+        raise ValueError("%s must hold one entry per pair" % noun)
+    return v
+
+
+def _rot(Rn):
+    return np.ascontiguousarray(Rn, dtype=np.float32).reshape(9) if Rn is not None else None
+
+
+def _structs(m, given, *a):
+    """The params structs of metric m: the caller's, and where one is None the record's default made from a (what the method's
+    own signature offers for it: overlap and metric, loss and metric, loss, or nothing)."""
+    make = m.make
+    if len(make) == 1:                                   # (a metric has one struct or two; written out, this runs on every call)
+        g, = given
+        return (g if g is not None else make[0](*a),)
+    g0, g1 = given
+    return (g0 if g0 is not None else make[0](*a), g1 if g1 is not None else make[1](*a))
+
+
+# The cloud arguments of a kss_icp_* entry in C order, by the record's `normals`, picked from (source, its count or offsets, its
+# normals, target, its count or offsets, its normals); "map": the source with its normals, then a voxel map as the target.
+_CLOUDS = {"both": operator.itemgetter(0, 1, 2, 3, 4, 5), "target": operator.itemgetter(0, 1, 3, 4, 5),
+           "none": operator.itemgetter(0, 1, 3, 4), "map": operator.itemgetter(0, 1, 2, 3)}
+
+
+# What differs between the kss_icp_* families, and nothing else:
+#   single, many   the C symbols of the single pair and of the many-pairs form (their _dev twins add the suffix)
+#   sums           the C symbol of the one-pass record, None where there is none
+#   normals        "none", "target" or "both": which normals follow the clouds ("map": the source's, then a voxel map as the target)
+#   make           one default maker per extra params struct, in C order (_structs() calls them; the trimmed families' struct is
+#                  no default: their methods always make it from their own overlap and metric)
+#   trace          the per-pass trace field of the LAST struct, rows ninfo wide; None: no such trace
+#   info, ninfo    the result key and width of the per-call info record (ninfo doubles, a batch: a row per pair); None: none
+#   per_pair       (noun, dtype) of the per-pair array that follows each struct in the many-pairs form
+#   ncol           the width of a trace_sums row; None: NSUMS or P2L_NSUMS by the last struct's metric
+Metric = collections.namedtuple("Metric", "single many sums normals make trace info ninfo per_pair ncol")
+_OVERLAPS, _SCALES, _EPSILONS, _ALIGNS = ("overlaps", np.float64), ("scales", np.float64), ("epsilons", np.float64), ("aligns", np.int32)
+_ICP = Metric("kss_icp", "kss_icp_batch", None, "none", (), None, None, 0, (), NSUMS)
+_P2L = Metric("kss_icp_p2l", "kss_icp_p2l_batch", "kss_p2l_sums", "target", (), None, None, 0, (), P2L_NSUMS)
+_TRIMMED = Metric("kss_icp_trimmed", "kss_icp_trimmed_batch", None, "target", (TrimParams,), "trace_trim", "trim_info", TRIM_NINFO,
+                  (_OVERLAPS,), None)
+_O2O = Metric("kss_icp_o2o", "kss_icp_o2o_batch", None, "target", (O2oParams,), "trace_o2o", "o2o_info", O2O_NINFO, (_OVERLAPS,), None)
+_RECIP = Metric("kss_icp_recip", "kss_icp_recip_pairs", None, "target", (RecipParams,), "trace_recip", "recip_info", RECIP_NINFO,
+                (_OVERLAPS,), None)          # (the many-pairs form is spelled _pairs: include/kssicp.h)
+_SIM = Metric("kss_icp_sim", "kss_icp_sim_batch", "kss_sim_sums", "none", (sim_params,), "trace_sim", "sim_info", SIM_NINFO, (_OVERLAPS,), NSUMS)
+_ROBUST = Metric("kss_icp_robust", "kss_icp_robust_batch", "kss_robust_sums", "target", (robust_params,), "trace_robust", "robust_info",
+                 ROBUST_NINFO, (_SCALES,), None)
+_GICP = Metric("kss_icp_gicp", "kss_icp_gicp_batch", "kss_gicp_sums", "both", (gicp_params,), None, None, 0, (_EPSILONS,), P2L_NSUMS)
+_SYMM = Metric("kss_icp_symm", "kss_icp_symm_batch", "kss_symm_sums", "both", (symm_params,), None, None, 0, (_ALIGNS,), P2L_NSUMS)
+_SYMM_ROBUST = Metric("kss_icp_symm_robust", "kss_icp_symm_robust_batch", "kss_symm_robust_sums", "both",
+                      (lambda loss: symm_params(), lambda loss: robust_params(loss, METRIC_PLANE)), "trace_robust", "robust_info",
+                      ROBUST_NINFO, (_ALIGNS, _SCALES), P2L_NSUMS)
+_VGICP = Metric("kss_icp_vgicp", None, "kss_vgicp_sums", "map", (gicp_params,), None, "info", VGICP_NINFO, (), P2L_NSUMS)
+
+
 # ---- context --------------------------------------------------------------------------------------------
 class Context:
     """One kss_ctx (one GPU, one stream)."""
@@ -741,22 +821,56 @@ class Context:
             setattr(p, k, v)
         return p
 
-    def _icp_call(self, call, where, p, ns, ncol, trace_cap, fitness_corr, tp=None):
-        """call(res) with the trace and fitness_corr arrays attached to the params p (and to the TrimParams or RobustParams tp),
-        detached again whether it returns or raises; the result dictionary of icp()."""
-        tname = ("trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else
-                 "trace_o2o" if isinstance(tp, O2oParams) else "trace_recip" if isinstance(tp, RecipParams) else "trace_trim")
-        ninfo = (SIM_NINFO if isinstance(tp, SimParams) else O2O_NINFO if isinstance(tp, O2oParams) else
-                 RECIP_NINFO if isinstance(tp, RecipParams) else TRIM_NINFO)
-        res = IcpResult()
-        tr = None
-        fc = None
+    # ---- the pair metrics: one traced call under the host forms (single pair / batch) and the three _dev batch forms that trace;
+    # one plain call for the records.  The untraced _dev ICP forms attach nothing and keep their literal calls: they are the thin
+    # wrappers a caller times, and tests/test_binding_calls.py checks each of them against its symbol's argtypes.
+    def _icp_call(self, m, dev, src, ns, sn, tgt, nt, tn, p, structs=(), arrays=None, so=None, trace_cap=0, fitness_corr=False):
+        """The kss_icp_* entry of metric m -- the _dev twin if dev, the many-pairs form if the source offsets so are given -- on the
+        marshalled clouds (src, its count ns, its normals sn; tgt, nt, tn the same of the target; a batch: the marshalled offsets
+        for the counts), the IcpParams p, m's params structs and (a batch) the caller's per-pair array beside each, checked and
+        converted here.  Every entry that can trace is called from here and nowhere else.  The trace and fitness_corr
+        arrays, the latter sized for the sources of the pair (a batch: of pair 0), are attached to p and to m's last struct and
+        detached again whether the call returns or raises.  Returns (the IcpResult, or the ctypes array of a batch; the info
+        record or None; the dictionary of the extras)."""
+        single, many, _, normals, _, trace, key, ninfo, per_pair, ncol = m
+        batch = so is not None
+        args = [self.h, *_CLOUDS[normals]((src, ns, sn, tgt, nt, tn))]
+        if batch:
+            npairs = len(so) - 1
+            res = (IcpResult * npairs)()
+            args.append(npairs)
+            args.append(C.byref(p))
+            for st, a, (noun, dtype) in zip(structs, arrays, per_pair):
+                args.append(C.byref(st))
+                args.append(_p(_per_pair(a, dtype, npairs, noun)))
+            args.append(C.cast(res, C.c_void_p))
+        else:
+            res = IcpResult()
+            args.append(C.byref(p))
+            for st in structs:
+                args.append(C.byref(st))
+            args.append(C.byref(res))
+        info = None
+        if key:
+            info = np.zeros((npairs, ninfo) if batch else ninfo, np.float64)
+            args.append(_p(info))
+        where = many if batch else single
+        if dev:
+            where += "_dev"
+        if trace_cap <= 0 and not fitness_corr:            # nothing to attach: the plain checked call
+            self._chk(getattr(self.L, where)(*args), where)
+            return res, info, {}
+        tp = structs[-1] if trace else None
+        tr = fc = None
         try:
             if fitness_corr:
+                if batch:
+                    ns = int(so[1] - so[0]) if npairs > 0 else 0
                 fc = (np.full(ns, -1, np.int32), np.full(ns, np.nan, np.float32))
                 p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
                 p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
             if trace_cap > 0:
+                ncol = ncol or (P2L_NSUMS if tp.metric == METRIC_PLANE else NSUMS)
                 tr = (np.zeros((trace_cap, ncol), np.float64), np.zeros((trace_cap, 16), np.float32), C.c_int(0),
                       np.zeros((trace_cap, ninfo), np.float64) if tp is not None else None)
                 p.trace_sums = tr[0].ctypes.data_as(C.POINTER(C.c_double))
@@ -764,57 +878,115 @@ class Context:
                 p.trace_cap = trace_cap
                 p.trace_n = C.pointer(tr[2])
                 if tp is not None:
-                    setattr(tp, tname, tr[3].ctypes.data_as(C.POINTER(C.c_double)))
-            self._chk(call(res), where)
+                    setattr(tp, trace, tr[3].ctypes.data_as(C.POINTER(C.c_double)))
+            self._chk(getattr(self.L, where)(*args), where)
         finally:
             if tr:
                 p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-                if isinstance(tp, (RobustParams, SimParams, O2oParams, RecipParams)):
-                    setattr(tp, tname, None)
+                if tp is not None:
+                    setattr(tp, trace, None)
             if fc:
                 p.fitness_idx = None; p.fitness_d2 = None
-        out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
-               "state": res.state, "fitness": res.fitness, "last_mse": res.last_mse}
+        extra = {}
         if tr:
             n = tr[2].value
-            out["trace_sums"] = tr[0][:n].copy()
-            out["trace_Tk"] = tr[1][:n].reshape(-1, 4, 4).copy()
+            extra["trace_sums"] = tr[0][:n].copy()
+            extra["trace_Tk"] = tr[1][:n].reshape(-1, 4, 4).copy()
             if tp is not None:
-                out[tname] = tr[3][:n].copy()
+                extra[trace] = tr[3][:n].copy()
         if fc:
-            out["fitness_idx"], out["fitness_d2"] = fc
+            extra["fitness_idx"], extra["fitness_d2"] = fc
+        return res, info, extra
+
+    @staticmethod
+    def _result(m, res, info, extra):
+        """The result dictionary of icp(), with the extras and m's info record under m's key."""
+        out = {"T": res.matrix(), "iterations": res.iterations, "converged": bool(res.converged),
+               "state": res.state, "fitness": res.fitness, "last_mse": res.last_mse}
+        out.update(extra)
+        if m.info:
+            out[m.info] = info
         return out
 
-    def icp(self, src, tgt, params=None, trace_cap=0, fitness_corr=False):
+    @staticmethod
+    def _offsets(src_off, tgt_off):
+        so = np.ascontiguousarray(src_off, dtype=np.int64)
+        to = np.ascontiguousarray(tgt_off, dtype=np.int64)
+        if len(so) != len(to) or len(so) < 1:
+            raise ValueError("src_off and tgt_off must hold npairs + 1 entries each")
+        return so, to
+
+    def _pair(self, m, src, tgt, src_normals, tgt_normals, params, structs, trace_cap, fitness_corr):
+        """Host arrays, one pair: the result dictionary."""
         s, t = _f32(src), _f32(tgt)
+        sn = _normals(src_normals, len(s), "source")
+        tn = _normals(tgt_normals, len(t), "target" if m.normals == "both" else "")
         p = params if params is not None else self.icp_params()
-        return self._icp_call(lambda res: self.L.kss_icp(self.h, _p(s), len(s), _p(t), len(t), C.byref(p), C.byref(res)),
-                              "kss_icp", p, len(s), NSUMS, trace_cap, fitness_corr)
+        res, info, extra = self._icp_call(m, False, _p(s), len(s), _p(sn), _p(t), len(t), _p(tn), p, structs, None, None, trace_cap,
+                                          fitness_corr)
+        return self._result(m, res, info, extra)
+
+    def _pairs(self, m, src_all, src_off, tgt_all, tgt_off, src_normals_all, tgt_normals_all, params, structs, per_pair, trace_cap,
+               fitness_corr):
+        """Host arrays, many pairs: (list of IcpResult, [info of every pair,] extras of pair 0)."""
+        s, t = _f32(src_all), _f32(tgt_all)
+        sn = _normals(src_normals_all, len(s), "source")
+        tn = _normals(tgt_normals_all, len(t), "target" if m.normals == "both" else "")
+        so, to = self._offsets(src_off, tgt_off)
+        p = params if params is not None else self.icp_params()
+        res, info, extra = self._icp_call(m, False, _p(s), _p(so), _p(sn), _p(t), _p(to), _p(tn), p, structs, per_pair, so, trace_cap,
+                                          fitness_corr)
+        return (list(res), info, extra) if m.info else (list(res), extra)
+
+    def _pairs_dev_traced(self, m, d_src_all, src_off, d_tgt_all, tgt_off, d_src_normals_all, d_tgt_normals_all, params, structs, per_pair,
+                          trace_cap):
+        """Device pointers, many pairs, of the families on both clouds' normals (gicp, symm, symm_robust): the only _dev forms that
+        trace.  They take a trace_cap, accept params None and return pair 0's extras behind the list (and the info)."""
+        so, to = self._offsets(src_off, tgt_off)
+        p = params if params is not None else self.icp_params()
+        res, info, extra = self._icp_call(m, True, _dp(d_src_all), _p(so), _dp(d_src_normals_all), _dp(d_tgt_all), _p(to),
+                                          _dp(d_tgt_normals_all), p, structs, per_pair, so, trace_cap)
+        return (list(res), info, extra) if m.info else (list(res), extra)
+
+    def _sums(self, m, dev, args, structs=(), ncol=P2L_NSUMS, with_info=False):
+        """The one-pass record of metric m (kss_*_sums, its _dev twin if dev), a plain checked call: args, m's structs, the sums
+        and, for the robust records, the info.  Returns sums, or (sums, info)."""
+        where = m.sums + ("_dev" if dev else "")
+        sums = np.zeros(ncol, np.float64)
+        info = np.zeros(m.ninfo, np.float64) if with_info else None
+        self._chk(getattr(self.L, where)(self.h, *args, *[C.byref(st) for st in structs], _p(sums), *([_p(info)] if with_info else [])),
+                  where)
+        return (sums, info) if with_info else sums
+
+    def _sums_both(self, m, src, src_normals, tgt, tgt_normals, idx, max_d2, Rn, structs, with_info=False):
+        """_sums of a metric on both clouds' normals, host arrays."""
+        s, t = _f32(src), _f32(tgt)
+        sn, tn = _normals(src_normals, len(s), "source"), _normals(tgt_normals, len(t), "target")
+        i = np.ascontiguousarray(idx, dtype=np.int32)
+        return self._sums(m, False, (_p(s), _p(sn), _p(t), _p(tn), _p(i), len(s), len(t), float(max_d2), _p(_rot(Rn))), structs,
+                          with_info=with_info)
+
+    def _sums_both_dev(self, m, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, Rn, structs, with_info=False):
+        """_sums of a metric on both clouds' normals, device pointers (Rn stays a host array)."""
+        return self._sums(m, True, (_dp(d_src), _dp(d_src_normals), _dp(d_tgt), _dp(d_tgt_normals), _dp(d_idx), int(n), int(nt),
+                                    float(max_d2), _p(_rot(Rn))), structs, with_info=with_info)
+
+    def icp(self, src, tgt, params=None, trace_cap=0, fitness_corr=False):
+        return self._pair(_ICP, src, tgt, None, None, params, (), trace_cap, fitness_corr)
 
     # ---- point-to-plane
     def p2l_sums(self, src, tgt, normals, idx, max_d2=1.0):
         s, t, nr = _f32(src), _f32(tgt), _f32(normals)
         i = np.ascontiguousarray(idx, dtype=np.int32)
-        sums = np.empty(P2L_NSUMS, np.float64)
-        self._chk(self.L.kss_p2l_sums(self.h, _p(s), _p(t), _p(nr), _p(i), len(s), len(t), float(max_d2), _p(sums)), "kss_p2l_sums")
-        return sums
+        return self._sums(_P2L, False, (_p(s), _p(t), _p(nr), _p(i), len(s), len(t), float(max_d2)))
 
     def p2l_sums_dev(self, d_src, d_tgt, d_normals, d_idx, n, nt, max_d2=1.0):
-        sums = np.empty(P2L_NSUMS, np.float64)
-        self._chk(self.L.kss_p2l_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_tgt)), C.c_void_p(int(d_normals)),
-                                          C.c_void_p(int(d_idx)), int(n), int(nt), float(max_d2), _p(sums)), "kss_p2l_sums_dev")
-        return sums
+        return self._sums(_P2L, True, (_dp(d_src), _dp(d_tgt), _dp(d_normals), _dp(d_idx), int(n), int(nt), float(max_d2)))
 
     def icp_p2l(self, src, tgt, normals=None, params=None, trace_cap=0, fitness_corr=False):
         """Point-to-plane ICP (kss_icp_p2l).  normals: nt x 3 target normals, or None to have the library compute them
         (kss_normals' definition, k = 20, rounded to float).  Same result dictionary as icp(); trace_sums rows hold P2L_NSUMS."""
-        s, t = _f32(src), _f32(tgt)
-        nr = _f32(normals) if normals is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        p = params if params is not None else self.icp_params()
-        return self._icp_call(lambda res: self.L.kss_icp_p2l(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(res)),
-                              "kss_icp_p2l", p, len(s), P2L_NSUMS, trace_cap, fitness_corr)
+        return self._pair(_P2L, src, tgt, None, normals, params, (), trace_cap, fitness_corr)
 
     def icp_p2l_dev(self, d_src, ns, d_tgt, nt, d_normals, params):
         """kss_icp_p2l_dev on device pointers (d_normals may be 0 / None); returns the IcpResult."""
@@ -834,8 +1006,7 @@ class Context:
 
     def trim_threshold_dev(self, d_d2, n, max_d2=1.0, overlap=0.5):
         info = np.zeros(TRIM_NINFO, np.float64)
-        self._chk(self.L.kss_trim_threshold_dev(self.h, C.c_void_p(int(d_d2)), int(n), float(max_d2), float(overlap), _p(info)),
-                  "kss_trim_threshold_dev")
+        self._chk(self.L.kss_trim_threshold_dev(self.h, _dp(d_d2), int(n), float(max_d2), float(overlap), _p(info)), "kss_trim_threshold_dev")
         return info
 
     def icp_trimmed(self, src, tgt, normals=None, overlap=0.5, metric=METRIC_POINT, params=None, trace_cap=0, fitness_corr=False):
@@ -843,18 +1014,7 @@ class Context:
         kept.  metric METRIC_POINT (normals must be None) or METRIC_PLANE (normals nt x 3, or None to have them computed).
         The result dictionary of icp_p2l() plus trace_trim (one {m, k, tau, kept} row per traced pass) and trim_info (the last
         pass's); trace_sums rows hold NSUMS or P2L_NSUMS doubles by metric."""
-        s, t = _f32(src), _f32(tgt)
-        nr = _f32(normals) if normals is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        p = params if params is not None else self.icp_params()
-        tp = TrimParams(float(overlap), int(metric), None)
-        info = np.zeros(TRIM_NINFO, np.float64)
-        out = self._icp_call(lambda res: self.L.kss_icp_trimmed(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(tp),
-                                                                C.byref(res), _p(info)),
-                             "kss_icp_trimmed", p, len(s), P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, tp)
-        out["trim_info"] = info
-        return out
+        return self._pair(_TRIMMED, src, tgt, None, normals, params, (TrimParams(float(overlap), int(metric), None),), trace_cap, fitness_corr)
 
     def icp_trimmed_dev(self, d_src, ns, d_tgt, nt, d_normals, params, overlap=0.5, metric=METRIC_POINT):
         """kss_icp_trimmed_dev on device pointers (d_normals may be 0 / None); returns (IcpResult, trim_info)."""
@@ -883,9 +1043,8 @@ class Context:
     def o2o_filter_dev(self, d_idx, d_d2, n, nt, max_d2=1.0, d_idx_out=None, d_d2_out=None):
         """kss_o2o_filter_dev on device pointers (an output may be 0 / None, or its input); returns (m, u)."""
         info = np.zeros(2, np.float64)
-        self._chk(self.L.kss_o2o_filter_dev(self.h, C.c_void_p(int(d_idx)), C.c_void_p(int(d_d2)), int(n), int(nt), float(max_d2),
-                                            C.c_void_p(int(d_idx_out)) if d_idx_out else None,
-                                            C.c_void_p(int(d_d2_out)) if d_d2_out else None, _p(info)), "kss_o2o_filter_dev")
+        self._chk(self.L.kss_o2o_filter_dev(self.h, _dp(d_idx), _dp(d_d2), int(n), int(nt), float(max_d2), _dp(d_idx_out), _dp(d_d2_out),
+                                            _p(info)), "kss_o2o_filter_dev")
         return int(info[0]), int(info[1])
 
     def o2o_filter_batch(self, idx_all, d2_all, off, nts, max_d2=1.0):
@@ -907,18 +1066,7 @@ class Context:
         """One-to-one ICP (kss_icp_o2o): of all sources that chose one target only the closest keeps its correspondence, then
         icp_trimmed()'s pass at `overlap` over the survivors.  Arguments and result dictionary as icp_trimmed(), with trace_o2o
         (one {u, k, tau, kept, m} row per traced pass) and o2o_info (the last pass's) in place of the trimmed records."""
-        s, t = _f32(src), _f32(tgt)
-        nr = _f32(normals) if normals is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        p = params if params is not None else self.icp_params()
-        op = O2oParams(float(overlap), int(metric), None)
-        info = np.zeros(O2O_NINFO, np.float64)
-        out = self._icp_call(lambda res: self.L.kss_icp_o2o(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(op),
-                                                            C.byref(res), _p(info)),
-                             "kss_icp_o2o", p, len(s), P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, op)
-        out["o2o_info"] = info
-        return out
+        return self._pair(_O2O, src, tgt, None, normals, params, (O2oParams(float(overlap), int(metric), None),), trace_cap, fitness_corr)
 
     def icp_o2o_dev(self, d_src, ns, d_tgt, nt, d_normals, params, overlap=1.0, metric=METRIC_POINT):
         """kss_icp_o2o_dev on device pointers (d_normals may be 0 / None); returns (IcpResult, o2o_info)."""
@@ -949,28 +1097,15 @@ class Context:
     def recip_filter_dev(self, d_src, n, d_tgt, nt, d_idx, d_d2, max_d2=1.0, nn_fma=0, d_idx_out=None, d_d2_out=None):
         """kss_recip_filter_dev on device pointers (an output may be 0 / None, or its input); returns (m, u, r)."""
         info = np.zeros(3, np.float64)
-        self._chk(self.L.kss_recip_filter_dev(self.h, C.c_void_p(int(d_src)), int(n), C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_idx)),
-                                              C.c_void_p(int(d_d2)), float(max_d2), int(nn_fma),
-                                              C.c_void_p(int(d_idx_out)) if d_idx_out else None,
-                                              C.c_void_p(int(d_d2_out)) if d_d2_out else None, _p(info)), "kss_recip_filter_dev")
+        self._chk(self.L.kss_recip_filter_dev(self.h, _dp(d_src), int(n), _dp(d_tgt), int(nt), _dp(d_idx), _dp(d_d2), float(max_d2),
+                                              int(nn_fma), _dp(d_idx_out), _dp(d_d2_out), _p(info)), "kss_recip_filter_dev")
         return int(info[0]), int(info[1]), int(info[2])
 
     def icp_recip(self, src, tgt, normals=None, overlap=1.0, metric=METRIC_POINT, params=None, trace_cap=0, fitness_corr=False):
         """Reciprocal ICP (kss_icp_recip): a correspondence is kept only where source and target are each other's nearest, then
         icp_trimmed()'s pass at `overlap` over the mutual winners.  Arguments and result dictionary as icp_o2o(), with trace_recip
         (one {r, k, tau, kept, m, u} row per traced pass) and recip_info (the last pass's)."""
-        s, t = _f32(src), _f32(tgt)
-        nr = _f32(normals) if normals is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        p = params if params is not None else self.icp_params()
-        rp = RecipParams(float(overlap), int(metric), None)
-        info = np.zeros(RECIP_NINFO, np.float64)
-        out = self._icp_call(lambda res: self.L.kss_icp_recip(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(rp),
-                                                              C.byref(res), _p(info)),
-                             "kss_icp_recip", p, len(s), P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, rp)
-        out["recip_info"] = info
-        return out
+        return self._pair(_RECIP, src, tgt, None, normals, params, (RecipParams(float(overlap), int(metric), None),), trace_cap, fitness_corr)
 
     def icp_recip_dev(self, d_src, ns, d_tgt, nt, d_normals, params, overlap=1.0, metric=METRIC_POINT):
         """kss_icp_recip_dev on device pointers (d_normals may be 0 / None); returns (IcpResult, recip_info)."""
@@ -988,30 +1123,18 @@ class Context:
         of squares)."""
         s, t = _f32(src), _f32(tgt)
         i = np.ascontiguousarray(idx, dtype=np.int32)
-        sums = np.empty(NSUMS, np.float64)
-        self._chk(self.L.kss_sim_sums(self.h, _p(s), _p(t), _p(i), len(s), len(t), float(max_d2), _p(sums)), "kss_sim_sums")
-        return sums
+        return self._sums(_SIM, False, (_p(s), _p(t), _p(i), len(s), len(t), float(max_d2)), ncol=NSUMS)
 
     def sim_sums_dev(self, d_src, d_tgt, d_idx, n, nt, max_d2=1.0):
-        sums = np.empty(NSUMS, np.float64)
-        self._chk(self.L.kss_sim_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_tgt)), C.c_void_p(int(d_idx)), int(n), int(nt),
-                                          float(max_d2), _p(sums)), "kss_sim_sums_dev")
-        return sums
+        return self._sums(_SIM, True, (_dp(d_src), _dp(d_tgt), _dp(d_idx), int(n), int(nt), float(max_d2)), ncol=NSUMS)
 
     def icp_sim(self, src, tgt, sp=None, params=None, trace_cap=0, fitness_corr=False):
         """Similarity ICP (kss_icp_sim): trimmed ICP on the point metric with Umeyama's scale in the solve, the accumulated scale
         kept in [sp.scale_min, sp.scale_max].  sp: a SimParams (sim_params()), None for the defaults.  The result dictionary of
         icp_trimmed() with trace_sim (one {m, k, tau, kept, s_k, s_acc} row per traced pass) and sim_info (the last pass's) in
         place of the trimmed records, plus scale = sim_info[5] (1 when no pass ran); T holds the accumulated similarity."""
-        s, t = _f32(src), _f32(tgt)
-        p = params if params is not None else self.icp_params()
-        sp = sp if sp is not None else sim_params()
-        info = np.zeros(SIM_NINFO, np.float64)
-        out = self._icp_call(lambda res: self.L.kss_icp_sim(self.h, _p(s), len(s), _p(t), len(t), C.byref(p), C.byref(sp), C.byref(res),
-                                                            _p(info)),
-                             "kss_icp_sim", p, len(s), NSUMS, trace_cap, fitness_corr, sp)
-        out["sim_info"] = info
-        out["scale"] = float(info[5]) if info[5] > 0 else 1.0
+        out = self._pair(_SIM, src, tgt, None, None, params, _structs(_SIM, (sp,)), trace_cap, fitness_corr)
+        out["scale"] = float(out["sim_info"][5]) if out["sim_info"][5] > 0 else 1.0
         return out
 
     def icp_sim_dev(self, d_src, ns, d_tgt, nt, params, sp=None):
@@ -1024,33 +1147,22 @@ class Context:
         return res, info
 
     # ---- robust ICP
-    @staticmethod
-    def _robust_params(rp, loss, metric):
-        return rp if rp is not None else robust_params(loss, metric)
-
     def robust_sums(self, src, tgt, normals, idx, max_d2=1.0, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT):
         """kss_robust_sums: (sums, info) of one robust pass over given correspondences.  rp: a RobustParams (robust_params()), or
         None for the defaults of loss / metric.  normals: nt x 3 for the plane metric, None for the point metric; sums holds
         NSUMS or P2L_NSUMS doubles by metric, info {m, c2, sum of weights, cnt}."""
-        rp = self._robust_params(rp, loss, metric)
+        rp, = _structs(_ROBUST, (rp,), loss, metric)
         s, t = _f32(src), _f32(tgt)
         nr = _f32(normals) if normals is not None else None
         i = np.ascontiguousarray(idx, dtype=np.int32)
-        sums = np.zeros(P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, np.float64)
-        info = np.zeros(ROBUST_NINFO, np.float64)
-        self._chk(self.L.kss_robust_sums(self.h, _p(s), _p(t), _p(nr), _p(i), len(s), len(t), float(max_d2), C.byref(rp), _p(sums),
-                                         _p(info)), "kss_robust_sums")
-        return sums, info
+        return self._sums(_ROBUST, False, (_p(s), _p(t), _p(nr), _p(i), len(s), len(t), float(max_d2)), (rp,),
+                          P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, True)
 
     def robust_sums_dev(self, d_src, d_tgt, d_normals, d_idx, n, nt, max_d2=1.0, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT):
         """kss_robust_sums_dev on device pointers (d_normals 0 / None for the point metric); returns (sums, info)."""
-        rp = self._robust_params(rp, loss, metric)
-        sums = np.zeros(P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, np.float64)
-        info = np.zeros(ROBUST_NINFO, np.float64)
-        self._chk(self.L.kss_robust_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_tgt)),
-                                             C.c_void_p(int(d_normals)) if d_normals else None, C.c_void_p(int(d_idx)), int(n), int(nt),
-                                             float(max_d2), C.byref(rp), _p(sums), _p(info)), "kss_robust_sums_dev")
-        return sums, info
+        rp, = _structs(_ROBUST, (rp,), loss, metric)
+        return self._sums(_ROBUST, True, (_dp(d_src), _dp(d_tgt), _dp(d_normals), _dp(d_idx), int(n), int(nt), float(max_d2)), (rp,),
+                          P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, True)
 
     def icp_robust(self, src, tgt, normals=None, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT, params=None, trace_cap=0,
                    fitness_corr=False):
@@ -1058,22 +1170,11 @@ class Context:
         fixed or taken per pass from the median residual.  rp: a RobustParams (robust_params()), or None for the defaults of
         loss / metric; normals as in icp_trimmed().  The result dictionary of icp_trimmed() with trace_robust (one {m, c2, sum
         of weights, cnt} row per traced pass) and robust_info (the last pass's) in place of the trimmed records."""
-        rp = self._robust_params(rp, loss, metric)
-        s, t = _f32(src), _f32(tgt)
-        nr = _f32(normals) if normals is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        p = params if params is not None else self.icp_params()
-        info = np.zeros(ROBUST_NINFO, np.float64)
-        out = self._icp_call(lambda res: self.L.kss_icp_robust(self.h, _p(s), len(s), _p(t), len(t), _p(nr), C.byref(p), C.byref(rp),
-                                                               C.byref(res), _p(info)),
-                             "kss_icp_robust", p, len(s), P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, rp)
-        out["robust_info"] = info
-        return out
+        return self._pair(_ROBUST, src, tgt, None, normals, params, _structs(_ROBUST, (rp,), loss, metric), trace_cap, fitness_corr)
 
     def icp_robust_dev(self, d_src, ns, d_tgt, nt, d_normals, params, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT):
         """kss_icp_robust_dev on device pointers (d_normals may be 0 / None); returns (IcpResult, robust_info)."""
-        rp = self._robust_params(rp, loss, metric)
+        rp = rp if rp is not None else robust_params(loss, metric)
         res = IcpResult()
         info = np.zeros(ROBUST_NINFO, np.float64)
         self._chk(self.L.kss_icp_robust_dev(self.h, C.c_void_p(int(d_src)), int(ns), C.c_void_p(int(d_tgt)), int(nt),
@@ -1082,52 +1183,20 @@ class Context:
         return res, info
 
     # ---- generalized ICP
-    @staticmethod
-    def _gicp_normals(normals, n, what):
-        nr = _f32(normals) if normals is not None else None
-        if nr is not None and len(nr) != n:
-            raise ValueError("%s normals must have one row per point" % what)
-        return nr
-
-    @staticmethod
-    def _gicp_rot(Rn):
-        return np.ascontiguousarray(Rn, dtype=np.float32).reshape(9) if Rn is not None else None
-
     def gicp_sums(self, src, src_normals, tgt, tgt_normals, idx, max_d2=1.0, Rn=None, gp=None):
         """kss_gicp_sums: the P2L_NSUMS record of one generalized-ICP pass over given correspondences.  Rn: the 3 x 3 applied to the
         source normals (None: identity); either set of normals may be None (computed); gp: a GicpParams (gicp_params())."""
-        gp = gp if gp is not None else gicp_params()
-        s, t = _f32(src), _f32(tgt)
-        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
-        i = np.ascontiguousarray(idx, dtype=np.int32)
-        r = self._gicp_rot(Rn)
-        sums = np.zeros(P2L_NSUMS, np.float64)
-        self._chk(self.L.kss_gicp_sums(self.h, _p(s), _p(sn), _p(t), _p(tn), _p(i), len(s), len(t), float(max_d2), _p(r), C.byref(gp),
-                                       _p(sums)), "kss_gicp_sums")
-        return sums
+        return self._sums_both(_GICP, src, src_normals, tgt, tgt_normals, idx, max_d2, Rn, _structs(_GICP, (gp,)))
 
     def gicp_sums_dev(self, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2=1.0, Rn=None, gp=None):
         """kss_gicp_sums_dev on device pointers (either normals pointer may be 0 / None; Rn stays a host array)."""
-        gp = gp if gp is not None else gicp_params()
-        r = self._gicp_rot(Rn)
-        sums = np.zeros(P2L_NSUMS, np.float64)
-        self._chk(self.L.kss_gicp_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
-                                           C.c_void_p(int(d_tgt)), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
-                                           C.c_void_p(int(d_idx)), int(n), int(nt), float(max_d2), _p(r), C.byref(gp), _p(sums)),
-                  "kss_gicp_sums_dev")
-        return sums
+        return self._sums_both_dev(_GICP, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, Rn, _structs(_GICP, (gp,)))
 
     def icp_gicp(self, src, tgt, src_normals=None, tgt_normals=None, gp=None, params=None, trace_cap=0, fitness_corr=False):
         """Generalized ICP (kss_icp_gicp): every correspondence is weighed by the inverse of the sum of both points' surface
         covariances, given as the normals of both clouds (ns x 3 and nt x 3; None: computed with kss_normals' definition at
         gp.normals_k and rounded to float).  gp: a GicpParams (gicp_params()).  The result dictionary of icp_p2l()."""
-        gp = gp if gp is not None else gicp_params()
-        s, t = _f32(src), _f32(tgt)
-        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
-        p = params if params is not None else self.icp_params()
-        return self._icp_call(lambda res: self.L.kss_icp_gicp(self.h, _p(s), len(s), _p(sn), _p(t), len(t), _p(tn), C.byref(p), C.byref(gp),
-                                                              C.byref(res)),
-                              "kss_icp_gicp", p, len(s), P2L_NSUMS, trace_cap, fitness_corr)
+        return self._pair(_GICP, src, tgt, src_normals, tgt_normals, params, _structs(_GICP, (gp,)), trace_cap, fitness_corr)
 
     def icp_gicp_dev(self, d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals, params, gp=None):
         """kss_icp_gicp_dev on device pointers (either normals pointer may be 0 / None); returns the IcpResult."""
@@ -1143,7 +1212,7 @@ class Context:
         """kss_vmap_create: the VoxelMap of the target (nt x 3) at voxel edge `leaf`; normals: nt x 3, or None to compute them at
         normals_k as icp_gicp does."""
         t = _f32(tgt)
-        tn = self._gicp_normals(normals, len(t), "target")
+        tn = _normals(normals, len(t), "target")
         vp = vmap_params(leaf=float(leaf), normals_k=int(normals_k))
         h = C.c_void_p()
         self._chk(self.L.kss_vmap_create(self.h, _p(t), len(t), _p(tn), C.byref(vp), C.byref(h)), "kss_vmap_create")
@@ -1153,30 +1222,21 @@ class Context:
         """kss_vmap_create_dev on device pointers (the normals pointer may be 0 / None)."""
         vp = vmap_params(leaf=float(leaf), normals_k=int(normals_k))
         h = C.c_void_p()
-        self._chk(self.L.kss_vmap_create_dev(self.h, C.c_void_p(int(d_tgt)), int(nt), C.c_void_p(int(d_normals)) if d_normals else None,
-                                             C.byref(vp), C.byref(h)), "kss_vmap_create_dev")
+        self._chk(self.L.kss_vmap_create_dev(self.h, _dp(d_tgt), int(nt), _dp(d_normals), C.byref(vp), C.byref(h)), "kss_vmap_create_dev")
         return VoxelMap(self, h)
 
     def vgicp_sums(self, src, src_normals, vmap, max_d2=1.0, Rn=None, gp=None):
         """kss_vgicp_sums: the P2L_NSUMS record of one voxelized generalized-ICP pass at the positions passed in.  Rn: the 3 x 3
         applied to the source normals (None: identity); src_normals may be None (computed); gp: a GicpParams (gicp_params())."""
-        gp = gp if gp is not None else gicp_params()
         s = _f32(src)
-        sn = self._gicp_normals(src_normals, len(s), "source")
-        r = self._gicp_rot(Rn)
-        sums = np.zeros(P2L_NSUMS, np.float64)
-        self._chk(self.L.kss_vgicp_sums(self.h, _p(s), _p(sn), len(s), vmap.h if vmap is not None else None, float(max_d2), _p(r),
-                                        C.byref(gp), _p(sums)), "kss_vgicp_sums")
-        return sums
+        sn = _normals(src_normals, len(s), "source")
+        return self._sums(_VGICP, False, (_p(s), _p(sn), len(s), vmap.h if vmap is not None else None, float(max_d2), _p(_rot(Rn))),
+                          _structs(_VGICP, (gp,)))
 
     def vgicp_sums_dev(self, d_src, d_src_normals, n, vmap, max_d2=1.0, Rn=None, gp=None):
         """kss_vgicp_sums_dev on device pointers (the normals pointer may be 0 / None; Rn stays a host array)."""
-        gp = gp if gp is not None else gicp_params()
-        r = self._gicp_rot(Rn)
-        sums = np.zeros(P2L_NSUMS, np.float64)
-        self._chk(self.L.kss_vgicp_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_src_normals)) if d_src_normals else None, int(n),
-                                            vmap.h, float(max_d2), _p(r), C.byref(gp), _p(sums)), "kss_vgicp_sums_dev")
-        return sums
+        return self._sums(_VGICP, True, (_dp(d_src), _dp(d_src_normals), int(n), vmap.h, float(max_d2), _p(_rot(Rn))),
+                          _structs(_VGICP, (gp,)))
 
     def icp_vgicp(self, src, vmap, src_normals=None, gp=None, params=None, trace_cap=0):
         """Voxelized generalized ICP (kss_icp_vgicp) of the source (ns x 3) against a VoxelMap: icp_gicp's metric with the voxel's
@@ -1184,16 +1244,11 @@ class Context:
         gp.normals_k).  The result dictionary of icp_gicp() plus "info", the VGICP_NINFO doubles {kept in the last pass, ns, [30]
         of the last pass, voxels}.  "fitness" is the mean squared distance to the voxel mean over the sources kept at the final
         pose, not icp()'s."""
-        gp = gp if gp is not None else gicp_params()
         s = _f32(src)
-        sn = self._gicp_normals(src_normals, len(s), "source")
+        sn = _normals(src_normals, len(s), "source")
         p = params if params is not None else self.icp_params()
-        info = np.zeros(VGICP_NINFO, np.float64)
-        out = self._icp_call(lambda res: self.L.kss_icp_vgicp(self.h, _p(s), len(s), _p(sn), vmap.h if vmap is not None else None, C.byref(p),
-                                                              C.byref(gp), C.byref(res), _p(info)),
-                             "kss_icp_vgicp", p, len(s), P2L_NSUMS, trace_cap, False)
-        out["info"] = info
-        return out
+        return self._result(_VGICP, *self._icp_call(_VGICP, False, src=_p(s), ns=len(s), sn=_p(sn), tgt=vmap.h if vmap is not None else None,
+                                                    nt=None, tn=None, p=p, structs=_structs(_VGICP, (gp,)), trace_cap=trace_cap))
 
     def icp_vgicp_dev(self, d_src, ns, d_src_normals, vmap, params, gp=None):
         """kss_icp_vgicp_dev on device pointers (the normals pointer may be 0 / None); returns (IcpResult, info)."""
@@ -1208,38 +1263,17 @@ class Context:
     def symm_sums(self, src, src_normals, tgt, tgt_normals, idx, max_d2=1.0, Rn=None, sp=None):
         """kss_symm_sums: the P2L_NSUMS record of one symmetric-ICP pass over given correspondences.  Rn: the 3 x 3 applied to the
         source normals (None: identity); either set of normals may be None (computed); sp: a SymmParams (symm_params())."""
-        sp = sp if sp is not None else symm_params()
-        s, t = _f32(src), _f32(tgt)
-        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
-        i = np.ascontiguousarray(idx, dtype=np.int32)
-        r = self._gicp_rot(Rn)
-        sums = np.zeros(P2L_NSUMS, np.float64)
-        self._chk(self.L.kss_symm_sums(self.h, _p(s), _p(sn), _p(t), _p(tn), _p(i), len(s), len(t), float(max_d2), _p(r), C.byref(sp),
-                                       _p(sums)), "kss_symm_sums")
-        return sums
+        return self._sums_both(_SYMM, src, src_normals, tgt, tgt_normals, idx, max_d2, Rn, _structs(_SYMM, (sp,)))
 
     def symm_sums_dev(self, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2=1.0, Rn=None, sp=None):
         """kss_symm_sums_dev on device pointers (either normals pointer may be 0 / None; Rn stays a host array)."""
-        sp = sp if sp is not None else symm_params()
-        r = self._gicp_rot(Rn)
-        sums = np.zeros(P2L_NSUMS, np.float64)
-        self._chk(self.L.kss_symm_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
-                                           C.c_void_p(int(d_tgt)), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
-                                           C.c_void_p(int(d_idx)), int(n), int(nt), float(max_d2), _p(r), C.byref(sp), _p(sums)),
-                  "kss_symm_sums_dev")
-        return sums
+        return self._sums_both_dev(_SYMM, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, Rn, _structs(_SYMM, (sp,)))
 
     def icp_symm(self, src, tgt, src_normals=None, tgt_normals=None, sp=None, params=None, trace_cap=0, fitness_corr=False):
         """Symmetric ICP (kss_icp_symm): the point-to-plane residual against the sum of both clouds' normals, each cloud turned by
         half the step (ns x 3 and nt x 3 normals; None: computed with kss_normals' definition at sp.normals_k and rounded to
         float).  sp: a SymmParams (symm_params()).  The result dictionary of icp_p2l()."""
-        sp = sp if sp is not None else symm_params()
-        s, t = _f32(src), _f32(tgt)
-        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
-        p = params if params is not None else self.icp_params()
-        return self._icp_call(lambda res: self.L.kss_icp_symm(self.h, _p(s), len(s), _p(sn), _p(t), len(t), _p(tn), C.byref(p), C.byref(sp),
-                                                              C.byref(res)),
-                              "kss_icp_symm", p, len(s), P2L_NSUMS, trace_cap, fitness_corr)
+        return self._pair(_SYMM, src, tgt, src_normals, tgt_normals, params, _structs(_SYMM, (sp,)), trace_cap, fitness_corr)
 
     def icp_symm_dev(self, d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals, params, sp=None):
         """kss_icp_symm_dev on device pointers (either normals pointer may be 0 / None); returns the IcpResult."""
@@ -1255,54 +1289,28 @@ class Context:
         """kss_symm_robust_sums: (sums, info) of one robust symmetric pass over given correspondences: symm_sums()' arguments and a
         RobustParams of the plane metric (rp None: the defaults of loss).  sums holds P2L_NSUMS doubles in the robust plane layout,
         info {m, c2, sum of weights, cnt}."""
-        sp = sp if sp is not None else symm_params()
-        rp = self._robust_params(rp, loss, METRIC_PLANE)
-        s, t = _f32(src), _f32(tgt)
-        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
-        i = np.ascontiguousarray(idx, dtype=np.int32)
-        r = self._gicp_rot(Rn)
-        sums = np.zeros(P2L_NSUMS, np.float64)
-        info = np.zeros(ROBUST_NINFO, np.float64)
-        self._chk(self.L.kss_symm_robust_sums(self.h, _p(s), _p(sn), _p(t), _p(tn), _p(i), len(s), len(t), float(max_d2), _p(r),
-                                              C.byref(sp), C.byref(rp), _p(sums), _p(info)), "kss_symm_robust_sums")
-        return sums, info
+        return self._sums_both(_SYMM_ROBUST, src, src_normals, tgt, tgt_normals, idx, max_d2, Rn, _structs(_SYMM_ROBUST, (sp, rp), loss),
+                               True)
 
     def symm_robust_sums_dev(self, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2=1.0, Rn=None, sp=None, rp=None,
                              loss=LOSS_TUKEY):
         """kss_symm_robust_sums_dev on device pointers (either normals pointer may be 0 / None; Rn stays a host array); returns
         (sums, info)."""
-        sp = sp if sp is not None else symm_params()
-        rp = self._robust_params(rp, loss, METRIC_PLANE)
-        r = self._gicp_rot(Rn)
-        sums = np.zeros(P2L_NSUMS, np.float64)
-        info = np.zeros(ROBUST_NINFO, np.float64)
-        self._chk(self.L.kss_symm_robust_sums_dev(self.h, C.c_void_p(int(d_src)), C.c_void_p(int(d_src_normals)) if d_src_normals else None,
-                                                  C.c_void_p(int(d_tgt)), C.c_void_p(int(d_tgt_normals)) if d_tgt_normals else None,
-                                                  C.c_void_p(int(d_idx)), int(n), int(nt), float(max_d2), _p(r), C.byref(sp), C.byref(rp),
-                                                  _p(sums), _p(info)), "kss_symm_robust_sums_dev")
-        return sums, info
+        return self._sums_both_dev(_SYMM_ROBUST, d_src, d_src_normals, d_tgt, d_tgt_normals, d_idx, n, nt, max_d2, Rn,
+                                   _structs(_SYMM_ROBUST, (sp, rp), loss), True)
 
     def icp_symm_robust(self, src, tgt, src_normals=None, tgt_normals=None, sp=None, rp=None, loss=LOSS_TUKEY, params=None, trace_cap=0,
                         fitness_corr=False):
         """Robust symmetric ICP (kss_icp_symm_robust): icp_symm()'s metric with icp_robust()'s M-estimator weights, for pairs far
         apart in angle that carry outliers or overlap in part.  Normals and sp as in icp_symm(); rp: a RobustParams of the plane
         metric (None: the defaults of loss).  The result dictionary of icp_robust(), trace_robust and robust_info included."""
-        sp = sp if sp is not None else symm_params()
-        rp = self._robust_params(rp, loss, METRIC_PLANE)
-        s, t = _f32(src), _f32(tgt)
-        sn, tn = self._gicp_normals(src_normals, len(s), "source"), self._gicp_normals(tgt_normals, len(t), "target")
-        p = params if params is not None else self.icp_params()
-        info = np.zeros(ROBUST_NINFO, np.float64)
-        out = self._icp_call(lambda res: self.L.kss_icp_symm_robust(self.h, _p(s), len(s), _p(sn), _p(t), len(t), _p(tn), C.byref(p),
-                                                                    C.byref(sp), C.byref(rp), C.byref(res), _p(info)),
-                             "kss_icp_symm_robust", p, len(s), P2L_NSUMS, trace_cap, fitness_corr, rp)
-        out["robust_info"] = info
-        return out
+        return self._pair(_SYMM_ROBUST, src, tgt, src_normals, tgt_normals, params, _structs(_SYMM_ROBUST, (sp, rp), loss), trace_cap,
+                          fitness_corr)
 
     def icp_symm_robust_dev(self, d_src, ns, d_src_normals, d_tgt, nt, d_tgt_normals, params, sp=None, rp=None, loss=LOSS_TUKEY):
         """kss_icp_symm_robust_dev on device pointers (either normals pointer may be 0 / None); returns (IcpResult, robust_info)."""
         sp = sp if sp is not None else symm_params()
-        rp = self._robust_params(rp, loss, METRIC_PLANE)
+        rp = rp if rp is not None else robust_params(loss, METRIC_PLANE)
         res = IcpResult()
         info = np.zeros(ROBUST_NINFO, np.float64)
         self._chk(self.L.kss_icp_symm_robust_dev(self.h, C.c_void_p(int(d_src)), int(ns),
@@ -1312,79 +1320,11 @@ class Context:
         return res, info
 
     # ---- point-to-plane and trimmed ICP, many pairs per call
-    def _batch_call(self, call, where, p, so, ncol, trace_cap, fitness_corr, tp=None):
-        """call(res) for a batch: the trace and fitness_corr arrays (pair 0's) attached to p / tp as in _icp_call, detached again
-        whether it returns or raises.  Returns (list of IcpResult, extras of pair 0)."""
-        tname = ("trace_robust" if isinstance(tp, RobustParams) else "trace_sim" if isinstance(tp, SimParams) else
-                 "trace_o2o" if isinstance(tp, O2oParams) else "trace_recip" if isinstance(tp, RecipParams) else "trace_trim")
-        ninfo = (SIM_NINFO if isinstance(tp, SimParams) else O2O_NINFO if isinstance(tp, O2oParams) else
-                 RECIP_NINFO if isinstance(tp, RecipParams) else TRIM_NINFO)
-        npairs = len(so) - 1
-        res = (IcpResult * npairs)()
-        ns0 = int(so[1] - so[0]) if npairs > 0 else 0
-        tr = fc = None
-        try:
-            if fitness_corr:
-                fc = (np.full(ns0, -1, np.int32), np.full(ns0, np.nan, np.float32))
-                p.fitness_idx = fc[0].ctypes.data_as(C.POINTER(C.c_int32))
-                p.fitness_d2 = fc[1].ctypes.data_as(C.POINTER(C.c_float))
-            if trace_cap > 0:
-                tr = (np.zeros((trace_cap, ncol), np.float64), np.zeros((trace_cap, 16), np.float32), C.c_int(0),
-                      np.zeros((trace_cap, ninfo), np.float64) if tp is not None else None)
-                p.trace_sums = tr[0].ctypes.data_as(C.POINTER(C.c_double))
-                p.trace_Tk = tr[1].ctypes.data_as(C.POINTER(C.c_float))
-                p.trace_cap = trace_cap
-                p.trace_n = C.pointer(tr[2])
-                if tp is not None:
-                    setattr(tp, tname, tr[3].ctypes.data_as(C.POINTER(C.c_double)))
-            self._chk(call(C.cast(res, C.c_void_p)), where)
-        finally:
-            if tr:
-                p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
-                if isinstance(tp, (RobustParams, SimParams, O2oParams, RecipParams)):
-                    setattr(tp, tname, None)
-            if fc:
-                p.fitness_idx = None; p.fitness_d2 = None
-        extra = {}
-        if tr:
-            n = tr[2].value
-            extra["trace_sums"] = tr[0][:n].copy()
-            extra["trace_Tk"] = tr[1][:n].reshape(-1, 4, 4).copy()
-            if tp is not None:
-                extra[tname] = tr[3][:n].copy()
-        if fc:
-            extra["fitness_idx"], extra["fitness_d2"] = fc
-        return list(res), extra
-
-    @staticmethod
-    def _offsets(src_off, tgt_off):
-        so = np.ascontiguousarray(src_off, dtype=np.int64)
-        to = np.ascontiguousarray(tgt_off, dtype=np.int64)
-        if len(so) != len(to) or len(so) < 1:
-            raise ValueError("src_off and tgt_off must hold npairs + 1 entries each")
-        return so, to
-
-    @staticmethod
-    def _overlaps(overlaps, npairs):
-        if overlaps is None:
-            return None
-        ov = np.ascontiguousarray(overlaps, dtype=np.float64).reshape(-1)
-        if len(ov) != npairs:
-            raise ValueError("overlaps must hold one entry per pair")
-        return ov
-
     def icp_p2l_batch(self, src_all, src_off, tgt_all, tgt_off, normals_all=None, params=None, trace_cap=0, fitness_corr=False):
         """kss_icp_p2l_batch: point-to-plane ICP of npairs pairs in one call (packed clouds, npairs + 1 offsets in points; normals_all
         laid out like tgt_all, or None to have them computed).  Returns (list of IcpResult, dictionary with pair 0's trace_sums /
         trace_Tk / fitness_idx / fitness_d2 where asked for)."""
-        s, t = _f32(src_all), _f32(tgt_all)
-        nr = _f32(normals_all) if normals_all is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        so, to = self._offsets(src_off, tgt_off)
-        p = params if params is not None else self.icp_params()
-        return self._batch_call(lambda res: self.L.kss_icp_p2l_batch(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), len(so) - 1, C.byref(p), res),
-                                "kss_icp_p2l_batch", p, so, P2L_NSUMS, trace_cap, fitness_corr)
+        return self._pairs(_P2L, src_all, src_off, tgt_all, tgt_off, None, normals_all, params, (), (), trace_cap, fitness_corr)
 
     def icp_p2l_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params):
         """kss_icp_p2l_batch_dev on device pointers (d_normals_all may be 0 / None); returns the list of IcpResult."""
@@ -1399,27 +1339,15 @@ class Context:
                           params=None, trace_cap=0, fitness_corr=False):
         """kss_icp_trimmed_batch: trimmed ICP of npairs pairs in one call.  overlaps: one per pair, or None for `overlap` everywhere.
         Returns (list of IcpResult, trim_info of every pair as npairs x TRIM_NINFO, dictionary with pair 0's traces)."""
-        s, t = _f32(src_all), _f32(tgt_all)
-        nr = _f32(normals_all) if normals_all is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        ov = self._overlaps(overlaps, npairs)
-        p = params if params is not None else self.icp_params()
-        tp = TrimParams(float(overlap), int(metric), None)
-        info = np.zeros((max(npairs, 0), TRIM_NINFO), np.float64)
-        res, extra = self._batch_call(
-            lambda res: self.L.kss_icp_trimmed_batch(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), npairs, C.byref(p), C.byref(tp), _p(ov), res, _p(info)),
-            "kss_icp_trimmed_batch", p, so, P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, tp)
-        return res, info, extra
+        return self._pairs(_TRIMMED, src_all, src_off, tgt_all, tgt_off, None, normals_all, params,
+                           (TrimParams(float(overlap), int(metric), None),), (overlaps,), trace_cap, fitness_corr)
 
     def icp_trimmed_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params, overlaps=None, overlap=0.5,
                               metric=METRIC_POINT):
         """kss_icp_trimmed_batch_dev on device pointers; returns (list of IcpResult, trim_info npairs x TRIM_NINFO)."""
         so, to = self._offsets(src_off, tgt_off)
         npairs = len(so) - 1
-        ov = self._overlaps(overlaps, npairs)
+        ov = _per_pair(overlaps, np.float64, npairs, "overlaps")
         res = (IcpResult * npairs)()
         tp = TrimParams(float(overlap), int(metric), None)
         info = np.zeros((npairs, TRIM_NINFO), np.float64)
@@ -1432,27 +1360,15 @@ class Context:
                       params=None, trace_cap=0, fitness_corr=False):
         """kss_icp_o2o_batch: one-to-one ICP of npairs pairs in one call.  Arguments as icp_trimmed_batch().  Returns (list of
         IcpResult, o2o_info of every pair as npairs x O2O_NINFO, dictionary with pair 0's traces)."""
-        s, t = _f32(src_all), _f32(tgt_all)
-        nr = _f32(normals_all) if normals_all is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        ov = self._overlaps(overlaps, npairs)
-        p = params if params is not None else self.icp_params()
-        op = O2oParams(float(overlap), int(metric), None)
-        info = np.zeros((max(npairs, 0), O2O_NINFO), np.float64)
-        res, extra = self._batch_call(
-            lambda res: self.L.kss_icp_o2o_batch(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), npairs, C.byref(p), C.byref(op), _p(ov), res, _p(info)),
-            "kss_icp_o2o_batch", p, so, P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, op)
-        return res, info, extra
+        return self._pairs(_O2O, src_all, src_off, tgt_all, tgt_off, None, normals_all, params, (O2oParams(float(overlap), int(metric), None),),
+                           (overlaps,), trace_cap, fitness_corr)
 
     def icp_o2o_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params, overlaps=None, overlap=1.0,
                           metric=METRIC_POINT):
         """kss_icp_o2o_batch_dev on device pointers; returns (list of IcpResult, o2o_info npairs x O2O_NINFO)."""
         so, to = self._offsets(src_off, tgt_off)
         npairs = len(so) - 1
-        ov = self._overlaps(overlaps, npairs)
+        ov = _per_pair(overlaps, np.float64, npairs, "overlaps")
         res = (IcpResult * npairs)()
         op = O2oParams(float(overlap), int(metric), None)
         info = np.zeros((npairs, O2O_NINFO), np.float64)
@@ -1485,38 +1401,24 @@ class Context:
         o, to = self._offsets(off, tgt_off)
         nseg = len(o) - 1
         info = np.zeros((max(nseg, 0), 3), np.float64)
-        self._chk(self.L.kss_recip_filter_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(o), C.c_void_p(int(d_tgt_all)), _p(to), nseg,
-                                                    C.c_void_p(int(d_idx_all)), C.c_void_p(int(d_d2_all)), float(max_d2), int(nn_fma),
-                                                    C.c_void_p(int(d_idx_out_all)) if d_idx_out_all else None,
-                                                    C.c_void_p(int(d_d2_out_all)) if d_d2_out_all else None, _p(info)),
-                  "kss_recip_filter_batch_dev")
+        self._chk(self.L.kss_recip_filter_batch_dev(self.h, _dp(d_src_all), _p(o), _dp(d_tgt_all), _p(to), nseg, _dp(d_idx_all),
+                                                    _dp(d_d2_all), float(max_d2), int(nn_fma), _dp(d_idx_out_all), _dp(d_d2_out_all),
+                                                    _p(info)), "kss_recip_filter_batch_dev")
         return info
 
     def icp_recip_batch(self, src_all, src_off, tgt_all, tgt_off, normals_all=None, overlaps=None, overlap=1.0, metric=METRIC_POINT,
                         params=None, trace_cap=0, fitness_corr=False):
         """kss_icp_recip_pairs: reciprocal ICP of npairs pairs in one call.  Arguments as icp_o2o_batch().  Returns (list of
         IcpResult, recip_info of every pair as npairs x RECIP_NINFO, dictionary with pair 0's traces, trace_recip among them)."""
-        s, t = _f32(src_all), _f32(tgt_all)
-        nr = _f32(normals_all) if normals_all is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        ov = self._overlaps(overlaps, npairs)
-        p = params if params is not None else self.icp_params()
-        rp = RecipParams(float(overlap), int(metric), None)
-        info = np.zeros((max(npairs, 0), RECIP_NINFO), np.float64)
-        res, extra = self._batch_call(
-            lambda res: self.L.kss_icp_recip_pairs(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), npairs, C.byref(p), C.byref(rp), _p(ov), res, _p(info)),
-            "kss_icp_recip_pairs", p, so, P2L_NSUMS if metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, rp)
-        return res, info, extra
+        return self._pairs(_RECIP, src_all, src_off, tgt_all, tgt_off, None, normals_all, params,
+                           (RecipParams(float(overlap), int(metric), None),), (overlaps,), trace_cap, fitness_corr)
 
     def icp_recip_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params, overlaps=None, overlap=1.0,
                             metric=METRIC_POINT):
         """kss_icp_recip_pairs_dev on device pointers; returns (list of IcpResult, recip_info npairs x RECIP_NINFO)."""
         so, to = self._offsets(src_off, tgt_off)
         npairs = len(so) - 1
-        ov = self._overlaps(overlaps, npairs)
+        ov = _per_pair(overlaps, np.float64, npairs, "overlaps")
         res = (IcpResult * npairs)()
         rp = RecipParams(float(overlap), int(metric), None)
         info = np.zeros((npairs, RECIP_NINFO), np.float64)
@@ -1529,23 +1431,14 @@ class Context:
         """kss_icp_sim_batch: similarity ICP of npairs pairs in one call.  overlaps: one per pair, or None for sp.overlap everywhere.
         Returns (list of IcpResult, sim_info of every pair as npairs x SIM_NINFO -- column 5 is the pair's scale --, dictionary with
         pair 0's traces)."""
-        s, t = _f32(src_all), _f32(tgt_all)
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        ov = self._overlaps(overlaps, npairs)
-        p = params if params is not None else self.icp_params()
-        sp = sp if sp is not None else sim_params()
-        info = np.zeros((max(npairs, 0), SIM_NINFO), np.float64)
-        res, extra = self._batch_call(
-            lambda res: self.L.kss_icp_sim_batch(self.h, _p(s), _p(so), _p(t), _p(to), npairs, C.byref(p), C.byref(sp), _p(ov), res, _p(info)),
-            "kss_icp_sim_batch", p, so, NSUMS, trace_cap, fitness_corr, sp)
-        return res, info, extra
+        return self._pairs(_SIM, src_all, src_off, tgt_all, tgt_off, None, None, params, _structs(_SIM, (sp,)), (overlaps,), trace_cap,
+                           fitness_corr)
 
     def icp_sim_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, params, overlaps=None, sp=None):
         """kss_icp_sim_batch_dev on device pointers; returns (list of IcpResult, sim_info npairs x SIM_NINFO)."""
         so, to = self._offsets(src_off, tgt_off)
         npairs = len(so) - 1
-        ov = self._overlaps(overlaps, npairs)
+        ov = _per_pair(overlaps, np.float64, npairs, "overlaps")
         res = (IcpResult * npairs)()
         sp = sp if sp is not None else sim_params()
         info = np.zeros((npairs, SIM_NINFO), np.float64)
@@ -1555,42 +1448,21 @@ class Context:
         return list(res), info
 
     # ---- robust ICP, many pairs per call
-    @staticmethod
-    def _scales(scales, npairs):
-        if scales is None:
-            return None
-        sc = np.ascontiguousarray(scales, dtype=np.float64).reshape(-1)
-        if len(sc) != npairs:
-            raise ValueError("scales must hold one entry per pair")
-        return sc
-
     def icp_robust_batch(self, src_all, src_off, tgt_all, tgt_off, normals_all=None, rp=None, loss=LOSS_HUBER, metric=METRIC_POINT,
                          scales=None, params=None, trace_cap=0, fitness_corr=False):
         """kss_icp_robust_batch: robust ICP of npairs pairs in one call.  rp as in icp_robust() (loss, metric, tune and min_scale of
         the whole batch); scales: one per pair (> 0 fixed, 0 automatic), or None for rp.scale everywhere.  Returns (list of
         IcpResult, robust_info of every pair as npairs x ROBUST_NINFO, dictionary with pair 0's traces, trace_robust among them)."""
-        rp = self._robust_params(rp, loss, metric)
-        s, t = _f32(src_all), _f32(tgt_all)
-        nr = _f32(normals_all) if normals_all is not None else None
-        if nr is not None and len(nr) != len(t):
-            raise ValueError("normals must have one row per target point")
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        sc = self._scales(scales, npairs)
-        p = params if params is not None else self.icp_params()
-        info = np.zeros((max(npairs, 0), ROBUST_NINFO), np.float64)
-        res, extra = self._batch_call(
-            lambda res: self.L.kss_icp_robust_batch(self.h, _p(s), _p(so), _p(t), _p(to), _p(nr), npairs, C.byref(p), C.byref(rp), _p(sc), res, _p(info)),
-            "kss_icp_robust_batch", p, so, P2L_NSUMS if rp.metric == METRIC_PLANE else NSUMS, trace_cap, fitness_corr, rp)
-        return res, info, extra
+        return self._pairs(_ROBUST, src_all, src_off, tgt_all, tgt_off, None, normals_all, params,
+                           _structs(_ROBUST, (rp,), loss, metric), (scales,), trace_cap, fitness_corr)
 
     def icp_robust_batch_dev(self, d_src_all, src_off, d_tgt_all, tgt_off, d_normals_all, params, rp=None, loss=LOSS_HUBER,
                              metric=METRIC_POINT, scales=None):
         """kss_icp_robust_batch_dev on device pointers; returns (list of IcpResult, robust_info npairs x ROBUST_NINFO)."""
-        rp = self._robust_params(rp, loss, metric)
+        rp = rp if rp is not None else robust_params(loss, metric)
         so, to = self._offsets(src_off, tgt_off)
         npairs = len(so) - 1
-        sc = self._scales(scales, npairs)
+        sc = _per_pair(scales, np.float64, npairs, "scales")
         res = (IcpResult * npairs)()
         info = np.zeros((npairs, ROBUST_NINFO), np.float64)
         self._chk(self.L.kss_icp_robust_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
@@ -1599,94 +1471,38 @@ class Context:
         return list(res), info
 
     # ---- generalized ICP, many pairs per call
-    @staticmethod
-    def _epsilons(epsilons, npairs):
-        if epsilons is None:
-            return None
-        ep = np.ascontiguousarray(epsilons, dtype=np.float64).reshape(-1)
-        if len(ep) != npairs:
-            raise ValueError("epsilons must hold one entry per pair")
-        return ep
-
     def icp_gicp_batch(self, src_all, src_off, tgt_all, tgt_off, src_normals_all=None, tgt_normals_all=None, epsilons=None, gp=None,
                        params=None, trace_cap=0, fitness_corr=False):
         """kss_icp_gicp_batch: generalized ICP of npairs pairs in one call (packed clouds, npairs + 1 offsets in points; the normals
         laid out like their clouds, either None to have them computed per cloud at gp.normals_k).  epsilons: one per pair, or None
         for gp.epsilon everywhere.  Returns (list of IcpResult, dictionary with pair 0's trace_sums / trace_Tk / fitness_idx /
         fitness_d2 where asked for)."""
-        gp = gp if gp is not None else gicp_params()
-        s, t = _f32(src_all), _f32(tgt_all)
-        sn, tn = self._gicp_normals(src_normals_all, len(s), "source"), self._gicp_normals(tgt_normals_all, len(t), "target")
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        ep = self._epsilons(epsilons, npairs)
-        p = params if params is not None else self.icp_params()
-        return self._batch_call(
-            lambda res: self.L.kss_icp_gicp_batch(self.h, _p(s), _p(so), _p(sn), _p(t), _p(to), _p(tn), npairs, C.byref(p), C.byref(gp),
-                                                  _p(ep), res),
-            "kss_icp_gicp_batch", p, so, P2L_NSUMS, trace_cap, fitness_corr)
+        return self._pairs(_GICP, src_all, src_off, tgt_all, tgt_off, src_normals_all, tgt_normals_all, params, _structs(_GICP, (gp,)),
+                           (epsilons,), trace_cap, fitness_corr)
 
     def icp_gicp_batch_dev(self, d_src_all, src_off, d_src_normals_all, d_tgt_all, tgt_off, d_tgt_normals_all, params=None, epsilons=None,
                            gp=None, trace_cap=0):
         """kss_icp_gicp_batch_dev on device pointers (either normals pointer may be 0 / None; the offsets stay host arrays).
         Returns (list of IcpResult, dictionary with pair 0's trace_sums / trace_Tk where asked for)."""
-        gp = gp if gp is not None else gicp_params()
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        ep = self._epsilons(epsilons, npairs)
-        p = params if params is not None else self.icp_params()
-        return self._batch_call(
-            lambda res: self.L.kss_icp_gicp_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so),
-                                                      C.c_void_p(int(d_src_normals_all)) if d_src_normals_all else None,
-                                                      C.c_void_p(int(d_tgt_all)), _p(to),
-                                                      C.c_void_p(int(d_tgt_normals_all)) if d_tgt_normals_all else None, npairs,
-                                                      C.byref(p), C.byref(gp), _p(ep), res),
-            "kss_icp_gicp_batch_dev", p, so, P2L_NSUMS, trace_cap, False)
+        return self._pairs_dev_traced(_GICP, d_src_all, src_off, d_tgt_all, tgt_off, d_src_normals_all, d_tgt_normals_all, params,
+                               _structs(_GICP, (gp,)), (epsilons,), trace_cap)
 
     # ---- symmetric ICP, many pairs per call
-    @staticmethod
-    def _aligns(aligns, npairs):
-        if aligns is None:
-            return None
-        al = np.ascontiguousarray(aligns, dtype=np.int32).reshape(-1)
-        if len(al) != npairs:
-            raise ValueError("aligns must hold one entry per pair")
-        return al
-
     def icp_symm_batch(self, src_all, src_off, tgt_all, tgt_off, src_normals_all=None, tgt_normals_all=None, aligns=None, sp=None,
                        params=None, trace_cap=0, fitness_corr=False):
         """kss_icp_symm_batch: symmetric ICP of npairs pairs in one call (packed clouds, npairs + 1 offsets in points; the normals
         laid out like their clouds, either None to have them computed per cloud at sp.normals_k).  aligns: one align_normals (0 or
         1) per pair, or None for sp.align_normals everywhere.  Returns (list of IcpResult, dictionary with pair 0's trace_sums /
         trace_Tk / fitness_idx / fitness_d2 where asked for)."""
-        sp = sp if sp is not None else symm_params()
-        s, t = _f32(src_all), _f32(tgt_all)
-        sn, tn = self._gicp_normals(src_normals_all, len(s), "source"), self._gicp_normals(tgt_normals_all, len(t), "target")
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        al = self._aligns(aligns, npairs)
-        p = params if params is not None else self.icp_params()
-        return self._batch_call(
-            lambda res: self.L.kss_icp_symm_batch(self.h, _p(s), _p(so), _p(sn), _p(t), _p(to), _p(tn), npairs, C.byref(p), C.byref(sp),
-                                                  _p(al), res),
-            "kss_icp_symm_batch", p, so, P2L_NSUMS, trace_cap, fitness_corr)
+        return self._pairs(_SYMM, src_all, src_off, tgt_all, tgt_off, src_normals_all, tgt_normals_all, params, _structs(_SYMM, (sp,)),
+                           (aligns,), trace_cap, fitness_corr)
 
     def icp_symm_batch_dev(self, d_src_all, src_off, d_src_normals_all, d_tgt_all, tgt_off, d_tgt_normals_all, params=None, aligns=None,
                            sp=None, trace_cap=0):
         """kss_icp_symm_batch_dev on device pointers (either normals pointer may be 0 / None; the offsets and aligns stay host
         arrays).  Returns (list of IcpResult, dictionary with pair 0's trace_sums / trace_Tk where asked for)."""
-        sp = sp if sp is not None else symm_params()
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        al = self._aligns(aligns, npairs)
-        p = params if params is not None else self.icp_params()
-        return self._batch_call(
-            lambda res: self.L.kss_icp_symm_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so),
-                                                      C.c_void_p(int(d_src_normals_all)) if d_src_normals_all else None,
-                                                      C.c_void_p(int(d_tgt_all)), _p(to),
-                                                      C.c_void_p(int(d_tgt_normals_all)) if d_tgt_normals_all else None, npairs,
-                                                      C.byref(p), C.byref(sp), _p(al), res),
-            "kss_icp_symm_batch_dev", p, so, P2L_NSUMS, trace_cap, False)
+        return self._pairs_dev_traced(_SYMM, d_src_all, src_off, d_tgt_all, tgt_off, d_src_normals_all, d_tgt_normals_all, params,
+                               _structs(_SYMM, (sp,)), (aligns,), trace_cap)
 
     # ---- robust symmetric ICP, many pairs per call
     def icp_symm_robust_batch(self, src_all, src_off, tgt_all, tgt_off, src_normals_all=None, tgt_normals_all=None, aligns=None,
@@ -1695,57 +1511,30 @@ class Context:
         icp_symm_batch(); rp as in icp_symm_robust() (loss, tune and min_scale of the whole batch); scales: one per pair (> 0 fixed,
         0 automatic), or None for rp.scale everywhere.  Returns (list of IcpResult, robust_info of every pair as npairs x
         ROBUST_NINFO, dictionary with pair 0's traces, trace_robust among them)."""
-        sp = sp if sp is not None else symm_params()
-        rp = self._robust_params(rp, loss, METRIC_PLANE)
-        s, t = _f32(src_all), _f32(tgt_all)
-        sn, tn = self._gicp_normals(src_normals_all, len(s), "source"), self._gicp_normals(tgt_normals_all, len(t), "target")
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        al = self._aligns(aligns, npairs)
-        sc = self._scales(scales, npairs)
-        p = params if params is not None else self.icp_params()
-        info = np.zeros((max(npairs, 0), ROBUST_NINFO), np.float64)
-        res, extra = self._batch_call(
-            lambda res: self.L.kss_icp_symm_robust_batch(self.h, _p(s), _p(so), _p(sn), _p(t), _p(to), _p(tn), npairs, C.byref(p),
-                                                         C.byref(sp), _p(al), C.byref(rp), _p(sc), res, _p(info)),
-            "kss_icp_symm_robust_batch", p, so, P2L_NSUMS, trace_cap, fitness_corr, rp)
-        return res, info, extra
+        return self._pairs(_SYMM_ROBUST, src_all, src_off, tgt_all, tgt_off, src_normals_all, tgt_normals_all, params,
+                           _structs(_SYMM_ROBUST, (sp, rp), loss), (aligns, scales), trace_cap, fitness_corr)
 
     def icp_symm_robust_batch_dev(self, d_src_all, src_off, d_src_normals_all, d_tgt_all, tgt_off, d_tgt_normals_all, params=None,
                                   aligns=None, scales=None, sp=None, rp=None, loss=LOSS_TUKEY, trace_cap=0):
         """kss_icp_symm_robust_batch_dev on device pointers (either normals pointer may be 0 / None; the offsets, aligns and scales
         stay host arrays).  Returns (list of IcpResult, robust_info npairs x ROBUST_NINFO, dictionary with pair 0's traces)."""
-        sp = sp if sp is not None else symm_params()
-        rp = self._robust_params(rp, loss, METRIC_PLANE)
-        so, to = self._offsets(src_off, tgt_off)
-        npairs = len(so) - 1
-        al = self._aligns(aligns, npairs)
-        sc = self._scales(scales, npairs)
-        p = params if params is not None else self.icp_params()
-        info = np.zeros((max(npairs, 0), ROBUST_NINFO), np.float64)
-        res, extra = self._batch_call(
-            lambda res: self.L.kss_icp_symm_robust_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so),
-                                                             C.c_void_p(int(d_src_normals_all)) if d_src_normals_all else None,
-                                                             C.c_void_p(int(d_tgt_all)), _p(to),
-                                                             C.c_void_p(int(d_tgt_normals_all)) if d_tgt_normals_all else None, npairs,
-                                                             C.byref(p), C.byref(sp), _p(al), C.byref(rp), _p(sc), res, _p(info)),
-            "kss_icp_symm_robust_batch_dev", p, so, P2L_NSUMS, trace_cap, False, rp)
-        return res, info, extra
+        return self._pairs_dev_traced(_SYMM_ROBUST, d_src_all, src_off, d_tgt_all, tgt_off, d_src_normals_all,
+                               d_tgt_normals_all, params, _structs(_SYMM_ROBUST, (sp, rp), loss), (aligns, scales), trace_cap)
 
     def trim_threshold_batch(self, d2_all, off, overlaps, max_d2=1.0):
         """kss_trim_threshold_batch: {m, k, tau, kept} of every segment [off[i], off[i + 1]) of d2_all, nseg x TRIM_NINFO."""
         d = np.ascontiguousarray(d2_all, dtype=np.float32).reshape(-1)
         o = np.ascontiguousarray(off, dtype=np.int64)
-        ov = self._overlaps(overlaps, len(o) - 1)
+        ov = _per_pair(overlaps, np.float64, len(o) - 1, "overlaps")
         info = np.zeros((max(len(o) - 1, 0), TRIM_NINFO), np.float64)
         self._chk(self.L.kss_trim_threshold_batch(self.h, _p(d), _p(o), len(o) - 1, float(max_d2), _p(ov), _p(info)), "kss_trim_threshold_batch")
         return info
 
     def trim_threshold_batch_dev(self, d_d2_all, off, overlaps, max_d2=1.0):
         o = np.ascontiguousarray(off, dtype=np.int64)
-        ov = self._overlaps(overlaps, len(o) - 1)
+        ov = _per_pair(overlaps, np.float64, len(o) - 1, "overlaps")
         info = np.zeros((max(len(o) - 1, 0), TRIM_NINFO), np.float64)
-        self._chk(self.L.kss_trim_threshold_batch_dev(self.h, C.c_void_p(int(d_d2_all)), _p(o), len(o) - 1, float(max_d2), _p(ov), _p(info)),
+        self._chk(self.L.kss_trim_threshold_batch_dev(self.h, _dp(d_d2_all), _p(o), len(o) - 1, float(max_d2), _p(ov), _p(info)),
                   "kss_trim_threshold_batch_dev")
         return info
 
