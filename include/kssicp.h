@@ -775,14 +775,37 @@ int kss_vgicp_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_src_norm
  * mean, not to a nearest target point.
  * last_info (may be NULL): {kept in the last pass of the loop, ns, [30] of that pass, voxels of the map}.
  * p->nn_mode, p->nn_fma and the nn_* tuning fields are not read.  KSS_ERR_ARG: everything kss_vgicp_sums refuses, a NULL p or res,
- * a set p->allreduce, a set p->fitness_idx or p->fitness_d2 (there are no correspondences to return).  Many pairs per call, a
- * count weight, a 7- or 27-voxel neighbourhood, robust or trimmed weights, the C++ mirror classes and the CLI do not have this
- * method. */
+ * a set p->allreduce, a set p->fitness_idx or p->fitness_d2 (there are no correspondences to return).  A count weight, a 7- or
+ * 27-voxel neighbourhood, robust or trimmed weights, the C++ mirror classes and the CLI do not have this method. */
 #define KSS_VGICP_NINFO 4
 int kss_icp_vgicp(kss_ctx *ctx, const float *src, int64_t ns, const float *src_normals, const kss_vmap *map, const kss_icp_params *p,
                   const kss_gicp_params *gp, kss_icp_result *res, double last_info[KSS_VGICP_NINFO]);
 int kss_icp_vgicp_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const kss_vmap *map,
                       const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res, double last_info[KSS_VGICP_NINFO]);
+
+/* ---- voxelized generalized ICP for MANY scans against ONE map per call ----
+ * src_all and src_off as in kss_icp_gicp_batch: packed float[n][3] scans and nscans + 1 HOST offsets in points (the _dev form takes
+ * device scans and normals; the offsets stay a host array); offsets whose first entry is not 0 address a sub-range of the packed
+ * arrays.  src_normals_all is laid out like src_all; NULL: each scan's normals are computed as kss_icp_vgicp computes them, per
+ * scan, at gp->normals_k from the scan as passed in.  epsilons: one double per scan, or NULL for gp->epsilon everywhere.
+ * p->max_corr_dist and the convergence criteria hold for the whole call.  One map serves every scan and is not changed.
+ * Nothing is redefined: scan i's record -- T, iterations, converged, state, last_mse, fitness and its KSS_VGICP_NINFO doubles
+ * last_info[i * KSS_VGICP_NINFO ..] (last_info may be NULL) -- is the kss_icp_vgicp call on that scan BIT FOR BIT, in any batch
+ * order and any split over calls; the fitness too, since it is [28] / [0] of one more evaluation of the same fixed-order record at
+ * F_i * the original scan (NaN where nothing is kept).  trace_* describe scan 0; results[i].pair_id = i.  The scans run in
+ * lockstep, one small table copy and two launches per pass whatever the scan count; a scan that ends -- converged,
+ * KSS_STATE_NO_CORRESPONDENCES, KSS_STATE_DEGENERATE -- leaves the others untouched.  A start pose per scan is the caller's to
+ * apply to the scan beforehand; a map per scan is not offered.
+ * KSS_ERR_ARG: a NULL ctx (refused before anything touches the device), src_all, src_off, p, gp or results; nscans <= 0; an
+ * empty scan or decreasing offsets; not a live map of ctx; gp->epsilon or an epsilons entry outside (0, 1] or NaN; normals_k
+ * outside 3..64 where the normals are computed; a set p->allreduce, p->fitness_idx or p->fitness_d2; more partial rows than
+ * kss_icp_p2l_batch takes (the sum over the scans of min(2048, ceil(ns_i / 256)) above 0x7fff0000). */
+int kss_icp_vgicp_batch(kss_ctx *ctx, const float *src_all, const int64_t *src_off, const float *src_normals_all, int nscans,
+                        const kss_vmap *map, const kss_icp_params *p, const kss_gicp_params *gp, const double *epsilons,
+                        kss_icp_result *results, double *last_info /* nscans * KSS_VGICP_NINFO, may be NULL */);
+int kss_icp_vgicp_batch_dev(kss_ctx *ctx, const float *d_src_all, const int64_t *src_off, const float *d_src_normals_all, int nscans,
+                            const kss_vmap *map, const kss_icp_params *p, const kss_gicp_params *gp, const double *epsilons,
+                            kss_icp_result *results, double *last_info /* nscans * KSS_VGICP_NINFO, may be NULL */);
 
 /* ---- symmetric ICP (point-to-plane on the sum of both normals; Rusinkiewicz: A Symmetric Objective Function for ICP, SIGGRAPH
  * 2019; PCL's TransformationEstimationSymmetricPointToPlaneLLS) for one pair ----

@@ -61,6 +61,7 @@ SYMBOLS = [
     "kss_recip_filter_batch", "kss_recip_filter_batch_dev", "kss_icp_recip_pairs", "kss_icp_recip_pairs_dev",
     "kss_vmap_default_params", "kss_vmap_create", "kss_vmap_create_dev", "kss_vmap_destroy", "kss_vmap_info", "kss_vmap_read",
     "kss_vgicp_sums", "kss_vgicp_sums_dev", "kss_icp_vgicp", "kss_icp_vgicp_dev",
+    "kss_icp_vgicp_batch", "kss_icp_vgicp_batch_dev",
 ]
 
 
@@ -249,6 +250,8 @@ def _declare(L):
         getattr(L, n).argtypes = [vp, vp, vp, i64, vp, dbl, vp, C.POINTER(GicpParams), vp]
     for n in ("kss_icp_vgicp", "kss_icp_vgicp_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, vp, C.POINTER(IcpParams), C.POINTER(GicpParams), C.POINTER(IcpResult), vp]
+    for n in ("kss_icp_vgicp_batch", "kss_icp_vgicp_batch_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, vp, C.c_int, vp, C.POINTER(IcpParams), C.POINTER(GicpParams), vp, vp, vp]
     for n in ("kss_icp_p2l_batch", "kss_icp_p2l_batch_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(IcpParams), vp]
     for n in ("kss_icp_trimmed_batch", "kss_icp_trimmed_batch_dev"):
@@ -638,9 +641,10 @@ def _structs(m, given, *a):
 
 
 # The cloud arguments of a kss_icp_* entry in C order, by the record's `normals`, picked from (source, its count or offsets, its
-# normals, target, its count or offsets, its normals); "map": the source with its normals, then a voxel map as the target.
+# normals, target, its count or offsets, its normals); "map": the source with its normals, then a voxel map as the target;
+# "scans": packed scans with their offsets and normals -- the one map they share follows the scan count (_icp_call).
 _CLOUDS = {"both": operator.itemgetter(0, 1, 2, 3, 4, 5), "target": operator.itemgetter(0, 1, 3, 4, 5),
-           "none": operator.itemgetter(0, 1, 3, 4), "map": operator.itemgetter(0, 1, 2, 3)}
+           "none": operator.itemgetter(0, 1, 3, 4), "map": operator.itemgetter(0, 1, 2, 3), "scans": operator.itemgetter(0, 1, 2)}
 
 
 # What differs between the kss_icp_* families, and nothing else:
@@ -671,6 +675,7 @@ _SYMM_ROBUST = Metric("kss_icp_symm_robust", "kss_icp_symm_robust_batch", "kss_s
                       (lambda loss: symm_params(), lambda loss: robust_params(loss, METRIC_PLANE)), "trace_robust", "robust_info",
                       ROBUST_NINFO, (_ALIGNS, _SCALES), P2L_NSUMS)
 _VGICP = Metric("kss_icp_vgicp", None, "kss_vgicp_sums", "map", (gicp_params,), None, "info", VGICP_NINFO, (), P2L_NSUMS)
+_VGICP_BATCH = Metric(None, "kss_icp_vgicp_batch", None, "scans", (gicp_params,), None, "info", VGICP_NINFO, (_EPSILONS,), P2L_NSUMS)
 
 
 # ---- context --------------------------------------------------------------------------------------------
@@ -839,6 +844,8 @@ class Context:
             npairs = len(so) - 1
             res = (IcpResult * npairs)()
             args.append(npairs)
+            if normals == "scans":                         # (many scans against one map: the map follows their count)
+                args.append(tgt)
             args.append(C.byref(p))
             for st, a, (noun, dtype) in zip(structs, arrays, per_pair):
                 args.append(C.byref(st))
@@ -1562,6 +1569,28 @@ class Context:
         self._chk(self.L.kss_icp_batch_dev(self.h, C.c_void_p(int(d_src_all)), _p(so), C.c_void_p(int(d_tgt_all)), _p(to),
                                            npairs, C.byref(params), C.cast(res, C.c_void_p)), "kss_icp_batch_dev")
         return res
+
+    # ---- voxelized generalized ICP, many scans against one map per call
+    def icp_vgicp_batch(self, src_all, src_off, vmap, src_normals_all=None, epsilons=None, gp=None, params=None, trace_cap=0):
+        """kss_icp_vgicp_batch: voxelized generalized ICP of nscans scans (packed, nscans + 1 offsets in points) against ONE
+        VoxelMap in one call.  src_normals_all: laid out like src_all, or None to have every scan's computed at gp.normals_k;
+        epsilons: one per scan, or None for gp.epsilon everywhere.  Returns a list of icp_vgicp()'s dictionaries, one per scan
+        ("info": the scan's VGICP_NINFO doubles, "pair_id": its index), scan 0's trace_sums / trace_Tk on entry 0 where asked for."""
+        s = _f32(src_all)
+        sn = _normals(src_normals_all, len(s), "source")
+        so = np.ascontiguousarray(src_off, dtype=np.int64)
+        p = params if params is not None else self.icp_params()
+        res, info, extra = self._icp_call(_VGICP_BATCH, False, _p(s), _p(so), _p(sn), vmap.h if vmap is not None else None, None, None, p,
+                                          _structs(_VGICP_BATCH, (gp,)), (epsilons,), so, trace_cap)
+        return [dict(self._result(_VGICP_BATCH, r, info[i], extra if i == 0 else {}), pair_id=r.pair_id) for i, r in enumerate(res)]
+
+    def icp_vgicp_batch_dev(self, d_src_all, src_off, d_src_normals_all, vmap, params, epsilons=None, gp=None):
+        """kss_icp_vgicp_batch_dev on device pointers (the normals pointer may be 0 / None; the offsets and epsilons stay host
+        arrays); returns (list of IcpResult, info nscans x VGICP_NINFO)."""
+        so = np.ascontiguousarray(src_off, dtype=np.int64)
+        res, info, _ = self._icp_call(_VGICP_BATCH, True, _dp(d_src_all), _p(so), _dp(d_src_normals_all), vmap.h, None, None, params,
+                                      _structs(_VGICP_BATCH, (gp,)), (epsilons,), so)
+        return list(res), info
 
     def transform_apply_f32(self, T, pts):
         a = _f32(pts)

@@ -1159,6 +1159,58 @@ int kss_icp_vgicp(kss_ctx* c, const float* src, int64_t ns, const float* src_nor
     return icp_vgicp_any(c, true, src, ns, src_normals, m, p, gp, res, last_info);
 }
 
+// Many scans against one map.  Every check comes before anything touches the device; then the scans as
+// pair_rebase / pair_stage bring a batch in (indexed from 0, a host caller's slice into stage_src / pb_snrm), the normals that are
+// missing scan by scan as kss_icp_vgicp computes them (batch_normals_dev into pb_snrm), and vgicpb_run_dev.
+static int icp_vgicp_batch_any(kss_ctx* c, bool host, const float* src, const int64_t* src_off, const float* snrm, int nscans, const kss_vmap* m,
+                               const kss_icp_params* p, const kss_gicp_params* gp, const double* epsilons, kss_icp_result* res, double* last_info) {
+    if (!c) return KSS_ERR_ARG;
+    const char* who = "icp_vgicp_batch";
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!src || !src_off || !p || !gp || !res) return bad("null argument");
+    if (nscans <= 0) return bad("bad batch");
+    if (src_off[0] < 0) return bad("negative offset");
+    int64_t rows = 0;
+    for (int i = 0; i < nscans; ++i) {
+        const int64_t n = src_off[i + 1] - src_off[i];
+        if (n <= 0) return bad("empty scan");
+        if (n > 0x7fff0000ll) return bad("cloud too large");
+        rows += stream_blocks(n);
+        if (rows > PAIRB_INDEX_MAX) return bad("batch too large for 32-bit indexing");
+    }
+    if (!vmap_live(c, m)) return bad("not a live map of this context");
+    KCHK(gicp_check(c, who, gp, !snrm, nscans, epsilons));
+    if (p->allreduce) return bad("the source-row split (allreduce) is not available for voxelized generalized ICP");
+    if (p->fitness_idx || p->fitness_d2) return bad("there are no correspondences to return: fitness_idx and fitness_d2 must be NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t s0 = src_off[0];
+    std::vector<int64_t> so((size_t)nscans + 1);
+    for (int i = 0; i <= nscans; ++i) so[i] = src_off[i] - s0;
+    src += 3 * s0;
+    if (snrm) snrm += 3 * s0;
+    if (host) {
+        const size_t sb = (size_t)so[nscans] * 3 * sizeof(float);
+        KCHK(upload(c, c->stage_src, src, sb));
+        src = (const float*)c->stage_src.p;
+        if (snrm) {
+            KCHK(upload(c, c->pb_snrm, snrm, sb));
+            snrm = (const float*)c->pb_snrm.p;
+        }
+    }
+    if (!snrm) KCHK(batch_normals_dev(c, src, so.data(), nscans, gp->normals_k, c->pb_snrm, &snrm));
+    std::vector<double> eps((size_t)nscans, gp->epsilon);
+    if (epsilons) eps.assign(epsilons, epsilons + nscans);
+    return vgicpb_run_dev(c, src, so.data(), snrm, nscans, m, p, eps.data(), res, last_info);
+}
+int kss_icp_vgicp_batch_dev(kss_ctx* c, const float* d_src_all, const int64_t* src_off, const float* d_src_normals_all, int nscans, const kss_vmap* m,
+                            const kss_icp_params* p, const kss_gicp_params* gp, const double* epsilons, kss_icp_result* results, double* last_info) {
+    return icp_vgicp_batch_any(c, false, d_src_all, src_off, d_src_normals_all, nscans, m, p, gp, epsilons, results, last_info);
+}
+int kss_icp_vgicp_batch(kss_ctx* c, const float* src_all, const int64_t* src_off, const float* src_normals_all, int nscans, const kss_vmap* m,
+                        const kss_icp_params* p, const kss_gicp_params* gp, const double* epsilons, kss_icp_result* results, double* last_info) {
+    return icp_vgicp_batch_any(c, true, src_all, src_off, src_normals_all, nscans, m, p, gp, epsilons, results, last_info);
+}
+
 // ---- symmetric ICP and its robust form -----------------------------
 int kss_symm_default_params(kss_symm_params* sp) {
     if (!sp) return KSS_ERR_ARG;

@@ -339,6 +339,10 @@ int vgicp_record_dev(kss_ctx* c, const float* d_src, const float* d_snrm, int64_
                      double epsilon, double* sums);
 int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* map, const kss_icp_params* p, double epsilon,
                   kss_icp_result* res, double* info);
+// nscans >= 1 scans against one map in lockstep (kss_icp_vgicp_batch_dev; the entry points check their arguments): d_src / d_snrm
+// packed, src_off nscans + 1 offsets in points from 0, epsilons one per scan; info_all: nscans * KSS_VGICP_NINFO doubles or null
+int vgicpb_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_snrm, int nscans, const kss_vmap* map,
+                   const kss_icp_params* p, const double* epsilons, kss_icp_result* results, double* info_all);
 // npairs >= 1 pairs in lockstep (kss_icp_p2l_batch, kss_icp_trimmed_batch, kss_icp_robust_batch, kss_icp_gicp_batch,
 // kss_icp_symm_batch, kss_icp_symm_robust_batch -- symm with robust takes both symm_aligns and rscales): d_nrm laid
 // out like d_tgt; overlaps: one per pair (trimmed; M.overlap is not read); rscales: one per pair (robust; M.rs is not read), all

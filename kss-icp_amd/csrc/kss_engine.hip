@@ -2356,6 +2356,111 @@ int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snr
     return KSS_OK;
 }
 
+// ---- the same for many scans against one map (kss_icp_vgicp_batch) ----
+// nscans >= 1 scans in lockstep, every scan on its own PairTrack.  Per pass: the per-scan table (step, rotation, e, active flag)
+// rewritten in pinned memory and copied in one transfer, the batch's rows launch -- pass 0 on the caller's packed scans unmoved,
+// pass k >= 1 moving every active scan by ITS last step on the way in, from the caller's scans (k = 1) or cur[(k - 1) & 1] into
+// cur[k & 1] -- and its final launch into h_p2l, ONE synchronisation, then vgicp_run_dev's host step for every active scan (the
+// host pool from 64 scans up, each scan on exactly one thread).  A scan that ends goes inactive in the table: the workgroups of
+// the later passes leave at once for it and its record in h_p2l is not written again.  The fitness evaluation is one more pass
+// with every scan active, moved by its own fin from the caller's scans.  src_off: from 0; epsilons: one per scan.
+int vgicpb_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_snrm, int nscans, const kss_vmap* map,
+                   const kss_icp_params* p, const double* epsilons, kss_icp_result* results, double* info_all) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const kss_icp_params& P = *p;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int np = nscans;
+    std::vector<PairbDesc> desc((size_t)np);
+    int64_t total_rows = 0;
+    for (int i = 0; i < np; ++i) {
+        PairbDesc& d = desc[i];
+        d.src_base = src_off[i]; d.ns = src_off[i + 1] - src_off[i];
+        d.tgt_off = 0; d.nt = 0; d.overlap = 1.0;
+        d.row_base = (int32_t)total_rows; d.nrows = stream_blocks(d.ns);
+        total_rows += d.nrows;
+        if (total_rows > PAIRB_INDEX_MAX) return set_err(c, KSS_ERR_ARG, "icp_vgicp_batch: batch too large for 32-bit indexing");
+    }
+    const int64_t total_src = src_off[np];
+    KCHK(stage_pairb(c, desc, true));
+    KCHK(ensure(c, c->p2l_rows, (size_t)total_rows * P2L_NSUMS * sizeof(double)));
+    for (DevBuf& b : c->cur) KCHK(ensure(c, b, (size_t)total_src * 3 * sizeof(float)));
+    KCHK(ensure(c, c->pb_gicp, (size_t)np * sizeof(VgicpbPass)));
+    KCHK(ensure_pinned(c, c->h_gicp, c->h_gicp_cap, (size_t)np * sizeof(VgicpbPass)));
+    KCHK(ensure_pinned(c, c->h_p2l, c->h_p2l_cap, (size_t)np * P2L_NSUMS * sizeof(double)));
+    PairMode M;
+    M.plane = true; M.gicp = true;
+    VgicpbPass* hpass = (VgicpbPass*)c->h_gicp;
+    float* d_cur[2] = {(float*)c->cur[0].p, (float*)c->cur[1].p};
+    const double* hrec = (const double*)c->h_p2l;   // np records of P2L_NSUMS doubles
+    VgicpbArgs a = {map->dev(), nullptr, nullptr, d_snrm, P.max_corr_dist * P.max_corr_dist, (const PairbDesc*)c->pb_desc.p,
+                    (const int32_t*)c->pb_rowpair.p, (const VgicpbPass*)c->pb_gicp.p, (double*)c->p2l_rows.p};
+    std::vector<PairTrack> tr((size_t)np, PairTrack(P));
+    std::vector<int> active((size_t)np, P.max_iterations > 0 ? 1 : 0);
+    std::vector<double> last((size_t)np * KSS_VGICP_NINFO, 0.0);
+    for (int i = 0; i < np; ++i) { last[(size_t)i * KSS_VGICP_NINFO + 1] = (double)desc[i].ns; last[(size_t)i * KSS_VGICP_NINFO + 3] = (double)map->b.nvox; }
+    // the table as the next launch reads it (T: the row-major 4 x 4 whose upper three rows the scan's sources are moved by), one
+    // copy, rows + final into h_p2l, one synchronisation
+    auto pass = [&](bool fitness, const float* d_in, float* d_out, bool move) -> int {
+        ProfScope ps(c, KSS_K_CORR_REDUCE);
+        for (int i = 0; i < np; ++i) {
+            VgicpbPass& e = hpass[i];
+            std::memcpy(e.t, fitness ? tr[i].fin : tr[i].tk, sizeof e.t);
+            std::memcpy(e.r, rot_of(tr[i].fin).r, sizeof e.r);
+            e.active = fitness ? 1 : active[i];
+            e.e = 1.0 - epsilons[i];
+        }
+        HIPCHK(c, hipMemcpyAsync(c->pb_gicp.p, hpass, (size_t)np * sizeof(VgicpbPass), hipMemcpyHostToDevice, c->stream));
+        a.in = d_in; a.out = d_out;
+        launch_vgicpb_rows(c->stream, (int)total_rows, move, a);
+        launch_vgicpb_final(c->stream, np, a, (double*)c->h_p2l_dev);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KSS_OK;
+    };
+    if (P.trace_n) *P.trace_n = 0;
+    int n_active = P.max_iterations > 0 ? np : 0;
+    const auto t1 = std::chrono::steady_clock::now();
+    for (int it = 0; n_active > 0; ++it) {
+        KCHK(pass(false, it <= 1 ? d_src : d_cur[(it - 1) & 1], it == 0 ? nullptr : d_cur[it & 1], it > 0));
+        std::atomic<int> finished{0};
+        auto solve = [&](int pb, int pe) {
+            int fin_here = 0;
+            for (int i = pb; i < pe; ++i) {
+                if (!active[i]) continue;
+                const double* s = hrec + (size_t)i * P2L_NSUMS;
+                last[(size_t)i * KSS_VGICP_NINFO] = s[0]; last[(size_t)i * KSS_VGICP_NINFO + 2] = s[30];
+                double unused[KSS_SIM_NINFO] = {};
+                if (!pair_host_step(P, M, s, unused, tr[i], i == 0)) { active[i] = 0; ++fin_here; }
+            }
+            finished.fetch_add(fin_here, std::memory_order_relaxed);
+        };
+        if (np >= 64) {
+            std::atomic<int> next{0};
+            constexpr int kBlock = 64;   // scans claimed at a time (pairs_loop's grain)
+            c->pool.parallel_for(np, [&](int, int) {
+                for (;;) {
+                    const int pb = next.fetch_add(1) * kBlock;
+                    if (pb >= np) break;
+                    solve(pb, std::min(np, pb + kBlock));
+                }
+            });
+        } else {
+            solve(0, np);
+        }
+        n_active -= finished.load(std::memory_order_relaxed);
+    }
+    for (int i = 0; i < np; ++i) fill_result(results[i], tr[i].fin, tr[i].iters, tr[i].converged, tr[i].state, tr[i].last_mse, 0.0, i);
+    if (P.compute_fitness) {   // [28] / [0] of one more evaluation at fin_i * scan i, over the sources that have a voxel (kept ones)
+        KCHK(pass(true, d_src, d_cur[0], true));
+        for (int i = 0; i < np; ++i) results[i].fitness = hrec[(size_t)i * P2L_NSUMS + 28] / hrec[(size_t)i * P2L_NSUMS];
+    }
+    if (info_all) std::memcpy(info_all, last.data(), last.size() * sizeof(double));
+    const auto t2 = std::chrono::steady_clock::now();
+    c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return KSS_OK;
+}
+
 
 // tau / m / k / kept of n squared distances on the device (kss_trim_threshold_dev)
 int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, double overlap, double* info) {

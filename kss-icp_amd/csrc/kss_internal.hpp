@@ -461,6 +461,33 @@ void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs&
 // ... and the weighted one, with {m, c2, sum of weights, cnt} into d_info[pair * KSS_ROBUST_NINFO]
 void launch_pairb_robust_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out, double* d_info);
 
+// ---- voxelized generalized ICP for many scans per call (kss_pairb.hip) ----
+// What one pass of one scan needs beyond its descriptor: the float 3 x 4 step T_{k-1} its sources take on the way in (read by the
+// moving form only), the rotation block of its accumulated transform (the float bits the single-scan call takes as Rn),
+// e = 1 - epsilon and whether the scan still takes part.  One entry per scan; the host rewrites the table before every pass.
+struct VgicpbPass {
+    float t[12];
+    float r[9];
+    int32_t active;
+    double e;
+};
+static_assert(sizeof(VgicpbPass) == 96, "the host and the device table share this layout");
+// The batch walk's arguments, by value: the map, the batch-wide positions in (packed float triples by global original index) and,
+// moving form, out (another array), the source normals laid out like them, the per-scan descriptors (src_base, ns, row_base,
+// nrows are read), the row -> scan table, the pass table and total_rows rows of KSS_P2L_NSUMS doubles.
+struct VgicpbArgs {
+    VmapDev v;
+    const float* in; float* out; const float* sn;
+    double max_d2;
+    const PairbDesc* desc; const int32_t* row_pair; const VgicpbPass* pass;
+    double* rows;
+};
+// one launch over total_rows = the sum of the scans' stream_blocks(ns) workgroups: every active scan's rows; move: its sources
+// are first moved by its own pass[scan].t and stored to a.out
+void launch_vgicpb_rows(hipStream_t st, int total_rows, bool move, const VgicpbArgs& a);
+// one workgroup per scan: every active scan's record into d_out[scan * KSS_P2L_NSUMS] (device or host-mapped), slot 31 as 0
+void launch_vgicpb_final(hipStream_t st, int nscans, const VgicpbArgs& a, double* d_out);
+
 // ---- one-to-one rejection (kss_o2o.hip) ----
 // The filter's arguments, by value: idx / d2 the NN pass's, batch-wide by original source index (a pair's at desc[p].src_base, its
 // idx counting inside its own target); desc / row_pair / state as in PairbArgs (row_pair null: the one pair desc[0]; state null:

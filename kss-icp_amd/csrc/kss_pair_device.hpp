@@ -629,6 +629,12 @@ struct VgicpMetric {   // voxelized generalized: the map, GicpMetric's rotation 
     double e;
     VgicpMetric(const VmapDev& v_, const VmapMove& T_, const float* in_, float* out_, const GicpRot& Rn_, double e_)
         : v(v_), T(T_), in(in_), out(out_), Rn(Rn_), e(e_) {}
+    __device__ VgicpMetric(const VgicpbArgs& a, const VgicpbPass& pp) : v(a.v), in(a.in), out(a.out), e(pp.e) {   // (pp: the scan's entry, uniform)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) T.m[k] = pp.t[k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Rn.r[k] = pp.r[k];
+    }
     __device__ void begin() {}
     template <int SRC>
     __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float*, const float*, int64_t i, int64_t, float*) const {

@@ -19,6 +19,8 @@
 //                         d2), the pair's TrimState alone -- its {m, k, tau, kept} is no part of the robust info record.
 //   pairb_final_kernel    one workgroup per pair: the fixed-order column sums of the pair's rows, written to host-mapped memory.
 //   pairb_robust_final_kernel    the same with the weighted record's columns and {m, c2, sum of weights, cnt}.
+//   vgicpb_rows_kernel<MOVE>, vgicpb_final_kernel    many scans against one voxel map: the same walk over
+//                         VgicpMetric and the same column sums, on a per-scan pass table of their own (no NN pass, no PairState).
 // Workgroups of pairs that are no longer active leave at once: they read the per-pair state table of the NN pass.  Fixed-scale
 // pairs skip the keys and the select; a batch without an automatic pair does not launch them.
 // The generalized and symmetric forms read the rotation applied to the source normals and e / align_normals once per workgroup
@@ -215,6 +217,43 @@ void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs&
     if (sim) hipLaunchKernelGGL((pairb_final_kernel<false, true>), g, b, 0, st, (const double*)a.rows, a.desc, a.state, d_out);
     else if (plane) hipLaunchKernelGGL(pairb_final_kernel<true>, g, b, 0, st, (const double*)a.rows, a.desc, a.state, d_out);
     else hipLaunchKernelGGL(pairb_final_kernel<false>, g, b, 0, st, (const double*)a.rows, a.desc, a.state, d_out);
+}
+
+// ---- voxelized generalized ICP, many scans against one map (kss_icp_vgicp_batch) ----
+// The batch form of pair_rows_kernel<VgicpMetric<MOVE>, SRC_F3>: workgroup b of scan p runs pair_walk over the scan's own ns
+// sources b * 256 + t + k * 256 * stream_blocks(ns), offset by the scan's base into the packed arrays -- the single-scan kernel's
+// assignment -- on vgicp_source<MOVE> and block_sum, so a scan's rows are the single call's.  The scan's pass entry (its step, the
+// rotation for its normals, e, the active flag) is one uniform load per workgroup; workgroups of scans that have ended leave at once.
+template <bool MOVE>
+__global__ __launch_bounds__(P2L_THREADS) void vgicpb_rows_kernel(const VgicpbArgs a) {
+    const int p = a.row_pair[blockIdx.x];
+    const VgicpbPass pp = a.pass[p];
+    if (pp.active == 0) return;
+    const PairbDesc d = a.desc[p];
+    const VgicpMetric<MOVE> m(a, pp);
+    const PairSrc s = {nullptr, nullptr, nullptr, nullptr, nullptr, a.sn, a.max_d2};
+    pair_walk<VgicpMetric<MOVE>, SRC_F3>(m, s, nullptr, nullptr, d.src_base, (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x,
+                                         d.ns, (int64_t)d.nrows * P2L_THREADS, 0, a.rows, nullptr);
+}
+
+// pairb_final_kernel<true> on the pass table's active flag
+__global__ __launch_bounds__(P2L_THREADS) void vgicpb_final_kernel(const double* __restrict__ rows, const PairbDesc* __restrict__ desc,
+                                                                   const VgicpbPass* __restrict__ pass, double* __restrict__ out) {
+    __shared__ double shg[P2L_GROUPS][P2L_NSUMS];
+    const int p = blockIdx.x;
+    if (pass[p].active == 0) return;
+    const PairbDesc d = desc[p];
+    const double v = p2l_rows_column_sum(rows + (int64_t)d.row_base * P2L_NSUMS, d.nrows, shg);
+    if (threadIdx.x < P2L_NSUMS) out[(int64_t)p * P2L_NSUMS + threadIdx.x] = threadIdx.x == P2L_NSUMS - 1 ? 0.0 : v;
+}
+
+void launch_vgicpb_rows(hipStream_t st, int total_rows, bool move, const VgicpbArgs& a) {
+    if (move) hipLaunchKernelGGL(vgicpb_rows_kernel<true>, dim3(total_rows), dim3(P2L_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(vgicpb_rows_kernel<false>, dim3(total_rows), dim3(P2L_THREADS), 0, st, a);
+}
+
+void launch_vgicpb_final(hipStream_t st, int nscans, const VgicpbArgs& a, double* d_out) {
+    hipLaunchKernelGGL(vgicpb_final_kernel, dim3(nscans), dim3(P2L_THREADS), 0, st, (const double*)a.rows, a.desc, a.pass, d_out);
 }
 
 void launch_pairb_robust_final(hipStream_t st, bool plane, int npairs, const PairbArgs& a, double* d_out, double* d_info) {

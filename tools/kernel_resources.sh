@@ -17,7 +17,7 @@ for l in open('/tmp/_kr.log'):
 import subprocess
 print(sys.argv[1])
 for n, r in rows.items():
-    if not any(k in n for k in ("resident_icp", "grid_pass_kernel", "gridb_pass", "cand_", "nn_sweep_kernelILi4ELb0ELb0", "rot_search_kernelILi4ELi256", "preshape", "corr_reduce", "finalize", "pair_rows", "p2l_final", "trim_", "robust_", "gicp_", "symm_", "sim_", "pairb_", "o2o_", "recip_", "vmap_")): continue
+    if not any(k in n for k in ("resident_icp", "grid_pass_kernel", "gridb_pass", "cand_", "nn_sweep_kernelILi4ELb0ELb0", "rot_search_kernelILi4ELi256", "preshape", "corr_reduce", "finalize", "pair_rows", "p2l_final", "trim_", "robust_", "gicp_", "symm_", "sim_", "pairb_", "o2o_", "recip_", "vmap_", "vgicpb_")): continue
     try: d = subprocess.run(["c++filt", n], capture_output=True, text=True).stdout.strip().split('(')[0]
     except OSError: d = n
     print("  %-110s VGPRs %3d  SGPRs %3d  spilled %3d + %d  scratch %4d B  waves/SIMD %d  LDS %6d" % (d[:110], r.get("VGPRs", -1), r.get("TotalSGPRs", -1), r.get("VGPRs Spill", 0), r.get("SGPRs Spill", 0), r.get("ScratchSize", 0), r.get("Occupancy", 0), r.get("LDS Size", 0)))
