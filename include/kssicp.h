@@ -747,6 +747,46 @@ int kss_vmap_info(const kss_vmap *map, double info[KSS_VMAP_NINFO]);
  * alone.  KSS_ERR_CAPACITY (*nvox set) when capacity < *nvox. */
 int kss_vmap_read(kss_ctx *ctx, const kss_vmap *map, int64_t *lin, double *stats, int64_t capacity, int64_t *nvox);
 
+/* ---- a map that grows scan by scan, in a fixed box ----
+ * Scan-to-map registration: register a scan against the map, insert it at the pose just found, take the next scan.  The map
+ * keeps every voxel's N, s_a and P_ab in f64 beside the record (9 more doubles a voxel), so an insert CONTINUES the serial sums of
+ * the definition above: kss_vmap_create(A) followed by an insert of B is, in every bit of kss_vmap_read and kss_vmap_info, the map
+ * kss_vmap_create builds from A followed by the rows of B that are mapped and inside; and on a box map any split of a cloud
+ * over calls, down to one point per call, gives the map of one call.  kss_vmap_create's own results do not change in any bit.
+ *
+ * kss_vmap_create_box: an EMPTY map (0 mapped targets, 0 voxels; kss_vmap_read returns 0 voxels and kss_icp_vgicp against it ends
+ * in KSS_STATE_NO_CORRESPONDENCES) over the caller's box: lo_a = lo[a], a zero taken as +0;  inv = 1.0f / (float)leaf;
+ * dims_a = 1 + floorf((hi_a - lo_a) * inv) in float, nothing fused.  vp->normals_k is not read.  KSS_ERR_ARG: a NULL argument; a
+ * lo or hi that is not finite; hi_a < lo_a; a leaf kss_vmap_create refuses; an f that is not finite; more than 2^26 cells.
+ *
+ * kss_vmap_insert[_dev]: n points (packed float triples; the _dev form takes device pointers) into a live map of ctx, from
+ * kss_vmap_create or kss_vmap_create_box.  The box, origin, inv and dims never change.
+ *   normals     NULL: computed as kss_icp_vgicp computes a scan's normals, at normals_k (3..64), from pts as passed in, before
+ *               the pose;
+ *   pose        T: a HOST row-major float 4x4, or NULL: nothing is moved or turned.  Otherwise the position is
+ *               p' = ((T00*x + T01*y) + T02*z) + T03 in float with no fma (transform_apply_f32's and the VGICP loop's move) and
+ *               the normal is, in f64 on the widened floats, m_k = (R_k0*n0 + R_k1*n1) + R_k2*n2 (kss_icp_vgicp's m).  NULL: p' = p
+ *               and m = (double)n.  An identity T gives the bits of NULL;
+ *   mapped      p' and the three float normal components are finite;
+ *   inside      0 <= f_a < dims_a on all three axes, f_a from p' by the map's expression, compared in float: the lookup's rule.
+ *               Mapped points outside the box are counted in info[2] and change nothing;
+ *   record      for the inserted points in ascending index of this call, after everything inserted earlier, serially in f64,
+ *               nothing fused: N += 1, s_a += (double)p'_a, P_ab += m_a * m_b; then mean = s / N and S = P / N.
+ * The voxels stay packed in ascending lin (an insert may renumber them); info[0] and info[1] of kss_vmap_info become the totals.
+ * info (may be NULL): KSS_VMAP_NINSERT doubles.  A cloud with nothing to add -- every point non-finite or outside the box -- is
+ * KSS_OK with the map unchanged.  KSS_ERR_ARG: a NULL ctx, map or pts; n <= 0; not a live map of ctx; normals_k outside 3..64
+ * where the normals are computed; a T entry that is not finite.  A refused call or a failed allocation leaves the map exactly as
+ * it was: every allocation precedes the first store into the map's table, and the new records are built beside the old ones and
+ * take their place at the end.  An insert costs a pass over the dense cell table, whatever n is, and synchronises the context's
+ * stream.
+ * Not offered: eviction of voxels or points, a box that slides or grows, a cap on the points a voxel takes. */
+int kss_vmap_create_box(kss_ctx *ctx, const float lo[3], const float hi[3], const kss_vmap_params *vp, kss_vmap **out);
+#define KSS_VMAP_NINSERT 4   /* {points added, points not mapped, points outside the box, voxels created by this call} */
+int kss_vmap_insert(kss_ctx *ctx, kss_vmap *map, const float *pts, int64_t n, const float *normals,
+                    const float T[16], int normals_k, double info[KSS_VMAP_NINSERT]);
+int kss_vmap_insert_dev(kss_ctx *ctx, kss_vmap *map, const float *d_pts, int64_t n, const float *d_normals,
+                        const float T[16], int normals_k, double info[KSS_VMAP_NINSERT]);
+
 /* One pass.  F and R_F as in kss_icp_gicp.  For source i: its current float position p and its float normal ns = src_normals[i]
  * (by ORIGINAL index).  Everything after the lookup is f64 on the widened floats, nothing fused, in kss_icp_gicp's order:
  *   voxel       f_a from p by the map's expression above; the source has a voxel iff 0 <= f_a < dims_a on all three axes --

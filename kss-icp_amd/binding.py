@@ -28,6 +28,7 @@ SIM_NINFO = 6            # KSS_SIM_NINFO: {m, k, tau, kept, s_k, s_acc after the
 O2O_NINFO = 5            # KSS_O2O_NINFO: {u survivors, k, tau, kept, m candidates} of a one-to-one pass
 VMAP_NINFO = 10          # KSS_VMAP_NINFO: {mapped targets, voxels, dims x y z, leaf, origin x y z, inv widened} of a voxel map
 VMAP_NSTAT = 10          # KSS_VMAP_NSTAT: {N, mean x y z, S00 S01 S02 S11 S12 S22} of a voxel
+VMAP_NINSERT = 4         # KSS_VMAP_NINSERT: {points added, points not mapped, points outside the box, voxels created} of an insert
 VGICP_NINFO = 4          # KSS_VGICP_NINFO: {kept in the last pass, ns, [30] of the last pass, voxels of the map}
 RECIP_NINFO = 6          # KSS_RECIP_NINFO: {r mutual winners, k, tau, kept, m candidates, u winners} of a reciprocal pass
 F32, F64 = 0, 1
@@ -60,6 +61,7 @@ SYMBOLS = [
     "kss_recip_filter", "kss_recip_filter_dev", "kss_recip_default_params", "kss_icp_recip", "kss_icp_recip_dev",
     "kss_recip_filter_batch", "kss_recip_filter_batch_dev", "kss_icp_recip_pairs", "kss_icp_recip_pairs_dev",
     "kss_vmap_default_params", "kss_vmap_create", "kss_vmap_create_dev", "kss_vmap_destroy", "kss_vmap_info", "kss_vmap_read",
+    "kss_vmap_create_box", "kss_vmap_insert", "kss_vmap_insert_dev",
     "kss_vgicp_sums", "kss_vgicp_sums_dev", "kss_icp_vgicp", "kss_icp_vgicp_dev",
     "kss_icp_vgicp_batch", "kss_icp_vgicp_batch_dev",
 ]
@@ -246,6 +248,9 @@ def _declare(L):
     L.kss_vmap_destroy.argtypes = [vp, vp]
     L.kss_vmap_info.argtypes = [vp, vp]
     L.kss_vmap_read.argtypes = [vp, vp, vp, vp, i64, C.POINTER(i64)]
+    L.kss_vmap_create_box.argtypes = [vp, vp, vp, C.POINTER(VmapParams), C.POINTER(vp)]
+    for n in ("kss_vmap_insert", "kss_vmap_insert_dev"):
+        getattr(L, n).argtypes = [vp, vp, vp, i64, vp, vp, C.c_int, vp]
     for n in ("kss_vgicp_sums", "kss_vgicp_sums_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, i64, vp, dbl, vp, C.POINTER(GicpParams), vp]
     for n in ("kss_icp_vgicp", "kss_icp_vgicp_dev"):
@@ -513,8 +518,9 @@ def vmap_params(**kw):
 
 
 class VoxelMap:
-    """A voxel map of one target cloud (kss_vmap): made by Context.vmap() / vmap_dev(), it lives on the device until close() -- or
-    until its context is closed, which frees it -- and serves any number of Context.icp_vgicp() / vgicp_sums() calls."""
+    """A voxel map of one target cloud (kss_vmap): made by Context.vmap() / vmap_dev(), or empty over a box by Context.vmap_box(),
+    it lives on the device until close() -- or until its context is closed, which frees it -- serves any number of
+    Context.icp_vgicp() / vgicp_sums() calls and takes further clouds with insert()."""
 
     def __init__(self, ctx, handle):
         self.ctx, self.h = ctx, handle
@@ -535,6 +541,24 @@ class VoxelMap:
         stats = np.zeros((n.value, VMAP_NSTAT), np.float64)
         self.ctx._chk(self.ctx.L.kss_vmap_read(self.ctx.h, self.h, _p(lin), _p(stats), n.value, C.byref(n)), "kss_vmap_read")
         return lin, stats
+
+    def _insert(self, name, pts, n, normals, T, normals_k):
+        Tm = None if T is None else np.ascontiguousarray(T, dtype=np.float32).reshape(16)
+        info = np.zeros(VMAP_NINSERT, np.float64)
+        self.ctx._chk(getattr(self.ctx.L, name)(self.ctx.h, self.h, pts, int(n), normals, _p(Tm), int(normals_k), _p(info)), name)
+        return info
+
+    def insert(self, pts, normals=None, T=None, normals_k=20):
+        """kss_vmap_insert: the cloud (n x 3) into the map at the pose T (a 4 x 4, None: as it is); normals: n x 3, or None to
+        compute them at normals_k from the cloud as passed in.  The box never changes: points outside it are counted and left
+        out.  Returns the VMAP_NINSERT doubles {points added, points not mapped, points outside the box, voxels created}."""
+        a = _f32(pts)
+        nr = _normals(normals, len(a), "cloud")
+        return self._insert("kss_vmap_insert", _p(a), len(a), _p(nr), T, normals_k)
+
+    def insert_dev(self, d_pts, n, d_normals, T=None, normals_k=20):
+        """kss_vmap_insert_dev on device pointers (the normals pointer may be 0 / None; T stays a host array)."""
+        return self._insert("kss_vmap_insert_dev", _dp(d_pts), n, _dp(d_normals), T, normals_k)
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -1583,6 +1607,16 @@ class Context:
         res, info, extra = self._icp_call(_VGICP_BATCH, False, _p(s), _p(so), _p(sn), vmap.h if vmap is not None else None, None, None, p,
                                           _structs(_VGICP_BATCH, (gp,)), (epsilons,), so, trace_cap)
         return [dict(self._result(_VGICP_BATCH, r, info[i], extra if i == 0 else {}), pair_id=r.pair_id) for i, r in enumerate(res)]
+
+    def vmap_box(self, lo, hi, leaf):
+        """kss_vmap_create_box: an EMPTY VoxelMap over the box lo .. hi (3 floats each) at voxel edge `leaf`, to be filled by
+        VoxelMap.insert()."""
+        a = np.ascontiguousarray(lo, dtype=np.float32).reshape(3)
+        b = np.ascontiguousarray(hi, dtype=np.float32).reshape(3)
+        vp = vmap_params(leaf=float(leaf))
+        h = C.c_void_p()
+        self._chk(self.L.kss_vmap_create_box(self.h, _p(a), _p(b), C.byref(vp), C.byref(h)), "kss_vmap_create_box")
+        return VoxelMap(self, h)
 
     def icp_vgicp_batch_dev(self, d_src_all, src_off, d_src_normals_all, vmap, params, epsilons=None, gp=None):
         """kss_icp_vgicp_batch_dev on device pointers (the normals pointer may be 0 / None; the offsets and epsilons stay host

@@ -1092,13 +1092,74 @@ int kss_vmap_read(kss_ctx* c, const kss_vmap* m, int64_t* lin, double* stats, in
     if (!vmap_live(c, m)) return set_err(c, KSS_ERR_ARG, "vmap_read: not a live map of this context");
     if (!nvox) return set_err(c, KSS_ERR_ARG, "vmap_read: null argument");
     *nvox = m->b.nvox;
-    if (!lin && !stats) return KSS_OK;   // the count alone
+    if ((!lin && !stats) || m->b.nvox == 0) return KSS_OK;   // the count alone; a box map nothing was inserted into has no record
     if (capacity < m->b.nvox) return set_err(c, KSS_ERR_CAPACITY, "vmap_read: output buffer too small");
     HIPCHK(c, hipSetDevice(c->device));
     if (lin) HIPCHK(c, hipMemcpyAsync(lin, m->b.lin, (size_t)m->b.nvox * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     if (stats) HIPCHK(c, hipMemcpyAsync(stats, m->b.rec, (size_t)m->b.nvox * KSS_VMAP_NSTAT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return KSS_OK;
+}
+
+// ---- a map that grows ----
+int kss_vmap_create_box(kss_ctx* c, const float lo[3], const float hi[3], const kss_vmap_params* vp, kss_vmap** out) {
+    if (!c) return KSS_ERR_ARG;
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string("vmap_create_box: ") + what).c_str()); };
+    if (out) *out = nullptr;
+    if (!lo || !hi || !vp || !out) return bad("null argument");
+    if (!(vp->leaf > 0.0) || !std::isfinite(vp->leaf)) return bad("leaf must be finite and > 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    kss_vmap* m = new (std::nothrow) kss_vmap();
+    if (!m) return KSS_ERR_NOMEM;
+    const int rc = vmap_empty(c->stream, lo, hi, 1.0f / (float)vp->leaf, m->b);
+    if (rc != 0) {
+        delete m;
+        if (rc == 1) return bad("a box that is not finite, has hi < lo, or a grid that is not finite or has more than 2^26 cells");
+        return rc == 2 ? set_err(c, KSS_ERR_NOMEM, "vmap_create_box: hipMalloc") : set_err(c, KSS_ERR_HIP, "vmap_create_box: the table's fill failed");
+    }
+    m->ctx = c;
+    m->leaf = vp->leaf;
+    c->vmaps.push_back(m);
+    *out = m;
+    return KSS_OK;
+}
+
+// the cloud and its normals on the device as vgicp_enter brings a scan in, then vmap_insert
+static int vmap_insert_any(kss_ctx* c, bool host, kss_vmap* m, const float* pts, int64_t n, const float* nrm, const float* T, int normals_k,
+                           double* info) {
+    if (!c) return KSS_ERR_ARG;
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string("vmap_insert: ") + what).c_str()); };
+    if (!pts) return bad("null argument");
+    if (!vmap_live(c, m)) return bad("not a live map of this context");
+    if (n <= 0) return bad("empty cloud");
+    if (n > 0x7fff0000ll) return bad("cloud too large");
+    if (!nrm && (normals_k < 3 || normals_k > 64)) return bad("normals_k must be in 3..64");
+    for (int k = 0; T && k < 16; ++k)
+        if (!std::isfinite(T[k])) return bad("T must be finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (host) {
+        const size_t sb = (size_t)n * 3 * sizeof(float);
+        KCHK(upload(c, c->stage_src, pts, sb));
+        pts = (const float*)c->stage_src.p;
+        if (nrm) {
+            KCHK(upload(c, c->gicp_snrm, nrm, sb));
+            nrm = (const float*)c->gicp_snrm.p;
+        }
+    }
+    if (!nrm) KCHK(cloud_normals_dev(c, pts, n, normals_k, c->gicp_snrm, &nrm));
+    int64_t counts[KSS_VMAP_NINSERT] = {0, 0, 0, 0};
+    const int rc = vmap_insert(c->stream, m->b, pts, nrm, n, T, counts);
+    if (rc != 0) return rc == 2 ? set_err(c, KSS_ERR_NOMEM, "vmap_insert: hipMalloc") : set_err(c, KSS_ERR_HIP, "vmap_insert: the insert failed");
+    for (int k = 0; info && k < KSS_VMAP_NINSERT; ++k) info[k] = (double)counts[k];
+    return KSS_OK;
+}
+int kss_vmap_insert_dev(kss_ctx* c, kss_vmap* m, const float* d_pts, int64_t n, const float* d_normals, const float T[16], int normals_k,
+                        double info[KSS_VMAP_NINSERT]) {
+    return vmap_insert_any(c, false, m, d_pts, n, d_normals, T, normals_k, info);
+}
+int kss_vmap_insert(kss_ctx* c, kss_vmap* m, const float* pts, int64_t n, const float* normals, const float T[16], int normals_k,
+                    double info[KSS_VMAP_NINSERT]) {
+    return vmap_insert_any(c, true, m, pts, n, normals, T, normals_k, info);
 }
 
 // what both the record and the loop check and stage: the source on the device with its normals, given or computed

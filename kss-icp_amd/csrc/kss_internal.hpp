@@ -352,9 +352,17 @@ struct VmapDev {
     int dims[3];
 };
 struct VmapMove { float m[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}; };   // the upper three rows of a row-major float 4 x 4
-// What the build hands back: the device arrays the map owns (hipMalloc, freed by the caller) and its header.
+// What the build hands back: the device arrays the map owns (cell; rec with acc and lin behind it in one allocation; after an
+// insert a second allocation of that kind, not in use; freed by vmap_free) and its header.
+// acc: VMAP_NACC doubles per voxel, the sums {s x y z, P00 P01 P02 P11 P12 P22} whose quotients by N are the record: what an
+// insert continues.  A map without a voxel (vmap_empty) holds the table alone: rec, lin and acc are null.
+constexpr int VMAP_NACC = 9;
+constexpr int VMAP_NINSERT = 4;                  // {points added, points not mapped, points outside the box, voxels created}
+static_assert(VMAP_NINSERT == KSS_VMAP_NINSERT, "kss_internal.hpp and include/kssicp.h disagree");
 struct VmapBuilt {
-    int32_t* cell = nullptr; double* rec = nullptr; int64_t* lin = nullptr;
+    int32_t* cell = nullptr; double* rec = nullptr; int64_t* lin = nullptr; double* acc = nullptr;
+    int64_t cap = 0;                          // voxels the allocation behind rec has room for (>= nvox)
+    void* spare = nullptr; int64_t spare_cap = 0;   // the allocation the last insert's records left behind: the next insert's
     int64_t mapped = 0, nvox = 0;
     int dims[3] = {0, 0, 0};
     float lo[3] = {0, 0, 0}, inv = 0;
@@ -363,6 +371,14 @@ struct VmapBuilt {
 // target, or a grid that is not finite or has more than VMAP_MAX_CELLS cells; 2: out of memory; 3: a HIP error (1 - 3: nothing is held).
 int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t nt, float inv, VmapBuilt& out);
 void vmap_free(VmapBuilt& b);
+// An empty map over the box lo .. hi (kss_vmap_create_box): the table of -1 alone.  0: made; 1: a box that is not finite, is
+// inverted or has more than VMAP_MAX_CELLS cells; 2: out of memory; 3: a HIP error.
+int vmap_empty(hipStream_t st, const float lo[3], const float hi[3], float inv, VmapBuilt& out);
+// n points (device, packed float triples, with their normals) into the map b at the HOST float 4 x 4 T (null: as they are):
+// kss_vmap_insert's definition.  Every allocation precedes the first store into b's cell table, which is renumbered in place; the
+// new records, lin and sums are built beside b's and take their place after the last synchronisation.  2 (out of memory): b is
+// what it was.  counts: the VMAP_NINSERT tallies.  Scratch is allocated and freed inside.
+int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d_nrm, int64_t n, const float* T, int64_t counts[VMAP_NINSERT]);
 struct GicpRot;
 // one rows launch of pair_rows_kernel over VgicpMetric: a.n sources (packed float triples d_in, normals a.s.sn) against the map;
 // T set: every source is first moved by *T and stored to d_out (not d_in)

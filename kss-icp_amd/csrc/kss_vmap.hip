@@ -13,11 +13,12 @@
 //   rank fix              every target ranks itself among its voxel's targets by original index (grid_rank_fix_kernel's pattern):
 //                         the slots of a voxel now hold its targets in ascending index whatever the atomics did.
 //   stats                 one lane per voxel walks its slots: N, sum q, sum n n^T in f64, then the six + three divisions.
+//                         The sums themselves are kept too (acc, nine doubles a voxel): kss_vmap_insert continues them (below).
 // A voxel of N targets costs N^2 index compares in the rank fix (spread over its N lanes) and N dependent f64 additions on one
 // lane in the walk: nothing at a few points per voxel, and seconds to minutes for a million-point cloud inside ONE voxel (a leaf
 // far larger than the cloud) -- which is not a map anyone registers against.
 // No float atomic, nothing fused (fp contraction is off), no workspace of the context: the scratch is allocated here and freed
-// before the build returns, and what the map keeps (table, records, lin) is its own.
+// before the build returns, and what the map keeps (table, records, lin, sums) is its own.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -178,8 +179,10 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_rank_fix_kernel(const int32
 // one lane per voxel: the record of the definition, serially in ascending original index
 __global__ __launch_bounds__(VMAP_THREADS) void vmap_stats_kernel(const float* __restrict__ tgt, const float* __restrict__ nrm,
                                                                    const int32_t* __restrict__ order, const int32_t* __restrict__ vstart, int64_t nvox,
-                                                                   double* __restrict__ rec) {
+                                                                   const int64_t* __restrict__ vlin, double* __restrict__ rec,
+                                                                   double* __restrict__ acc, int64_t* __restrict__ lin) {
     for (int64_t v = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * VMAP_THREADS) {
+        lin[v] = vlin[v];   // (packed into the scratch by the compact, before the voxel count is known; kept at the map's own size)
         double s[3] = {0.0, 0.0, 0.0}, P[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         const int32_t lo = vstart[v], hi = vstart[v + 1];
         for (int32_t k = lo; k < hi; ++k) {
@@ -197,14 +200,20 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_stats_kernel(const float* _
         for (int a = 0; a < 3; ++a) r[1 + a] = s[a] / N;
 #pragma unroll
         for (int a = 0; a < 6; ++a) r[4 + a] = P[a] / N;
+        double* q = acc + v * VMAP_NACC;   // the sums themselves: what kss_vmap_insert continues
+#pragma unroll
+        for (int a = 0; a < 3; ++a) q[a] = s[a];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) q[3 + a] = P[a];
     }
 }
 
 void vmap_free(VmapBuilt& b) {
     if (b.cell) (void)hipFree(b.cell);
-    if (b.rec) (void)hipFree(b.rec);
-    if (b.lin) (void)hipFree(b.lin);
-    b.cell = nullptr; b.rec = nullptr; b.lin = nullptr;
+    if (b.rec) (void)hipFree(b.rec);   // (acc and lin are parts of this allocation: vmap_pack_alloc)
+    if (b.spare) (void)hipFree(b.spare);
+    b.cell = nullptr; b.rec = nullptr; b.lin = nullptr; b.acc = nullptr; b.spare = nullptr;
+    b.cap = b.spare_cap = 0;
 }
 
 // the build's scratch: one allocation, carved into 256-byte aligned parts
@@ -220,6 +229,24 @@ struct VmapScratch {
         return p;
     }
 };
+
+// rec, acc and lin for up to cap voxels as ONE allocation with rec as its base: an insert replaces all three at once, and a
+// release costs more than every kernel of an insert together (0.17 ms: DESIGN.md 2.34)
+static size_t vmap_pack_bytes(int64_t cap) {
+    return VmapScratch::pad((size_t)cap * VMAP_NSTAT * sizeof(double)) + VmapScratch::pad((size_t)cap * VMAP_NACC * sizeof(double)) + (size_t)cap * sizeof(int64_t);
+}
+static void vmap_pack_at(VmapBuilt& b, void* base, int64_t cap) {
+    b.rec = (double*)base;
+    b.acc = (double*)((char*)base + VmapScratch::pad((size_t)cap * VMAP_NSTAT * sizeof(double)));
+    b.lin = (int64_t*)((char*)b.acc + VmapScratch::pad((size_t)cap * VMAP_NACC * sizeof(double)));
+    b.cap = cap;
+}
+static bool vmap_pack_alloc(VmapBuilt& b, int64_t cap) {
+    void* base = nullptr;
+    if (hipMalloc(&base, vmap_pack_bytes(cap)) != hipSuccess) return false;
+    vmap_pack_at(b, base, cap);
+    return true;
+}
 
 int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t nt, float inv, VmapBuilt& out) {
     const int nb = stream_blocks(nt);
@@ -255,7 +282,8 @@ int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t n
     VmapScratch w;
     const size_t scan_bytes = std::max(scan_scratch_bytes((int)ncells), scan_scratch_bytes((int)vmax));
     const size_t want = VmapScratch::pad((size_t)ncells * 4) + VmapScratch::pad(((size_t)ncells + 1) * 4) + VmapScratch::pad(scan_bytes) +
-                        4 * VmapScratch::pad((size_t)nt * 4) + VmapScratch::pad((size_t)vmax * 4) + VmapScratch::pad(((size_t)vmax + 1) * 4);
+                        4 * VmapScratch::pad((size_t)nt * 4) + VmapScratch::pad((size_t)vmax * 4) + VmapScratch::pad(((size_t)vmax + 1) * 4) +
+                        VmapScratch::pad((size_t)vmax * 8);
     if (hipMalloc((void**)&b.cell, (size_t)ncells * sizeof(int32_t)) != hipSuccess) return 2;
     if (hipMalloc((void**)&w.base, want) != hipSuccess) { vmap_free(b); return 2; }
     int32_t* d_flag = w.take<int32_t>((size_t)ncells);
@@ -267,32 +295,266 @@ int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t n
     int32_t* d_order = w.take<int32_t>((size_t)nt);
     int32_t* d_vcnt = w.take<int32_t>((size_t)vmax);
     int32_t* d_vstart = w.take<int32_t>((size_t)vmax + 1);
+    int64_t* d_vlin = w.take<int64_t>((size_t)vmax);
     auto fail = [&](int rc) { vmap_free(b); return rc; };
-    if (hipMalloc((void**)&b.lin, (size_t)vmax * sizeof(int64_t)) != hipSuccess) return fail(2);
-    if (hipMemsetAsync(b.cell, 0, (size_t)ncells * sizeof(int32_t), st) != hipSuccess) return fail(3);
+    if (hipMemsetAsync(b.cell, 0,(size_t)ncells * sizeof(int32_t), st) != hipSuccess) return fail(3);
     if (hipMemsetAsync(d_flag, 0, (size_t)ncells * sizeof(int32_t), st) != hipSuccess) return fail(3);
     hipLaunchKernelGGL(vmap_count_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, d_tgt, d_nrm, nt, g, d_lin32, d_slot, b.cell, d_flag);
     launch_scan(st, d_flag, (int)ncells, d_vox, d_scan, false);
-    hipLaunchKernelGGL(vmap_compact_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, b.cell, (const int32_t*)d_vox, ncells, b.lin, d_vcnt);
+    hipLaunchKernelGGL(vmap_compact_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, b.cell, (const int32_t*)d_vox, ncells, d_vlin, d_vcnt);
     int32_t nvox32 = 0;
     if (hipMemcpyAsync(&nvox32, d_vox + ncells, sizeof nvox32, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(3);
     if (hipStreamSynchronize(st) != hipSuccess) return fail(3);
     const int64_t nvox = nvox32;
     if (nvox < 1 || nvox > vmax) return fail(3);
-    if (hipMalloc((void**)&b.rec, (size_t)nvox * VMAP_NSTAT * sizeof(double)) != hipSuccess) return fail(2);
+    if (!vmap_pack_alloc(b, nvox)) return fail(2);
     launch_scan(st, d_vcnt, (int)nvox, d_vstart, d_scan, false);
     hipLaunchKernelGGL(vmap_scatter_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, (const int32_t*)d_lin32, (const int32_t*)d_slot, nt,
                        (const int32_t*)b.cell, (const int32_t*)d_vstart, d_tmp);
     hipLaunchKernelGGL(vmap_rank_fix_kernel, dim3(stream_blocks(mapped)), dim3(VMAP_THREADS), 0, st, (const int32_t*)d_tmp, mapped,
                        (const int32_t*)d_lin32, (const int32_t*)b.cell, (const int32_t*)d_vstart, d_order);
     hipLaunchKernelGGL(vmap_stats_kernel, dim3(stream_blocks(nvox)), dim3(VMAP_THREADS), 0, st, d_tgt, d_nrm, (const int32_t*)d_order,
-                       (const int32_t*)d_vstart, nvox, b.rec);
+                       (const int32_t*)d_vstart, nvox, (const int64_t*)d_vlin, b.rec, b.acc, b.lin);
     if (hipGetLastError() != hipSuccess) return fail(3);
     if (hipStreamSynchronize(st) != hipSuccess) return fail(3);   // (the scratch is freed on return)
     b.mapped = mapped; b.nvox = nvox;
     for (int a = 0; a < 3; ++a) { b.dims[a] = g.dims[a]; b.lo[a] = g.lo[a]; }
     b.inv = inv;
     out = b;
+    return 0;
+}
+
+// ---- insertion into a live map (kss_vmap_insert) ---------------------------------------------------------------
+// The box, origin, inv and dims stay; the voxels are renumbered (a new occupied cell may lie between two old ones) and every
+// touched voxel's sums are continued from acc.
+//   flags                 flag[c] = occupied before;
+//   cell                  every new point moved and turned, its lin, its arrival slot (an integer atomic on a zeroed count table in
+//                         the scratch), the cell's flag (hit now) and the two tallies of points left out;
+//   scan                  the new numbering in ascending lin; the voxel count and the tallies go to the host, which allocates the
+//                         new records.  Up to here the map has only been read: a call with nothing to add, a refused one and a
+//                         failed allocation leave it as it was.
+//   compact               the cell table IN PLACE, at the occupied cells alone (an empty cell stays -1, and a cell is occupied iff
+//                         the scan steps over it, so the scan is the only table read in full): the new lin, the per-voxel NEW-point
+//                         counts and every voxel's old number (-1: created now), the gather index of the old N and sums;
+//   scan, scatter, rank   the build's kernels on the new points alone: a voxel's new points in ascending index of this call;
+//   continue              one lane per voxel: from the old sums (zero for a created voxel) on through its new points, serially in
+//                         f64, then the nine divisions; a voxel without a new point is copied.
+// The new rec, acc and lin are built beside the old ones and replace them on the host after the last synchronisation; the old
+// ones stay with the map as the next insert's destination (VmapBuilt::spare).
+struct VmapPose {
+    float m[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    int on = 0;   // 0: the points and normals as they are
+};
+
+// the point as the map takes it (transform_apply_f32_kernel's expression); true: mapped
+__device__ __forceinline__ bool vmap_moved(const float* __restrict__ pts, const float* __restrict__ nrm, int64_t i, const VmapPose& T, float& x, float& y, float& z) {
+    x = pts[3 * i]; y = pts[3 * i + 1]; z = pts[3 * i + 2];
+    if (T.on) {
+        const float a = x, b = y, c = z;
+        x = ((T.m[0] * a + T.m[1] * b) + T.m[2] * c) + T.m[3];
+        y = ((T.m[4] * a + T.m[5] * b) + T.m[6] * c) + T.m[7];
+        z = ((T.m[8] * a + T.m[9] * b) + T.m[10] * c) + T.m[11];
+    }
+    return isfinite(x) && isfinite(y) && isfinite(z) && isfinite(nrm[3 * i]) && isfinite(nrm[3 * i + 1]) && isfinite(nrm[3 * i + 2]);
+}
+
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_insert_cell_kernel(const float* __restrict__ pts, const float* __restrict__ nrm, int64_t n,
+                                                                         const VmapPose T, const VmapGrid g, int32_t* __restrict__ lin32,
+                                                                         int32_t* __restrict__ slot, int32_t* __restrict__ cnt,
+                                                                         int32_t* __restrict__ flag, unsigned long long* __restrict__ tally) {
+    unsigned long long unmapped = 0, outside = 0;
+    for (int64_t i = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * VMAP_THREADS) {
+        float x, y, z;
+        if (!vmap_moved(pts, nrm, i, T, x, y, z)) { lin32[i] = -1; ++unmapped; continue; }
+        // the lookup's rule (vgicp_source): compared in float
+        const float fx = floorf((x - g.lo[0]) * g.inv), fy = floorf((y - g.lo[1]) * g.inv), fz = floorf((z - g.lo[2]) * g.inv);
+        if (!(fx >= 0.0f && fx < (float)g.dims[0] && fy >= 0.0f && fy < (float)g.dims[1] && fz >= 0.0f && fz < (float)g.dims[2])) {
+            lin32[i] = -1; ++outside; continue;
+        }
+        const int32_t lin = (int32_t)(((int64_t)fz * g.dims[1] + (int64_t)fy) * g.dims[0] + (int64_t)fx);   // (inside the table: the test above)
+        lin32[i] = lin;
+        slot[i] = atomicAdd(&cnt[lin], 1);
+        flag[lin] = 1;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        unmapped += __shfl_down(unmapped, off, 64);
+        outside += __shfl_down(outside, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (unmapped) atomicAdd(&tally[0], unmapped);
+        if (outside) atomicAdd(&tally[1], outside);
+    }
+}
+
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_insert_flags_kernel(const int32_t* __restrict__ old_cell, int64_t ncells,
+                                                                          int32_t* __restrict__ flag) {
+    for (int64_t c = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; c < ncells; c += (int64_t)gridDim.x * VMAP_THREADS)
+        flag[c] = old_cell[c] >= 0 ? 1 : 0;
+}
+
+// the map's cell table renumbered in place.  vox: the exclusive scan of the flags, ncells + 1 entries
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_insert_compact_kernel(int32_t* __restrict__ cell, const int32_t* __restrict__ cnt,
+                                                                            const int32_t* __restrict__ vox, int64_t ncells,
+                                                                            int64_t* __restrict__ lin, int32_t* __restrict__ vcnt,
+                                                                            int32_t* __restrict__ vold) {
+    for (int64_t c = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; c < ncells; c += (int64_t)gridDim.x * VMAP_THREADS) {
+        const int32_t v = vox[c];
+        if (vox[c + 1] == v) continue;
+        lin[v] = c;
+        vcnt[v] = cnt[c];   // (0: an old voxel no new point fell into)
+        vold[v] = cell[c];
+        cell[c] = v;
+    }
+}
+
+// one lane per voxel of the new numbering: the old sums continued through the voxel's new points in ascending index
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_continue_kernel(const float* __restrict__ pts, const float* __restrict__ nrm, const VmapPose T,
+                                                                      const int32_t* __restrict__ order, const int32_t* __restrict__ vstart,
+                                                                      const int32_t* __restrict__ vold, const double* __restrict__ old_rec,
+                                                                      const double* __restrict__ old_acc, int64_t nvox, double* __restrict__ rec,
+                                                                      double* __restrict__ acc) {
+    for (int64_t v = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * VMAP_THREADS) {
+        const int32_t lo = vstart[v], hi = vstart[v + 1];
+        const int64_t ov = vold[v];
+        double* r = rec + v * VMAP_NSTAT;
+        double* q = acc + v * VMAP_NACC;
+        if (lo == hi) {   // (an old voxel: a created one has a new point)
+#pragma unroll
+            for (int a = 0; a < VMAP_NSTAT; ++a) r[a] = old_rec[ov * VMAP_NSTAT + a];
+#pragma unroll
+            for (int a = 0; a < VMAP_NACC; ++a) q[a] = old_acc[ov * VMAP_NACC + a];
+            continue;
+        }
+        double N = 0.0, s[3] = {0.0, 0.0, 0.0}, P[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (ov >= 0) {
+            N = old_rec[ov * VMAP_NSTAT];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) s[a] = old_acc[ov * VMAP_NACC + a];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) P[a] = old_acc[ov * VMAP_NACC + 3 + a];
+        }
+        for (int32_t k = lo; k < hi; ++k) {
+            const int64_t i = order[k];
+            float x, y, z;
+            (void)vmap_moved(pts, nrm, i, T, x, y, z);
+            double n0 = (double)nrm[3 * i], n1 = (double)nrm[3 * i + 1], n2 = (double)nrm[3 * i + 2];
+            if (T.on) {   // VgicpMetric's expression for a turned source normal
+                const double u0 = n0, u1 = n1, u2 = n2;
+                n0 = ((double)T.m[0] * u0 + (double)T.m[1] * u1) + (double)T.m[2] * u2;
+                n1 = ((double)T.m[4] * u0 + (double)T.m[5] * u1) + (double)T.m[6] * u2;
+                n2 = ((double)T.m[8] * u0 + (double)T.m[9] * u1) + (double)T.m[10] * u2;
+            }
+            s[0] += (double)x; s[1] += (double)y; s[2] += (double)z;
+            P[0] += n0 * n0; P[1] += n0 * n1; P[2] += n0 * n2;
+            P[3] += n1 * n1; P[4] += n1 * n2;
+            P[5] += n2 * n2;
+        }
+        N += (double)(hi - lo);
+        r[0] = N;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { r[1 + a] = s[a] / N; q[a] = s[a]; }
+#pragma unroll
+        for (int a = 0; a < 6; ++a) { r[4 + a] = P[a] / N; q[3 + a] = P[a]; }
+    }
+}
+
+int vmap_empty(hipStream_t st, const float lo[3], const float hi[3], float inv, VmapBuilt& out) {
+    VmapBuilt b;
+    int64_t ncells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || hi[a] < lo[a]) return 1;
+        b.lo[a] = lo[a] == 0.0f ? 0.0f : lo[a];   // (a zero origin is +0)
+        const float f = floorf((hi[a] - b.lo[a]) * inv);   // vmap_build's lines
+        if (!(f >= 0.0f && f < (float)VMAP_MAX_CELLS)) return 1;   // (a NaN and an infinity included)
+        b.dims[a] = 1 + (int)f;
+        ncells *= b.dims[a];
+        if (ncells > VMAP_MAX_CELLS) return 1;
+    }
+    b.inv = inv;
+    if (hipMalloc((void**)&b.cell, (size_t)ncells * sizeof(int32_t)) != hipSuccess) return 2;
+    if (hipMemsetAsync(b.cell, 0xff, (size_t)ncells * sizeof(int32_t), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        vmap_free(b);
+        return 3;
+    }
+    out = b;
+    return 0;
+}
+
+int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d_nrm, int64_t n, const float* T, int64_t counts[VMAP_NINSERT]) {
+    VmapPose pose;
+    if (T) {
+        for (int k = 0; k < 12; ++k) pose.m[k] = T[k];
+        pose.on = 1;
+    }
+    VmapGrid g;
+    g.inv = b.inv;
+    for (int a = 0; a < 3; ++a) { g.lo[a] = b.lo[a]; g.dims[a] = b.dims[a]; }
+    const int64_t ncells = (int64_t)b.dims[0] * b.dims[1] * b.dims[2];
+    const int64_t vmax = std::min<int64_t>(b.nvox + n, ncells);   // at most this many voxels afterwards
+    const int nb = stream_blocks(n);
+    // ---- the scratch; the map is only read until the new records are allocated ----
+    VmapBuilt nw;   // rec, acc and lin that take the place of b's
+    VmapScratch w;
+    const size_t scan_bytes = std::max(scan_scratch_bytes((int)ncells), scan_scratch_bytes((int)vmax));
+    const size_t want = 2 * VmapScratch::pad((size_t)ncells * 4) + VmapScratch::pad(((size_t)ncells + 1) * 4) + VmapScratch::pad(scan_bytes) +
+                        4 * VmapScratch::pad((size_t)n * 4) + 2 * VmapScratch::pad((size_t)vmax * 4) + VmapScratch::pad(((size_t)vmax + 1) * 4) +
+                        VmapScratch::pad(2 * sizeof(unsigned long long));
+    if (hipMalloc((void**)&w.base, want) != hipSuccess) return 2;
+    int32_t* d_cnt = w.take<int32_t>((size_t)ncells);
+    int32_t* d_flag = w.take<int32_t>((size_t)ncells);
+    int32_t* d_vox = w.take<int32_t>((size_t)ncells + 1);
+    int32_t* d_scan = (int32_t*)w.take<char>(scan_bytes);
+    int32_t* d_lin32 = w.take<int32_t>((size_t)n);
+    int32_t* d_slot = w.take<int32_t>((size_t)n);
+    int32_t* d_tmp = w.take<int32_t>((size_t)n);
+    int32_t* d_order = w.take<int32_t>((size_t)n);
+    int32_t* d_vcnt = w.take<int32_t>((size_t)vmax);
+    int32_t* d_vold = w.take<int32_t>((size_t)vmax);
+    int32_t* d_vstart = w.take<int32_t>((size_t)vmax + 1);
+    unsigned long long* d_tally = w.take<unsigned long long>(2);
+    if (hipMemsetAsync(d_cnt, 0, (size_t)ncells * sizeof(int32_t), st) != hipSuccess) return 3;
+    if (hipMemsetAsync(d_tally, 0, 2 * sizeof(unsigned long long), st) != hipSuccess) return 3;
+    hipLaunchKernelGGL(vmap_insert_flags_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, (const int32_t*)b.cell, ncells, d_flag);
+    hipLaunchKernelGGL(vmap_insert_cell_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, d_pts, d_nrm, n, pose, g, d_lin32, d_slot, d_cnt, d_flag, d_tally);
+    launch_scan(st, d_flag, (int)ncells, d_vox, d_scan, false);
+    int32_t nvox32 = 0;
+    unsigned long long tally[2] = {0, 0};
+    if (hipMemcpyAsync(&nvox32, d_vox + ncells, sizeof nvox32, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
+    if (hipMemcpyAsync(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
+    if (hipGetLastError() != hipSuccess) return 3;
+    if (hipStreamSynchronize(st) != hipSuccess) return 3;
+    const int64_t nvox = nvox32;
+    const int64_t added = n - (int64_t)tally[0] - (int64_t)tally[1];
+    if (added < 0 || nvox < b.nvox || nvox > vmax || (added == 0 && nvox != b.nvox)) return 3;
+    counts[0] = added; counts[1] = (int64_t)tally[0]; counts[2] = (int64_t)tally[1]; counts[3] = nvox - b.nvox;
+    if (added == 0) return 0;   // nothing to add: the map stays
+    // the records that are not in use (the ones the last insert replaced) take the new ones; where they are too small they are
+    // released and allocated again with half as much headroom, so a sequence of inserts releases nothing but its scratch.  This is
+    // the last allocation, in front of the first store into the map's table
+    if (b.spare_cap < nvox) {
+        if (b.spare) (void)hipFree(b.spare);
+        b.spare = nullptr; b.spare_cap = 0;
+        const int64_t cap = std::min<int64_t>(nvox + nvox / 2, ncells);
+        if (hipMalloc(&b.spare, vmap_pack_bytes(cap)) != hipSuccess) { b.spare = nullptr; return 2; }
+        b.spare_cap = cap;
+    }
+    vmap_pack_at(nw, b.spare, b.spare_cap);
+    // ---- the table in place, the records beside the old ones (a HIP error from here on leaves a map that is not to be used) ----
+    hipLaunchKernelGGL(vmap_insert_compact_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, b.cell, (const int32_t*)d_cnt,
+                       (const int32_t*)d_vox, ncells, nw.lin, d_vcnt, d_vold);
+    launch_scan(st, d_vcnt, (int)nvox, d_vstart, d_scan, false);
+    hipLaunchKernelGGL(vmap_scatter_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, (const int32_t*)d_lin32, (const int32_t*)d_slot, n,
+                       (const int32_t*)b.cell, (const int32_t*)d_vstart, d_tmp);
+    hipLaunchKernelGGL(vmap_rank_fix_kernel, dim3(stream_blocks(added)), dim3(VMAP_THREADS), 0, st, (const int32_t*)d_tmp, added,
+                       (const int32_t*)d_lin32, (const int32_t*)b.cell, (const int32_t*)d_vstart, d_order);
+    hipLaunchKernelGGL(vmap_continue_kernel, dim3(stream_blocks(nvox)), dim3(VMAP_THREADS), 0, st, d_pts, d_nrm, pose, (const int32_t*)d_order,
+                       (const int32_t*)d_vstart, (const int32_t*)d_vold, (const double*)b.rec, (const double*)b.acc, nvox, nw.rec, nw.acc);
+    if (hipGetLastError() != hipSuccess) return 3;
+    if (hipStreamSynchronize(st) != hipSuccess) return 3;   // (the scratch is freed on return)
+    b.spare = b.rec; b.spare_cap = b.cap;   // (null and 0 for a box map's first insert)
+    b.rec = nw.rec; b.acc = nw.acc; b.lin = nw.lin; b.cap = nw.cap;
+    b.mapped += added; b.nvox = nvox;
     return 0;
 }
 
