@@ -779,13 +779,49 @@ int kss_vmap_read(kss_ctx *ctx, const kss_vmap *map, int64_t *lin, double *stats
  * it was: every allocation precedes the first store into the map's table, and the new records are built beside the old ones and
  * take their place at the end.  An insert costs a pass over the dense cell table, whatever n is, and synchronises the context's
  * stream.
- * Not offered: eviction of voxels or points, a box that slides or grows, a cap on the points a voxel takes. */
+ * Not offered: eviction of points, a box that grows, a cap on the points a voxel takes.  A box that slides: kss_vmap_shift below. */
 int kss_vmap_create_box(kss_ctx *ctx, const float lo[3], const float hi[3], const kss_vmap_params *vp, kss_vmap **out);
 #define KSS_VMAP_NINSERT 4   /* {points added, points not mapped, points outside the box, voxels created by this call} */
 int kss_vmap_insert(kss_ctx *ctx, kss_vmap *map, const float *pts, int64_t n, const float *normals,
                     const float T[16], int normals_k, double info[KSS_VMAP_NINSERT]);
 int kss_vmap_insert_dev(kss_ctx *ctx, kss_vmap *map, const float *d_pts, int64_t n, const float *d_normals,
                         const float T[16], int normals_k, double info[KSS_VMAP_NINSERT]);
+
+/* ---- a map whose box slides over its lattice ----
+ * For a sensor that travels: the box keeps its size and moves by whole cells, so the table stays small and the map follows.
+ * A map has a window base base_a, an integer number of cells per axis, 0 for every map from kss_vmap_create and
+ * kss_vmap_create_box.  lo, inv, leaf and dims never change: lo is the ANCHOR of the lattice, the corner of the box only while
+ * base = 0.  With a base, everywhere a map is looked up or inserted into (kss_vgicp_sums, kss_icp_vgicp, kss_icp_vgicp_batch,
+ * kss_vmap_insert):
+ *   cell        f_a = floorf((x_a - lo_a) * inv) as above, unchanged and not fused;
+ *   inside      (float)base_a <= f_a < (float)(base_a + dims_a) on all three axes, compared in float; a NaN is outside;
+ *   local cell  c_a = (int64)f_a - base_a, and lin = (c_z * dims_y + c_y) * dims_x + c_x from the local cells.
+ * base = 0 gives the expressions above in every bit.  kss_vmap_info keeps its ten slots, the origin slots stay lo;
+ * kss_vmap_read returns window-local lin; kss_vmap_window returns base (KSS_ERR_ARG: a NULL argument; like kss_vmap_info it
+ * trusts its handle).
+ *
+ * kss_vmap_shift: base'_a = base_a + k_a.  A voxel of local cell c survives iff 0 <= c_a - k_a < dims_a on all three axes; its
+ * new lin is lin - delta, delta = (k_z * dims_y + k_y) * dims_x + k_x, so the survivors stay packed in ascending lin in their
+ * relative order, and each keeps its record and its f64 sums BIT FOR BIT.  A voxel that does not survive is gone: if its cell
+ * comes back into the window later, the cell is empty.  info[0] of kss_vmap_info drops by the sum of the dropped voxels' N (an
+ * integer sum, exact in any order).  k = (0, 0, 0): KSS_OK, nothing is launched, the map is untouched.  |k_a| >= dims_a on any
+ * axis: the map becomes empty as kss_vmap_create_box leaves one.  info (may be NULL): KSS_VMAP_NSHIFT doubles.
+ * KSS_ERR_ARG: a NULL ctx, map or k; not a live map of ctx; base'_a < -2^24 or base'_a + dims_a > 2^24 on any axis (beyond
+ * that f is not an exact integer in float).  A refused call or a failed allocation leaves the map exactly as it was: every
+ * allocation precedes the first store into the table.  A shift costs O(voxels) -- the table is touched at occupied cells alone
+ * -- and synchronises the context's stream.
+ *
+ * kss_vmap_recentre: the shift that brings centre's cell to the middle of the window, decided on the host, then one
+ * kss_vmap_shift.  f_a of centre by the map's expression;  want_a = (int64)f_a - dims_a / 2 (integer division);
+ * k_a = want_a - base_a if |want_a - base_a| > slack, else 0.  k_out (may be NULL) receives k.  KSS_ERR_ARG: a NULL centre; a
+ * centre that is not finite; slack < 0; an |f_a| above 2^24; everything kss_vmap_shift refuses.
+ * Not offered: eviction by age, a cap on the points a voxel takes, a window that changes dims, a shift by a fraction of a cell,
+ * remembering what left the window; the C++ mirror classes and the CLI do not have these entries. */
+#define KSS_VMAP_NSHIFT 4   /* {voxels kept, voxels dropped, mapped points dropped, delta} */
+int kss_vmap_window(const kss_vmap *map, int64_t base[3]);
+int kss_vmap_shift(kss_ctx *ctx, kss_vmap *map, const int64_t k[3], double info[KSS_VMAP_NSHIFT]);
+int kss_vmap_recentre(kss_ctx *ctx, kss_vmap *map, const float centre[3], int64_t slack, int64_t k_out[3],
+                      double info[KSS_VMAP_NSHIFT]);
 
 /* One pass.  F and R_F as in kss_icp_gicp.  For source i: its current float position p and its float normal ns = src_normals[i]
  * (by ORIGINAL index).  Everything after the lookup is f64 on the widened floats, nothing fused, in kss_icp_gicp's order:

@@ -16,7 +16,7 @@ from .binding import (KssError, Context, IcpParams, IcpResult, RegisterResult, P
                       LOSS_L2, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, ROBUST_NINFO, RobustParams, robust_params, robust_weight,
                       robust_scale2, GicpParams, gicp_params, gicp_metric, SymmParams, symm_params, rigid_from_symm_sums,
                       SIM_NINFO, SimParams, sim_params, sim_from_sums, O2O_NINFO, O2oParams, o2o_params,
-                      RECIP_NINFO, RecipParams, recip_params, VMAP_NINFO, VMAP_NSTAT, VMAP_NINSERT, VGICP_NINFO, VmapParams, vmap_params, VoxelMap)
+                      RECIP_NINFO, RecipParams, recip_params, VMAP_NINFO, VMAP_NSTAT, VMAP_NINSERT, VMAP_NSHIFT, VGICP_NINFO, VmapParams, vmap_params, VoxelMap)
 from . import synth
 from . import shard
 
@@ -27,4 +27,4 @@ __all__ = ["KssError", "Context", "IcpParams", "IcpResult", "RegisterResult", "P
            "LOSS_L2", "LOSS_HUBER", "LOSS_TUKEY", "LOSS_CAUCHY", "ROBUST_NINFO", "RobustParams", "robust_params", "robust_weight",
            "robust_scale2", "GicpParams", "gicp_params", "gicp_metric", "SymmParams", "symm_params", "rigid_from_symm_sums",
            "SIM_NINFO", "SimParams", "sim_params", "sim_from_sums", "O2O_NINFO", "O2oParams", "o2o_params",
-           "RECIP_NINFO", "RecipParams", "recip_params", "VMAP_NINFO", "VMAP_NSTAT", "VMAP_NINSERT", "VGICP_NINFO", "VmapParams", "vmap_params", "VoxelMap"]
+           "RECIP_NINFO", "RecipParams", "recip_params", "VMAP_NINFO", "VMAP_NSTAT", "VMAP_NINSERT", "VMAP_NSHIFT", "VGICP_NINFO", "VmapParams", "vmap_params", "VoxelMap"]

@@ -29,6 +29,7 @@ O2O_NINFO = 5            # KSS_O2O_NINFO: {u survivors, k, tau, kept, m candidat
 VMAP_NINFO = 10          # KSS_VMAP_NINFO: {mapped targets, voxels, dims x y z, leaf, origin x y z, inv widened} of a voxel map
 VMAP_NSTAT = 10          # KSS_VMAP_NSTAT: {N, mean x y z, S00 S01 S02 S11 S12 S22} of a voxel
 VMAP_NINSERT = 4         # KSS_VMAP_NINSERT: {points added, points not mapped, points outside the box, voxels created} of an insert
+VMAP_NSHIFT = 4          # KSS_VMAP_NSHIFT: {voxels kept, voxels dropped, mapped points dropped, delta} of a shift
 VGICP_NINFO = 4          # KSS_VGICP_NINFO: {kept in the last pass, ns, [30] of the last pass, voxels of the map}
 RECIP_NINFO = 6          # KSS_RECIP_NINFO: {r mutual winners, k, tau, kept, m candidates, u winners} of a reciprocal pass
 F32, F64 = 0, 1
@@ -61,7 +62,7 @@ SYMBOLS = [
     "kss_recip_filter", "kss_recip_filter_dev", "kss_recip_default_params", "kss_icp_recip", "kss_icp_recip_dev",
     "kss_recip_filter_batch", "kss_recip_filter_batch_dev", "kss_icp_recip_pairs", "kss_icp_recip_pairs_dev",
     "kss_vmap_default_params", "kss_vmap_create", "kss_vmap_create_dev", "kss_vmap_destroy", "kss_vmap_info", "kss_vmap_read",
-    "kss_vmap_create_box", "kss_vmap_insert", "kss_vmap_insert_dev",
+    "kss_vmap_create_box", "kss_vmap_insert", "kss_vmap_insert_dev", "kss_vmap_window", "kss_vmap_shift", "kss_vmap_recentre",
     "kss_vgicp_sums", "kss_vgicp_sums_dev", "kss_icp_vgicp", "kss_icp_vgicp_dev",
     "kss_icp_vgicp_batch", "kss_icp_vgicp_batch_dev",
 ]
@@ -251,6 +252,9 @@ def _declare(L):
     L.kss_vmap_create_box.argtypes = [vp, vp, vp, C.POINTER(VmapParams), C.POINTER(vp)]
     for n in ("kss_vmap_insert", "kss_vmap_insert_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, i64, vp, vp, C.c_int, vp]
+    L.kss_vmap_window.argtypes = [vp, vp]
+    L.kss_vmap_shift.argtypes = [vp, vp, vp, vp]
+    L.kss_vmap_recentre.argtypes = [vp, vp, vp, i64, vp, vp]
     for n in ("kss_vgicp_sums", "kss_vgicp_sums_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, i64, vp, dbl, vp, C.POINTER(GicpParams), vp]
     for n in ("kss_icp_vgicp", "kss_icp_vgicp_dev"):
@@ -559,6 +563,31 @@ class VoxelMap:
     def insert_dev(self, d_pts, n, d_normals, T=None, normals_k=20):
         """kss_vmap_insert_dev on device pointers (the normals pointer may be 0 / None; T stays a host array)."""
         return self._insert("kss_vmap_insert_dev", _dp(d_pts), n, _dp(d_normals), T, normals_k)
+
+    def window(self):
+        """kss_vmap_window: the window base, three int64 cells (0 until a shift)."""
+        base = np.zeros(3, np.int64)
+        rc = self.ctx.L.kss_vmap_window(self.h, _p(base))
+        if rc != 0:
+            raise KssError(rc, "kss_vmap_window")
+        return base
+
+    def shift(self, k):
+        """kss_vmap_shift: the window moved by k whole cells per axis (3 integers); voxels that leave it are gone.  Returns the
+        VMAP_NSHIFT doubles {voxels kept, voxels dropped, mapped points dropped, delta}."""
+        kk = np.ascontiguousarray([int(x) for x in np.asarray(k).reshape(3)], dtype=np.int64)
+        info = np.zeros(VMAP_NSHIFT, np.float64)
+        self.ctx._chk(self.ctx.L.kss_vmap_shift(self.ctx.h, self.h, _p(kk), _p(info)), "kss_vmap_shift")
+        return info
+
+    def recentre(self, centre, slack=0):
+        """kss_vmap_recentre: the shift that brings the cell of centre (3 floats) to the middle of the window, made on the axes
+        where it is more than `slack` cells.  Returns (k [3] int64, the VMAP_NSHIFT doubles)."""
+        c = np.ascontiguousarray(centre, dtype=np.float32).reshape(3)
+        k = np.zeros(3, np.int64)
+        info = np.zeros(VMAP_NSHIFT, np.float64)
+        self.ctx._chk(self.ctx.L.kss_vmap_recentre(self.ctx.h, self.h, _p(c), int(slack), _p(k), _p(info)), "kss_vmap_recentre")
+        return k, info
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):

@@ -1162,6 +1162,51 @@ int kss_vmap_insert(kss_ctx* c, kss_vmap* m, const float* pts, int64_t n, const 
     return vmap_insert_any(c, true, m, pts, n, normals, T, normals_k, info);
 }
 
+// ---- a window that slides over the lattice ----
+int kss_vmap_window(const kss_vmap* m, int64_t base[3]) {
+    if (!m || !base) return KSS_ERR_ARG;
+    for (int a = 0; a < 3; ++a) base[a] = m->b.base[a];
+    return KSS_OK;
+}
+
+// the shift by k of a live map of c; who: the entry's name in the error text
+static int vmap_shift_checked(kss_ctx* c, const char* who, kss_vmap* m, const int64_t k[3], double* info) {
+    constexpr int64_t LIM = 1ll << 24;   // beyond it f is not an exact integer in float
+    for (int a = 0; a < 3; ++a) {
+        if (k[a] > 2 * LIM || k[a] < -2 * LIM) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": the window would leave +-2^24 cells").c_str());
+        const int64_t nb = m->b.base[a] + k[a];
+        if (nb < -LIM || nb + m->b.dims[a] > LIM) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": the window would leave +-2^24 cells").c_str());
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int64_t counts[KSS_VMAP_NSHIFT] = {0, 0, 0, 0};
+    const int rc = vmap_shift(c->stream, m->b, k, counts);
+    if (rc != 0) return rc == 2 ? set_err(c, KSS_ERR_NOMEM, (std::string(who) + ": hipMalloc").c_str()) : set_err(c, KSS_ERR_HIP, (std::string(who) + ": the shift failed").c_str());
+    for (int i = 0; info && i < KSS_VMAP_NSHIFT; ++i) info[i] = (double)counts[i];
+    return KSS_OK;
+}
+
+int kss_vmap_shift(kss_ctx* c, kss_vmap* m, const int64_t k[3], double info[KSS_VMAP_NSHIFT]) {
+    if (!c) return KSS_ERR_ARG;
+    if (!k) return set_err(c, KSS_ERR_ARG, "vmap_shift: null argument");
+    if (!vmap_live(c, m)) return set_err(c, KSS_ERR_ARG, "vmap_shift: not a live map of this context");
+    return vmap_shift_checked(c, "vmap_shift", m, k, info);
+}
+
+int kss_vmap_recentre(kss_ctx* c, kss_vmap* m, const float centre[3], int64_t slack, int64_t k_out[3], double info[KSS_VMAP_NSHIFT]) {
+    if (!c) return KSS_ERR_ARG;
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string("vmap_recentre: ") + what).c_str()); };
+    if (!centre) return bad("null argument");
+    if (!vmap_live(c, m)) return bad("not a live map of this context");
+    if (!std::isfinite(centre[0]) || !std::isfinite(centre[1]) || !std::isfinite(centre[2])) return bad("centre must be finite");
+    if (slack < 0) return bad("slack must be >= 0");
+    int64_t k[3];
+    if (!vmap_recentre_k(m->b, centre, slack, k)) return bad("the centre's cell is beyond +-2^24");
+    const int rc = vmap_shift_checked(c, "vmap_recentre", m, k, info);
+    if (rc == KSS_OK && k_out)
+        for (int a = 0; a < 3; ++a) k_out[a] = k[a];
+    return rc;
+}
+
 // what both the record and the loop check and stage: the source on the device with its normals, given or computed
 static int vgicp_enter(kss_ctx* c, const char* who, bool host, const float*& src, const float*& snrm, int64_t n, const kss_vmap* m,
                        const kss_gicp_params* gp, const void* out) {

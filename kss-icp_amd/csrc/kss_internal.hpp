@@ -342,7 +342,8 @@ void launch_p2l_final(hipStream_t st, const double* d_rows, int nrows, double* d
 // ---- voxelized generalized ICP (kss_vmap.hip, kss_pair.hip) ----
 // A voxel map as the kernels see it, by value: the dense cell -> voxel table over dims[0] * dims[1] * dims[2] cells (-1: empty,
 // lin = (cz * dims[1] + cy) * dims[0] + cx), the packed voxel records in ascending lin and the float origin and 1 / leaf of
-// f_a = floorf((x_a - lo[a]) * inv).
+// f_a = floorf((x_a - lo[a]) * inv).  base: the window's first cell per axis on that lattice (kss_vmap_shift; 0
+// until a shift): a point is inside iff base[a] <= f_a < base[a] + dims[a], and its local cell is f_a - base[a].
 constexpr int VMAP_NSTAT = 10;                   // {N, mean x y z, S00 S01 S02 S11 S12 S22}
 constexpr int64_t VMAP_MAX_CELLS = 1ll << 26;
 static_assert(VMAP_NSTAT == KSS_VMAP_NSTAT, "kss_internal.hpp and include/kssicp.h disagree");
@@ -350,6 +351,7 @@ struct VmapDev {
     const int32_t* cell; const double* rec;
     float lo[3]; float inv;
     int dims[3];
+    int base[3];
 };
 struct VmapMove { float m[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}; };   // the upper three rows of a row-major float 4 x 4
 // What the build hands back: the device arrays the map owns (cell; rec with acc and lin behind it in one allocation; after an
@@ -358,13 +360,15 @@ struct VmapMove { float m[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}; };   // th
 // insert continues.  A map without a voxel (vmap_empty) holds the table alone: rec, lin and acc are null.
 constexpr int VMAP_NACC = 9;
 constexpr int VMAP_NINSERT = 4;                  // {points added, points not mapped, points outside the box, voxels created}
-static_assert(VMAP_NINSERT == KSS_VMAP_NINSERT, "kss_internal.hpp and include/kssicp.h disagree");
+constexpr int VMAP_NSHIFT = 4;                   // {voxels kept, voxels dropped, mapped points dropped, delta}
+static_assert(VMAP_NINSERT == KSS_VMAP_NINSERT && VMAP_NSHIFT == KSS_VMAP_NSHIFT, "kss_internal.hpp and include/kssicp.h disagree");
 struct VmapBuilt {
     int32_t* cell = nullptr; double* rec = nullptr; int64_t* lin = nullptr; double* acc = nullptr;
     int64_t cap = 0;                          // voxels the allocation behind rec has room for (>= nvox)
     void* spare = nullptr; int64_t spare_cap = 0;   // the allocation the last insert's records left behind: the next insert's
     int64_t mapped = 0, nvox = 0;
     int dims[3] = {0, 0, 0};
+    int base[3] = {0, 0, 0};                  // the window's first cell per axis (kss_vmap_shift); |base|, |base + dims| <= 2^24
     float lo[3] = {0, 0, 0}, inv = 0;
 };
 // The build: eleven to thirteen launches and three synchronisations on st; its scratch is allocated and freed inside.  0: built; 1: no mapped
@@ -379,6 +383,13 @@ int vmap_empty(hipStream_t st, const float lo[3], const float hi[3], float inv, 
 // new records, lin and sums are built beside b's and take their place after the last synchronisation.  2 (out of memory): b is
 // what it was.  counts: the VMAP_NINSERT tallies.  Scratch is allocated and freed inside.
 int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d_nrm, int64_t n, const float* T, int64_t counts[VMAP_NINSERT]);
+// The window of b moved by k whole cells per axis (kss_vmap_shift's definition; the caller has checked that the new base is in
+// range): O(voxels), no pass over the dense table.  Every allocation precedes the first store into b's table; the survivors are
+// packed into b.spare, which then changes places with the records.  2 (out of memory): b is what it was.  counts: the VMAP_NSHIFT
+// tallies.  k = 0 and a map without a voxel launch nothing.
+int vmap_shift(hipStream_t st, VmapBuilt& b, const int64_t k[3], int64_t counts[VMAP_NSHIFT]);
+// kss_vmap_recentre's k for the centre (finite) at the slack: false where an |f_a| is above 2^24
+bool vmap_recentre_k(const VmapBuilt& b, const float centre[3], int64_t slack, int64_t k[3]);
 struct GicpRot;
 // one rows launch of pair_rows_kernel over VgicpMetric: a.n sources (packed float triples d_in, normals a.s.sn) against the map;
 // T set: every source is first moved by *T and stored to d_out (not d_in)

@@ -200,8 +200,12 @@ __device__ __forceinline__ void vgicp_source(double (&acc)[P2L_NSUMS], const flo
         out[3 * i] = sx; out[3 * i + 1] = sy; out[3 * i + 2] = sz;
     }
     const float fx = floorf((sx - v.lo[0]) * v.inv), fy = floorf((sy - v.lo[1]) * v.inv), fz = floorf((sz - v.lo[2]) * v.inv);
-    if (!(fx >= 0.0f && fx < (float)v.dims[0] && fy >= 0.0f && fy < (float)v.dims[1] && fz >= 0.0f && fz < (float)v.dims[2])) return;
-    const int32_t vox = v.cell[((int64_t)fz * v.dims[1] + (int64_t)fy) * v.dims[0] + (int64_t)fx];   // (inside the table: the test above)
+    // the window (kss_vmap_shift): base <= f < base + dims, both bounds exact in float; base = 0 gives 0 <= f < dims
+    if (!(fx >= (float)v.base[0] && fx < (float)(v.base[0] + v.dims[0]) && fy >= (float)v.base[1] && fy < (float)(v.base[1] + v.dims[1]) &&
+          fz >= (float)v.base[2] && fz < (float)(v.base[2] + v.dims[2]))) return;
+    // (inside the window |f| <= 2^24, so the conversion to int is the conversion to int64; inside the table: the test above)
+    const int cx = (int)fx - v.base[0], cy = (int)fy - v.base[1], cz = (int)fz - v.base[2];
+    const int32_t vox = v.cell[((int64_t)cz * v.dims[1] + cy) * v.dims[0] + cx];
     if (vox < 0) return;
     const float ux = sn[3 * i], uy = sn[3 * i + 1], uz = sn[3 * i + 2];
     if (!(isfinite(ux) && isfinite(uy) && isfinite(uz))) return;

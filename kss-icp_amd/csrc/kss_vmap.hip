@@ -109,6 +109,7 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_bounds_final_kernel(const f
 struct VmapGrid {
     float lo[3]; float inv;
     int dims[3];
+    int base[3];   // the window's first cell per axis (0 in the build, whose box starts at the origin): VmapDev's
 };
 
 // the cell of a mapped target.  x >= lo and x <= hi give 0 <= f <= dims - 1 (subtraction, multiplication by inv >= 0 and floorf
@@ -268,6 +269,7 @@ int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t n
     g.inv = inv;
     int64_t ncells = 1;
     for (int a = 0; a < 3; ++a) {
+        g.base[a] = 0;
         g.lo[a] = hbox[a] == 0.0f ? 0.0f : hbox[a];   // (a zero origin is +0)
         const float f = floorf((hbox[3 + a] - g.lo[a]) * inv);
         if (!(f >= 0.0f && f < (float)VMAP_MAX_CELLS)) return 1;   // (a NaN included: 0 * inf)
@@ -366,12 +368,14 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_insert_cell_kernel(const fl
     for (int64_t i = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * VMAP_THREADS) {
         float x, y, z;
         if (!vmap_moved(pts, nrm, i, T, x, y, z)) { lin32[i] = -1; ++unmapped; continue; }
-        // the lookup's rule (vgicp_source): compared in float
+        // the lookup's rule (vgicp_source): compared in float, against the window base .. base + dims
         const float fx = floorf((x - g.lo[0]) * g.inv), fy = floorf((y - g.lo[1]) * g.inv), fz = floorf((z - g.lo[2]) * g.inv);
-        if (!(fx >= 0.0f && fx < (float)g.dims[0] && fy >= 0.0f && fy < (float)g.dims[1] && fz >= 0.0f && fz < (float)g.dims[2])) {
+        if (!(fx >= (float)g.base[0] && fx < (float)(g.base[0] + g.dims[0]) && fy >= (float)g.base[1] && fy < (float)(g.base[1] + g.dims[1]) &&
+              fz >= (float)g.base[2] && fz < (float)(g.base[2] + g.dims[2]))) {
             lin32[i] = -1; ++outside; continue;
         }
-        const int32_t lin = (int32_t)(((int64_t)fz * g.dims[1] + (int64_t)fy) * g.dims[0] + (int64_t)fx);   // (inside the table: the test above)
+        const int cx = (int)fx - g.base[0], cy = (int)fy - g.base[1], cz = (int)fz - g.base[2];   // (|f| <= 2^24 inside the window)
+        const int32_t lin = (int32_t)(((int64_t)cz * g.dims[1] + cy) * g.dims[0] + cx);   // (inside the table: the test above)
         lin32[i] = lin;
         slot[i] = atomicAdd(&cnt[lin], 1);
         flag[lin] = 1;
@@ -489,7 +493,7 @@ int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d
     }
     VmapGrid g;
     g.inv = b.inv;
-    for (int a = 0; a < 3; ++a) { g.lo[a] = b.lo[a]; g.dims[a] = b.dims[a]; }
+    for (int a = 0; a < 3; ++a) { g.lo[a] = b.lo[a]; g.dims[a] = b.dims[a]; g.base[a] = b.base[a]; }
     const int64_t ncells = (int64_t)b.dims[0] * b.dims[1] * b.dims[2];
     const int64_t vmax = std::min<int64_t>(b.nvox + n, ncells);   // at most this many voxels afterwards
     const int nb = stream_blocks(n);
@@ -555,6 +559,143 @@ int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d
     b.spare = b.rec; b.spare_cap = b.cap;   // (null and 0 for a box map's first insert)
     b.rec = nw.rec; b.acc = nw.acc; b.lin = nw.lin; b.cap = nw.cap;
     b.mapped += added; b.nvox = nvox;
+    return 0;
+}
+
+// ---- the window moved over the lattice (kss_vmap_shift) --------------------------------------------------------
+// lo, inv, leaf and dims stay; base += k.  A voxel of local cell c survives iff 0 <= c_a - k_a < dims_a on all three axes, and its
+// lin becomes lin - delta, delta = (k_z * dims_y + k_y) * dims_x + k_x: the survivors keep their relative order, so they stay
+// packed in ascending lin and their rec and acc are copied bit for bit.  No pass over the dense table:
+//   flag                  one lane per old voxel: its lin decoded into the local cell, the survive flag, and the dropped voxels' N
+//                         tallied as a 64-bit integer (a wave shuffle, one integer atomic per wave);
+//   scan                  the new numbering; the kept count and the tally go to the host, which makes room in b.spare.  Up to here
+//                         the map has only been read;
+//   clear                 cell[lin[v]] = -1 for every old voxel, dropped ones included;
+//   move                  a launch of its own behind the clear -- one voxel's new cell may be another voxel's old one -- : a
+//                         survivor's rec, acc and lin - delta into its new slot, the slot's number into cell[lin - delta].
+// The host then swaps the record allocations as the insert does.  Nothing survives: the clear alone, and the map is an empty one.
+struct VmapShift {
+    int dims[3];
+    int k[3];   // clamped to +-dims: a larger shift drops everything just the same
+};
+
+__device__ __forceinline__ bool vmap_shift_survives(const VmapShift& s, int64_t lin) {
+    const int64_t row = lin / s.dims[0];
+    const int cx = (int)(lin - row * s.dims[0]), cz = (int)(row / s.dims[1]), cy = (int)(row - (int64_t)cz * s.dims[1]);
+    const int nx = cx - s.k[0], ny = cy - s.k[1], nz = cz - s.k[2];
+    return nx >= 0 && nx < s.dims[0] && ny >= 0 && ny < s.dims[1] && nz >= 0 && nz < s.dims[2];
+}
+
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_shift_flag_kernel(const int64_t* __restrict__ lin, const double* __restrict__ rec, int64_t nvox,
+                                                                        const VmapShift s, int32_t* __restrict__ flag,
+                                                                        unsigned long long* __restrict__ tally) {
+    unsigned long long dropped = 0;
+    for (int64_t v = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * VMAP_THREADS) {
+        const bool keep = vmap_shift_survives(s, lin[v]);
+        flag[v] = keep ? 1 : 0;
+        if (!keep) dropped += (unsigned long long)rec[v * VMAP_NSTAT];   // N: an integer below 2^53
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) dropped += __shfl_down(dropped, off, 64);
+    if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(&tally[0], dropped);
+}
+
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_shift_clear_kernel(const int64_t* __restrict__ lin, int64_t nvox, int32_t* __restrict__ cell) {
+    for (int64_t v = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * VMAP_THREADS) cell[lin[v]] = -1;
+}
+
+// num: the exclusive scan of the flags, nvox + 1 entries; a survivor is a voxel the scan steps over
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_shift_move_kernel(const int64_t* __restrict__ lin, const double* __restrict__ rec,
+                                                                        const double* __restrict__ acc, const int32_t* __restrict__ num, int64_t nvox,
+                                                                        int64_t ncells, int64_t delta, int64_t* __restrict__ nlin, double* __restrict__ nrec,
+                                                                        double* __restrict__ nacc, int32_t* __restrict__ cell) {
+    for (int64_t v = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * VMAP_THREADS) {
+        const int64_t w = num[v];
+        if (num[v + 1] == w) continue;
+        const int64_t to = lin[v] - delta;
+        if (to < 0 || to >= ncells) continue;   // (a survivor's new cell is in the window: this only keeps a store inside the table)
+#pragma unroll
+        for (int a = 0; a < VMAP_NSTAT; ++a) nrec[w * VMAP_NSTAT + a] = rec[v * VMAP_NSTAT + a];
+#pragma unroll
+        for (int a = 0; a < VMAP_NACC; ++a) nacc[w * VMAP_NACC + a] = acc[v * VMAP_NACC + a];
+        nlin[w] = to;
+        cell[to] = (int32_t)w;
+    }
+}
+
+bool vmap_recentre_k(const VmapBuilt& b, const float centre[3], int64_t slack, int64_t k[3]) {
+    for (int a = 0; a < 3; ++a) {
+        const float f = floorf((centre[a] - b.lo[a]) * b.inv);   // the map's expression
+        if (!(fabsf(f) <= 16777216.0f)) return false;            // (a NaN and an infinity included)
+        const int64_t d = ((int64_t)f - b.dims[a] / 2) - b.base[a];
+        k[a] = (d > slack || -d > slack) ? d : 0;
+    }
+    return true;
+}
+
+int vmap_shift(hipStream_t st, VmapBuilt& b, const int64_t k[3], int64_t counts[VMAP_NSHIFT]) {
+    VmapShift s;
+    for (int a = 0; a < 3; ++a) {
+        s.dims[a] = b.dims[a];
+        s.k[a] = (int)std::max<int64_t>(-b.dims[a], std::min<int64_t>(b.dims[a], k[a]));
+    }
+    const int64_t delta = (k[2] * b.dims[1] + k[1]) * b.dims[0] + k[0];   // (|k_a| <= 2^25 and dims_x * dims_y <= 2^26: below 2^52)
+    counts[0] = b.nvox; counts[1] = 0; counts[2] = 0; counts[3] = delta;
+    if (k[0] == 0 && k[1] == 0 && k[2] == 0) return 0;
+    if (b.nvox == 0) {   // nothing to move: the window alone
+        for (int a = 0; a < 3; ++a) b.base[a] += (int)k[a];
+        return 0;
+    }
+    const int64_t ncells = (int64_t)b.dims[0] * b.dims[1] * b.dims[2];
+    const int64_t nvox = b.nvox;
+    const int nb = stream_blocks(nvox);
+    // ---- the scratch; the map is only read until the destination is allocated ----
+    VmapScratch w;
+    const size_t scan_bytes = scan_scratch_bytes((int)nvox);
+    const size_t want = VmapScratch::pad((size_t)nvox * 4) + VmapScratch::pad(((size_t)nvox + 1) * 4) + VmapScratch::pad(scan_bytes) +
+                        VmapScratch::pad(sizeof(unsigned long long));
+    if (hipMalloc((void**)&w.base, want) != hipSuccess) return 2;
+    int32_t* d_flag = w.take<int32_t>((size_t)nvox);
+    int32_t* d_num = w.take<int32_t>((size_t)nvox + 1);
+    int32_t* d_scan = (int32_t*)w.take<char>(scan_bytes);
+    unsigned long long* d_tally = w.take<unsigned long long>(1);
+    if (hipMemsetAsync(d_tally, 0, sizeof(unsigned long long), st) != hipSuccess) return 3;
+    hipLaunchKernelGGL(vmap_shift_flag_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, (const int64_t*)b.lin, (const double*)b.rec, nvox, s, d_flag, d_tally);
+    launch_scan(st, d_flag, (int)nvox, d_num, d_scan, false);
+    int32_t kept32 = 0;
+    unsigned long long tally = 0;
+    if (hipMemcpyAsync(&kept32, d_num + nvox, sizeof kept32, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
+    if (hipMemcpyAsync(&tally, d_tally, sizeof tally, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
+    if (hipGetLastError() != hipSuccess) return 3;
+    if (hipStreamSynchronize(st) != hipSuccess) return 3;
+    const int64_t kept = kept32;
+    if (kept < 0 || kept > nvox || (int64_t)tally > b.mapped || (kept == nvox) != (tally == 0) || (kept == 0 && (int64_t)tally != b.mapped)) return 3;
+    // the destination: the records not in use, grown by the insert's rule where they are too small.  The last allocation, in
+    // front of the first store into the map's table
+    if (kept > 0 && b.spare_cap < kept) {
+        if (b.spare) (void)hipFree(b.spare);
+        b.spare = nullptr; b.spare_cap = 0;
+        const int64_t cap = std::min<int64_t>(kept + kept / 2, ncells);
+        if (hipMalloc(&b.spare, vmap_pack_bytes(cap)) != hipSuccess) { b.spare = nullptr; return 2; }
+        b.spare_cap = cap;
+    }
+    // ---- the table at the occupied cells alone (a HIP error from here on leaves a map that is not to be used) ----
+    hipLaunchKernelGGL(vmap_shift_clear_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, (const int64_t*)b.lin, nvox, b.cell);
+    VmapBuilt nw;
+    if (kept > 0) {
+        vmap_pack_at(nw, b.spare, b.spare_cap);
+        hipLaunchKernelGGL(vmap_shift_move_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, (const int64_t*)b.lin, (const double*)b.rec, (const double*)b.acc,
+                           (const int32_t*)d_num, nvox, ncells, delta, nw.lin, nw.rec, nw.acc, b.cell);
+    }
+    if (hipGetLastError() != hipSuccess) return 3;
+    if (hipStreamSynchronize(st) != hipSuccess) return 3;   // (the scratch is freed on return)
+    if (kept > 0) {
+        b.spare = b.rec; b.spare_cap = b.cap;
+        b.rec = nw.rec; b.acc = nw.acc; b.lin = nw.lin; b.cap = nw.cap;
+    }   // (nothing kept: the records stay where they are, with no voxel in them)
+    for (int a = 0; a < 3; ++a) b.base[a] += (int)k[a];
+    b.mapped -= (int64_t)tally; b.nvox = kept;
+    counts[0] = kept; counts[1] = nvox - kept; counts[2] = (int64_t)tally;
     return 0;
 }
 
