@@ -484,40 +484,12 @@ __device__ __forceinline__ void top3_insert(float d, int j, float (&bd)[3], int 
     }
 }
 
-// one wave per sample: lanes stride over the samples keeping their own top-3, lane 0 merges the 64 x 3 candidates
-__global__ __launch_bounds__(64) void aivs_knn3_kernel(const double* __restrict__ P, const int32_t* __restrict__ samples, int ns,
-                                                       int32_t* __restrict__ nn1, float* __restrict__ d1, float* __restrict__ d2) {
-    __shared__ float sd[64][3];
-    __shared__ int si[64][3];
-    const int i = blockIdx.x, lane = threadIdx.x;
-    const int pi = samples[i];
-    const float ax = (float)P[3 * (int64_t)pi], ay = (float)P[3 * (int64_t)pi + 1], az = (float)P[3 * (int64_t)pi + 2];
-    float bd[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-    int bi[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
-    for (int j = lane; j < ns; j += 64) {
-        const int pj = samples[j];
-        const float dx = ax - (float)P[3 * (int64_t)pj], dy = ay - (float)P[3 * (int64_t)pj + 1], dz = az - (float)P[3 * (int64_t)pj + 2];
-        top3_insert((dx * dx + dy * dy) + dz * dz, j, bd, bi);
-    }
-    for (int k = 0; k < 3; ++k) { sd[lane][k] = bd[k]; si[lane][k] = bi[k]; }
-    __syncthreads();
-    if (lane == 0) {
-        float md[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
-        int mi[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff};
-        for (int l = 0; l < 64; ++l)
-            for (int k = 0; k < 3; ++k)
-                if (si[l][k] != 0x7fffffff) top3_insert(sd[l][k], si[l][k], md, mi);
-        nn1[i] = mi[1];
-        d1[i] = sqrtf(md[1]);
-        d2[i] = sqrtf(md[2]);
-    }
-}
-
-// The same from a packed copy of the samples' float coordinates (aivs_sample_coords_kernel): a step of the walk is three
-// coalesced loads that depend on nothing, four steps in flight -- the kernel above goes through samples[j] and then P[]: two
+// One wave per sample, four samples per block: the lanes stride over all samples, each keeping its own top-3, and the wave
+// merges them.  The walk reads a packed copy of the samples' float coordinates (aivs_sample_coords_kernel): a step is three
+// coalesced loads that depend on nothing, four steps in flight -- going through samples[j] and then P[] would be two
 // dependent round trips per step, 1.5 us each -- and the 64 x 3 candidates of a wave are merged by three rounds of a
-// wave-wide minimum on (distance, index) instead of one lane inserting 192 entries.  The three nearest under a strict total
-// order do not depend on the order of evaluation: same results.
+// wave-wide minimum on (distance, index), not by one lane inserting 192 entries.  The three nearest under a strict total
+// order do not depend on the order of evaluation.
 __global__ __launch_bounds__(256) void aivs_sample_coords_kernel(const double* __restrict__ P, const int32_t* __restrict__ samples, int ns, float* __restrict__ co) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= ns) return;
