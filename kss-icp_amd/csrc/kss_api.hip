@@ -4,6 +4,7 @@
 #pragma clang fp contract(off)
 
 #include <cmath>
+#include <functional>
 
 #include "kss_ctx.hpp"
 #include "kss_gicp.hpp"
@@ -1026,6 +1027,42 @@ static bool vmap_live(const kss_ctx* c, const kss_vmap* m) {
     return m && std::find(c->vmaps.begin(), c->vmaps.end(), m) != c->vmaps.end();
 }
 
+// A cloud of n points and its normals onto the device: a host caller's into pts_buf and nrm_buf, normals that are not given
+// computed at normals_k into nrm_buf.  pts and nrm then point at what the kernels read
+static int cloud_stage(kss_ctx* c, bool host, const float*& pts, const float*& nrm, int64_t n, int normals_k, DevBuf& pts_buf, DevBuf& nrm_buf) {
+    if (host) {
+        const size_t bytes = (size_t)n * 3 * sizeof(float);
+        KCHK(upload(c, pts_buf, pts, bytes));
+        pts = (const float*)pts_buf.p;
+        if (nrm) {
+            KCHK(upload(c, nrm_buf, nrm, bytes));
+            nrm = (const float*)nrm_buf.p;
+        }
+    }
+    if (!nrm) KCHK(cloud_normals_dev(c, pts, n, normals_k, nrm_buf, &nrm));
+    return KSS_OK;
+}
+
+// A new handle around what make(VmapBuilt&) builds, listed with the context's live maps.  make's 1 / 2 / 3 are KSS_ERR_ARG with
+// the entry's `refused`, KSS_ERR_NOMEM and KSS_ERR_HIP with its `failed`, and nothing is held
+static int vmap_register(kss_ctx* c, const char* who, const char* refused, const char* failed, const kss_vmap_params* vp, kss_vmap** out,
+                         const std::function<int(VmapBuilt&)>& make) {
+    kss_vmap* m = new (std::nothrow) kss_vmap();
+    if (!m) return KSS_ERR_NOMEM;
+    const int rc = make(m->b);
+    if (rc != 0) {
+        delete m;
+        const std::string w = std::string(who) + ": ";
+        if (rc == 1) return set_err(c, KSS_ERR_ARG, (w + refused).c_str());
+        return rc == 2 ? set_err(c, KSS_ERR_NOMEM, (w + "hipMalloc").c_str()) : set_err(c, KSS_ERR_HIP, (w + failed).c_str());
+    }
+    m->ctx = c;
+    m->leaf = vp->leaf;
+    c->vmaps.push_back(m);
+    *out = m;
+    return KSS_OK;
+}
+
 static int vmap_create_any(kss_ctx* c, bool host, const float* tgt, int64_t nt, const float* nrm, const kss_vmap_params* vp, kss_vmap** out) {
     if (!c) return KSS_ERR_ARG;
     auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string("vmap_create: ") + what).c_str()); };
@@ -1036,29 +1073,9 @@ static int vmap_create_any(kss_ctx* c, bool host, const float* tgt, int64_t nt, 
     if (!(vp->leaf > 0.0) || !std::isfinite(vp->leaf)) return bad("leaf must be finite and > 0");
     if (!nrm && (vp->normals_k < 3 || vp->normals_k > 64)) return bad("normals_k must be in 3..64");
     HIPCHK(c, hipSetDevice(c->device));
-    if (host) {
-        const size_t tb = (size_t)nt * 3 * sizeof(float);
-        KCHK(upload(c, c->stage_tgt, tgt, tb));
-        tgt = (const float*)c->stage_tgt.p;
-        if (nrm) {
-            KCHK(upload(c, c->p2l_nrm, nrm, tb));
-            nrm = (const float*)c->p2l_nrm.p;
-        }
-    }
-    if (!nrm) KCHK(cloud_normals_dev(c, tgt, nt, vp->normals_k, c->p2l_nrm, &nrm));
-    kss_vmap* m = new (std::nothrow) kss_vmap();
-    if (!m) return KSS_ERR_NOMEM;
-    const int rc = vmap_build(c->stream, tgt, nrm, nt, 1.0f / (float)vp->leaf, m->b);
-    if (rc != 0) {
-        delete m;
-        if (rc == 1) return bad("no target with finite coordinates and normal, or a grid that is not finite or has more than 2^26 cells");
-        return rc == 2 ? set_err(c, KSS_ERR_NOMEM, "vmap_create: hipMalloc") : set_err(c, KSS_ERR_HIP, "vmap_create: the build failed");
-    }
-    m->ctx = c;
-    m->leaf = vp->leaf;
-    c->vmaps.push_back(m);
-    *out = m;
-    return KSS_OK;
+    KCHK(cloud_stage(c, host, tgt, nrm, nt, vp->normals_k, c->stage_tgt, c->p2l_nrm));
+    return vmap_register(c, "vmap_create", "no target with finite coordinates and normal, or a grid that is not finite or has more than 2^26 cells",
+                         "the build failed", vp, out, [&](VmapBuilt& b) { return vmap_build(c->stream, tgt, nrm, nt, 1.0f / (float)vp->leaf, b); });
 }
 int kss_vmap_create_dev(kss_ctx* c, const float* d_tgt, int64_t nt, const float* d_tgt_normals, const kss_vmap_params* vp, kss_vmap** out) {
     return vmap_create_any(c, false, d_tgt, nt, d_tgt_normals, vp, out);
@@ -1109,22 +1126,11 @@ int kss_vmap_create_box(kss_ctx* c, const float lo[3], const float hi[3], const 
     if (!lo || !hi || !vp || !out) return bad("null argument");
     if (!(vp->leaf > 0.0) || !std::isfinite(vp->leaf)) return bad("leaf must be finite and > 0");
     HIPCHK(c, hipSetDevice(c->device));
-    kss_vmap* m = new (std::nothrow) kss_vmap();
-    if (!m) return KSS_ERR_NOMEM;
-    const int rc = vmap_empty(c->stream, lo, hi, 1.0f / (float)vp->leaf, m->b);
-    if (rc != 0) {
-        delete m;
-        if (rc == 1) return bad("a box that is not finite, has hi < lo, or a grid that is not finite or has more than 2^26 cells");
-        return rc == 2 ? set_err(c, KSS_ERR_NOMEM, "vmap_create_box: hipMalloc") : set_err(c, KSS_ERR_HIP, "vmap_create_box: the table's fill failed");
-    }
-    m->ctx = c;
-    m->leaf = vp->leaf;
-    c->vmaps.push_back(m);
-    *out = m;
-    return KSS_OK;
+    return vmap_register(c, "vmap_create_box", "a box that is not finite, has hi < lo, or a grid that is not finite or has more than 2^26 cells",
+                         "the table's fill failed", vp, out, [&](VmapBuilt& b) { return vmap_empty(c->stream, lo, hi, 1.0f / (float)vp->leaf, b); });
 }
 
-// the cloud and its normals on the device as vgicp_enter brings a scan in, then vmap_insert
+// the cloud and its normals on the device (cloud_stage), then vmap_insert
 static int vmap_insert_any(kss_ctx* c, bool host, kss_vmap* m, const float* pts, int64_t n, const float* nrm, const float* T, int normals_k,
                            double* info) {
     if (!c) return KSS_ERR_ARG;
@@ -1137,16 +1143,7 @@ static int vmap_insert_any(kss_ctx* c, bool host, kss_vmap* m, const float* pts,
     for (int k = 0; T && k < 16; ++k)
         if (!std::isfinite(T[k])) return bad("T must be finite");
     HIPCHK(c, hipSetDevice(c->device));
-    if (host) {
-        const size_t sb = (size_t)n * 3 * sizeof(float);
-        KCHK(upload(c, c->stage_src, pts, sb));
-        pts = (const float*)c->stage_src.p;
-        if (nrm) {
-            KCHK(upload(c, c->gicp_snrm, nrm, sb));
-            nrm = (const float*)c->gicp_snrm.p;
-        }
-    }
-    if (!nrm) KCHK(cloud_normals_dev(c, pts, n, normals_k, c->gicp_snrm, &nrm));
+    KCHK(cloud_stage(c, host, pts, nrm, n, normals_k, c->stage_src, c->gicp_snrm));
     int64_t counts[KSS_VMAP_NINSERT] = {0, 0, 0, 0};
     const int rc = vmap_insert(c->stream, m->b, pts, nrm, n, T, counts);
     if (rc != 0) return rc == 2 ? set_err(c, KSS_ERR_NOMEM, "vmap_insert: hipMalloc") : set_err(c, KSS_ERR_HIP, "vmap_insert: the insert failed");
@@ -1219,17 +1216,7 @@ static int vgicp_enter(kss_ctx* c, const char* who, bool host, const float*& src
     if (n > 0x7fff0000ll) return bad("cloud too large");
     KCHK(gicp_check(c, who, gp, !snrm));
     HIPCHK(c, hipSetDevice(c->device));
-    if (host) {
-        const size_t sb = (size_t)n * 3 * sizeof(float);
-        KCHK(upload(c, c->stage_src, src, sb));
-        src = (const float*)c->stage_src.p;
-        if (snrm) {
-            KCHK(upload(c, c->gicp_snrm, snrm, sb));
-            snrm = (const float*)c->gicp_snrm.p;
-        }
-    }
-    if (!snrm) KCHK(cloud_normals_dev(c, src, n, gp->normals_k, c->gicp_snrm, &snrm));
-    return KSS_OK;
+    return cloud_stage(c, host, src, snrm, n, gp->normals_k, c->stage_src, c->gicp_snrm);
 }
 
 static int vgicp_sums_any(kss_ctx* c, bool host, const float* src, const float* snrm, int64_t n, const kss_vmap* m, double max_d2, const float* Rn,

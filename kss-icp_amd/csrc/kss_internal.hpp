@@ -371,8 +371,10 @@ struct VmapBuilt {
     int base[3] = {0, 0, 0};                  // the window's first cell per axis (kss_vmap_shift); |base|, |base + dims| <= 2^24
     float lo[3] = {0, 0, 0}, inv = 0;
 };
-// The build: eleven to thirteen launches and three synchronisations on st; its scratch is allocated and freed inside.  0: built; 1: no mapped
-// target, or a grid that is not finite or has more than VMAP_MAX_CELLS cells; 2: out of memory; 3: a HIP error (1 - 3: nothing is held).
+// The build: the box of the mapped targets, vmap_empty's table over it, vmap_insert's pipeline with no pose and records of exactly
+// the voxel count.  Eleven to thirteen launches (the two scans take two or three each), two memsets over three tables, three
+// readback copies and three synchronisations (box, voxel count, end) on st; its scratch is allocated and freed inside.  0: built; 1: no mapped target, or a grid that is not
+// finite or has more than VMAP_MAX_CELLS cells; 2: out of memory; 3: a HIP error (1 - 3: nothing is held).
 int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t nt, float inv, VmapBuilt& out);
 void vmap_free(VmapBuilt& b);
 // An empty map over the box lo .. hi (kss_vmap_create_box): the table of -1 alone.  0: made; 1: a box that is not finite, is

@@ -1,30 +1,44 @@
-// kss_vmap.hip -- the voxel map of voxelized generalized ICP (kss_vmap_create): one Gaussian per occupied voxel
-// of a target cloud, built once and kept for as many registrations as the caller likes.  The definition is restated at kss_vmap
-// in include/kssicp.h; the record of a voxel is a SERIAL f64 sum over its targets in ascending original index, so every bit of it
-// is determined by the cloud alone.
-//   bounds (2 launches)   the float box of the mapped targets (all six of position and normal finite) and their count: fminf /
-//                         fmaxf partials per workgroup, then one workgroup.  dims follow on the host: f is monotone in x, so the
-//                         largest f_a is f_a of the largest x_a.
-//   count                 every mapped target's cell: its lin, its arrival slot in the cell (an integer atomic; the order of arrival
-//                         is undone below) and the cell's occupied flag.
-//   scan, compact         the exclusive scan of the flags numbers the occupied cells in ascending lin: the dense table becomes
-//                         cell -> voxel (-1: empty), the voxels' lin and counts are packed.
-//   scan, scatter         the exclusive scan of the packed counts gives every voxel its slots; a target goes to start + arrival slot.
-//   rank fix              every target ranks itself among its voxel's targets by original index (grid_rank_fix_kernel's pattern):
-//                         the slots of a voxel now hold its targets in ascending index whatever the atomics did.
-//   stats                 one lane per voxel walks its slots: N, sum q, sum n n^T in f64, then the six + three divisions.
-//                         The sums themselves are kept too (acc, nine doubles a voxel): kss_vmap_insert continues them (below).
-// A voxel of N targets costs N^2 index compares in the rank fix (spread over its N lanes) and N dependent f64 additions on one
+// kss_vmap.hip -- the voxel map of voxelized generalized ICP: one Gaussian per occupied voxel of a
+// box, kept for as many registrations as the caller likes.  The definitions are restated at kss_vmap, kss_vmap_insert and
+// kss_vmap_shift in include/kssicp.h; the record of a voxel is a SERIAL f64 sum over its points in ascending index of each call,
+// in the order of the calls, so every bit of it is determined by the clouds alone.
+// ONE pipeline puts points into a map (vmap_insert_into); the box, origin, inv and dims never change, the voxels are renumbered
+// (a new occupied cell may lie between two old ones) and every touched voxel's sums are continued from acc:
+//   flags                 flag[c] = occupied before: a memset for a map without a voxel, else one pass over the table;
+//   cell                  every new point moved and turned, its lin, its arrival slot in the cell (an integer atomic on a zeroed
+//                         count table in the scratch; the order of arrival is undone below), the cell's flag (hit now) and the two
+//                         tallies of points left out;
+//   scan                  the exclusive scan of the flags numbers the occupied cells in ascending lin; the voxel count and the
+//                         tallies go to the host, which makes room for the new records.  Up to here the map has only been read: a
+//                         call with nothing to add, a refused one and a failed allocation leave it as it was;
+//   compact               the cell table IN PLACE, at the occupied cells alone (an empty cell stays -1, and a cell is occupied iff
+//                         the scan steps over it, so the scan is the only table read in full): the new lin, the per-voxel NEW-point
+//                         counts and every voxel's old number (-1: created now), the gather index of the old N and sums;
+//   scan, scatter         the exclusive scan of the packed counts gives every voxel its slots; a point goes to start + arrival slot;
+//   rank fix              every point ranks itself among its voxel's new points by index (grid_rank_fix_kernel's pattern): the
+//                         slots of a voxel now hold them in ascending index whatever the atomics did;
+//   continue              one lane per voxel: from the old sums (zero for a created voxel) on through its new points, serially in
+//                         f64, then the six + three divisions; a voxel without a new point is copied.
+// The new rec, acc and lin are built in the records that are not in use (VmapBuilt::spare) and change places with the old ones on
+// the host after the last synchronisation.  The three entry points:
+//   vmap_build            the float box of the mapped targets and their count (2 launches: fminf / fmaxf partials per workgroup,
+//                         then one workgroup; dims follow on the host: f is monotone in x, so the largest f_a is f_a of the largest
+//                         x_a), an empty table over it, the pipeline with no pose and records of exactly the voxel count;
+//   vmap_empty            the empty table alone (kss_vmap_create_box);
+//   vmap_insert           the pipeline on a live map, records with half as much headroom again.
+// vmap_shift (below) moves the window and shares the records' reserve and swap.
+// A voxel of N new points costs N^2 index compares in the rank fix (spread over its N lanes) and N dependent f64 additions on one
 // lane in the walk: nothing at a few points per voxel, and seconds to minutes for a million-point cloud inside ONE voxel (a leaf
 // far larger than the cloud) -- which is not a map anyone registers against.
 // No float atomic, nothing fused (fp contraction is off), no workspace of the context: the scratch is allocated here and freed
-// before the build returns, and what the map keeps (table, records, lin, sums) is its own.
+// before a call returns, and what the map keeps (table, records, lin, sums) is its own.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <limits>
 
 #include "kss_internal.hpp"
@@ -33,8 +47,21 @@ namespace kss {
 
 constexpr int VMAP_THREADS = 256;
 
-__device__ __forceinline__ bool vmap_mapped(const float* __restrict__ tgt, const float* __restrict__ nrm, int64_t i, float& x, float& y, float& z) {
-    x = tgt[3 * i]; y = tgt[3 * i + 1]; z = tgt[3 * i + 2];
+struct VmapPose {
+    VmapMove mv;
+    int on = 0;   // 0: the points and normals as they are
+};
+
+// the point as the map takes it (transform_apply_f32_kernel's expression); true: mapped, all six of position and normal finite
+__device__ __forceinline__ bool vmap_moved(const float* __restrict__ pts, const float* __restrict__ nrm, int64_t i, const VmapPose& T, float& x, float& y, float& z) {
+    x = pts[3 * i]; y = pts[3 * i + 1]; z = pts[3 * i + 2];
+    if (T.on) {
+        const float* m = T.mv.m;
+        const float a = x, b = y, c = z;
+        x = ((m[0] * a + m[1] * b) + m[2] * c) + m[3];
+        y = ((m[4] * a + m[5] * b) + m[6] * c) + m[7];
+        z = ((m[8] * a + m[9] * b) + m[10] * c) + m[11];
+    }
     return isfinite(x) && isfinite(y) && isfinite(z) && isfinite(nrm[3 * i]) && isfinite(nrm[3 * i + 1]) && isfinite(nrm[3 * i + 2]);
 }
 
@@ -74,7 +101,7 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_bounds_kernel(const float* 
     unsigned long long cnt = 0;
     for (int64_t i = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; i < nt; i += (int64_t)gridDim.x * VMAP_THREADS) {
         float p[3];
-        if (!vmap_mapped(tgt, nrm, i, p[0], p[1], p[2])) continue;
+        if (!vmap_moved(tgt, nrm, i, VmapPose(), p[0], p[1], p[2])) continue;
 #pragma unroll
         for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], p[a]); hi[a] = fmaxf(hi[a], p[a]); }
         ++cnt;
@@ -109,256 +136,8 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_bounds_final_kernel(const f
 struct VmapGrid {
     float lo[3]; float inv;
     int dims[3];
-    int base[3];   // the window's first cell per axis (0 in the build, whose box starts at the origin): VmapDev's
+    int base[3];   // the window's first cell per axis (0 until a shift): VmapDev's
 };
-
-// the cell of a mapped target.  x >= lo and x <= hi give 0 <= f <= dims - 1 (subtraction, multiplication by inv >= 0 and floorf
-// are monotone); the clamp only keeps an index inside the table should that reasoning ever be wrong.
-__device__ __forceinline__ int32_t vmap_lin(const VmapGrid& g, float x, float y, float z) {
-    const float p[3] = {x, y, z};
-    int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float f = floorf((p[a] - g.lo[a]) * g.inv);
-        c[a] = f >= 0.0f ? (f < (float)g.dims[a] ? (int)f : g.dims[a] - 1) : 0;
-    }
-    return (int32_t)(((int64_t)c[2] * g.dims[1] + c[1]) * g.dims[0] + c[0]);   // (below 2^26)
-}
-
-__global__ __launch_bounds__(VMAP_THREADS) void vmap_count_kernel(const float* __restrict__ tgt, const float* __restrict__ nrm, int64_t nt,
-                                                                   const VmapGrid g, int32_t* __restrict__ lin32, int32_t* __restrict__ slot,
-                                                                   int32_t* __restrict__ cnt, int32_t* __restrict__ flag) {
-    for (int64_t i = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; i < nt; i += (int64_t)gridDim.x * VMAP_THREADS) {
-        float x, y, z;
-        if (!vmap_mapped(tgt, nrm, i, x, y, z)) { lin32[i] = -1; continue; }
-        const int32_t lin = vmap_lin(g, x, y, z);
-        lin32[i] = lin;
-        slot[i] = atomicAdd(&cnt[lin], 1);
-        flag[lin] = 1;
-    }
-}
-
-// cnt -> the cell table in place; vox: the exclusive scan of the flags
-__global__ __launch_bounds__(VMAP_THREADS) void vmap_compact_kernel(int32_t* __restrict__ cell, const int32_t* __restrict__ vox, int64_t ncells,
-                                                                     int64_t* __restrict__ vlin, int32_t* __restrict__ vcnt) {
-    for (int64_t c = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; c < ncells; c += (int64_t)gridDim.x * VMAP_THREADS) {
-        const int32_t n = cell[c];
-        if (n > 0) {
-            const int32_t v = vox[c];
-            vlin[v] = c;
-            vcnt[v] = n;
-            cell[c] = v;
-        } else {
-            cell[c] = -1;
-        }
-    }
-}
-
-__global__ __launch_bounds__(VMAP_THREADS) void vmap_scatter_kernel(const int32_t* __restrict__ lin32, const int32_t* __restrict__ slot, int64_t nt,
-                                                                     const int32_t* __restrict__ cell, const int32_t* __restrict__ vstart,
-                                                                     int32_t* __restrict__ tmp) {
-    for (int64_t i = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; i < nt; i += (int64_t)gridDim.x * VMAP_THREADS) {
-        const int32_t lin = lin32[i];
-        if (lin >= 0) tmp[vstart[cell[lin]] + slot[i]] = (int32_t)i;
-    }
-}
-
-// slot j of tmp: its target's rank by original index among the targets of its voxel
-__global__ __launch_bounds__(VMAP_THREADS) void vmap_rank_fix_kernel(const int32_t* __restrict__ tmp, int64_t mapped, const int32_t* __restrict__ lin32,
-                                                                      const int32_t* __restrict__ cell, const int32_t* __restrict__ vstart,
-                                                                      int32_t* __restrict__ order) {
-    for (int64_t j = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; j < mapped; j += (int64_t)gridDim.x * VMAP_THREADS) {
-        const int32_t me = tmp[j];
-        const int32_t v = cell[lin32[me]];
-        const int32_t lo = vstart[v], hi = vstart[v + 1];
-        int32_t rank = 0;
-        for (int32_t k = lo; k < hi; ++k) rank += tmp[k] < me ? 1 : 0;
-        order[lo + rank] = me;
-    }
-}
-
-// one lane per voxel: the record of the definition, serially in ascending original index
-__global__ __launch_bounds__(VMAP_THREADS) void vmap_stats_kernel(const float* __restrict__ tgt, const float* __restrict__ nrm,
-                                                                   const int32_t* __restrict__ order, const int32_t* __restrict__ vstart, int64_t nvox,
-                                                                   const int64_t* __restrict__ vlin, double* __restrict__ rec,
-                                                                   double* __restrict__ acc, int64_t* __restrict__ lin) {
-    for (int64_t v = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * VMAP_THREADS) {
-        lin[v] = vlin[v];   // (packed into the scratch by the compact, before the voxel count is known; kept at the map's own size)
-        double s[3] = {0.0, 0.0, 0.0}, P[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        const int32_t lo = vstart[v], hi = vstart[v + 1];
-        for (int32_t k = lo; k < hi; ++k) {
-            const int64_t i = order[k];
-            const double n0 = (double)nrm[3 * i], n1 = (double)nrm[3 * i + 1], n2 = (double)nrm[3 * i + 2];
-            s[0] += (double)tgt[3 * i]; s[1] += (double)tgt[3 * i + 1]; s[2] += (double)tgt[3 * i + 2];
-            P[0] += n0 * n0; P[1] += n0 * n1; P[2] += n0 * n2;
-            P[3] += n1 * n1; P[4] += n1 * n2;
-            P[5] += n2 * n2;
-        }
-        const double N = (double)(hi - lo);
-        double* r = rec + v * VMAP_NSTAT;
-        r[0] = N;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) r[1 + a] = s[a] / N;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) r[4 + a] = P[a] / N;
-        double* q = acc + v * VMAP_NACC;   // the sums themselves: what kss_vmap_insert continues
-#pragma unroll
-        for (int a = 0; a < 3; ++a) q[a] = s[a];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) q[3 + a] = P[a];
-    }
-}
-
-void vmap_free(VmapBuilt& b) {
-    if (b.cell) (void)hipFree(b.cell);
-    if (b.rec) (void)hipFree(b.rec);   // (acc and lin are parts of this allocation: vmap_pack_alloc)
-    if (b.spare) (void)hipFree(b.spare);
-    b.cell = nullptr; b.rec = nullptr; b.lin = nullptr; b.acc = nullptr; b.spare = nullptr;
-    b.cap = b.spare_cap = 0;
-}
-
-// the build's scratch: one allocation, carved into 256-byte aligned parts
-struct VmapScratch {
-    char* base = nullptr;
-    size_t used = 0;
-    ~VmapScratch() { if (base) (void)hipFree(base); }
-    static size_t pad(size_t bytes) { return (bytes + 255) / 256 * 256; }
-    template <class T>
-    T* take(size_t count) {
-        T* p = (T*)(base + used);
-        used += pad(count * sizeof(T));
-        return p;
-    }
-};
-
-// rec, acc and lin for up to cap voxels as ONE allocation with rec as its base: an insert replaces all three at once, and a
-// release costs more than every kernel of an insert together (0.17 ms: DESIGN.md 2.34)
-static size_t vmap_pack_bytes(int64_t cap) {
-    return VmapScratch::pad((size_t)cap * VMAP_NSTAT * sizeof(double)) + VmapScratch::pad((size_t)cap * VMAP_NACC * sizeof(double)) + (size_t)cap * sizeof(int64_t);
-}
-static void vmap_pack_at(VmapBuilt& b, void* base, int64_t cap) {
-    b.rec = (double*)base;
-    b.acc = (double*)((char*)base + VmapScratch::pad((size_t)cap * VMAP_NSTAT * sizeof(double)));
-    b.lin = (int64_t*)((char*)b.acc + VmapScratch::pad((size_t)cap * VMAP_NACC * sizeof(double)));
-    b.cap = cap;
-}
-static bool vmap_pack_alloc(VmapBuilt& b, int64_t cap) {
-    void* base = nullptr;
-    if (hipMalloc(&base, vmap_pack_bytes(cap)) != hipSuccess) return false;
-    vmap_pack_at(b, base, cap);
-    return true;
-}
-
-int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t nt, float inv, VmapBuilt& out) {
-    const int nb = stream_blocks(nt);
-    // ---- the box ----
-    VmapScratch box;
-    if (hipMalloc((void**)&box.base, VmapScratch::pad((size_t)(nb + 1) * 6 * sizeof(float)) + VmapScratch::pad((size_t)(nb + 1) * 8)) != hipSuccess) return 2;
-    float* d_part = box.take<float>((size_t)(nb + 1) * 6);
-    unsigned long long* d_pcnt = box.take<unsigned long long>((size_t)nb + 1);
-    hipLaunchKernelGGL(vmap_bounds_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, d_tgt, d_nrm, nt, d_part, d_pcnt);
-    hipLaunchKernelGGL(vmap_bounds_final_kernel, dim3(1), dim3(VMAP_THREADS), 0, st, (const float*)d_part, (const unsigned long long*)d_pcnt, nb,
-                       d_part + (size_t)nb * 6, d_pcnt + nb);
-    float hbox[6];
-    unsigned long long hcnt = 0;
-    if (hipMemcpyAsync(hbox, d_part + (size_t)nb * 6, sizeof hbox, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
-    if (hipMemcpyAsync(&hcnt, d_pcnt + nb, sizeof hcnt, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
-    if (hipStreamSynchronize(st) != hipSuccess) return 3;
-    if (hcnt == 0) return 1;
-    VmapGrid g;
-    g.inv = inv;
-    int64_t ncells = 1;
-    for (int a = 0; a < 3; ++a) {
-        g.base[a] = 0;
-        g.lo[a] = hbox[a] == 0.0f ? 0.0f : hbox[a];   // (a zero origin is +0)
-        const float f = floorf((hbox[3 + a] - g.lo[a]) * inv);
-        if (!(f >= 0.0f && f < (float)VMAP_MAX_CELLS)) return 1;   // (a NaN included: 0 * inf)
-        g.dims[a] = 1 + (int)f;
-        ncells *= g.dims[a];
-        if (ncells > VMAP_MAX_CELLS) return 1;
-    }
-    const int64_t mapped = (int64_t)hcnt;
-    const int64_t vmax = std::min<int64_t>(mapped, ncells);   // at most this many voxels
-    // ---- the table (kept) and the scratch ----
-    VmapBuilt b;
-    VmapScratch w;
-    const size_t scan_bytes = std::max(scan_scratch_bytes((int)ncells), scan_scratch_bytes((int)vmax));
-    const size_t want = VmapScratch::pad((size_t)ncells * 4) + VmapScratch::pad(((size_t)ncells + 1) * 4) + VmapScratch::pad(scan_bytes) +
-                        4 * VmapScratch::pad((size_t)nt * 4) + VmapScratch::pad((size_t)vmax * 4) + VmapScratch::pad(((size_t)vmax + 1) * 4) +
-                        VmapScratch::pad((size_t)vmax * 8);
-    if (hipMalloc((void**)&b.cell, (size_t)ncells * sizeof(int32_t)) != hipSuccess) return 2;
-    if (hipMalloc((void**)&w.base, want) != hipSuccess) { vmap_free(b); return 2; }
-    int32_t* d_flag = w.take<int32_t>((size_t)ncells);
-    int32_t* d_vox = w.take<int32_t>((size_t)ncells + 1);
-    int32_t* d_scan = (int32_t*)w.take<char>(scan_bytes);
-    int32_t* d_lin32 = w.take<int32_t>((size_t)nt);
-    int32_t* d_slot = w.take<int32_t>((size_t)nt);
-    int32_t* d_tmp = w.take<int32_t>((size_t)nt);
-    int32_t* d_order = w.take<int32_t>((size_t)nt);
-    int32_t* d_vcnt = w.take<int32_t>((size_t)vmax);
-    int32_t* d_vstart = w.take<int32_t>((size_t)vmax + 1);
-    int64_t* d_vlin = w.take<int64_t>((size_t)vmax);
-    auto fail = [&](int rc) { vmap_free(b); return rc; };
-    if (hipMemsetAsync(b.cell, 0,(size_t)ncells * sizeof(int32_t), st) != hipSuccess) return fail(3);
-    if (hipMemsetAsync(d_flag, 0, (size_t)ncells * sizeof(int32_t), st) != hipSuccess) return fail(3);
-    hipLaunchKernelGGL(vmap_count_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, d_tgt, d_nrm, nt, g, d_lin32, d_slot, b.cell, d_flag);
-    launch_scan(st, d_flag, (int)ncells, d_vox, d_scan, false);
-    hipLaunchKernelGGL(vmap_compact_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, b.cell, (const int32_t*)d_vox, ncells, d_vlin, d_vcnt);
-    int32_t nvox32 = 0;
-    if (hipMemcpyAsync(&nvox32, d_vox + ncells, sizeof nvox32, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(3);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(3);
-    const int64_t nvox = nvox32;
-    if (nvox < 1 || nvox > vmax) return fail(3);
-    if (!vmap_pack_alloc(b, nvox)) return fail(2);
-    launch_scan(st, d_vcnt, (int)nvox, d_vstart, d_scan, false);
-    hipLaunchKernelGGL(vmap_scatter_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, (const int32_t*)d_lin32, (const int32_t*)d_slot, nt,
-                       (const int32_t*)b.cell, (const int32_t*)d_vstart, d_tmp);
-    hipLaunchKernelGGL(vmap_rank_fix_kernel, dim3(stream_blocks(mapped)), dim3(VMAP_THREADS), 0, st, (const int32_t*)d_tmp, mapped,
-                       (const int32_t*)d_lin32, (const int32_t*)b.cell, (const int32_t*)d_vstart, d_order);
-    hipLaunchKernelGGL(vmap_stats_kernel, dim3(stream_blocks(nvox)), dim3(VMAP_THREADS), 0, st, d_tgt, d_nrm, (const int32_t*)d_order,
-                       (const int32_t*)d_vstart, nvox, (const int64_t*)d_vlin, b.rec, b.acc, b.lin);
-    if (hipGetLastError() != hipSuccess) return fail(3);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(3);   // (the scratch is freed on return)
-    b.mapped = mapped; b.nvox = nvox;
-    for (int a = 0; a < 3; ++a) { b.dims[a] = g.dims[a]; b.lo[a] = g.lo[a]; }
-    b.inv = inv;
-    out = b;
-    return 0;
-}
-
-// ---- insertion into a live map (kss_vmap_insert) ---------------------------------------------------------------
-// The box, origin, inv and dims stay; the voxels are renumbered (a new occupied cell may lie between two old ones) and every
-// touched voxel's sums are continued from acc.
-//   flags                 flag[c] = occupied before;
-//   cell                  every new point moved and turned, its lin, its arrival slot (an integer atomic on a zeroed count table in
-//                         the scratch), the cell's flag (hit now) and the two tallies of points left out;
-//   scan                  the new numbering in ascending lin; the voxel count and the tallies go to the host, which allocates the
-//                         new records.  Up to here the map has only been read: a call with nothing to add, a refused one and a
-//                         failed allocation leave it as it was.
-//   compact               the cell table IN PLACE, at the occupied cells alone (an empty cell stays -1, and a cell is occupied iff
-//                         the scan steps over it, so the scan is the only table read in full): the new lin, the per-voxel NEW-point
-//                         counts and every voxel's old number (-1: created now), the gather index of the old N and sums;
-//   scan, scatter, rank   the build's kernels on the new points alone: a voxel's new points in ascending index of this call;
-//   continue              one lane per voxel: from the old sums (zero for a created voxel) on through its new points, serially in
-//                         f64, then the nine divisions; a voxel without a new point is copied.
-// The new rec, acc and lin are built beside the old ones and replace them on the host after the last synchronisation; the old
-// ones stay with the map as the next insert's destination (VmapBuilt::spare).
-struct VmapPose {
-    float m[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    int on = 0;   // 0: the points and normals as they are
-};
-
-// the point as the map takes it (transform_apply_f32_kernel's expression); true: mapped
-__device__ __forceinline__ bool vmap_moved(const float* __restrict__ pts, const float* __restrict__ nrm, int64_t i, const VmapPose& T, float& x, float& y, float& z) {
-    x = pts[3 * i]; y = pts[3 * i + 1]; z = pts[3 * i + 2];
-    if (T.on) {
-        const float a = x, b = y, c = z;
-        x = ((T.m[0] * a + T.m[1] * b) + T.m[2] * c) + T.m[3];
-        y = ((T.m[4] * a + T.m[5] * b) + T.m[6] * c) + T.m[7];
-        z = ((T.m[8] * a + T.m[9] * b) + T.m[10] * c) + T.m[11];
-    }
-    return isfinite(x) && isfinite(y) && isfinite(z) && isfinite(nrm[3 * i]) && isfinite(nrm[3 * i + 1]) && isfinite(nrm[3 * i + 2]);
-}
 
 __global__ __launch_bounds__(VMAP_THREADS) void vmap_insert_cell_kernel(const float* __restrict__ pts, const float* __restrict__ nrm, int64_t n,
                                                                          const VmapPose T, const VmapGrid g, int32_t* __restrict__ lin32,
@@ -412,6 +191,29 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_insert_compact_kernel(int32
     }
 }
 
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_scatter_kernel(const int32_t* __restrict__ lin32, const int32_t* __restrict__ slot, int64_t nt,
+                                                                     const int32_t* __restrict__ cell, const int32_t* __restrict__ vstart,
+                                                                     int32_t* __restrict__ tmp) {
+    for (int64_t i = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; i < nt; i += (int64_t)gridDim.x * VMAP_THREADS) {
+        const int32_t lin = lin32[i];
+        if (lin >= 0) tmp[vstart[cell[lin]] + slot[i]] = (int32_t)i;
+    }
+}
+
+// slot j of tmp: its target's rank by original index among the targets of its voxel
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_rank_fix_kernel(const int32_t* __restrict__ tmp, int64_t mapped, const int32_t* __restrict__ lin32,
+                                                                      const int32_t* __restrict__ cell, const int32_t* __restrict__ vstart,
+                                                                      int32_t* __restrict__ order) {
+    for (int64_t j = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; j < mapped; j += (int64_t)gridDim.x * VMAP_THREADS) {
+        const int32_t me = tmp[j];
+        const int32_t v = cell[lin32[me]];
+        const int32_t lo = vstart[v], hi = vstart[v + 1];
+        int32_t rank = 0;
+        for (int32_t k = lo; k < hi; ++k) rank += tmp[k] < me ? 1 : 0;
+        order[lo + rank] = me;
+    }
+}
+
 // one lane per voxel of the new numbering: the old sums continued through the voxel's new points in ascending index
 __global__ __launch_bounds__(VMAP_THREADS) void vmap_continue_kernel(const float* __restrict__ pts, const float* __restrict__ nrm, const VmapPose T,
                                                                       const int32_t* __restrict__ order, const int32_t* __restrict__ vstart,
@@ -444,10 +246,11 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_continue_kernel(const float
             (void)vmap_moved(pts, nrm, i, T, x, y, z);
             double n0 = (double)nrm[3 * i], n1 = (double)nrm[3 * i + 1], n2 = (double)nrm[3 * i + 2];
             if (T.on) {   // VgicpMetric's expression for a turned source normal
+                const float* m = T.mv.m;
                 const double u0 = n0, u1 = n1, u2 = n2;
-                n0 = ((double)T.m[0] * u0 + (double)T.m[1] * u1) + (double)T.m[2] * u2;
-                n1 = ((double)T.m[4] * u0 + (double)T.m[5] * u1) + (double)T.m[6] * u2;
-                n2 = ((double)T.m[8] * u0 + (double)T.m[9] * u1) + (double)T.m[10] * u2;
+                n0 = ((double)m[0] * u0 + (double)m[1] * u1) + (double)m[2] * u2;
+                n1 = ((double)m[4] * u0 + (double)m[5] * u1) + (double)m[6] * u2;
+                n2 = ((double)m[8] * u0 + (double)m[9] * u1) + (double)m[10] * u2;
             }
             s[0] += (double)x; s[1] += (double)y; s[2] += (double)z;
             P[0] += n0 * n0; P[1] += n0 * n1; P[2] += n0 * n2;
@@ -463,21 +266,91 @@ __global__ __launch_bounds__(VMAP_THREADS) void vmap_continue_kernel(const float
     }
 }
 
-int vmap_empty(hipStream_t st, const float lo[3], const float hi[3], float inv, VmapBuilt& out) {
-    VmapBuilt b;
+void vmap_free(VmapBuilt& b) {
+    if (b.cell) (void)hipFree(b.cell);
+    if (b.rec) (void)hipFree(b.rec);   // (acc and lin are parts of this allocation: vmap_pack_at)
+    if (b.spare) (void)hipFree(b.spare);
+    b.cell = nullptr; b.rec = nullptr; b.lin = nullptr; b.acc = nullptr; b.spare = nullptr;
+    b.cap = b.spare_cap = 0;
+}
+
+// a call's scratch: one allocation, carved into 256-byte aligned parts
+struct VmapScratch {
+    char* base = nullptr;
+    size_t used = 0;
+    ~VmapScratch() { if (base) (void)hipFree(base); }
+    static size_t pad(size_t bytes) { return (bytes + 255) / 256 * 256; }
+    template <class T>
+    T* take(size_t count) {
+        T* p = (T*)(base + used);
+        used += pad(count * sizeof(T));
+        return p;
+    }
+};
+
+// rec, acc and lin for up to cap voxels as ONE allocation with rec as its base: an insert replaces all three at once, and a
+// release costs more than every kernel of an insert together (0.17 ms: DESIGN.md 2.34)
+static size_t vmap_pack_bytes(int64_t cap) {
+    return VmapScratch::pad((size_t)cap * VMAP_NSTAT * sizeof(double)) + VmapScratch::pad((size_t)cap * VMAP_NACC * sizeof(double)) + (size_t)cap * sizeof(int64_t);
+}
+static void vmap_pack_at(VmapBuilt& b, void* base, int64_t cap) {
+    b.rec = (double*)base;
+    b.acc = (double*)((char*)base + VmapScratch::pad((size_t)cap * VMAP_NSTAT * sizeof(double)));
+    b.lin = (int64_t*)((char*)b.acc + VmapScratch::pad((size_t)cap * VMAP_NACC * sizeof(double)));
+    b.cap = cap;
+}
+// b.spare with room for n voxels: kept where it is large enough, else released and allocated again for `fresh` (>= n) voxels --
+// the caller's headroom rule.  false: out of memory, b has no spare and is otherwise what it was
+static bool vmap_reserve(VmapBuilt& b, int64_t n, int64_t fresh) {
+    if (b.spare_cap >= n) return true;
+    if (b.spare) (void)hipFree(b.spare);
+    b.spare = nullptr; b.spare_cap = 0;
+    if (hipMalloc(&b.spare, vmap_pack_bytes(fresh)) != hipSuccess) { b.spare = nullptr; return false; }
+    b.spare_cap = fresh;
+    return true;
+}
+// the records just built in b.spare and the ones in use change places (the latter null and 0 for a map that had none)
+static void vmap_swap(VmapBuilt& b) {
+    void* const old = b.rec;
+    const int64_t old_cap = b.cap;
+    vmap_pack_at(b, b.spare, b.spare_cap);
+    b.spare = old; b.spare_cap = old_cap;
+}
+
+static VmapGrid vmap_grid(const VmapBuilt& b) {
+    VmapGrid g;
+    g.inv = b.inv;
+    for (int a = 0; a < 3; ++a) { g.lo[a] = b.lo[a]; g.dims[a] = b.dims[a]; g.base[a] = b.base[a]; }
+    return g;
+}
+
+// The header of a map over the box lo .. hi and its table of -1, filled on st and NOT waited for.  vmap_empty's return codes;
+// 2 and 3 hold nothing
+static int vmap_table(hipStream_t st, const float lo[3], const float hi[3], float inv, VmapBuilt& b) {
     int64_t ncells = 1;
     for (int a = 0; a < 3; ++a) {
         if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || hi[a] < lo[a]) return 1;
         b.lo[a] = lo[a] == 0.0f ? 0.0f : lo[a];   // (a zero origin is +0)
-        const float f = floorf((hi[a] - b.lo[a]) * inv);   // vmap_build's lines
-        if (!(f >= 0.0f && f < (float)VMAP_MAX_CELLS)) return 1;   // (a NaN and an infinity included)
+        const float f = floorf((hi[a] - b.lo[a]) * inv);
+        if (!(f >= 0.0f && f < (float)VMAP_MAX_CELLS)) return 1;   // (a NaN and an infinity included: 0 * inf)
         b.dims[a] = 1 + (int)f;
         ncells *= b.dims[a];
         if (ncells > VMAP_MAX_CELLS) return 1;
     }
     b.inv = inv;
     if (hipMalloc((void**)&b.cell, (size_t)ncells * sizeof(int32_t)) != hipSuccess) return 2;
-    if (hipMemsetAsync(b.cell, 0xff, (size_t)ncells * sizeof(int32_t), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    if (hipMemsetAsync(b.cell, 0xff, (size_t)ncells * sizeof(int32_t), st) != hipSuccess) {
+        vmap_free(b);
+        return 3;
+    }
+    return 0;
+}
+
+int vmap_empty(hipStream_t st, const float lo[3], const float hi[3], float inv, VmapBuilt& out) {
+    VmapBuilt b;
+    const int rc = vmap_table(st, lo, hi, inv, b);
+    if (rc != 0) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) {
         vmap_free(b);
         return 3;
     }
@@ -485,29 +358,25 @@ int vmap_empty(hipStream_t st, const float lo[3], const float hi[3], float inv, 
     return 0;
 }
 
-int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d_nrm, int64_t n, const float* T, int64_t counts[VMAP_NINSERT]) {
-    VmapPose pose;
-    if (T) {
-        for (int k = 0; k < 12; ++k) pose.m[k] = T[k];
-        pose.on = 1;
-    }
-    VmapGrid g;
-    g.inv = b.inv;
-    for (int a = 0; a < 3; ++a) { g.lo[a] = b.lo[a]; g.dims[a] = b.dims[a]; g.base[a] = b.base[a]; }
+// The pipeline of the header comment: n points into b at the pose.  headroom: records that have to be allocated get half as much
+// room again (a map that is inserted into), else exactly the voxel count (the build).  vmap_insert's return codes and counts
+static int vmap_insert_into(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d_nrm, int64_t n, const VmapPose& pose, bool headroom,
+                            int64_t counts[VMAP_NINSERT]) {
+    const VmapGrid g = vmap_grid(b);
     const int64_t ncells = (int64_t)b.dims[0] * b.dims[1] * b.dims[2];
     const int64_t vmax = std::min<int64_t>(b.nvox + n, ncells);   // at most this many voxels afterwards
     const int nb = stream_blocks(n);
     // ---- the scratch; the map is only read until the new records are allocated ----
-    VmapBuilt nw;   // rec, acc and lin that take the place of b's
     VmapScratch w;
     const size_t scan_bytes = std::max(scan_scratch_bytes((int)ncells), scan_scratch_bytes((int)vmax));
     const size_t want = 2 * VmapScratch::pad((size_t)ncells * 4) + VmapScratch::pad(((size_t)ncells + 1) * 4) + VmapScratch::pad(scan_bytes) +
                         4 * VmapScratch::pad((size_t)n * 4) + 2 * VmapScratch::pad((size_t)vmax * 4) + VmapScratch::pad(((size_t)vmax + 1) * 4) +
                         VmapScratch::pad(2 * sizeof(unsigned long long));
     if (hipMalloc((void**)&w.base, want) != hipSuccess) return 2;
+    int32_t* d_vox = w.take<int32_t>((size_t)ncells + 1);          // (the scan's total and the tallies behind it: read back together)
+    unsigned long long* d_tally = w.take<unsigned long long>(2);   // (the tallies, the count table, the flags: zeroed together)
     int32_t* d_cnt = w.take<int32_t>((size_t)ncells);
     int32_t* d_flag = w.take<int32_t>((size_t)ncells);
-    int32_t* d_vox = w.take<int32_t>((size_t)ncells + 1);
     int32_t* d_scan = (int32_t*)w.take<char>(scan_bytes);
     int32_t* d_lin32 = w.take<int32_t>((size_t)n);
     int32_t* d_slot = w.take<int32_t>((size_t)n);
@@ -516,33 +385,33 @@ int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d
     int32_t* d_vcnt = w.take<int32_t>((size_t)vmax);
     int32_t* d_vold = w.take<int32_t>((size_t)vmax);
     int32_t* d_vstart = w.take<int32_t>((size_t)vmax + 1);
-    unsigned long long* d_tally = w.take<unsigned long long>(2);
-    if (hipMemsetAsync(d_cnt, 0, (size_t)ncells * sizeof(int32_t), st) != hipSuccess) return 3;
-    if (hipMemsetAsync(d_tally, 0, 2 * sizeof(unsigned long long), st) != hipSuccess) return 3;
-    hipLaunchKernelGGL(vmap_insert_flags_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, (const int32_t*)b.cell, ncells, d_flag);
+    // one memset zeroes the tallies and the counts -- and, for a map without a voxel, the flags behind them: no cell was occupied
+    // before (the table is all -1), so they need no pass over it
+    const bool fresh = b.nvox == 0;
+    if (hipMemsetAsync(d_tally, 0, (size_t)((char*)(fresh ? d_flag + ncells : d_cnt + ncells) - (char*)d_tally), st) != hipSuccess) return 3;
+    if (!fresh) hipLaunchKernelGGL(vmap_insert_flags_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, (const int32_t*)b.cell, ncells, d_flag);
     hipLaunchKernelGGL(vmap_insert_cell_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, d_pts, d_nrm, n, pose, g, d_lin32, d_slot, d_cnt, d_flag, d_tally);
     launch_scan(st, d_flag, (int)ncells, d_vox, d_scan, false);
-    int32_t nvox32 = 0;
-    unsigned long long tally[2] = {0, 0};
-    if (hipMemcpyAsync(&nvox32, d_vox + ncells, sizeof nvox32, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
-    if (hipMemcpyAsync(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
+    // ONE copy brings back the scan's total, vox[ncells], and the tallies with the padding between them (a second copy waits
+    // 20 us behind the first: DESIGN.md 2.36)
+    alignas(8) unsigned char back[256 + 2 * sizeof(unsigned long long)];
+    const size_t back_bytes = (size_t)((char*)(d_tally + 2) - (char*)(d_vox + ncells));   // (4 .. 256 bytes, then the 16 of the tallies)
+    if (hipMemcpyAsync(back, d_vox + ncells, back_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
     if (hipGetLastError() != hipSuccess) return 3;
     if (hipStreamSynchronize(st) != hipSuccess) return 3;
+    int32_t nvox32;
+    unsigned long long tally[2];
+    memcpy(&nvox32, back, sizeof nvox32);
+    memcpy(tally, back + back_bytes - sizeof tally, sizeof tally);
     const int64_t nvox = nvox32;
     const int64_t added = n - (int64_t)tally[0] - (int64_t)tally[1];
     if (added < 0 || nvox < b.nvox || nvox > vmax || (added == 0 && nvox != b.nvox)) return 3;
     counts[0] = added; counts[1] = (int64_t)tally[0]; counts[2] = (int64_t)tally[1]; counts[3] = nvox - b.nvox;
     if (added == 0) return 0;   // nothing to add: the map stays
-    // the records that are not in use (the ones the last insert replaced) take the new ones; where they are too small they are
-    // released and allocated again with half as much headroom, so a sequence of inserts releases nothing but its scratch.  This is
-    // the last allocation, in front of the first store into the map's table
-    if (b.spare_cap < nvox) {
-        if (b.spare) (void)hipFree(b.spare);
-        b.spare = nullptr; b.spare_cap = 0;
-        const int64_t cap = std::min<int64_t>(nvox + nvox / 2, ncells);
-        if (hipMalloc(&b.spare, vmap_pack_bytes(cap)) != hipSuccess) { b.spare = nullptr; return 2; }
-        b.spare_cap = cap;
-    }
+    // the records that are not in use (the ones the last insert replaced) take the new ones, so a sequence of inserts releases
+    // nothing but its scratch.  This is the last allocation, in front of the first store into the map's table
+    if (!vmap_reserve(b, nvox, headroom ? std::min<int64_t>(nvox + nvox / 2, ncells) : nvox)) return 2;
+    VmapBuilt nw;   // rec, acc and lin that take the place of b's
     vmap_pack_at(nw, b.spare, b.spare_cap);
     // ---- the table in place, the records beside the old ones (a HIP error from here on leaves a map that is not to be used) ----
     hipLaunchKernelGGL(vmap_insert_compact_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, b.cell, (const int32_t*)d_cnt,
@@ -556,9 +425,49 @@ int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d
                        (const int32_t*)d_vstart, (const int32_t*)d_vold, (const double*)b.rec, (const double*)b.acc, nvox, nw.rec, nw.acc);
     if (hipGetLastError() != hipSuccess) return 3;
     if (hipStreamSynchronize(st) != hipSuccess) return 3;   // (the scratch is freed on return)
-    b.spare = b.rec; b.spare_cap = b.cap;   // (null and 0 for a box map's first insert)
-    b.rec = nw.rec; b.acc = nw.acc; b.lin = nw.lin; b.cap = nw.cap;
+    vmap_swap(b);
     b.mapped += added; b.nvox = nvox;
+    return 0;
+}
+
+int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d_nrm, int64_t n, const float* T, int64_t counts[VMAP_NINSERT]) {
+    VmapPose pose;
+    if (T) {
+        for (int k = 0; k < 12; ++k) pose.mv.m[k] = T[k];
+        pose.on = 1;
+    }
+    return vmap_insert_into(st, b, d_pts, d_nrm, n, pose, true, counts);
+}
+
+int vmap_build(hipStream_t st, const float* d_tgt, const float* d_nrm, int64_t nt, float inv, VmapBuilt& out) {
+    const int nb = stream_blocks(nt);
+    // ---- the box ----
+    VmapScratch box;
+    if (hipMalloc((void**)&box.base, VmapScratch::pad((size_t)(nb + 1) * 6 * sizeof(float)) + VmapScratch::pad((size_t)(nb + 1) * 8)) != hipSuccess) return 2;
+    float* d_part = box.take<float>((size_t)(nb + 1) * 6);
+    unsigned long long* d_pcnt = box.take<unsigned long long>((size_t)nb + 1);
+    hipLaunchKernelGGL(vmap_bounds_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, d_tgt, d_nrm, nt, d_part, d_pcnt);
+    hipLaunchKernelGGL(vmap_bounds_final_kernel, dim3(1), dim3(VMAP_THREADS), 0, st, (const float*)d_part, (const unsigned long long*)d_pcnt, nb,
+                       d_part + (size_t)nb * 6, d_pcnt + nb);
+    float hbox[6];
+    unsigned long long hcnt = 0;
+    if (hipMemcpyAsync(hbox, d_part + (size_t)nb * 6, sizeof hbox, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
+    if (hipMemcpyAsync(&hcnt, d_pcnt + nb, sizeof hcnt, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
+    if (hipStreamSynchronize(st) != hipSuccess) return 3;
+    if (hcnt == 0) return 1;
+    // ---- the empty table over it, then the mapped targets inserted as they are.  x >= lo and x <= hi give 0 <= f <= dims - 1
+    // (subtraction, multiplication by inv >= 0 and floorf are monotone), so the insert must take exactly the box pass's targets ----
+    VmapBuilt b;
+    int rc = vmap_table(st, hbox, hbox + 3, inv, b);
+    if (rc != 0) return rc;
+    int64_t counts[VMAP_NINSERT] = {0, 0, 0, 0};
+    rc = vmap_insert_into(st, b, d_tgt, d_nrm, nt, VmapPose(), false, counts);
+    if (rc == 0 && (counts[0] != (int64_t)hcnt || counts[1] != nt - (int64_t)hcnt || counts[2] != 0)) rc = 3;
+    if (rc != 0) {
+        vmap_free(b);
+        return rc;
+    }
+    out = b;
     return 0;
 }
 
@@ -672,13 +581,7 @@ int vmap_shift(hipStream_t st, VmapBuilt& b, const int64_t k[3], int64_t counts[
     if (kept < 0 || kept > nvox || (int64_t)tally > b.mapped || (kept == nvox) != (tally == 0) || (kept == 0 && (int64_t)tally != b.mapped)) return 3;
     // the destination: the records not in use, grown by the insert's rule where they are too small.  The last allocation, in
     // front of the first store into the map's table
-    if (kept > 0 && b.spare_cap < kept) {
-        if (b.spare) (void)hipFree(b.spare);
-        b.spare = nullptr; b.spare_cap = 0;
-        const int64_t cap = std::min<int64_t>(kept + kept / 2, ncells);
-        if (hipMalloc(&b.spare, vmap_pack_bytes(cap)) != hipSuccess) { b.spare = nullptr; return 2; }
-        b.spare_cap = cap;
-    }
+    if (!vmap_reserve(b, kept, std::min<int64_t>(kept + kept / 2, ncells))) return 2;
     // ---- the table at the occupied cells alone (a HIP error from here on leaves a map that is not to be used) ----
     hipLaunchKernelGGL(vmap_shift_clear_kernel, dim3(nb), dim3(VMAP_THREADS), 0, st, (const int64_t*)b.lin, nvox, b.cell);
     VmapBuilt nw;
@@ -689,10 +592,7 @@ int vmap_shift(hipStream_t st, VmapBuilt& b, const int64_t k[3], int64_t counts[
     }
     if (hipGetLastError() != hipSuccess) return 3;
     if (hipStreamSynchronize(st) != hipSuccess) return 3;   // (the scratch is freed on return)
-    if (kept > 0) {
-        b.spare = b.rec; b.spare_cap = b.cap;
-        b.rec = nw.rec; b.acc = nw.acc; b.lin = nw.lin; b.cap = nw.cap;
-    }   // (nothing kept: the records stay where they are, with no voxel in them)
+    if (kept > 0) vmap_swap(b);   // (nothing kept: the records stay where they are, with no voxel in them)
     for (int a = 0; a < 3; ++a) b.base[a] += (int)k[a];
     b.mapped -= (int64_t)tally; b.nvox = kept;
     counts[0] = kept; counts[1] = nvox - kept; counts[2] = (int64_t)tally;

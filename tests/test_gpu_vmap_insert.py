@@ -429,3 +429,55 @@ def test_sequence_static_map_runs_out(pkg, ctx, O, scenes, seed):
         assert [e[1]["state"] for e in out[5:]] == [V.STATE_NO_CORRESPONDENCES] * 2
     finally:
         m.close()
+
+
+def _equal_maps(a, b):
+    (la, sa), (lb, sb) = a.read(), b.read()
+    assert np.array_equal(la, lb) and np.array_equal(_bits(sa), _bits(sb)) and np.array_equal(_bits(a.info()), _bits(b.info()))
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 1000])
+def test_create_is_box_plus_insert(pkg, ctx, n):
+    """kss_vmap_create is the cloud's own box, made empty, and one insert: the two doors into the one pipeline give the same bits."""
+    A, an, _, _ = _halves(pkg, n)
+    m, b = ctx.vmap(A, 0.1, normals=an), ctx.vmap_box(A.min(0), A.max(0), 0.1)
+    try:
+        info = b.insert(A, an)
+        _equal_maps(m, b)
+        assert np.array_equal(info, [n, 0, 0, len(m.read()[0])]), info
+    finally:
+        m.close(); b.close()
+
+
+def test_non_finite_through_both_doors(pkg, ctx):
+    """A NaN coordinate, an infinite coordinate and a NaN normal component, at the first, a middle and the last index: the create
+    leaves the three out of its box and of its map, the insert into the finite rows' box counts them as not mapped."""
+    A, an, _, _ = _halves(pkg, 257)
+    A[0, 1] = np.nan; A[128, 2] = np.inf; an[256, 0] = np.nan
+    ok = np.isfinite(A).all(1) & np.isfinite(an).all(1)
+    assert ok.sum() == 254
+    m, b = ctx.vmap(A, 0.1, normals=an), ctx.vmap_box(A[ok].min(0), A[ok].max(0), 0.1)
+    try:
+        info = b.insert(A, an)
+        _equal_maps(m, b)
+        assert np.array_equal(info, [254, 3, 0, len(m.read()[0])]), info
+        assert m.info()[0] == 254
+        _same_map(m, V.build(A, an, 0.1))
+    finally:
+        m.close(); b.close()
+
+
+def test_two_inserts_into_a_created_map(pkg, ctx):
+    """A created map has records of exactly its voxel count and none to spare: the first insert allocates its destination, the
+    second goes into the records the first one replaced (too small by now, so they are grown) -- the swap in both directions."""
+    A, an, B, bn = _halves(pkg, 1000)
+    m = ctx.vmap(A, 0.1, normals=an)
+    ref = R.create(A, an, 0.1)
+    try:
+        _same_map(m, ref)
+        first = _both(m, ref, B, bn)
+        second = _both(m, ref, (B * F32(0.97)).astype(F32), bn, _pose(pkg, 5.0, (0.01, 0.0, -0.01)))
+        third = _both(m, ref, A, an)                                 # no voxel is created: the spare is large enough as it is
+        assert first[3] > 0 and second[3] > 0 and third[3] == 0 and third[0] == len(A)
+    finally:
+        m.close()
