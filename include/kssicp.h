@@ -823,6 +823,45 @@ int kss_vmap_shift(kss_ctx *ctx, kss_vmap *map, const int64_t k[3], double info[
 int kss_vmap_recentre(kss_ctx *ctx, kss_vmap *map, const float centre[3], int64_t slack, int64_t k_out[3],
                       double info[KSS_VMAP_NSHIFT]);
 
+/* ---- a pyramid of maps: a live map coarsened, for registration coarse to fine ----
+ * A map's basin is about a leaf wide.  A coarser level needs no point, no normal and no second insert: the map keeps every voxel's
+ * f64 sums N, s_a, P_ab, and a coarse voxel is the ordered sum of its children's sums.
+ *
+ * kss_vmap_coarsen: a NEW map whose voxels are k x k x k blocks of map's, k in 2..8.
+ *   header      lo' = lo (the same lattice anchor);  leaf' = (double)k * leaf;  inv' = 1.0f / (float)leaf';  base'_a =
+ *               floor(base_a / k), rounded towards minus infinity (a shifted map can have a negative base);  dims'_a =
+ *               (dims_a + k - 2) / k + 1 in integer division: a function of dims and k alone that covers the fine window at every
+ *               base (one layer may stay empty) and never exceeds dims_a;
+ *   parent      a fine voxel of local cell c has the lattice cell a = base + c; its parent's lattice cell is A_a = floor(a_a / k),
+ *               its parent's local cell C = A - base', and lin' = (C_z * dims'_y + C_y) * dims'_x + C_x.  Membership is integer
+ *               arithmetic on the fine cells: no point is looked up again;
+ *   record      over the children in ascending fine lin -- ascending (a_z, a_y, a_x) --, serially in f64 from +0, nothing fused,
+ *               from the children's KEPT SUMS (not their quotients): N' = sum N (exact), s'_a += s_a, P'_ab += P_ab; then mean' =
+ *               s' / N' and S' = P' / N'.  A coarse voxel of one child has that child's sums and record bit for bit;
+ *   totals      the mapped-targets total is map's; the voxels are packed in ascending lin'.
+ * *out is an ordinary live map of ctx with its own table, records and sums: it holds no reference to map, which may be destroyed
+ * first, and every entry takes it -- the lookup with its own inv', kss_vmap_insert continuing s' and P', kss_vmap_shift, read,
+ * info, window, destroy.  inv' is rounded on its own, so a point next to a coarse cell face may be looked up in (or inserted
+ * into) a NEIGHBOUR of its fine voxel's parent; where leaf and k are powers of two the two agree exactly.  A map without a voxel
+ * coarsens to an empty map, as kss_vmap_create_box leaves one.  map is not changed in any bit.
+ * Coarsening twice is not coarsening once: coarsen(coarsen(m, 2), 2) holds the voxels of coarsen(m, 4), but its sums were added in
+ * another order and are not bit-equal.
+ * KSS_ERR_ARG: a NULL argument; k outside 2..8; not a live map of ctx.  A failed allocation holds nothing.  The call synchronises
+ * the context's stream once, where the voxel count comes back; the merge is launched behind it and not waited for (every call
+ * that reads a map runs behind it on the context's stream).
+ *
+ * kss_vmap_coarsen_into: dst, a live map of ctx other than map, refreshed: afterwards it equals a fresh kss_vmap_coarsen(map, k)
+ * in every bit of kss_vmap_read, kss_vmap_info and kss_vmap_window, whatever it held before -- inserts and shifts of its own
+ * included.  Its lo, leaf, inv and dims must equal, bit for bit, what kss_vmap_coarsen(map, k) would give (its base need not):
+ * otherwise KSS_ERR_ARG with both maps untouched.  It reuses dst's table, its records where they have room and its work area (a
+ * coarse map keeps the flags and numbering of its fill, about twice its table): the call a scan-to-map loop makes after every
+ * insert and recentre allocates nothing while the voxel count fits.  Every allocation precedes the first store into dst; a failed
+ * allocation leaves dst as it was.  KSS_ERR_ARG also: everything kss_vmap_coarsen refuses; dst not a live map of ctx; dst == map.
+ * Not offered: a coarse map that follows its source by itself, a pyramid object that refreshes itself; the C++ mirror classes and
+ * the CLI do not have these entries. */
+int kss_vmap_coarsen(kss_ctx *ctx, const kss_vmap *map, int k, kss_vmap **out);
+int kss_vmap_coarsen_into(kss_ctx *ctx, const kss_vmap *map, int k, kss_vmap *dst);
+
 /* One pass.  F and R_F as in kss_icp_gicp.  For source i: its current float position p and its float normal ns = src_normals[i]
  * (by ORIGINAL index).  Everything after the lookup is f64 on the widened floats, nothing fused, in kss_icp_gicp's order:
  *   voxel       f_a from p by the map's expression above; the source has a voxel iff 0 <= f_a < dims_a on all three axes --
@@ -858,6 +897,40 @@ int kss_icp_vgicp(kss_ctx *ctx, const float *src, int64_t ns, const float *src_n
                   const kss_gicp_params *gp, kss_icp_result *res, double last_info[KSS_VGICP_NINFO]);
 int kss_icp_vgicp_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const kss_vmap *map,
                       const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res, double last_info[KSS_VGICP_NINFO]);
+
+/* ---- voxelized generalized ICP from a start pose, and coarse to fine over several maps ----
+ * kss_icp_vgicp_from[_dev]: kss_icp_vgicp with the accumulated F started at T0 instead of the identity.  T0: a HOST row-major
+ * float 4x4 (as kss_vmap_insert's T), or NULL: kss_icp_vgicp bit for bit.  With T0, pass 0 works on T0 * src by the loop's float
+ * move, ((T00*x + T01*y) + T02*z) + T03 with no fma; the source normals are turned by R_F in f64 from the ORIGINAL float normals,
+ * as in every pass -- nothing is rounded to float on the way, which a caller who applies the pose to the scan beforehand cannot
+ * avoid --; every step is composed as before, F = T_k * F, the float Matrix4f product.  res->T is the final F, start pose
+ * included; the fitness is evaluated at F * the original source.  An identity T0 gives the result bits of NULL (finite clouds).
+ * KSS_ERR_ARG: everything kss_icp_vgicp refuses; a T0 entry that is not finite.
+ *
+ * kss_icp_vgicp_c2f[_dev]: the ladder in one call.  maps[0 .. nlevels), nlevels in 1..KSS_VGICP_MAX_LEVELS: live maps of ctx in
+ * the order they are to be used, the caller puts the coarsest first; any maps will do, they need not come from kss_vmap_coarsen.
+ * Level l is the kss_icp_vgicp_from call on maps[l] from A_{l-1}, with A_{-1} = T0 (or NULL) and A_l = results[l].T.  results[l]
+ * and last_info[l * KSS_VGICP_NINFO ..] (last_info may be NULL) are that call's BIT FOR BIT, with two departures: the fitness is
+ * evaluated for the last level only (earlier levels as with compute_fitness = 0), and trace_* describe the last level.
+ * results[l].pair_id = l.  A level that ends in KSS_STATE_NO_CORRESPONDENCES or KSS_STATE_DEGENERATE hands on the pose it
+ * reached and the ladder goes on: the last record tells the caller how it ended.  The scan is staged once and NULL normals are
+ * computed once: that is what the entry saves over a loop of calls.  The criteria of p hold for every level.
+ * KSS_ERR_ARG: everything kss_icp_vgicp_from refuses; a NULL maps or results; nlevels outside 1..8; any level that is not a live
+ * map of ctx -- all checked before anything is launched.
+ * Not offered: the ladder or start poses for a batch of scans (kss_icp_vgicp_batch), criteria per level; the C++ mirror classes
+ * and the CLI do not have these entries. */
+#define KSS_VGICP_MAX_LEVELS 8
+int kss_icp_vgicp_from(kss_ctx *ctx, const float *src, int64_t ns, const float *src_normals, const kss_vmap *map, const float T0[16],
+                       const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res, double last_info[KSS_VGICP_NINFO]);
+int kss_icp_vgicp_from_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const kss_vmap *map,
+                           const float T0[16], const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *res,
+                           double last_info[KSS_VGICP_NINFO]);
+int kss_icp_vgicp_c2f(kss_ctx *ctx, const float *src, int64_t ns, const float *src_normals, const kss_vmap *const *maps, int nlevels,
+                      const float T0[16], const kss_icp_params *p, const kss_gicp_params *gp, kss_icp_result *results,
+                      double *last_info /* nlevels * KSS_VGICP_NINFO, may be NULL */);
+int kss_icp_vgicp_c2f_dev(kss_ctx *ctx, const float *d_src, int64_t ns, const float *d_src_normals, const kss_vmap *const *maps,
+                          int nlevels, const float T0[16], const kss_icp_params *p, const kss_gicp_params *gp,
+                          kss_icp_result *results, double *last_info /* nlevels * KSS_VGICP_NINFO, may be NULL */);
 
 /* ---- voxelized generalized ICP for MANY scans against ONE map per call ----
  * src_all and src_off as in kss_icp_gicp_batch: packed float[n][3] scans and nscans + 1 HOST offsets in points (the _dev form takes

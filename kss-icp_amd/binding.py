@@ -63,7 +63,9 @@ SYMBOLS = [
     "kss_recip_filter_batch", "kss_recip_filter_batch_dev", "kss_icp_recip_pairs", "kss_icp_recip_pairs_dev",
     "kss_vmap_default_params", "kss_vmap_create", "kss_vmap_create_dev", "kss_vmap_destroy", "kss_vmap_info", "kss_vmap_read",
     "kss_vmap_create_box", "kss_vmap_insert", "kss_vmap_insert_dev", "kss_vmap_window", "kss_vmap_shift", "kss_vmap_recentre",
+    "kss_vmap_coarsen", "kss_vmap_coarsen_into",
     "kss_vgicp_sums", "kss_vgicp_sums_dev", "kss_icp_vgicp", "kss_icp_vgicp_dev",
+    "kss_icp_vgicp_from", "kss_icp_vgicp_from_dev", "kss_icp_vgicp_c2f", "kss_icp_vgicp_c2f_dev",
     "kss_icp_vgicp_batch", "kss_icp_vgicp_batch_dev",
 ]
 
@@ -255,6 +257,12 @@ def _declare(L):
     L.kss_vmap_window.argtypes = [vp, vp]
     L.kss_vmap_shift.argtypes = [vp, vp, vp, vp]
     L.kss_vmap_recentre.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.kss_vmap_coarsen.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+    L.kss_vmap_coarsen_into.argtypes = [vp, vp, C.c_int, vp]
+    for n in ("kss_icp_vgicp_from", "kss_icp_vgicp_from_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, vp, vp, C.POINTER(IcpParams), C.POINTER(GicpParams), C.POINTER(IcpResult), vp]
+    for n in ("kss_icp_vgicp_c2f", "kss_icp_vgicp_c2f_dev"):
+        getattr(L, n).argtypes = [vp, vp, i64, vp, vp, C.c_int, vp, C.POINTER(IcpParams), C.POINTER(GicpParams), vp, vp]
     for n in ("kss_vgicp_sums", "kss_vgicp_sums_dev"):
         getattr(L, n).argtypes = [vp, vp, vp, i64, vp, dbl, vp, C.POINTER(GicpParams), vp]
     for n in ("kss_icp_vgicp", "kss_icp_vgicp_dev"):
@@ -588,6 +596,19 @@ class VoxelMap:
         info = np.zeros(VMAP_NSHIFT, np.float64)
         self.ctx._chk(self.ctx.L.kss_vmap_recentre(self.ctx.h, self.h, _p(c), int(slack), _p(k), _p(info)), "kss_vmap_recentre")
         return k, info
+
+    def coarsen(self, k):
+        """kss_vmap_coarsen: a NEW VoxelMap whose voxels are k x k x k blocks of this one's (k in 2..8), summed from the kept
+        f64 sums: leaf k times as large, the same lattice anchor.  It is a map of its own and outlives this one."""
+        h = C.c_void_p()
+        self.ctx._chk(self.ctx.L.kss_vmap_coarsen(self.ctx.h, self.h, int(k), C.byref(h)), "kss_vmap_coarsen")
+        return VoxelMap(self.ctx, h)
+
+    def coarsen_into(self, dst, k):
+        """kss_vmap_coarsen_into: dst, a VoxelMap that coarsen(k) of this map made (or one of its lo, leaf, inv and dims), refilled
+        from this map as it stands now -- whatever dst held before."""
+        self.ctx._chk(self.ctx.L.kss_vmap_coarsen_into(self.ctx.h, self.h, int(k), dst.h if dst is not None else None),
+                      "kss_vmap_coarsen_into")
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -1654,6 +1675,78 @@ class Context:
         res, info, _ = self._icp_call(_VGICP_BATCH, True, _dp(d_src_all), _p(so), _dp(d_src_normals_all), vmap.h, None, None, params,
                                       _structs(_VGICP_BATCH, (gp,)), (epsilons,), so)
         return list(res), info
+
+    # ---- voxelized generalized ICP from a start pose and coarse to fine (the pyramid)
+    def _vgicp_traced(self, name, p, trace_cap, call, nlevels=None):
+        """The checked call of a kss_icp_vgicp_from / _c2f entry with the caller's trace attached to p and detached again; returns
+        the dictionary of the extras."""
+        if trace_cap <= 0:
+            self._chk(call(), name)
+            return {}
+        tr = (np.zeros((trace_cap, P2L_NSUMS), np.float64), np.zeros((trace_cap, 16), np.float32), C.c_int(0))
+        try:
+            p.trace_sums = tr[0].ctypes.data_as(C.POINTER(C.c_double))
+            p.trace_Tk = tr[1].ctypes.data_as(C.POINTER(C.c_float))
+            p.trace_cap = trace_cap
+            p.trace_n = C.pointer(tr[2])
+            self._chk(call(), name)
+        finally:
+            p.trace_sums = None; p.trace_Tk = None; p.trace_cap = 0; p.trace_n = None
+        n = tr[2].value
+        return {"trace_sums": tr[0][:n].copy(), "trace_Tk": tr[1][:n].reshape(-1, 4, 4).copy()}
+
+    @staticmethod
+    def _pose(T0):
+        return None if T0 is None else np.ascontiguousarray(T0, dtype=np.float32).reshape(16)
+
+    def icp_vgicp_from(self, src, vmap, T0, src_normals=None, gp=None, params=None, trace_cap=0):
+        """kss_icp_vgicp_from: icp_vgicp() with the accumulated pose started at T0 (a 4 x 4; None: icp_vgicp itself).  The result's
+        "T" includes T0; the normals are turned from the original ones in every pass."""
+        s = _f32(src)
+        sn = _normals(src_normals, len(s), "source")
+        p = params if params is not None else self.icp_params()
+        gp = gp if gp is not None else gicp_params()
+        res, info, Tm = IcpResult(), np.zeros(VGICP_NINFO, np.float64), self._pose(T0)
+        extra = self._vgicp_traced("kss_icp_vgicp_from", p, trace_cap, lambda: self.L.kss_icp_vgicp_from(
+            self.h, _p(s), len(s), _p(sn), vmap.h if vmap is not None else None, _p(Tm), C.byref(p), C.byref(gp), C.byref(res), _p(info)))
+        return self._result(_VGICP, res, info, extra)
+
+    def icp_vgicp_from_dev(self, d_src, ns, d_src_normals, vmap, T0, params, gp=None):
+        """kss_icp_vgicp_from_dev on device pointers (the normals pointer may be 0 / None; T0 stays a host array); returns
+        (IcpResult, info)."""
+        gp = gp if gp is not None else gicp_params()
+        res, info, Tm = IcpResult(), np.zeros(VGICP_NINFO, np.float64), self._pose(T0)
+        self._chk(self.L.kss_icp_vgicp_from_dev(self.h, _dp(d_src), int(ns), _dp(d_src_normals), vmap.h, _p(Tm), C.byref(params), C.byref(gp),
+                                                C.byref(res), _p(info)), "kss_icp_vgicp_from_dev")
+        return res, info
+
+    @staticmethod
+    def _levels(vmaps):
+        return (C.c_void_p * len(vmaps))(*[m.h if m is not None else None for m in vmaps])
+
+    def icp_vgicp_c2f(self, src, vmaps, T0=None, src_normals=None, gp=None, params=None, trace_cap=0):
+        """kss_icp_vgicp_c2f: the ladder -- icp_vgicp_from() on every VoxelMap of vmaps in turn (the coarsest first), each level
+        from the pose of the one before, the scan staged and its normals computed once.  Returns a list of icp_vgicp()'s
+        dictionaries, one per level; "fitness" is evaluated and the trace filled for the last level only."""
+        s = _f32(src)
+        sn = _normals(src_normals, len(s), "source")
+        p = params if params is not None else self.icp_params()
+        gp = gp if gp is not None else gicp_params()
+        n = len(vmaps)
+        res, info, Tm, lv = (IcpResult * max(n, 1))(), np.zeros((max(n, 1), VGICP_NINFO), np.float64), self._pose(T0), self._levels(vmaps)
+        extra = self._vgicp_traced("kss_icp_vgicp_c2f", p, trace_cap, lambda: self.L.kss_icp_vgicp_c2f(
+            self.h, _p(s), len(s), _p(sn), C.cast(lv, C.c_void_p), n, _p(Tm), C.byref(p), C.byref(gp), C.cast(res, C.c_void_p), _p(info)))
+        return [self._result(_VGICP, res[l], info[l], extra if l == n - 1 else {}) for l in range(n)]
+
+    def icp_vgicp_c2f_dev(self, d_src, ns, d_src_normals, vmaps, T0, params, gp=None):
+        """kss_icp_vgicp_c2f_dev on device pointers (the normals pointer may be 0 / None; T0 stays a host array or None); returns
+        (list of IcpResult, info [nlevels, VGICP_NINFO])."""
+        gp = gp if gp is not None else gicp_params()
+        n = len(vmaps)
+        res, info, Tm, lv = (IcpResult * max(n, 1))(), np.zeros((max(n, 1), VGICP_NINFO), np.float64), self._pose(T0), self._levels(vmaps)
+        self._chk(self.L.kss_icp_vgicp_c2f_dev(self.h, _dp(d_src), int(ns), _dp(d_src_normals), C.cast(lv, C.c_void_p), n, _p(Tm),
+                                               C.byref(params), C.byref(gp), C.cast(res, C.c_void_p), _p(info)), "kss_icp_vgicp_c2f_dev")
+        return list(res)[:n], info[:n]
 
     def transform_apply_f32(self, T, pts):
         a = _f32(pts)

@@ -1204,6 +1204,51 @@ int kss_vmap_recentre(kss_ctx* c, kss_vmap* m, const float centre[3], int64_t sl
     return rc;
 }
 
+// ---- the pyramid ----
+// what both coarsen entries refuse; who: the entry's name in the error text
+static int vmap_coarsen_check(kss_ctx* c, const char* who, const kss_vmap* m, int k) {
+    if (!vmap_live(c, m)) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": not a live map of this context").c_str());
+    if (k < 2 || k > 8) return set_err(c, KSS_ERR_ARG, (std::string(who) + ": k must be in 2..8").c_str());
+    return KSS_OK;
+}
+
+int kss_vmap_coarsen(kss_ctx* c, const kss_vmap* m, int k, kss_vmap** out) {
+    if (!c) return KSS_ERR_ARG;
+    if (out) *out = nullptr;
+    if (!out) return set_err(c, KSS_ERR_ARG, "vmap_coarsen: null argument");
+    KCHK(vmap_coarsen_check(c, "vmap_coarsen", m, k));
+    HIPCHK(c, hipSetDevice(c->device));
+    kss_vmap_params vp;
+    vp.leaf = (double)k * m->leaf;
+    vp.normals_k = 0;   // (not read)
+    return vmap_register(c, "vmap_coarsen", "", "the merge failed", &vp, out, [&](VmapBuilt& b) {
+        vmap_coarsen_header(m->b, k, vp.leaf, b);
+        int rc = vmap_coarsen_table(b);
+        if (rc == 0) rc = vmap_coarsen_into(c->stream, m->b, k, b);
+        if (rc != 0) vmap_free(b);
+        return rc;
+    });
+}
+
+int kss_vmap_coarsen_into(kss_ctx* c, const kss_vmap* m, int k, kss_vmap* dst) {
+    if (!c) return KSS_ERR_ARG;
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string("vmap_coarsen_into: ") + what).c_str()); };
+    KCHK(vmap_coarsen_check(c, "vmap_coarsen_into", m, k));
+    if (!vmap_live(c, dst)) return bad("the destination is not a live map of this context");
+    if (dst == m) return bad("the destination is the map itself");
+    VmapBuilt h;
+    const double leaf = (double)k * m->leaf;
+    vmap_coarsen_header(m->b, k, leaf, h);
+    // bit for bit what kss_vmap_coarsen would give (base is the refresh's to set)
+    if (std::memcmp(&dst->leaf, &leaf, sizeof leaf) != 0 || std::memcmp(&dst->b.inv, &h.inv, sizeof h.inv) != 0 ||
+        std::memcmp(dst->b.lo, h.lo, sizeof h.lo) != 0 || std::memcmp(dst->b.dims, h.dims, sizeof h.dims) != 0)
+        return bad("the destination's lo, leaf, inv or dims are not kss_vmap_coarsen's for this map and k");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = vmap_coarsen_into(c->stream, m->b, k, dst->b);
+    if (rc != 0) return rc == 2 ? set_err(c, KSS_ERR_NOMEM, "vmap_coarsen_into: hipMalloc") : set_err(c, KSS_ERR_HIP, "vmap_coarsen_into: the merge failed");
+    return KSS_OK;
+}
+
 // what both the record and the loop check and stage: the source on the device with its normals, given or computed
 static int vgicp_enter(kss_ctx* c, const char* who, bool host, const float*& src, const float*& snrm, int64_t n, const kss_vmap* m,
                        const kss_gicp_params* gp, const void* out) {
@@ -1233,23 +1278,62 @@ int kss_vgicp_sums(kss_ctx* c, const float* src, const float* src_normals, int64
     return vgicp_sums_any(c, true, src, src_normals, n, m, max_d2, Rn, gp, sums);
 }
 
-static int icp_vgicp_any(kss_ctx* c, bool host, const float* src, int64_t ns, const float* snrm, const kss_vmap* m, const kss_icp_params* p,
-                         const kss_gicp_params* gp, kss_icp_result* res, double* last_info) {
-    if (!c) return KSS_ERR_ARG;
-    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string("icp_vgicp: ") + what).c_str()); };
+// who: the entry's name in the error text; T0: kss_icp_vgicp_from's start pose, or null
+static int icp_vgicp_check(kss_ctx* c, const char* who, const float* T0, const kss_icp_params* p) {
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string(who) + ": " + what).c_str()); };
     if (!p) return bad("null argument");
     if (p->allreduce) return bad("the source-row split (allreduce) is not available for voxelized generalized ICP");
     if (p->fitness_idx || p->fitness_d2) return bad("there are no correspondences to return: fitness_idx and fitness_d2 must be NULL");
-    KCHK(vgicp_enter(c, "icp_vgicp", host, src, snrm, ns, m, gp, res));
-    return vgicp_run_dev(c, src, ns, snrm, m, p, gp->epsilon, res, last_info);
+    for (int k = 0; T0 && k < 16; ++k)
+        if (!std::isfinite(T0[k])) return bad("T0 must be finite");
+    return KSS_OK;
+}
+static int icp_vgicp_any(kss_ctx* c, const char* who, bool host, const float* src, int64_t ns, const float* snrm, const kss_vmap* m, const float* T0,
+                         const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* res, double* last_info) {
+    if (!c) return KSS_ERR_ARG;
+    KCHK(icp_vgicp_check(c, who, T0, p));
+    KCHK(vgicp_enter(c, who, host, src, snrm, ns, m, gp, res));
+    return vgicp_run_dev(c, src, ns, snrm, m, T0, p, gp->epsilon, res, last_info);
 }
 int kss_icp_vgicp_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const kss_vmap* m, const kss_icp_params* p,
                       const kss_gicp_params* gp, kss_icp_result* res, double last_info[KSS_VGICP_NINFO]) {
-    return icp_vgicp_any(c, false, d_src, ns, d_src_normals, m, p, gp, res, last_info);
+    return icp_vgicp_any(c, "icp_vgicp", false, d_src, ns, d_src_normals, m, nullptr, p, gp, res, last_info);
 }
 int kss_icp_vgicp(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const kss_vmap* m, const kss_icp_params* p,
                   const kss_gicp_params* gp, kss_icp_result* res, double last_info[KSS_VGICP_NINFO]) {
-    return icp_vgicp_any(c, true, src, ns, src_normals, m, p, gp, res, last_info);
+    return icp_vgicp_any(c, "icp_vgicp", true, src, ns, src_normals, m, nullptr, p, gp, res, last_info);
+}
+int kss_icp_vgicp_from_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const kss_vmap* m, const float T0[16],
+                           const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* res, double last_info[KSS_VGICP_NINFO]) {
+    return icp_vgicp_any(c, "icp_vgicp_from", false, d_src, ns, d_src_normals, m, T0, p, gp, res, last_info);
+}
+int kss_icp_vgicp_from(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const kss_vmap* m, const float T0[16],
+                       const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* res, double last_info[KSS_VGICP_NINFO]) {
+    return icp_vgicp_any(c, "icp_vgicp_from", true, src, ns, src_normals, m, T0, p, gp, res, last_info);
+}
+
+// The ladder: every check before anything is staged or launched, the scan staged and its normals computed ONCE (vgicp_enter on
+// the first level's map), then vgicp_c2f_run_dev
+static int icp_vgicp_c2f_any(kss_ctx* c, bool host, const float* src, int64_t ns, const float* snrm, const kss_vmap* const* maps, int nlevels,
+                             const float* T0, const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* results, double* last_info) {
+    if (!c) return KSS_ERR_ARG;
+    const char* who = "icp_vgicp_c2f";
+    auto bad = [&](const char* what) { return set_err(c, KSS_ERR_ARG, (std::string(who) + ": " + what).c_str()); };
+    if (!maps || !results) return bad("null argument");
+    if (nlevels < 1 || nlevels > KSS_VGICP_MAX_LEVELS) return bad("nlevels must be in 1..8");
+    for (int l = 0; l < nlevels; ++l)
+        if (!vmap_live(c, maps[l])) return bad("a level is not a live map of this context");
+    KCHK(icp_vgicp_check(c, who, T0, p));
+    KCHK(vgicp_enter(c, who, host, src, snrm, ns, maps[0], gp, results));
+    return vgicp_c2f_run_dev(c, src, ns, snrm, maps, nlevels, T0, p, gp->epsilon, results, last_info);
+}
+int kss_icp_vgicp_c2f_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_src_normals, const kss_vmap* const* maps, int nlevels,
+                          const float T0[16], const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* results, double* last_info) {
+    return icp_vgicp_c2f_any(c, false, d_src, ns, d_src_normals, maps, nlevels, T0, p, gp, results, last_info);
+}
+int kss_icp_vgicp_c2f(kss_ctx* c, const float* src, int64_t ns, const float* src_normals, const kss_vmap* const* maps, int nlevels,
+                      const float T0[16], const kss_icp_params* p, const kss_gicp_params* gp, kss_icp_result* results, double* last_info) {
+    return icp_vgicp_c2f_any(c, true, src, ns, src_normals, maps, nlevels, T0, p, gp, results, last_info);
 }
 
 // Many scans against one map.  Every check comes before anything touches the device; then the scans as

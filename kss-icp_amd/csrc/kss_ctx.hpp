@@ -338,8 +338,12 @@ int trim_threshold_dev(kss_ctx* c, const float* d_d2, int64_t n, double max_d2, 
 // kss_icp_gicp's host step on a pass of two launches and no NN pass; info: KSS_VGICP_NINFO doubles or null.
 int vgicp_record_dev(kss_ctx* c, const float* d_src, const float* d_snrm, int64_t n, const kss_vmap* map, double max_d2, const float* Rn,
                      double epsilon, double* sums);
-int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* map, const kss_icp_params* p, double epsilon,
-                  kss_icp_result* res, double* info);
+// T0: the HOST float 4 x 4 the accumulated pose starts at (kss_icp_vgicp_from), null: the identity, kss_icp_vgicp's loop as it was.
+int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* map, const float* T0, const kss_icp_params* p,
+                  double epsilon, kss_icp_result* res, double* info);
+// the ladder (kss_icp_vgicp_c2f): level l is vgicp_run_dev on maps[l] from level l - 1's pose; info: nlevels * KSS_VGICP_NINFO or null
+int vgicp_c2f_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* const* maps, int nlevels, const float* T0,
+                      const kss_icp_params* p, double epsilon, kss_icp_result* results, double* info);
 // nscans >= 1 scans against one map in lockstep (kss_icp_vgicp_batch_dev; the entry points check their arguments): d_src / d_snrm
 // packed, src_off nscans + 1 offsets in points from 0, epsilons one per scan; info_all: nscans * KSS_VGICP_NINFO doubles or null
 int vgicpb_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const float* d_snrm, int nscans, const kss_vmap* map,

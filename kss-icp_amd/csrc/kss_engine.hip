@@ -2319,8 +2319,10 @@ int vgicp_record_dev(kss_ctx* c, const float* d_src, const float* d_snrm, int64_
     return KSS_OK;
 }
 
-int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* map, const kss_icp_params* p, double epsilon,
-                  kss_icp_result* res, double* info) {
+// T0 (kss_icp_vgicp_from): fin starts at T0, pass 0 moves the caller's cloud by T0 into cur[0] on the way in and pass
+// k >= 1 reads cur[(k - 1) & 1]; null: the loop above, unchanged.
+int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* map, const float* T0, const kss_icp_params* p,
+                  double epsilon, kss_icp_result* res, double* info) {
     HIPCHK(c, hipSetDevice(c->device));
     const kss_icp_params& P = *p;
     const auto t0 = std::chrono::steady_clock::now();
@@ -2333,12 +2335,14 @@ int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snr
     float* d_cur[2] = {(float*)c->cur[0].p, (float*)c->cur[1].p};   // pass k >= 1 writes [k & 1] and reads what pass k - 1 wrote
     const double* hrec = (const double*)c->h_p2l;
     PairTrack t(P);
+    if (T0) std::memcpy(t.fin, T0, sizeof t.fin);
     double last[KSS_VGICP_NINFO] = {0.0, (double)ns, 0.0, (double)map->b.nvox};
     if (P.trace_n) *P.trace_n = 0;
     const auto t1 = std::chrono::steady_clock::now();
     for (int it = 0; P.max_iterations > 0; ++it) {
         // pass it works on T_{it-1} ... T_0 * source: the last step is applied on the way in
-        KCHK(vgicp_pass_launch(c, a, map, it == 0 ? nullptr : t.tk, it <= 1 ? d_src : d_cur[(it - 1) & 1], d_cur[it & 1], rot_of(t.fin), epsilon,
+        // (without a start pose pass 0 moves nothing, so pass 1 still reads the caller's cloud)
+        KCHK(vgicp_pass_launch(c, a, map, it == 0 ? T0 : t.tk, it <= (T0 ? 0 : 1) ? d_src : d_cur[(it - 1) & 1], d_cur[it & 1], rot_of(t.fin), epsilon,
                                unfused));
         last[0] = hrec[0]; last[2] = hrec[30];
         double unused[KSS_SIM_NINFO] = {};
@@ -2353,6 +2357,24 @@ int vgicp_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snr
     const auto t2 = std::chrono::steady_clock::now();
     c->last_setup_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
     c->last_loop_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return KSS_OK;
+}
+
+// The ladder (kss_icp_vgicp_c2f): the staged scan and its normals serve every level; a level is vgicp_run_dev from
+// the pose of the one before, whatever its state; the fitness evaluation and the caller's trace belong to the last level.
+int vgicp_c2f_run_dev(kss_ctx* c, const float* d_src, int64_t ns, const float* d_snrm, const kss_vmap* const* maps, int nlevels, const float* T0,
+                      const kss_icp_params* p, double epsilon, kss_icp_result* results, double* info) {
+    kss_icp_params quiet = *p;   // the levels in front of the last: no fitness evaluation, no trace
+    quiet.compute_fitness = 0;
+    quiet.trace_sums = nullptr; quiet.trace_Tk = nullptr; quiet.trace_cap = 0; quiet.trace_n = nullptr;
+    double setup_ms = 0.0, loop_ms = 0.0;
+    for (int l = 0; l < nlevels; ++l) {
+        KCHK(vgicp_run_dev(c, d_src, ns, d_snrm, maps[l], l == 0 ? T0 : results[l - 1].T, l == nlevels - 1 ? p : &quiet, epsilon, &results[l],
+                           info ? info + (size_t)l * KSS_VGICP_NINFO : nullptr));
+        results[l].pair_id = l;
+        setup_ms += c->last_setup_ms; loop_ms += c->last_loop_ms;
+    }
+    c->last_setup_ms = setup_ms; c->last_loop_ms = loop_ms;
     return KSS_OK;
 }
 

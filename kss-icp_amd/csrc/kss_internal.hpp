@@ -366,6 +366,8 @@ struct VmapBuilt {
     int32_t* cell = nullptr; double* rec = nullptr; int64_t* lin = nullptr; double* acc = nullptr;
     int64_t cap = 0;                          // voxels the allocation behind rec has room for (>= nvox)
     void* spare = nullptr; int64_t spare_cap = 0;   // the allocation the last insert's records left behind: the next insert's
+    void* work = nullptr; size_t work_bytes = 0;    // a coarse map's flags, numbering and scan scratch (vmap_coarsen_into): kept, so
+                                                    // that a refresh allocates nothing; null for every other map
     int64_t mapped = 0, nvox = 0;
     int dims[3] = {0, 0, 0};
     int base[3] = {0, 0, 0};                  // the window's first cell per axis (kss_vmap_shift); |base|, |base + dims| <= 2^24
@@ -392,6 +394,15 @@ int vmap_insert(hipStream_t st, VmapBuilt& b, const float* d_pts, const float* d
 int vmap_shift(hipStream_t st, VmapBuilt& b, const int64_t k[3], int64_t counts[VMAP_NSHIFT]);
 // kss_vmap_recentre's k for the centre (finite) at the slack: false where an |f_a| is above 2^24
 bool vmap_recentre_k(const VmapBuilt& b, const float centre[3], int64_t slack, int64_t k[3]);
+// The pyramid (kss_vmap_coarsen).  vmap_coarsen_header: lo, inv, dims and base of the k-fold coarsening of src at
+// the leaf k * leaf into h (nothing is allocated).  vmap_coarsen_table: the cell table of such a header, allocated and NOT filled
+// (the fill writes every cell); 2: out of memory.  vmap_coarsen_into: dst, whose lo, inv and dims are that header's, refilled from
+// src's kept sums -- its table, records and work area reused where they have room; every allocation precedes the first store
+// into dst, 2 (out of memory): dst is what it was.  ONE synchronisation of st, where the voxel count comes back; the two launches
+// behind it are not waited for (every reader of a map is ordered behind them on st or synchronises st first).
+void vmap_coarsen_header(const VmapBuilt& src, int k, double leaf, VmapBuilt& h);
+int vmap_coarsen_table(VmapBuilt& h);
+int vmap_coarsen_into(hipStream_t st, const VmapBuilt& src, int k, VmapBuilt& dst);
 struct GicpRot;
 // one rows launch of pair_rows_kernel over VgicpMetric: a.n sources (packed float triples d_in, normals a.s.sn) against the map;
 // T set: every source is first moved by *T and stored to d_out (not d_in)

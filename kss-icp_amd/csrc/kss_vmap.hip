@@ -26,12 +26,13 @@
 //                         x_a), an empty table over it, the pipeline with no pose and records of exactly the voxel count;
 //   vmap_empty            the empty table alone (kss_vmap_create_box);
 //   vmap_insert           the pipeline on a live map, records with half as much headroom again.
-// vmap_shift (below) moves the window and shares the records' reserve and swap.
+// vmap_shift (below) moves the window and shares the records' reserve and swap; vmap_coarsen (at the end) fills a map from the
+// kept sums of another.
 // A voxel of N new points costs N^2 index compares in the rank fix (spread over its N lanes) and N dependent f64 additions on one
 // lane in the walk: nothing at a few points per voxel, and seconds to minutes for a million-point cloud inside ONE voxel (a leaf
 // far larger than the cloud) -- which is not a map anyone registers against.
 // No float atomic, nothing fused (fp contraction is off), no workspace of the context: the scratch is allocated here and freed
-// before a call returns, and what the map keeps (table, records, lin, sums) is its own.
+// before a call returns, and what the map keeps (table, records, lin, sums; a coarse map also the work area of its fill) is its own.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -270,8 +271,10 @@ void vmap_free(VmapBuilt& b) {
     if (b.cell) (void)hipFree(b.cell);
     if (b.rec) (void)hipFree(b.rec);   // (acc and lin are parts of this allocation: vmap_pack_at)
     if (b.spare) (void)hipFree(b.spare);
-    b.cell = nullptr; b.rec = nullptr; b.lin = nullptr; b.acc = nullptr; b.spare = nullptr;
+    if (b.work) (void)hipFree(b.work);
+    b.cell = nullptr; b.rec = nullptr; b.lin = nullptr; b.acc = nullptr; b.spare = nullptr; b.work = nullptr;
     b.cap = b.spare_cap = 0;
+    b.work_bytes = 0;
 }
 
 // a call's scratch: one allocation, carved into 256-byte aligned parts
@@ -596,6 +599,180 @@ int vmap_shift(hipStream_t st, VmapBuilt& b, const int64_t k[3], int64_t counts[
     for (int a = 0; a < 3; ++a) b.base[a] += (int)k[a];
     b.mapped -= (int64_t)tally; b.nvox = kept;
     counts[0] = kept; counts[1] = nvox - kept; counts[2] = (int64_t)tally;
+    return 0;
+}
+
+// ---- the pyramid: a map whose voxels are k x k x k blocks of another's (kss_vmap_coarsen) ------------------------
+// lo stays, leaf' = k * leaf, base'_a = floor(base_a / k), dims'_a = (dims_a + k - 2) / k + 1.  A fine voxel of lattice cell a has
+// the parent floor(a / k); a coarse voxel is the serial f64 sum of its children's KEPT sums in ascending fine lin.  No point is
+// looked at, and the fine map is only read:
+//   flag                  one lane per fine voxel: its lin decoded, its parent's coarse lin, flag[lin'] = 1 (plain stores of the
+//                         same value) on a zeroed flag table over the coarse cells;
+//   scan                  the exclusive scan of the flags numbers the coarse voxels in ascending lin'; their count goes to the
+//                         host, which makes room in the destination's records.  Up to here the destination has only been read;
+//   compact               EVERY cell of the coarse table (the voxel's number or -1: what the destination held does not matter) and
+//                         lin';
+//   merge                 a group of G lanes per coarse voxel: the up to k^3 children in ascending (a_z, a_y, a_x), G look-ups in
+//                         the fine cell table at a time, one per lane; then every lane of the group walks the G answers in lane
+//                         order (a shuffle each) and adds the occupied children's N, s and P -- all lanes the same additions in the
+//                         same order, so the serial sum of the definition is the group's, and lane 0 stores it and the quotients.
+// The flags, the numbering and the scan's scratch live in the destination's work area, allocated once for its dims: a refresh of
+// a coarse map (kss_vmap_coarsen_into) allocates nothing while the voxel count fits the records it has.
+struct VmapCoarse {
+    int k;
+    int fdims[3], fbase[3];   // the fine map's
+    int dims[3], base[3];     // the coarse map's
+};
+
+__device__ __forceinline__ int vmap_floor_div(int a, int k) {
+    const int q = a / k;
+    return (a % k != 0 && a < 0) ? q - 1 : q;
+}
+
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_coarsen_flag_kernel(const int64_t* __restrict__ lin, int64_t nvox, const VmapCoarse g,
+                                                                          int32_t* __restrict__ flag) {
+    for (int64_t v = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * VMAP_THREADS) {
+        const int64_t l = lin[v];
+        const int64_t row = l / g.fdims[0];
+        const int cx = (int)(l - row * g.fdims[0]), cz = (int)(row / g.fdims[1]), cy = (int)(row - (int64_t)cz * g.fdims[1]);
+        const int X = vmap_floor_div(g.fbase[0] + cx, g.k) - g.base[0], Y = vmap_floor_div(g.fbase[1] + cy, g.k) - g.base[1],
+                  Z = vmap_floor_div(g.fbase[2] + cz, g.k) - g.base[2];
+        // (a parent is in the coarse window by the choice of dims': this only keeps a store inside the table)
+        if (X < 0 || X >= g.dims[0] || Y < 0 || Y >= g.dims[1] || Z < 0 || Z >= g.dims[2]) continue;
+        flag[((int64_t)Z * g.dims[1] + Y) * g.dims[0] + X] = 1;
+    }
+}
+
+// vox: the exclusive scan of the flags, ncells + 1 entries
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_coarsen_compact_kernel(const int32_t* __restrict__ vox, int64_t ncells, int64_t cap,
+                                                                             int32_t* __restrict__ cell, int64_t* __restrict__ lin) {
+    for (int64_t c = (int64_t)blockIdx.x * VMAP_THREADS + threadIdx.x; c < ncells; c += (int64_t)gridDim.x * VMAP_THREADS) {
+        const int32_t v = vox[c];
+        const bool occ = vox[c + 1] != v && v < cap;   // (v < cap: the host has made room for the scan's total)
+        cell[c] = occ ? v : -1;
+        if (occ) lin[v] = c;
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(VMAP_THREADS) void vmap_coarsen_merge_kernel(const int64_t* __restrict__ lin, int64_t nvox, const VmapCoarse g,
+                                                                           const int32_t* __restrict__ fcell, const double* __restrict__ frec,
+                                                                           const double* __restrict__ facc, double* __restrict__ rec,
+                                                                           double* __restrict__ acc) {
+    const int t = threadIdx.x & (G - 1);
+    const int nchild = g.k * g.k * g.k;
+    const int64_t groups = (int64_t)gridDim.x * (VMAP_THREADS / G);
+    for (int64_t v = (int64_t)blockIdx.x * (VMAP_THREADS / G) + threadIdx.x / G; v < nvox; v += groups) {
+        const int64_t l = lin[v];
+        const int64_t row = l / g.dims[0];
+        const int X = (int)(l - row * g.dims[0]), Z = (int)(row / g.dims[1]), Y = (int)(row - (int64_t)Z * g.dims[1]);
+        // the first child's local cell in the fine window (it may lie in front of the window: those children do not exist)
+        const int x0 = (g.base[0] + X) * g.k - g.fbase[0], y0 = (g.base[1] + Y) * g.k - g.fbase[1], z0 = (g.base[2] + Z) * g.k - g.fbase[2];
+        double N = 0.0, s[3] = {0.0, 0.0, 0.0}, P[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int j0 = 0; j0 < nchild; j0 += G) {
+            const int j = j0 + t;
+            int32_t mine = -1;
+            if (j < nchild) {
+                const int jz = j / (g.k * g.k), jy = (j - jz * g.k * g.k) / g.k, jx = j - (jz * g.k + jy) * g.k;
+                const int cx = x0 + jx, cy = y0 + jy, cz = z0 + jz;
+                if (cx >= 0 && cx < g.fdims[0] && cy >= 0 && cy < g.fdims[1] && cz >= 0 && cz < g.fdims[2])
+                    mine = fcell[((int64_t)cz * g.fdims[1] + cy) * g.fdims[0] + cx];
+            }
+#pragma unroll
+            for (int u = 0; u < G; ++u) {
+                const int64_t fv = __shfl(mine, u, G);
+                if (fv < 0) continue;
+                N += frec[fv * VMAP_NSTAT];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) s[a] += facc[fv * VMAP_NACC + a];
+#pragma unroll
+                for (int a = 0; a < 6; ++a) P[a] += facc[fv * VMAP_NACC + 3 + a];
+            }
+        }
+        if (t != 0) continue;
+        double* r = rec + v * VMAP_NSTAT;
+        double* q = acc + v * VMAP_NACC;
+        r[0] = N;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { r[1 + a] = s[a] / N; q[a] = s[a]; }
+#pragma unroll
+        for (int a = 0; a < 6; ++a) { r[4 + a] = P[a] / N; q[3 + a] = P[a]; }
+    }
+}
+
+template <int G>
+static void launch_coarsen_merge(hipStream_t st, const VmapBuilt& src, const VmapCoarse& g, const VmapBuilt& dst, int64_t nvox) {
+    const int64_t blocks = (nvox + VMAP_THREADS / G - 1) / (VMAP_THREADS / G);
+    hipLaunchKernelGGL(vmap_coarsen_merge_kernel<G>, dim3((unsigned)std::min<int64_t>(blocks, 1 << 20)), dim3(VMAP_THREADS), 0, st,
+                       (const int64_t*)dst.lin, nvox, g, (const int32_t*)src.cell, (const double*)src.rec, (const double*)src.acc, dst.rec, dst.acc);
+}
+
+void vmap_coarsen_header(const VmapBuilt& src, int k, double leaf, VmapBuilt& h) {
+    for (int a = 0; a < 3; ++a) {
+        h.lo[a] = src.lo[a];
+        const int q = src.base[a] / k;
+        h.base[a] = (src.base[a] % k != 0 && src.base[a] < 0) ? q - 1 : q;
+        h.dims[a] = (src.dims[a] + k - 2) / k + 1;
+    }
+    h.inv = 1.0f / (float)leaf;
+}
+
+int vmap_coarsen_table(VmapBuilt& h) {
+    const int64_t ncells = (int64_t)h.dims[0] * h.dims[1] * h.dims[2];
+    if (hipMalloc((void**)&h.cell, (size_t)ncells * sizeof(int32_t)) != hipSuccess) { h.cell = nullptr; return 2; }
+    return 0;
+}
+
+int vmap_coarsen_into(hipStream_t st, const VmapBuilt& src, int k, VmapBuilt& dst) {
+    VmapCoarse g;
+    g.k = k;
+    VmapBuilt h;
+    vmap_coarsen_header(src, k, 1.0, h);   // (base and dims alone are read from h)
+    for (int a = 0; a < 3; ++a) { g.fdims[a] = src.dims[a]; g.fbase[a] = src.base[a]; g.dims[a] = dst.dims[a]; g.base[a] = h.base[a]; }
+    const int64_t ncells = (int64_t)dst.dims[0] * dst.dims[1] * dst.dims[2];
+    if (src.nvox == 0) {   // an empty map, as vmap_empty leaves one
+        if (hipMemsetAsync(dst.cell, 0xff, (size_t)ncells * sizeof(int32_t), st) != hipSuccess) return 3;
+        for (int a = 0; a < 3; ++a) dst.base[a] = h.base[a];
+        dst.mapped = 0; dst.nvox = 0;
+        return 0;
+    }
+    // ---- the work area: a function of dst's dims alone, so it is allocated by the first fill and kept ----
+    const size_t scan_bytes = scan_scratch_bytes((int)ncells);
+    const size_t want = VmapScratch::pad((size_t)ncells * 4) + VmapScratch::pad(((size_t)ncells + 1) * 4) + VmapScratch::pad(scan_bytes);
+    if (dst.work_bytes < want) {
+        void* nw = nullptr;
+        if (hipMalloc(&nw, want) != hipSuccess) return 2;
+        if (dst.work) (void)hipFree(dst.work);
+        dst.work = nw; dst.work_bytes = want;
+    }
+    VmapScratch w;
+    w.base = (char*)dst.work;
+    int32_t* d_flag = w.take<int32_t>((size_t)ncells);
+    int32_t* d_vox = w.take<int32_t>((size_t)ncells + 1);
+    int32_t* d_scan = (int32_t*)w.take<char>(scan_bytes);
+    w.base = nullptr;   // (the map's, not this call's to free)
+    if (hipMemsetAsync(d_flag, 0, (size_t)ncells * sizeof(int32_t), st) != hipSuccess) return 3;
+    hipLaunchKernelGGL(vmap_coarsen_flag_kernel, dim3(stream_blocks(src.nvox)), dim3(VMAP_THREADS), 0, st, (const int64_t*)src.lin, src.nvox, g, d_flag);
+    launch_scan(st, d_flag, (int)ncells, d_vox, d_scan, false);
+    int32_t nvox32 = 0;
+    if (hipMemcpyAsync(&nvox32, d_vox + ncells, sizeof nvox32, hipMemcpyDeviceToHost, st) != hipSuccess) return 3;
+    if (hipGetLastError() != hipSuccess) return 3;
+    if (hipStreamSynchronize(st) != hipSuccess) return 3;   // the call's one synchronisation
+    const int64_t nvox = nvox32;
+    if (nvox <= 0 || nvox > src.nvox || nvox > ncells) return 3;
+    // the records: the ones in use where they have room, else the ones not in use, else new ones by the insert's rule.  The last
+    // allocation, in front of the first store into dst
+    if (dst.cap < nvox) {
+        if (!vmap_reserve(dst, nvox, std::min<int64_t>(nvox + nvox / 2, ncells))) return 2;
+        vmap_swap(dst);
+    }
+    hipLaunchKernelGGL(vmap_coarsen_compact_kernel, dim3(stream_blocks(ncells)), dim3(VMAP_THREADS), 0, st, (const int32_t*)d_vox, ncells, dst.cap,
+                       dst.cell, dst.lin);
+    if (k <= 3) launch_coarsen_merge<8>(st, src, g, dst, nvox);    // 8 or 27 children: one or four rounds of 8 look-ups
+    else launch_coarsen_merge<64>(st, src, g, dst, nvox);          // 64 .. 512 children: a wave per voxel, one to eight rounds
+    if (hipGetLastError() != hipSuccess) return 3;
+    for (int a = 0; a < 3; ++a) dst.base[a] = h.base[a];
+    dst.mapped = src.mapped; dst.nvox = nvox;
     return 0;
 }
 
