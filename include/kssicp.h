@@ -890,8 +890,46 @@ int kss_vgicp_sums_dev(kss_ctx *ctx, const float *d_src, const float *d_src_norm
  * mean, not to a nearest target point.
  * last_info (may be NULL): {kept in the last pass of the loop, ns, [30] of that pass, voxels of the map}.
  * p->nn_mode, p->nn_fma and the nn_* tuning fields are not read.  KSS_ERR_ARG: everything kss_vgicp_sums refuses, a NULL p or res,
- * a set p->allreduce, a set p->fitness_idx or p->fitness_d2 (there are no correspondences to return).  A count weight, a 7- or
- * 27-voxel neighbourhood, robust or trimmed weights, the C++ mirror classes and the CLI do not have this method. */
+ * a set p->allreduce, a set p->fitness_idx or p->fitness_d2 (there are no correspondences to return).  A count weight, robust or
+ * trimmed weights, the C++ mirror classes and the CLI do not have this method.
+ *
+ * ---- the 7- and 27-voxel neighbourhoods ----
+ * The text above is the map's neighbourhood setting 1, which every map starts at: kss_vmap_create[_dev], kss_vmap_create_box and
+ * kss_vmap_coarsen (which does not inherit its source's setting).  kss_vmap_set_neighbourhood(map, nb) with nb one of
+ * KSS_VMAP_NB_1, KSS_VMAP_NB_7, KSS_VMAP_NB_27 writes a host-side header field of the map: nothing is launched, and every later
+ * call that looks the map up reads it -- kss_vgicp_sums[_dev], kss_icp_vgicp[_dev], kss_icp_vgicp_from[_dev],
+ * kss_icp_vgicp_c2f[_dev] (per level, by that level's map) and kss_icp_vgicp_batch[_dev], the fitness evaluation included.
+ * kss_vmap_insert, kss_vmap_shift and kss_vmap_recentre do not touch it; kss_vmap_coarsen_into leaves dst's as it is.
+ * kss_vmap_neighbourhood reads it (KSS_ERR_ARG: a NULL argument; like kss_vmap_info it trusts its handle).
+ * kss_vmap_set_neighbourhood: KSS_ERR_ARG for an nb that is not 1, 7 or 27, a NULL argument, or a handle that is not a live map of
+ * ctx; a refused call leaves the setting unchanged.  At setting 1, set or never set, every entry gives the results it gave
+ * before the setting existed, in every bit.  At 7 and 27 a source is matched against its own voxel AND the occupied voxels
+ * around it, one correspondence each:
+ *   lattice cell   f_a from the current float position by the map's expression, unchanged.  The source has a lattice cell iff
+ *                  |f_a| <= 2^24 on all three axes -- compared in float, so a NaN has none; then a_a = (int)f_a.
+ *   neighbours     offsets o with each component in {-1, 0, 1}: for 7 the centre and the six with exactly one non-zero
+ *                  component, for 27 all of them; in the order: the centre first, then the others in ascending (o_z, o_y, o_x).
+ *                  The neighbour cell is a + o in integer arithmetic; it is in the window iff base_a <= a_a + o_a < base_a + dims_a
+ *                  on all axes (base: kss_vmap_window).  Each neighbour is tested on its own: a source whose own cell is outside
+ *                  the window, or empty, still takes the neighbours that are inside and occupied.
+ *   correspondence one per neighbour that is in the window and occupied, and the rest is the one-pass text above with that
+ *                  voxel's record: ns finite (tested once per source), d = mean - p and !(dd > max_d2), m from R_F and the
+ *                  original normal (once per source), C, M and the dropped rule from that voxel's S, the terms of the record.  No
+ *                  count weight and no distance weight.
+ *   record         the KSS_P2L_NSUMS slots summed over the correspondences: per lane the sources in the walk's order, per source
+ *                  the neighbours in the order above, then the unchanged block and row reduction.  [0] is the number of kept
+ *                  CORRESPONDENCES (not of distinct sources): min_correspondences and MSE = [28] / [0] use it as they are, and
+ *                  last_info[0] remains [0].  [29] and [31] stay 0.
+ *   identity       a source whose own voxel is occupied, and none of whose other neighbours is in the window and occupied, adds
+ *                  the same terms in the same order as at setting 1.  So on a map of one voxel (dims 1 x 1 x 1) with every source
+ *                  inside it, settings 7 and 27 give the record and the whole run of setting 1 in every bit.
+ * Not offered: a count or a distance weight per neighbour; a per-call override of the map's setting; the number of distinct
+ * sources kept (the record counts correspondences); the C++ mirror classes and the CLI. */
+#define KSS_VMAP_NB_1  1
+#define KSS_VMAP_NB_7  7
+#define KSS_VMAP_NB_27 27
+int kss_vmap_set_neighbourhood(kss_ctx *ctx, kss_vmap *map, int nb);
+int kss_vmap_neighbourhood(const kss_vmap *map, int *nb);
 #define KSS_VGICP_NINFO 4
 int kss_icp_vgicp(kss_ctx *ctx, const float *src, int64_t ns, const float *src_normals, const kss_vmap *map, const kss_icp_params *p,
                   const kss_gicp_params *gp, kss_icp_result *res, double last_info[KSS_VGICP_NINFO]);

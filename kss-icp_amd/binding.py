@@ -63,7 +63,7 @@ SYMBOLS = [
     "kss_recip_filter_batch", "kss_recip_filter_batch_dev", "kss_icp_recip_pairs", "kss_icp_recip_pairs_dev",
     "kss_vmap_default_params", "kss_vmap_create", "kss_vmap_create_dev", "kss_vmap_destroy", "kss_vmap_info", "kss_vmap_read",
     "kss_vmap_create_box", "kss_vmap_insert", "kss_vmap_insert_dev", "kss_vmap_window", "kss_vmap_shift", "kss_vmap_recentre",
-    "kss_vmap_coarsen", "kss_vmap_coarsen_into",
+    "kss_vmap_coarsen", "kss_vmap_coarsen_into", "kss_vmap_set_neighbourhood", "kss_vmap_neighbourhood",
     "kss_vgicp_sums", "kss_vgicp_sums_dev", "kss_icp_vgicp", "kss_icp_vgicp_dev",
     "kss_icp_vgicp_from", "kss_icp_vgicp_from_dev", "kss_icp_vgicp_c2f", "kss_icp_vgicp_c2f_dev",
     "kss_icp_vgicp_batch", "kss_icp_vgicp_batch_dev",
@@ -259,6 +259,8 @@ def _declare(L):
     L.kss_vmap_recentre.argtypes = [vp, vp, vp, i64, vp, vp]
     L.kss_vmap_coarsen.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
     L.kss_vmap_coarsen_into.argtypes = [vp, vp, C.c_int, vp]
+    L.kss_vmap_set_neighbourhood.argtypes = [vp, vp, C.c_int]
+    L.kss_vmap_neighbourhood.argtypes = [vp, C.POINTER(C.c_int)]
     for n in ("kss_icp_vgicp_from", "kss_icp_vgicp_from_dev"):
         getattr(L, n).argtypes = [vp, vp, i64, vp, vp, vp, C.POINTER(IcpParams), C.POINTER(GicpParams), C.POINTER(IcpResult), vp]
     for n in ("kss_icp_vgicp_c2f", "kss_icp_vgicp_c2f_dev"):
@@ -609,6 +611,20 @@ class VoxelMap:
         from this map as it stands now -- whatever dst held before."""
         self.ctx._chk(self.ctx.L.kss_vmap_coarsen_into(self.ctx.h, self.h, int(k), dst.h if dst is not None else None),
                       "kss_vmap_coarsen_into")
+
+    def set_neighbourhood(self, nb):
+        """kss_vmap_set_neighbourhood: 1 (the source's own voxel, what every map starts at), 7 or 27 -- the voxels every later
+        vgicp_sums / icp_vgicp* call on this map matches a source against, one correspondence per occupied one."""
+        self.ctx._chk(self.ctx.L.kss_vmap_set_neighbourhood(self.ctx.h, self.h, int(nb)), "kss_vmap_set_neighbourhood")
+
+    @property
+    def neighbourhood(self):
+        """kss_vmap_neighbourhood: the map's setting, 1, 7 or 27."""
+        nb = C.c_int(0)
+        rc = self.ctx.L.kss_vmap_neighbourhood(self.h, C.byref(nb))
+        if rc != 0:
+            raise KssError(rc, "kss_vmap_neighbourhood")
+        return nb.value
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):

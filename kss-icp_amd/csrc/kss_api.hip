@@ -1249,6 +1249,22 @@ int kss_vmap_coarsen_into(kss_ctx* c, const kss_vmap* m, int k, kss_vmap* dst) {
     return KSS_OK;
 }
 
+// ---- the neighbourhood of every lookup ----
+// a header field on the host: nothing is launched, and the next call that looks the map up reads it (kss_vmap::nb)
+int kss_vmap_set_neighbourhood(kss_ctx* c, kss_vmap* m, int nb) {
+    if (!c) return KSS_ERR_ARG;
+    if (!vmap_live(c, m)) return set_err(c, KSS_ERR_ARG, "vmap_set_neighbourhood: not a live map of this context");
+    if (nb != KSS_VMAP_NB_1 && nb != KSS_VMAP_NB_7 && nb != KSS_VMAP_NB_27) return set_err(c, KSS_ERR_ARG, "vmap_set_neighbourhood: nb must be 1, 7 or 27");
+    m->nb = nb;
+    return KSS_OK;
+}
+
+int kss_vmap_neighbourhood(const kss_vmap* m, int* nb) {
+    if (!m || !nb) return KSS_ERR_ARG;
+    *nb = m->nb;
+    return KSS_OK;
+}
+
 // what both the record and the loop check and stage: the source on the device with its normals, given or computed
 static int vgicp_enter(kss_ctx* c, const char* who, bool host, const float*& src, const float*& snrm, int64_t n, const kss_vmap* m,
                        const kss_gicp_params* gp, const void* out) {

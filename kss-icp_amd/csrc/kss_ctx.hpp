@@ -38,6 +38,7 @@ struct kss_vmap {
     kss_ctx* ctx = nullptr;
     VmapBuilt b;
     double leaf = 0.0;
+    int nb = 1;   // the neighbourhood every lookup of this map uses (kss_vmap_set_neighbourhood): 1, 7 or 27; a header field, host side
     VmapDev dev() const { return VmapDev{b.cell, b.rec, {b.lo[0], b.lo[1], b.lo[2]}, b.inv, {b.dims[0], b.dims[1], b.dims[2]},
                                         {b.base[0], b.base[1], b.base[2]}}; }
 };

@@ -2300,9 +2300,9 @@ static int vgicp_pass_launch(kss_ctx* c, const PairArgs& a, const kss_vmap* map,
     if (T) std::memcpy(mv.m, T, sizeof mv.m);
     if (T && unfused) {
         launch_transform_apply_f32(c->stream, T, d_in, a.n, d_out);
-        launch_vgicp_rows(c->stream, a, map->dev(), nullptr, d_out, nullptr, Rn, 1.0 - epsilon);
+        launch_vgicp_rows(c->stream, a, map->dev(), nullptr, d_out, nullptr, Rn, 1.0 - epsilon, map->nb);
     } else {
-        launch_vgicp_rows(c->stream, a, map->dev(), T ? &mv : nullptr, d_in, d_out, Rn, 1.0 - epsilon);
+        launch_vgicp_rows(c->stream, a, map->dev(), T ? &mv : nullptr, d_in, d_out, Rn, 1.0 - epsilon, map->nb);
     }
     launch_p2l_final(c->stream, a.rows, stream_blocks(a.n), (double*)c->h_p2l_dev);
     HIPCHK(c, hipGetLastError());
@@ -2416,6 +2416,7 @@ int vgicpb_run_dev(kss_ctx* c, const float* d_src, const int64_t* src_off, const
     const double* hrec = (const double*)c->h_p2l;   // np records of P2L_NSUMS doubles
     VgicpbArgs a = {map->dev(), nullptr, nullptr, d_snrm, P.max_corr_dist * P.max_corr_dist, (const PairbDesc*)c->pb_desc.p,
                     (const int32_t*)c->pb_rowpair.p, (const VgicpbPass*)c->pb_gicp.p, (double*)c->p2l_rows.p};
+    a.nb = map->nb;
     std::vector<PairTrack> tr((size_t)np, PairTrack(P));
     std::vector<int> active((size_t)np, P.max_iterations > 0 ? 1 : 0);
     std::vector<double> last((size_t)np * KSS_VGICP_NINFO, 0.0);

@@ -405,9 +405,10 @@ int vmap_coarsen_table(VmapBuilt& h);
 int vmap_coarsen_into(hipStream_t st, const VmapBuilt& src, int k, VmapBuilt& dst);
 struct GicpRot;
 // one rows launch of pair_rows_kernel over VgicpMetric: a.n sources (packed float triples d_in, normals a.s.sn) against the map;
-// T set: every source is first moved by *T and stored to d_out (not d_in)
+// T set: every source is first moved by *T and stored to d_out (not d_in); nb: the map's neighbourhood setting, 1 (the kernels as
+// they were), 7 or 27 (VgicpMetric<MOVE, true>)
 void launch_vgicp_rows(hipStream_t st, const PairArgs& a, const VmapDev& v, const VmapMove* T, const float* d_in, float* d_out, const GicpRot& Rn,
-                       double e);
+                       double e, int nb);
 // exclusive scan of d_counts[0 .. n) into d_start[0 .. n] (kss_grid.hip); d_scratch holds scan_scratch_bytes(n)
 void launch_scan(hipStream_t st, int32_t* d_counts, int ncells, int32_t* d_start, int32_t* d_scratch, bool clear);
 
@@ -521,9 +522,10 @@ struct VgicpbArgs {
     double max_d2;
     const PairbDesc* desc; const int32_t* row_pair; const VgicpbPass* pass;
     double* rows;
+    int nb = 1;   // the map's neighbourhood setting (kss_vmap_set_neighbourhood): 1, 7 or 27
 };
 // one launch over total_rows = the sum of the scans' stream_blocks(ns) workgroups: every active scan's rows; move: its sources
-// are first moved by its own pass[scan].t and stored to a.out
+// are first moved by its own pass[scan].t and stored to a.out; a.nb of 7 or 27: the neighbourhood kernels
 void launch_vgicpb_rows(hipStream_t st, int total_rows, bool move, const VgicpbArgs& a);
 // one workgroup per scan: every active scan's record into d_out[scan * KSS_P2L_NSUMS] (device or host-mapped), slot 31 as 0
 void launch_vgicpb_final(hipStream_t st, int nscans, const VgicpbArgs& a, double* d_out);

@@ -15,6 +15,8 @@
 // no atomic across workgroups: the hand-over is the launch boundary, and nothing here has to be zero at rest.
 #pragma clang fp contract(off)
 
+#include <cassert>
+
 #include "kss_pair_device.hpp"
 
 namespace kss {
@@ -62,8 +64,20 @@ template <bool MOVE>
 void launch_vgicp_rows(hipStream_t st, const PairArgs& a, const VgicpMetric<MOVE>& m) {
     hipLaunchKernelGGL((pair_rows_kernel<VgicpMetric<MOVE>, SRC_F3>), dim3(stream_blocks(a.n)), dim3(P2L_THREADS), 0, st, a, m);
 }
+// the map's 7- or 27-voxel neighbourhood: the same walk over VgicpMetric<MOVE, true>, which carries the setting
+template <bool MOVE>
+void launch_vgicp_nb_rows(hipStream_t st, const PairArgs& a, VgicpMetric<MOVE, true> m, int nb) {
+    m.nb = nb;
+    hipLaunchKernelGGL((pair_rows_kernel<VgicpMetric<MOVE, true>, SRC_F3>), dim3(stream_blocks(a.n)), dim3(P2L_THREADS), 0, st, a, m);
+}
 void launch_vgicp_rows(hipStream_t st, const PairArgs& a, const VmapDev& v, const VmapMove* T, const float* d_in, float* d_out, const GicpRot& Rn,
-                       double e) {
+                       double e, int nb) {
+    assert(nb == 1 || nb == 7 || nb == 27);   // (kss_vmap_set_neighbourhood admits nothing else)
+    if (nb == 7 || nb == 27) {
+        if (T) launch_vgicp_nb_rows<true>(st, a, VgicpMetric<true, true>(v, *T, d_in, d_out, Rn, e), nb);
+        else launch_vgicp_nb_rows<false>(st, a, VgicpMetric<false, true>(v, VmapMove(), d_in, nullptr, Rn, e), nb);
+        return;
+    }
     if (T) launch_vgicp_rows<true>(st, a, VgicpMetric<true>(v, *T, d_in, d_out, Rn, e));
     else launch_vgicp_rows<false>(st, a, VgicpMetric<false>(v, VmapMove(), d_in, nullptr, Rn, e));
 }

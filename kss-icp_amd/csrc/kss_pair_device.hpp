@@ -183,14 +183,80 @@ __device__ __forceinline__ void gicp_source(double (&acc)[P2L_NSUMS], const floa
 }
 
 // ---- voxelized generalized ICP ---------------------------------------------------------------------------
+// The 7- and 27-voxel neighbourhoods (kss_vmap_set_neighbourhood): what a source at the moved position s with the
+// lattice coordinates f adds when the map's setting is nb = 7 or 27 -- one correspondence per neighbour cell that is in the window
+// and occupied, the centre first, then the others in ascending (o_z, o_y, o_x).  Two phases, so that no table read waits for an
+// accumulation:
+//   1  every table read of the neighbourhood, unrolled: up to 27 independent loads (a row of three x-neighbours is twelve
+//      contiguous bytes), each kept in this lane's own column of an LDS array, and a bit per occupied neighbour -- bit 0 the
+//      centre, bits 1 .. 26 the others in the definition's order;
+//   2  a loop over the set bits, lowest first: the voxel index back from LDS, the record's ten doubles, and vgicp_correspondence,
+//      the body vgicp_source runs on its one voxel, so a source whose only occupied neighbour is its own voxel adds setting 1's
+//      terms in setting 1's order.  The loop is not unrolled: one body.
+// A lane reads only what it wrote itself, in program order: no barrier.  The source's normal is tested, and m formed, once.
+constexpr int VGICP_NB_MAX = 27;
+// What ONE correspondence adds: the source at the widened position p, its turned normal m, against the voxel record rec =
+// {N, mean x y z, S00 S01 S02 S11 S12 S22}.  The one body of both lookups -- vgicp_source's own voxel and every neighbour of
+// vgicp_neighbours -- so the identity of the header (a source whose only occupied neighbour is its own voxel adds setting 1's terms)
+// holds by construction.
+__device__ __forceinline__ void vgicp_correspondence(double (&acc)[P2L_NSUMS], const double* __restrict__ rec, double px, double py, double pz,
+                                                     const double (&m)[3], double max_d2, double e) {
+    const double d0 = rec[1] - px, d1 = rec[2] - py, dz = rec[3] - pz;
+    const double dd = (d0 * d0 + d1 * d1) + dz * dz;
+    if (dd > max_d2) return;
+    const double Q[6] = {rec[4], rec[5], rec[6], rec[7], rec[8], rec[9]};
+    double M[6];
+    if (!gicp_metric_of_g(Q, m, e, M)) return;
+    gicp_accumulate(acc, M, px, py, pz, d0, d1, dz, dd);
+}
+__device__ __forceinline__ void vgicp_neighbours(double (&acc)[P2L_NSUMS], const float* __restrict__ sn, const VmapDev& v, int64_t i, float sx, float sy,
+                                                 float sz, float fx, float fy, float fz, double max_d2, const GicpRot& Rn, double e, int nb) {
+    __shared__ int32_t nbv[VGICP_NB_MAX][P2L_THREADS];
+    // a lattice cell: |f_a| <= 2^24 on all axes, compared in float (a NaN has none); then the conversion to int is exact
+    constexpr float LIM = 16777216.0f;
+    if (!(fabsf(fx) <= LIM && fabsf(fy) <= LIM && fabsf(fz) <= LIM)) return;
+    const float ux = sn[3 * i], uy = sn[3 * i + 1], uz = sn[3 * i + 2];
+    // local cell of the source: |a|, |base| <= 2^24, so the difference and c + o are plain ints; a + o is in the window iff
+    // 0 <= c + o < dims
+    const int cx = (int)fx - v.base[0], cy = (int)fy - v.base[1], cz = (int)fz - v.base[2];
+    const int64_t centre = ((int64_t)cz * v.dims[1] + cy) * v.dims[0] + cx;   // (read only behind its neighbour's window test)
+    const int64_t sy_ = v.dims[0], sz_ = (int64_t)v.dims[1] * v.dims[0];
+    const bool full = nb == 27;
+    unsigned mask = 0;
+#pragma unroll
+    for (int k = 0; k < VGICP_NB_MAX; ++k) {
+        const int ox = k % 3 - 1, oy = (k / 3) % 3 - 1, oz = k / 9 - 1;                  // ascending (o_z, o_y, o_x)
+        const int bit = k == 13 ? 0 : (k < 13 ? k + 1 : k);                             // the centre first
+        const bool axis = (ox != 0) + (oy != 0) + (oz != 0) <= 1;                        // one of the 7
+        const int x = cx + ox, y = cy + oy, z = cz + oz;
+        int32_t vox = -1;
+        if ((axis || full) && x >= 0 && x < v.dims[0] && y >= 0 && y < v.dims[1] && z >= 0 && z < v.dims[2])
+            vox = v.cell[centre + (oz * sz_ + oy * sy_ + ox)];
+        if (axis || full) nbv[bit][threadIdx.x] = vox;   // (a slot is read only where its bit is set: at 7 the other 20 are not written)
+        mask |= (vox >= 0 ? 1u : 0u) << bit;
+    }
+    if (mask == 0 || !(isfinite(ux) && isfinite(uy) && isfinite(uz))) return;
+    const double px = (double)sx, py = (double)sy, pz = (double)sz;
+    const double us[3] = {(double)ux, (double)uy, (double)uz};
+    double m[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) m[k] = ((double)Rn.r[3 * k] * us[0] + (double)Rn.r[3 * k + 1] * us[1]) + (double)Rn.r[3 * k + 2] * us[2];
+#pragma unroll 1
+    while (mask) {
+        const int bit = __ffs(mask) - 1;
+        mask &= mask - 1;
+        vgicp_correspondence(acc, v.rec + (int64_t)nbv[bit][threadIdx.x] * VMAP_NSTAT, px, py, pz, m, max_d2, e);
+    }
+}
+
 // Source i against the voxel map v: the definition at kss_icp_vgicp in include/kssicp.h.  No idx is read: the voxel is looked up
 // from the source's own position -- f_a = floorf((p_a - lo_a) * inv), the build's expression, compared in float so that a NaN
 // has no voxel -- and the voxel's mean and average n n^T stand where gicp_source has q and nq nq^T.  MOVE: the position read
 // from `in` is first moved by the float 3 x 4 T as transform_apply_f32_kernel moves it and stored to `out` (another array), so a
 // pass needs no launch for the move.
-template <bool MOVE>
+template <bool MOVE, bool NEIGH = false>
 __device__ __forceinline__ void vgicp_source(double (&acc)[P2L_NSUMS], const float* __restrict__ in, float* __restrict__ out, const float* __restrict__ sn,
-                                             const VmapDev& v, const VmapMove& T, int64_t i, double max_d2, const GicpRot& Rn, double e) {
+                                             const VmapDev& v, const VmapMove& T, int64_t i, double max_d2, const GicpRot& Rn, double e, int nb = 1) {
     float sx = in[3 * i], sy = in[3 * i + 1], sz = in[3 * i + 2];
     if constexpr (MOVE) {
         const float x = sx, y = sy, z = sz;
@@ -200,6 +266,10 @@ __device__ __forceinline__ void vgicp_source(double (&acc)[P2L_NSUMS], const flo
         out[3 * i] = sx; out[3 * i + 1] = sy; out[3 * i + 2] = sz;
     }
     const float fx = floorf((sx - v.lo[0]) * v.inv), fy = floorf((sy - v.lo[1]) * v.inv), fz = floorf((sz - v.lo[2]) * v.inv);
+    if constexpr (NEIGH) {   // (the move and its store are done: once per source, before any lookup)
+        vgicp_neighbours(acc, sn, v, i, sx, sy, sz, fx, fy, fz, max_d2, Rn, e, nb);
+        return;
+    }
     // the window (kss_vmap_shift): base <= f < base + dims, both bounds exact in float; base = 0 gives 0 <= f < dims
     if (!(fx >= (float)v.base[0] && fx < (float)(v.base[0] + v.dims[0]) && fy >= (float)v.base[1] && fy < (float)(v.base[1] + v.dims[1]) &&
           fz >= (float)v.base[2] && fz < (float)(v.base[2] + v.dims[2]))) return;
@@ -209,18 +279,11 @@ __device__ __forceinline__ void vgicp_source(double (&acc)[P2L_NSUMS], const flo
     if (vox < 0) return;
     const float ux = sn[3 * i], uy = sn[3 * i + 1], uz = sn[3 * i + 2];
     if (!(isfinite(ux) && isfinite(uy) && isfinite(uz))) return;
-    const double* __restrict__ rec = v.rec + (int64_t)vox * VMAP_NSTAT;   // {N, mean x y z, S00 S01 S02 S11 S12 S22}
-    const double px = (double)sx, py = (double)sy, pz = (double)sz;
-    const double d0 = rec[1] - px, d1 = rec[2] - py, dz = rec[3] - pz;
-    const double dd = (d0 * d0 + d1 * d1) + dz * dz;
-    if (dd > max_d2) return;
     const double us[3] = {(double)ux, (double)uy, (double)uz};
-    const double Q[6] = {rec[4], rec[5], rec[6], rec[7], rec[8], rec[9]};
-    double m[3], M[6];
+    double m[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) m[k] = ((double)Rn.r[3 * k] * us[0] + (double)Rn.r[3 * k + 1] * us[1]) + (double)Rn.r[3 * k + 2] * us[2];
-    if (!gicp_metric_of_g(Q, m, e, M)) return;
-    gicp_accumulate(acc, M, px, py, pz, d0, d1, dz, dd);
+    vgicp_correspondence(acc, v.rec + (int64_t)vox * VMAP_NSTAT, (double)sx, (double)sy, (double)sz, m, max_d2, e);
 }
 
 // ---- symmetric ICP --------------------------------------------------------------------------------------
@@ -621,8 +684,12 @@ struct GicpMetric {   // generalized: the rotation applied to the source normals
         gicp_source<SRC>(acc, s.src3, s.src4, s.perm, s.idx, s.d2, s.sn, tgt, nrm, i, nt, s.max_d2, Rn, e);
     }
 };
-template <bool MOVE>
-struct VgicpMetric {   // voxelized generalized: the map, GicpMetric's rotation and e, and (MOVE) the step the sources take on the way in
+template <bool NEIGH>
+struct VgicpNb { static constexpr int nb = 1; };          // the map's neighbourhood setting: a member only where it is read
+template <>
+struct VgicpNb<true> { int nb = 7; };
+template <bool MOVE, bool NEIGH = false>
+struct VgicpMetric : VgicpNb<NEIGH> {   // voxelized generalized: the map, GicpMetric's rotation and e, and (MOVE) the step the sources take on the way in
     static constexpr int NC = P2L_NSUMS;
     static constexpr bool KEYS = false, F3 = true;
     VmapDev v;
@@ -638,12 +705,13 @@ struct VgicpMetric {   // voxelized generalized: the map, GicpMetric's rotation 
         for (int k = 0; k < 12; ++k) T.m[k] = pp.t[k];
 #pragma unroll
         for (int k = 0; k < 9; ++k) Rn.r[k] = pp.r[k];
+        if constexpr (NEIGH) this->nb = a.nb;
     }
     __device__ void begin() {}
     template <int SRC>
     __device__ __forceinline__ void source(double (&acc)[NC], const PairSrc& s, const float*, const float*, int64_t i, int64_t, float*) const {
         static_assert(SRC == SRC_F3, "the voxel lookup reads packed float triples");
-        vgicp_source<MOVE>(acc, in, out, s.sn, v, T, i, s.max_d2, Rn, e);
+        vgicp_source<MOVE, NEIGH>(acc, in, out, s.sn, v, T, i, s.max_d2, Rn, e, this->nb);
     }
 };
 template <int MODE>

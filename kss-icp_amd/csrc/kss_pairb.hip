@@ -28,6 +28,8 @@
 // read by global original index.
 #pragma clang fp contract(off)
 
+#include <cassert>
+
 #include "kss_pair_device.hpp"
 
 namespace kss {
@@ -224,16 +226,17 @@ void launch_pairb_final(hipStream_t st, bool plane, int npairs, const PairbArgs&
 // sources b * 256 + t + k * 256 * stream_blocks(ns), offset by the scan's base into the packed arrays -- the single-scan kernel's
 // assignment -- on vgicp_source<MOVE> and block_sum, so a scan's rows are the single call's.  The scan's pass entry (its step, the
 // rotation for its normals, e, the active flag) is one uniform load per workgroup; workgroups of scans that have ended leave at once.
-template <bool MOVE>
+// NEIGH: the map's 7- or 27-voxel neighbourhood (a.nb) through vgicp_source<MOVE, true>.
+template <bool MOVE, bool NEIGH = false>
 __global__ __launch_bounds__(P2L_THREADS) void vgicpb_rows_kernel(const VgicpbArgs a) {
     const int p = a.row_pair[blockIdx.x];
     const VgicpbPass pp = a.pass[p];
     if (pp.active == 0) return;
     const PairbDesc d = a.desc[p];
-    const VgicpMetric<MOVE> m(a, pp);
+    const VgicpMetric<MOVE, NEIGH> m(a, pp);
     const PairSrc s = {nullptr, nullptr, nullptr, nullptr, nullptr, a.sn, a.max_d2};
-    pair_walk<VgicpMetric<MOVE>, SRC_F3>(m, s, nullptr, nullptr, d.src_base, (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x,
-                                         d.ns, (int64_t)d.nrows * P2L_THREADS, 0, a.rows, nullptr);
+    pair_walk<VgicpMetric<MOVE, NEIGH>, SRC_F3>(m, s, nullptr, nullptr, d.src_base, (int64_t)((int)blockIdx.x - d.row_base) * P2L_THREADS + threadIdx.x,
+                                                d.ns, (int64_t)d.nrows * P2L_THREADS, 0, a.rows, nullptr);
 }
 
 // pairb_final_kernel<true> on the pass table's active flag
@@ -248,6 +251,12 @@ __global__ __launch_bounds__(P2L_THREADS) void vgicpb_final_kernel(const double*
 }
 
 void launch_vgicpb_rows(hipStream_t st, int total_rows, bool move, const VgicpbArgs& a) {
+    assert(a.nb == 1 || a.nb == 7 || a.nb == 27);   // (kss_vmap_set_neighbourhood admits nothing else)
+    if (a.nb == 7 || a.nb == 27) {
+        if (move) hipLaunchKernelGGL((vgicpb_rows_kernel<true, true>), dim3(total_rows), dim3(P2L_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((vgicpb_rows_kernel<false, true>), dim3(total_rows), dim3(P2L_THREADS), 0, st, a);
+        return;
+    }
     if (move) hipLaunchKernelGGL(vgicpb_rows_kernel<true>, dim3(total_rows), dim3(P2L_THREADS), 0, st, a);
     else hipLaunchKernelGGL(vgicpb_rows_kernel<false>, dim3(total_rows), dim3(P2L_THREADS), 0, st, a);
 }

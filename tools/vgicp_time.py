@@ -5,7 +5,8 @@ normals given: the map build time (median of `reps` builds, each destroyed again
 median of `reps` differences is printed), then iterations to convergence and |T - T_true| in PCL mode.  Two pairs: config_c2's
 size, 100k x 100k, and a 100k source against a 1M-point target -- the line that shows a pass's independence from the map's size.
 KSS_VGICP_UNFUSED=1 (read once per process) times the form whose move is a launch of its own.
-usage: python tools/vgicp_time.py [passes=50] [reps=5]"""
+A third argument sets the map's neighbourhood (1, 7 or 27); without it the map stays at 1 and nothing more is printed.
+usage: python tools/vgicp_time.py [passes=50] [reps=5] [neighbourhood=1]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,6 +15,7 @@ import torch
 pkg = g.load_package(); S = pkg.synth
 passes = int(sys.argv[1]) if len(sys.argv) > 1 else 50
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+nb = int(sys.argv[3]) if len(sys.argv) > 3 else None
 ctx = pkg.Context(0)
 print("move: %s" % ("a launch of its own (KSS_VGICP_UNFUSED)" if os.environ.get("KSS_VGICP_UNFUSED", "0") not in ("", "0") else "fused into the rows launch"))
 
@@ -38,6 +40,9 @@ for nt, ns, leaf in ((100000, 100000, 0.02), (1000000, 100000, 0.006)):
         build.append(t * 1e3)
         m.close()
     m = ctx.vmap_dev(dt.data_ptr(), nt, leaf, dtn.data_ptr())
+    if nb is not None:
+        m.set_neighbourhood(nb)
+        print("neighbourhood: %d" % m.neighbourhood, flush=True)
     info = m.info()
     lin, stats = m.read()
     b = sorted(build[1:])
